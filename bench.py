@@ -126,6 +126,9 @@ def parse_args():
     ap.add_argument("--no-f32-leg", action="store_true", help="(kept for old command lines) same as --legs none")
     ap.add_argument("--no-colours", action="store_true", help="do not carry the RGB of the points through the road chain")
     ap.add_argument("--detail", default=None, help="where the FULL record goes (default gpurun_out/bench_detail.json); stdout carries the compact line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the headline engine's timed path returned in its last timed step as DIR/<name>.npy "
+                         "(float32 / float64, at most 64 MB: per-pixel maps at a fixed seeded sample of pixels, clouds cut to their first points)")
     return ap.parse_args()
 
 
@@ -184,6 +187,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         sys.exit("--gpus must be >= 1")
+    if args.steps < 1:
+        sys.exit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
 
@@ -311,7 +316,8 @@ def main():
             d0 = float(eng.monodepth_forward(state["frames"]).median().item())
             target = cam.f * cam.b / prm.depth / cam.disp_mult                    # disparity (fraction of width) of a point at 10 m
             logit = lambda p: float(np.log(p / (1.0 - p)))
-            state["bias"] = logit(target / 0.3) - logit(min(max(d0, 1e-4), 0.2999) / 0.3)
+            # rounded to 1/64: the bias is an input of the run, and two builds whose medians differ in the last bits must get the same one
+            state["bias"] = round((logit(target / 0.3) - logit(min(max(d0, 1e-4), 0.2999) / 0.3)) * 64.0) / 64.0
             wm["dec/disp1/biases"] = (wm["dec/disp1/biases"] + np.float32(state["bias"])).astype(np.float32)
             if rank == 0:
                 log(f"disp1 bias {state['bias']:+.3f} (median disparity {d0:.4f} -> {target:.4f})")
@@ -407,6 +413,8 @@ def main():
             dts.append(float(tmax.item()))
             if not args.overlap:
                 read_buckets()
+        # what the last timed step returned (config 5: the sequence driver returns the gathered records only)
+        timed = {"out": out if args.config == 4 else None, "records": allrec}
         prof_dt = sum(dts)
         if args.overlap:
             # the roofline evidence: one more region of --steps steps on ONE stream with the library's per-launch HIP events, untimed
@@ -436,7 +444,7 @@ def main():
         dt_mean = sum(dts) / len(dts)
         res = {"label": label, "dts": dts, "dt_mean": dt_mean, "value": world * B * args.steps / dt_mean, "buckets": list(buckets.values()),
                "prof_dt": prof_dt, "prof_ms_per_step": prof_dt / args.steps * 1e3,
-               "stage_ms": stage_ms, "out": out}
+               "stage_ms": stage_ms, "out": out, "timed": timed}
         if rank == 0:
             log(f"[{label}] {res['value']:.1f} frames/s ({dt_mean / args.steps * 1e3:.2f} ms/step; regions " +
                 ", ".join(f"{d / args.steps * 1e3:.2f}" for d in dts) + f" ms/step); stage ms of the last step: resize {stage_ms[0]:.2f}  "
@@ -494,6 +502,8 @@ def main():
     if rank == 0:
         log(f"setup {time.time() - t_setup:.1f}s; arenas: " + ", ".join(f"{k} {v / 2**30:.2f} GiB" for k, v in eng.bytes.items()))
     head = measure(eng, args.precision)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, head["timed"], log)
     if rank != 0:
         if world > 1:
             dist.destroy_process_group()
@@ -710,6 +720,58 @@ def compact_line(d: dict) -> dict:
     out["legs"] = {k: compact_leg(v) for k, v in (d.get("legs") or {}).items()} or None
     out["detail"] = "gpurun_out/bench_detail.json (this run; copied per round to profiles/r0N_bench_detail.json): by_kernel lists, strict statistics, per-region times"
     return out
+
+
+DUMP_LIMIT = 64 << 20       # bytes of all the files --dump-outputs writes
+DUMP_PIXELS = 1 << 20       # per-pixel maps: this many pixels of the batch, at fixed seeded positions
+DUMP_POINTS = 4096          # clouds: the first this many points of every frame, in gather order (NaN past the frame's count)
+
+
+def dump_outputs(d, timed, log):
+    """--dump-outputs: the arrays the timed path returned in its last timed step, as DIR/<name>.npy in float32 / float64.  The bench's
+    inputs are seeded, so two builds can be compared file for file.  records_<field>: the gathered road-width records, whole;
+    road_mask / fence_mask / argmax / disp_pp: sampled at the flat indices in pixel_index; road_xyz / road_rgb / fence_xyz / fence_rgb
+    [frame, point, 3] with n_road / n_fence; f2f_<field> with --approach both."""
+    import numpy as np
+    import torch
+    from semantic_depth_amd.engine import F2F_DTYPE, RW_DTYPE, Engine
+    arrays = {}
+    rec = Engine.records(timed["records"])
+    for f in RW_DTYPE.names:
+        arrays[f"records_{f}"] = rec[f].astype(np.float64)
+    out = timed["out"]
+    if out is not None:
+        dense = {"road_mask": out["seg"]["road"], "fence_mask": out["seg"]["fence"], "argmax": out["seg"]["argmax"], "disp_pp": out["disp_pp"]}
+        n = dense["disp_pp"].numel()
+        idx = np.sort(np.random.default_rng(0).choice(n, size=min(DUMP_PIXELS, n), replace=False))
+        idx_t = torch.from_numpy(idx).to(dense["disp_pp"].device)
+        arrays["pixel_index"] = idx.astype(np.float64)
+        for k, t in dense.items():
+            arrays[k] = t.reshape(-1)[idx_t].float().cpu().numpy()
+        fz = out["fuse"]
+        for k in ("road", "fence"):
+            if fz.get(f"{k}_xyz") is None:
+                continue
+            cnt = fz[f"n_{k}"].cpu().numpy()
+            arrays[f"n_{k}"] = cnt.astype(np.float64)
+            keep = min(DUMP_POINTS, fz[f"{k}_xyz"].shape[1])
+            for part in ("xyz", "rgb"):
+                t = fz.get(f"{k}_{part}")
+                if t is None:
+                    continue
+                a = t[:, :keep].float().cpu().numpy()
+                a[np.arange(keep)[None, :] >= cnt[:, None]] = np.nan        # (past a frame's count the buffer holds no point)
+                arrays[f"{k}_{part}"] = a
+        if out.get("f2f") is not None:
+            f2 = Engine.f2f_records(out["f2f"])
+            for f in F2F_DTYPE.names:
+                arrays[f"f2f_{f}"] = f2[f].astype(np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, total
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+    log(f"bench.py: {len(arrays)} arrays ({total / 2**20:.1f} MB) of the last timed step -> {d}")
 
 
 def pmc_traffic(label: str, pattern: str):
