@@ -160,6 +160,18 @@ sd_status sd_monodepth_forward(sd_handle* h, const uint8_t* frames, int B, float
 sd_status sd_resize_cubic_u8(sd_handle* h, const uint8_t* src, int B, int src_h, int src_w, int channels, uint8_t* dst, int dst_h,
                              int dst_w, void* stream);
 
+/* Output stage of the sequence tool, semantic_depth_cityscapes_sequence.py:303-336 (overlay of :463-485): the per-frame result image
+ * for B frames in device memory, in one launch with no host synchronisation.  frames u8 [B,src_h,src_w,3] (the network-size BGR input),
+ * road_mask / fence_mask u8 [B,src_h,src_w] (sd_fcn8s_forward; non-zero = set), records [B] (sd_road_width) -> dst u8 [B,dst_h,dst_w,3]:
+ * PIL's Image.paste of road_color then fence_color (HOST pointers, 3 bytes each in the frame's channel order) with alpha on the masked
+ * pixels (t = d*(255-a) + c*a + 128, ((t >> 8) + t) >> 8), cv2.resize INTER_CUBIC of that overlay to (dst_w, dst_h) with exactly the
+ * integers of sd_resize_cubic_u8 (up-, down-scaling and equal sizes), then cv2.rectangle((0,0), (dst_w, int(0.25*dst_h)), (156,157,159), -1)
+ * on the frames whose record has found != 0.  The sequence tool pastes (128,64,128) and (190,153,153) with alpha 64; semantic_depth.py:565
+ * uses (160,10,10) for the fence.  dst_h, dst_w at most 16384. */
+sd_status sd_compose_result_frames(sd_handle* h, const uint8_t* frames, const uint8_t* road_mask, const uint8_t* fence_mask,
+                                   const sd_rw_result* records, int B, int src_h, int src_w, const uint8_t* road_color,
+                                   const uint8_t* fence_color, int alpha, uint8_t* dst, int dst_h, int dst_w, void* stream);
+
 /* HOST helper of the frame reader that replaces cv2.imread (semantic_depth.py:105; seq:123): reconstructs the scanlines of an
  * inflated 8-bit non-interlaced PNG (filter byte + width*channels bytes per row; channels 1 gray, 2 gray+alpha, 3 RGB, 4 RGBA)
  * and writes OpenCV's IMREAD_COLOR layout, u8 [height,width,3] BGR (alpha dropped, gray replicated).  Both pointers are HOST
@@ -185,6 +197,13 @@ sd_status sd_image_decode_bgr(const uint8_t* file_host, size_t len, uint8_t* bgr
  * PNG of that shape).  Returns SD_OK when every file decoded. */
 sd_status sd_decode_files_bgr(const char* const* paths, int n, int height, int width, uint8_t* out_host, size_t frame_stride, int threads,
                               int* status_out);
+/* HOST: the writer behind the sequence tool's cv2.imwrite('<dir>/<name>.png', frame) (seq:336): encodes n u8 [height,width,3] BGR frames at
+ * frames_host + i * frame_stride as 8-bit RGB PNGs (filter type 0 rows, one zlib stream at `level` 0..9) and writes them to paths[i], on
+ * `threads` native threads (<= 0: one per host CPU).  Pixel-exact, not byte-identical to OpenCV's file: sd_png_decode_bgr reads each
+ * file back as the input frame.  status_out (nullable, int[n]): per-file sd_status (SD_ERR_NOTFOUND: the file could not be written).
+ * Returns SD_OK when every file was written. */
+sd_status sd_png_encode_bgr_files(const char* const* paths, int n, int height, int width, const uint8_t* frames_host, size_t frame_stride,
+                                  int level, int threads, int* status_out);
 
 /* HOST helper of the PLY writer that replaces semantic_depth_lib/point_cloud_2_ply.py:70 (numpy.savetxt(fh, rows, "%f %f %f %d %d %d")):
  * n vertex rows "x y z r g b\n" -- coordinates as "%f" % float(v) prints them (fixed, six decimals, correctly rounded; nan / inf /

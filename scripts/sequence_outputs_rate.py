@@ -1,0 +1,104 @@
+"""frames/s of distributed.run_sequence_files on 1024 x 2048 PNG frames with the sequence tool's files off and on (one GPU).
+
+    python scripts/sequence_outputs_rate.py [--frames 128] [--batch 32] [--precision f16x2] [--level 1] [--threads 0]
+
+Setup as bench.py --config 5 (smooth random frames, seeded weights, the monodepth bias calibrated so that the median depth is the
+measuring depth); the frames are written once, untimed.  Each run is timed from the first decode to the last file written
+(SequenceOutputs.close).  Prints one JSON line: both rates, whether the records agree, the bytes written and the host threads of
+the writer and of the decoder.
+"""
+import argparse
+import json
+import os
+import shutil
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=128)
+    ap.add_argument("--batch", type=int, default=32)
+    ap.add_argument("--precision", default="f16x2")
+    ap.add_argument("--level", type=int, default=1)
+    ap.add_argument("--threads", type=int, default=0)
+    ap.add_argument("--keep", action="store_true", help="keep the written files (default: removed)")
+    args = ap.parse_args()
+
+    import torch
+
+    import __graft_entry__ as graft
+    graft.build()
+    from semantic_depth_amd import _lib as L
+    from semantic_depth_amd import outputs
+    from semantic_depth_amd import weights as Wt
+    from semantic_depth_amd.distributed import make_engine_step, run_sequence_files
+    from semantic_depth_amd.engine import RW_DTYPE, Camera, Engine, RoadWidthParams
+    from semantic_depth_amd.frame_io import default_decode_workers
+
+    H, W, B = 512, 1024, args.batch
+    cam = Camera(1048.64 / 2, 519.277 / 2, 1000.0, 1.0, 3800.0)
+    prm = RoadWidthParams()
+    rng = np.random.default_rng(1000)
+    base = rng.integers(0, 256, (B, 2 * H // 8, 2 * W // 8, 3), dtype=np.uint8)
+    frames = np.repeat(np.repeat(base, 8, axis=1), 8, axis=2)
+    frames = (frames.astype(np.int16) + rng.integers(-16, 17, frames.shape, dtype=np.int16)).clip(0, 255).astype(np.uint8)
+    work = tempfile.mkdtemp(prefix="sd_seq_rate_")
+    try:
+        src = os.path.join(work, "in")
+        os.makedirs(src)
+        paths = [os.path.join(src, f"frame_{i:06d}.png") for i in range(args.frames)]
+        outputs.write_png_batch(paths, frames[np.arange(args.frames) % B], level=1)
+
+        wf = Wt.make_fcn8s_weights(1, decoder_std=0.05)
+        wm = Wt.make_monodepth_weights("resnet50", 2)
+        eng = Engine(H, W, B, "resnet50", precision=args.precision, range_check=False)
+        eng.load_weights(L.SD_NET_FCN8S, wf)
+        eng.load_weights(L.SD_NET_MONODEPTH, wm)
+        fr = eng.resize_cubic(torch.from_numpy(frames).cuda())
+        d0 = float(eng.monodepth_forward(fr).median().item())
+        target = cam.f * cam.b / prm.depth / cam.disp_mult
+        logit = lambda p: float(np.log(p / (1.0 - p)))
+        bias = round((logit(target / 0.3) - logit(min(max(d0, 1e-4), 0.2999) / 0.3)) * 64.0) / 64.0
+        eng.load_weights(L.SD_NET_MONODEPTH, {"dec/disp1/biases": (wm["dec/disp1/biases"] + np.float32(bias)).astype(np.float32)})
+
+        threads = args.threads if args.threads > 0 else default_decode_workers()
+
+        def run(with_outputs, frame_paths, tag):
+            outs = None
+            if with_outputs:
+                outs = outputs.SequenceOutputs(os.path.join(work, tag), outputs.sequence_names(frame_paths), depth=prm.depth, level=args.level,
+                                               threads=threads)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            rec = run_sequence_files(frame_paths, make_engine_step(eng, lambda i: cam, prm, outputs=outs), batch=B, device="cuda")
+            torch.cuda.synchronize()
+            return time.perf_counter() - t0, rec
+
+        run(True, paths[:B], "warm_on")                  # (warm-up: tables, pinned staging, allocator)
+        run(False, paths[:B], "warm_off")
+        t_off, rec_off = run(False, paths, "off")
+        t_on, rec_on = run(True, paths, "on")
+        found = int(rec_on.cpu().numpy().view(RW_DTYPE)["found"].sum())
+        out_dir = os.path.join(work, "on")
+        nbytes = sum(os.path.getsize(os.path.join(dp, f)) for dp, _, fs in os.walk(out_dir) for f in fs)
+        print(json.dumps(dict(frames=args.frames, batch=B, precision=args.precision, png_level=args.level,
+                              fps_outputs_off=round(args.frames / t_off, 1), fps_outputs_on=round(args.frames / t_on, 1),
+                              records_identical=bool(torch.equal(rec_on.cpu(), rec_off.cpu())), found=found, bytes_written=nbytes,
+                              writer_threads=threads, decode_threads=default_decode_workers(), host_cpus=len(os.sched_getaffinity(0)))))
+        eng.close()
+    finally:
+        if args.keep:
+            print("files kept in", work)
+        else:
+            shutil.rmtree(work, ignore_errors=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -72,9 +72,12 @@ SIGNATURES = {
     "sd_jpeg_decode_bgr": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sd_image_decode_bgr": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sd_decode_files_bgr": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, C.POINTER(C.c_int)]),
+    "sd_png_encode_bgr_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, C.c_int,
+                                          C.POINTER(C.c_int)]),
     "sd_ply_format_rows": (C.c_int64, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int]),
     "sd_post_process": (C.c_int, [_H, _P, C.c_int, _P, _P]),
     "sd_resize_cubic_u8": (C.c_int, [_H, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "sd_compose_result_frames": (C.c_int, [_H, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "sd_fuse_backproject": (C.c_int, [_H, _P, _P, _P, _P, C.POINTER(sd_camera), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sd_postprocess_fuse_backproject": (C.c_int, [_H, _P, _P, _P, _P, _P, C.POINTER(sd_camera), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "sd_road_width": (C.c_int, [_H, _P, _P, _P, C.c_int, C.c_int, C.POINTER(sd_rw_params), _P, _P, _P, _P, _P]),

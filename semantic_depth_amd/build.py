@@ -32,6 +32,7 @@ SOURCES = [
     ("conv_stem.hip", []),
     ("ops_misc.hip", []),
     ("resize.hip", []),
+    ("compose.hip", []),
     ("fuse.hip", ["-ffp-contract=off"]),
     ("pcl.hip", ["-ffp-contract=off"]),
     ("plan.cpp", []),

@@ -31,9 +31,11 @@ struct sd_handle {
     char* wm = nullptr;   // monodepth weight arena
     char* ws = nullptr;   // workspace arena
     // workspace carve (byte offsets)
-    size_t o_fcn = 0, o_mono = 0, o_fuse = 0, o_fuse1 = 0, o_cams = 0, o_bufA = 0, o_bufB = 0, o_rgbA = 0, o_rgbB = 0, o_cnt = 0, o_plane = 0, o_o3d = 0, o_misc = 0, o_rsz = 0, o_cmp = 0;
+    size_t o_fcn = 0, o_mono = 0, o_fuse = 0, o_fuse1 = 0, o_cams = 0, o_bufA = 0, o_bufB = 0, o_rgbA = 0, o_rgbB = 0, o_cnt = 0, o_plane = 0, o_o3d = 0, o_misc = 0, o_rsz = 0, o_cmp = 0, o_rsz_cmp = 0;
     std::vector<int> rsz_host;      // tap tables of the last sd_resize_cubic_u8 geometry (kept alive for the async upload)
     int rsz_key[4] = {0, 0, 0, 0};
+    std::vector<int> cmp_rsz_host;  // the same for sd_compose_result_frames (own slot: the input resize and the output compose alternate
+    int cmp_rsz_key[4] = {0, 0, 0, 0};   //  every batch with different geometries, and a shared slot would re-upload and synchronise each time)
     size_t ws_bytes = 0;
     int last_fcn_images = 0, last_mono_images = 0;
     int reserve_cus = 0;            // sd_set_reserved_cus: CUs the persistent conv launches leave free
@@ -91,6 +93,7 @@ void carve_workspace(sd_handle* h) {
     h->o_misc = take(4096 + al(B * 7 * sizeof(int32_t)) + al(B * 12 * sizeof(double)));   // scalars | f2f counts | f2f planes
     h->o_cmp = take(cmp_scratch_bytes(h->max_batch));
     h->o_rsz = take((size_t)RSZ_MAX * 16 * sizeof(int));          // resize tap tables: [RSZ_MAX][4] x idx | x weight | y idx | y weight
+    h->o_rsz_cmp = take((size_t)RSZ_MAX * 16 * sizeof(int));      // the same layout for sd_compose_result_frames
     h->ws_bytes = off;
 }
 
@@ -617,6 +620,25 @@ static void resize_tables(int dst, int src, int* idx, int* wgt) {
     }
 }
 
+// the tap tables of one resize geometry in the workspace slot at `off` (uploaded when the geometry changed; the upload waits for the
+// stream first, because the previous tables may still be in use)
+static sd_status upload_resize_tables(sd_handle* h, size_t off, int* key_store, std::vector<int>& host, int src_h, int src_w, int dst_h,
+                                      int dst_w, hipStream_t s, int** xi, int** xa, int** yi, int** ya) {
+    int* dev = reinterpret_cast<int*>(h->ws + off);
+    *xi = dev; *xa = dev + 4 * (size_t)RSZ_MAX; *yi = dev + 8 * (size_t)RSZ_MAX; *ya = dev + 12 * (size_t)RSZ_MAX;
+    const int key[4] = {src_h, src_w, dst_h, dst_w};
+    if (std::memcmp(key, key_store, sizeof(key)) != 0) {
+        HIPCHK(h, hipStreamSynchronize(s));
+        host.assign((size_t)RSZ_MAX * 16, 0);
+        int* hx = host.data();
+        resize_tables(dst_w, src_w, hx, hx + 4 * (size_t)RSZ_MAX);
+        resize_tables(dst_h, src_h, hx + 8 * (size_t)RSZ_MAX, hx + 12 * (size_t)RSZ_MAX);
+        HIPCHK(h, hipMemcpy(dev, hx, host.size() * sizeof(int), hipMemcpyHostToDevice));
+        std::memcpy(key_store, key, sizeof(key));
+    }
+    return SD_OK;
+}
+
 sd_status sd_resize_cubic_u8(sd_handle* h, const uint8_t* src, int B, int src_h, int src_w, int channels, uint8_t* dst, int dst_h,
                              int dst_w, void* stream) {
     if (!h || !src || !dst || B <= 0 || src_h <= 0 || src_w <= 0 || channels <= 0 || channels > 4 || dst_h <= 0 || dst_w <= 0 ||
@@ -628,19 +650,33 @@ sd_status sd_resize_cubic_u8(sd_handle* h, const uint8_t* src, int B, int src_h,
         HIPCHK(h, hipMemcpyAsync(dst, src, (size_t)B * src_h * src_w * channels, hipMemcpyDeviceToDevice, s));
         return SD_OK;
     }
-    int* dev = reinterpret_cast<int*>(h->ws + h->o_rsz);
-    int *xi = dev, *xa = dev + 4 * (size_t)RSZ_MAX, *yi = dev + 8 * (size_t)RSZ_MAX, *ya = dev + 12 * (size_t)RSZ_MAX;
-    const int key[4] = {src_h, src_w, dst_h, dst_w};
-    if (std::memcmp(key, h->rsz_key, sizeof(key)) != 0) {
-        HIPCHK(h, hipStreamSynchronize(s));                        // the previous tables may still be in use
-        h->rsz_host.assign((size_t)RSZ_MAX * 16, 0);
-        int* hx = h->rsz_host.data();
-        resize_tables(dst_w, src_w, hx, hx + 4 * (size_t)RSZ_MAX);
-        resize_tables(dst_h, src_h, hx + 8 * (size_t)RSZ_MAX, hx + 12 * (size_t)RSZ_MAX);
-        HIPCHK(h, hipMemcpy(dev, hx, h->rsz_host.size() * sizeof(int), hipMemcpyHostToDevice));
-        std::memcpy(h->rsz_key, key, sizeof(key));
-    }
+    int *xi, *xa, *yi, *ya;
+    const sd_status st = upload_resize_tables(h, h->o_rsz, h->rsz_key, h->rsz_host, src_h, src_w, dst_h, dst_w, s, &xi, &xa, &yi, &ya);
+    if (st != SD_OK) return st;
     HIPCHK(h, launch_resize_cubic_u8(src, dst, B, src_h, src_w, dst_h, dst_w, channels, xi, xa, yi, ya, s));
+    return SD_OK;
+}
+
+sd_status sd_compose_result_frames(sd_handle* h, const uint8_t* frames, const uint8_t* road_mask, const uint8_t* fence_mask,
+                                   const sd_rw_result* records, int B, int src_h, int src_w, const uint8_t* road_color,
+                                   const uint8_t* fence_color, int alpha, uint8_t* dst, int dst_h, int dst_w, void* stream) {
+    if (!h || !frames || !road_mask || !fence_mask || !records || !dst || !road_color || !fence_color || B <= 0 || src_h <= 0 ||
+        src_w <= 0 || dst_h <= 0 || dst_w <= 0 || dst_h > RSZ_MAX || dst_w > RSZ_MAX || alpha < 0 || alpha > 255)
+        return fail(h, SD_ERR_INVALID, "sd_compose_result_frames: bad arguments (destination extent at most 16384, alpha 0..255)");
+    if (!h->bound) return fail(h, SD_ERR_STATE, "sd_bind_memory first");
+    hipStream_t s = (hipStream_t)stream;
+    int *xi, *xa, *yi, *ya;
+    const sd_status st = upload_resize_tables(h, h->o_rsz_cmp, h->cmp_rsz_key, h->cmp_rsz_host, src_h, src_w, dst_h, dst_w, s, &xi, &xa, &yi, &ya);
+    if (st != SD_OK) return st;
+    ComposeArgs a{};
+    a.xi = xi; a.xa = xa; a.yi = yi; a.ya = ya;
+    a.frames = frames; a.road = road_mask; a.fence = fence_mask; a.records = reinterpret_cast<const RwResultDev*>(records); a.dst = dst;
+    a.B = B; a.sh = src_h; a.sw = src_w; a.dh = dst_h; a.dw = dst_w; a.alpha = alpha;
+    a.banner_y1 = std::min((int)(0.25 * dst_h), dst_h - 1);       // cv2.rectangle((0,0), (w, int(0.25*h)), ..., -1): inclusive, clipped
+    a.aligned = (reinterpret_cast<uintptr_t>(dst) & 3) == 0;
+    const uint8_t banner[3] = {156, 157, 159};
+    for (int c = 0; c < 3; ++c) { a.road_c[c] = road_color[c]; a.fence_c[c] = fence_color[c]; a.banner[c] = banner[c]; }
+    HIPCHK(h, launch_compose_result_frames(a, s));
     return SD_OK;
 }
 

@@ -63,6 +63,7 @@ extern "C" sd_status sd_png_unfilter_bgr(const uint8_t* filtered, int height, in
 // ---------------------------------------------------------------------------------------------------------------------
 #include <zlib.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdio>
 #include <thread>
@@ -206,6 +207,104 @@ extern "C" sd_status sd_decode_files_bgr(const char* const* paths, int n, int he
     try {
         for (int t = 1; t < threads; ++t) pool.emplace_back(work);
     } catch (...) {                                             // (thread creation refused: the calling thread and the workers that exist do the batch)
+    }
+    work();
+    for (auto& th : pool) th.join();
+    return failed.load() ? SD_ERR_INVALID : SD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The writer of the sequence tool's result images (cv2.imwrite at seq:336): BGR -> RGB rows with filter type 0, one zlib
+// stream deflated in pieces of a few rows (no whole-frame raw copy), one IDAT per deflate output block, on native threads.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+void put_be32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
+
+bool write_chunk(FILE* fp, const char* tag, const uint8_t* data, uint32_t n) {
+    uint8_t hd[8];
+    put_be32(hd, n);
+    std::memcpy(hd + 4, tag, 4);
+    uLong crc = crc32(0L, reinterpret_cast<const Bytef*>(tag), 4);
+    if (n) crc = crc32(crc, data, n);
+    uint8_t tl[4];
+    put_be32(tl, (uint32_t)crc);
+    return std::fwrite(hd, 1, 8, fp) == 8 && (n == 0 || std::fwrite(data, 1, n, fp) == n) && std::fwrite(tl, 1, 4, fp) == 4;
+}
+
+sd_status png_encode_file(const char* path, const uint8_t* bgr, int h, int w, int level) {
+    FILE* fp = std::fopen(path, "wb");
+    if (!fp) return SD_ERR_NOTFOUND;
+    bool ok = std::fwrite(kPngSig, 1, 8, fp) == 8;
+    uint8_t ihdr[13];
+    put_be32(ihdr, (uint32_t)w);
+    put_be32(ihdr + 4, (uint32_t)h);
+    ihdr[8] = 8; ihdr[9] = 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;       // 8-bit RGB, deflate, filter method 0, no interlace
+    ok = ok && write_chunk(fp, "IHDR", ihdr, 13);
+    z_stream zs;
+    std::memset(&zs, 0, sizeof(zs));
+    if (ok && deflateInit(&zs, level) != Z_OK) ok = false;
+    const size_t row = 1 + (size_t)w * 3;
+    const int rows_per_piece = (int)std::max<size_t>(1, (size_t)(256 << 10) / row);
+    std::vector<uint8_t> raw, out(256 << 10);
+    if (ok) {
+        raw.resize(row * (size_t)std::min(rows_per_piece, h));
+        for (int y0 = 0; ok && y0 < h; y0 += rows_per_piece) {
+            const int ny = std::min(rows_per_piece, h - y0);
+            for (int y = 0; y < ny; ++y) {
+                uint8_t* r = raw.data() + (size_t)y * row;
+                const uint8_t* s = bgr + (size_t)(y0 + y) * w * 3;
+                r[0] = 0;
+                for (int x = 0; x < w; ++x) { r[1 + 3 * x] = s[3 * x + 2]; r[2 + 3 * x] = s[3 * x + 1]; r[3 + 3 * x] = s[3 * x]; }
+            }
+            zs.next_in = raw.data();
+            zs.avail_in = (uInt)(row * ny);
+            const int flush = y0 + ny >= h ? Z_FINISH : Z_NO_FLUSH;
+            int r;
+            do {
+                zs.next_out = out.data();
+                zs.avail_out = (uInt)out.size();
+                r = deflate(&zs, flush);
+                if (r == Z_STREAM_ERROR) { ok = false; break; }
+                const uint32_t got = (uint32_t)(out.size() - zs.avail_out);
+                if (got && !write_chunk(fp, "IDAT", out.data(), got)) { ok = false; break; }
+            } while (zs.avail_out == 0 || (flush == Z_FINISH && r != Z_STREAM_END));
+        }
+        deflateEnd(&zs);
+    }
+    ok = ok && write_chunk(fp, "IEND", nullptr, 0);
+    ok = (std::fclose(fp) == 0) && ok;
+    return ok ? SD_OK : SD_ERR_NOTFOUND;
+}
+
+}  // namespace
+
+extern "C" sd_status sd_png_encode_bgr_files(const char* const* paths, int n, int height, int width, const uint8_t* frames_host,
+                                             size_t frame_stride, int level, int threads, int* status_out) {
+    if (!paths || n < 0 || height <= 0 || width <= 0 || (n > 0 && !frames_host) || frame_stride < (size_t)height * width * 3 || level < 0 ||
+        level > 9)
+        return SD_ERR_INVALID;
+    if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
+    threads = threads < 1 ? 1 : (threads > n ? (n > 0 ? n : 1) : threads);
+    std::atomic<int> next(0), failed(0);
+    auto work = [&]() {
+        for (;;) {
+            const int i = next.fetch_add(1);
+            if (i >= n) break;
+            sd_status st = SD_ERR_NOTFOUND;
+            try {
+                if (paths[i]) st = png_encode_file(paths[i], frames_host + (size_t)i * frame_stride, height, width, level);
+            } catch (...) {
+                st = SD_ERR_INVALID;
+            }
+            if (status_out) status_out[i] = st;
+            if (st != SD_OK) failed.fetch_add(1);
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        for (int t = 1; t < threads; ++t) pool.emplace_back(work);
+    } catch (...) {
     }
     work();
     for (auto& th : pool) th.join();

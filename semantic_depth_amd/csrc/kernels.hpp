@@ -293,6 +293,18 @@ hipError_t launch_post_process(const float* disp_raw, float* disp_pp, int B, int
 // resize.hip: cv2.INTER_CUBIC for u8 frames; xi/xa (yi/ya): [dw][4] ([dh][4]) tap indices and fixed-point weights (device)
 hipError_t launch_resize_cubic_u8(const uint8_t* src, uint8_t* dst, int B, int sh, int sw, int dh, int dw, int C, const int* xi, const int* xa,
                                   const int* yi, const int* ya, hipStream_t s);
+// compose.hip: the sequence tool's result image -- PIL-paste overlay of the masks, cubic resize (the tables of resize.hip), banner on
+// frames whose record has found != 0; frames u8 [B,sh,sw,3], masks u8 [B,sh,sw], dst u8 [B,dh,dw,3] (device)
+struct RwResultDev;
+struct ComposeArgs {
+    const uint8_t* frames; const uint8_t* road; const uint8_t* fence; const RwResultDev* records;
+    uint8_t* dst;
+    const int* xi; const int* xa; const int* yi; const int* ya;
+    int B, sh, sw, dh, dw;
+    int alpha, banner_y1, aligned;
+    uint8_t road_c[3], fence_c[3], banner[3];
+};
+hipError_t launch_compose_result_frames(const ComposeArgs& a, hipStream_t s);
 struct FuseParams {
     const float* disp_pp;      // [B,H,W]
     const uint8_t* road; const uint8_t* fence; const uint8_t* frames;

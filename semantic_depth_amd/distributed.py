@@ -94,35 +94,57 @@ def run_sequence(load_frames, n_frames: int, step, batch: int = 32, group=None, 
     return out
 
 
-def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", workers: int = 0) -> torch.Tensor:
+def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", workers: int = 0, outputs=None) -> torch.Tensor:
     """run_sequence on FILES (semantic_depth_cityscapes_sequence.py:689-701 reads ``sorted(glob(input_folder))`` frame by frame): rank r
     decodes ONLY its shard of the sorted list -- frame_io.FrameFeeder: one native call per batch into pinned staging, upload one batch
     ahead, ``workers`` decode threads (default: this rank's share of the node's CPUs, frame_io.default_decode_workers) -- and hands every
-    batch to ``step(frames_on_device, first_global_index)``; one all_gather of the records at the end."""
+    batch to ``step(frames_on_device, first_global_index)``; one all_gather of the records at the end.
+    ``outputs`` (default: ``step.outputs``, set by ``make_engine_step(..., outputs=)``): an outputs.SequenceOutputs the step feeds; this
+    rank writes the files of its shard only, and the manifest last -- 'ok', or 'range_error' / 'error' when the run raised (the files
+    written before are then not valid outputs; the exception still propagates)."""
     from .frame_io import FrameFeeder
     paths = sorted(paths)
     n_frames = len(paths)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
     rank = dist.get_rank(group) if dist.is_initialized() else 0
     lo, hi = shard_range(n_frames, rank, world)
-    parts = []
-    if hi > lo:
-        with FrameFeeder(paths[lo:hi], batch, device=device, workers=workers) as feeder:
-            for frames, first in feeder:
-                rec = step(frames, lo + first)
-                assert rec.dtype == torch.uint8 and tuple(rec.shape) == (frames.shape[0], RECORD_BYTES), (rec.dtype, rec.shape)
-                parts.append(rec)
-    local = torch.cat(parts, 0) if parts else torch.zeros((0, RECORD_BYTES), dtype=torch.uint8, device=device)
-    out = gather_records(local, n_frames, group)
-    if getattr(step, "finish", None) is not None:
-        step.finish()
+    outputs = outputs if outputs is not None else getattr(step, "outputs", None)
+    if outputs is not None:
+        if len(outputs.names) != n_frames:
+            raise ValueError(f"SequenceOutputs has {len(outputs.names)} names for {n_frames} frames")
+        outputs.begin(rank, world, lo, hi)
+    try:
+        parts = []
+        if hi > lo:
+            with FrameFeeder(paths[lo:hi], batch, device=device, workers=workers) as feeder:
+                for frames, first in feeder:
+                    rec = step(frames, lo + first)
+                    assert rec.dtype == torch.uint8 and tuple(rec.shape) == (frames.shape[0], RECORD_BYTES), (rec.dtype, rec.shape)
+                    parts.append(rec)
+        local = torch.cat(parts, 0) if parts else torch.zeros((0, RECORD_BYTES), dtype=torch.uint8, device=device)
+        out = gather_records(local, n_frames, group)
+        if getattr(step, "finish", None) is not None:
+            step.finish()
+    except BaseException as e:
+        if outputs is not None:
+            from .engine import RangeError
+            try:
+                outputs.close("range_error" if isinstance(e, RangeError) else "error")
+            except Exception:
+                pass                      # (the run's own exception is the one reported)
+        raise
+    if outputs is not None:
+        outputs.close("ok")
     return out
 
 
-def make_engine_step(engine, camera_of, params=None, approach: str = "rw"):
+def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outputs=None):
     """``step`` for run_sequence on a real Engine: host or device u8 frames of any size -> (cubic resize to the network shape on
     the GPU, semantic_depth_cityscapes_sequence.py:123-130) -> Engine.process_batch -> record buffer.
-    ``camera_of(global_frame_index) -> engine.Camera`` (the sequence tool: cx = 1048.64/4·s, cy = 519.277/4·s, disp_mult = 3800)."""
+    ``camera_of(global_frame_index) -> engine.Camera`` (the sequence tool: cx = 1048.64/4·s, cy = 519.277/4·s, disp_mult = 3800).
+    ``outputs`` (outputs.SequenceOutputs, None = records only): also the sequence tool's files -- process_batch keeps the final road clouds
+    when PLYs are asked for, Engine.compose_result_frames makes the result images at the original frame size on the device, and the
+    batch goes to ``outputs.submit`` (copies on a side stream, written on host threads); the records are the same either way."""
     from .engine import RoadWidthParams
 
     prm = params or RoadWidthParams()
@@ -130,10 +152,21 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw"):
     def step(frames, lo):
         fr = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames))
         fr = fr.to(engine.device, non_blocking=True)
-        if tuple(fr.shape[1:3]) != (engine.H, engine.W):
+        size = tuple(fr.shape[1:3])
+        if size != (engine.H, engine.W):
             fr = engine.resize_cubic(fr)
         cams = [camera_of(lo + i) for i in range(fr.shape[0])]
-        return engine.process_batch(fr, cams, prm, approach=approach)["records"]
+        if outputs is None:
+            return engine.process_batch(fr, cams, prm, approach=approach)["records"]
+        out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.ply)
+        rec = out["records"]
+        images = None
+        if outputs.images:
+            images = engine.compose_result_frames(fr, out["seg"]["road"], out["seg"]["fence"], rec, size[0], size[1], outputs.road_color,
+                                                  outputs.fence_color, outputs.alpha)
+        outputs.submit(lo, rec, size, images=images, final=out.get("road_final"))
+        return rec
 
     step.finish = getattr(engine, "check_range", None)
+    step.outputs = outputs
     return step

@@ -236,6 +236,26 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_resize_cubic_u8")
         return out
 
+    def compose_result_frames(self, frames: torch.Tensor, road: torch.Tensor, fence: torch.Tensor, records: torch.Tensor, out_h: int, out_w: int,
+                              road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, out: torch.Tensor | None = None) -> torch.Tensor:
+        """the sequence tool's result image (semantic_depth_cityscapes_sequence.py:303-336) for B device frames in one launch
+        (sd_compose_result_frames): PIL paste of the road, then the fence colour on the network-size u8 [B,h,w,3] ``frames`` where the
+        u8 [B,h,w] masks are set, INTER_CUBIC resize to (out_h, out_w), the 25 % grey banner on frames whose record (u8 [B,104] device
+        buffer of road_width) has found != 0.  Colours are in the frames' channel order; semantic_depth.py:565 pastes (160,10,10) on fences."""
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous() and frames.dim() == 4 and frames.shape[3] == 3
+        B, sh, sw = frames.shape[:3]
+        for m in (road, fence):
+            assert m.dtype == torch.uint8 and m.is_cuda and m.is_contiguous() and tuple(m.shape) == (B, sh, sw), m.shape
+        assert records.dtype == torch.uint8 and records.is_cuda and records.is_contiguous() and tuple(records.shape) == (B, RW_DTYPE.itemsize)
+        if out is None:
+            out = torch.empty((B, out_h, out_w, 3), dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, out_h, out_w, 3), out.shape
+        rc, fc = (C.c_uint8 * 3)(*road_color), (C.c_uint8 * 3)(*fence_color)
+        st = self.lib.sd_compose_result_frames(self.h, _ptr(frames), _ptr(road), _ptr(fence), _ptr(records), B, sh, sw, rc, fc, int(alpha),
+                                               _ptr(out), out_h, out_w, self._stream())
+        L.check(self.lib, self.h, st, "sd_compose_result_frames")
+        return out
+
     def post_process(self, disp_raw: torch.Tensor):
         B = disp_raw.shape[0]
         assert disp_raw.dtype == torch.float32 and tuple(disp_raw.shape[1:]) == (2, self.H, self.W) and disp_raw.is_contiguous()

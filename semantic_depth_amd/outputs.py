@@ -7,6 +7,8 @@
     road_plane_grid / fence_plane_grids <- the ``plane3D`` arrays of :215-219, :294-309 rebuilt through the reference's own pcl call sequence
     focal_sweep                     <- semantic_depth.py:854-944  (``results/<f>/data.txt``, ``best_focal_lengths.txt``)
     write_png                       <- cv2.imwrite(...png) at :406 (zlib-deflated 8-bit RGB; pixel-identical, not byte-identical)
+    SequenceOutputs                 <- the files of the sequence tool, semantic_depth_cityscapes_sequence.py:303-361 (``result_sequence_imgs/<name>.png``,
+                                       ``result_sequence_ply/<name>_rw.ply``), written from the batched driver (distributed.run_sequence_files)
 
 The text files are byte-identical to what the reference's own statements write (tests/test_outputs.py holds fixtures produced
 by executing those statements, extracted from the reference by ``tests/golden/make_golden.py``).  Glyph rendering of
@@ -324,3 +326,235 @@ def focal_sweep(process, input_frames: dict, frame_depther, focal_lengths=(380, 
         fh.write("Best f fence2fence:  {}\n".format(best["f2f"][1]))
         fh.write("Best f overall:      {}\n".format(best["overall"][1]))
     return dict(best_f_rw=best["rw"][1], best_f_f2f=best["f2f"][1], best_f_overall=best["overall"][1], per_f=per_f)
+
+
+# ------------------------------------------------------------------------------------------------ the sequence tool's files
+SEQ_IMG_DIR, SEQ_PLY_DIR = "result_sequence_imgs", "result_sequence_ply"          # semantic_depth_cityscapes_sequence.py:671-680
+
+
+def sequence_names(paths) -> list:
+    """``output_name`` of every frame in the order the sequence tool visits them (seq:689-699): basename without extension of
+    ``sorted(paths)``"""
+    return [os.path.splitext(os.path.basename(p))[0] for p in sorted(paths)]
+
+
+def write_png_batch(paths, frames_bgr, level: int = 1, threads: int = 0) -> list:
+    """cv2.imwrite(paths[i], frames_bgr[i]) for u8 [n,h,w,3] BGR frames: 8-bit RGB PNGs at zlib ``level``, encoded and written by ONE native
+    call on ``threads`` C++ threads (sd_png_encode_bgr_files; 0 = one per CPU), no interpreter lock held.  Pixel-exact (sd_png_decode_bgr /
+    any PNG reader gives the frames back), not byte-identical to OpenCV's files.  Returns the paths."""
+    import ctypes as C
+
+    from . import _lib as L
+    a = np.ascontiguousarray(frames_bgr, dtype=np.uint8)
+    if a.ndim != 4 or a.shape[3] != 3 or a.shape[0] != len(paths):
+        raise ValueError(f"frames must be u8 [n,h,w,3] with n = len(paths), got {a.shape} for {len(paths)} paths")
+    n, h, w = a.shape[:3]
+    if n == 0:
+        return []
+    arr = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
+    status = (C.c_int * n)()
+    st = L.load().sd_png_encode_bgr_files(arr, n, h, w, a.ctypes.data_as(C.c_void_p), h * w * 3, int(level), int(threads), status)
+    if st != L.SD_OK:
+        bad = [(paths[i], status[i]) for i in range(n) if status[i] != L.SD_OK]
+        raise OSError(f"write_png_batch: {len(bad) or n} image(s) could not be written (status {st}): {bad[:3]}")
+    return list(paths)
+
+
+def rw_ply_bytes(road3D, road_colors, left_pt_rw=None, right_pt_rw=None) -> bytes:
+    """the bytes of ``<name>_rw.ply`` (seq:357-361): PointCloud2Ply(road3D, road_colors, ...) plus, when the line was found (both end
+    points given, [1,3] each), create_3Dline_from_3Dpoints(left, right, [250,0,0]), after prepare_and_save_point_cloud's minimum-z filter.
+    An empty road cloud (the reference's np.min raises there) gives a file with no vertex."""
+    from .point_cloud_2_ply import format_rows
+    pts, col = np.asarray(road3D).reshape(-1, 3), np.asarray(road_colors).reshape(-1, 3)
+    if left_pt_rw is not None and right_pt_rw is not None:
+        line, colors_line = pcl.create_3Dline_from_3Dpoints(np.array(left_pt_rw, np.float64), np.array(right_pt_rw, np.float64), [250, 0, 0])
+        pts, col = np.append(pts, line, axis=0), np.append(col, colors_line, axis=0)
+    if len(pts):
+        keep = pts[:, 2] > pts[:, 2].min()
+        pts, col = pts[keep], col[keep]
+    return PointCloud2Ply.ply_header.format(vertex_count=len(pts)).encode() + format_rows(pts, col, threads=1)
+
+
+class SequenceOutputs:
+    """what the sequence tool writes for every frame (seq:303-361), fed batch by batch by the step of ``make_engine_step(..., outputs=)``:
+
+        <directory>/result_sequence_imgs/<name>.png           the overlay at the original frame size, 25 % banner when the line was found
+                                                              (``images``; Engine.compose_result_frames on the GPU, sd_png_encode_bgr_files)
+        <directory>/result_sequence_imgs/<name>_overlay.json  the banner and the cv2.putText items of overlay_items_sequence (``items``;
+                                                              glyphs are not rasterised, module docstring)
+        <directory>/result_sequence_ply/<name>_rw.ply         the denoised road cloud + the red road-width line (``ply``; rw_ply_bytes)
+        <directory>/manifest_rank<r>.json                     written last by close(): the files of this rank and 'ok' / 'range_error' / 'error'
+
+    ``names``: output names of the WHOLE sorted frame list (sequence_names), indexed by global frame index.  submit() takes the device
+    tensors of one batch, copies them into pinned staging on a side stream behind an event of the current stream, and writes them on
+    worker threads -- at most two batches in flight -- with the per-pixel and per-point work in native code (no interpreter lock).
+    ``threads``: native encoder threads per batch and PLY writer threads (0: frame_io.default_decode_workers())."""
+
+    def __init__(self, directory: str, names, depth: float = 10.0, images: bool = True, ply: bool = True, items: bool = True, level: int = 1,
+                 threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64):
+        from concurrent.futures import ThreadPoolExecutor
+
+        from .frame_io import default_decode_workers
+        if not 0 <= level <= 9:
+            raise ValueError("PNG compression level must be 0..9")
+        self.directory, self.names, self.depth = directory, list(names), float(depth)
+        self.images, self.ply, self.items, self.level = bool(images), bool(ply), bool(items), int(level)
+        self.road_color, self.fence_color, self.alpha = tuple(road_color), tuple(fence_color), int(alpha)
+        self.threads = threads if threads > 0 else default_decode_workers()
+        self.img_dir, self.ply_dir = os.path.join(directory, SEQ_IMG_DIR), os.path.join(directory, SEQ_PLY_DIR)
+        for d, on in ((self.img_dir, self.images or self.items), (self.ply_dir, self.ply)):
+            if on:
+                os.makedirs(d, exist_ok=True)
+        self.rank, self.world, self.shard = 0, 1, (0, len(self.names))
+        self._batches = ThreadPoolExecutor(max_workers=2)           # one per batch in flight
+        self._writers = ThreadPoolExecutor(max_workers=self.threads)  # PLY / JSON files of a batch
+        self._jobs, self._k, self._files = [], 0, []
+        self._staging = [dict(), dict()]                             # pinned host buffers per in-flight slot
+        self._streams = None
+        self.manifest = None
+
+    # ---------------------------------------------------------------- driver interface
+    def begin(self, rank: int, world: int, lo: int, hi: int):
+        """the shard [lo, hi) this rank writes (run_sequence_files calls it before the first batch)"""
+        self.rank, self.world, self.shard = int(rank), int(world), (int(lo), int(hi))
+
+    def submit(self, lo: int, records, size: tuple, images=None, final=None):
+        """one batch: ``records`` u8 [n,104] (sd_rw_result), ``size`` = (h, w) of the original frames, ``images`` u8 [n,h,w,3] (the composed
+        result images) or None, ``final`` = dict(xyz f32 [n,cap,3], rgb u8 [n,cap,3], n i32 [n]) (process_batch(want_final=True)'s
+        road_final) or None.  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
+        tensors of every step)."""
+        import torch
+        if self.manifest is not None:
+            raise RuntimeError("SequenceOutputs.submit after close")
+        n = int(records.shape[0])
+        if lo < 0 or lo + n > len(self.names):
+            raise ValueError(f"frames {lo}..{lo + n - 1} are beyond the {len(self.names)} names")
+        if self.images and images is None or self.ply and final is None:
+            raise ValueError("SequenceOutputs: this batch lacks the images / final road clouds the outputs ask for")
+        while len(self._jobs) >= 2:                                    # at most two batches in flight
+            self._files.extend(self._jobs.pop(0).result())
+        slot = self._k & 1
+        self._k += 1
+        ev = None
+        if records.is_cuda:
+            if self._streams is None:
+                self._streams = [torch.cuda.Stream(records.device), torch.cuda.Stream(records.device)]
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(records.device))
+        self._jobs.append(self._batches.submit(self._write_batch, slot, lo, records, tuple(size), images, final, ev))
+
+    def close(self, status: str = "ok") -> str:
+        """wait for every batch, then write this rank's manifest LAST: the files written and ``status`` ('ok'; 'range_error' / 'error':
+        the run failed and the files listed are not valid outputs).  Returns the manifest path."""
+        if self.manifest is not None:
+            return self.manifest
+        err = None
+        for f in self._jobs:
+            try:
+                self._files.extend(f.result())
+            except Exception as e:                                    # (a failed write is reported after the manifest says so)
+                err = err or e
+        self._jobs = []
+        self._batches.shutdown()
+        self._writers.shutdown()
+        if err is not None and status == "ok":
+            status = "error"
+        self.manifest = os.path.join(self.directory, "manifest_rank{}.json".format(self.rank))
+        files = sorted(os.path.relpath(p, self.directory) for p in self._files)
+        with open(self.manifest, "w") as f:
+            json.dump(dict(rank=self.rank, world=self.world, frames=list(self.shard), status=status, valid=status == "ok", files=files), f, indent=1)
+        if err is not None:
+            raise err
+        return self.manifest
+
+    # ---------------------------------------------------------------- worker side
+    def _pinned(self, slot: int, key: str, shape, dtype, pin: bool):
+        import torch
+        buf = self._staging[slot].get(key)
+        numel = int(np.prod(shape))
+        if buf is None or buf.numel() < numel or buf.dtype != dtype:
+            buf = self._staging[slot][key] = torch.empty(max(numel, 1), dtype=dtype, pin_memory=pin)
+        return buf[:numel].view(*shape)
+
+    def _to_host(self, slot, lo, records, images, final, ev):
+        """numpy views of the batch (device tensors: copied into pinned staging on this slot's side stream behind ``ev``)"""
+        import torch
+        if ev is None:
+            rec = records.numpy() if isinstance(records, torch.Tensor) else np.asarray(records)
+            img = None if images is None else (images.numpy() if isinstance(images, torch.Tensor) else np.asarray(images))
+            clouds = None
+            if final is not None:
+                cnt = np.asarray(final["n"].cpu() if isinstance(final["n"], torch.Tensor) else final["n"])
+                xyz, rgb = (np.asarray(final[k].cpu() if isinstance(final[k], torch.Tensor) else final[k]) for k in ("xyz", "rgb"))
+                clouds = [(xyz[i, :cnt[i]], rgb[i, :cnt[i]]) for i in range(len(cnt))]
+            return rec, img, clouds
+        s = self._streams[slot]
+        with torch.cuda.stream(s):
+            s.wait_event(ev)
+            rec = self._pinned(slot, "rec", tuple(records.shape), torch.uint8, True)
+            rec.copy_(records, non_blocking=True)
+            img = None
+            if images is not None:
+                img = self._pinned(slot, "img", tuple(images.shape), torch.uint8, True)
+                img.copy_(images, non_blocking=True)
+            cnt = None
+            if final is not None:
+                cnt = self._pinned(slot, "n", tuple(final["n"].shape), torch.int32, True)
+                cnt.copy_(final["n"], non_blocking=True)
+            s.synchronize()
+            clouds = None
+            if final is not None:
+                cn = cnt.numpy().astype(np.int64)
+                off = np.concatenate([[0], np.cumsum(cn)])
+                xyz = self._pinned(slot, "xyz", (int(off[-1]), 3), torch.float32, True)
+                rgb = self._pinned(slot, "rgb", (int(off[-1]), 3), torch.uint8, True)
+                for i in range(len(cn)):
+                    if cn[i]:
+                        xyz[off[i]:off[i + 1]].copy_(final["xyz"][i, :cn[i]], non_blocking=True)
+                        rgb[off[i]:off[i + 1]].copy_(final["rgb"][i, :cn[i]], non_blocking=True)
+                s.synchronize()
+                xn, rn = xyz.numpy(), rgb.numpy()
+                clouds = [(xn[off[i]:off[i + 1]], rn[off[i]:off[i + 1]]) for i in range(len(cn))]
+        return rec.numpy(), None if img is None else img.numpy(), clouds
+
+    def _write_batch(self, slot, lo, records, size, images, final, ev):
+        from .engine import RW_DTYPE
+        rec_u8, img, clouds = self._to_host(slot, lo, records, images, final, ev)
+        recs = np.ascontiguousarray(rec_u8).view(RW_DTYPE).reshape(-1)
+        n = len(recs)
+        names = self.names[lo:lo + n]
+        h, w = size
+        files, futs = [], []
+
+        def ends(r):
+            if not r["found"]:
+                return None, None
+            return r["left_pt"].astype(np.float64)[None, :], r["right_pt"].astype(np.float64)[None, :]
+
+        def write_ply(i):
+            path = os.path.join(self.ply_dir, "{}_rw.ply".format(names[i]))
+            left, right = ends(recs[i])
+            xyz, rgb = clouds[i]
+            with open(path, "wb") as f:
+                f.write(rw_ply_bytes(xyz.astype(np.float64), rgb, left, right))
+            return path
+
+        def write_items(i):
+            r = recs[i]
+            left, right = ends(r)
+            banner, items = overlay_items_sequence(w, h, self.depth, bool(r["found"]), left, right, float(r["width"]) if r["found"] else None)
+            path = os.path.join(self.img_dir, "{}_overlay.json".format(names[i]))
+            with open(path, "w") as f:
+                json.dump(dict(banner=banner, items=items), f)
+            return path
+
+        for i in range(n):
+            if self.ply:
+                futs.append(self._writers.submit(write_ply, i))
+            if self.items:
+                futs.append(self._writers.submit(write_items, i))
+        if self.images:
+            assert img.shape == (n, h, w, 3), (img.shape, (n, h, w))
+            files.extend(write_png_batch([os.path.join(self.img_dir, "{}.png".format(nm)) for nm in names], img, self.level, self.threads))
+        files.extend(f.result() for f in futs)
+        return files
