@@ -573,9 +573,7 @@ __global__ __launch_bounds__(512, (N16 && MT == 1) ? 2 : 1) void conv_direct_ker
                 if (p.out_f16) epilogue(tag, IntTag<1>{}); else epilogue(tag, IntTag<0>{});
             }
         };
-        // SEMDEPTH_X3_DIAG=2 on the H2 form (decomposition runs, scripts/decompose_x3.py f16x2; 0 in production): no epilogue at all
-        if (H2 && !N16 && (SD_DIAG_BITS(p.sw) & 2)) { if (acc[0][0][0] == 12345.678f) p.out[0] = acc[MT - 1][NB - 1][3]; }
-        else if (p.act == ACT_RELU) ep(ActTag<ACT_RELU>{});
+        if (p.act == ACT_RELU) ep(ActTag<ACT_RELU>{});
         else if (p.act == ACT_ELU) ep(ActTag<ACT_ELU>{});
         else if (N16 && p.act == ACT_SIGMOID03) ep(ActTag<ACT_SIGMOID03>{});
         else ep(ActTag<ACT_NONE>{});
@@ -602,9 +600,8 @@ hipError_t launch_conv_direct(const ConvDirectParams& p, hipStream_t s) {
     // N16 layers (full-resolution decoder tail: two chunks of little arithmetic per tile) are bound by the DMA latency of
     // a two-stage ring: 8-row tiles, 64 KiB of LDS, TWO workgroups per CU cover each other's waits
     // every source behind a x2 upsample: source-resolution halo tiles (48 KiB of LDS for N16 with 16-row tiles: they stay)
-    const bool up = p.all_up && !(p.H & 1) && !(p.W & 1) && !(p.sw & SW_NO_UPTILE);
-    const bool mt1 = n16 && !up && !(p.sw & SW_NO_N16_MT1);
-    const int th = mt1 ? 8 : 16;
+    const bool up = p.all_up && !(p.H & 1) && !(p.W & 1);
+    const int th = n16 && !up ? 8 : 16;
     const int tiles = (p.W / D_TW) * ((p.H + th - 1) / th) * p.N * p.nsplit;
     // persistent grid: as many workgroups as the instantiation keeps resident (1-3 per CU, by LDS and registers)
 #define SD_DIRECT_(NB_, MT_, F16_, N16_, UP_, W1_, X2_, ...) \
@@ -613,38 +610,37 @@ hipError_t launch_conv_direct(const ConvDirectParams& p, hipStream_t s) {
          const int slots = (cus - p.reserve_cus > 0 ? cus - p.reserve_cus : 1) * per_cu; \
          const dim3 grid((unsigned)(tiles < slots ? tiles : slots)); \
          hipLaunchKernelGGL((conv_direct_kernel<NB_, MT_, F16_, N16_, UP_, W1_, X2_, ##__VA_ARGS__>), grid, dim3(512), 0, s, q); } while (0)
-#define SD_DIRECT_H2(NB_, MT_, N16_) do { if (up) SD_DIRECT_(NB_, MT_, true, N16_, true, false, true, true); else SD_DIRECT_(NB_, MT_, true, N16_, false, false, true, true); } while (0)
+#define SD_DIRECT_H2(NB_) do { if (up) SD_DIRECT_(NB_, 2, true, false, true, false, true, true); else SD_DIRECT_(NB_, 2, true, false, false, false, true, true); } while (0)
+// N16: 8-row tiles without an upsample, 16-row up-tiles behind one
+#define SD_DIRECT_N16(F16_, W1_, ...) do { if (up) SD_DIRECT_(1, 2, F16_, true, true, W1_, ##__VA_ARGS__); else SD_DIRECT_(1, 1, F16_, true, false, W1_, ##__VA_ARGS__); } while (0)
     if (p.fold) {               // upsample-folded upconv layers of SD_PREC_F16X2: source-resolution tiles, 16 tap matrices per chunk
         if (p.f16 != 4 || p.out_f16 != 3 || !up || p.pool || n16) return hipErrorInvalidValue;
         if (nb == 1) SD_DIRECT_(1, 2, true, false, true, false, true, true, true); else SD_DIRECT_(2, 2, true, false, true, false, true, true, true);
         return hipGetLastError();
     }
-#define SD_DIRECT(NB_, MT_, F16_, N16_, W1_) do { if (up) SD_DIRECT_(NB_, MT_, F16_, N16_, true, W1_, false); else SD_DIRECT_(NB_, MT_, F16_, N16_, false, W1_, false); } while (0)
+#define SD_DIRECT(NB_, F16_, W1_) do { if (up) SD_DIRECT_(NB_, 2, F16_, false, true, W1_, false); else SD_DIRECT_(NB_, 2, F16_, false, false, W1_, false); } while (0)
     if (p.f16 == 4) {           // SD_PREC_F16X2: fp16 hi + scaled lo x fp16 hi + lo weights, three products (every tile shape of the bf16 form)
         if (p.out_f16 != 3) return hipErrorInvalidValue;
-        if (mt1) SD_DIRECT_H2(1, 1, true);
-        else if (n16) SD_DIRECT_H2(1, 2, true);
-        else if (nb == 1) SD_DIRECT_H2(1, 2, false);
-        else SD_DIRECT_H2(2, 2, false);
+        if (n16) SD_DIRECT_N16(true, false, true, true);
+        else if (nb == 1) SD_DIRECT_H2(1);
+        else SD_DIRECT_H2(2);
     } else if (p.f16 == 3) {           // fp16 hi + lo input x w_hi: the 64-channel-pass form only (the planner asks for nothing else)
-        if (mt1 || n16 || nb == 1 || up) return hipErrorInvalidValue;
+        if (n16 || nb == 1 || up) return hipErrorInvalidValue;
         SD_DIRECT_(2, 2, true, false, false, false, true);
     } else if (p.f16 == 2) {           // fp16, ONE product
-        if (mt1) SD_DIRECT(1, 1, true, true, true);
-        else if (n16) SD_DIRECT(1, 2, true, true, true);
-        else if (nb == 1) SD_DIRECT(1, 2, true, false, true);
-        else SD_DIRECT(2, 2, true, false, true);
+        if (n16) SD_DIRECT_N16(true, true, false);
+        else if (nb == 1) SD_DIRECT(1, true, true);
+        else SD_DIRECT(2, true, true);
     } else if (p.f16) {
-        if (mt1) SD_DIRECT(1, 1, true, true, false);
-        else if (n16) SD_DIRECT(1, 2, true, true, false);
-        else if (nb == 1) SD_DIRECT(1, 2, true, false, false);
-        else SD_DIRECT(2, 2, true, false, false);
+        if (n16) SD_DIRECT_N16(true, false, false);
+        else if (nb == 1) SD_DIRECT(1, true, false);
+        else SD_DIRECT(2, true, false);
     } else {
-        if (mt1) SD_DIRECT(1, 1, false, true, false);
-        else if (n16) SD_DIRECT(1, 2, false, true, false);
-        else if (nb == 1) SD_DIRECT(1, 2, false, false, false);
-        else SD_DIRECT(2, 2, false, false, false);
+        if (n16) SD_DIRECT_N16(false, false, false);
+        else if (nb == 1) SD_DIRECT(1, false, false);
+        else SD_DIRECT(2, false, false);
     }
+#undef SD_DIRECT_N16
 #undef SD_DIRECT_H2
 #undef SD_DIRECT_
 #undef SD_DIRECT

@@ -58,14 +58,8 @@ constexpr int T3_TW = 32, T3_HW = T3_TW + 2, T3_WAVES = 8, T3_TH = 16, T3_HH = T
 // source with the 3x3 taps that read the same source pixel added up (plan.hpp OpDesc::fold): 16 tap matrices per chunk instead of 9, but
 // 4 instead of 9 MFMAs per output pixel.  Wave w owns parity w & 3 and the source rows 4 (w >> 2) .. + 3 of the tile: its two 32-pixel MFMA
 // column groups are 2 source rows x 16 source columns each.
-// TIMED (SEMDEPTH_X3_DIAG=4; <2, false, 2, 2> only, decomposition runs): s_memtime stamps around every phase's wait + barrier, the barrier in front of the
-// epilogue and the epilogue itself, summed per wave over the items of a workgroup; waves 0 and 4 of the middle workgroup print their sums.
-template <int NB, bool UP, int KEEP, int WSLOTS, bool FOLD = false, bool TIMED = false>
+template <int NB, bool UP, int KEEP, int WSLOTS, bool FOLD = false>
 __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectParams p) {
-    int tm_loop = 0, tm_wb = 0, tm_wb0 = 0, tm_bar = 0, tm_ep = 0, tm_start = 0, tm_pro = 0, tm_epv = 0, tm_epw = 0, tm_eps = 0;      // (low 32 bits of s_memtime)
-    auto now = []() { return (int)__builtin_amdgcn_s_memtime(); };
-    int tm_items = 0;
-    if constexpr (TIMED) tm_start = now();
     static_assert(!FOLD || (UP && WSLOTS == 2 && KEEP == 2), "the folded form: upconv layers, two-slot ring, kept X fragments");
     constexpr int NTAP = FOLD ? 16 : 9;                        // tap matrices per chunk
     constexpr int S_HH = UP ? T3_HH / 2 + 1 : T3_HH, S_HW = UP ? T3_HW / 2 + 1 : T3_HW;      // stored tile
@@ -96,8 +90,6 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) void*)lds;      // LDS byte address
     const int frow = lane & 31, fk = lane >> 5;
     const int fpar = wave & 3, fpy = fpar >> 1, fpx = fpar & 1, fhh = wave >> 2;     // FOLD: this wave's parity and half of the tile's source rows
-    // SEMDEPTH_X3_DIAG (decomposition runs, latched in the handle's switches): 1 no output stores, 2 no MFMAs; 0 in production
-    const int diag = SD_DIAG_BITS(p.sw);
 
     // work item = (tile, pass of <= 64 output channels); the passes of a tile are neighbouring items
     const int items = total * p.nsplit;
@@ -245,11 +237,8 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
         advance();
     }
     int g = 0, q = 0;                    // chunks / phases consumed so far
-    if constexpr (TIMED) tm_pro = now() - tm_start;
     for (; tid < items; tid += gridDim.x) {
         const int half = cur.half;
-        int tm_i0 = 0;
-        if constexpr (TIMED) { tm_i0 = now(); ++tm_items; }
         f32x16 acc[T3_MT][NB];
 #pragma unroll
         for (int a = 0; a < T3_MT; ++a)
@@ -279,9 +268,8 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
             // weight fragment's ds_read + s_waitcnt directly in front of its 2 NPX MFMAs, and in the lo / mid phases the two waves of a
             // SIMD do not have enough MFMAs per group to cover an LDS round trip): the weight fragment of group g + 2 and the X rows of the
             // plane this phase reads for the first time (row dy + 2 / the first two rows of the next dx) are issued before group g's MFMAs.
-            auto phase = [&](auto ph_tag, auto nomfma_tag, auto&& issue) {
+            auto phase = [&](auto ph_tag, auto&& issue) {
                 constexpr int PH = decltype(ph_tag)::value, NPX = PH + 1, G = 9 * NB;
-                constexpr bool NOMFMA = decltype(nomfma_tag)::value != 0;
                 constexpr bool NEWKEPT = PH < KEEP;              // the plane first read in this phase stays in xk
                 const u32x4* const Wq = lds + 2 * XBUF + (q % WSLOTS) * WUNITS;
                 auto wfrag = [&](int grp) {
@@ -313,16 +301,14 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
                         else if (dx < 2) { xnew(dx + 1, 0); xnew(dx + 1, 1); }
                     }
                     __builtin_amdgcn_sched_barrier(0);
-                    if constexpr (!NOMFMA) {
-                        const u32x4 wv = wq[grp % 3];
+                    const u32x4 wv = wq[grp % 3];
 #pragma unroll
-                        for (int pl = NPX - 1; pl >= 0; --pl)          // the smaller planes first
+                    for (int pl = NPX - 1; pl >= 0; --pl)          // the smaller planes first
 #pragma unroll
-                            for (int a = 0; a < T3_MT; ++a) {
-                                const u32x4 xv = pl < KEEP ? xk[pl < KEEP ? pl : 0][dx][a + dy] : (pl == PH ? xn[a + dy] : xo[pl >= KEEP && pl < PH ? pl - KEEP : 0][a + dy]);
-                                acc[a][nb] = mfma_frag<false>(wv, xv, acc[a][nb]);
-                            }
-                    }
+                        for (int a = 0; a < T3_MT; ++a) {
+                            const u32x4 xv = pl < KEEP ? xk[pl < KEEP ? pl : 0][dx][a + dy] : (pl == PH ? xn[a + dy] : xo[pl >= KEEP && pl < PH ? pl - KEEP : 0][a + dy]);
+                            acc[a][nb] = mfma_frag<false>(wv, xv, acc[a][nb]);
+                        }
                     __builtin_amdgcn_sched_barrier(0);
                     issue(grp);
                     __builtin_amdgcn_sched_barrier(0);
@@ -366,9 +352,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
-            // (SEMDEPTH_X3_DIAG & 2 selects the copy of a phase without MFMAs; production runs the branch-free one)
-#define SD_PHASE(PH_, ...) do { if constexpr (FOLD) phase_fold(IntTag<PH_>{}, __VA_ARGS__); \
-                                else if (diag & 2) phase(IntTag<PH_>{}, IntTag<1>{}, __VA_ARGS__); else phase(IntTag<PH_>{}, IntTag<0>{}, __VA_ARGS__); } while (0)
+#define SD_PHASE(PH_, ...) do { if constexpr (FOLD) phase_fold(IntTag<PH_>{}, __VA_ARGS__); else phase(IntTag<PH_>{}, __VA_ARGS__); } while (0)
             if constexpr (WSLOTS == 3) {
                 // ---- three-slot pipeline: phase q issues the weight plane of phase q + 2 and the X plane first read in phase q + 2
                 // lo(c): W_hi(c) + X_lo(c)
@@ -404,20 +388,15 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
                 if (more) { kc = kn; }
             } else {
             // ---- phase lo: W_lo x X_hi (36 MFMAs per wave at NB = 2); brings W_mid of this chunk
-            int tm_a = 0;
-            if constexpr (TIMED) tm_a = now();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            if constexpr (TIMED) { const int d = now() - tm_a; tm_wb += d; if (c == 0) tm_wb0 += d; }
             SD_PHASE(0, [&](int grp) {
                 if (grp < WS) wslot(wcur, 1, grp, (q + 1) & 1);
             });
             ++q;
             // ---- phase mid: W_mid x (X_mid, X_hi) (72); brings W_hi of this chunk and X_hi of the cursor chunk
-            if constexpr (TIMED) tm_a = now();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            if constexpr (TIMED) tm_wb += now() - tm_a;
             if (more) kn = begin_chunk(d3load_chunk(p.chunks + ic), icur, ic, (g + 1) & 1);
             SD_PHASE(1, [&](int grp) {
                 if (grp < WS) wslot(wcur, 0, grp, (q + 1) & 1);
@@ -425,10 +404,8 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
             });
             ++q;
             // ---- phase hi: W_hi x (X_lo, X_mid, X_hi) (108); brings W_lo and X_mid, X_lo of the cursor chunk
-            if constexpr (TIMED) tm_a = now();
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
-            if constexpr (TIMED) tm_wb += now() - tm_a;
             SD_PHASE(2, [&](int grp) {
                 if (!more) return;
                 if (grp < WS) wslot(kn.w, 2, grp, (q + 1) & 1);
@@ -441,10 +418,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
 
         // ---- epilogue: bias + activation, the exact three-way split, LDS transpose one plane at a time in the X buffer just consumed
         //      (the other one is being filled for the next item), 16-byte runs of 8 channels per pixel and plane ----
-        int tm_e0 = 0, tm_e1 = 0;
-        if constexpr (TIMED) tm_e0 = now();
         __builtin_amdgcn_s_barrier();
-        if constexpr (TIMED) { tm_e1 = now(); tm_loop += tm_e0 - tm_i0; tm_bar += tm_e1 - tm_e0; }
         auto epilogue = [&](auto tag) {
             constexpr int ACT = decltype(tag)::value;
             constexpr int SEGS = 4 * NB, PPP = 64 / SEGS;        // 16-byte segments per pixel, pixels per store pass
@@ -490,7 +464,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
 #pragma unroll
                     for (int ps = 0; ps < (16 + PPP - 1) / PPP; ++ps) {
                         const int pix = ps * PPP + prow;
-                        if (pix < 16 && yp < Hp && seg * 8 < p.Cout && !(diag & 1)) {
+                        if (pix < 16 && yp < Hp && seg * 8 < p.Cout) {
                             uint16_t* o = out_hi + ((size_t)(cur.img * Hp + yp) * Wp + (cur.tx0 >> 1) + pix) * p.Cstride + n0 + seg * 8;
                             *reinterpret_cast<u32x4*>(o + pl * p.out_plane) = *reinterpret_cast<const u32x4*>(sh + pix * ROW + seg * 16);
                         }
@@ -504,8 +478,6 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
             for (int a = 0; a < T3_MT; ++a) {
                 const int y = cur.ty0 + T3_MT * wave + a;
                 uint2 pp[3][4 * NB];
-                int tm_x = 0;
-                if constexpr (TIMED) tm_x = now();
 #pragma unroll
                 for (int r4 = 0; r4 < 4 * NB; ++r4) {
                     if (8 * r4 >= p.Cout) continue;         // rows past Cout are padding, never stored
@@ -516,7 +488,6 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
                     for (int r = 0; r < 4; ++r) v[r] = act_x3<ACT>(v[r]);
                     split4_x3(v, pp[0][r4], pp[1][r4], pp[2][r4]);
                 }
-                if constexpr (TIMED) { __builtin_amdgcn_sched_barrier(0); const int n = now(); tm_epv += n - tm_x; tm_x = n; }
 #pragma unroll
                 for (int pl0 = 0; pl0 < 3; pl0 += EPL) {
 #pragma unroll
@@ -528,14 +499,13 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
                         }
                     __builtin_amdgcn_wave_barrier();
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    if constexpr (TIMED) { const int n = now(); tm_epw += n - tm_x; tm_x = n; }
 #pragma unroll
                     for (int ps = 0; ps < 32 / PPP; ++ps) {
                         const int pix = ps * PPP + prow;
                         // FOLD: pixel pix of column group a = source (row 4 hh + 2 a + (pix >> 4), column pix & 15) of this wave's parity
                         const int yo = FOLD ? cur.ty0 + 2 * (4 * fhh + 2 * a + (pix >> 4)) + fpy : y;
                         const int xo = FOLD ? cur.tx0 + 2 * (pix & 15) + fpx : cur.tx0 + pix;
-                        if (yo < p.H && seg * 8 < p.Cout && !(diag & 1)) {
+                        if (yo < p.H && seg * 8 < p.Cout) {
                             uint16_t* o = out_hi + ((size_t)(cur.img * p.H + yo) * p.W + xo) * p.Cstride + n0 + seg * 8;
 #pragma unroll
                             for (int e = 0; e < EPL; ++e)
@@ -544,14 +514,12 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
                     }
                     __builtin_amdgcn_wave_barrier();
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                    if constexpr (TIMED) { const int n = now(); tm_eps += n - tm_x; tm_x = n; }
                 }
             }
         };
         if (p.act == ACT_RELU) epilogue(ActTag<ACT_RELU>{});
         else if (p.act == ACT_ELU) epilogue(ActTag<ACT_ELU>{});
         else epilogue(ActTag<ACT_NONE>{});
-        if constexpr (TIMED) tm_ep += now() - tm_e1;
         if constexpr (WSLOTS == 3) {
             // gfx9 counts stores in vmcnt too and loads / stores may complete out of order with respect to each other: a COUNTED wait is
             // only sound over the DMA loads alone.  Drain the epilogue's stores (and the DMAs of the last phase with them) once per tile.
@@ -561,14 +529,6 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
         if (tid + (int)gridDim.x < items) cur = tile_of(tid + gridDim.x);
     }
 #undef SD_PHASE
-    if constexpr (TIMED) {
-        const int total = now() - tm_start;
-        if ((int)blockIdx.x == (int)gridDim.x / 2 && lane == 0 && (wave == 0 || wave == 4))
-            printf("[conv_direct3 timed] H=%d W=%d Cout=%d chunks=%d items=%d wave %d: prologue %d | per item: loop %.0f (wait+barrier of its %d phases %.0f, of the first one %.0f) "
-                   "barrier before the epilogue %.0f epilogue %.0f (bias + act + split %.0f, LDS writes + wait %.0f, LDS reads + stores + wait %.0f) | total %d ticks\n",
-                   p.H, p.W, p.Cout * p.nsplit, p.nchunks, tm_items, wave, tm_pro, (double)tm_loop / tm_items, 3 * p.nchunks, (double)tm_wb / tm_items, (double)tm_wb0 / tm_items,
-                   (double)tm_bar / tm_items, (double)tm_ep / tm_items, (double)tm_epv / tm_items, (double)tm_epw / tm_items, (double)tm_eps / tm_items, total);
-    }
 }
 
 hipError_t launch_conv_direct3(const ConvDirectParams& p, hipStream_t s) {
@@ -582,7 +542,7 @@ hipError_t launch_conv_direct3(const ConvDirectParams& p, hipStream_t s) {
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
         cus = prop.multiProcessorCount;
     }
-    const bool up = p.all_up && !(p.H & 1) && !(p.W & 1) && !(p.sw & SW_NO_UPTILE);
+    const bool up = p.all_up && !(p.H & 1) && !(p.W & 1);
     const int tiles = (p.W / T3_TW) * ((p.H + T3_TH - 1) / T3_TH) * p.N * p.nsplit;
     const int wgs = cus - p.reserve_cus > 0 ? cus - p.reserve_cus : 1;
     const dim3 grid((unsigned)(tiles < wgs ? tiles : wgs));        // persistent: one workgroup per CU (158 KB of LDS)
@@ -592,31 +552,12 @@ hipError_t launch_conv_direct3(const ConvDirectParams& p, hipStream_t s) {
         else hipLaunchKernelGGL((conv_direct3_kernel<2, true, 2, 2, true>), grid, dim3(512), 0, s, p);
         return hipGetLastError();
     }
-    // Production: X fragments of the hi / mid planes kept in registers (KEEP = 2), two-slot weight ring.  The variants measured and not
-    // adopted -- KEEP = 0 (re-read fragments: -1 %, profiles/r03d_conv_direct3_keep_ab.txt), the three-slot ring of the NB = 1 layers (equal
-    // or 3-6 % slower, profiles/r03g_conv_direct3_ring3_ab.txt) -- are compiled only with -DSD_DEV_VARIANTS (SEMDEPTH_X3_KEEP=0,
-    // SEMDEPTH_X3_RING3 then select them); the default build carries six instantiations of this kernel instead of sixteen.
-    const ConvDirectParams& pd = p;
-#ifdef SD_DEV_VARIANTS
-    if ((p.sw & SW_X3_DIAG_TIMED) && p.Cout > 32 && !up) {          // SEMDEPTH_X3_DIAG=4: the timed copy of the dominant form
-        hipLaunchKernelGGL((conv_direct3_kernel<2, false, 2, 2, false, true>), grid, dim3(512), 0, s, pd);
-        return hipGetLastError();
-    }
-    const int keep = (p.sw & SW_X3_NOKEEP) ? 0 : 2;
-    const bool ring3 = (p.sw & SW_X3_RING3) != 0;
-#define SD_D3(NB_, UP_, WS_) do { if (keep >= 2) hipLaunchKernelGGL((conv_direct3_kernel<NB_, UP_, 2, WS_>), grid, dim3(512), 0, s, pd); \
-                                  else hipLaunchKernelGGL((conv_direct3_kernel<NB_, UP_, 0, WS_>), grid, dim3(512), 0, s, pd); } while (0)
-    if (p.Cout <= 32) {
-        if (ring3) { if (up) SD_D3(1, true, 3); else SD_D3(1, false, 3); }
-        else { if (up) SD_D3(1, true, 2); else SD_D3(1, false, 2); }
-    } else {
-        if (up) SD_D3(2, true, 2); else SD_D3(2, false, 2);
-    }
-#else
-#define SD_D3(NB_, UP_, WS_) hipLaunchKernelGGL((conv_direct3_kernel<NB_, UP_, 2, WS_>), grid, dim3(512), 0, s, pd)
-    if (p.Cout <= 32) { if (up) SD_D3(1, true, 2); else SD_D3(1, false, 2); }
-    else { if (up) SD_D3(2, true, 2); else SD_D3(2, false, 2); }
-#endif
+    // X fragments of the hi / mid planes kept in registers (KEEP = 2), two-slot weight ring.  Measured and not adopted: KEEP = 0 (re-read
+    // fragments: -1 %, profiles/r03d_conv_direct3_keep_ab.txt) and the three-slot ring of the NB = 1 layers (equal or 3-6 % slower,
+    // profiles/r03g_conv_direct3_ring3_ab.txt); the kernel template keeps both forms, nothing launches them.
+#define SD_D3(NB_, UP_) hipLaunchKernelGGL((conv_direct3_kernel<NB_, UP_, 2, 2>), grid, dim3(512), 0, s, p)
+    if (p.Cout <= 32) { if (up) SD_D3(1, true); else SD_D3(1, false); }
+    else { if (up) SD_D3(2, true); else SD_D3(2, false); }
 #undef SD_D3
     return hipGetLastError();
 }

@@ -30,13 +30,11 @@ int conv_dma_variant(const ConvParams& p) {
     if (p.Cout % 256 == 0 && ((M + 127) / 128) * (p.Cout / 256) >= thr) return 1;     // 128 x 256
     if (p.Cout % 128 == 0 && ((M + 255) / 256) * (p.Cout / 128) >= thr) return 2;     // 256 x 128
     if (p.Cout % 64 == 0 && p.Cout % 128 != 0 && ((M + 255) / 256) * (p.Cout / 64) >= thr) return 3;      // 256 x 64
-    if (p.Cout == 32 && !p.pool && !p.out_planar16 && (M + 255) / 256 >= thr && !(p.sw & SW_NO_DMA32)) return 4;      // 256 x 32 (monodepth-vgg conv1b)
+    if (p.Cout == 32 && !p.pool && !p.out_planar16 && (M + 255) / 256 >= thr) return 4;      // 256 x 32 (monodepth-vgg conv1b)
     return 0;
 }
 
-hipError_t launch_conv_dma(const ConvParams& p0, hipStream_t s) {
-    ConvParams p = p0;
-    p.dbg = (p.sw & SW_DMA_DBG16) ? 16 : 0;
+hipError_t launch_conv_dma(const ConvParams& p, hipStream_t s) {
     const long M = (long)p.N * p.Hout * p.Wout;
     const int v = conv_dma_variant(p);
     if (v == 1) launch_dma_v1(p, M, s);

@@ -71,8 +71,6 @@ constexpr int G3_ROW = G3_NT * 64 + 16;
 // q + 3, which is now one and a half k-tiles ahead: the lo phase of k-tile kt issues (X_lo, W_hi) of kt + 1, the hi phase (X_hi, W_lo) of kt + 2.
 // 64 KB per k-tile against 48 MFMAs per wave: the L2 -> LDS path bounds it at 0.75 of the MFMA rate.  The accumulator times ConvParams::alpha,
 // HS output planes.
-// TIMED (SEMDEPTH_X3_DIAG=3; MODE 1 only, decomposition runs): s_memtime stamps around the counted wait, the barrier and the body of every phase, summed
-// per wave; waves 0 and 4 of the middle workgroup print their sums (the instrumentation itself costs ~10 % of the wave cycles: read the SPLIT, not the total)
 // S16 (round 5; the bf16 x 3 engine's production form): the same ring and the same LDS traffic, multiplied by v_mfma_f32_16x16x32 instead of 32x32x16 -- a k-tile is ONE
 // k-step of 32, a wave's 128 x 64 tile 8 x 4 blocks of 16 x 16, the products grouped by X plane with the weight fragments kept.  In isolation the 16x16x32 form
 // sustains 15-17 % more products per second on plane data under the power cap (half the accumulator traffic per MAC; profiles/r05_probe_mfma_shapes.txt); in this
@@ -80,10 +78,8 @@ constexpr int G3_ROW = G3_NT * 64 + 16;
 // 32-clock MFMAs): -3 % on the layers of this kernel, +1 % end to end (profiles/r05_mfma16_ab.txt, r05_conv_dma3_hooks.txt).  Its sums differ in the last bits from the
 // 32x32x16 form's (SEMDEPTH_MFMA32), as this block's always did from conv_dma.hip's: which of the two blocks a layer takes is decided per ENGINE, not per call
 // (conv_dma3_eligible).  The three-product (HS) form takes it for its 1x1 layers (-1.9 %) and stays on 32x32x16 for fc6 (2 % slower there).
-template <int MODE, bool HS = false, bool TIMED = false, bool S16 = false>
+template <int MODE, bool HS = false, bool S16 = false>
 __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, int M, int tilesM, int tilesN) {
-    long long tm_wait = 0, tm_bar = 0, tm_body = 0, tm_t0 = 0, tm_pro = 0;
-    if constexpr (TIMED) tm_t0 = __builtin_amdgcn_s_memtime();
     constexpr int NPL = HS ? 2 : 3;                          // planes per operand
     static_assert(G3_NW * NPL * 32 * G3_ROW <= G3_LDS * 16, "epilogue slabs fit in the ring");
     __shared__ __attribute__((aligned(16))) u32x4 lds[G3_LDS];
@@ -294,7 +290,6 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
 #pragma unroll
     for (int a = 0; a < G3_MT; ++a) { if constexpr (S16) xa[a] = xfrag16(0, 0, a); else xk[0][0][a] = xfrag(0, 0, a); }
     int q = 0;
-    if constexpr (TIMED) tm_pro = __builtin_amdgcn_s_memtime() - tm_t0;
     KCur k1 = knext(KCur{t0, 0});                             // the k-tile whose pairs are being issued (the one after the k-tile being multiplied)
     KCtx c3 = make_ctx(k1.idx, g3load_kentry(ktab + k1.idx)); // (at least two k-tiles) its gather entry and address context
     // HS: the hi phase issues the lo pair of the k-tile after that one
@@ -304,18 +299,14 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
     for (int kt = 0; kt < ktiles; ++kt) {
         auto phase = [&](auto ph_tag) {
             constexpr int PH = decltype(ph_tag)::value, NPX = PH + 1;
-            long long ts0 = 0, ts1 = 0, ts2 = 0;
-            if constexpr (TIMED) ts0 = __builtin_amdgcn_s_memtime();
             // pairs q and q + 1 have landed once at most the previous phase's DMAs are outstanding (pair q + 1 feeds the tail's prefetch)
             if (prev1 == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if constexpr (TIMED) ts1 = __builtin_amdgcn_s_memtime();
             __builtin_amdgcn_s_barrier();
-            if constexpr (TIMED) ts2 = __builtin_amdgcn_s_memtime();
             // the pair of phase q + 3 goes into the slot phase q - 1 has just finished reading -- its four DMA instructions are spread
             // BEHIND the first four MFMA groups of this phase (at the top of the phase, with the MFMA pipe drained by the barrier, each
             // of them would cost its full issue latency)
-            const bool doissue = q + 3 < nphase && !(TIMED && (p.sw & SW_X3_DIAG_TIMED));      // = 3 (kt + 1) + ph  (SEMDEPTH_X3_DIAG=7: timed copy without DMA pieces)
+            const bool doissue = q + 3 < nphase;      // = 3 (kt + 1) + ph
             auto piece = [&](int n) {
                 if (!doissue) return;
                 if constexpr (HS) {          // phase q + 3: from the lo phase the hi pair of the next k-tile, from the hi phase the lo pair of the one after it
@@ -415,7 +406,6 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
                 }
             }
             ++q;
-            if constexpr (TIMED) { const long long ts3 = __builtin_amdgcn_s_memtime(); tm_wait += ts1 - ts0; tm_bar += ts2 - ts1; tm_body += ts3 - ts2; }
         };
         // S16: the phases on 16x16x32 MFMAs, grouped BY X PLANE: a wave's tile is 128 pixels x 64 channels, so the weight fragments are the smaller set to keep
         // in registers (2 planes x 4 blocks = 32 VGPRs; the 32x32x16 form keeps 64 VGPRs of X fragments) -- with 32 accumulator tuples the kept-X form spills.
@@ -431,14 +421,10 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
             // the six-product hi phase holds the most registers (accumulators + three weight planes + both X halves = 208) while its DMA pieces need their address
             // temporaries: the second half's X fragments are read behind the LAST piece there (five groups before their first use) instead of the first
             constexpr bool LATE_XB = KP == 3;
-            long long ts0 = 0, ts1 = 0, ts2 = 0;
-            if constexpr (TIMED) ts0 = __builtin_amdgcn_s_memtime();
             if (prev1 == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if constexpr (TIMED) ts1 = __builtin_amdgcn_s_memtime();
             __builtin_amdgcn_s_barrier();
-            if constexpr (TIMED) ts2 = __builtin_amdgcn_s_memtime();
-            const bool doissue = q + 3 < nphase && !(TIMED && (p.sw & SW_X3_DIAG_TIMED));      // (SEMDEPTH_X3_DIAG=7: the timed copy WITHOUT its DMA pieces -- what do the hooks cost?)
+            const bool doissue = q + 3 < nphase;
             auto piece = [&](int n) {
                 if (!doissue) return;
                 if constexpr (HS) {
@@ -519,7 +505,6 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
                 }
             }
             ++q;
-            if constexpr (TIMED) { const long long ts3 = __builtin_amdgcn_s_memtime(); tm_wait += ts1 - ts0; tm_bar += ts2 - ts1; tm_body += ts3 - ts2; }
         };
         if constexpr (S16) {
             phase16(IntTag<0>{});
@@ -543,13 +528,6 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
     // ---- epilogue: bias + activation in f32, exact three-way split, LDS transpose (one slab per plane and wave), 16-byte runs ----
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    // SEMDEPTH_X3_DIAG (decomposition runs, latched in the handle's switches; 0 in production): 1 = no output stores, 2 = no epilogue at all
-    const int diag = TIMED ? 0 : SD_DIAG_BITS(p.sw);
-    if (diag & 2) {
-        if constexpr (S16) { if (acc16[0][0][0] == 12345.678f) p.out[0] = acc16[7][3][3]; }
-        else { if (acc[0][0][0] == 12345.678f) p.out[0] = acc[1][1][3]; }
-        return;
-    }
     // (the epilogue's per-lane values are formed from an opaque copy of the lane id: nothing of it is hoisted above the k-loop, whose registers are all taken)
     int lane_e = lane;
     asm volatile("" : "+v"(lane_e));
@@ -603,7 +581,7 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
             for (int ps = 0; ps < 32 / PPP; ++ps) {
                 const int pix = ps * PPP + prow;
                 const int mo = m0 + a * 32 + pix;
-                if (mo < M && !(diag & 1)) {
+                if (mo < M) {
                     size_t opix = (size_t)mo;
                     if (p.rowgrp) {              // (image group, row, image of the group, column) -> (image, row, column)
                         const int q1 = mo / p.Wout, q2 = q1 / p.rowgrp, g = q2 / p.Hout;
@@ -623,18 +601,9 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
     };
-    long long tm_e0 = 0;
-    if constexpr (TIMED) tm_e0 = __builtin_amdgcn_s_memtime();
     if (p.act == ACT_RELU) ep3(ActTag<ACT_RELU>{});
     else if (p.act == ACT_ELU) ep3(ActTag<ACT_ELU>{});
     else ep3(ActTag<ACT_NONE>{});
-    if constexpr (TIMED) {
-        const long long te = __builtin_amdgcn_s_memtime();
-        if ((int)blockIdx.x == (int)gridDim.x / 2 && lane == 0 && (wave == 0 || wave == 4))
-            printf("[conv_dma3 timed] %s K=%d ktiles=%d wave %d: prologue %lld | per phase (%d phases): wait %.1f barrier %.1f body %.1f | loop %lld epilogue %lld total %lld ticks\n",
-                   HS ? "HS" : "x3", p.Kpad, ktiles, wave, tm_pro, nphase, (double)tm_wait / nphase, (double)tm_bar / nphase, (double)tm_body / nphase,
-                   tm_wait + tm_bar + tm_body, te - tm_e0, te - tm_t0);
-    }
 }
 
 int conv_dma3_mode(const ConvParams& p);
@@ -644,9 +613,8 @@ bool conv_dma3_eligible(const ConvParams& p) {
     // SD_PREC_F16X2: measured against the two-stage block of conv_dma.hip (profiles/r05_hs_phased_gemm_ab.txt), the two-phase ring wins on the 1x1 layers (fc7
     // 1.50 -> 1.29 ms, the res2 / res5 block tails 3-12 %) and -- since a piece's address arithmetic is formed once per k-tile -- on the row-grouped fc6
     // (6.93 -> 6.50 ms: it also skips the taps on padding rows), and loses on the small strided 3x3 of res4_6 (0.135 -> 0.178): the 1x1 layers and fc6 only
-    // (SEMDEPTH_HS_PHASED_TAPS: every tap layer, the A/B switch of that measurement)
     // (the rule must not look at the call: the k x k stride-1 single-source layers -- fc6 --, row-grouped or not)
-    if (p.f16 == 4 && conv_dma3_mode(p) != 1 && !(p.kh >= 3 && p.stride == 1 && !p.fold && p.noup) && !(p.sw & SW_HS_TAPS)) return false;
+    if (p.f16 == 4 && conv_dma3_mode(p) != 1 && !(p.kh >= 3 && p.stride == 1 && !p.fold && p.noup)) return false;
     if (p.fold) return true;                                   // (a folded layer always runs here when it can: its results must not depend on the batch)
     if (p.sw & SW_NO_DMA3) return false;                       // (A/B switch of the handle)
     // enough tiles to occupy the chip -- counted on a FULL pass of the engine (ConvParams::Nmax), not on the frames of this call: this block and conv_dma.hip's
@@ -670,19 +638,13 @@ hipError_t launch_conv_dma3(const ConvParams& p, hipStream_t s) {
     // the 16x16x32 form: every bf16 x 3 layer and the three-product engine's 1x1 layers (-1.9 % on them; its fc6 is 2 % faster on 32x32x16: r05_mfma16_ab.txt).
     // SEMDEPTH_MFMA32: the 32x32x16 form everywhere (same-box A/B)
     const bool s16 = !(p.sw & SW_MFMA32);
-#define SD_G3(MODE_, HS_, TIMED_) do { if (s16) hipLaunchKernelGGL((conv_dma3_kernel<MODE_, HS_, TIMED_, !(HS_) || (MODE_) == 1>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN); \
-                                       else hipLaunchKernelGGL((conv_dma3_kernel<MODE_, HS_, TIMED_, false>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN); } while (0)
-#ifdef SD_DEV_VARIANTS
-    if (mode == 1 && (p.sw & SW_X3_DIAG_NOSTORE) && (p.sw & SW_X3_DIAG_NOMFMA)) {          // SEMDEPTH_X3_DIAG=3: the timed copy of the 1x1 form
-        if (p.f16 == 4) SD_G3(1, true, true); else SD_G3(1, false, true);
-        return hipGetLastError();
-    }
-#endif
+#define SD_G3(MODE_, HS_) do { if (s16) hipLaunchKernelGGL((conv_dma3_kernel<MODE_, HS_, !(HS_) || (MODE_) == 1>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN); \
+                                else hipLaunchKernelGGL((conv_dma3_kernel<MODE_, HS_, false>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN); } while (0)
     if (p.f16 == 4) {           // SD_PREC_F16X2: the two-plane, two-phase form
-        if (mode == 1) SD_G3(1, true, false); else if (mode == 2) SD_G3(2, true, false); else SD_G3(0, true, false);
+        if (mode == 1) SD_G3(1, true); else if (mode == 2) SD_G3(2, true); else SD_G3(0, true);
         return hipGetLastError();
     }
-    if (mode == 1) SD_G3(1, false, false); else if (mode == 2) SD_G3(2, false, false); else SD_G3(0, false, false);
+    if (mode == 1) SD_G3(1, false); else if (mode == 2) SD_G3(2, false); else SD_G3(0, false);
 #undef SD_G3
     return hipGetLastError();
 }

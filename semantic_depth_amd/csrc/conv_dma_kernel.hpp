@@ -568,7 +568,7 @@ void launch_dma_variant(const ConvParams& p, long M, hipStream_t s) {
     const int tilesM = (int)((M + WM * MT * 32 - 1) / (WM * MT * 32)), tilesN = p.Cout / (WN * NT * 32);
     const dim3 grid((unsigned)(tilesM * tilesN * ((p.fold && !p.x3) ? 4 : 1))), block(64 * WM * WN);
     if (p.fold && p.x3) return;                                // (folded GEMMs: the two-plane forms here, bf16 x 3 on conv_dma3.hip; the caller sees hipErrorInvalidValue)
-    const int mode = (p.dbg & 16) ? 0 : p.simple;
+    const int mode = p.simple;
     constexpr bool x3_fits = 2 * 12 * (WM * MT * 32 + WN * NT * 32) * 16 <= 160 * 1024;
     if constexpr (x3_fits) if (p.x3) {               // bf16 x 3: two stages
         if (mode == 2) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 2, 2, false, false, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);

@@ -63,8 +63,6 @@ __global__ __launch_bounds__(512, 1) void dec_tail1_kernel(const DecTailParams p
     const int ntx = (W + DT_TW - 1) / DT_TW, nty = H / DT_TH;
     const int ntiles = ntx * nty * p.N;
     const int lp = lane & 15, lg = lane >> 4;            // MFMA fragment: pixel / output channel (lane & 15), k group (lane >> 4)
-    // SEMDEPTH_X3_DIAG (decomposition runs; 0 in production): 1 / 2 / 3 = without stage 1 / 2 / 3
-    const int diag = SD_DIAG_BITS(p.sw);
 
     struct Tile { int img, y0, x0; };
     auto tile_of = [&](int it) {
@@ -230,44 +228,42 @@ __global__ __launch_bounds__(512, 1) void dec_tail1_kernel(const DecTailParams p
                     if ((ge[j] >> 24) & 1) Ub[NPL * DT_UPL + pl * DT_EPL + er * DT_UC + uc] = ev;
                 }
                 // stage 1: u rows 2 n + py, n = 0 .. UR / 2 - 1, columns 2 m + px (m = lane & 15)
-                if (diag != 1) {
-                    // source fragment of tile row r, column shift b: pixel column m + px + b, octet lane >> 4
-                    auto frag = [&](int r, int b, int pl) {
-                        const int acol = lp + px + b;
-                        return A[pl * DT_APL + (r * DT_AC + acol) * 4 + (lg ^ ((acol >> 1) & 3))];
-                    };
-                    u32x4 F[2][2][3];                                             // [row slot][b][plane]
+                // source fragment of tile row r, column shift b: pixel column m + px + b, octet lane >> 4
+                auto frag = [&](int r, int b, int pl) {
+                    const int acol = lp + px + b;
+                    return A[pl * DT_APL + (r * DT_AC + acol) * 4 + (lg ^ ((acol >> 1) & 3))];
+                };
+                u32x4 F[2][2][3];                                             // [row slot][b][plane]
+#pragma unroll
+                for (int b = 0; b < 2; ++b)
+#pragma unroll
+                    for (int pl = 0; pl < NPL; ++pl) F[0][b][pl] = frag(py, b, pl);
+#pragma unroll
+                for (int n = 0; n < DT_UR / 2; ++n) {
+                    const int s0 = n & 1, s1_ = s0 ^ 1;                       // slots of source rows n + py (a = 0) and n + py + 1 (a = 1)
 #pragma unroll
                     for (int b = 0; b < 2; ++b)
 #pragma unroll
-                        for (int pl = 0; pl < NPL; ++pl) F[0][b][pl] = frag(py, b, pl);
+                        for (int pl = 0; pl < NPL; ++pl) F[s1_][b][pl] = frag(n + py + 1, b, pl);
+                    f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-                    for (int n = 0; n < DT_UR / 2; ++n) {
-                        const int s0 = n & 1, s1_ = s0 ^ 1;                       // slots of source rows n + py (a = 0) and n + py + 1 (a = 1)
-#pragma unroll
-                        for (int b = 0; b < 2; ++b)
-#pragma unroll
-                            for (int pl = 0; pl < NPL; ++pl) F[s1_][b][pl] = frag(n + py + 1, b, pl);
-                        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                        for (int b = 0; b < 2; ++b) {
-                            acc0 = mac6(w1[b], F[s0][b][0], F[s0][b][1], F[s0][b][HS ? 1 : 2], acc0);
-                            acc1 = mac6(w1[2 + b], F[s1_][b][0], F[s1_][b][1], F[s1_][b][HS ? 1 : 2], acc1);
-                        }
-                        f32x4 v = HS ? (acc0 + acc1) * p.alpha + bias1 : acc0 + acc1 + bias1;
-                        v = act_split4<ACT_ELU>(v);      // (act_x3<ELU> and act_split<ELU> are the same function)
-                        const int ru = 2 * n + py, uc = 2 * lp + px;
-                        const bool in = (unsigned)(y0 - 2 + ru) < (unsigned)H && (unsigned)(x0 - 2 + uc) < (unsigned)W;
-                        if (!in) v = f32x4{0.f, 0.f, 0.f, 0.f};
-                        uint2 hh, mm, ll;
-                        uint2* const up = reinterpret_cast<uint2*>(Ub) + ((ru * DT_UC + uc) * 2 + ((lg >> 1) ^ ((uc >> 2) & 1))) * 2 + (lg & 1);
-                        if constexpr (HS) {
-                            split4_hs(v, hh, mm, (sat_ptr_t) nullptr);
-                            up[0] = hh; up[2 * DT_UPL] = mm;
-                        } else {
-                            split4_x3(v, hh, mm, ll);
-                            up[0] = hh; up[2 * DT_UPL] = mm; up[4 * DT_UPL] = ll;
-                        }
+                    for (int b = 0; b < 2; ++b) {
+                        acc0 = mac6(w1[b], F[s0][b][0], F[s0][b][1], F[s0][b][HS ? 1 : 2], acc0);
+                        acc1 = mac6(w1[2 + b], F[s1_][b][0], F[s1_][b][1], F[s1_][b][HS ? 1 : 2], acc1);
+                    }
+                    f32x4 v = HS ? (acc0 + acc1) * p.alpha + bias1 : acc0 + acc1 + bias1;
+                    v = act_split4<ACT_ELU>(v);      // (act_x3<ELU> and act_split<ELU> are the same function)
+                    const int ru = 2 * n + py, uc = 2 * lp + px;
+                    const bool in = (unsigned)(y0 - 2 + ru) < (unsigned)H && (unsigned)(x0 - 2 + uc) < (unsigned)W;
+                    if (!in) v = f32x4{0.f, 0.f, 0.f, 0.f};
+                    uint2 hh, mm, ll;
+                    uint2* const up = reinterpret_cast<uint2*>(Ub) + ((ru * DT_UC + uc) * 2 + ((lg >> 1) ^ ((uc >> 2) & 1))) * 2 + (lg & 1);
+                    if constexpr (HS) {
+                        split4_hs(v, hh, mm, (sat_ptr_t) nullptr);
+                        up[0] = hh; up[2 * DT_UPL] = mm;
+                    } else {
+                        split4_x3(v, hh, mm, ll);
+                        up[0] = hh; up[2 * DT_UPL] = mm; up[4 * DT_UPL] = ll;
                     }
                 }
             }
@@ -297,7 +293,7 @@ __global__ __launch_bounds__(512, 1) void dec_tail1_kernel(const DecTailParams p
         for (int k = 0; k <= K; ++k) {
             const Tile cur = tile_of(first + (k >= 1 ? k - 1 : 0) * stride);
             // ---------------- phase A: stage 2 of tile k - 1: i rows ri0 .. of the 16-pixel strip (the other group: stage 1 of tile k)
-            if (k >= 1 && diag != 2) {
+            if (k >= 1) {
                 const u32x4* const Ub = UE + ((k - 1) & 1) * DT_UE;
                 u32x4 G[3][2][3];                                             // [u row slot][half][plane]
                 auto gload = [&](int slot, int ru) {
@@ -330,7 +326,7 @@ __global__ __launch_bounds__(512, 1) void dec_tail1_kernel(const DecTailParams p
             __syncthreads();
             // ---------------- phase B: stage 3 of tile k - 1, a quarter of the tile's pixels per wave: VALU time is per wave instruction, so
             //                  one pass on each SIMD (56 of 64 lanes) instead of two passes on two of them
-            if (k >= 1 && diag != 3 && lane < DT_NPIX / 4) head(cur, wv * (DT_NPIX / 4) + lane);
+            if (k >= 1 && lane < DT_NPIX / 4) head(cur, wv * (DT_NPIX / 4) + lane);
             __syncthreads();
         }
     }

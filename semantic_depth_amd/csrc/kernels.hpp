@@ -7,33 +7,21 @@ namespace sd {
 
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 
-// run-time switches (SEMDEPTH_DISABLE=name,... -- plan.cpp sd_disabled; the closed A/Bs and the decomposition runs of earlier rounds in -DSD_DEV_VARIANTS builds
-// only), latched ONCE per handle in sd_create (plan.cpp latch_switches) and handed to the launchers in their parameter structs: nothing on the launch path calls getenv
+// run-time switches (SEMDEPTH_DISABLE=name,... -- plan.cpp sd_disabled), latched ONCE per handle in sd_create (plan.cpp latch_switches) and handed to the
+// launchers in their parameter structs: nothing on the launch path calls getenv.  Bit values are fixed; retired switches leave gaps.
 enum Switch : unsigned {
-    SW_NO_N16 = 1u << 0, SW_NO_UPTILE = 1u << 1, SW_NO_N16_MT1 = 1u << 2, SW_NO_DMA_BIG = 1u << 3, SW_NO_DMA32 = 1u << 4,
-    SW_NO_STEM = 1u << 5, SW_NO_FUSE4 = 1u << 6, SW_NO_SMALLN_TILE = 1u << 7, SW_NO_DMA = 1u << 8, SW_DMA_DBG16 = 1u << 9,
+    SW_NO_N16 = 1u << 0, SW_NO_DMA_BIG = 1u << 3,
+    SW_NO_STEM = 1u << 5, SW_NO_FUSE4 = 1u << 6, SW_NO_DMA = 1u << 8,
     SW_PROFILE_VERBOSE = 1u << 10, SW_NO_FUSE1 = 1u << 11,
-    // bf16 x 3 engine (round 3): SEMDEPTH_X3_KEEP=0 (no register-cached X fragments), SEMDEPTH_X3_RING3 (three-slot weight ring of the
-    // NB = 1 layers), SEMDEPTH_NO_DMA3 (128 x 256 two-stage GEMM block instead of the phased 256 x 256 one), SEMDEPTH_X3_DIAG=1|2|3
-    // (decomposition runs of conv_direct3: no output stores / no MFMAs)
-    SW_X3_NOKEEP = 1u << 12, SW_X3_RING3 = 1u << 13, SW_NO_DMA3 = 1u << 14, SW_X3_DIAG_NOSTORE = 1u << 15, SW_X3_DIAG_NOMFMA = 1u << 16,
+    SW_NO_DMA3 = 1u << 14,       // SEMDEPTH_DISABLE=dma3: bf16 x 3 layers on the 128 x 256 two-stage GEMM block instead of the phased 256 x 256 one
     SW_NO_FOLD = 1u << 17,       // SEMDEPTH_NO_FOLD: the upconv layers as 3x3 convs on the upsampled source (plan-time switch)
     SW_NO_TAIL1 = 1u << 18,      // SEMDEPTH_NO_TAIL1: upconv1 / iconv1 / disp1 of the bf16 x 3 monodepth as three launches (plan-time switch)
     SW_NO_ROWSKIP = 1u << 19,    // SEMDEPTH_NO_ROWSKIP: conv_dma3 without the row-grouped pixel order (ConvParams::rowgrp)
     SW_NO_FLAT = 1u << 20,       // SEMDEPTH_NO_FLAT: conv_dma3's 1x1 layers through the general gather
-    SW_X3_DIAG_TIMED = 1u << 21, // SEMDEPTH_X3_DIAG=4: conv_direct3's timed copy (s_memtime stamps per item; decomposition runs)
-    SW_HS_TAPS = 1u << 23,       // SEMDEPTH_HS_PHASED_TAPS: ALL tap layers of the three-product engine (folded upconvs, strided 3x3; fc6 is there anyway) on conv_dma3's two-phase ring
     SW_MFMA32 = 1u << 22         // SEMDEPTH_MFMA32: conv_dma3's bf16 x 3 layers on 32x32x16 MFMAs instead of 16x16x32 (round 5; conv_dma3.hip "S16")
 };
 unsigned latch_switches();      // plan.cpp
 bool sd_disabled(const char* what);   // plan.cpp: is `what` in SEMDEPTH_DISABLE?
-// decomposition runs (SEMDEPTH_X3_DIAG: 1 no output stores, 2 no MFMAs / no epilogue): compiled into -DSD_DEV_VARIANTS builds only -- in the shipped library
-// the expression is the constant 0 and every branch on it folds away
-#ifdef SD_DEV_VARIANTS
-#define SD_DIAG_BITS(sw) ((((sw) & sd::SW_X3_DIAG_NOSTORE) ? 1 : 0) | (((sw) & sd::SW_X3_DIAG_NOMFMA) ? 2 : 0))
-#else
-#define SD_DIAG_BITS(sw) 0
-#endif
 
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_ELU = 2, ACT_SIGMOID03 = 3 /* 0.3*sigmoid, monodepth get_disp */ };
 
@@ -83,7 +71,6 @@ struct ConvParams {
                        // window: out is [N,Hout/2,Wout/2,Cout]
     int simple;        // 1: one source, stride 1, no upsample, all k-tiles vec: the DMA kernel computes its gather addresses;
                        // 2: two-source 1x1 GEMM (ResNet conv3 + projection), per-source strides, no upsample
-    int dbg;           // SEMDEPTH_DMA_DBG=16: general gather path on SIMPLE layers too (A/B switch; 0 in production)
     int m_fastest;     // block order: 1 = consecutive blocks walk M (share a weight panel), 0 = walk N
     unsigned sw;       // Switch bits of the handle
     int reserve_cus;   // persistent launches use (CUs - reserve_cus) workgroups: the CUs left free take the per-frame tail of the previous step
@@ -267,7 +254,7 @@ struct SmallNParams {
     unsigned sw;        // Switch bits of the handle
 };
 hipError_t launch_conv_smalln(const SmallNParams& p, hipStream_t s);
-bool conv_smalln_tiled(int in_split, int k, int W, int C, int nout, unsigned sw);   // the LDS-tiled kernel takes this layer (it alone reads sub-planar inputs)
+bool conv_smalln_tiled(int in_split, int k, int W, int C, int nout);   // the LDS-tiled kernel takes this layer (it alone reads sub-planar inputs)
 
 // ---------------------------------------------------------------------------------------------
 // misc network ops (ops_misc.hip)

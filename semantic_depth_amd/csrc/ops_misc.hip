@@ -486,8 +486,8 @@ template <int IN_SPLIT>
 static void launch_smalln_t(const SmallNParams& p, hipStream_t s) {
     const long npix = (long)p.N * p.H * p.W;
     const int K = p.k * p.k * p.C;
-    if (IN_SPLIT && p.k == 3 && p.W % SN_TW == 0 && p.C % 8 == 0 && p.nout <= 2 && p.zero16 && (size_t)K * 4 * p.nout <= 24576 &&
-        !(p.sw & SW_NO_SMALLN_TILE)) {
+    // (IN_SPLIT 3, fp16 hi + lo input: the per-thread / per-wave kernels only)
+    if (IN_SPLIT && IN_SPLIT != 3 && p.k == 3 && p.W % SN_TW == 0 && p.C % 8 == 0 && p.nout <= 2 && p.zero16 && (size_t)K * 4 * p.nout <= 24576) {
         const dim3 grid((unsigned)((p.W / SN_TW) * ((p.H + SN_TH - 1) / SN_TH) * p.N));
         const size_t lds = (size_t)K * 4 * p.nout;
         if (IN_SPLIT == 5) {
@@ -518,12 +518,11 @@ static void launch_smalln_t(const SmallNParams& p, hipStream_t s) {
         hipLaunchKernelGGL(conv_smalln_wave_kernel<IN_SPLIT>, dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, s, p);
     }
 }
-bool conv_smalln_tiled(int in_split, int k, int W, int C, int nout, unsigned sw) {
-    return in_split && k == 3 && W % SN_TW == 0 && C % 8 == 0 && nout <= 2 && (size_t)9 * C * 4 * nout <= 24576 &&
-           !(sw & SW_NO_SMALLN_TILE);
+bool conv_smalln_tiled(int in_split, int k, int W, int C, int nout) {
+    return in_split && k == 3 && W % SN_TW == 0 && C % 8 == 0 && nout <= 2 && (size_t)9 * C * 4 * nout <= 24576;
 }
 hipError_t launch_conv_smalln(const SmallNParams& p, hipStream_t s) {
-    if (p.in_sub && !(conv_smalln_tiled(p.in_split, p.k, p.W, p.C, p.nout, p.sw) && p.zero16)) return hipErrorInvalidValue;   // sub-planes: tiled kernel only
+    if (p.in_sub && !(conv_smalln_tiled(p.in_split, p.k, p.W, p.C, p.nout) && p.zero16)) return hipErrorInvalidValue;   // sub-planes: tiled kernel only
     if (p.out_split && (p.nout != 2 || p.k * p.k * p.C > 2048)) return hipErrorInvalidValue;
     if (p.in_split && p.x3) {            // bf16 x 3 input: exact f32 arithmetic on the reconstructed values (tiled or per-thread / per-wave)
         if (p.in_sub) return hipErrorInvalidValue;
@@ -532,9 +531,7 @@ hipError_t launch_conv_smalln(const SmallNParams& p, hipStream_t s) {
         launch_smalln_t<5>(p, s);                // (sub-planar inputs: the tiled kernel, checked above)
     } else if (p.in_split && p.f16 == 2) {      // fp16 hi + lo input: the per-thread / per-wave kernels only
         if (p.in_sub || p.out_split) return hipErrorInvalidValue;
-        SmallNParams q = p;
-        q.sw |= SW_NO_SMALLN_TILE;
-        launch_smalln_t<3>(q, s);
+        launch_smalln_t<3>(p, s);
     } else if (p.in_split && p.f16) launch_smalln_t<2>(p, s);
     else if (p.in_split) launch_smalln_t<1>(p, s);
     else launch_smalln_t<0>(p, s);

@@ -10,10 +10,8 @@
 namespace sd {
 
 // SEMDEPTH_DISABLE=name[,name...]: the ONE run-time variable that switches specialised kernels off in favour of the generic ones behind them (parity tests, A/B
-// runs).  Names: dma dma3 direct stem fold tail1 pool_fuse planar n16 fuse1 fuse4 flat rowskip dma_big mfma16.  Read when a handle is created (plan + switches).
-// Closed A/Bs of earlier rounds (SEMDEPTH_NO_UPTILE, _NO_N16_MT1, _NO_DMA32, _NO_SMALLN_TILE, _X3_RING3, _X3_KEEP, _HS_PHASED_TAPS, _DMA_DBG, _NO_PLANAR_WIDE,
-// _NO_DIRECT128, _DIRECT_MINPIX, _NO_MFMA_HEADS, _X3_NO_POOL_FUSE) and the decomposition runs (SEMDEPTH_X3_DIAG) exist in -DSD_DEV_VARIANTS builds only
-// (SEMDEPTH_DEV_BUILD=1 python -m semantic_depth_amd.build --force).
+// runs).  Names: dma dma3 direct stem fold tail1 pool_fuse planar n16 fuse1 fuse4 flat rowskip dma_big mfma16.  Read when a handle is created (plan + switches),
+// latch_switches adds SEMDEPTH_PROFILE_VERBOSE=1 to the same switch word.
 bool sd_disabled(const char* what) {
     const char* e = std::getenv("SEMDEPTH_DISABLE");
     if (!e) return false;
@@ -41,31 +39,14 @@ std::string sd_disable_unknown() {
     }
     return "";
 }
-static const char* dev_env(const char* name) {
-#ifdef SD_DEV_VARIANTS
-    return std::getenv(name);
-#else
-    (void)name;
-    return nullptr;
-#endif
-}
-
 unsigned latch_switches() {
     static const struct { const char* name; unsigned bit; } tab[] = {
         {"n16", SW_NO_N16}, {"dma_big", SW_NO_DMA_BIG}, {"stem", SW_NO_STEM}, {"fuse4", SW_NO_FUSE4}, {"dma", SW_NO_DMA}, {"fuse1", SW_NO_FUSE1},
         {"dma3", SW_NO_DMA3}, {"fold", SW_NO_FOLD}, {"tail1", SW_NO_TAIL1}, {"rowskip", SW_NO_ROWSKIP}, {"flat", SW_NO_FLAT}, {"mfma16", SW_MFMA32}};
-    static const struct { const char* name; unsigned bit; } dev[] = {
-        {"SEMDEPTH_NO_UPTILE", SW_NO_UPTILE}, {"SEMDEPTH_NO_N16_MT1", SW_NO_N16_MT1}, {"SEMDEPTH_NO_DMA32", SW_NO_DMA32}, {"SEMDEPTH_NO_SMALLN_TILE", SW_NO_SMALLN_TILE},
-        {"SEMDEPTH_X3_RING3", SW_X3_RING3}, {"SEMDEPTH_HS_PHASED_TAPS", SW_HS_TAPS}};
     unsigned sw = 0;
     for (const auto& e : tab)
         if (sd_disabled(e.name)) sw |= e.bit;
-    for (const auto& e : dev)
-        if (dev_env(e.name)) sw |= e.bit;
-    if (const char* d = dev_env("SEMDEPTH_DMA_DBG")) if (atoi(d) & 16) sw |= SW_DMA_DBG16;
     if (const char* v = std::getenv("SEMDEPTH_PROFILE_VERBOSE")) if (v[0] == '1') sw |= SW_PROFILE_VERBOSE;
-    if (const char* v = dev_env("SEMDEPTH_X3_KEEP")) if (atoi(v) == 0) sw |= SW_X3_NOKEEP;
-    if (const char* v = dev_env("SEMDEPTH_X3_DIAG")) sw |= ((atoi(v) & 1) ? SW_X3_DIAG_NOSTORE : 0u) | ((atoi(v) & 2) ? SW_X3_DIAG_NOMFMA : 0u) | ((atoi(v) & 4) ? SW_X3_DIAG_TIMED : 0u);
     return sw;
 }
 
@@ -152,10 +133,7 @@ struct Builder {
         // full-resolution few-channel 3x3 layers of the split engine go to the direct (halo-tile) kernel
         // 128 .. 512 output channels: 2 .. 8 passes of 64 per tile (256 and more only where an image has enough tiles: the
         // choice must not depend on the batch)
-        const char* mp = dev_env("SEMDEPTH_DIRECT_MINPIX");
-        const int64_t minpix = mp ? std::atoll(mp) : 512;
-        const bool split128 = (Cout == 128 && !dev_env("SEMDEPTH_NO_DIRECT128")) ||
-                              ((Cout == 256 || Cout == 512) && (int64_t)Hin * Win >= minpix);
+        const bool split128 = Cout == 128 || ((Cout == 256 || Cout == 512) && (int64_t)Hin * Win >= 512);
         bool direct = p.prec && k == 3 && stride == 1 && (Cout <= 32 || Cout == 64 || split128) && Cout % 8 == 0 && Win % 32 == 0 && residual < 0 &&
                       !sd_disabled("direct");
         for (int i = 0; i < op.nsrc; ++i)
@@ -189,7 +167,7 @@ struct Builder {
             op.nsplit = Cout > 64 ? Cout / 64 : 1;
             // bf16 x 3 and (round 6) SD_PREC_F16X2, an upconv layer (one x2-upsampled source): the upsample-folded form of the direct kernel (OpDesc::fold;
             // f16x2: the 32 / 64-channel forms -- a 16-channel upconv1 outside the fused decoder tail runs the 16-wide MFMA kernel unfolded)
-            op.fold = ((p.x3 || (p.h2 && Cout >= 32)) && op.nsrc == 1 && op.up[0] && p.tensors[op.src[0]].C % 16 == 0 && Hout % 2 == 0 && !(latch_switches() & (SW_NO_FOLD | SW_NO_UPTILE))) ? 1 : 0;
+            op.fold = ((p.x3 || (p.h2 && Cout >= 32)) && op.nsrc == 1 && op.up[0] && p.tensors[op.src[0]].C % 16 == 0 && Hout % 2 == 0 && !(latch_switches() & SW_NO_FOLD)) ? 1 : 0;
             op.w = wslot(wname, {k, k, Ctf, Cout}, WL_DIRECT_SPLIT, nch * (op.fold ? 16 : 9) * 16, Cout <= 32 ? 32 : 64, 0, op.nsplit);
             WeightSlot& ws = p.weights[op.w];
             ws.nsrc = op.nsrc; ws.fold = op.fold;
@@ -267,7 +245,7 @@ struct Builder {
         // a 3x3 head whose output feeds the next iconv (disp4..disp2, written as one zero-padded octet per pixel) is a direct
         // conv on the 16-wide MFMA: its two real output channels ride in a 16-column weight image
         if (feeds_conv && p.prec && !p.x3 && k == 3 && t.W % 32 == 0 && t.C % 8 == 0 && nout <= 8 && nout == cout_tf &&
-            !sd_disabled("direct") && !sd_disabled("n16") && !dev_env("SEMDEPTH_NO_MFMA_HEADS")) {
+            !sd_disabled("direct") && !sd_disabled("n16")) {
             op.kind = OP_CONV_DIRECT; op.stride = 1;
             op.nchunks = (t.C + 15) / 16;
             op.nsplit = 1;
@@ -325,7 +303,7 @@ struct Builder {
         const int Ho = zero3 ? (t.H - 1) / 2 + 1 : t.H / 2, Wo = zero3 ? (t.W - 1) / 2 + 1 : t.W / 2;
         // a direct conv whose only consumer is this pool applies it in its epilogue (max commutes with bias + ReLU/ELU);
         // the full-resolution tensor is then never written
-        if (!zero3 && !(p.x3 && dev_env("SEMDEPTH_X3_NO_POOL_FUSE")) && !p.ops.empty() && p.ops.back().kind == OP_CONV_DIRECT && p.ops.back().dst == src && t.H % 2 == 0 && t.W % 2 == 0 &&
+        if (!zero3 && !p.ops.empty() && p.ops.back().kind == OP_CONV_DIRECT && p.ops.back().dst == src && t.H % 2 == 0 && t.W % 2 == 0 &&
             (p.ops.back().act == ACT_RELU || p.ops.back().act == ACT_ELU || p.ops.back().act == ACT_NONE) && !sd_disabled("pool_fuse")) {
             OpDesc& prod = p.ops.back();
             prod.fuse_pool = 1;
@@ -380,7 +358,6 @@ struct Builder {
             }
             return;
         }
-        const bool wide = !dev_env("SEMDEPTH_NO_PLANAR_WIDE");
         for (size_t ti = 0; ti < p.tensors.size(); ++ti) {
             TensorDesc& t = p.tensors[ti];
             if (t.C % 16 || (int)ti == p.t_output || (int)ti == p.t_input) continue;
@@ -389,7 +366,7 @@ struct Builder {
             for (const OpDesc& op : p.ops) {
                 if (op.dst == (int)ti)
                     made = op.kind == OP_CONV_DIRECT ||
-                           (wide && op.kind == OP_CONV && op.vec && op.Kvec == op.Kpad && t.C % 64 == 0 && op.Kpad >= 64 &&
+                           (op.kind == OP_CONV && op.vec && op.Kvec == op.Kpad && t.C % 64 == 0 && op.Kpad >= 64 &&
                             !sd_disabled("dma")) ||
                            // (three-product engine, round 5: a stem conv's output, as on bf16 x 3 above)
                            (p.h2 && op.kind == OP_CONV && op.nsrc == 1 && op.src[0] == p.t_input && (op.k & 1) && op.k <= 7 && !op.fold && !op.fuse_pool &&
@@ -398,7 +375,7 @@ struct Builder {
                 for (int j = 0; j < op.nsrc; ++j) reads = reads || op.src[j] == (int)ti;
                 if (!reads) continue;
                 ++readers;
-                const bool head = wide && op.kind == OP_SMALLN && conv_smalln_tiled(1, op.k, t.W, t.C, op.nout, latch_switches());
+                const bool head = op.kind == OP_SMALLN && conv_smalln_tiled(1, op.k, t.W, t.C, op.nout);
                 ok = ok && (op.kind == OP_CONV_DIRECT || head || (p.h2 && op.kind == OP_POOL3Z && t.C % 8 == 0)) && op.residual != (int)ti;
             }
             if (made && ok && readers > 0) t.planar16 = 1;
