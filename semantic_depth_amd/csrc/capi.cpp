@@ -146,20 +146,31 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int nframes,
         if (op.w >= 0) b += (double)p.weights[op.w].bytes;
         return b;
     };
-    // 0 f32, 1 split bf16, 2 ONE fp16 plane, 4 bf16 x 3, 5 fp16 hi + scaled lo (fp16 hi + lo tensors never reach the ops that take this)
-    auto FMT = [&](int t) -> int { return p.tensors[t].fmt ? (p.tensors[t].x3 ? 4 : p.tensors[t].f16 == 3 ? 5 : p.tensors[t].f16 ? 2 : 1) : 0; };
+    // a conv launch in a profiling bracket: its start event is the end event of the conv launched right before it when nothing else came between
+    // (sd_handle::prof_pool).  M x Nc: the record's GEMM extent; `kernel` names the launch for the record
+    auto bracketed = [&](const OpDesc& op, hipError_t& e, int M, int Nc, auto&& launch, auto&& kernel) -> sd_status {
+        if (!h->prof) { e = launch(); return SD_OK; }
+        hipEvent_t ea = h->prof_last, eb = nullptr;
+        if (!ea) { if (!(ea = prof_event(h))) return fail(h, SD_ERR_HIP, "hipEventCreate"); hipEventRecord(ea, s); }
+        if (!(eb = prof_event(h))) return fail(h, SD_ERR_HIP, "hipEventCreate");
+        e = launch();
+        hipEventRecord(eb, s);
+        h->prof_last = eb;
+        h->prof_recs.push_back({kernel(), op.flops * N / p.images, ea, eb, op.name.c_str(), M, Nc, op.K, op_bytes(op)});
+        return SD_OK;
+    };
     for (const WeightSlot& wsl : p.weights)
         if (!wsl.loaded) return fail(h, SD_ERR_STATE, "weight not loaded: " + wsl.name);
     h->prof_last = nullptr;                 // (other work may have been put on the stream since the previous call)
     for (const OpDesc& op : p.ops) {
         hipError_t e = hipSuccess;
-        bool conv_op = false;
+        sd_status st = SD_OK;
         switch (op.kind) {
             case OP_PRE_VGG:
-                e = launch_pre_vgg(frames, T(op.dst), (long)nframes * h->H * h->W, FMT(op.dst), PL(op.dst), s);
+                e = launch_pre_vgg(frames, T(op.dst), (long)nframes * h->H * h->W, p.tensors[op.dst].fmt, PL(op.dst), s);
                 break;
             case OP_PRE_MONO:
-                e = launch_pre_mono(frames, T(op.dst), nframes, h->H, h->W, FMT(op.dst), PL(op.dst), p.input_scale == 1.f ? 1 : 0, s);
+                e = launch_pre_mono(frames, T(op.dst), nframes, h->H, h->W, p.tensors[op.dst].fmt, PL(op.dst), p.input_scale == 1.f ? 1 : 0, s);
                 break;
             case OP_CONV: {
                 const TensorDesc& d = p.tensors[op.dst];
@@ -184,15 +195,14 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int nframes,
                 c.act = op.act; c.m_fastest = op.m_fastest;
                 c.out_plane = PL(op.dst); c.Nmax = p.images;
                 c.zero16 = h->ws + h->o_misc + 256;        // the arena is zero-filled and nothing writes here
-                const bool split = p.prec != 0;
-                c.f16 = op.f16; c.out_f16 = d.f16; c.alpha = op.f16 == 4 ? 1.f / p.weights[op.w].wscale : 1.f;
+                const bool split = p.engine != ENG_F32;
+                c.scheme = op.scheme; c.out_fmt = d.fmt; c.alpha = op.scheme == SC_HS ? 1.f / p.weights[op.w].wscale : 1.f;
                 c.src0 = T(op.src[0]); c.src0_plane = PL(op.src[0]);
                 c.out_planar16 = d.planar16;
                 c.sw = h->sw; c.reserve_cus = h->reserve_cus;
                 c.sat = reinterpret_cast<unsigned long long*>(h->ws + h->o_misc + SAT_OFF);
-                c.x3 = p.x3;
                 // conv_dma3.hip, k x k stride-1 layers on one source (fc6): one output row of 256 / Wout images per tile, taps on padding rows skipped
-                const bool ph3 = p.x3 || p.h2;          // the phased 256 x 256 GEMM block of conv_dma3.hip exists for these two engines
+                const bool ph3 = op.scheme == SC_BF16X3 || op.scheme == SC_HS;     // the phased 256 x 256 GEMM block of conv_dma3.hip exists for these two
                 if (ph3 && !op.fold && op.nsrc == 1 && op.vec && op.Kvec == op.Kpad && op.k >= 3 && op.sstride[0] == 1 && !op.up[0] && !c.pool &&
                     op.Kpad == op.k * op.k * s0.C && c.Wout > 0 && 256 % c.Wout == 0 && N % (256 / c.Wout) == 0 && !(h->sw & SW_NO_ROWSKIP))
                     c.rowgrp = 256 / c.Wout;
@@ -206,30 +216,15 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int nframes,
                 if (op.fold) {          // (conv_dma3.hip: the GEMM's pixel space is the source itself)
                     c.fold = 1; c.simple = 0; c.Hin = s0.H; c.Win = s0.W; c.Hout = s0.H; c.Wout = s0.W; c.kh = c.kw = 2;
                 }
-                hipEvent_t ea = nullptr, eb = nullptr;
-                if (h->prof) {
-                    ea = h->prof_last;
-                    if (!ea) { if (!(ea = prof_event(h))) return fail(h, SD_ERR_HIP, "hipEventCreate"); hipEventRecord(ea, s); }
-                    if (!(eb = prof_event(h))) return fail(h, SD_ERR_HIP, "hipEventCreate");
-                }
                 const bool dma3 = split && conv_dma3_eligible(c) && !(h->sw & SW_NO_DMA);
                 const bool dma = !dma3 && split && conv_dma_variant(c) != 0 && !(h->sw & SW_NO_DMA);
                 const bool stem = split && !dma && !dma3 && conv_stem_eligible(c);
                 if (c.out_planar16 && !stem && !dma) return fail(h, SD_ERR_STATE, "sub-planar output needs the LDS-DMA or the stem conv kernel");
                 if (c.pool && !dma) return fail(h, SD_ERR_STATE, "fused pool needs the LDS-DMA conv kernel");
-                if (c.fold && !dma3 && !(dma && !c.x3)) return fail(h, SD_ERR_STATE, "an upsample-folded conv needs the conv_dma3 kernel (bf16 x 3) or a two-plane form of conv_dma");
-                e = dma3 ? launch_conv_dma3(c, s) : dma ? launch_conv_dma(c, s) : stem ? launch_conv_stem(c, s) : split ? launch_conv_split(c, s) : launch_conv_igemm(c, s);
-                if (h->prof) {
-                    hipEventRecord(eb, s);
-                    h->prof_last = eb; conv_op = true;
-                    static const char* const dma3_names[3] = {"conv_dma3_kernel<0>", "conv_dma3_kernel<1>", "conv_dma3_kernel<2>"};
-                    static const char* const dmah_names[3] = {"conv_dma_hs_phased_kernel<0>", "conv_dma_hs_phased_kernel<1>", "conv_dma_hs_phased_kernel<2>"};
-                    // (one bucket for the bench line; the per-layer listing of SEMDEPTH_PROFILE_VERBOSE names the gather variant)
-                    const char* const dma3_name = (h->sw & SW_PROFILE_VERBOSE) ? (c.f16 == 4 ? dmah_names : dma3_names)[conv_dma3_mode(c)]
-                                                                               : (c.f16 == 4 ? "conv_dma_hs_phased_kernel" : "conv_dma3_kernel");
-                    h->prof_recs.push_back({dma3 ? dma3_name : dma ? conv_dma_kernel_name(c) : stem ? (c.x3 ? "conv_stem_x3_kernel" : c.f16 == 4 ? "conv_stem_hs_kernel" : c.f16 ? "conv_stem_f16w_kernel" : "conv_stem_kernel") : split ? conv_split_kernel_name(c) : conv_igemm_kernel_name(c), op.flops * N / p.images, ea, eb,
-                                            op.name.c_str(), N * c.Hout * c.Wout * (c.fold ? 4 : 1), d.C, op.K, op_bytes(op)});
-                }
+                if (c.fold && !dma3 && !(dma && c.scheme != SC_BF16X3)) return fail(h, SD_ERR_STATE, "an upsample-folded conv needs the conv_dma3 kernel (bf16 x 3) or a two-plane form of conv_dma");
+                st = bracketed(op, e, N * c.Hout * c.Wout * (c.fold ? 4 : 1), d.C,
+                               [&] { return dma3 ? launch_conv_dma3(c, s) : dma ? launch_conv_dma(c, s) : stem ? launch_conv_stem(c, s) : split ? launch_conv_split(c, s) : launch_conv_igemm(c, s); },
+                               [&] { return dma3 ? conv_dma3_kernel_name(c) : dma ? conv_dma_kernel_name(c) : stem ? conv_stem_kernel_name(c) : split ? conv_split_kernel_name(c) : conv_igemm_kernel_name(c); });
                 break;
             }
             case OP_CONV_DIRECT: {
@@ -248,21 +243,12 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int nframes,
                 c.out = T(op.dst); c.out_plane = PL(op.dst); c.act = op.act; c.Nmax = p.images;
                 c.zero16 = h->ws + h->o_misc + 256;
                 c.rows_per_wave = 2;
-                c.f16 = op.f16; c.out_f16 = d.f16; c.alpha = op.f16 == 4 ? 1.f / p.weights[op.w].wscale : 1.f;
+                c.scheme = op.scheme; c.out_fmt = d.fmt; c.alpha = op.scheme == SC_HS ? 1.f / p.weights[op.w].wscale : 1.f;
                 c.sw = h->sw; c.reserve_cus = h->reserve_cus;
                 c.sat = reinterpret_cast<unsigned long long*>(h->ws + h->o_misc + SAT_OFF);
-                hipEvent_t ea = nullptr, eb = nullptr;
-                if (h->prof) {
-                    ea = h->prof_last;
-                    if (!ea) { if (!(ea = prof_event(h))) return fail(h, SD_ERR_HIP, "hipEventCreate"); hipEventRecord(ea, s); }
-                    if (!(eb = prof_event(h))) return fail(h, SD_ERR_HIP, "hipEventCreate");
-                }
-                e = p.x3 ? launch_conv_direct3(c, s) : launch_conv_direct(c, s);
-                if (h->prof) {
-                    hipEventRecord(eb, s);
-                    h->prof_last = eb; conv_op = true;
-                    h->prof_recs.push_back({p.x3 ? conv_direct3_kernel_name(c) : conv_direct_kernel_name(c), op.flops * N / p.images, ea, eb, op.name.c_str(), N * c.H * c.W, d.C, op.K, op_bytes(op)});
-                }
+                const bool x3 = op.scheme == SC_BF16X3;
+                st = bracketed(op, e, N * c.H * c.W, d.C, [&] { return x3 ? launch_conv_direct3(c, s) : launch_conv_direct(c, s); },
+                               [&] { return x3 ? conv_direct3_kernel_name(c) : conv_direct_kernel_name(c); });
                 break;
             }
             case OP_DEC_TAIL1: {
@@ -274,19 +260,10 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int nframes,
                 c.w2 = reinterpret_cast<const u32x4_t*>(Wp(op.w2)); c.b2 = Wp(op.b2);
                 c.wd = Wp(op.w3); c.bd = Wp(op.b3);
                 c.out = T(op.dst); c.sw = h->sw; c.reserve_cus = h->reserve_cus;
-                c.hs = p.h2; c.alpha = p.h2 ? 1.f / p.weights[op.w].wscale : 1.f; c.alpha2 = p.h2 ? 1.f / p.weights[op.w2].wscale : 1.f;
-                hipEvent_t ea = nullptr, eb = nullptr;
-                if (h->prof) {
-                    ea = h->prof_last;
-                    if (!ea) { if (!(ea = prof_event(h))) return fail(h, SD_ERR_HIP, "hipEventCreate"); hipEventRecord(ea, s); }
-                    if (!(eb = prof_event(h))) return fail(h, SD_ERR_HIP, "hipEventCreate");
-                }
-                e = launch_dec_tail1(c, s);
-                if (h->prof) {
-                    hipEventRecord(eb, s);
-                    h->prof_last = eb; conv_op = true;
-                    h->prof_recs.push_back({p.h2 ? "dec_tail1_hs_kernel" : "dec_tail1_x3_kernel", op.flops * N / p.images, ea, eb, op.name.c_str(), N * d.H * d.W, 16, op.K, op_bytes(op)});
-                }
+                c.scheme = engine_forms(p.engine).conv;
+                const bool hs = c.scheme == SC_HS;
+                c.alpha = hs ? 1.f / p.weights[op.w].wscale : 1.f; c.alpha2 = hs ? 1.f / p.weights[op.w2].wscale : 1.f;
+                st = bracketed(op, e, N * d.H * d.W, 16, [&] { return launch_dec_tail1(c, s); }, [&] { return hs ? "dec_tail1_hs_kernel" : "dec_tail1_x3_kernel"; });
                 break;
             }
             case OP_SMALLN: {
@@ -294,8 +271,7 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int nframes,
                 SmallNParams c{};
                 c.x = T(op.src[0]); c.N = N; c.H = s0.H; c.W = s0.W; c.C = s0.C; c.k = op.k; c.nout = op.nout;
                 c.wt = Wp(op.w); c.bias = Wp(op.b); c.out = T(op.dst); c.act = op.act;
-                c.in_split = FMT(op.src[0]) != 0; c.out_split = FMT(op.dst) != 0; c.in_plane = PL(op.src[0]); c.out_plane = PL(op.dst);
-                c.f16 = s0.f16; c.out_f16 = p.tensors[op.dst].f16; c.x3 = p.x3;
+                c.in_fmt = s0.fmt; c.out_fmt = p.tensors[op.dst].fmt; c.in_plane = PL(op.src[0]); c.out_plane = PL(op.dst);
                 c.in_sub = s0.planar16 ? (size_t)p.images * s0.H * s0.W * 16 : 0;
                 c.out_c = p.tensors[op.dst].C;
                 c.zero16 = h->ws + h->o_misc + 256;
@@ -305,12 +281,12 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int nframes,
             }
             case OP_POOL2: {
                 const TensorDesc& s0 = p.tensors[op.src[0]];
-                e = launch_maxpool2(T(op.src[0]), T(op.dst), N, s0.H, s0.W, s0.C, FMT(op.src[0]), PL(op.src[0]), PL(op.dst), s);
+                e = launch_maxpool2(T(op.src[0]), T(op.dst), N, s0.H, s0.W, s0.C, s0.fmt, PL(op.src[0]), PL(op.dst), s);
                 break;
             }
             case OP_POOL3Z: {
                 const TensorDesc& s0 = p.tensors[op.src[0]];
-                e = launch_maxpool3z(T(op.src[0]), T(op.dst), N, s0.H, s0.W, s0.C, FMT(op.src[0]), PL(op.src[0]), PL(op.dst), s0.planar16 ? p.images : 0, s);
+                e = launch_maxpool3z(T(op.src[0]), T(op.dst), N, s0.H, s0.W, s0.C, s0.fmt, PL(op.src[0]), PL(op.dst), s0.planar16 ? p.images : 0, s);
                 break;
             }
             case OP_DECONV4_ADD: {
@@ -325,7 +301,9 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int nframes,
                 break;
             }
         }
-        if (!conv_op) h->prof_last = nullptr;       // something else went onto the stream: the next conv records its own start
+        if (st != SD_OK) return st;
+        if (op.kind != OP_CONV && op.kind != OP_CONV_DIRECT && op.kind != OP_DEC_TAIL1)
+            h->prof_last = nullptr;                 // something else went onto the stream: the next conv records its own start
         if (e != hipSuccess) return fail(h, SD_ERR_HIP, "launch " + op.name + ": " + hipGetErrorString(e));
     }
     (net == SD_NET_FCN8S ? h->last_fcn_images : h->last_mono_images) = N;
@@ -407,6 +385,16 @@ sd_status sd_precision_plan(const sd_handle* h, sd_net net, char* layers_out, si
     return p.f16_ops.size() + 1 > cap && layers_out ? SD_ERR_INVALID : SD_OK;
 }
 
+// the conv engine of a precision: SD_PREC_MIXED and SD_PREC_PLAN are the bf16 x 2 engine with a precision plan (sd_create)
+static Engine engine_of(sd_precision prec) {
+    switch (prec) {
+        case SD_PREC_F32: return ENG_F32;
+        case SD_PREC_BF16X3: return ENG_BF16X3;
+        case SD_PREC_F16X2: return ENG_F16X2;
+        default: return ENG_BF16X2;
+    }
+}
+
 static sd_status create_impl(sd_handle** out, int device, int H, int W, int max_batch, sd_encoder enc, sd_precision prec,
                              const char* fcn_f16, const char* mono_f16) {
     if (!out || H <= 0 || W <= 0 || max_batch <= 0) return SD_ERR_INVALID;
@@ -426,8 +414,7 @@ static sd_status create_impl(sd_handle** out, int device, int H, int W, int max_
     if (const char* e = std::getenv("SEMDEPTH_CHUNK")) chunk = std::max(1, atoi(e));
     h->chunk = std::min(max_batch, chunk);
     try {
-        // exact f32 MFMA | split, three bf16 planes | split, fp16 hi + scaled lo planes | split (bf16 x 2 + the fp16 forms of the plan)
-        const int eng = h->prec == SD_PREC_F32 ? 0 : h->prec == SD_PREC_BF16X3 ? 2 : h->prec == SD_PREC_F16X2 ? 3 : 1;
+        const Engine eng = engine_of(prec);
         h->fcn = build_fcn8s(h->chunk, H, W, eng, fcn_f16);
         h->mono = build_monodepth(enc == SD_ENC_VGG ? 0 : 1, h->chunk, H, W, eng, mono_f16);
     } catch (const std::exception& ex) {
@@ -512,7 +499,7 @@ sd_status sd_load_weight(sd_handle* h, sd_net net, const char* name, const float
             const size_t plane = (size_t)t.Ktotal * t.CoutPad * 2, rows = (size_t)t.Kpad * t.CoutPad * 2, ro = (size_t)t.k_off * t.CoutPad * 2;
             HIPCHK(h, hipMemcpy(base + ro, buf.data(), rows, hipMemcpyHostToDevice));
             HIPCHK(h, hipMemcpy(base + plane + ro, reinterpret_cast<char*>(buf.data()) + rows, rows, hipMemcpyHostToDevice));
-            if (t.x3) HIPCHK(h, hipMemcpy(base + 2 * plane + ro, reinterpret_cast<char*>(buf.data()) + 2 * rows, rows, hipMemcpyHostToDevice));
+            if (t.planes == WP_BF16X3) HIPCHK(h, hipMemcpy(base + 2 * plane + ro, reinterpret_cast<char*>(buf.data()) + 2 * rows, rows, hipMemcpyHostToDevice));
         } else {
             const int root = t.owner >= 0 ? t.owner : j;
             bool grouped = t.owner >= 0;
@@ -532,7 +519,7 @@ sd_status sd_load_weight(sd_handle* h, sd_net net, const char* name, const float
         }
         return SD_OK;
     };
-    if (s.hs) {
+    if (s.planes == WP_HS) {
         // SD_PREC_F16X2: the planes hold w' = w * 2^k in fp16 (hi + lo), k chosen HERE per layer so that the largest stored |w'| lies in
         // [2^12, 2^13) -- any finite f32 weight tensor loads (round 5 used a fixed 2^12 and refused |w| >= 16), and a layer of tiny weights
         // keeps the low plane's bits.  A stored value of an upsample-folded layer is a sum of up to four taps: bounded by 4 max |w|.  Slots
@@ -541,7 +528,7 @@ sd_status sd_load_weight(sd_handle* h, sd_net net, const char* name, const float
         const int root = s.owner >= 0 ? s.owner : idx;
         std::vector<int> members;
         for (int j = 0; j < (int)p.weights.size(); ++j)
-            if ((j == root || p.weights[j].owner == root) && p.weights[j].hs) members.push_back(j);
+            if ((j == root || p.weights[j].owner == root) && p.weights[j].planes == WP_HS) members.push_back(j);
         const bool grouped = members.size() > 1;
         for (size_t i = 0; i < nel; ++i)
             if (!std::isfinite(data[i])) return fail(h, SD_ERR_INVALID, std::string("weight ") + name + ": non-finite value");
@@ -936,15 +923,15 @@ sd_status sd_net_tensor(sd_handle* h, sd_net net, const char* name, float* out, 
     if (it == p.tensor_by_name.end()) return fail(h, SD_ERR_NOTFOUND, std::string("unknown tensor ") + name);
     const TensorDesc& t = p.tensors[it->second];
     const int N = net == SD_NET_FCN8S ? h->last_fcn_images : h->last_mono_images;
-    if (shape_out) { shape_out[0] = N; shape_out[1] = t.H; shape_out[2] = t.W; shape_out[3] = t.fmt ? t.Ctf : t.C; }
+    if (shape_out) { shape_out[0] = N; shape_out[1] = t.H; shape_out[2] = t.W; shape_out[3] = t.fmt != PL_F32 ? t.Ctf : t.C; }
     if (!out) return SD_OK;
     if (!h->bound) return fail(h, SD_ERR_STATE, "sd_bind_memory first");
-    const size_t numel = (size_t)N * t.H * t.W * (t.fmt ? t.Ctf : t.C);
+    const size_t numel = (size_t)N * t.H * t.W * (t.fmt != PL_F32 ? t.Ctf : t.C);
     if (numel > cap_floats) return fail(h, SD_ERR_INVALID, "output buffer too small");
     const char* abase = h->ws + (net == SD_NET_FCN8S ? h->o_fcn : h->o_mono);
-    if (t.fmt)      // split-bf16 planes -> f32
+    if (t.fmt != PL_F32)      // split planes -> f32
         HIPCHK(h, launch_unsplit(reinterpret_cast<const float*>(abase + t.offset), out, (long)N * t.H * t.W, t.C, t.Ctf, (size_t)p.images * t.H * t.W * t.C,
-                                 t.planar16 ? (size_t)p.images * t.H * t.W * 16 : 0, t.x3 ? -1 : t.f16, (hipStream_t)stream));
+                                 t.planar16 ? (size_t)p.images * t.H * t.W * 16 : 0, t.fmt, (hipStream_t)stream));
     else
         HIPCHK(h, hipMemcpyAsync(out, abase + t.offset, numel * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return SD_OK;

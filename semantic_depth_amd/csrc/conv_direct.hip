@@ -569,8 +569,8 @@ __global__ __launch_bounds__(512, (N16 && MT == 1) ? 2 : 1) void conv_direct_ker
         auto ep = [&](auto tag) {
             if constexpr (H2) { epilogue(tag, IntTag<3>{}); return; }           // (an HS layer writes HS planes, nothing else)
             else {
-                if constexpr (!N16) { if (p.out_f16 == 2) { epilogue(tag, IntTag<2>{}); return; } }
-                if (p.out_f16) epilogue(tag, IntTag<1>{}); else epilogue(tag, IntTag<0>{});
+                if constexpr (!N16) { if (p.out_fmt == PL_F16X2) { epilogue(tag, IntTag<2>{}); return; } }
+                if (p.out_fmt != PL_BF16X2) epilogue(tag, IntTag<1>{}); else epilogue(tag, IntTag<0>{});      // (PL_F16)
             }
         };
         if (p.act == ACT_RELU) ep(ActTag<ACT_RELU>{});
@@ -583,7 +583,7 @@ __global__ __launch_bounds__(512, (N16 && MT == 1) ? 2 : 1) void conv_direct_ker
 
 hipError_t launch_conv_direct(const ConvDirectParams& p, hipStream_t s) {
     if ((p.act == ACT_SIGMOID03 || p.nreal) && (p.Cout > 16 || p.nsplit != 1 || p.pool || (p.sw & SW_NO_N16))) return hipErrorInvalidValue;
-    if (p.out_f16 == 2 && p.Cout <= 16 && p.nsplit == 1 && !p.pool) return hipErrorInvalidValue;      // (the 16-wide form writes formats 0 and 1)
+    if (p.out_fmt == PL_F16X2 && p.Cout <= 16 && p.nsplit == 1 && !p.pool) return hipErrorInvalidValue;      // (the 16-wide form writes PL_BF16X2 and PL_F16)
     if (p.W % D_TW || p.Cout > 64 || p.Cout % 8 || p.nsplit < 1 || p.nsplit > 8 || (p.nsplit > 1 && p.Cout != 64)) return hipErrorInvalidValue;
     static int cus = 0;
     if (!cus) {
@@ -614,31 +614,24 @@ hipError_t launch_conv_direct(const ConvDirectParams& p, hipStream_t s) {
 // N16: 8-row tiles without an upsample, 16-row up-tiles behind one
 #define SD_DIRECT_N16(F16_, W1_, ...) do { if (up) SD_DIRECT_(1, 2, F16_, true, true, W1_, ##__VA_ARGS__); else SD_DIRECT_(1, 1, F16_, true, false, W1_, ##__VA_ARGS__); } while (0)
     if (p.fold) {               // upsample-folded upconv layers of SD_PREC_F16X2: source-resolution tiles, 16 tap matrices per chunk
-        if (p.f16 != 4 || p.out_f16 != 3 || !up || p.pool || n16) return hipErrorInvalidValue;
+        if (p.scheme != SC_HS || p.out_fmt != PL_HS || !up || p.pool || n16) return hipErrorInvalidValue;
         if (nb == 1) SD_DIRECT_(1, 2, true, false, true, false, true, true, true); else SD_DIRECT_(2, 2, true, false, true, false, true, true, true);
         return hipGetLastError();
     }
 #define SD_DIRECT(NB_, F16_, W1_) do { if (up) SD_DIRECT_(NB_, 2, F16_, false, true, W1_, false); else SD_DIRECT_(NB_, 2, F16_, false, false, W1_, false); } while (0)
-    if (p.f16 == 4) {           // SD_PREC_F16X2: fp16 hi + scaled lo x fp16 hi + lo weights, three products (every tile shape of the bf16 form)
-        if (p.out_f16 != 3) return hipErrorInvalidValue;
-        if (n16) SD_DIRECT_N16(true, false, true, true);
-        else if (nb == 1) SD_DIRECT_H2(1);
-        else SD_DIRECT_H2(2);
-    } else if (p.f16 == 3) {           // fp16 hi + lo input x w_hi: the 64-channel-pass form only (the planner asks for nothing else)
-        if (n16 || nb == 1 || up) return hipErrorInvalidValue;
-        SD_DIRECT_(2, 2, true, false, false, false, true);
-    } else if (p.f16 == 2) {           // fp16, ONE product
-        if (n16) SD_DIRECT_N16(true, true, false);
-        else if (nb == 1) SD_DIRECT(1, true, true);
-        else SD_DIRECT(2, true, true);
-    } else if (p.f16) {
-        if (n16) SD_DIRECT_N16(true, false, false);
-        else if (nb == 1) SD_DIRECT(1, true, false);
-        else SD_DIRECT(2, true, false);
-    } else {
-        if (n16) SD_DIRECT_N16(false, false, false);
-        else if (nb == 1) SD_DIRECT(1, false, false);
-        else SD_DIRECT(2, false, false);
+    switch (p.scheme) {
+        case SC_HS:             // every tile shape of the bf16 form
+            if (p.out_fmt != PL_HS) return hipErrorInvalidValue;
+            if (n16) SD_DIRECT_N16(true, false, true, true); else if (nb == 1) SD_DIRECT_H2(1); else SD_DIRECT_H2(2);
+            break;
+        case SC_F16XW:          // the 64-channel-pass form only (the planner asks for nothing else)
+            if (n16 || nb == 1 || up) return hipErrorInvalidValue;
+            SD_DIRECT_(2, 2, true, false, false, false, true);
+            break;
+        case SC_F16X1: if (n16) SD_DIRECT_N16(true, true, false); else if (nb == 1) SD_DIRECT(1, true, true); else SD_DIRECT(2, true, true); break;
+        case SC_F16W: if (n16) SD_DIRECT_N16(true, false, false); else if (nb == 1) SD_DIRECT(1, true, false); else SD_DIRECT(2, true, false); break;
+        case SC_BF16X2: if (n16) SD_DIRECT_N16(false, false, false); else if (nb == 1) SD_DIRECT(1, false, false); else SD_DIRECT(2, false, false); break;
+        default: return hipErrorInvalidValue;
     }
 #undef SD_DIRECT_N16
 #undef SD_DIRECT_H2
@@ -651,13 +644,19 @@ hipError_t launch_conv_direct(const ConvDirectParams& p, hipStream_t s) {
 // 16-wide MFMA form
 const char* conv_direct_kernel_name(const ConvDirectParams& p) {
     const bool n16 = p.Cout <= 16 && p.nsplit == 1 && !p.pool && !(p.sw & SW_NO_N16);
-    // f16w: fp16 activations x two fp16 weight planes (2 products); f16x1: fp16 x fp16 (1 product); f16w_x2: fp16 hi+lo x w_hi (2 products)
-    if (p.f16 == 4 && p.fold) return p.Cout <= 32 ? "conv_direct_hs_fold_kernel<1>" : "conv_direct_hs_fold_kernel<2>";
-    if (p.f16 == 4) return n16 ? "conv_direct_hs_kernel<1,n16>" : p.Cout <= 32 ? "conv_direct_hs_kernel<1,2>" : "conv_direct_hs_kernel<2,2>";
-    if (p.f16 == 3) return "conv_direct_f16w_x2_kernel<2,2>";
-    if (n16) return p.f16 == 2 ? "conv_direct_f16x1_kernel<1,n16>" : p.f16 ? "conv_direct_f16w_kernel<1,n16>" : "conv_direct_kernel<1,n16>";
-    if (p.Cout <= 32) return p.f16 == 2 ? "conv_direct_f16x1_kernel<1,2>" : p.f16 ? "conv_direct_f16w_kernel<1,2>" : "conv_direct_kernel<1,2>";
-    return p.f16 == 2 ? "conv_direct_f16x1_kernel<2,2>" : p.f16 ? "conv_direct_f16w_kernel<2,2>" : "conv_direct_kernel<2,2>";
+    static const char* const names[4][3] = {
+        {"conv_direct_kernel<1,n16>", "conv_direct_kernel<1,2>", "conv_direct_kernel<2,2>"},
+        {"conv_direct_f16w_kernel<1,n16>", "conv_direct_f16w_kernel<1,2>", "conv_direct_f16w_kernel<2,2>"},
+        {"conv_direct_f16x1_kernel<1,n16>", "conv_direct_f16x1_kernel<1,2>", "conv_direct_f16x1_kernel<2,2>"},
+        {"conv_direct_hs_kernel<1,n16>", "conv_direct_hs_kernel<1,2>", "conv_direct_hs_kernel<2,2>"}};
+    const int shape = n16 ? 0 : p.Cout <= 32 ? 1 : 2;
+    switch (p.scheme) {
+        case SC_HS: return p.fold ? (p.Cout <= 32 ? "conv_direct_hs_fold_kernel<1>" : "conv_direct_hs_fold_kernel<2>") : names[3][shape];
+        case SC_F16XW: return "conv_direct_f16w_x2_kernel<2,2>";
+        case SC_F16X1: return names[2][shape];
+        case SC_F16W: return names[1][shape];
+        default: return names[0][shape];
+    }
 }
 
 }  // namespace sd

@@ -532,7 +532,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
 }
 
 hipError_t launch_conv_direct3(const ConvDirectParams& p, hipStream_t s) {
-    if (p.act == ACT_SIGMOID03 || p.nreal || p.out_planar16 || p.f16 || p.out_f16) return hipErrorInvalidValue;   // (heads run as small-N kernels)
+    if (p.act == ACT_SIGMOID03 || p.nreal || p.out_planar16 || p.scheme != SC_BF16X3 || p.out_fmt != PL_BF16X3) return hipErrorInvalidValue;   // (heads run as small-N kernels)
     if (p.W % T3_TW || p.Cout > 64 || p.Cout % 8 || p.nsplit < 1 || p.nsplit > 8 || (p.nsplit > 1 && p.Cout != 64)) return hipErrorInvalidValue;
     if (p.pool && ((p.H & 1) || (p.W & 1))) return hipErrorInvalidValue;
     static int cus = 0;

@@ -23,10 +23,10 @@ int conv_dma_variant(const ConvParams& p) {
     // 256 x 256 (one workgroup per CU): 128 flop per byte of L2 -> LDS DMA, the resource the long-K GEMMs run against.  The one-product
     // form of 128 x 256 / 256 x 128 fits TWO workgroups per CU (72 KB of ring, 124 VGPRs): one's epilogue and pipeline fill run under
     // the other's k-loop, which wins below ~32 k-tiles (measured: K <= 640 +5..14 %, K = 768..1280 equal, K >= 1536 and fc6 -2..4 %)
-    const bool shortk = p.f16 == 2 && p.Kpad < 1024;
-    if (p.x3 && (p.pool || p.out_planar16)) return 0;         // (bf16 x 3: plain outputs only)
-    if (p.fold && p.x3) return 0;                             // (folded GEMMs of bf16 x 3: conv_dma3.hip)
-    if (big && !p.x3 && !shortk && !p.pool && p.Cout % 256 == 0 && ((M + 255) / 256) * (p.Cout / 256) * (p.fold ? 4 : 1) >= 512) return 5;
+    const bool x3 = p.scheme == SC_BF16X3, shortk = p.scheme == SC_F16X1 && p.Kpad < 1024;
+    if (x3 && (p.pool || p.out_planar16)) return 0;           // (bf16 x 3: plain outputs only)
+    if (p.fold && x3) return 0;                               // (folded GEMMs of bf16 x 3: conv_dma3.hip)
+    if (big && !x3 && !shortk && !p.pool && p.Cout % 256 == 0 && ((M + 255) / 256) * (p.Cout / 256) * (p.fold ? 4 : 1) >= 512) return 5;
     if (p.Cout % 256 == 0 && ((M + 127) / 128) * (p.Cout / 256) >= thr) return 1;     // 128 x 256
     if (p.Cout % 128 == 0 && ((M + 255) / 256) * (p.Cout / 128) >= thr) return 2;     // 256 x 128
     if (p.Cout % 64 == 0 && p.Cout % 128 != 0 && ((M + 255) / 256) * (p.Cout / 64) >= thr) return 3;      // 256 x 64
@@ -41,27 +41,30 @@ hipError_t launch_conv_dma(const ConvParams& p, hipStream_t s) {
     else if (v == 2) launch_dma_v2(p, M, s);
     else if (v == 3) launch_dma_v3(p, M, s);
     else if (v == 4) launch_dma_v4(p, M, s);
-    else if (v == 5 && !p.x3) launch_dma_v5(p, M, s);
+    else if (v == 5 && p.scheme != SC_BF16X3) launch_dma_v5(p, M, s);
     else return hipErrorInvalidValue;
     return hipGetLastError();
 }
 
 const char* conv_dma_kernel_name(const ConvParams& p) {
-    // f16w: fp16 activations x two fp16 weight planes (2 products); f16x1: fp16 x fp16 (1 product)
     static const char* const names3[5] = {"conv_dma_x3_kernel<2,4,2,2>", "conv_dma_x3_kernel<4,2,2,2>", "conv_dma_x3_kernel<4,2,2,1>", "conv_dma_x3_kernel<8,1,1,1>",
                                           "conv_dma_x3_kernel<2,4,2,2>"};
-    if (p.x3) { const int v3 = conv_dma_variant(p); return names3[v3 >= 1 && v3 <= 5 ? v3 - 1 : 2]; }
     static const char* const names[3][5] = {
         {"conv_dma_kernel<2,4,2,2>", "conv_dma_kernel<4,2,2,2>", "conv_dma_kernel<4,2,2,1>", "conv_dma_kernel<8,1,1,1>", "conv_dma_kernel<2,4,4,2>"},
         {"conv_dma_f16w_kernel<2,4,2,2>", "conv_dma_f16w_kernel<4,2,2,2>", "conv_dma_f16w_kernel<4,2,2,1>", "conv_dma_f16w_kernel<8,1,1,1>",
          "conv_dma_f16w_kernel<2,4,4,2>"},
         {"conv_dma_f16x1_kernel<2,4,2,2>", "conv_dma_f16x1_kernel<4,2,2,2>", "conv_dma_f16x1_kernel<4,2,2,1>", "conv_dma_f16x1_kernel<8,1,1,1>",
          "conv_dma_f16x1_kernel<2,4,4,2>"}};
-    const int v = conv_dma_variant(p);
     static const char* const namesh[5] = {"conv_dma_hs_kernel<2,4,2,2>", "conv_dma_hs_kernel<4,2,2,2>", "conv_dma_hs_kernel<4,2,2,1>", "conv_dma_hs_kernel<8,1,1,1>",
                                           "conv_dma_hs_kernel<2,4,4,2>"};
-    if (p.f16 == 4) return namesh[v >= 1 && v <= 5 ? v - 1 : 2];
-    return names[p.f16 == 2 ? 2 : (p.f16 ? 1 : 0)][v >= 1 && v <= 5 ? v - 1 : 2];
+    const int v = conv_dma_variant(p), i = v >= 1 && v <= 5 ? v - 1 : 2;
+    switch (p.scheme) {
+        case SC_BF16X3: return names3[i];
+        case SC_HS: return namesh[i];
+        case SC_F16X1: return names[2][i];
+        case SC_F16W: return names[1][i];
+        default: return names[0][i];
+    }
 }
 
 }  // namespace sd

@@ -609,12 +609,12 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
 int conv_dma3_mode(const ConvParams& p);
 // layers the 256 x 256 phased block takes: bf16 x 3, all-vec K axis, Cout a multiple of 256 and enough blocks to occupy the chip
 bool conv_dma3_eligible(const ConvParams& p) {
-    if (!(p.x3 || p.f16 == 4) || !p.vec || !p.zero16 || p.pool || p.out_planar16 || p.residual || p.Cout % G3_BN || p.Kpad < 64 || p.CoutPad != p.Cout) return false;
+    if ((p.scheme != SC_BF16X3 && p.scheme != SC_HS) || !p.vec || !p.zero16 || p.pool || p.out_planar16 || p.residual || p.Cout % G3_BN || p.Kpad < 64 || p.CoutPad != p.Cout) return false;
     // SD_PREC_F16X2: measured against the two-stage block of conv_dma.hip (profiles/r05_hs_phased_gemm_ab.txt), the two-phase ring wins on the 1x1 layers (fc7
     // 1.50 -> 1.29 ms, the res2 / res5 block tails 3-12 %) and -- since a piece's address arithmetic is formed once per k-tile -- on the row-grouped fc6
     // (6.93 -> 6.50 ms: it also skips the taps on padding rows), and loses on the small strided 3x3 of res4_6 (0.135 -> 0.178): the 1x1 layers and fc6 only
     // (the rule must not look at the call: the k x k stride-1 single-source layers -- fc6 --, row-grouped or not)
-    if (p.f16 == 4 && conv_dma3_mode(p) != 1 && !(p.kh >= 3 && p.stride == 1 && !p.fold && p.noup)) return false;
+    if (p.scheme == SC_HS && conv_dma3_mode(p) != 1 && !(p.kh >= 3 && p.stride == 1 && !p.fold && p.noup)) return false;
     if (p.fold) return true;                                   // (a folded layer always runs here when it can: its results must not depend on the batch)
     if (p.sw & SW_NO_DMA3) return false;                       // (A/B switch of the handle)
     // enough tiles to occupy the chip -- counted on a FULL pass of the engine (ConvParams::Nmax), not on the frames of this call: this block and conv_dma.hip's
@@ -629,6 +629,14 @@ bool conv_dma3_eligible(const ConvParams& p) {
 // 3x3: precomputed pixel offset + scalar tap offset), 0 = the general gather
 int conv_dma3_mode(const ConvParams& p) { return (p.flat && !p.fold && !p.rowgrp) ? 1 : p.noup ? 2 : 0; }
 
+// one bucket per form for the bench line; the per-layer listing of SEMDEPTH_PROFILE_VERBOSE names the gather variant
+const char* conv_dma3_kernel_name(const ConvParams& p) {
+    static const char* const x3[3] = {"conv_dma3_kernel<0>", "conv_dma3_kernel<1>", "conv_dma3_kernel<2>"};
+    static const char* const hs[3] = {"conv_dma_hs_phased_kernel<0>", "conv_dma_hs_phased_kernel<1>", "conv_dma_hs_phased_kernel<2>"};
+    if (p.sw & SW_PROFILE_VERBOSE) return (p.scheme == SC_HS ? hs : x3)[conv_dma3_mode(p)];
+    return p.scheme == SC_HS ? "conv_dma_hs_phased_kernel" : "conv_dma3_kernel";
+}
+
 hipError_t launch_conv_dma3(const ConvParams& p, hipStream_t s) {
     if (!conv_dma3_eligible(p)) return hipErrorInvalidValue;
     const long M = (long)p.N * p.Hout * p.Wout;
@@ -640,11 +648,13 @@ hipError_t launch_conv_dma3(const ConvParams& p, hipStream_t s) {
     const bool s16 = !(p.sw & SW_MFMA32);
 #define SD_G3(MODE_, HS_) do { if (s16) hipLaunchKernelGGL((conv_dma3_kernel<MODE_, HS_, !(HS_) || (MODE_) == 1>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN); \
                                 else hipLaunchKernelGGL((conv_dma3_kernel<MODE_, HS_, false>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN); } while (0)
-    if (p.f16 == 4) {           // SD_PREC_F16X2: the two-plane, two-phase form
-        if (mode == 1) SD_G3(1, true); else if (mode == 2) SD_G3(2, true); else SD_G3(0, true);
-        return hipGetLastError();
+#define SD_G3_MODE(HS_) do { if (mode == 1) SD_G3(1, HS_); else if (mode == 2) SD_G3(2, HS_); else SD_G3(0, HS_); } while (0)
+    switch (p.scheme) {
+        case SC_HS: SD_G3_MODE(true); break;         // the two-plane, two-phase form
+        case SC_BF16X3: SD_G3_MODE(false); break;
+        default: return hipErrorInvalidValue;
     }
-    if (mode == 1) SD_G3(1, false); else if (mode == 2) SD_G3(2, false); else SD_G3(0, false);
+#undef SD_G3_MODE
 #undef SD_G3
     return hipGetLastError();
 }

@@ -554,7 +554,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (F16 && MT * NT <= 4) ? 4 :
     };
     auto ep = [&](auto tag) {
         if constexpr (H2) epilogue(tag, IntTag<3>{});          // (an HS layer writes HS planes, nothing else)
-        else { if (p.out_f16) epilogue(tag, IntTag<1>{}); else epilogue(tag, IntTag<0>{}); }
+        else { if (p.out_fmt != PL_BF16X2) epilogue(tag, IntTag<1>{}); else epilogue(tag, IntTag<0>{}); }     // (PL_F16)
     };
     if (p.act == ACT_RELU) ep(ActTag<ACT_RELU>{});
     else if (p.act == ACT_ELU) ep(ActTag<ACT_ELU>{});
@@ -566,33 +566,23 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (F16 && MT * NT <= 4) ? 4 :
 template <int WM, int WN, int MT, int NT, int S3, int S2, int S1>
 void launch_dma_variant(const ConvParams& p, long M, hipStream_t s) {
     const int tilesM = (int)((M + WM * MT * 32 - 1) / (WM * MT * 32)), tilesN = p.Cout / (WN * NT * 32);
-    const dim3 grid((unsigned)(tilesM * tilesN * ((p.fold && !p.x3) ? 4 : 1))), block(64 * WM * WN);
-    if (p.fold && p.x3) return;                                // (folded GEMMs: the two-plane forms here, bf16 x 3 on conv_dma3.hip; the caller sees hipErrorInvalidValue)
+    const bool x3 = p.scheme == SC_BF16X3;
+    const dim3 grid((unsigned)(tilesM * tilesN * ((p.fold && !x3) ? 4 : 1))), block(64 * WM * WN);
+    if (p.fold && x3) return;                                  // (folded GEMMs: the two-plane forms here, bf16 x 3 on conv_dma3.hip; the caller sees hipErrorInvalidValue)
     const int mode = p.simple;
     constexpr bool x3_fits = 2 * 12 * (WM * MT * 32 + WN * NT * 32) * 16 <= 160 * 1024;
-    if constexpr (x3_fits) if (p.x3) {               // bf16 x 3: two stages
-        if (mode == 2) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 2, 2, false, false, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-        else if (mode == 1) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 1, 2, false, false, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-        else hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 0, 2, false, false, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-        return;
+    // template arguments after MODE: ring depth, F16 input, one product, bf16 x 3, HS
+#define SD_DMA(S_, ...) do { if (mode == 2) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 2, S_, ##__VA_ARGS__>), grid, block, 0, s, p, (int)M, tilesM, tilesN); \
+                             else if (mode == 1) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 1, S_, ##__VA_ARGS__>), grid, block, 0, s, p, (int)M, tilesM, tilesN); \
+                             else hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 0, S_, ##__VA_ARGS__>), grid, block, 0, s, p, (int)M, tilesM, tilesN); } while (0)
+    switch (p.scheme) {
+        case SC_BF16X3: if constexpr (x3_fits) SD_DMA(2, false, false, true); break;       // two stages
+        case SC_HS: SD_DMA(S3, false, false, false, true); break;                          // the three-product stage
+        case SC_F16X1: SD_DMA(S1, true, true); break;
+        case SC_F16W: SD_DMA(S2, true); break;
+        default: SD_DMA(S3); break;
     }
-    if (p.f16 == 4) {                     // SD_PREC_F16X2: the three-product stage, fp16 HS planes
-        if (mode == 2) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 2, S3, false, false, false, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-        else if (mode == 1) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 1, S3, false, false, false, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-        else hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 0, S3, false, false, false, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-        return;
-    }
-    if (p.f16 == 2) {
-        if (mode == 2) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 2, S1, true, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-        else if (mode == 1) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 1, S1, true, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-        else hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 0, S1, true, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-    } else if (p.f16) {
-        if (mode == 2) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 2, S2, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-        else if (mode == 1) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 1, S2, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-        else hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 0, S2, true>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-    } else if (mode == 2) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 2, S3>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-    else if (mode == 1) hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 1, S3>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
-    else hipLaunchKernelGGL((conv_dma_kernel<WM, WN, MT, NT, 0, S3>), grid, block, 0, s, p, (int)M, tilesM, tilesN);
+#undef SD_DMA
 }
 
 

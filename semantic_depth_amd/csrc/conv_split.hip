@@ -123,14 +123,14 @@ __device__ __forceinline__ void split_epilogue_x3(f32x16 (&acc)[MT][NT], unsigne
 }
 template <int MT, int NT, bool F16, bool H2 = false>
 __device__ __forceinline__ void split_epilogue(f32x16 (&acc)[MT][NT], unsigned char* slab, const ConvParams& p, int m0, int n0, int M, int lane) {
-    // the template's F16 is the INPUT format of the kernel; the output planes follow p.out_f16 (the consumers' format)
+    // the template's F16 is the INPUT format of the kernel; the output planes follow p.out_fmt (the consumers' format)
     if constexpr (H2) {
         if (p.act == ACT_RELU) split_epilogue_act<ACT_RELU, MT, NT, 3>(acc, slab, p, m0, n0, M, lane);
         else if (p.act == ACT_ELU) split_epilogue_act<ACT_ELU, MT, NT, 3>(acc, slab, p, m0, n0, M, lane);
         else split_epilogue_act<ACT_NONE, MT, NT, 3>(acc, slab, p, m0, n0, M, lane);
         return;
     }
-    if (p.out_f16) {
+    if (p.out_fmt != PL_BF16X2) {        // (PL_F16)
         if (p.act == ACT_RELU) split_epilogue_act<ACT_RELU, MT, NT, 1>(acc, slab, p, m0, n0, M, lane);
         else if (p.act == ACT_ELU) split_epilogue_act<ACT_ELU, MT, NT, 1>(acc, slab, p, m0, n0, M, lane);
         else split_epilogue_act<ACT_NONE, MT, NT, 1>(acc, slab, p, m0, n0, M, lane);
@@ -331,7 +331,7 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void conv_split_kernel(cons
 #pragma unroll
             for (int pr = 0; pr < NPR; ++pr) {
                 if (!X3 && F16 && pr == 1) continue;                      // fp16 activations: no lo plane, products x*w_lo and x*w_hi
-                if (!X3 && F16 && pr == 0 && p.f16 == 2) continue;        // one-product layer (':1'): x*w_hi only, as conv_dma / conv_direct W1
+                if (!X3 && F16 && pr == 0 && p.scheme == SC_F16X1) continue;        // one-product layer (':1'): x*w_hi only, as conv_dma / conv_direct W1
                 const int xi = X3 ? xp3[pr] : xp2[pr], wi = X3 ? wp3[pr] : wp2[pr];
 #pragma unroll
                 for (int b = 0; b < NT; ++b) {
@@ -363,25 +363,16 @@ static hipError_t launch_scfg(const ConvParams& p, hipStream_t s) {
     const int tilesM = (int)((M + T::BM - 1) / T::BM);
     const int tilesN = (p.Cout + T::BN - 1) / T::BN;
     dim3 grid((unsigned)(tilesM * tilesN));
-    if (p.x3) {
-        if (p.vec)
-            hipLaunchKernelGGL((conv_split_kernel<WAVES_M, WAVES_N, MT, NT, true, false, true>), grid, dim3(T::NTHR), 0, s, p, (int)M, tilesM, tilesN);
-        else
-            hipLaunchKernelGGL((conv_split_kernel<WAVES_M, WAVES_N, MT, NT, false, false, true>), grid, dim3(T::NTHR), 0, s, p, (int)M, tilesM, tilesN);
-    } else if (p.f16 == 4) {
-        if (p.vec)
-            hipLaunchKernelGGL((conv_split_kernel<WAVES_M, WAVES_N, MT, NT, true, false, false, true>), grid, dim3(T::NTHR), 0, s, p, (int)M, tilesM, tilesN);
-        else
-            hipLaunchKernelGGL((conv_split_kernel<WAVES_M, WAVES_N, MT, NT, false, false, false, true>), grid, dim3(T::NTHR), 0, s, p, (int)M, tilesM, tilesN);
-    } else if (p.f16) {
-        if (p.vec)
-            hipLaunchKernelGGL((conv_split_kernel<WAVES_M, WAVES_N, MT, NT, true, true>), grid, dim3(T::NTHR), 0, s, p, (int)M, tilesM, tilesN);
-        else
-            hipLaunchKernelGGL((conv_split_kernel<WAVES_M, WAVES_N, MT, NT, false, true>), grid, dim3(T::NTHR), 0, s, p, (int)M, tilesM, tilesN);
-    } else if (p.vec)
-        hipLaunchKernelGGL((conv_split_kernel<WAVES_M, WAVES_N, MT, NT, true>), grid, dim3(T::NTHR), 0, s, p, (int)M, tilesM, tilesN);
-    else
-        hipLaunchKernelGGL((conv_split_kernel<WAVES_M, WAVES_N, MT, NT, false>), grid, dim3(T::NTHR), 0, s, p, (int)M, tilesM, tilesN);
+#define SD_SPLIT(...) do { if (p.vec) hipLaunchKernelGGL((conv_split_kernel<WAVES_M, WAVES_N, MT, NT, true, ##__VA_ARGS__>), grid, dim3(T::NTHR), 0, s, p, (int)M, tilesM, tilesN); \
+                          else hipLaunchKernelGGL((conv_split_kernel<WAVES_M, WAVES_N, MT, NT, false, ##__VA_ARGS__>), grid, dim3(T::NTHR), 0, s, p, (int)M, tilesM, tilesN); } while (0)
+    switch (p.scheme) {         // (template arguments after VEC: F16 input, bf16 x 3, HS)
+        case SC_BF16X3: SD_SPLIT(false, true); break;
+        case SC_HS: SD_SPLIT(false, false, true); break;
+        case SC_F16W: case SC_F16X1: SD_SPLIT(true); break;
+        case SC_BF16X2: SD_SPLIT(); break;
+        default: return hipErrorInvalidValue;
+    }
+#undef SD_SPLIT
     return hipGetLastError();
 }
 
@@ -414,31 +405,21 @@ hipError_t launch_conv_split(const ConvParams& p, hipStream_t s) {
 }
 
 const char* conv_split_kernel_name(const ConvParams& p) {
-    if (p.x3) {
-        switch (split_variant(p)) {
-            case 0:  return "conv_split_x3_kernel<2,4,2,2>";
-            case 1:  return "conv_split_x3_kernel<4,2,2,2>";
-            case 2:  return "conv_split_x3_kernel<2,2,2,2>";
-            case 3:  return "conv_split_x3_kernel<4,1,2,2>";
-            default: return "conv_split_x3_kernel<4,1,2,1>";
-        }
-    }
-    if (p.f16 == 4) return "conv_split_hs_kernel";
-    if (p.f16) {
-        switch (split_variant(p)) {
-            case 0:  return "conv_split_f16w_kernel<2,4,2,2>";
-            case 1:  return "conv_split_f16w_kernel<4,2,2,2>";
-            case 2:  return "conv_split_f16w_kernel<2,2,2,2>";
-            case 3:  return "conv_split_f16w_kernel<4,1,2,2>";
-            default: return "conv_split_f16w_kernel<4,1,2,1>";
-        }
-    }
-    switch (split_variant(p)) {
-        case 0:  return p.vec ? "conv_split_kernel<2,4,2,2,true>" : "conv_split_kernel<2,4,2,2,false>";
-        case 1:  return p.vec ? "conv_split_kernel<4,2,2,2,true>" : "conv_split_kernel<4,2,2,2,false>";
-        case 2:  return p.vec ? "conv_split_kernel<2,2,2,2,true>" : "conv_split_kernel<2,2,2,2,false>";
-        case 3:  return p.vec ? "conv_split_kernel<4,1,2,2,true>" : "conv_split_kernel<4,1,2,2,false>";
-        default: return p.vec ? "conv_split_kernel<4,1,2,1,true>" : "conv_split_kernel<4,1,2,1,false>";
+    static const char* const x3[5] = {"conv_split_x3_kernel<2,4,2,2>", "conv_split_x3_kernel<4,2,2,2>", "conv_split_x3_kernel<2,2,2,2>",
+                                      "conv_split_x3_kernel<4,1,2,2>", "conv_split_x3_kernel<4,1,2,1>"};
+    static const char* const f16w[5] = {"conv_split_f16w_kernel<2,4,2,2>", "conv_split_f16w_kernel<4,2,2,2>", "conv_split_f16w_kernel<2,2,2,2>",
+                                        "conv_split_f16w_kernel<4,1,2,2>", "conv_split_f16w_kernel<4,1,2,1>"};
+    static const char* const bf16[2][5] = {
+        {"conv_split_kernel<2,4,2,2,false>", "conv_split_kernel<4,2,2,2,false>", "conv_split_kernel<2,2,2,2,false>", "conv_split_kernel<4,1,2,2,false>",
+         "conv_split_kernel<4,1,2,1,false>"},
+        {"conv_split_kernel<2,4,2,2,true>", "conv_split_kernel<4,2,2,2,true>", "conv_split_kernel<2,2,2,2,true>", "conv_split_kernel<4,1,2,2,true>",
+         "conv_split_kernel<4,1,2,1,true>"}};
+    const int v = split_variant(p);
+    switch (p.scheme) {
+        case SC_BF16X3: return x3[v];
+        case SC_HS: return "conv_split_hs_kernel";
+        case SC_F16W: case SC_F16X1: return f16w[v];
+        default: return bf16[p.vec ? 1 : 0][v];
     }
 }
 

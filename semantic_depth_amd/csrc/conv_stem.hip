@@ -224,7 +224,7 @@ __global__ __launch_bounds__(512, 1) void conv_stem_kernel(const ConvParams p) {
         };
         auto ep = [&](auto tag) {
             if constexpr (H2) epilogue(tag, IntTag<3>{});
-            else { if (p.out_f16) epilogue(tag, IntTag<1>{}); else epilogue(tag, IntTag<0>{}); }
+            else { if (p.out_fmt != PL_BF16X2) epilogue(tag, IntTag<1>{}); else epilogue(tag, IntTag<0>{}); }     // (PL_F16; X3 ignores the tag)
         };
         if (p.act == ACT_RELU) ep(ActTag<ACT_RELU>{});
         else if (p.act == ACT_ELU) ep(ActTag<ACT_ELU>{});
@@ -240,9 +240,18 @@ bool conv_stem_eligible(const ConvParams& p) {
     if (p.out_planar16 && p.Cout % 16) return false;
     const int rw = p.stride == 1 ? 2 : 1, th = 8 * rw;
     const int ih = (th - 1) * p.stride + p.kh, iw = (ST_TW - 1) * p.stride + p.kh;
-    const int npl = p.x3 ? 3 : 2, nb = p.Cout / 32;
+    const int npl = p.scheme == SC_BF16X3 ? 3 : 2, nb = p.Cout / 32;
     const size_t lds = (size_t)npl * ST_MAXPIX * 8 + (size_t)(p.Kpad / 8) * p.Cout * 16 * npl + (size_t)8 * 32 * (64 * nb + 16);
     return ih * iw <= ST_MAXPIX && lds + 512 <= 160 * 1024 && (p.kh * p.kw * 4 + 15) / 16 <= 32 && !(p.sw & SW_NO_STEM);      // (+ the tap table)
+}
+
+const char* conv_stem_kernel_name(const ConvParams& p) {
+    switch (p.scheme) {
+        case SC_BF16X3: return "conv_stem_x3_kernel";
+        case SC_HS: return "conv_stem_hs_kernel";
+        case SC_F16W: case SC_F16X1: return "conv_stem_f16w_kernel";
+        default: return "conv_stem_kernel";
+    }
 }
 
 hipError_t launch_conv_stem(const ConvParams& p, hipStream_t s) {
@@ -256,7 +265,7 @@ hipError_t launch_conv_stem(const ConvParams& p, hipStream_t s) {
     }
     const int nb = p.Cout / 32, rw = p.stride == 1 ? 2 : 1;
     const int tiles = (p.Wout / ST_TW) * ((p.Hout + 8 * rw - 1) / (8 * rw)) * p.N;
-    const int npl = p.x3 ? 3 : 2;
+    const int npl = p.scheme == SC_BF16X3 ? 3 : 2;
     const size_t wbytes = (size_t)(p.Kpad / 8) * p.Cout * 16 * npl;
     const size_t lds = (size_t)npl * ST_MAXPIX * 8 + wbytes + (size_t)8 * 32 * (64 * nb + 16);
     if (lds + 512 > 160 * 1024) return hipErrorInvalidValue;
@@ -268,19 +277,16 @@ hipError_t launch_conv_stem(const ConvParams& p, hipStream_t s) {
         if (!attr) { hipFuncSetAttribute((const void*)conv_stem_kernel<NB_, RW_, F_, ##__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512); attr = true; } \
         hipLaunchKernelGGL((conv_stem_kernel<NB_, RW_, F_, ##__VA_ARGS__>), grid, dim3(512), lds, s, p);                \
     } while (0)
-    if (p.x3) {
-        if (nb == 1 && rw == 1) SD_STEM(1, 1, false, true); else if (nb == 1) SD_STEM(1, 2, false, true);
-        else if (rw == 1) SD_STEM(2, 1, false, true); else SD_STEM(2, 2, false, true);
-    } else if (p.f16 == 4) {
-        if (nb == 1 && rw == 1) SD_STEM(1, 1, false, false, true); else if (nb == 1) SD_STEM(1, 2, false, false, true);
-        else if (rw == 1) SD_STEM(2, 1, false, false, true); else SD_STEM(2, 2, false, false, true);
-    } else if (p.f16) {
-        if (nb == 1 && rw == 1) SD_STEM(1, 1, true); else if (nb == 1) SD_STEM(1, 2, true);
-        else if (rw == 1) SD_STEM(2, 1, true); else SD_STEM(2, 2, true);
-    } else {
-        if (nb == 1 && rw == 1) SD_STEM(1, 1, false); else if (nb == 1) SD_STEM(1, 2, false);
-        else if (rw == 1) SD_STEM(2, 1, false); else SD_STEM(2, 2, false);
+#define SD_STEM_ALL(...) do { if (nb == 1 && rw == 1) SD_STEM(1, 1, __VA_ARGS__); else if (nb == 1) SD_STEM(1, 2, __VA_ARGS__); \
+                              else if (rw == 1) SD_STEM(2, 1, __VA_ARGS__); else SD_STEM(2, 2, __VA_ARGS__); } while (0)
+    switch (p.scheme) {         // (template arguments after RW: F16 input, bf16 x 3, HS)
+        case SC_BF16X3: SD_STEM_ALL(false, true); break;
+        case SC_HS: SD_STEM_ALL(false, false, true); break;
+        case SC_F16W: case SC_F16X1: SD_STEM_ALL(true); break;
+        case SC_BF16X2: SD_STEM_ALL(false); break;
+        default: return hipErrorInvalidValue;
     }
+#undef SD_STEM_ALL
 #undef SD_STEM
     return hipGetLastError();
 }

@@ -345,8 +345,12 @@ hipError_t launch_dec_tail1(const DecTailParams& p, hipStream_t s) {
     }
     const int tiles = ((p.W + DT_TW - 1) / DT_TW) * (p.H / DT_TH) * p.N;
     const int wgs = cus - p.reserve_cus > 0 ? cus - p.reserve_cus : 1;
-    if (p.hs) hipLaunchKernelGGL(dec_tail1_kernel<true>, dim3((unsigned)(tiles < wgs ? tiles : wgs)), dim3(512), 0, s, p);
-    else hipLaunchKernelGGL(dec_tail1_kernel<false>, dim3((unsigned)(tiles < wgs ? tiles : wgs)), dim3(512), 0, s, p);
+    const dim3 grid((unsigned)(tiles < wgs ? tiles : wgs));
+    switch (p.scheme) {
+        case SC_HS: hipLaunchKernelGGL(dec_tail1_kernel<true>, grid, dim3(512), 0, s, p); break;
+        case SC_BF16X3: hipLaunchKernelGGL(dec_tail1_kernel<false>, grid, dim3(512), 0, s, p); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

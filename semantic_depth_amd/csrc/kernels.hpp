@@ -25,6 +25,30 @@ bool sd_disabled(const char* what);   // plan.cpp: is `what` in SEMDEPTH_DISABLE
 
 enum Act { ACT_NONE = 0, ACT_RELU = 1, ACT_ELU = 2, ACT_SIGMOID03 = 3 /* 0.3*sigmoid, monodepth get_disp */ };
 
+// Plane format of an activation tensor: what a kernel reads or writes (the arithmetic of each form is in split_fmt.hpp).  The split forms are
+// 16-bit planes at element offsets 0, plane and 2 * plane.  The values are the SPLIT / IN_SPLIT template arguments of the ops_misc.hip kernels.
+//   PL_F32     f32 NHWC
+//   PL_BF16X2  bf16 hi + lo planes (SD_PREC_BF16X2 / MIXED / PLAN)
+//   PL_F16     ONE fp16 plane (precision plan: the input of the fp16 layers)
+//   PL_F16X2   fp16 hi + lo planes (precision plan: the input of the ':x' layers, written by a direct conv's epilogue only)
+//   PL_BF16X3  bf16 hi + mid + lo planes (SD_PREC_BF16X3)
+//   PL_HS      fp16 hi + a lo plane scaled by 2^11 (SD_PREC_F16X2, split_fmt.hpp "HS")
+enum Planes : int { PL_F32 = 0, PL_BF16X2 = 1, PL_F16 = 2, PL_F16X2 = 3, PL_BF16X3 = 4, PL_HS = 5 };
+constexpr int plane_count(Planes f) { return f == PL_BF16X3 ? 3 : (f == PL_F32 || f == PL_F16) ? 1 : 2; }
+constexpr int elem_bytes(Planes f) { return f == PL_F32 ? 4 : 2 * plane_count(f); }
+
+// Product scheme of a conv layer: its input planes x its weight planes, and the MFMA products it issues per product.
+//   SC_F32     exact f32 MFMA (conv_igemm.hip)
+//   SC_BF16X2  PL_BF16X2 x bf16 (w_hi, w_lo): three products
+//   SC_F16W    PL_F16 x fp16 (w_hi, w_lo): two products (precision plan)
+//   SC_F16X1   PL_F16 x fp16 w_hi: one product, plain fp16 (plan ':1')
+//   SC_F16XW   PL_F16X2 x fp16 w_hi: two products (plan ':x', direct 3x3 layers only)
+//   SC_BF16X3  PL_BF16X3 x three bf16 weight planes: six products
+//   SC_HS      PL_HS x fp16 hi + lo of w * 2^k: three products, the accumulator scaled by `alpha` = 2^-k
+// SC_BF16X2 < SC_F16W < SC_F16X1 is the precision plan's order: a layer it names twice takes the form with fewer products (plan.cpp).
+enum Scheme : int { SC_F32 = 0, SC_BF16X2 = 1, SC_F16W = 2, SC_F16X1 = 3, SC_F16XW = 4, SC_BF16X3 = 5, SC_HS = 6 };
+constexpr bool plan_f16(Scheme s) { return s == SC_F16W || s == SC_F16X1 || s == SC_F16XW; }    // the precision plan's fp16 forms
+
 // ---------------------------------------------------------------------------------------------
 // implicit-GEMM convolution on the f32 MFMA (conv_igemm.hip)
 // ---------------------------------------------------------------------------------------------
@@ -61,11 +85,9 @@ struct ConvParams {
     int Nmax;          // split engine: images of a full chunk (plane stride of a source = Nmax*H*W*C elements)
     const void* src0;  // first source tensor (hi plane) and the element offset of its lo plane: conv_stem.hip reads it directly
     size_t src0_plane;
-    int f16;           // 1: the INPUT is ONE fp16 plane and the weights two fp16 planes (2 MFMA products, split_fmt.hpp); 2: the same
-                       // input and w_hi only (1 MFMA product: plain fp16 x fp16; conv_dma / conv_direct, the others run the 2-product form)
-                       // 4 (SD_PREC_F16X2): fp16 hi + SCALED lo input planes x fp16 hi + lo weights, THREE products, `alpha` applied (split_fmt.hpp "HS")
-    int out_f16;       // OUTPUT split planes are fp16 (the format the consumers of the output tensor compute in); 3 = fp16 hi + scaled lo (HS)
-    float alpha;       // f16 == 4: 1 / WeightSlot::wscale = 2^-k of the layer's weight scale: out = act(acc * alpha + bias)
+    Scheme scheme;     // product scheme (conv_dma / conv_direct run SC_F16X1 as one product, the others as SC_F16W)
+    Planes out_fmt;    // format of the output planes (the format the consumers of the output tensor compute in)
+    float alpha;       // SC_HS: 1 / WeightSlot::wscale = 2^-k of the layer's weight scale: out = act(acc * alpha + bias)
     int out_planar16;  // conv_stem.hip: write the output as Cout/16 sub-planes of 16 channels (TensorDesc::planar16)
     int pool;          // conv_dma.hip: output pixels are walked in 2x2-window-major order and the epilogue max-pools each
                        // window: out is [N,Hout/2,Wout/2,Cout]
@@ -76,7 +98,9 @@ struct ConvParams {
     int reserve_cus;   // persistent launches use (CUs - reserve_cus) workgroups: the CUs left free take the per-frame tail of the previous step
                        // that runs beside the networks on a side stream (sd_set_reserved_cus; 0 = every CU)
     unsigned long long* sat;   // DEVICE counter of fp16-saturated output values (split_fmt.hpp sat_report; sd_saturation_count)
-    int x3;            // 1: bf16 x 3 planes in, out and in the weights (SD_PREC_BF16X3: six MFMA products per product, split_fmt.hpp)
+    int fold;          // 1 (conv_dma3.hip): upsample-folded 3x3 conv (OpDesc::fold).  Hout x Wout are the SOURCE dims (the GEMM's pixel space), the
+                       // grid carries four parities, parity q = 2 py + px reads weight rows [q Kpad, (q + 1) Kpad) and table entries [q Kpad/32, ...)
+                       // and writes source pixel (i, j) to output pixel (2 i + py, 2 j + px) of the [N, 2 Hout, 2 Wout, Cout] tensor
     int flat;          // 1 (conv_dma3.hip): a 1x1 conv without upsample (every source read at tap (0, 0), per-source strides allowed): the gather
                        // offset of a lane is computed once per source geometry (conv_dma3_kernel<FLAT>); SEMDEPTH_NO_FLAT switches it off
     int noup;          // 1 (conv_dma3.hip): the ONE source is not read through an upsample, stride 1 or 2, planes below 4 GB: the gather of a
@@ -84,9 +108,6 @@ struct ConvParams {
     int rowgrp;        // > 0 (conv_dma3.hip): the GEMM's pixels are ordered (image group of rowgrp images, row, image, column) with rowgrp * Wout = 256,
                        // so that a 256-pixel tile is ONE output row of rowgrp images and skips the k-tiles of the taps whose input row is zero
                        // padding (fc6: 7x7 on 16 rows, 10.7 % of the k-tiles).  Results are bit-identical to the plain order.
-    int fold;          // 1 (conv_dma3.hip): upsample-folded 3x3 conv (OpDesc::fold).  Hout x Wout are the SOURCE dims (the GEMM's pixel space), the
-                       // grid carries four parities, parity q = 2 py + px reads weight rows [q Kpad, (q + 1) Kpad) and table entries [q Kpad/32, ...)
-                       // and writes source pixel (i, j) to output pixel (2 i + py, 2 j + px) of the [N, 2 Hout, 2 Wout, Cout] tensor
 };
 hipError_t launch_conv_igemm(const ConvParams& p, hipStream_t s);
 const char* conv_igemm_kernel_name(const ConvParams& p);
@@ -99,10 +120,12 @@ int conv_dma_variant(const ConvParams& p);
 hipError_t launch_conv_dma(const ConvParams& p, hipStream_t s);
 bool conv_stem_eligible(const ConvParams& p);                        // conv_stem.hip: layers on the 4-channel network input
 hipError_t launch_conv_stem(const ConvParams& p, hipStream_t s);
+const char* conv_stem_kernel_name(const ConvParams& p);
 const char* conv_dma_kernel_name(const ConvParams& p);
 bool conv_dma3_eligible(const ConvParams& p);                        // conv_dma3.hip: bf16 x 3, 256 x 256 block with phased weight planes
 hipError_t launch_conv_dma3(const ConvParams& p, hipStream_t s);
 int conv_dma3_mode(const ConvParams& p);                             // gather variant (conv_dma3_kernel<MODE>) the layer runs
+const char* conv_dma3_kernel_name(const ConvParams& p);
 
 #ifdef __HIPCC__
 // ELU for the conv epilogues.  expm1f() is a ~60-instruction library routine and the monodepth layers apply it to every
@@ -121,7 +144,7 @@ __device__ __forceinline__ float fast_elu_split(float v) {
 }
 template <int ACT> struct ActTag { static constexpr int value = ACT; };
 template <bool B> struct BoolTag { static constexpr bool value = B; };   // output plane format of an epilogue: true = fp16 planes
-template <int I> struct IntTag { static constexpr int value = I; };      // the same, three-way (split_fmt.hpp split2_fmt)
+template <int I> struct IntTag { static constexpr int value = I; };      // the same, three-way (split_fmt.hpp split2_fmt); a Planes value
 // activation selected at compile time inside the epilogues (a run-time switch per value costs more than the arithmetic)
 template <int ACT> __device__ __forceinline__ float act_split(float v) {
     if (ACT == 1) return fmaxf(v, 0.f);
@@ -195,11 +218,9 @@ struct ConvDirectParams {
     int act, Nmax;
     const void* zero16;
     int rows_per_wave;           // 1: 8 x 32 tiles, 2: 16 x 32 tiles (see conv_direct.hip)
-    int f16;                     // 1: ONE fp16 input plane x two fp16 weight planes (2 MFMA products); 2: x w_hi only (1 product);
-                                 // 3: fp16 hi + lo input planes x w_hi (2 products: x_hi*w_hi + x_lo*w_hi)
-                                 // 4 (SD_PREC_F16X2): fp16 hi + scaled lo input planes x fp16 hi + lo weights, THREE products, `alpha` applied
-    int out_f16;                 // OUTPUT planes: 0 bf16 hi + lo, 1 ONE fp16 plane, 2 fp16 hi + lo, 3 fp16 hi + scaled lo (HS)
-    float alpha;                 // f16 == 4: 2^-k of the layer's weight scale: out = act(acc * alpha + bias)
+    Scheme scheme;               // product scheme
+    Planes out_fmt;              // format of the output planes
+    float alpha;                 // SC_HS: 2^-k of the layer's weight scale: out = act(acc * alpha + bias)
     int pool;                    // 1: fused 2x2 stride-2 max pool, out is [N,H/2,W/2,Cout] (needs rows_per_wave == 2)
     unsigned sw;                 // Switch bits of the handle
     int reserve_cus;             // the persistent grid is (CUs - reserve_cus) workgroups (ConvParams::reserve_cus)
@@ -225,17 +246,17 @@ struct DecTailParams {
     const float* bd;       // [1]
     float* out;            // [N, H, W] f32
     unsigned sw;
-    int hs;                // 1 (SD_PREC_F16X2): a / d2 are fp16 hi + scaled lo planes, w1 / w2 hold fp16 hi + lo of w * 2^k in planes 0 and 1 (split_fmt.hpp "HS")
+    Scheme scheme;         // SC_BF16X3, or SC_HS: a / d2 are PL_HS planes, w1 / w2 hold fp16 hi + lo of w * 2^k in planes 0 and 1
     int reserve_cus;       // the persistent grid is (CUs - reserve_cus) workgroups (ConvParams::reserve_cus)
-    float alpha, alpha2;   // hs: 2^-k of upconv1's / iconv1's weight scale, applied to the accumulators of stage 1 / stage 2
+    float alpha, alpha2;   // SC_HS: 2^-k of upconv1's / iconv1's weight scale, applied to the accumulators of stage 1 / stage 2
 };
 bool dec_tail1_eligible(int H, int W);
 hipError_t launch_dec_tail1(const DecTailParams& p, hipStream_t s);
 
 // small-N convolution (N <= 4 output channels: score 1x1 convs, monodepth disparity heads)
 struct SmallNParams {
-    const float* x;     // [N,H,W,C] (f32, or split planes when in_split)
-    int in_split, out_split;       // activation formats (split_fmt.hpp); out_split needs nout == 2
+    const float* x;     // [N,H,W,C] in the planes of in_fmt
+    Planes in_fmt, out_fmt;        // a split out_fmt needs nout == 2; PL_F16X2 inputs: the per-thread / per-wave kernels only
     int out_c;                     // stored channels of a split output (2, or 8 = zero-padded octet for the direct conv)
     size_t in_plane, out_plane;    // element offset of the lo plane
     size_t in_sub;                 // > 0: the input is stored as C/16 sub-planes of 16 channels, in_sub elements each
@@ -248,23 +269,20 @@ struct SmallNParams {
     float* out;         // [N,H,W,nout]
     int act;
     const void* zero16; // 16 zero bytes (padding source of the LDS-DMA halo loads of the tiled kernel)
-    int f16;            // INPUT planes: 0 bf16 hi + lo, 1 ONE fp16 plane, 2 fp16 hi + lo (per-thread / per-wave kernels), 3 fp16 hi + scaled lo (HS)
-    int x3;             // split planes (in and out) are bf16 x 3 (per-thread / per-wave kernels)
-    int out_f16;        // OUTPUT split planes (out_split) are fp16 (3: fp16 hi + scaled lo)
     unsigned sw;        // Switch bits of the handle
 };
 hipError_t launch_conv_smalln(const SmallNParams& p, hipStream_t s);
-bool conv_smalln_tiled(int in_split, int k, int W, int C, int nout);   // the LDS-tiled kernel takes this layer (it alone reads sub-planar inputs)
+bool conv_smalln_tiled(Planes in_fmt, int k, int W, int C, int nout);   // the LDS-tiled kernel takes this layer (it alone reads sub-planar inputs)
 
 // ---------------------------------------------------------------------------------------------
 // misc network ops (ops_misc.hip)
 // ---------------------------------------------------------------------------------------------
-// `split`: 0 f32, 1 split-bf16 planes (split_fmt.hpp), 2 ONE fp16 plane, 4 bf16 x 3 planes, 5 fp16 hi + scaled lo (HS); `plane*` = element offset of the lo plane
-hipError_t launch_pre_vgg(const uint8_t* frames, float* out, long npix, int split, size_t plane, hipStream_t s);                 // K1
-hipError_t launch_pre_mono(const uint8_t* frames, float* out, int B, int H, int W, int split, size_t plane, int raw, hipStream_t s);      // /255 (raw: not) + fliplr pair
-hipError_t launch_maxpool2(const float* x, float* y, int N, int H, int W, int C, int split, size_t plane_in, size_t plane_out, hipStream_t s);
-hipError_t launch_maxpool3z(const float* x, float* y, int N, int H, int W, int C, int split, size_t plane_in, size_t plane_out, int sub_nmax, hipStream_t s);
-hipError_t launch_unsplit(const float* x, float* y, long npix, int C, int Ctf, size_t plane, size_t sub, int f16, hipStream_t s);  // split planes -> f32 [npix][Ctf]; f16 = TensorDesc::f16, or -1: bf16 x 3
+// `fmt`: the tensor's planes (PL_F16X2 only for launch_unsplit); `plane*` = element offset of the second plane
+hipError_t launch_pre_vgg(const uint8_t* frames, float* out, long npix, Planes fmt, size_t plane, hipStream_t s);                 // K1
+hipError_t launch_pre_mono(const uint8_t* frames, float* out, int B, int H, int W, Planes fmt, size_t plane, int raw, hipStream_t s);      // /255 (raw: not) + fliplr pair
+hipError_t launch_maxpool2(const float* x, float* y, int N, int H, int W, int C, Planes fmt, size_t plane_in, size_t plane_out, hipStream_t s);
+hipError_t launch_maxpool3z(const float* x, float* y, int N, int H, int W, int C, Planes fmt, size_t plane_in, size_t plane_out, int sub_nmax, hipStream_t s);
+hipError_t launch_unsplit(const float* x, float* y, long npix, int C, int Ctf, size_t plane, size_t sub, Planes fmt, hipStream_t s);  // split planes -> f32 [npix][Ctf]
 // y[n,2i+ky-1,2j+kx-1,o] += x[n,i,j,c]*w[ky,kx,o,c]; y += bias + skip   (3->3 channels; fcn8s/fcn.py:186-204)
 hipError_t launch_deconv4s2_add(const float* x, const float* w, const float* bias, const float* skip, float* y,
                                 int N, int H, int W, hipStream_t s);

@@ -9,54 +9,54 @@ namespace sd {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// Every op below exists for the activation formats f32 NHWC (0), split-bf16 planes (1), ONE fp16 plane (2), [read side: fp16 hi + lo (3)]
-// , bf16 x 3 planes (4) and fp16 hi + scaled lo (5, "HS": SD_PREC_F16X2) of split_fmt.hpp (template parameter SPLIT; `plane` = element offset between planes).
+// Every op below exists for each activation format (template parameter SPLIT: a Planes value, kernels.hpp; PL_F16X2 on the read side of the
+// small-N heads only; `plane` = element offset between planes).
 // ---------------------------------------------------------------------------------------------
 // K1: VGG 'Processing' block [UPSTREAM Udacity vgg]: split (c0,c1,c2), subtract means, concat reversed.
 // 4 stored channels (the 4th is zero and meets zero weight rows): conv1_1 gathers whole channel quads.
 // ---------------------------------------------------------------------------------------------
 template <int SPLIT>
 __device__ __forceinline__ void store4(float* base, size_t plane, long quad_index, f32x4 v) {
-    if (SPLIT == 5) {              // fp16 hi + scaled lo
+    if (SPLIT == PL_HS) {              // fp16 hi + scaled lo
         uint2 h, l;
         split4_hs(v, h, l, (sat_ptr_t) nullptr);
         reinterpret_cast<uint2*>(base)[quad_index] = h;
         reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(base) + plane)[quad_index] = l;
-    } else if (SPLIT == 4) {              // bf16 x 3: exact
+    } else if (SPLIT == PL_BF16X3) {              // bf16 x 3: exact
         uint2 h, m, l;
         split4_x3(v, h, m, l);
         uint16_t* b16 = reinterpret_cast<uint16_t*>(base);
         reinterpret_cast<uint2*>(b16)[quad_index] = h;
         reinterpret_cast<uint2*>(b16 + plane)[quad_index] = m;
         reinterpret_cast<uint2*>(b16 + 2 * plane)[quad_index] = l;
-    } else if (SPLIT) {
+    } else if (SPLIT != PL_F32) {
         uint2 h, l;
-        split4_t<SPLIT == 2>(v, h, l);
+        split4_t<SPLIT == PL_F16>(v, h, l);
         uint2* hp = reinterpret_cast<uint2*>(base);             // bf16 plane: one uint2 per channel quad
         hp[quad_index] = h;
-        if (SPLIT != 2) reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(base) + plane)[quad_index] = l;      // fp16: ONE plane
+        if (SPLIT != PL_F16) reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(base) + plane)[quad_index] = l;      // fp16: ONE plane
     } else {
         reinterpret_cast<f32x4*>(base)[quad_index] = v;
     }
 }
 template <int SPLIT>
 __device__ __forceinline__ f32x4 load4(const float* base, size_t plane, long quad_index) {
-    if (SPLIT == 5)
+    if (SPLIT == PL_HS)
         return recon4_hs(reinterpret_cast<const uint2*>(base)[quad_index], reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(base) + plane)[quad_index]);
-    if (SPLIT == 4) {
+    if (SPLIT == PL_BF16X3) {
         const uint16_t* b16 = reinterpret_cast<const uint16_t*>(base);
         return recon4_x3(reinterpret_cast<const uint2*>(b16)[quad_index], reinterpret_cast<const uint2*>(b16 + plane)[quad_index],
                          reinterpret_cast<const uint2*>(b16 + 2 * plane)[quad_index]);
     }
-    if (SPLIT) {
+    if (SPLIT != PL_F32) {
         const uint2 h = reinterpret_cast<const uint2*>(base)[quad_index];
         uint2 l = {0u, 0u};
-        if (SPLIT != 2) l = reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(base) + plane)[quad_index];
-        if (SPLIT == 3) {          // fp16 hi + lo planes (read side only: the score heads on pool3 / pool4)
+        if (SPLIT != PL_F16) l = reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(base) + plane)[quad_index];
+        if (SPLIT == PL_F16X2) {          // fp16 hi + lo planes (read side only: the score heads on pool3 / pool4)
             const f32x2_t a = recon2_f16x2(h.x, l.x), b = recon2_f16x2(h.y, l.y);
             return f32x4{a[0], a[1], b[0], b[1]};
         }
-        return recon4_t<SPLIT == 2>(h, l);
+        return recon4_t<SPLIT == PL_F16>(h, l);
     }
     return reinterpret_cast<const f32x4*>(base)[quad_index];
 }
@@ -68,14 +68,21 @@ __global__ __launch_bounds__(256) void pre_vgg_kernel(const uint8_t* __restrict_
     const uint8_t* p = in + i * 3;
     store4<SPLIT>(out, plane, i, (f32x4){(float)p[2] - 103.939f, (float)p[1] - 116.779f, (float)p[0] - 123.68f, 0.f});
 }
-hipError_t launch_pre_vgg(const uint8_t* frames, float* out, long npix, int split, size_t plane, hipStream_t s) {
-    const dim3 grid((unsigned)((npix + 255) / 256));
-    if (split == 5) hipLaunchKernelGGL(pre_vgg_kernel<5>, grid, dim3(256), 0, s, frames, out, npix, plane);
-    else if (split == 4) hipLaunchKernelGGL(pre_vgg_kernel<4>, grid, dim3(256), 0, s, frames, out, npix, plane);
-    else if (split == 2) hipLaunchKernelGGL(pre_vgg_kernel<2>, grid, dim3(256), 0, s, frames, out, npix, plane);
-    else if (split) hipLaunchKernelGGL(pre_vgg_kernel<1>, grid, dim3(256), 0, s, frames, out, npix, plane);
-    else hipLaunchKernelGGL(pre_vgg_kernel<0>, grid, dim3(256), 0, s, frames, out, npix, plane);
+// runs launch(IntTag<fmt>{}) for the formats the element-wise kernels are built for (every one but PL_F16X2)
+template <class L> static hipError_t with_planes(Planes fmt, L&& launch) {
+    switch (fmt) {
+        case PL_F32: launch(IntTag<PL_F32>{}); break;
+        case PL_BF16X2: launch(IntTag<PL_BF16X2>{}); break;
+        case PL_F16: launch(IntTag<PL_F16>{}); break;
+        case PL_BF16X3: launch(IntTag<PL_BF16X3>{}); break;
+        case PL_HS: launch(IntTag<PL_HS>{}); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
+}
+hipError_t launch_pre_vgg(const uint8_t* frames, float* out, long npix, Planes fmt, size_t plane, hipStream_t s) {
+    const dim3 grid((unsigned)((npix + 255) / 256));
+    return with_planes(fmt, [&](auto f) { hipLaunchKernelGGL(pre_vgg_kernel<decltype(f)::value>, grid, dim3(256), 0, s, frames, out, npix, plane); });
 }
 
 // monodepth input: frame.astype(f32)/255 and its fliplr, stacked per frame (semantic_depth.py:671-672)
@@ -94,15 +101,10 @@ __global__ __launch_bounds__(256) void pre_mono_kernel(const uint8_t* __restrict
     store4<SPLIT>(out, plane, ((long)(2 * b) * H + y) * W + x, v);
     store4<SPLIT>(out, plane, ((long)(2 * b + 1) * H + y) * W + (W - 1 - x), v);
 }
-hipError_t launch_pre_mono(const uint8_t* frames, float* out, int B, int H, int W, int split, size_t plane, int raw, hipStream_t s) {
+hipError_t launch_pre_mono(const uint8_t* frames, float* out, int B, int H, int W, Planes fmt, size_t plane, int raw, hipStream_t s) {
     long npix = (long)B * H * W;
     const dim3 grid((unsigned)((npix + 255) / 256));
-    if (split == 5) hipLaunchKernelGGL(pre_mono_kernel<5>, grid, dim3(256), 0, s, frames, out, B, H, W, plane, raw);
-    else if (split == 4) hipLaunchKernelGGL(pre_mono_kernel<4>, grid, dim3(256), 0, s, frames, out, B, H, W, plane, raw);
-    else if (split == 2) hipLaunchKernelGGL(pre_mono_kernel<2>, grid, dim3(256), 0, s, frames, out, B, H, W, plane, raw);
-    else if (split) hipLaunchKernelGGL(pre_mono_kernel<1>, grid, dim3(256), 0, s, frames, out, B, H, W, plane, raw);
-    else hipLaunchKernelGGL(pre_mono_kernel<0>, grid, dim3(256), 0, s, frames, out, B, H, W, plane, raw);
-    return hipGetLastError();
+    return with_planes(fmt, [&](auto f) { hipLaunchKernelGGL(pre_mono_kernel<decltype(f)::value>, grid, dim3(256), 0, s, frames, out, B, H, W, plane, raw); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -128,15 +130,10 @@ __global__ __launch_bounds__(256) void maxpool2_kernel(const float* __restrict__
     for (int j = 0; j < 4; ++j) m[j] = fmaxf(fmaxf(a[j], b[j]), fmaxf(d[j], e[j]));
     store4<SPLIT>(y, plane_out, i, m);
 }
-hipError_t launch_maxpool2(const float* x, float* y, int N, int H, int W, int C, int split, size_t plane_in, size_t plane_out, hipStream_t s) {
+hipError_t launch_maxpool2(const float* x, float* y, int N, int H, int W, int C, Planes fmt, size_t plane_in, size_t plane_out, hipStream_t s) {
     long total = (long)N * (H / 2) * (W / 2) * (C / 4);
     const dim3 grid((unsigned)((total + 255) / 256));
-    if (split == 5) hipLaunchKernelGGL(maxpool2_kernel<5>, grid, dim3(256), 0, s, x, y, N, H, W, C / 4, plane_in, plane_out);
-    else if (split == 4) hipLaunchKernelGGL(maxpool2_kernel<4>, grid, dim3(256), 0, s, x, y, N, H, W, C / 4, plane_in, plane_out);
-    else if (split == 2) hipLaunchKernelGGL(maxpool2_kernel<2>, grid, dim3(256), 0, s, x, y, N, H, W, C / 4, plane_in, plane_out);
-    else if (split) hipLaunchKernelGGL(maxpool2_kernel<1>, grid, dim3(256), 0, s, x, y, N, H, W, C / 4, plane_in, plane_out);
-    else hipLaunchKernelGGL(maxpool2_kernel<0>, grid, dim3(256), 0, s, x, y, N, H, W, C / 4, plane_in, plane_out);
-    return hipGetLastError();
+    return with_planes(fmt, [&](auto f) { hipLaunchKernelGGL(maxpool2_kernel<decltype(f)::value>, grid, dim3(256), 0, s, x, y, N, H, W, C / 4, plane_in, plane_out); });
 }
 
 template <int SPLIT>
@@ -225,26 +222,26 @@ __global__ __launch_bounds__(256) void maxpool3z_oct_kernel(const float* __restr
     reinterpret_cast<u32x4_t*>(y)[i] = (u32x4_t){h0.x, h0.y, h1.x, h1.y};
     if (!F16) reinterpret_cast<u32x4_t*>(reinterpret_cast<uint16_t*>(y) + plane_out)[i] = (u32x4_t){l0.x, l0.y, l1.x, l1.y};
 }
-hipError_t launch_maxpool3z(const float* x, float* y, int N, int H, int W, int C, int split, size_t plane_in, size_t plane_out, int sub_nmax, hipStream_t s) {
+hipError_t launch_maxpool3z(const float* x, float* y, int N, int H, int W, int C, Planes fmt, size_t plane_in, size_t plane_out, int sub_nmax, hipStream_t s) {
     const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
-    if (sub_nmax && !(split && C % 16 == 0)) return hipErrorInvalidValue;      // (sub-planar inputs: the octet kernel only)
-    if (split && C % 8 == 0) {
+    if (sub_nmax && !(fmt != PL_F32 && C % 16 == 0)) return hipErrorInvalidValue;      // (sub-planar inputs: the octet kernel only)
+    if (fmt != PL_F32 && C % 8 == 0) {       // (the octet kernel counts 16-bit planes)
         const long tot8 = (long)N * Ho * Wo * (C / 8);
         const dim3 g8((unsigned)((tot8 + 255) / 256));
-        if (split == 5) hipLaunchKernelGGL((maxpool3z_oct_kernel<2, true>), g8, dim3(256), 0, s, x, y, N, H, W, C / 8, plane_in, plane_out, sub_nmax);
-        else if (split == 4) hipLaunchKernelGGL(maxpool3z_oct_kernel<3>, g8, dim3(256), 0, s, x, y, N, H, W, C / 8, plane_in, plane_out, sub_nmax);
-        else if (split == 2) hipLaunchKernelGGL(maxpool3z_oct_kernel<1>, g8, dim3(256), 0, s, x, y, N, H, W, C / 8, plane_in, plane_out, sub_nmax);
-        else hipLaunchKernelGGL(maxpool3z_oct_kernel<2>, g8, dim3(256), 0, s, x, y, N, H, W, C / 8, plane_in, plane_out, sub_nmax);
+#define SD_OCT(...) hipLaunchKernelGGL((maxpool3z_oct_kernel<__VA_ARGS__>), g8, dim3(256), 0, s, x, y, N, H, W, C / 8, plane_in, plane_out, sub_nmax)
+        switch (fmt) {
+            case PL_BF16X2: SD_OCT(2); break;
+            case PL_F16: SD_OCT(1); break;
+            case PL_BF16X3: SD_OCT(3); break;
+            case PL_HS: SD_OCT(2, true); break;
+            default: return hipErrorInvalidValue;
+        }
+#undef SD_OCT
         return hipGetLastError();
     }
     long total = (long)N * Ho * Wo * (C / 4);
     const dim3 grid((unsigned)((total + 255) / 256));
-    if (split == 5) hipLaunchKernelGGL(maxpool3z_kernel<5>, grid, dim3(256), 0, s, x, y, N, H, W, C / 4, plane_in, plane_out);
-    else if (split == 4) hipLaunchKernelGGL(maxpool3z_kernel<4>, grid, dim3(256), 0, s, x, y, N, H, W, C / 4, plane_in, plane_out);
-    else if (split == 2) hipLaunchKernelGGL(maxpool3z_kernel<2>, grid, dim3(256), 0, s, x, y, N, H, W, C / 4, plane_in, plane_out);
-    else if (split) hipLaunchKernelGGL(maxpool3z_kernel<1>, grid, dim3(256), 0, s, x, y, N, H, W, C / 4, plane_in, plane_out);
-    else hipLaunchKernelGGL(maxpool3z_kernel<0>, grid, dim3(256), 0, s, x, y, N, H, W, C / 4, plane_in, plane_out);
-    return hipGetLastError();
+    return with_planes(fmt, [&](auto f) { hipLaunchKernelGGL(maxpool3z_kernel<decltype(f)::value>, grid, dim3(256), 0, s, x, y, N, H, W, C / 4, plane_in, plane_out); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -298,24 +295,24 @@ __global__ __launch_bounds__(256) void conv_smalln_thread_kernel(const SmallNPar
             }
         }
     }
-    if (p.out_split) {            // NOUT == 2: one bf16 pair per plane
+    if (p.out_fmt != PL_F32) {    // NOUT == 2: one bf16 pair per plane
         unsigned h, l, m = 0u;
         const f32x2_t v2 = {smalln_act(acc[0], p.act), smalln_act(acc[NOUT > 1 ? 1 : 0], p.act)};
-        if (p.x3) split2_x3(v2, h, m, l);
-        else if (p.out_f16 == 3) split2_hs(v2, h, l, (sat_ptr_t) nullptr);
-        else if (p.out_f16) split2_t<true>(v2, h, l);
+        if (p.out_fmt == PL_BF16X3) split2_x3(v2, h, m, l);
+        else if (p.out_fmt == PL_HS) split2_hs(v2, h, l, (sat_ptr_t) nullptr);
+        else if (p.out_fmt == PL_F16) split2_t<true>(v2, h, l);
         else split2_t<false>(v2, h, l);
-        const bool two = !p.out_f16 || p.out_f16 == 3;          // a second plane exists (bf16 hi + lo, fp16 hi + scaled lo)
+        const bool two = p.out_fmt == PL_BF16X2 || p.out_fmt == PL_HS;          // a second plane exists (bf16 hi + lo, fp16 hi + scaled lo)
         uint16_t* const o16 = reinterpret_cast<uint16_t*>(p.out);
         if (p.out_c == 8) {       // one zero-padded channel octet per pixel (source of the direct 3x3 kernel)
             reinterpret_cast<u32x4_t*>(o16)[pix] = (u32x4_t){h, 0u, 0u, 0u};
-            if (p.x3) {
+            if (p.out_fmt == PL_BF16X3) {
                 reinterpret_cast<u32x4_t*>(o16 + p.out_plane)[pix] = (u32x4_t){m, 0u, 0u, 0u};
                 reinterpret_cast<u32x4_t*>(o16 + 2 * p.out_plane)[pix] = (u32x4_t){l, 0u, 0u, 0u};
             } else if (two) reinterpret_cast<u32x4_t*>(o16 + p.out_plane)[pix] = (u32x4_t){l, 0u, 0u, 0u};
         } else {
             reinterpret_cast<unsigned*>(o16)[pix] = h;
-            if (p.x3) {
+            if (p.out_fmt == PL_BF16X3) {
                 reinterpret_cast<unsigned*>(o16 + p.out_plane)[pix] = m;
                 reinterpret_cast<unsigned*>(o16 + 2 * p.out_plane)[pix] = l;
             } else if (two) reinterpret_cast<unsigned*>(o16 + p.out_plane)[pix] = l;
@@ -453,14 +450,14 @@ __global__ __launch_bounds__(256) void conv_smalln_tile_kernel(const SmallNParam
     const int y = ty0 + row;
     if (y >= p.H) return;
     const long pix = ((long)img * p.H + y) * p.W + tx0 + col;
-    if (p.out_split) {            // NOUT == 2: one bf16 pair per plane
+    if (p.out_fmt != PL_F32) {    // NOUT == 2: one bf16 pair per plane
         unsigned h, l, m = 0u;
         const f32x2_t v2 = {smalln_act(acc[0], p.act), smalln_act(acc[NOUT > 1 ? 1 : 0], p.act)};
         if (NPL == 3) split2_x3(v2, h, m, l);
         else if (HS) split2_hs(v2, h, l, (sat_ptr_t) nullptr);
-        else if (p.out_f16) split2_t<true>(v2, h, l);
+        else if (p.out_fmt == PL_F16) split2_t<true>(v2, h, l);
         else split2_t<false>(v2, h, l);
-        const bool two = HS || !p.out_f16;
+        const bool two = HS || p.out_fmt != PL_F16;
         uint16_t* const o16 = reinterpret_cast<uint16_t*>(p.out);
         if (p.out_c == 8) {
             reinterpret_cast<u32x4_t*>(o16)[pix] = (u32x4_t){h, 0u, 0u, 0u};
@@ -486,23 +483,13 @@ template <int IN_SPLIT>
 static void launch_smalln_t(const SmallNParams& p, hipStream_t s) {
     const long npix = (long)p.N * p.H * p.W;
     const int K = p.k * p.k * p.C;
-    // (IN_SPLIT 3, fp16 hi + lo input: the per-thread / per-wave kernels only)
-    if (IN_SPLIT && IN_SPLIT != 3 && p.k == 3 && p.W % SN_TW == 0 && p.C % 8 == 0 && p.nout <= 2 && p.zero16 && (size_t)K * 4 * p.nout <= 24576) {
+    if (IN_SPLIT != PL_F32 && IN_SPLIT != PL_F16X2 && p.k == 3 && p.W % SN_TW == 0 && p.C % 8 == 0 && p.nout <= 2 && p.zero16 && (size_t)K * 4 * p.nout <= 24576) {
         const dim3 grid((unsigned)((p.W / SN_TW) * ((p.H + SN_TH - 1) / SN_TH) * p.N));
         const size_t lds = (size_t)K * 4 * p.nout;
-        if (IN_SPLIT == 5) {
-            if (p.nout == 1) hipLaunchKernelGGL((conv_smalln_tile_kernel<1, 2, true>), grid, dim3(256), lds, s, p);
-            else hipLaunchKernelGGL((conv_smalln_tile_kernel<2, 2, true>), grid, dim3(256), lds, s, p);
-        } else if (IN_SPLIT == 4) {
-            if (p.nout == 1) hipLaunchKernelGGL((conv_smalln_tile_kernel<1, 3>), grid, dim3(256), lds, s, p);
-            else hipLaunchKernelGGL((conv_smalln_tile_kernel<2, 3>), grid, dim3(256), lds, s, p);
-        } else if (IN_SPLIT == 2) {
-            if (p.nout == 1) hipLaunchKernelGGL((conv_smalln_tile_kernel<1, 1>), grid, dim3(256), lds, s, p);
-            else hipLaunchKernelGGL((conv_smalln_tile_kernel<2, 1>), grid, dim3(256), lds, s, p);
-        } else {
-            if (p.nout == 1) hipLaunchKernelGGL((conv_smalln_tile_kernel<1, 2>), grid, dim3(256), lds, s, p);
-            else hipLaunchKernelGGL((conv_smalln_tile_kernel<2, 2>), grid, dim3(256), lds, s, p);
-        }
+        constexpr int NPL = plane_count((Planes)IN_SPLIT);
+        constexpr bool HS = IN_SPLIT == PL_HS;
+        if (p.nout == 1) hipLaunchKernelGGL((conv_smalln_tile_kernel<1, NPL, HS>), grid, dim3(256), lds, s, p);
+        else hipLaunchKernelGGL((conv_smalln_tile_kernel<2, NPL, HS>), grid, dim3(256), lds, s, p);
         return;
     }
     if (K <= 2048) {
@@ -518,43 +505,42 @@ static void launch_smalln_t(const SmallNParams& p, hipStream_t s) {
         hipLaunchKernelGGL(conv_smalln_wave_kernel<IN_SPLIT>, dim3((unsigned)((npix + 3) / 4)), dim3(256), 0, s, p);
     }
 }
-bool conv_smalln_tiled(int in_split, int k, int W, int C, int nout) {
-    return in_split && k == 3 && W % SN_TW == 0 && C % 8 == 0 && nout <= 2 && (size_t)9 * C * 4 * nout <= 24576;
+bool conv_smalln_tiled(Planes in_fmt, int k, int W, int C, int nout) {
+    return in_fmt != PL_F32 && k == 3 && W % SN_TW == 0 && C % 8 == 0 && nout <= 2 && (size_t)9 * C * 4 * nout <= 24576;
 }
 hipError_t launch_conv_smalln(const SmallNParams& p, hipStream_t s) {
-    if (p.in_sub && !(conv_smalln_tiled(p.in_split, p.k, p.W, p.C, p.nout) && p.zero16)) return hipErrorInvalidValue;   // sub-planes: tiled kernel only
-    if (p.out_split && (p.nout != 2 || p.k * p.k * p.C > 2048)) return hipErrorInvalidValue;
-    if (p.in_split && p.x3) {            // bf16 x 3 input: exact f32 arithmetic on the reconstructed values (tiled or per-thread / per-wave)
-        if (p.in_sub) return hipErrorInvalidValue;
-        launch_smalln_t<4>(p, s);
-    } else if (p.in_split && p.f16 == 3) {      // fp16 hi + scaled lo planes (SD_PREC_F16X2): f32 arithmetic on the reconstructed values
-        launch_smalln_t<5>(p, s);                // (sub-planar inputs: the tiled kernel, checked above)
-    } else if (p.in_split && p.f16 == 2) {      // fp16 hi + lo input: the per-thread / per-wave kernels only
-        if (p.in_sub || p.out_split) return hipErrorInvalidValue;
-        launch_smalln_t<3>(p, s);
-    } else if (p.in_split && p.f16) launch_smalln_t<2>(p, s);
-    else if (p.in_split) launch_smalln_t<1>(p, s);
-    else launch_smalln_t<0>(p, s);
+    if (p.in_sub && !(conv_smalln_tiled(p.in_fmt, p.k, p.W, p.C, p.nout) && p.zero16)) return hipErrorInvalidValue;   // sub-planes: tiled kernel only
+    if (p.out_fmt != PL_F32 && (p.nout != 2 || p.k * p.k * p.C > 2048)) return hipErrorInvalidValue;
+    switch (p.in_fmt) {        // (split inputs: f32 arithmetic on the reconstructed values)
+        case PL_F32: launch_smalln_t<PL_F32>(p, s); break;
+        case PL_BF16X2: launch_smalln_t<PL_BF16X2>(p, s); break;
+        case PL_F16: launch_smalln_t<PL_F16>(p, s); break;
+        case PL_F16X2: if (p.in_sub || p.out_fmt != PL_F32) return hipErrorInvalidValue; launch_smalln_t<PL_F16X2>(p, s); break;   // (per-thread / per-wave only)
+        case PL_BF16X3: if (p.in_sub) return hipErrorInvalidValue; launch_smalln_t<PL_BF16X3>(p, s); break;
+        case PL_HS: launch_smalln_t<PL_HS>(p, s); break;     // (sub-planar inputs: the tiled kernel, checked above)
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 
 // split planes [npix][C] -> f32 [npix][Ctf] (introspection: sd_net_tensor); Ctf < C for zero-padded tensors
 // (sub > 0: the tensor is stored as C/16 sub-planes of 16 channels, sub = elements per sub-plane, TensorDesc::planar16)
-__global__ __launch_bounds__(256) void unsplit_kernel(const float* __restrict__ x, float* __restrict__ y, long total, int C, int Ctf, size_t plane, size_t sub, int f16) {
+__global__ __launch_bounds__(256) void unsplit_kernel(const float* __restrict__ x, float* __restrict__ y, long total, int C, int Ctf, size_t plane, size_t sub, int fmt) {      // fmt: a Planes value
     long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= total) return;
     const long pix = i / Ctf;
     const int c = (int)(i - pix * Ctf);
     const uint16_t* h = reinterpret_cast<const uint16_t*>(x) + (sub ? (size_t)(c >> 4) * sub + (size_t)pix * 16 + (c & 15) : (size_t)pix * C + c);
-    if (f16 < 0) y[i] = (__uint_as_float((unsigned)h[0] << 16) + __uint_as_float((unsigned)h[plane] << 16)) + __uint_as_float((unsigned)h[2 * plane] << 16);   // bf16 x 3
-    else if (f16 == 3) y[i] = (float)__builtin_bit_cast(_Float16, h[0]) + (float)__builtin_bit_cast(_Float16, h[plane]) * (1.f / 2048.f);      // fp16 hi + scaled lo
-    else if (f16 == 2) y[i] = (float)__builtin_bit_cast(_Float16, h[0]) + (float)__builtin_bit_cast(_Float16, h[plane]);      // fp16 hi + lo
-    else if (f16) y[i] = (float)__builtin_bit_cast(_Float16, h[0]);                   // ONE fp16 plane
+    if (fmt == PL_BF16X3) y[i] = (__uint_as_float((unsigned)h[0] << 16) + __uint_as_float((unsigned)h[plane] << 16)) + __uint_as_float((unsigned)h[2 * plane] << 16);   // bf16 x 3
+    else if (fmt == PL_HS) y[i] = (float)__builtin_bit_cast(_Float16, h[0]) + (float)__builtin_bit_cast(_Float16, h[plane]) * (1.f / 2048.f);      // fp16 hi + scaled lo
+    else if (fmt == PL_F16X2) y[i] = (float)__builtin_bit_cast(_Float16, h[0]) + (float)__builtin_bit_cast(_Float16, h[plane]);      // fp16 hi + lo
+    else if (fmt == PL_F16) y[i] = (float)__builtin_bit_cast(_Float16, h[0]);                   // ONE fp16 plane
     else y[i] = __uint_as_float((unsigned)h[0] << 16) + __uint_as_float((unsigned)h[plane] << 16);
 }
-hipError_t launch_unsplit(const float* x, float* y, long npix, int C, int Ctf, size_t plane, size_t sub, int f16, hipStream_t s) {
+hipError_t launch_unsplit(const float* x, float* y, long npix, int C, int Ctf, size_t plane, size_t sub, Planes fmt, hipStream_t s) {
+    if (fmt == PL_F32) return hipErrorInvalidValue;
     const long total = npix * Ctf;
-    hipLaunchKernelGGL(unsplit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, y, total, C, Ctf, plane, sub, f16);
+    hipLaunchKernelGGL(unsplit_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, x, y, total, C, Ctf, plane, sub, fmt);
     return hipGetLastError();
 }
 

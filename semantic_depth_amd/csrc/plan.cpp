@@ -63,10 +63,8 @@ struct Builder {
     int tensor(const std::string& name, int N, int H, int W, int C) {
         TensorDesc t;
         t.name = name; t.N = N; t.H = H; t.W = W; t.C = C; t.Ctf = C;
-        t.fmt = p.prec ? 1 : 0;          // the split engine keeps its activations as split-bf16 planes
-        t.x3 = p.x3;
-        if (p.h2) t.f16 = 3;             // fp16 hi + scaled lo planes (SD_PREC_F16X2)
-        t.bytes = (size_t)N * H * W * C * (p.x3 ? 6 : sizeof(float));        // bf16 x 3: three 16-bit planes
+        t.fmt = engine_forms(p.engine).act;
+        t.bytes = (size_t)N * H * W * C * elem_bytes(t.fmt);
         p.tensors.push_back(t);
         p.tensor_by_name[name] = (int)p.tensors.size() - 1;
         return (int)p.tensors.size() - 1;
@@ -88,10 +86,9 @@ struct Builder {
             case WL_TAIL_ICONV: n = 6 * 3 * 64 * 4; break;          // [row block, half][plane][lane] x 16 bytes
             default: n = 1; for (int j = 0; j < s.rank; ++j) n *= (size_t)s.shape[j];
         }
-        s.bytes = n * sizeof(float);
-        if (p.x3 && (layout == WL_IGEMM_SPLIT || layout == WL_DIRECT_SPLIT)) { s.x3 = 1; s.bytes = n * 6; }      // three bf16 planes
-        if (p.h2 && (layout == WL_IGEMM_SPLIT || layout == WL_DIRECT_SPLIT)) { s.f16 = 1; s.hs = 1; }            // two fp16 planes of w * 2^k (WeightSlot::wscale)
-        if (p.h2 && (layout == WL_TAIL_UP || layout == WL_TAIL_ICONV)) s.hs = 1;                                 // the same in planes 0 and 1 of the fragments
+        const bool split = layout == WL_IGEMM_SPLIT || layout == WL_DIRECT_SPLIT;
+        if (split || layout == WL_TAIL_UP || layout == WL_TAIL_ICONV) s.planes = engine_forms(p.engine).w;
+        s.bytes = n * (split ? welem_bytes(s.planes) : sizeof(float));      // (the fragment sizes above count their planes)
         p.weights.push_back(s);
         p.weight_by_name[name] = (int)p.weights.size() - 1;
         return (int)p.weights.size() - 1;
@@ -134,7 +131,7 @@ struct Builder {
         // 128 .. 512 output channels: 2 .. 8 passes of 64 per tile (256 and more only where an image has enough tiles: the
         // choice must not depend on the batch)
         const bool split128 = Cout == 128 || ((Cout == 256 || Cout == 512) && (int64_t)Hin * Win >= 512);
-        bool direct = p.prec && k == 3 && stride == 1 && (Cout <= 32 || Cout == 64 || split128) && Cout % 8 == 0 && Win % 32 == 0 && residual < 0 &&
+        bool direct = p.engine != ENG_F32 && k == 3 && stride == 1 && (Cout <= 32 || Cout == 64 || split128) && Cout % 8 == 0 && Win % 32 == 0 && residual < 0 &&
                       !sd_disabled("direct");
         for (int i = 0; i < op.nsrc; ++i)
             if (p.tensors[op.src[i]].C % 8 || op.sstride[i] != 1) direct = false;
@@ -143,7 +140,7 @@ struct Builder {
         // The two-plane split engines (SD_PREC_F16X2, and bf16 x 2 / the precision plan: VERDICT r4 item 7): the same on conv_dma.hip, for outputs of 128
         // channels and more (upconv6 / 5 / 4; measured at 64 on f16x2: upconv3 0.74 ms as a direct 3x3 conv on the upsampled source, 0.89 ms folded on the
         // 256 x 64 GEMM block)
-        if (((p.x3 && Cout % 256 == 0) || (p.prec && !p.x3 && Cout % 128 == 0)) && k == 3 && stride == 1 && op.nsrc == 1 && op.up[0] && p.tensors[op.src[0]].C % 32 == 0 &&
+        if (((p.engine == ENG_BF16X3 && Cout % 256 == 0) || (p.engine != ENG_F32 && p.engine != ENG_BF16X3 && Cout % 128 == 0)) && k == 3 && stride == 1 && op.nsrc == 1 && op.up[0] && p.tensors[op.src[0]].C % 32 == 0 &&
             residual < 0 && !(latch_switches() & (SW_NO_FOLD | SW_NO_DMA))) {        // (the folded GEMM form exists on conv_dma3 only: SEMDEPTH_NO_DMA implies no fold)
             const TensorDesc& t = p.tensors[op.src[0]];
             op.fold = 1; op.vec = 1;
@@ -167,7 +164,7 @@ struct Builder {
             op.nsplit = Cout > 64 ? Cout / 64 : 1;
             // bf16 x 3 and (round 6) SD_PREC_F16X2, an upconv layer (one x2-upsampled source): the upsample-folded form of the direct kernel (OpDesc::fold;
             // f16x2: the 32 / 64-channel forms -- a 16-channel upconv1 outside the fused decoder tail runs the 16-wide MFMA kernel unfolded)
-            op.fold = ((p.x3 || (p.h2 && Cout >= 32)) && op.nsrc == 1 && op.up[0] && p.tensors[op.src[0]].C % 16 == 0 && Hout % 2 == 0 && !(latch_switches() & SW_NO_FOLD)) ? 1 : 0;
+            op.fold = ((p.engine == ENG_BF16X3 || (p.engine == ENG_F16X2 && Cout >= 32)) && op.nsrc == 1 && op.up[0] && p.tensors[op.src[0]].C % 16 == 0 && Hout % 2 == 0 && !(latch_switches() & SW_NO_FOLD)) ? 1 : 0;
             op.w = wslot(wname, {k, k, Ctf, Cout}, WL_DIRECT_SPLIT, nch * (op.fold ? 16 : 9) * 16, Cout <= 32 ? 32 : 64, 0, op.nsplit);
             WeightSlot& ws = p.weights[op.w];
             ws.nsrc = op.nsrc; ws.fold = op.fold;
@@ -180,9 +177,9 @@ struct Builder {
             push(op);
             return op.dst;
         }
-        const int bn = p.prec ? conv_split_tile_n(Cout) : conv_tile_n(Cout);
+        const int bn = p.engine != ENG_F32 ? conv_split_tile_n(Cout) : conv_tile_n(Cout);
         const int CoutPad = (Cout + bn - 1) / bn * bn;
-        op.w = wslot(wname, {k, k, Ctf, Cout}, p.prec ? WL_IGEMM_SPLIT : WL_IGEMM, op.Kpad, CoutPad);
+        op.w = wslot(wname, {k, k, Ctf, Cout}, p.engine != ENG_F32 ? WL_IGEMM_SPLIT : WL_IGEMM, op.Kpad, CoutPad);
         {
             WeightSlot& ws = p.weights[op.w];
             ws.nsrc = op.nsrc; ws.vec = op.vec; ws.Ktotal = op.Kpad;
@@ -215,9 +212,9 @@ struct Builder {
         op.src[0] = a; op.src[1] = b; op.sstride[0] = 1; op.sstride[1] = stride_b;
         op.k = 1; op.stride = 1; op.pad = 0; op.act = act;
         op.Ctot = ta.C + tb.C; op.K = op.Ctot; op.Kpad = op.K; op.Kvec = op.K; op.vec = 1;
-        const int bn = p.prec ? conv_split_tile_n(Cout) : conv_tile_n(Cout);
+        const int bn = p.engine != ENG_F32 ? conv_split_tile_n(Cout) : conv_tile_n(Cout);
         const int CoutPad = (Cout + bn - 1) / bn * bn;
-        const int lay = p.prec ? WL_IGEMM_SPLIT : WL_IGEMM;
+        const int lay = p.engine != ENG_F32 ? WL_IGEMM_SPLIT : WL_IGEMM;
         op.w = wslot(wA, {1, 1, ta.C, Cout}, lay, ta.C, CoutPad);
         const int w2 = wslot(wB, {1, 1, tb.C, Cout}, lay, tb.C, CoutPad);
         {
@@ -244,7 +241,7 @@ struct Builder {
         const TensorDesc& t = p.tensors[src];
         // a 3x3 head whose output feeds the next iconv (disp4..disp2, written as one zero-padded octet per pixel) is a direct
         // conv on the 16-wide MFMA: its two real output channels ride in a 16-column weight image
-        if (feeds_conv && p.prec && !p.x3 && k == 3 && t.W % 32 == 0 && t.C % 8 == 0 && nout <= 8 && nout == cout_tf &&
+        if (feeds_conv && p.engine != ENG_F32 && p.engine != ENG_BF16X3 && k == 3 && t.W % 32 == 0 && t.C % 8 == 0 && nout <= 8 && nout == cout_tf &&
             !sd_disabled("direct") && !sd_disabled("n16")) {
             op.kind = OP_CONV_DIRECT; op.stride = 1;
             op.nchunks = (t.C + 15) / 16;
@@ -265,10 +262,10 @@ struct Builder {
         op.b = wslot(bname, {cout_tf}, WL_BIAS4, 0, 0, nout);
         // a disparity map that feeds the next iconv is stored as ONE zero-padded channel octet per pixel in the split
         // engine (8 stored channels, 2 real), so the direct 3x3 kernel can DMA it like any other source
-        const bool octet = feeds_conv && p.prec;
+        const bool octet = feeds_conv && p.engine != ENG_F32;
         op.dst = tensor(name, t.N, t.H, t.W, octet ? 8 : nout);
         p.tensors[op.dst].Ctf = nout;
-        if (!feeds_conv) p.tensors[op.dst].fmt = 0;      // consumed by f32 kernels (deconv ladder, post-processing)
+        if (!feeds_conv) p.tensors[op.dst].fmt = PL_F32;      // consumed by f32 kernels (deconv ladder, post-processing)
         op.flops = 2.0 * p.tensors[src].N * p.tensors[src].H * p.tensors[src].W * nout * k * k * p.tensors[src].C;
         push(op);
         return op.dst;
@@ -288,7 +285,7 @@ struct Builder {
         op.w3 = wslot("dec/disp1/weights", {3, 3, 16, 2}, WL_SMALLN, 0, 0, 1);
         op.b3 = wslot("dec/disp1/biases", {2}, WL_BIAS4, 0, 0, 1);
         op.dst = tensor("dec/disp1", ta.N, 2 * ta.H, 2 * ta.W, 1);
-        p.tensors[op.dst].Ctf = 1; p.tensors[op.dst].fmt = 0; p.tensors[op.dst].x3 = 0;
+        p.tensors[op.dst].Ctf = 1; p.tensors[op.dst].fmt = PL_F32;
         p.tensors[op.dst].bytes = (size_t)ta.N * 2 * ta.H * 2 * ta.W * sizeof(float);
         op.K = 4 * 32 + 9 * 18 + 9;        // multiplications per output pixel and channel that run: folded upconv1 + iconv1 (16 channels each) + the head
         op.flops = 2.0 * ta.N * 4.0 * ta.H * ta.W * (16.0 * (4 * 32) + 16.0 * (9 * 18) + 9.0 * 16);
@@ -313,7 +310,7 @@ struct Builder {
             return prod.dst;
         }
         // the LDS-DMA conv kernel does the same by walking its output pixels in 2x2-window-major order
-        if (!zero3 && p.prec && !p.x3 && !p.ops.empty() && p.ops.back().kind == OP_CONV && p.ops.back().dst == src && p.ops.back().vec &&
+        if (!zero3 && p.engine != ENG_F32 && p.engine != ENG_BF16X3 && !p.ops.empty() && p.ops.back().kind == OP_CONV && p.ops.back().dst == src && p.ops.back().vec &&
             p.ops.back().nsrc == 1 && p.ops.back().Kvec == p.ops.back().Kpad && p.ops.back().Kpad >= 64 && t.C % 64 == 0 &&
             p.ops.back().residual < 0 && t.H % 2 == 0 && t.W % 2 == 0 &&
             (p.ops.back().act == ACT_RELU || p.ops.back().act == ACT_ELU || p.ops.back().act == ACT_NONE) && !sd_disabled("pool_fuse") &&
@@ -334,8 +331,8 @@ struct Builder {
     // LDS-tiled few-channel heads is handed over as 16-channel sub-planes (TensorDesc::planar16): the reader's 16-channel
     // chunk of a pixel row is then one contiguous run instead of 32 bytes out of every pixel's line
     void mark_planar() {
-        if (!p.prec || sd_disabled("planar")) return;
-        if (p.x3) {
+        if (p.engine == ENG_F32 || sd_disabled("planar")) return;
+        if (p.engine == ENG_BF16X3) {
             // bf16 x 3 (round 5): the one hand-off whose writer and reader both know the layout -- a stem conv (conv_stem.hip) whose output is read by direct 3x3
             // convs only (FCN-8s conv1_1 -> conv1_2): a 16-channel chunk of conv1_2's halo is then a contiguous run of the sub-plane instead of 32 bytes out of
             // every pixel's 128-byte line, which four chunk passes fetched four times (6.4 GB of input read as ~20)
@@ -369,14 +366,14 @@ struct Builder {
                            (op.kind == OP_CONV && op.vec && op.Kvec == op.Kpad && t.C % 64 == 0 && op.Kpad >= 64 &&
                             !sd_disabled("dma")) ||
                            // (three-product engine, round 5: a stem conv's output, as on bf16 x 3 above)
-                           (p.h2 && op.kind == OP_CONV && op.nsrc == 1 && op.src[0] == p.t_input && (op.k & 1) && op.k <= 7 && !op.fold && !op.fuse_pool &&
+                           (p.engine == ENG_F16X2 && op.kind == OP_CONV && op.nsrc == 1 && op.src[0] == p.t_input && (op.k & 1) && op.k <= 7 && !op.fold && !op.fuse_pool &&
                             op.residual < 0 && (t.C == 32 || t.C == 64) && t.W % 32 == 0 && !(latch_switches() & SW_NO_STEM));
                 bool reads = op.residual == (int)ti;
                 for (int j = 0; j < op.nsrc; ++j) reads = reads || op.src[j] == (int)ti;
                 if (!reads) continue;
                 ++readers;
-                const bool head = op.kind == OP_SMALLN && conv_smalln_tiled(1, op.k, t.W, t.C, op.nout);
-                ok = ok && (op.kind == OP_CONV_DIRECT || head || (p.h2 && op.kind == OP_POOL3Z && t.C % 8 == 0)) && op.residual != (int)ti;
+                const bool head = op.kind == OP_SMALLN && conv_smalln_tiled(PL_BF16X2, op.k, t.W, t.C, op.nout);
+                ok = ok && (op.kind == OP_CONV_DIRECT || head || (p.engine == ENG_F16X2 && op.kind == OP_POOL3Z && t.C % 8 == 0)) && op.residual != (int)ti;
             }
             if (made && ok && readers > 0) t.planar16 = 1;
         }
@@ -384,12 +381,10 @@ struct Builder {
 
     // precision plan: mark the conv layers named in p.f16_spec, then close the choice under the one-format-per-tensor rule
     void apply_precision_plan() {
-        if (p.h2) {                      // SD_PREC_F16X2: every conv in the three-product HS form (the tensors and weight slots were marked when they were made)
-            for (OpDesc& op : p.ops)
-                if (op.kind == OP_CONV || op.kind == OP_CONV_DIRECT) op.f16 = 4;
-            return;
-        }
-        if (!p.prec || p.x3 || p.f16_spec.empty()) return;
+        auto is_conv = [](const OpDesc& op) { return op.kind == OP_CONV || op.kind == OP_CONV_DIRECT; };
+        for (OpDesc& op : p.ops)
+            if (is_conv(op)) op.scheme = engine_forms(p.engine).conv;     // (the tensors and weight slots took the engine's form when they were made)
+        if (p.engine != ENG_BF16X2 || p.f16_spec.empty()) return;
         std::vector<std::string> toks;
         {
             size_t a = 0;
@@ -403,7 +398,6 @@ struct Builder {
                 a = b + 1;
             }
         }
-        auto is_conv = [](const OpDesc& op) { return op.kind == OP_CONV || op.kind == OP_CONV_DIRECT; };
         // token = layer name | prefix* | *, optionally followed by ":1" = ONE MFMA product (x * w_hi: plain fp16) instead of two, or by
         // ":x" = two products on fp16 hi + lo ACTIVATION planes and w_hi (the error is the weight's rounding, the input tensor keeps 22
         // bits: for layers whose input also feeds a score head; direct 3x3 layers only)
@@ -411,19 +405,19 @@ struct Builder {
             return t == "*" || t == n || (t.size() > 1 && t.back() == '*' && n.compare(0, t.size() - 1, t, 0, t.size() - 1) == 0);
         };
         for (std::string t : toks) {
-            int mode = 1;
-            if (t.size() > 2 && t.compare(t.size() - 2, 2, ":1") == 0) { mode = 2; t.erase(t.size() - 2); }
-            else if (t.size() > 2 && t.compare(t.size() - 2, 2, ":x") == 0) { mode = 3; t.erase(t.size() - 2); }
+            Scheme mode = SC_F16W;
+            if (t.size() > 2 && t.compare(t.size() - 2, 2, ":1") == 0) { mode = SC_F16X1; t.erase(t.size() - 2); }
+            else if (t.size() > 2 && t.compare(t.size() - 2, 2, ":x") == 0) { mode = SC_F16XW; t.erase(t.size() - 2); }
             bool any = false;
             for (OpDesc& op : p.ops) {
                 if (!match(t, op.name)) continue;
                 any = true;          // (a layer that is not an MFMA conv at this geometry, e.g. a small-N head, follows its input's format)
                 // a per-thread head named EXACTLY (no wildcard): its input tensor becomes ONE fp16 plane -- the producer writes half the
                 // bytes and the head reads half (dec/disp1 reads the full-resolution iconv1 output: 2.1 -> 1.07 GB each way)
-                if (op.kind == OP_SMALLN && t == op.name && mode == 1 && p.tensors[op.src[0]].fmt && p.tensors[op.src[0]].f16 < 1)
-                    p.tensors[op.src[0]].f16 = 1;
+                if (op.kind == OP_SMALLN && t == op.name && mode == SC_F16W && p.tensors[op.src[0]].fmt == PL_BF16X2)
+                    p.tensors[op.src[0]].fmt = PL_F16;
                 if (!is_conv(op)) continue;
-                if (mode == 3) {
+                if (mode == SC_F16XW) {
                     if (op.k != 3 || op.stride != 1 || p.tensors[op.dst].C % 64)
                         throw std::runtime_error("precision plan of " + p.net + ": ':x' needs a 3x3 stride-1 layer with a multiple of 64 output channels (" + op.name + ")");
                     // the form exists in the direct kernel only, on planes a direct kernel's epilogue wrote: where this geometry routes the
@@ -432,53 +426,53 @@ struct Builder {
                     for (int j = 0; j < op.nsrc && ok; ++j)
                         for (const OpDesc& q : p.ops)
                             if (q.dst == op.src[j] && q.kind != OP_CONV_DIRECT) ok = false;
-                    if (ok) op.f16 = 3;
-                } else if (op.f16 != 3) op.f16 = std::max(op.f16, mode);
+                    if (ok) op.scheme = SC_F16XW;
+                } else if (op.scheme != SC_F16XW) op.scheme = std::max(op.scheme, mode);      // (named twice: the form with fewer products)
             }
             if (!any) throw std::runtime_error("precision plan of " + p.net + ": no layer matches '" + t + "'");
         }
-        // closure.  tensor.f16: 0 bf16 hi+lo, 1 ONE fp16 plane, 2 fp16 hi+lo (its hi plane IS format 1: every fp16 layer can read it)
+        // closure, on the order PL_BF16X2 < PL_F16 < PL_F16X2 (the hi plane of PL_F16X2 IS PL_F16: every fp16 layer can read it)
         for (bool changed = true; changed;) {
             changed = false;
             for (OpDesc& op : p.ops) {
                 if (is_conv(op)) {
                     bool reads16 = false;
-                    for (int j = 0; j < op.nsrc; ++j) reads16 = reads16 || p.tensors[op.src[j]].f16;
-                    if (reads16 && !op.f16) { op.f16 = 1; changed = true; }
-                    if (op.f16)
+                    for (int j = 0; j < op.nsrc; ++j) reads16 = reads16 || p.tensors[op.src[j]].fmt == PL_F16 || p.tensors[op.src[j]].fmt == PL_F16X2;
+                    if (reads16 && op.scheme == SC_BF16X2) { op.scheme = SC_F16W; changed = true; }
+                    if (plan_f16(op.scheme))
                         for (int j = 0; j < op.nsrc; ++j) {
                             TensorDesc& t = p.tensors[op.src[j]];
-                            const int want = op.f16 == 3 ? 2 : 1;
-                            if (t.fmt && t.f16 < want) { t.f16 = want; changed = true; }
+                            const Planes want = op.scheme == SC_F16XW ? PL_F16X2 : PL_F16;
+                            if (t.fmt != PL_F32 && t.fmt < want) { t.fmt = want; changed = true; }
                         }
                 } else if (op.kind == OP_POOL2 || op.kind == OP_POOL3Z) {      // a stand-alone pool keeps the format of its source
                     TensorDesc &a = p.tensors[op.src[0]], &b = p.tensors[op.dst];
-                    if (a.fmt && b.fmt && a.f16 != b.f16) { a.f16 = b.f16 = std::max(a.f16, b.f16); changed = true; }
+                    if (a.fmt != PL_F32 && b.fmt != PL_F32 && a.fmt != b.fmt) { a.fmt = b.fmt = std::max(a.fmt, b.fmt); changed = true; }
                 }
             }
         }
         // an fp16 hi+lo tensor is written by a direct conv's epilogue and read by convs / per-thread heads only
         for (const OpDesc& op : p.ops) {
-            if (op.dst >= 0 && p.tensors[op.dst].fmt && p.tensors[op.dst].f16 == 2 && op.kind != OP_CONV_DIRECT)
+            if (op.dst >= 0 && p.tensors[op.dst].fmt == PL_F16X2 && op.kind != OP_CONV_DIRECT)
                 throw std::runtime_error("precision plan of " + p.net + ": the input of a ':x' layer must come from a direct 3x3 layer (" + op.name + ")");
-            if ((op.kind == OP_POOL2 || op.kind == OP_POOL3Z) && p.tensors[op.src[0]].f16 == 2)
+            if ((op.kind == OP_POOL2 || op.kind == OP_POOL3Z) && p.tensors[op.src[0]].fmt == PL_F16X2)
                 throw std::runtime_error("precision plan of " + p.net + ": a stand-alone pool cannot read fp16 hi+lo planes (" + op.name + ")");
         }
         if (p.net.compare(0, 9, "monodepth") == 0)
             for (OpDesc& op : p.ops)
-                if (is_conv(op) && op.f16 && op.nsrc == 1 && op.src[0] == p.t_input) {
+                if (is_conv(op) && plan_f16(op.scheme) && op.nsrc == 1 && op.src[0] == p.t_input) {
                     p.input_scale = 1.f;
                     p.weights[op.w].scale = 1.f / 255.f;
                 }
         double fl = 0;
         for (OpDesc& op : p.ops) {
-            if (!is_conv(op) || !op.f16) continue;
-            p.f16_ops += (p.f16_ops.empty() ? "" : ",") + op.name + (op.f16 == 2 ? ":1" : op.f16 == 3 ? ":x" : "");
+            if (!is_conv(op) || !plan_f16(op.scheme)) continue;
+            p.f16_ops += (p.f16_ops.empty() ? "" : ",") + op.name + (op.scheme == SC_F16X1 ? ":1" : op.scheme == SC_F16XW ? ":x" : "");
             fl += op.flops;
-            if (op.f16 == 2) p.flops_f16x1 += op.flops / std::max(1, p.images);
-            p.weights[op.w].f16 = 1;
+            if (op.scheme == SC_F16X1) p.flops_f16x1 += op.flops / std::max(1, p.images);
+            p.weights[op.w].planes = WP_F16X2;
             for (WeightSlot& s : p.weights)
-                if (s.owner == op.w && (s.layout == WL_IGEMM_SPLIT || s.layout == WL_DIRECT_SPLIT)) s.f16 = 1;
+                if (s.owner == op.w && (s.layout == WL_IGEMM_SPLIT || s.layout == WL_DIRECT_SPLIT)) s.planes = WP_F16X2;
         }
         p.flops_f16 = fl / std::max(1, p.images);
     }
@@ -504,7 +498,7 @@ struct Builder {
             if (s.owner >= 0) continue;
             s.offset = off;
             const bool ig = s.layout == WL_IGEMM || s.layout == WL_IGEMM_SPLIT;
-            off += align_up(ig ? (size_t)s.Ktotal * s.CoutPad * (s.x3 ? 6 : sizeof(float)) : s.bytes);
+            off += align_up(ig ? (size_t)s.Ktotal * s.CoutPad * welem_bytes(s.planes) : s.bytes);
         }
         for (auto& s : p.weights) if (s.owner >= 0) s.offset = p.weights[s.owner].offset;
         for (auto& op : p.ops)
@@ -548,10 +542,10 @@ struct Builder {
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------
-NetPlan build_fcn8s(int frames, int H, int W, int prec, const char* f16_layers) {
+NetPlan build_fcn8s(int frames, int H, int W, Engine engine, const char* f16_layers) {
     if (H % 32 || W % 32) throw std::runtime_error("FCN-8s needs H, W multiples of 32");
     Builder b;
-    b.p.prec = prec ? 1 : 0; b.p.x3 = prec == 2; b.p.h2 = prec == 3; b.p.f16_spec = (prec == 1 && f16_layers) ? f16_layers : "";
+    b.p.engine = engine; b.p.f16_spec = (engine == ENG_BF16X2 && f16_layers) ? f16_layers : "";
     b.p.net = "fcn8s"; b.p.frames = frames; b.p.images = frames; b.p.H = H; b.p.W = W;
     int x = b.tensor("input_pre", frames, H, W, 4);      // 4th channel is zero: float4 gathers in conv1_1
     b.p.tensors[x].Ctf = 3;
@@ -567,7 +561,7 @@ NetPlan build_fcn8s(int frames, int H, int W, int prec, const char* f16_layers) 
             const int xin = x;
             x = b.conv(n, {{x, 0}}, ch[s], 3, 1, ACT_RELU, "vgg/" + n + "/filter", "vgg/" + n + "/biases");
             // conv1_1 (stem kernel) -> conv1_2 (direct kernel): hand the 64 channels over as four 16-channel sub-planes
-            if (s == 0 && j == 1 && prec == 1 && b.p.ops.back().kind == OP_CONV_DIRECT && b.p.tensors[xin].C == 64 && W % 32 == 0 &&
+            if (s == 0 && j == 1 && engine == ENG_BF16X2 && b.p.ops.back().kind == OP_CONV_DIRECT && b.p.tensors[xin].C == 64 && W % 32 == 0 &&
                 !sd_disabled("planar") && !sd_disabled("stem")) {
                 b.p.tensors[xin].planar16 = 1;
             }
@@ -590,7 +584,7 @@ NetPlan build_fcn8s(int frames, int H, int W, int prec, const char* f16_layers) 
         op.b = b.wslot("dec/" + wn + "/bias", {3}, WL_RAW);
         const TensorDesc& t = b.p.tensors[src];
         op.dst = b.tensor(name, t.N, t.H * 2, t.W * 2, 3);
-        b.p.tensors[op.dst].fmt = 0;          // the deconv ladder is f32
+        b.p.tensors[op.dst].fmt = PL_F32;          // the deconv ladder is f32
         b.push(op);
         return op.dst;
     };
@@ -609,11 +603,11 @@ NetPlan build_fcn8s(int frames, int H, int W, int prec, const char* f16_layers) 
 }
 
 // ---------------------------------------------------------------------------------------------
-NetPlan build_monodepth(int encoder, int frames, int H, int W, int prec, const char* f16_layers) {
+NetPlan build_monodepth(int encoder, int frames, int H, int W, Engine engine, const char* f16_layers) {
     const int mult = encoder == 0 ? 128 : 64;
     if (H % mult || W % mult) throw std::runtime_error("monodepth needs H, W multiples of 128 (vgg) / 64 (resnet50)");
     Builder b;
-    b.p.prec = prec ? 1 : 0; b.p.x3 = prec == 2; b.p.h2 = prec == 3; b.p.f16_spec = (prec == 1 && f16_layers) ? f16_layers : "";
+    b.p.engine = engine; b.p.f16_spec = (engine == ENG_BF16X2 && f16_layers) ? f16_layers : "";
     b.p.net = encoder == 0 ? "monodepth-vgg" : "monodepth-resnet50";
     b.p.frames = frames; b.p.images = 2 * frames; b.p.H = H; b.p.W = W;
     const int N = 2 * frames;
@@ -667,7 +661,7 @@ NetPlan build_monodepth(int encoder, int frames, int H, int W, int prec, const c
     int disp_prev = -1;
     for (int lvl = top; lvl >= 1; --lvl) {
         const std::string L = std::to_string(lvl);
-        if (lvl == 1 && (b.p.x3 || b.p.h2) && dec_tail1_eligible(H, W) && !(latch_switches() & SW_NO_TAIL1)) {
+        if (lvl == 1 && (b.p.engine == ENG_BF16X3 || b.p.engine == ENG_F16X2) && dec_tail1_eligible(H, W) && !(latch_switches() & SW_NO_TAIL1)) {
             disp_prev = b.dec_tail1(x, disp_prev);
             break;
         }
@@ -746,7 +740,9 @@ void relayout_weight(const WeightSlot& s, const float* w, std::vector<float>& ou
             u += 0x7FFFu + ((u >> 16) & 1u);
             return (uint16_t)(u >> 16);
         };
-        const bool f16 = s.f16 != 0;                   // two fp16 planes: hi = fp16(w) (RNE, subnormals kept), lo = fp16(w - hi)
+        const bool f16 = s.planes == WP_F16X2 || s.planes == WP_HS;     // two fp16 planes: hi = fp16(w) (RNE, subnormals kept), lo = fp16(w - hi)
+        const bool x3 = s.planes == WP_BF16X3;
+        const float wsc = s.planes == WP_HS ? s.wscale : 1.f;             // (WP_HS: planes of w * 2^k)
         auto bf16_to_f = [](uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; std::memcpy(&f, &u, 4); return f; };
         if (s.fold) {
             // upsample-folded 3x3 (OpDesc::fold): parity q = 2 py + px, tap t = 2 a + b reads source pixel (i + a - 1 + py, j + b - 1 + px); the
@@ -770,12 +766,12 @@ void relayout_weight(const WeightSlot& s, const float* w, std::vector<float>& ou
                             for (int iy = 0; iy < ny; ++iy)
                                 for (int ix = 0; ix < nx; ++ix) acc += (double)w[((int64_t)(dys[iy] * 3 + dxs[ix]) * C + c) * Cout + n];
                             const float wf = (float)acc;
-                            if (f16) { f16_split(s.hs ? wf * s.wscale : wf, hi[base + n * 8], lo[base + n * 8]); continue; }      // (SD_PREC_F16X2: planes of w * 2^k)
+                            if (f16) { f16_split(wf * wsc, hi[base + n * 8], lo[base + n * 8]); continue; }
                             const uint16_t h = bf16(wf);
                             hi[base + n * 8] = h;
                             const float r1 = wf - bf16_to_f(h);
                             lo[base + n * 8] = bf16(r1);
-                            if (s.x3) lo3[base + n * 8] = bf16(r1 - bf16_to_f(lo[base + n * 8]));
+                            if (x3) lo3[base + n * 8] = bf16(r1 - bf16_to_f(lo[base + n * 8]));
                         }
                     }
                 }
@@ -804,12 +800,12 @@ void relayout_weight(const WeightSlot& s, const float* w, std::vector<float>& ou
                     } else {                          // two bf16 planes [k/8][n][8]
                         const size_t base = (size_t)(k / 8) * s.CoutPad * 8 + (k % 8);
                         for (int64_t n = 0; n < Cout; ++n) {
-                            if (f16) { f16_split(s.hs ? src[n] * s.wscale : src[n], hi[base + n * 8], lo[base + n * 8]); continue; }      // (hs: planes of w * 2^k)
+                            if (f16) { f16_split(src[n] * wsc, hi[base + n * 8], lo[base + n * 8]); continue; }
                             const uint16_t h = bf16(src[n]);
                             hi[base + n * 8] = h;
                             const float r1 = src[n] - bf16_to_f(h);
                             lo[base + n * 8] = bf16(r1);
-                            if (s.x3) lo3[base + n * 8] = bf16(r1 - bf16_to_f(lo[base + n * 8]));        // exact: w = hi + mid + lo
+                            if (x3) lo3[base + n * 8] = bf16(r1 - bf16_to_f(lo[base + n * 8]));        // exact: w = hi + mid + lo
                         }
                     }
                 }
@@ -821,6 +817,8 @@ void relayout_weight(const WeightSlot& s, const float* w, std::vector<float>& ou
         // [split][plane][chunk][tap 9][octet 2][CoutPad n][8]: chunk = 16 stored channels of one source
         const int64_t Ctf = s.shape[2], Cout = s.shape[3];
         const size_t plane = (size_t)s.Kpad * s.CoutPad;
+        const bool f16 = s.planes == WP_F16X2 || s.planes == WP_HS;
+        const float wsc = s.planes == WP_HS ? s.wscale : 1.f;
         uint16_t* const hi0 = reinterpret_cast<uint16_t*>(out.data());
         auto bf16 = [](float v) -> uint16_t { uint32_t u; std::memcpy(&u, &v, 4); u += 0x7FFFu + ((u >> 16) & 1u); return (uint16_t)(u >> 16); };
         auto bf16_to_f = [](uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; std::memcpy(&f, &u, 4); return f; };
@@ -843,8 +841,8 @@ void relayout_weight(const WeightSlot& s, const float* w, std::vector<float>& ou
                                 for (int iy = 0; iy < ny; ++iy)
                                     for (int ix = 0; ix < nx; ++ix) acc += (double)w[((int64_t)(dys[iy] * 3 + dxs[ix]) * Ctf + c) * Cout + n];
                                 const float wf = (float)acc;
-                                uint16_t* hi = hi0 + (size_t)(n / s.CoutPad) * (s.x3 ? 3 : 2) * plane + base + (n % s.CoutPad) * 8;
-                                if (s.f16) { f16_split(s.hs ? wf * s.wscale : wf, *hi, hi[plane]); continue; }       // (SD_PREC_F16X2: two fp16 planes of w * 2^k)
+                                uint16_t* hi = hi0 + (size_t)(n / s.CoutPad) * wplane_count(s.planes) * plane + base + (n % s.CoutPad) * 8;
+                                if (f16) { f16_split(wf * wsc, *hi, hi[plane]); continue; }
                                 const uint16_t h = bf16(wf);
                                 *hi = h;
                                 const float r1 = wf - bf16_to_f(h);
@@ -864,13 +862,13 @@ void relayout_weight(const WeightSlot& s, const float* w, std::vector<float>& ou
                         const float* src = w + ((int64_t)tap * Ctf + cb_tf + c) * Cout;
                         const size_t base = (((size_t)chunk * 9 + tap) * 2 + oct) * s.CoutPad * 8 + e;
                         for (int64_t n = 0; n < Cout; ++n) {
-                            uint16_t* hi = hi0 + (size_t)(n / s.CoutPad) * (s.x3 ? 3 : 2) * plane + base + (n % s.CoutPad) * 8;
-                            if (s.f16) { f16_split(s.hs ? src[n] * s.wscale : src[n], *hi, hi[plane]); continue; }
+                            uint16_t* hi = hi0 + (size_t)(n / s.CoutPad) * wplane_count(s.planes) * plane + base + (n % s.CoutPad) * 8;
+                            if (f16) { f16_split(src[n] * wsc, *hi, hi[plane]); continue; }
                             const uint16_t h = bf16(src[n]);
                             *hi = h;
                             const float r1 = src[n] - bf16_to_f(h);
                             hi[plane] = bf16(r1);
-                            if (s.x3) hi[2 * plane] = bf16(r1 - bf16_to_f(hi[plane]));                    // exact: w = hi + mid + lo
+                            if (s.planes == WP_BF16X3) hi[2 * plane] = bf16(r1 - bf16_to_f(hi[plane]));                    // exact: w = hi + mid + lo
                         }
                     }
             cb_tf += s.srcCtf[i];
@@ -882,7 +880,7 @@ void relayout_weight(const WeightSlot& s, const float* w, std::vector<float>& ou
         auto bf16_to_f = [](uint16_t h) { uint32_t u = (uint32_t)h << 16; float f; std::memcpy(&f, &u, 4); return f; };
         uint16_t* const o16 = reinterpret_cast<uint16_t*>(out.data());
         auto put = [&](int frag, int lane, int e, float v) {             // element e of the lane's eight, all three planes
-            if (s.hs) {              // SD_PREC_F16X2: fp16 hi + lo of w * 2^k in planes 0 and 1 (the kernel forms w_hi * 2^-11 in the third slot)
+            if (s.planes == WP_HS) {       // fp16 hi + lo of w * 2^k in planes 0 and 1 (the kernel forms w_hi * 2^-11 in the third slot)
                 uint16_t h16, l16;
                 f16_split(v * s.wscale, h16, l16);
                 o16[(((size_t)frag * 3 + 0) * 64 + lane) * 8 + e] = h16;
@@ -963,7 +961,7 @@ void build_conv_tables(const NetPlan& p, const OpDesc& op, const char* act_base,
     auto describe = [&](int s, int cl, int tap) {
         const TensorDesc& t = p.tensors[op.src[s]];
         KEntry e{nullptr, 1, 1, 1, 0, 0, 0};
-        e.base = reinterpret_cast<const float*>(act_base + t.offset + (size_t)cl * (t.fmt ? 2 : 4));   // hi plane when split
+        e.base = reinterpret_cast<const float*>(act_base + t.offset + (size_t)cl * (t.fmt != PL_F32 ? 2 : 4));   // hi plane when split
         e.H = t.H; e.W = t.W; e.C = t.C;
         e.dy = tap / op.k - op.pad; e.dx = tap % op.k - op.pad;
         const int nv = std::max(0, std::min(4, t.C - cl));

@@ -11,15 +11,33 @@
 
 namespace sd {
 
+// The conv engine a plan is built for: every activation, conv and split weight slot takes the engine's form (engine_forms); on ENG_BF16X2
+// the precision plan may move layers to the fp16 forms.  capi.cpp maps sd_precision to these.
+enum Engine : int { ENG_F32 = 0, ENG_BF16X2 = 1, ENG_BF16X3 = 2, ENG_F16X2 = 3 };
+
+// Planes of a split weight slot (plan.cpp relayout_weight):
+//   WP_F32     one f32 matrix (not a split layout)
+//   WP_BF16X2  bf16 hi, lo of w;  WP_BF16X3  bf16 hi, mid, lo of w (exact)
+//   WP_F16X2   fp16 hi = fp16(w), lo = fp16(w - hi): the precision plan's fp16 layers (SC_F16W / SC_F16X1 / SC_F16XW read w_hi only where they
+//              drop the product)
+//   WP_HS      fp16 hi, lo of w' = w * wscale, the lo plane NOT scaled (SC_HS; unlike the PL_HS activations): the epilogue multiplies by 1 / wscale
+enum WPlanes : int { WP_F32 = 0, WP_BF16X2 = 1, WP_BF16X3 = 2, WP_F16X2 = 3, WP_HS = 4 };
+
+constexpr int wplane_count(WPlanes w) { return w == WP_BF16X3 ? 3 : w == WP_F32 ? 1 : 2; }
+constexpr int welem_bytes(WPlanes w) { return w == WP_F32 ? 4 : 2 * wplane_count(w); }
+
+struct EngineForms { Planes act; Scheme conv; WPlanes w; };
+constexpr EngineForms engine_forms(Engine e) {
+    return e == ENG_F32 ? EngineForms{PL_F32, SC_F32, WP_F32} : e == ENG_BF16X3 ? EngineForms{PL_BF16X3, SC_BF16X3, WP_BF16X3}
+         : e == ENG_F16X2 ? EngineForms{PL_HS, SC_HS, WP_HS} : EngineForms{PL_BF16X2, SC_BF16X2, WP_BF16X2};
+}
+
 struct TensorDesc {
     std::string name;
     int N = 0, H = 0, W = 0, C = 0;   // C = stored channels
     int Ctf = 0;                      // channels the TensorFlow graph sees (input_pre stores 4, TF sees 3)
-    int fmt = 0;                      // 0: f32 NHWC; 1: split-bf16 planes (split_fmt.hpp)
-    int f16 = 0;                      // 3: fp16 hi + SCALED lo planes ("HS": every tensor of SD_PREC_F16X2, NetPlan::h2);
-                                      // 1: ONE fp16 plane, 2: fp16 hi + lo planes, instead of two bf16 planes (split_fmt.hpp): every conv that reads it runs the
-                                      // 2-product scheme x * (w_hi + w_lo) (precision plan, see NetPlan::f16_spec)
-    int x3 = 0;                       // 1: bf16 x 3 planes (SD_PREC_BF16X3; 6 bytes per element, planes at 0, plane, 2 * plane)
+    Planes fmt = PL_F32;              // `bytes` is fixed by the engine's format when the tensor is made: a tensor the precision plan turns into
+                                      // PL_F16 keeps its two-plane footprint
     int planar16 = 0;                 // split planes stored as C/16 sub-planes of 16 channels ([C/16][N][H][W][16] per plane): the
                                       // producer is the stem kernel, the only consumer a direct conv, whose 16-channel halo DMA
                                       // then reads whole 128-byte lines
@@ -42,11 +60,8 @@ struct WeightSlot {
     int nsplit = 1;        // WL_DIRECT_SPLIT: output channels are stored as nsplit blocks of CoutPad (128-channel layers: 2 x 64)
     int nsrc = 1, srcCtf[3] = {0, 0, 0}, srcCpad[3] = {0, 0, 0};   // WL_IGEMM: channel structure of the K axis
     int vec = 0;           // 1: K axis is ordered (32-channel block, tap, channel) instead of (tap, channel)
-    int f16 = 0;           // split layouts: two fp16 planes, hi = fp16(w), lo = fp16(w - hi) (the 2-product scheme of split_fmt.hpp)
-    int x3 = 0;            // split layouts: THREE bf16 planes hi, mid, lo (exact: w = hi + mid + lo), SD_PREC_BF16X3
-    int hs = 0;            // split layouts (with f16): the two fp16 planes hold w' = w * wscale (SD_PREC_F16X2: hi = fp16(w'), lo = fp16(w' - hi); the conv
-                           // epilogues multiply the accumulator by 1 / wscale)
-    float wscale = 4096.f; // hs: the layer's power-of-two weight scale 2^k, chosen by sd_load_weight from the tensor it is given so that the largest
+    WPlanes planes = WP_F32;   // split layouts and the dec_tail.hip fragments
+    float wscale = 4096.f; // WP_HS: the layer's power-of-two weight scale 2^k, chosen by sd_load_weight from the tensor it is given so that the largest
                            // stored |w'| lies in [2^12, 2^13) (folded layers: the bound 4 max|w| on a sum of four taps); slots that share an
                            // accumulator (ResNet conv3 + projection: `owner`) share one scale
     float scale = 1.f;     // the tensor is multiplied by this while it is loaded (monodepth stem with integer input: 1/255, see NetPlan::input_scale)
@@ -75,9 +90,7 @@ struct OpDesc {
     // conv engine
     int Ctot = 0;          // padded channels per tap (every source rounded up to a multiple of 4)
     int K = 0, Kpad = 0, vec = 0, m_fastest = 0;
-    int f16 = 0;                 // conv ops: 4 = SD_PREC_F16X2: fp16 hi + scaled lo sources x fp16 hi + lo weights (times 2^12), THREE products;
-                                 // 1 = sources are single fp16 planes, weights two fp16 planes, TWO MFMA products per product;
-                                 // 2 = the same sources, w_hi only, ONE product (plain fp16 x fp16)
+    Scheme scheme = SC_F32;      // conv ops
     int fold = 0;                // OP_CONV: a 3x3 stride-1 conv on a x2 nearest-neighbour upsampled source, run as FOUR 2x2 convs on the source itself
                                  // (one per output parity (y & 1, x & 1)): out[2i+py, 2j+px] = sum_{a,b in 0..1} Wf[py][px][a][b] . src[i+a-1+py, j+b-1+px]
                                  // with Wf = the 3x3 taps that read the same source pixel added up (plan.cpp relayout_weight).  4/9 of the
@@ -95,10 +108,7 @@ struct NetPlan {
     int frames = 0;        // frames per chunk
     int images = 0;        // images per chunk (monodepth: 2 per frame)
     int H = 0, W = 0;
-    int prec = 0;          // 0: exact f32 MFMA, 1: split engine (planes of split_fmt.hpp)
-    int x3 = 0;            // split engine with bf16 x 3 planes everywhere (SD_PREC_BF16X3): fp32-grade, six MFMA products per product
-    int h2 = 0;            // split engine with fp16 hi + scaled lo planes everywhere (SD_PREC_F16X2, split_fmt.hpp "HS"): fp32-grade, THREE fp16 MFMA
-                           // products per product, 4 bytes per activation element; the kernels of the bf16 x 2 engine in their H2 form
+    Engine engine = ENG_F32;
     // precision plan of the split engine: which conv layers run the 2-product fp16 scheme (fp16x2 activations x fp16 weights)
     // instead of the 3-product bf16 one.  f16_spec = what was asked for (comma-separated op names, a trailing '*' matches a
     // prefix, "*" = every layer, empty = none); f16_ops = the layers that run it after the consistency closure (a tensor has ONE
@@ -119,10 +129,9 @@ struct NetPlan {
     float input_scale = 1.f / 255.f;
 };
 
-// prec: 0 exact f32 MFMA, 1 split engine (bf16 x 2 + the fp16 forms of f16_layers), 2 split engine with bf16 x 3 planes (f16_layers ignored),
-// 3 split engine with fp16 hi + scaled lo planes (f16_layers ignored)
-NetPlan build_fcn8s(int frames, int H, int W, int prec, const char* f16_layers = nullptr);
-NetPlan build_monodepth(int encoder /*0 vgg, 1 resnet50*/, int frames, int H, int W, int prec, const char* f16_layers = nullptr);
+// f16_layers: the precision plan (NetPlan::f16_spec), ENG_BF16X2 only
+NetPlan build_fcn8s(int frames, int H, int W, Engine engine, const char* f16_layers = nullptr);
+NetPlan build_monodepth(int encoder /*0 vgg, 1 resnet50*/, int frames, int H, int W, Engine engine, const char* f16_layers = nullptr);
 
 // host-side re-layout of one TensorFlow-layout weight into its slot's kernel layout
 void relayout_weight(const WeightSlot& s, const float* tf_data, std::vector<float>& out);
