@@ -344,6 +344,18 @@ sd_status sd_set_reserved_cus(sd_handle* h, int n);
  * produced it instead of a counter somebody has to poll (semantic_depth_amd/engine.py Engine.check_range). */
 sd_status sd_saturation_count_async(sd_handle* h, uint64_t* host_dst, void* stream);
 
+/* the same clamps attributed to frames: dst[i] = values clamped in frame i of the caller's batch (a monodepth frame's fliplr copy counts
+ * toward the frame; every network pass adds at the frame's position in the batch) since the handle was bound or the counts last reset.
+ * Copied on `stream` behind the work already on it (dst = pinned host or device memory, n uint32 values); reset != 0 then zeroes the
+ * max_batch counters on the same stream.  The global counter of sd_saturation_count is not changed.  SD_ERR_INVALID for a NULL dst,
+ * n < 1 or n > max_batch. */
+sd_status sd_saturation_frames(sd_handle* h, uint32_t* dst, int n, int reset, void* stream);
+/* after the frames 0..n-1 of the last calls have been dealt with (recomputed on an engine without the fp16 limit): their clamps, and those of
+ * the rows no frame owns (the zero-padded rows of a partial last GEMM tile, which write no output), leave the global counter of
+ * sd_saturation_count; the per-frame counts are zeroed.  Enqueued on `stream`, no synchronisation.  SD_ERR_INVALID for n < 1 or
+ * n > max_batch. */
+sd_status sd_saturation_settle(sd_handle* h, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

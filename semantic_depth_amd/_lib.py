@@ -97,6 +97,8 @@ SIGNATURES = {
     "sd_pass_frames": (C.c_int, [_H]),
     "sd_saturation_count": (C.c_int, [_H, C.POINTER(C.c_uint64), C.c_int]),
     "sd_saturation_count_async": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "sd_saturation_frames": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "sd_saturation_settle": (C.c_int, [_H, C.c_int, C.c_void_p]),
     "sd_set_reserved_cus": (C.c_int, [_H, C.c_int]),
 }
 

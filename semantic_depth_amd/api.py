@@ -17,6 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from . import recompute as RC
 from .engine import Camera, Engine, FenceParams, RoadWidthParams
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -29,12 +30,16 @@ _engines: dict = {}
 # accumulation: the engine bench.py headlines; a value beyond the fp16 range of its planes raises engine.RangeError), "bf16x3" (three exact bf16 planes,
 # six products, no range limit) and "f32" (the f32 MFMA, a third of the speed).  The classes below default to the fastest; precision= selects the others.
 DEFAULT_PRECISION = "f16x2"
+# What an engine with fp16 planes does with a frame that leaves their range (Engine(on_range=)): "raise" RangeError for the call, or
+# "recompute" that frame on the fp32-grade bf16x3 engine and keep the others' results.  Part of the shared-engine key.
+DEFAULT_ON_RANGE = "raise"
 
 
-def shared_engine(H: int, W: int, device: int = 0, precision: str = DEFAULT_PRECISION, encoder: str | None = None, max_batch: int = 1) -> Engine:
+def shared_engine(H: int, W: int, device: int = 0, precision: str = DEFAULT_PRECISION, encoder: str | None = None, max_batch: int = 1,
+                  on_range: str = DEFAULT_ON_RANGE) -> Engine:
     """the registered Engine for this geometry; created on first use.  ``encoder`` None = whatever is registered (or 'vgg',
     the reference's default --monodepth_encoder, semantic_depth.py:721-722)."""
-    key = (int(H), int(W), int(device), precision)
+    key = (int(H), int(W), int(device), precision, RC.check_mode(on_range))
     per = _engines.setdefault(key, {})
     if encoder is None:
         if per:
@@ -42,7 +47,7 @@ def shared_engine(H: int, W: int, device: int = 0, precision: str = DEFAULT_PREC
         encoder = "vgg"
     eng = per.get(encoder)
     if eng is None or eng.max_batch < max_batch:
-        eng = Engine(H, W, max_batch, encoder, device, precision=precision)
+        eng = Engine(H, W, max_batch, encoder, device, precision=precision, on_range=on_range)
         eng._api_loaded = {}
         per[encoder] = eng
     return eng
@@ -50,7 +55,7 @@ def shared_engine(H: int, W: int, device: int = 0, precision: str = DEFAULT_PREC
 
 def register_engine(engine: Engine):
     """make an existing Engine the shared one for its geometry (bench / batched drivers build theirs with max_batch > 1)."""
-    key = (engine.H, engine.W, engine.device.index or 0, engine.precision)
+    key = (engine.H, engine.W, engine.device.index or 0, engine.precision, engine.on_range)
     if not hasattr(engine, "_api_loaded"):
         engine._api_loaded = {}
     _engines.setdefault(key, {})[engine.encoder] = engine
@@ -95,14 +100,15 @@ def _ensure_loaded(engine: Engine, net: int, weights: dict):
 class SegmentFrame:
     """SegmentFrame(input_shape, model_var_dir, use_frozen, use_xla, CUDA_DEVICE_NUMBER) — semantic_depth.py:464-469.
     ``model_var_dir``: dict / .npz of FCN-8s weights (weights.fcn8s_weight_shapes).  use_frozen / use_xla are accepted
-    and ignored (TF graph details)."""
+    and ignored (TF graph details).  ``on_range`` (Engine(on_range=)): 'raise' or 'recompute' a frame that leaves the fp16 range."""
 
     def __init__(self, input_shape, model_var_dir, use_frozen=True, use_xla=False, CUDA_DEVICE_NUMBER="0", engine: Engine | None = None,
-                 precision: str = DEFAULT_PRECISION):
+                 precision: str = DEFAULT_PRECISION, on_range: str = DEFAULT_ON_RANGE):
         self.input_shape = tuple(input_shape)
         self.model_var_dir = model_var_dir
         self.CUDA_DEVICE_NUMBER = CUDA_DEVICE_NUMBER
         self.precision = precision
+        self.on_range = RC.check_mode(on_range)
         self._weights = _load_weight_arg(model_var_dir)
         self._engine = engine
 
@@ -111,7 +117,8 @@ class SegmentFrame:
         """resolved on first use, so that a DepthFrame built before OR after this object decides the monodepth encoder of the
         shared Engine"""
         if self._engine is None:
-            self._engine = shared_engine(self.input_shape[0], self.input_shape[1], int(self.CUDA_DEVICE_NUMBER), self.precision)
+            self._engine = shared_engine(self.input_shape[0], self.input_shape[1], int(self.CUDA_DEVICE_NUMBER), self.precision,
+                                         on_range=self.on_range)
         _ensure_loaded(self._engine, L.SD_NET_FCN8S, self._weights)
         return self._engine
 
@@ -137,10 +144,10 @@ class SegmentFrame:
 
 class DepthFrame:
     """DepthFrame(is_city, encoder, input_height, input_width, checkpoint_path, f) — semantic_depth.py:575-624.
-    ``checkpoint_path``: dict / .npz of monodepth weights."""
+    ``checkpoint_path``: dict / .npz of monodepth weights.  ``on_range``: as SegmentFrame."""
 
     def __init__(self, is_city=False, encoder="vgg", input_height=256, input_width=512, checkpoint_path=None, f=None,
-                 engine: Engine | None = None, precision: str = DEFAULT_PRECISION, device: int = 0):
+                 engine: Engine | None = None, precision: str = DEFAULT_PRECISION, device: int = 0, on_range: str = DEFAULT_ON_RANGE):
         self.is_city, self.encoder = is_city, encoder
         self.input_height, self.input_width = input_height, input_width
         self.f = float(f) if f is not None else None
@@ -152,7 +159,7 @@ class DepthFrame:
             self.cx, self.cy, self.b = 314.05519001, 124.09658151, 1
             if self.f is None:
                 self.f = 380
-        self._engine = engine or shared_engine(input_height, input_width, device, precision, encoder)
+        self._engine = engine or shared_engine(input_height, input_width, device, precision, encoder, on_range=RC.check_mode(on_range))
         if self._engine.encoder != encoder or (self._engine.H, self._engine.W) != (input_height, input_width):
             raise ValueError(f"engine is {self._engine.encoder} {self._engine.H}x{self._engine.W}, DepthFrame wants {encoder} "
                              f"{input_height}x{input_width}")
@@ -219,8 +226,17 @@ class FrameProcessor:
 
     def __init__(self, frame_segmenter: SegmentFrame, frame_depther: DepthFrame, depth: float = 10.0,
                  disp_multiplier: float | None = None, params: RoadWidthParams | None = None, approach: str = "rw",
-                 fence_params: FenceParams | None = None):
+                 fence_params: FenceParams | None = None, on_range: str | None = None):
+        """``on_range``: None = whatever the operators' engines do; 'raise' / 'recompute' = what they must do (a mismatch is an error: the
+        shared engines are built by SegmentFrame / DepthFrame(on_range=))"""
         self.frame_segmenter, self.frame_depther = frame_segmenter, frame_depther
+        if on_range is not None:
+            RC.check_mode(on_range)
+            for op in (frame_segmenter, frame_depther):
+                want = getattr(op, "on_range", None) if op._engine is None else op._engine.on_range
+                if want is not None and want != on_range:
+                    raise ValueError(f"FrameProcessor(on_range={on_range!r}) over an operator whose engine does {want!r}: "
+                                     "build SegmentFrame / DepthFrame with the same on_range")
         self.depth = depth
         self.approach = approach
         self.disp_multiplier = disp_multiplier

@@ -57,8 +57,8 @@ struct sd_handle {
 namespace {
 
 size_t al(size_t v) { return (v + 255) / 256 * 256; }
+size_t sat_bytes(int max_batch) { return al(sizeof(uint64_t) + (size_t)(3 * max_batch + SAT_IMG_PAD + 1) * sizeof(uint32_t)); }
 constexpr int RSZ_MAX = 16384;     // largest destination extent of sd_resize_cubic_u8
-constexpr size_t SAT_OFF = 512;     // the fp16 saturation counter inside the o_misc scratch (zero16 lives at +256)
 
 sd_status fail(sd_handle* h, sd_status code, const std::string& msg) {
     if (h) h->err = msg;
@@ -90,7 +90,7 @@ void carve_workspace(sd_handle* h) {
     h->o_cnt = take(B * sizeof(int32_t) * 24);
     h->o_plane = take(B * sizeof(double) * 4);
     h->o_o3d = take(o3d_scratch_bytes(h->max_batch, h->cap));
-    h->o_misc = take(4096 + al(B * 7 * sizeof(int32_t)) + al(B * 12 * sizeof(double)));   // scalars | f2f counts | f2f planes
+    h->o_misc = take(4096 + al(B * 7 * sizeof(int32_t)) + al(B * 12 * sizeof(double)) + sat_bytes(h->max_batch));   // scalars | f2f counts | f2f planes | clamp counters
     h->o_cmp = take(cmp_scratch_bytes(h->max_batch));
     h->o_rsz = take((size_t)RSZ_MAX * 16 * sizeof(int));          // resize tap tables: [RSZ_MAX][4] x idx | x weight | y idx | y weight
     h->o_rsz_cmp = take((size_t)RSZ_MAX * 16 * sizeof(int));      // the same layout for sd_compose_result_frames
@@ -129,7 +129,19 @@ static hipEvent_t prof_event(sd_handle* h) {
 }
 
 // one chunk through a plan.  frames: u8 [nframes,H,W,3] (device)
-sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int nframes, const HeadOut* head, hipStream_t s) {
+// the fp16 clamp counters at the end of the o_misc scratch: the 64-bit global count (sd_saturation_count), then its per-image uint32
+// slots for one pass (split_fmt.hpp sat_check: 2 images per frame at most + SAT_IMG_PAD), then the per-frame counts (sd_saturation_frames),
+// then the count of the clamps no frame owns (rows of a partial last GEMM tile: zero-padded rows that write nothing; sd_saturation_settle)
+unsigned long long* sat_counter(sd_handle* h) {
+    const size_t B = (size_t)h->max_batch;
+    return reinterpret_cast<unsigned long long*>(h->ws + h->o_misc + 4096 + al(B * 7 * sizeof(int32_t)) + al(B * 12 * sizeof(double)));
+}
+int sat_img_slots(sd_handle* h) { return 2 * h->max_batch + SAT_IMG_PAD; }
+unsigned* sat_frames(sd_handle* h) { return reinterpret_cast<unsigned*>(sat_counter(h) + 1) + sat_img_slots(h); }
+unsigned* sat_orphans(sd_handle* h) { return sat_frames(h) + h->max_batch; }
+
+// one chunk through a plan.  frames: u8 [nframes,H,W,3] (device), frames frame0.. of the caller's batch
+sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, int nframes, const HeadOut* head, hipStream_t s) {
     NetPlan& p = plan_of(h, net);
     char* wbase = warena(h, net);
     char* abase = h->ws + (net == SD_NET_FCN8S ? h->o_fcn : h->o_mono);
@@ -200,7 +212,7 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int nframes,
                 c.src0 = T(op.src[0]); c.src0_plane = PL(op.src[0]);
                 c.out_planar16 = d.planar16;
                 c.sw = h->sw; c.reserve_cus = h->reserve_cus;
-                c.sat = reinterpret_cast<unsigned long long*>(h->ws + h->o_misc + SAT_OFF);
+                c.sat = sat_counter(h);
                 // conv_dma3.hip, k x k stride-1 layers on one source (fc6): one output row of 256 / Wout images per tile, taps on padding rows skipped
                 const bool ph3 = op.scheme == SC_BF16X3 || op.scheme == SC_HS;     // the phased 256 x 256 GEMM block of conv_dma3.hip exists for these two
                 if (ph3 && !op.fold && op.nsrc == 1 && op.vec && op.Kvec == op.Kpad && op.k >= 3 && op.sstride[0] == 1 && !op.up[0] && !c.pool &&
@@ -245,7 +257,7 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int nframes,
                 c.rows_per_wave = 2;
                 c.scheme = op.scheme; c.out_fmt = d.fmt; c.alpha = op.scheme == SC_HS ? 1.f / p.weights[op.w].wscale : 1.f;
                 c.sw = h->sw; c.reserve_cus = h->reserve_cus;
-                c.sat = reinterpret_cast<unsigned long long*>(h->ws + h->o_misc + SAT_OFF);
+                c.sat = sat_counter(h);
                 const bool x3 = op.scheme == SC_BF16X3;
                 st = bracketed(op, e, N * c.H * c.W, d.C, [&] { return x3 ? launch_conv_direct3(c, s) : launch_conv_direct(c, s); },
                                [&] { return x3 ? conv_direct3_kernel_name(c) : conv_direct_kernel_name(c); });
@@ -307,6 +319,9 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int nframes,
         if (e != hipSuccess) return fail(h, SD_ERR_HIP, "launch " + op.name + ": " + hipGetErrorString(e));
     }
     (net == SD_NET_FCN8S ? h->last_fcn_images : h->last_mono_images) = N;
+    // the pass's per-image clamp counts -> the counts of frames frame0.. (a monodepth frame's fliplr copy is its own frame's)
+    HIPCHK(h, launch_sat_fold(reinterpret_cast<unsigned*>(sat_counter(h) + 1), sat_frames(h) + frame0, sat_orphans(h), N,
+                              p.images / p.frames == 2 ? 1 : 0, sat_img_slots(h), s));
     return SD_OK;
 }
 
@@ -449,7 +464,8 @@ sd_status sd_bind_memory(sd_handle* h, void* wf, void* wm, void* ws) {
     HIPCHK(h, hipSetDevice(h->device));
     h->wf = (char*)wf; h->wm = (char*)wm; h->ws = (char*)ws;
     h->bound = true;
-    HIPCHK(h, hipMemset(h->ws + h->o_misc, 0, 4096));      // zero page (+256), saturation counter (+512), the scalar slot (+0)
+    HIPCHK(h, hipMemset(h->ws + h->o_misc, 0, 4096));      // zero page (+256), the scalar slot (+0)
+    HIPCHK(h, hipMemset(sat_counter(h), 0, sat_bytes(h->max_batch)));      // the clamp counters
     sd_status st = upload_tables(h, SD_NET_FCN8S);
     if (st != SD_OK) return st;
     return upload_tables(h, SD_NET_MONODEPTH);
@@ -576,7 +592,7 @@ sd_status sd_fcn8s_forward(sd_handle* h, const uint8_t* frames, int B, float* lo
         const int nb = std::min(h->chunk, B - b0);
         HeadOut ho{logits ? logits + (size_t)b0 * npix * 3 : nullptr, road ? road + (size_t)b0 * npix : nullptr,
                    fence ? fence + (size_t)b0 * npix : nullptr, argmax ? argmax + (size_t)b0 * npix : nullptr};
-        sd_status st = run_plan(h, SD_NET_FCN8S, frames + (size_t)b0 * npix * 3, nb, &ho, (hipStream_t)stream);
+        sd_status st = run_plan(h, SD_NET_FCN8S, frames + (size_t)b0 * npix * 3, b0, nb, &ho, (hipStream_t)stream);
         if (st != SD_OK) return st;
     }
     return SD_OK;
@@ -684,7 +700,7 @@ sd_status sd_monodepth_forward(sd_handle* h, const uint8_t* frames, int B, float
     const float* raw = reinterpret_cast<const float*>(h->ws + h->o_mono + p.tensors[p.t_output].offset);
     for (int b0 = 0; b0 < B; b0 += h->chunk) {
         const int nb = std::min(h->chunk, B - b0);
-        sd_status st = run_plan(h, SD_NET_MONODEPTH, frames + (size_t)b0 * npix * 3, nb, nullptr, s);
+        sd_status st = run_plan(h, SD_NET_MONODEPTH, frames + (size_t)b0 * npix * 3, b0, nb, nullptr, s);
         if (st != SD_OK) return st;
         if (disp_pp) HIPCHK(h, launch_post_process(raw, disp_pp + (size_t)b0 * npix, nb, h->H, h->W, s));
         if (disp_raw)
@@ -985,10 +1001,13 @@ sd_status sd_saturation_count(sd_handle* h, uint64_t* count_out, int reset) {
     HIPCHK(h, hipDeviceSynchronize());
     unsigned long long v = 0;
     if (count_out) {
-        HIPCHK(h, hipMemcpy(&v, h->ws + h->o_misc + SAT_OFF, sizeof(v), hipMemcpyDeviceToHost));
+        HIPCHK(h, hipMemcpy(&v, sat_counter(h), sizeof(v), hipMemcpyDeviceToHost));
         *count_out = (uint64_t)v;
     }
-    if (reset) HIPCHK(h, hipMemset(h->ws + h->o_misc + SAT_OFF, 0, sizeof(v)));
+    if (reset) {
+        HIPCHK(h, hipMemset(sat_counter(h), 0, sizeof(v)));
+        HIPCHK(h, hipMemset(sat_orphans(h), 0, sizeof(uint32_t)));      // (a part of the global count)
+    }
     return SD_OK;
 }
 
@@ -1003,7 +1022,27 @@ sd_status sd_set_reserved_cus(sd_handle* h, int n) {
 sd_status sd_saturation_count_async(sd_handle* h, uint64_t* host_dst, void* stream) {
     if (!h || !host_dst) return SD_ERR_INVALID;
     if (!h->bound) return fail(h, SD_ERR_STATE, "sd_bind_memory first");
-    HIPCHK(h, hipMemcpyAsync(host_dst, h->ws + h->o_misc + SAT_OFF, sizeof(uint64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIPCHK(h, hipMemcpyAsync(host_dst, sat_counter(h), sizeof(uint64_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    return SD_OK;
+}
+
+// the per-frame counts of the same clamps: frames 0..n-1 of the caller's batch, copied on `stream`; with reset the max_batch counters are then
+// zeroed on the same stream (the global counter of sd_saturation_count is not touched)
+sd_status sd_saturation_frames(sd_handle* h, uint32_t* dst, int n, int reset, void* stream) {
+    if (!h || !dst || n < 1 || n > h->max_batch) return fail(h, SD_ERR_INVALID, "sd_saturation_frames: bad arguments");
+    if (!h->bound) return fail(h, SD_ERR_STATE, "sd_bind_memory first");
+    hipStream_t s = (hipStream_t)stream;
+    HIPCHK(h, hipMemcpyAsync(dst, sat_frames(h), (size_t)n * sizeof(uint32_t), hipMemcpyDefault, s));
+    if (reset) HIPCHK(h, hipMemsetAsync(sat_frames(h), 0, (size_t)h->max_batch * sizeof(uint32_t), s));
+    return SD_OK;
+}
+
+// the clamps of frames 0..n-1 and those no frame owns leave the global counter; the per-frame counts and the unowned count are zeroed.
+// One single-workgroup kernel on `stream`, no synchronisation (the host-side recompute mode calls it once the flagged frames are recomputed)
+sd_status sd_saturation_settle(sd_handle* h, int n, void* stream) {
+    if (!h || n < 1 || n > h->max_batch) return fail(h, SD_ERR_INVALID, "sd_saturation_settle: bad arguments");
+    if (!h->bound) return fail(h, SD_ERR_STATE, "sd_bind_memory first");
+    HIPCHK(h, launch_sat_settle(sat_counter(h), sat_frames(h), sat_orphans(h), n, h->max_batch, (hipStream_t)stream));
     return SD_OK;
 }
 

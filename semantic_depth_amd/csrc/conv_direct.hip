@@ -434,7 +434,7 @@ __global__ __launch_bounds__(512, (N16 && MT == 1) ? 2 : 1) void conv_direct_ker
                             for (int r = 0; r < 4; ++r) v[r] = 4 * kg16 + r < p.nreal ? v[r] : 0.f;
                         }
                         uint2 h, l;
-                        split4_fmt<OF>(v, h, l, p.sat);
+                        split4_fmt<OF>(v, h, l, p.sat, [&] { return cur.img; });
                         if (4 * kg16 < p.Cout) {
                             *reinterpret_cast<uint2*>(s16 + (16 * pb + c16) * R16 + kg16 * 8) = h;
                             if constexpr (!O16) *reinterpret_cast<uint2*>(s16 + 32 * R16 + (16 * pb + c16) * R16 + kg16 * 8) = l;
@@ -472,7 +472,7 @@ __global__ __launch_bounds__(512, (N16 && MT == 1) ? 2 : 1) void conv_direct_ker
                     }
                     if constexpr (H2) v = v * p.alpha + bias[r4]; else v += bias[r4];
                     v = act_split4<ACT>(v);
-                    split4_fmt<OF>(v, hh[r4], ll[r4], p.sat);
+                    split4_fmt<OF>(v, hh[r4], ll[r4], p.sat, [&] { return cur.img; });
                 }
                 const int pp = frow >> 1;                    // pooled pixel of this lane pair
 #pragma unroll
@@ -524,7 +524,7 @@ __global__ __launch_bounds__(512, (N16 && MT == 1) ? 2 : 1) void conv_direct_ker
                     f32x4 v = {acc[a][nb][4 * q], acc[a][nb][4 * q + 1], acc[a][nb][4 * q + 2], acc[a][nb][4 * q + 3]};
                     if constexpr (H2) v = v * p.alpha + bias[r4]; else v += bias[r4];
                     v = act_split4<ACT>(v);
-                    split4_fmt<OF>(v, hh[r4], ll[r4], p.sat);
+                    split4_fmt<OF>(v, hh[r4], ll[r4], p.sat, [&] { return cur.img; });
                 }
 #pragma unroll
                 for (int pl = 0; pl < 2; ++pl) {

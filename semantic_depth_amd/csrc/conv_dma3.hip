@@ -562,7 +562,7 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
                     if constexpr (HS) {
                         v = v * p.alpha + bias_v[S16 ? r4 : b * 4 + r4];
                         v = act_split4<ACT>(v);
-                        split4_hs(v, h, m, p.sat);
+                        split4_hs(v, h, m, p.sat, [&] { return sat_img_of_row<true>(p, m0 + a * 32 + srow); });
                         *reinterpret_cast<uint2*>(slab + srow * ROW + nl * 2) = h;
                         *reinterpret_cast<uint2*>(slab + 32 * ROW + srow * ROW + nl * 2) = m;
                     } else {

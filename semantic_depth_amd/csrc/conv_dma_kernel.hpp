@@ -488,7 +488,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (F16 && MT * NT <= 4) ? 4 :
                         else v += bias_v[b * 4 + r4];
                         v = act_split4<ACT>(v);
                         uint2 h, l;
-                        split4_fmt<OF>(v, h, l, p.sat);
+                        split4_fmt<OF>(v, h, l, p.sat, [&] { return sat_img_of_row(p, m0 + a * 32 + (lane & 31)); });
                         if ((lane & 3) == 0) {
                             *reinterpret_cast<uint2*>(sh + ((lane & 31) >> 2) * ROW + nl * 2) = h;
                             if constexpr (!O16) *reinterpret_cast<uint2*>(sl + ((lane & 31) >> 2) * ROW + nl * 2) = l;
@@ -524,7 +524,7 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N, (F16 && MT * NT <= 4) ? 4 :
                     else v += bias_v[b * 4 + r4];
                     v = act_split4<ACT>(v);
                     uint2 h, l;
-                    split4_fmt<OF>(v, h, l, p.sat);
+                    split4_fmt<OF>(v, h, l, p.sat, [&] { return sat_img_of_row(p, m0 + a * 32 + (lane & 31)); });
                     *reinterpret_cast<uint2*>(sh + (lane & 31) * ROW + nl * 2) = h;
                     if constexpr (!O16) *reinterpret_cast<uint2*>(sl + (lane & 31) * ROW + nl * 2) = l;
                 }

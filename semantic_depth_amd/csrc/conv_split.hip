@@ -55,7 +55,7 @@ __device__ __forceinline__ void split_epilogue_act(f32x16 (&acc)[MT][NT], unsign
                 if (n < p.Cout) v += *reinterpret_cast<const f32x4*>(p.bias + n);
                 v = act_split4<ACT>(v);
                 uint2 h, l;
-                split4_fmt<OF>(v, h, l, p.sat);
+                split4_fmt<OF>(v, h, l, p.sat, [&] { return sat_img_of_row(p, m0 + a * 32 + (lane & 31)); });
                 *reinterpret_cast<uint2*>(sh + (lane & 31) * ROW + nl * 2) = h;
                 *reinterpret_cast<uint2*>(sl + (lane & 31) * ROW + nl * 2) = l;
             }

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(512, 1) void conv_stem_kernel(const ConvParams p) {
                         split4_x3(v, hh[r4], ll[r4], mm[r4]);          // hh = hi, ll = mid, mm = lo (memory order)
                     } else {
                         v = act_split4<ACT>(v);
-                        split4_fmt<OF>(v, hh[r4], ll[r4], p.sat);
+                        split4_fmt<OF>(v, hh[r4], ll[r4], p.sat, [&] { return cur.img; });
                         mm[r4] = ll[r4];
                     }
                 }

@@ -281,6 +281,12 @@ bool conv_smalln_tiled(Planes in_fmt, int k, int W, int C, int nout);   // the L
 hipError_t launch_pre_vgg(const uint8_t* frames, float* out, long npix, Planes fmt, size_t plane, hipStream_t s);                 // K1
 hipError_t launch_pre_mono(const uint8_t* frames, float* out, int B, int H, int W, Planes fmt, size_t plane, int raw, hipStream_t s);      // /255 (raw: not) + fliplr pair
 hipError_t launch_maxpool2(const float* x, float* y, int N, int H, int W, int C, Planes fmt, size_t plane_in, size_t plane_out, hipStream_t s);
+constexpr int SAT_IMG_PAD = 512;       // per-image clamp slots past a pass's images: the rows of a partial last GEMM tile (< 512) past the last image
+// behind a pass: add the per-image fp16 clamp counts img[0..nimg) into frames[i >> shift], those of the slots past nimg into *orphans,
+// and zero all nslots of them (ops_misc.hip)
+hipError_t launch_sat_fold(unsigned* img, unsigned* frames, unsigned* orphans, int nimg, int shift, int nslots, hipStream_t s);
+// sd_saturation_settle: *total -= frames[0..n) + *orphans (not below 0), then frames[0..nall) and *orphans = 0 (ops_misc.hip)
+hipError_t launch_sat_settle(unsigned long long* total, unsigned* frames, unsigned* orphans, int n, int nall, hipStream_t s);
 hipError_t launch_maxpool3z(const float* x, float* y, int N, int H, int W, int C, Planes fmt, size_t plane_in, size_t plane_out, int sub_nmax, hipStream_t s);
 hipError_t launch_unsplit(const float* x, float* y, long npix, int C, int Ctf, size_t plane, size_t sub, Planes fmt, hipStream_t s);  // split planes -> f32 [npix][Ctf]
 // y[n,2i+ky-1,2j+kx-1,o] += x[n,i,j,c]*w[ky,kx,o,c]; y += bias + skip   (3->3 channels; fcn8s/fcn.py:186-204)

@@ -657,4 +657,47 @@ hipError_t launch_deconv16s8_head(const float* x, const float* w, const float* b
     return hipGetLastError();
 }
 
+// the per-image clamp counts of one pass (split_fmt.hpp sat_check) -> per-frame counts; the rows of a partial last tile (images >= nimg)
+// belong to no frame: their count goes to *orphans
+__global__ __launch_bounds__(256) void sat_fold_kernel(unsigned* __restrict__ img, unsigned* __restrict__ frames, unsigned* __restrict__ orphans,
+                                                       int nimg, int shift, int nslots) {
+    for (int i = threadIdx.x; i < nslots; i += 256) {
+        const unsigned c = img[i];
+        if (c) {
+            atomicAdd(i < nimg ? frames + (i >> shift) : orphans, c);
+            img[i] = 0u;
+        }
+    }
+}
+
+hipError_t launch_sat_fold(unsigned* img, unsigned* frames, unsigned* orphans, int nimg, int shift, int nslots, hipStream_t s) {
+    hipLaunchKernelGGL(sat_fold_kernel, dim3(1), dim3(256), 0, s, img, frames, orphans, nimg, shift, nslots);
+    return hipGetLastError();
+}
+
+// sd_saturation_settle: the clamps of frames 0..n-1 and the unowned ones leave the global count, which cannot go below zero
+__global__ __launch_bounds__(256) void sat_settle_kernel(unsigned long long* __restrict__ total, unsigned* __restrict__ frames,
+                                                         unsigned* __restrict__ orphans, int n, int nall) {
+    __shared__ unsigned long long part[256];
+    unsigned long long sum = 0;
+    for (int i = threadIdx.x; i < nall; i += 256) {
+        if (i < n) sum += frames[i];
+        frames[i] = 0u;
+    }
+    part[threadIdx.x] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long t = *orphans;
+        for (int i = 0; i < 256; ++i) t += part[i];
+        *orphans = 0u;
+        const unsigned long long g = *total;
+        *total = g > t ? g - t : 0ull;
+    }
+}
+
+hipError_t launch_sat_settle(unsigned long long* total, unsigned* frames, unsigned* orphans, int n, int nall, hipStream_t s) {
+    hipLaunchKernelGGL(sat_settle_kernel, dim3(1), dim3(256), 0, s, total, frames, orphans, n, nall);
+    return hipGetLastError();
+}
+
 }  // namespace sd

@@ -116,17 +116,43 @@ template <bool F16> __device__ __forceinline__ f32x4_t recon4_t(uint2 h, uint2 l
 // left the fp16 range, i.e. the precision plan does not fit these weights; the host reads it through sd_saturation_count (a silent
 // clamp must not pass for a result).  A compare and a never-taken branch per value pair: a per-lane count carried through the
 // epilogue instead costs the register-capped kernels (two workgroups per CU at 128 VGPRs) hundreds of spilled registers.
+// `slot` (sd_saturation_frames): a functor, called only inside the never-taken branch, that returns the image of the pass the value pair
+// belongs to (-1: none): the epilogue site knows its output pixel, and the image index is computed from it there and nowhere else, so the
+// common path carries no extra register across the epilogue.
 typedef unsigned long long* sat_ptr_t;
-__device__ __forceinline__ void sat_check(f32x2_t c, f32x2_t v, sat_ptr_t sat) {
+struct NoSatSlot {
+    __device__ int operator()() const { return -1; }
+};
+template <class S = NoSatSlot> __device__ __forceinline__ void sat_check(f32x2_t c, f32x2_t v, sat_ptr_t sat, S slot = {}) {
     if (__builtin_expect((c[0] != v[0]) | (c[1] != v[1]), 0))
-        if (sat) atomicAdd(sat, (unsigned long long)((c[0] != v[0] ? 1 : 0) + (c[1] != v[1] ? 1 : 0)));
+        if (sat) {
+            const unsigned n = (c[0] != v[0] ? 1u : 0u) + (c[1] != v[1] ? 1u : 0u);
+            atomicAdd(sat, (unsigned long long)n);
+            const int img = slot();
+            if (img >= 0) atomicAdd(reinterpret_cast<unsigned*>(sat + 1) + img, n);      // (sat_img_slot)
+        }
 }
-template <bool F16> __device__ __forceinline__ void split2_t(f32x2_t v, unsigned& h, unsigned& l, sat_ptr_t sat) {
+// Per-image counts need nothing a kernel does not already hold: they live in the uint32 slots right behind the 64-bit counter, one per
+// image of the pass plus SAT_IMG_PAD for the rows of a partial last tile, which no image owns, and the host folds them into the per-frame
+// counts behind every pass (launch_sat_fold).  So the slot is `sat` + 8 bytes + 4 x the image, computed inside the branch.
+//
+// The image of GEMM row m of the conv kernels (ConvParams): [img, y, x] order (the fused pool's window-major order and the folded
+// upsample's parities keep the image at m / (Hout * Wout)), or (RG: conv_dma3, the only kernel that reads it) ConvParams::rowgrp's groups
+template <bool RG = false, class P> __device__ __forceinline__ int sat_img_of_row(const P& p, int m) {
+    if (RG && p.rowgrp) {
+        const int q1 = m / p.Wout, q2 = q1 / p.rowgrp, g = q2 / p.Hout;
+        return g * p.rowgrp + (q1 - q2 * p.rowgrp);
+    }
+    int hw = p.Hout * p.Wout;
+    asm volatile("" : "+s"(hw));          // (the division's reciprocal must not be hoisted out of the cold branch into a live VGPR)
+    return m / hw;
+}
+template <bool F16, class S = NoSatSlot> __device__ __forceinline__ void split2_t(f32x2_t v, unsigned& h, unsigned& l, sat_ptr_t sat, S slot = {}) {
     if constexpr (F16) {
         // saturate at the largest finite fp16 (v_med3_f32): an activation beyond 65504 must not become inf and poison the layers
         // behind it (NaN passes through); then round to nearest even.  There is no lo plane.
         const f32x2_t c = {__builtin_amdgcn_fmed3f(v[0], -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v[1], -65504.f, 65504.f)};
-        sat_check(c, v, sat);
+        sat_check(c, v, sat, slot);
         const f16x2_t hb = __builtin_convertvector(c, f16x2_t);
         h = __builtin_bit_cast(unsigned, hb);
         l = 0u;
@@ -137,26 +163,26 @@ template <bool F16> __device__ __forceinline__ void split2_t(f32x2_t v, unsigned
 template <bool F16> __device__ __forceinline__ void split2_t(f32x2_t v, unsigned& h, unsigned& l) {
     split2_t<F16>(v, h, l, (sat_ptr_t) nullptr);
 }
-template <bool F16> __device__ __forceinline__ void split4_t(f32x4_t v, uint2& h, uint2& l, sat_ptr_t sat) {
-    split2_t<F16>(f32x2_t{v[0], v[1]}, h.x, l.x, sat);
-    split2_t<F16>(f32x2_t{v[2], v[3]}, h.y, l.y, sat);
+template <bool F16, class S = NoSatSlot> __device__ __forceinline__ void split4_t(f32x4_t v, uint2& h, uint2& l, sat_ptr_t sat, S slot = {}) {
+    split2_t<F16>(f32x2_t{v[0], v[1]}, h.x, l.x, sat, slot);
+    split2_t<F16>(f32x2_t{v[2], v[3]}, h.y, l.y, sat, slot);
 }
 template <bool F16> __device__ __forceinline__ void split4_t(f32x4_t v, uint2& h, uint2& l) {
     split4_t<F16>(v, h, l, (sat_ptr_t) nullptr);
 }
 // fp16 hi + SCALED lo (HS): split and its inverse
-__device__ __forceinline__ void split2_hs(f32x2_t v, unsigned& h, unsigned& l, sat_ptr_t sat) {
+template <class S = NoSatSlot> __device__ __forceinline__ void split2_hs(f32x2_t v, unsigned& h, unsigned& l, sat_ptr_t sat, S slot = {}) {
     const f32x2_t c = {__builtin_amdgcn_fmed3f(v[0], -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v[1], -65504.f, 65504.f)};
-    sat_check(c, v, sat);
+    sat_check(c, v, sat, slot);
     const f16x2_t hb = __builtin_convertvector(c, f16x2_t);
     const f32x2_t r = (c - __builtin_convertvector(hb, f32x2_t)) * 2048.f;        // exact residual, exact scaling
     const f16x2_t lb = __builtin_convertvector(r, f16x2_t);
     h = __builtin_bit_cast(unsigned, hb);
     l = __builtin_bit_cast(unsigned, lb);
 }
-__device__ __forceinline__ void split4_hs(f32x4_t v, uint2& h, uint2& l, sat_ptr_t sat) {
-    split2_hs(f32x2_t{v[0], v[1]}, h.x, l.x, sat);
-    split2_hs(f32x2_t{v[2], v[3]}, h.y, l.y, sat);
+template <class S = NoSatSlot> __device__ __forceinline__ void split4_hs(f32x4_t v, uint2& h, uint2& l, sat_ptr_t sat, S slot = {}) {
+    split2_hs(f32x2_t{v[0], v[1]}, h.x, l.x, sat, slot);
+    split2_hs(f32x2_t{v[2], v[3]}, h.y, l.y, sat, slot);
 }
 __device__ __forceinline__ f32x2_t recon2_hs(unsigned h, unsigned l) {
     return __builtin_convertvector(__builtin_bit_cast(f16x2_t, h), f32x2_t) + __builtin_convertvector(__builtin_bit_cast(f16x2_t, l), f32x2_t) * (1.f / 2048.f);
@@ -173,24 +199,24 @@ __device__ __forceinline__ u32x4s_t hs_wscaled(u32x4s_t w) {
 }
 // output format of an epilogue: 0 = bf16 hi + lo, 1 = ONE fp16 plane, 3 = fp16 hi + SCALED lo (HS), 2 = fp16 hi + lo (the hi plane is bit for bit the one of format
 // 1, so every fp16 layer can read such a tensor; the lo plane serves the layers that multiply x_hi and x_lo by ONE weight plane)
-template <int FMT> __device__ __forceinline__ void split2_fmt(f32x2_t v, unsigned& h, unsigned& l, sat_ptr_t sat) {
+template <int FMT, class S = NoSatSlot> __device__ __forceinline__ void split2_fmt(f32x2_t v, unsigned& h, unsigned& l, sat_ptr_t sat, S slot = {}) {
     if constexpr (FMT == 3) {          // fp16 hi + scaled lo (SD_PREC_F16X2)
-        split2_hs(v, h, l, sat);
+        split2_hs(v, h, l, sat, slot);
     } else if constexpr (FMT == 2) {
         const f32x2_t c = {__builtin_amdgcn_fmed3f(v[0], -65504.f, 65504.f), __builtin_amdgcn_fmed3f(v[1], -65504.f, 65504.f)};
-        sat_check(c, v, sat);
+        sat_check(c, v, sat, slot);
         const f16x2_t hb = __builtin_convertvector(c, f16x2_t);
         const f32x2_t r = c - __builtin_convertvector(hb, f32x2_t);               // exact
         const f16x2_t lb = __builtin_convertvector(r, f16x2_t);
         h = __builtin_bit_cast(unsigned, hb);
         l = __builtin_bit_cast(unsigned, lb);
     } else {
-        split2_t<FMT == 1>(v, h, l, sat);
+        split2_t<FMT == 1>(v, h, l, sat, slot);
     }
 }
-template <int FMT> __device__ __forceinline__ void split4_fmt(f32x4_t v, uint2& h, uint2& l, sat_ptr_t sat) {
-    split2_fmt<FMT>(f32x2_t{v[0], v[1]}, h.x, l.x, sat);
-    split2_fmt<FMT>(f32x2_t{v[2], v[3]}, h.y, l.y, sat);
+template <int FMT, class S = NoSatSlot> __device__ __forceinline__ void split4_fmt(f32x4_t v, uint2& h, uint2& l, sat_ptr_t sat, S slot = {}) {
+    split2_fmt<FMT>(f32x2_t{v[0], v[1]}, h.x, l.x, sat, slot);
+    split2_fmt<FMT>(f32x2_t{v[2], v[3]}, h.y, l.y, sat, slot);
 }
 // fp16 hi + lo -> f32
 __device__ __forceinline__ f32x2_t recon2_f16x2(unsigned h, unsigned l) {

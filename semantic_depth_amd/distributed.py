@@ -138,16 +138,29 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     return out
 
 
-def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outputs=None):
+def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outputs=None, on_range: str | None = None):
     """``step`` for run_sequence on a real Engine: host or device u8 frames of any size -> (cubic resize to the network shape on
     the GPU, semantic_depth_cityscapes_sequence.py:123-130) -> Engine.process_batch -> record buffer.
     ``camera_of(global_frame_index) -> engine.Camera`` (the sequence tool: cx = 1048.64/4·s, cy = 519.277/4·s, disp_mult = 3800).
     ``outputs`` (outputs.SequenceOutputs, None = records only): also the sequence tool's files -- process_batch keeps the final road clouds
     when PLYs are asked for, Engine.compose_result_frames makes the result images at the original frame size on the device, and the
-    batch goes to ``outputs.submit`` (copies on a side stream, written on host threads); the records are the same either way."""
+    batch goes to ``outputs.submit`` (copies on a side stream, written on host threads); the records are the same either way.
+    ``on_range`` (None = the engine's own mode; else it must match Engine(on_range=)): with 'recompute' the frames that left the fp16 range
+    are recomputed on bf16x3 inside process_batch, so every batch's records, images and PLYs are final before gather_records and no rank
+    raises from ``step.finish`` for them; ``step.recomputed`` (and the manifest's 'recomputed' names) lists those frames."""
     from .engine import RoadWidthParams
+    from .recompute import check_mode
 
+    if on_range is not None and check_mode(on_range) != getattr(engine, "on_range", "raise"):
+        raise ValueError(f"make_engine_step(on_range={on_range!r}) on an engine built with on_range={getattr(engine, 'on_range', 'raise')!r}")
     prm = params or RoadWidthParams()
+    recomputed: list[int] = []
+
+    def note(lo):
+        idx = [lo + i for i in getattr(engine, "last_recomputed", [])]
+        recomputed.extend(idx)
+        if outputs is not None and idx:
+            outputs.mark_recomputed(idx)
 
     def step(frames, lo):
         fr = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames))
@@ -157,8 +170,11 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
             fr = engine.resize_cubic(fr)
         cams = [camera_of(lo + i) for i in range(fr.shape[0])]
         if outputs is None:
-            return engine.process_batch(fr, cams, prm, approach=approach)["records"]
+            rec = engine.process_batch(fr, cams, prm, approach=approach)["records"]
+            note(lo)
+            return rec
         out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.ply)
+        note(lo)
         rec = out["records"]
         images = None
         if outputs.images:
@@ -167,6 +183,9 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
         outputs.submit(lo, rec, size, images=images, final=out.get("road_final"))
         return rec
 
-    step.finish = getattr(engine, "check_range", None)
+    # ('recompute': every clamp in a stored output is attributed to its frame and that frame recomputed, so the step has no verdict left
+    # to give at the end -- no rank can raise alone here and leave the others in the all_gather)
+    step.finish = None if getattr(engine, "on_range", "raise") == "recompute" else getattr(engine, "check_range", None)
     step.outputs = outputs
+    step.recomputed = recomputed
     return step

@@ -7,12 +7,14 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import warnings
 from dataclasses import dataclass, asdict
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from . import recompute as RC
 
 RW_DTYPE = np.dtype([("width", "<f8"), ("x_left", "<f4"), ("x_right", "<f4"), ("left_pt", "<f4", 3), ("right_pt", "<f4", 3),
                      ("found", "<i4"), ("n_road", "<i4"), ("n_zcut", "<i4"), ("n_mad_y", "<i4"), ("n_mad_x", "<i4"),
@@ -84,14 +86,20 @@ FP16_PLANE_ENGINES = ("f16x2", "f16x2x2", "mixed", "plan")
 
 class Engine:
     def __init__(self, H: int, W: int, max_batch: int = 1, encoder: str = "resnet50", device: int = 0, precision: str = "f32",
-                 plan: tuple[str, str] | None = None, range_check: bool = True):
+                 plan: tuple[str, str] | None = None, range_check: bool = True, on_range: str = "raise"):
         """precision: 'f32' (exact f32 MFMA), 'bf16x3' (fp32-grade on the bf16 MFMA: every f32 operand as three bf16 planes that sum to it
         exactly, 6 MFMA products), 'f16x2' (fp32-grade on 3 fp16 MFMA products: activations as fp16 hi + 2^11-scaled lo planes, weights as fp16 hi + lo of
         w * 2^k, k per layer), 'bf16x2' (3 bf16 MFMA products, ~1e-5), 'mixed' (monodepth on 2 fp16 products), 'plan' (per-layer
         choice; ``plan`` = (fcn8s layers, monodepth layers) that run the 2-product scheme, default = the calibrated built-in).
         range_check (engines with fp16 planes): a value beyond the fp16 range is an ERROR -- every network call enqueues an 8-byte read of
         the device's saturation counter behind its launches and the next call / ``check_range()`` raises RangeError on a non-zero count
-        (no device synchronisation on the launch path)."""
+        (no device synchronisation on the launch path).
+        on_range: 'raise' (default): as above.  'recompute' (engines with fp16 planes): every network call (fcn8s_forward,
+        monodepth_forward, process_batch) reads and resets the per-frame clamp counts behind its launches (one small synchronising read),
+        recomputes the frames that left the fp16 range on a companion 'bf16x3' engine (built on first need, same geometry, encoder,
+        device and weights) and splices their results into the outputs on the device; the other frames keep this engine's results.
+        ``last_recomputed`` lists the frames of the last call that were recomputed."""
+        RC.check_mode(on_range)
         if not torch.cuda.is_available():
             raise RuntimeError("semantic_depth_amd.Engine needs a GPU (MI355X); there is no CPU fallback")
         self.lib = L.load()
@@ -123,8 +131,19 @@ class Engine:
         self.pass_frames = int(self.lib.sd_pass_frames(h))        # frames per network pass, as the handle latched it at sd_create
         self._sat_host = torch.zeros(1, dtype=torch.int64).pin_memory() if (range_check and precision in FP16_PLANE_ENGINES) else None
         self._sat_pending = None                                  # event behind the counter read in flight
+        # per-frame clamp counts (sd_saturation_frames): pinned uint32 [max_batch]
+        self._satf_host = torch.zeros(max_batch, dtype=torch.int32).pin_memory()
+        self.on_range = on_range                                  # (as asked: the registry keys of api.py use it)
+        self._recompute = on_range == "recompute" and precision in FP16_PLANE_ENGINES      # (the other engines cannot leave the range)
+        self._kept_weights: dict = {}                             # recompute: net -> {name: the caller's host array} for the companion
+        self._companion = None
+        self._warned = False
+        self.last_recomputed: list[int] = []
 
     def close(self):
+        if getattr(self, "_companion", None) is not None:
+            self._companion.close()
+            self._companion = None
         if getattr(self, "h", None):
             torch.cuda.synchronize(self.device)
             self.lib.sd_destroy(self.h)
@@ -153,6 +172,10 @@ class Engine:
             shape = (C.c_int64 * 4)(*a.shape)
             st = self.lib.sd_load_weight(self.h, net, name.encode(), a.ctypes.data_as(C.c_void_p), shape, a.ndim)
             L.check(self.lib, self.h, st, f"sd_load_weight({name})")
+        if self._recompute:
+            self._kept_weights.setdefault(net, {}).update(weights)
+            if self._companion is not None:
+                self._companion.load_weights(net, weights)
 
     # ------------------------------------------------------------------ fp16 range guard
     def _resolve_range(self, block: bool):
@@ -190,6 +213,49 @@ class Engine:
         self._post_range_check()
         self._resolve_range(block=True)
 
+    def _frame_counts(self, n: int, reset: bool) -> np.ndarray:
+        """clamp counts of frames 0..n-1 of the calls since the last reset (sd_saturation_frames; synchronises the stream)"""
+        L.check(self.lib, self.h, self.lib.sd_saturation_frames(self.h, C.c_void_p(self._satf_host.data_ptr()), int(n), int(reset), self._stream()),
+                "sd_saturation_frames")
+        torch.cuda.current_stream(self.device).synchronize()
+        return self._satf_host[:n].numpy().view(np.uint32).copy()
+
+    def saturated_frames(self, reset: bool = False, n: int | None = None) -> np.ndarray:
+        """bool [n]: which frames of the batch (position in the caller's batch; a monodepth frame's fliplr copy counts toward the frame)
+        had a value clamped to the fp16 range since the arenas were bound / the last reset (synchronises).  ``n`` defaults to max_batch.
+        The engines without fp16 planes report no frame."""
+        return self._frame_counts(self.max_batch if n is None else n, reset) > 0
+
+    def _companion_engine(self) -> "Engine":
+        if self._companion is None:
+            comp = Engine(self.H, self.W, self.max_batch, self.encoder, self.device.index or 0, precision="bf16x3")
+            for net, w in self._kept_weights.items():
+                comp.load_weights(net, w)
+            self._companion = comp
+        return self._companion
+
+    def _settle(self, frames: torch.Tensor, out, rerun):
+        """behind the launches of a network call: 'raise' mode -> the counter read of _post_range_check; 'recompute' mode -> read the
+        per-frame counts, rerun(companion, flagged frames), splice its results over those frames of ``out`` and settle the counters"""
+        if self._recompute:
+            B = frames.shape[0]
+            counts = self._frame_counts(B, reset=False)
+            idx = RC.flagged_frames(counts)
+            self.last_recomputed = idx
+            if idx:
+                sel = torch.tensor(idx, dtype=torch.int64, device=self.device)
+                sub = rerun(self._companion_engine(), frames.index_select(0, sel).contiguous())
+                out = RC.splice(out, sub, sel)
+                if not self._warned:
+                    self._warned = True
+                    warnings.warn(f"frames {idx} left the fp16 range of the '{self.precision}' engine and were recomputed on 'bf16x3' "
+                                  "(further recomputes of this engine are listed in Engine.last_recomputed only)", RuntimeWarning, stacklevel=3)
+            # every clamp of this call is now dealt with: those of the recomputed frames, and those of the zero-padded GEMM rows that no
+            # frame owns and nothing reads -- both leave the global counter (on the stream), so check_range stays quiet
+            L.check(self.lib, self.h, self.lib.sd_saturation_settle(self.h, B, self._stream()), "sd_saturation_settle")
+        self._post_range_check()
+        return out
+
     # ------------------------------------------------------------------ operators
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -200,6 +266,10 @@ class Engine:
         return frames.shape[0]
 
     def fcn8s_forward(self, frames: torch.Tensor, want_logits: bool = False):
+        out = self._fcn8s(frames, want_logits)
+        return self._settle(frames, out, lambda e, f: e.fcn8s_forward(f, want_logits))
+
+    def _fcn8s(self, frames: torch.Tensor, want_logits: bool = False):
         B = self._frames(frames)
         dev = self.device
         logits = torch.empty((B, self.H, self.W, 3), dtype=torch.float32, device=dev) if want_logits else None
@@ -208,22 +278,31 @@ class Engine:
         amax = torch.empty_like(road)
         st = self.lib.sd_fcn8s_forward(self.h, _ptr(frames), B, _ptr(logits), _ptr(road), _ptr(fence), _ptr(amax), self._stream())
         L.check(self.lib, self.h, st, "sd_fcn8s_forward")
-        self._post_range_check()
         return dict(logits=logits, road=road, fence=fence, argmax=amax)
 
     def monodepth_forward(self, frames: torch.Tensor, want_raw: bool = False, post_process: bool = True):
-        """post_process=False: leave the flip-pair post-processing to fuse_from_raw (one pass); returns None (B <= 32 frames)"""
+        """post_process=False: leave the flip-pair post-processing to fuse_from_raw (one pass); returns None (B <= 32 frames).
+        In 'recompute' mode the raw pair in the arena cannot be spliced: post_process=False is refused there (process_batch does it)."""
+        if not post_process:
+            if self._recompute:
+                raise ValueError("monodepth_forward(post_process=False) leaves the disparity in the arena, where on_range='recompute' cannot "
+                                 "splice it: use post_process=True or process_batch")
+            self._mono(frames, False, False)
+            self._post_range_check()
+            return None
+        out = self._mono(frames, want_raw, True)
+        return self._settle(frames, out, lambda e, f: e.monodepth_forward(f, want_raw))
+
+    def _mono(self, frames: torch.Tensor, want_raw: bool, post_process: bool):
         B = self._frames(frames)
         if not post_process:
             st = self.lib.sd_monodepth_forward(self.h, _ptr(frames), B, None, None, self._stream())
             L.check(self.lib, self.h, st, "sd_monodepth_forward")
-            self._post_range_check()
             return None
         pp = torch.empty((B, self.H, self.W), dtype=torch.float32, device=self.device)
         raw = torch.empty((B, 2, self.H, self.W), dtype=torch.float32, device=self.device) if want_raw else None
         st = self.lib.sd_monodepth_forward(self.h, _ptr(frames), B, _ptr(pp), _ptr(raw), self._stream())
         L.check(self.lib, self.h, st, "sd_monodepth_forward")
-        self._post_range_check()
         return (pp, raw) if want_raw else pp
 
     def resize_cubic(self, frames: torch.Tensor, out_h: int | None = None, out_w: int | None = None) -> torch.Tensor:
@@ -361,14 +440,21 @@ class Engine:
         Returns device tensors: seg, disp_pp, fuse, records (sd_rw_result), f2f (sd_f2f_result or None) [, final clouds]."""
         if approach not in ("rw", "both"):
             raise ValueError("approach must be 'rw' or 'both' (semantic_depth.py:743-745)")
-        seg = self.fcn8s_forward(frames)
+        cams = list(cams)
+        out = self._process_batch(frames, cams, params, approach, fence_params, colours, want_final)
+        # ('recompute': ONE per-frame read behind both networks and the tail; the companion reruns the whole path on the flagged frames)
+        return self._settle(frames, out, lambda e, f: e.process_batch(f, [cams[i] for i in self.last_recomputed], params, approach,
+                                                                      fence_params, colours, want_final))
+
+    def _process_batch(self, frames, cams, params, approach, fence_params, colours, want_final):
+        seg = self._fcn8s(frames)
         if frames.shape[0] <= self.pass_frames:
             # the raw disparity pair stays in the activation arena: post-processing, back-projection and both gathers in ONE launch
-            self.monodepth_forward(frames, post_process=False)
+            self._mono(frames, False, False)
             fz = self.fuse_from_raw(seg["road"], seg["fence"], frames, cams, want_rgb=colours)
             disp_pp = fz["disp_pp"]
         else:
-            disp_pp = self.monodepth_forward(frames)
+            disp_pp = self._mono(frames, False, True)
             fz = self.fuse_backproject(disp_pp, seg["road"], seg["fence"], frames, cams, want_rgb=colours)
         out = dict(seg=seg, disp_pp=disp_pp, fuse=fz, f2f=None)
         rw = self.road_width(fz["road_xyz"], fz["n_road"], params, want_final=want_final, road_rgb=fz["road_rgb"] if colours else None)

@@ -412,6 +412,7 @@ class SequenceOutputs:
         self._staging = [dict(), dict()]                             # pinned host buffers per in-flight slot
         self._streams = None
         self.manifest = None
+        self.recomputed: list[int] = []                               # global indices of the frames recomputed on bf16x3 (on_range='recompute')
 
     # ---------------------------------------------------------------- driver interface
     def begin(self, rank: int, world: int, lo: int, hi: int):
@@ -443,6 +444,11 @@ class SequenceOutputs:
             ev.record(torch.cuda.current_stream(records.device))
         self._jobs.append(self._batches.submit(self._write_batch, slot, lo, records, tuple(size), images, final, ev))
 
+    def mark_recomputed(self, frames):
+        """global frame indices whose outputs came from the bf16x3 recompute (make_engine_step(on_range='recompute')): the manifest lists
+        their names under 'recomputed'"""
+        self.recomputed.extend(int(i) for i in frames)
+
     def close(self, status: str = "ok") -> str:
         """wait for every batch, then write this rank's manifest LAST: the files written and ``status`` ('ok'; 'range_error' / 'error':
         the run failed and the files listed are not valid outputs).  Returns the manifest path."""
@@ -462,7 +468,8 @@ class SequenceOutputs:
         self.manifest = os.path.join(self.directory, "manifest_rank{}.json".format(self.rank))
         files = sorted(os.path.relpath(p, self.directory) for p in self._files)
         with open(self.manifest, "w") as f:
-            json.dump(dict(rank=self.rank, world=self.world, frames=list(self.shard), status=status, valid=status == "ok", files=files), f, indent=1)
+            json.dump(dict(rank=self.rank, world=self.world, frames=list(self.shard), status=status, valid=status == "ok", files=files,
+                           recomputed=[self.names[i] for i in sorted(set(self.recomputed))]), f, indent=1)
         if err is not None:
             raise err
         return self.manifest
