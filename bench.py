@@ -35,6 +35,11 @@ Prints ONE JSON line on rank 0 (contract in the round prompt) with
   `f32_exact`    the exact-f32 engine's numbers (= the headline when --precision f32)
   `parity`       the outputs of the timed batch against the CPU oracle (and, for a reduced-precision headline, the f32 engine)
   `cpu_baseline` the CPU oracle timed on this box's host cores (bounded sample), all cores and 1 thread
+
+A plain run does only what the headline needs: setup, warm-up, the timed regions, --dump-outputs, the line.  `roofline` and
+`fusion_roofline` then carry only what the timed regions themselves measured (--no-overlap: per-launch events; the default --overlap:
+nothing, null), and `legs`, `parity` and `cpu_baseline` are null (`f32_exact` too, unless the headline is f32).  --full adds everything
+above: the untimed one-stream region behind `roofline` and the stage split, the legs, the parity sections and the CPU baseline.
 """
 import argparse
 import contextlib
@@ -114,8 +119,11 @@ def parse_args():
     ap.add_argument("--encoder", default="resnet50")
     ap.add_argument("--precision", default=os.environ.get("SD_BENCH_PRECISION", DEFAULT_PRECISION), choices=sorted(DTYPE),
                     help="conv arithmetic of the HEADLINE engine (default: the reference's precision)")
-    ap.add_argument("--legs", default=None, help="comma-separated engines timed beside the headline (N = 1 only); default 'plan' "
-                    "(plus 'f32' when the headline is not f32); 'none' = no legs")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the one-stream profile region (roofline, stage split), the legs, the parity sections and the "
+                         "CPU baseline; without it a run does only what `value` and `ms_per_step` need")
+    ap.add_argument("--legs", default=None, help="--full only: comma-separated engines timed beside the headline (N = 1 only); default every "
+                    "other engine of bf16x3, f16x2, f32, plan; 'none' = no legs")
     ap.add_argument("--plan", default=None, help="precision plan of the 'plan' engine instead of the built-in one: 'fcn layers|monodepth layers' "
                     "(sd_create_with_plan syntax; the line then says so)")
     ap.add_argument("--approach", default="rw", choices=["rw", "both"],
@@ -129,7 +137,10 @@ def parse_args():
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the headline engine's timed path returned in its last timed step as DIR/<name>.npy "
                          "(float32 / float64, at most 64 MB: per-pixel maps at a fixed seeded sample of pixels, clouds cut to their first points)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.legs not in (None, "", "none") and not args.full:
+        ap.error("--legs needs --full")
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -246,7 +257,7 @@ def main():
     if custom_plan is not None and len(custom_plan) != 2:
         raise SystemExit("--plan needs the form 'fcn layers|monodepth layers'")
     if args.legs is None:
-        legs = [] if args.no_f32_leg else [p_ for p_ in ("bf16x3", "f16x2", "f32", "plan") if p_ != args.precision]
+        legs = [] if args.no_f32_leg or not args.full else [p_ for p_ in ("bf16x3", "f16x2", "f32", "plan") if p_ != args.precision]
     else:
         legs = [] if args.legs in ("", "none") else [p_ for p_ in args.legs.split(",") if p_ != args.precision]
     for p_ in legs:
@@ -344,7 +355,7 @@ def main():
         # The two networks run on the main stream; with --overlap the per-frame tail of step i (back-projection, road chain, record
         # gather) runs on a side stream underneath the convolutions of step i+1; the default keeps everything on one stream.
         side_stream = torch.cuda.Stream(priority=args.side_priority) if args.overlap else None
-        st = {"fused_once": False, "side": side_stream}
+        st = {"fused_once": False, "side": side_stream, "one_stream": False}
 
         def instrumented_step():
             """one step, stage by stage with stream events (the same launches as Engine.process_batch / make_engine_step)"""
@@ -378,9 +389,10 @@ def main():
                     f2f = eng.fence_to_fence(fz["fence_xyz"], fz["n_fence"], rec, FenceParams(depth=prm.depth),
                                              fence_rgb=fz["fence_rgb"] if colours else None)
                 ev[6].record()
+            st["one_stream"] = side is None
             return dict(seg=seg, disp_pp=fz["disp_pp"], fuse=fz, records=rec, f2f=f2f), allr
 
-        dts, buckets = [], {}
+        dts, buckets, out = [], {}, None
 
         def read_buckets():
             for b_ in eng.profile_read():                          # HIP-event buckets (read outside the timed regions)
@@ -416,7 +428,7 @@ def main():
         # what the last timed step returned (config 5: the sequence driver returns the gathered records only)
         timed = {"out": out if args.config == 4 else None, "records": allrec}
         prof_dt = sum(dts)
-        if args.overlap:
+        if args.overlap and args.full:
             # the roofline evidence: one more region of --steps steps on ONE stream with the library's per-launch HIP events, untimed
             torch.cuda.synchronize()
             st["side"] = None
@@ -436,10 +448,11 @@ def main():
             prof_dt = time.perf_counter() - t0
             read_buckets()
         eng.profile(False)
-        if args.config == 5:                                       # stage split + report tensors from one more (untimed) instrumented step
+        if args.config == 5 and args.full:                         # stage split + report tensors from one more (untimed) instrumented step
             out, _ = instrumented_step()
             torch.cuda.synchronize()
-        stage_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(6)]   # of the LAST step (events are only read after the timed regions)
+        # of the LAST step (events are only read after the timed regions), when it ran on one stream: a plain run under --overlap has none
+        stage_ms = [ev[i].elapsed_time(ev[i + 1]) for i in range(6)] if st["one_stream"] else None
         assert allrec.shape[0] == world * B
         dt_mean = sum(dts) / len(dts)
         res = {"label": label, "dts": dts, "dt_mean": dt_mean, "value": world * B * args.steps / dt_mean, "buckets": list(buckets.values()),
@@ -447,8 +460,9 @@ def main():
                "stage_ms": stage_ms, "out": out, "timed": timed}
         if rank == 0:
             log(f"[{label}] {res['value']:.1f} frames/s ({dt_mean / args.steps * 1e3:.2f} ms/step; regions " +
-                ", ".join(f"{d / args.steps * 1e3:.2f}" for d in dts) + f" ms/step); stage ms of the last step: resize {stage_ms[0]:.2f}  "
-                f"seg {stage_ms[1]:.2f}  disp {stage_ms[2]:.2f}  to3D {stage_ms[3]:.2f}  road {stage_ms[4]:.2f}")
+                ", ".join(f"{d / args.steps * 1e3:.2f}" for d in dts) + " ms/step)" +
+                (f"; stage ms of the last step: resize {stage_ms[0]:.2f}  seg {stage_ms[1]:.2f}  disp {stage_ms[2]:.2f}  to3D {stage_ms[3]:.2f}  "
+                 f"road {stage_ms[4]:.2f}" if stage_ms else ""))
         return res
 
     def outputs_of(eng):
@@ -480,16 +494,16 @@ def main():
         return {"value": round(res["value"], 3), "unit": "frames/s", "ms_per_step": round(res["dt_mean"] / args.steps * 1e3, 3),
                 "steps": args.steps, "warmup": args.warmup, "repeats": len(res["dts"]),
                 "repeat_ms_per_step": [round(d / args.steps * 1e3, 3) for d in res["dts"]], "dtype": DTYPE[precision],
-                "stage_ms_last_step": {"resize": round(res["stage_ms"][0], 2), "seg": round(res["stage_ms"][1], 2), "disp": round(res["stage_ms"][2], 2),
-                                       "to3D": round(res["stage_ms"][3], 2), "road": round(res["stage_ms"][4], 2),
-                                       **({"fence": round(res["stage_ms"][5], 2)} if args.approach == "both" else {})},
+                **({"stage_ms_last_step": {"resize": round(res["stage_ms"][0], 2), "seg": round(res["stage_ms"][1], 2), "disp": round(res["stage_ms"][2], 2),
+                                           "to3D": round(res["stage_ms"][3], 2), "road": round(res["stage_ms"][4], 2),
+                                           **({"fence": round(res["stage_ms"][5], 2)} if args.approach == "both" else {})}} if res["stage_ms"] else {}),
                 **({"tail_overlap": {"on": True, "side_stream_priority": args.side_priority, "reserved_cus": args.reserve_cus,
                                      "ms_per_step_one_stream": round(res["prof_ms_per_step"], 3),
                                      "frames_per_s_one_stream": round(world * B * 1e3 / res["prof_ms_per_step"], 3),
                                      "tail_ms_exposed": round(res["dt_mean"] / args.steps * 1e3 - sum(res["stage_ms"][:3]), 3),
                                      "note": "timed regions: the tail of step i (back-projection, road chain, record gather) runs on a side stream under "
                                              "the convolutions of step i+1; stage_ms_last_step and the roofline durations come from the extra "
-                                             "one-stream region"}} if args.overlap and args.config == 4 else {}),
+                                             "one-stream region"}} if args.overlap and args.config == 4 and res["stage_ms"] else {}),
                 **({"fp16_saturated_values": sat} if sat is not None else {}), **pl, "roofline": rl}
 
     eng = make_engine(args.precision)
@@ -509,28 +523,34 @@ def main():
             dist.destroy_process_group()
         return
 
-    out, stage_ms, dt = head["out"], head["stage_ms"], head["dt_mean"]
-    recs = Engine.records(out["records"])
-    road_frac = float(out["seg"]["road"].float().mean().item())
-    log(f"masks: road fraction {road_frac:.3f}; n_road mean {recs['n_road'].mean():.0f}; after chain {recs['n_ror'].mean():.0f}; "
-        f"found {int(recs['found'].sum())}/{B}; width mean {np.nanmean(recs['width']) if recs['found'].any() else float('nan'):.3f}")
+    out, stage_ms = head["out"], head["stage_ms"]
+    masks = {}                # (config 5: out exists under --full only)
+    if out is not None:
+        recs = Engine.records(out["records"])
+        road_frac = float(out["seg"]["road"].float().mean().item())
+        log(f"masks: road fraction {road_frac:.3f}; n_road mean {recs['n_road'].mean():.0f}; after chain {recs['n_ror'].mean():.0f}; "
+            f"found {int(recs['found'].sum())}/{B}; width mean {np.nanmean(recs['width']) if recs['found'].any() else float('nan'):.3f}")
+        masks = {"road_fraction": round(road_frac, 4), "n_road_mean": float(recs["n_road"].mean()), "n_after_chain_mean": float(recs["n_ror"].mean()),
+                 "found": int(recs["found"].sum())}
     head_rec = leg_record(eng, args.precision, head)
     roofline = head_rec.pop("roofline")
-    # second roofline: the fusion / back-projection stage is HBM-bound.  Algorithmic bytes of the stage as it runs
-    # here (one launch): read the raw disparity pair (8 B) + two masks (2 B) + the frame (3 B) per pixel, write disp_pp (4 B) per
-    # pixel and 15 B (xyz f32 + rgb u8) per gathered point.
-    n_pts = float(out["fuse"]["n_road"].sum().item()) + float(out["fuse"]["n_fence"].sum().item())
-    fuse_bytes = B * H * W * 17.0 + (15.0 if colours else 12.0) * n_pts
-    fuse_gbs = fuse_bytes / (stage_ms[3] * 1e-3) / 1e9 if stage_ms[3] > 0 else 0.0
-    fuse_traffic, fuse_traffic_src = pmc_traffic("fuse_onepass_kernel", "*pmc_fuse_traffic.json")
-    fusion_roofline = {"bound": "hbm", "achieved": round(fuse_gbs, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(fuse_gbs / 8000.0, 4),
-                       "traffic": fuse_traffic, "traffic_source": fuse_traffic_src, "kernel_short": "fuse_onepass_kernel",
-                       "kernel": "fuse_onepass_kernel (post-processing + back-projection + look-back gather; to3D stage of the last step, stream events)",
-                       "algorithmic_bytes": round(fuse_bytes), "algorithmic_bytes_per_frame": round(fuse_bytes / B),
-                       "stage_us_per_frame": round(stage_ms[3] * 1e3 / B, 2)}
+    fusion_roofline = None
+    if out is not None and stage_ms is not None:
+        # second roofline: the fusion / back-projection stage is HBM-bound.  Algorithmic bytes of the stage as it runs
+        # here (one launch): read the raw disparity pair (8 B) + two masks (2 B) + the frame (3 B) per pixel, write disp_pp (4 B) per
+        # pixel and 15 B (xyz f32 + rgb u8) per gathered point.
+        n_pts = float(out["fuse"]["n_road"].sum().item()) + float(out["fuse"]["n_fence"].sum().item())
+        fuse_bytes = B * H * W * 17.0 + (15.0 if colours else 12.0) * n_pts
+        fuse_gbs = fuse_bytes / (stage_ms[3] * 1e-3) / 1e9 if stage_ms[3] > 0 else 0.0
+        fuse_traffic, fuse_traffic_src = pmc_traffic("fuse_onepass_kernel", "*pmc_fuse_traffic.json")
+        fusion_roofline = {"bound": "hbm", "achieved": round(fuse_gbs, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(fuse_gbs / 8000.0, 4),
+                           "traffic": fuse_traffic, "traffic_source": fuse_traffic_src, "kernel_short": "fuse_onepass_kernel",
+                           "kernel": "fuse_onepass_kernel (post-processing + back-projection + look-back gather; to3D stage of the last step, stream events)",
+                           "algorithmic_bytes": round(fuse_bytes), "algorithmic_bytes_per_frame": round(fuse_bytes / B),
+                           "stage_us_per_frame": round(stage_ms[3] * 1e3 / B, 2)}
 
     # ------------------------------------------------------------------ legs (N = 1): the other engines, timed the same way, and parity
-    want_parity = world == 1
+    want_parity = world == 1 and args.full
     parity, leg_out, f32_exact, oracle_in = {}, {}, None, None
     outs = {}
     if want_parity:
@@ -560,7 +580,7 @@ def main():
 
     # ------------------------------------------------------------------ CPU baseline: the oracle on this box's host cores
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         cpu, parity["vs_cpu_oracle"] = cpu_baseline(state["frames"].cpu().numpy(), wf, wm, args.encoder, cam, oracle_in, eng, prm, log)
         for p_ in leg_out:      # the legs against the same oracle outputs
             if p_ in outs and cpu_baseline.last_ref is not None:
@@ -585,17 +605,16 @@ def main():
                    # 3x3 conv on the upsampled tensor); the reference graph as written: FCN-8s 443.19 + 2 x monodepth-resnet50 179.92
                    **({"gflop_per_frame_reference_graph": 803.03} if (H, W, args.encoder) == (512, 1024, "resnet50") else {}),
                    "camera": {"cx": cam.cx, "cy": cam.cy, "f": cam.f, "b": cam.b, "disp_mult": cam.disp_mult},
-                   "stage_ms_last_step": head_rec["stage_ms_last_step"],
+                   **({"stage_ms_last_step": head_rec["stage_ms_last_step"]} if "stage_ms_last_step" in head_rec else {}),
                    "approach": args.approach, "engine": args.precision,
-                   "colours_through_road_chain": colours, "overlap": bool(args.overlap),
+                   "colours_through_road_chain": colours, "overlap": bool(args.overlap), "full": bool(args.full),
                    **({"from_disk": True, "decode_threads_per_rank": __import__("semantic_depth_amd.frame_io", fromlist=["x"]).default_decode_workers(),
                        "input_stage": "PNG files on disk -> native decode (this rank's shard only) -> pinned staging -> upload, inside the timed region"}
                       if args.from_disk else {}),
                    **({k: head_rec[k] for k in ("precision_plan", "built_in_plan") if k in head_rec}),
                    **({"fp16_saturated_values": head_rec["fp16_saturated_values"]} if "fp16_saturated_values" in head_rec else {}),
                    **({"tail_overlap": head_rec["tail_overlap"]} if "tail_overlap" in head_rec else {}),
-                   "road_fraction": round(road_frac, 4), "n_road_mean": float(recs["n_road"].mean()), "n_after_chain_mean": float(recs["n_ror"].mean()),
-                   "found": int(recs["found"].sum())},
+                   **masks},
         "roofline": roofline, "fusion_roofline": fusion_roofline, "f32_exact": f32_exact, "legs": leg_out or None, "parity": parity or None,
         "cpu_baseline": cpu,
     }
@@ -696,7 +715,7 @@ def compact_line(d: dict) -> dict:
     figures, `legs` (and `f32_exact`) as {value, ms_per_step, dtype, roofline.frac, parity max-rels, fp16_saturated_values}"""
     cfg = d["config"]
     ccfg = {k: cfg[k] for k in ("library", "workload", "survey_config", "frames_per_step", "gflop_per_frame", "gflop_per_frame_reference_graph", "engine",
-                                "approach", "overlap", "stage_ms_last_step", "fp16_saturated_values", "from_disk", "decode_threads_per_rank",
+                                "approach", "overlap", "full", "stage_ms_last_step", "fp16_saturated_values", "from_disk", "decode_threads_per_rank",
                                 "road_fraction", "n_road_mean", "n_after_chain_mean", "found", "built_in_plan") if k in cfg}
     if "tail_overlap" in cfg:
         ccfg["tail_overlap"] = {k: cfg["tail_overlap"][k] for k in ("on", "side_stream_priority", "reserved_cus", "ms_per_step_one_stream", "frames_per_s_one_stream",

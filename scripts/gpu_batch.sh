@@ -23,5 +23,5 @@ for prec in f16x2 bf16x3; do
   timeout 300 python scripts/layer_times.py 32 resnet50 $prec 2> $o/layer_times_$prec.txt >/dev/null
 done
 timeout 900 python scripts/f32_grade_check.py --pairs 8 --extra > $o/f32_grade_check.txt 2> $o/f32_grade_check.log
-timeout 1200 python bench.py --steps 20 --detail $o/bench_detail.json > $o/bench_default.json 2> $o/bench_default.log
+timeout 1200 python bench.py --full --steps 20 --detail $o/bench_detail.json > $o/bench_default.json 2> $o/bench_default.log
 grep 'frames/s' $o/bench_default.log | cut -c1-200

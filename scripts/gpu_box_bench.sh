@@ -7,7 +7,8 @@ o=$PWD/gpurun_out/${1:-r06box}
 other=${2:-.r05tree}
 mkdir -p $o
 run() {  # tree label
-  ( cd $1 && timeout 600 python bench.py --precision f16x2 --legs bf16x3,plan --no-cpu-baseline --steps 10 > $o/bench_$2.json 2> $o/bench_$2.log )
+  full=$(grep -q -- '"--full"' $1/bench.py && echo --full)     # (a tree older than --full times its legs without it)
+  ( cd $1 && timeout 600 python bench.py $full --precision f16x2 --legs bf16x3,plan --no-cpu-baseline --steps 10 > $o/bench_$2.json 2> $o/bench_$2.log )
   grep 'frames/s' $o/bench_$2.log | cut -c1-150 | sed "s/^/$2 /"
 }
 run . this_1

@@ -91,3 +91,28 @@ def test_the_stdout_line_of_a_full_size_record_stays_under_8_kb():
     assert line["parity"]["vs_cpu_oracle"]["logits_max_rel"] < 1e-3
     # every dtype string of the line is a short one
     assert all(len(s_) < 160 for s_ in bench.DTYPE.values())
+
+
+def test_a_plain_record_gives_a_line_with_the_contract_keys():
+    """a run without --full measures no roofline region, no legs, no parity and no CPU baseline: the record then carries those as null
+    and no stage split or tail-overlap figures, and compact_line must still give the contract's keys with the headline's numbers."""
+    import json
+    bench = _bench_module()
+    full = json.load(open(os.path.join(ROOT, "profiles", "r05_bench_default.json")))
+    for k in ("roofline", "fusion_roofline", "f32_exact", "legs", "parity", "cpu_baseline"):
+        full[k] = None
+    for k in ("stage_ms_last_step", "tail_overlap", "road_fraction", "n_road_mean", "n_after_chain_mean", "found"):
+        full["config"].pop(k, None)
+    full["config"]["full"] = False
+    line = bench.compact_line(full)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[k] == full[k], k
+    for k in ("roofline", "fusion_roofline", "f32_exact", "legs", "parity", "cpu_baseline"):
+        assert line[k] is None, k
+    assert line["config"]["full"] is False and "stage_ms_last_step" not in line["config"]
+
+
+def test_legs_need_full():
+    r = _run(["--legs", "f32"])
+    assert r.returncode != 0 and "--legs needs --full" in r.stderr
+    assert r.stdout.strip() == ""
