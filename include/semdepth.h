@@ -31,7 +31,8 @@ enum {
     SD_ERR_INVALID = -1,   /* bad argument */
     SD_ERR_HIP = -2,       /* HIP runtime error (text in sd_last_error) */
     SD_ERR_STATE = -3,     /* call order violated (e.g. forward before weights are loaded) */
-    SD_ERR_NOTFOUND = -4   /* unknown weight / tensor name */
+    SD_ERR_NOTFOUND = -4,  /* unknown weight / tensor name */
+    SD_ERR_FORMAT = -5     /* sd_decode_files_jpeg_coef: the file is readable but not a JPEG -- decode it with sd_decode_files_bgr */
 };
 
 typedef enum { SD_ENC_VGG = 0, SD_ENC_RESNET50 = 1 } sd_encoder;      /* semantic_depth.py:721-722 --encoder */
@@ -197,6 +198,52 @@ sd_status sd_image_decode_bgr(const uint8_t* file_host, size_t len, uint8_t* bgr
  * PNG of that shape).  Returns SD_OK when every file decoded. */
 sd_status sd_decode_files_bgr(const char* const* paths, int n, int height, int width, uint8_t* out_host, size_t frame_stride, int threads,
                               int* status_out);
+/* ---- JPEG frames, split route: entropy decoding on the host, everything behind it on the GPU ----
+ * What the reconstruction of one JPEG frame needs besides its quantised coefficients, and nothing else.  height / width are the STORED
+ * size (before the EXIF orientation); orientation is 1..8; adobe_transform is the APP14 flag (-1: no Adobe marker, 0: the components are
+ * R, G, B).  Component 0 is sampled hmax x vmax, components 1 and 2 are sampled 1 x 1 (hmax x vmax is 1x1, 2x1 or 2x2; 1x1 for ncomp 1).
+ * blocks_w / blocks_h: 8x8 blocks per row / column of the component's padded plane.  coef_offset: element (int16) offset of the
+ * component's first block in the frame's coefficient buffer -- the components follow each other without gaps, component 0 at 0.
+ * qt: the component's quantisation table in natural (row-major) order. */
+typedef struct {
+    int32_t height, width;
+    int32_t ncomp, hmax, vmax;
+    int32_t orientation, adobe_transform;
+    int32_t reserved;                 /* 0 */
+    int32_t blocks_w[3], blocks_h[3];
+    int64_t coef_offset[3];
+    uint16_t qt[3][64];
+} sd_jpeg_frame_desc;
+/* HOST: the front half of sd_jpeg_decode_bgr.  Huffman-decodes the file and writes the QUANTISED coefficients of every 8x8 block of the
+ * padded component planes to coef_out_host: natural order inside a block, blocks row-major, components one after the other
+ * (desc_out->coef_offset).  Baseline, extended-sequential and progressive files alike; no sample plane is allocated.
+ * coef_out_host NULL: parses up to the first SOS and fills only *desc_out (its qt entries are final only after a full call); the full
+ * call needs 2 * (coef_offset[ncomp-1] + 64 * blocks_w[ncomp-1] * blocks_h[ncomp-1]) bytes.  capacity_bytes below that: SD_ERR_INVALID
+ * before anything is allocated or written.  Accepts exactly the files sd_jpeg_decode_bgr accepts, with the same status otherwise. */
+sd_status sd_jpeg_decode_coefficients(const uint8_t* file_host, size_t len, int16_t* coef_out_host, size_t capacity_bytes,
+                                      sd_jpeg_frame_desc* desc_out);
+/* HOST: the back half of sd_jpeg_decode_bgr driven from a coefficient buffer (dequantise, ISLOW inverse DCT, fancy upsampling, colour,
+ * orientation; the code the one-call decoder runs): sd_jpeg_reconstruct_bgr_host after sd_jpeg_decode_coefficients writes the bytes
+ * of sd_jpeg_decode_bgr.  It is the CPU statement of sd_jpeg_reconstruct_bgr.  u8 [height,width,3] BGR AFTER the orientation;
+ * SD_ERR_INVALID for a descriptor that is not self-consistent or out_capacity < height * width * 3. */
+sd_status sd_jpeg_reconstruct_bgr_host(const int16_t* coef_host, const sd_jpeg_frame_desc* desc, uint8_t* bgr_out_host, size_t out_capacity);
+/* HOST: the batch reader beside sd_decode_files_bgr for the split route: file i -> coefficients at coef_out_host + i * frame_stride_bytes
+ * (e.g. a pinned staging buffer) and descs_out[i], on `threads` native threads (<= 0: one per host CPU).  height x width is the size
+ * AFTER the orientation every frame must have.  status_out (nullable, int[n]): SD_ERR_NOTFOUND unreadable file; SD_ERR_FORMAT a readable
+ * file that is not a JPEG (nothing written for it: send it down the BGR route); SD_ERR_INVALID a JPEG that is refused, has another
+ * size or needs more than frame_stride_bytes.  Returns SD_OK when every status is SD_OK or SD_ERR_FORMAT, else SD_ERR_INVALID. */
+sd_status sd_decode_files_jpeg_coef(const char* const* paths, int n, int height, int width, int16_t* coef_out_host, size_t frame_stride_bytes,
+                                    sd_jpeg_frame_desc* descs_out, int threads, int* status_out);
+/* bytes of device workspace sd_jpeg_reconstruct_bgr needs for these B frames (their padded u8 component planes) */
+sd_status sd_jpeg_reconstruct_workspace(const sd_jpeg_frame_desc* descs_host, int B, size_t* bytes_out);
+/* DEVICE: B frames' coefficients (frame b at coef_dev + b * frame_stride_bytes, laid out as sd_jpeg_decode_coefficients writes them) ->
+ * u8 [height,width,3] BGR after the orientation at bgr_dev + b * bgr_frame_stride, the integers of sd_jpeg_decode_bgr for every stream it
+ * accepts.  Two kernels per group of 8 frames (dequantise + inverse DCT into the padded planes of the workspace; upsample + colour +
+ * orientation); the descriptors travel as kernel arguments, so descs_host may be reused when the call returns.  Enqueued on `stream`, no
+ * synchronisation; the handle need not be bound.  SD_ERR_INVALID: a descriptor that is not self-consistent, coefficients beyond
+ * frame_stride_bytes, a frame beyond bgr_frame_stride, workspace_bytes below sd_jpeg_reconstruct_workspace -- nothing is launched. */
+sd_status sd_jpeg_reconstruct_bgr(sd_handle* h, const int16_t* coef_dev, size_t frame_stride_bytes, const sd_jpeg_frame_desc* descs_host, int B,
+                                  uint8_t* bgr_dev, size_t bgr_frame_stride, void* workspace_dev, size_t workspace_bytes, void* stream);
 /* HOST: the writer behind the sequence tool's cv2.imwrite('<dir>/<name>.png', frame) (seq:336): encodes n u8 [height,width,3] BGR frames at
  * frames_host + i * frame_stride as 8-bit RGB PNGs (filter type 0 rows, one zlib stream at `level` 0..9) and writes them to paths[i], on
  * `threads` native threads (<= 0: one per host CPU).  Pixel-exact, not byte-identical to OpenCV's file: sd_png_decode_bgr reads each

@@ -1,67 +1,147 @@
 """Input-stage feed rate (dev tool, run on the GPU box): can the host keep the GPU supplied at the benchmarked
-frames/s?  Measures, for Cityscapes-sized 1024 x 2048 frames:
-  decode    frame_io.imread (zlib inflate + sd_png_unfilter_bgr) per core and with a thread pool
+frames/s?  Measures, for frames of one size (default: generated Cityscapes-sized 1024 x 2048 PNGs):
+  decode    one thread per frame (whole decode; for JPEG also the coefficient-only half of the split route) and the native batch reader
   upload    pinned host -> HBM copy of decoded frames
-  resize    Engine.resize_cubic 1024x2048 -> 512x1024 on the GPU
-  feeder    frame_io.FrameFeeder end to end (decode + pinned upload, one batch ahead)
-    python scripts/feed_rate.py [--frames 256] [--workers 128] [--out profiles/r03_feed_rate.json]
+  resize    Engine.resize_cubic to 512 x 1024 on the GPU
+  feeder    frame_io.FrameFeeder end to end (decode + pinned upload + resize, one batch ahead), best and median of --repeats passes
+    python scripts/feed_rate.py [--frames 256] [--workers N] [--format png|jpeg] [--jpeg host|device] [--frames-dir DIR] [--out FILE]
+--frames-dir times the *.png / *.jpg files of a directory instead of generating frames (JPEG frames cannot be written here without
+Pillow, which a GPU box may lack: write them elsewhere and ship them).  --jpeg device feeds through FrameFeeder(jpeg="device"): Huffman
+decoding on the host, reconstruction on the GPU; the script passes jpeg= only then, so --jpeg host also runs in a tree that lacks the
+split route (the parent commit's, for an A/B of the host route).  Nothing is written unless --out is given.
 """
 import argparse
+import ctypes as C
+import glob
 import json
 import os
 import sys
 import tempfile
 import time
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+from semantic_depth_amd import _lib as L                    # noqa: E402
 from semantic_depth_amd import frame_io, outputs            # noqa: E402
 from semantic_depth_amd.engine import Engine                # noqa: E402
+
+
+def _generate(td, n, fmt):
+    H, W = 1024, 2048
+    rng = np.random.default_rng(0)
+    # street-like content: smooth gradients + texture noise (PNG of pure noise does not compress; real frames do, ~2.2 MB each)
+    yy, xx = np.mgrid[0:H, 0:W]
+    paths = []
+    for i in range(n):
+        base = np.stack([(yy // 3 + xx // 5 + 7 * i) % 256, (xx // 4 + 3 * i) % 256, (yy // 2 + xx // 7) % 256], -1).astype(np.uint8)
+        img = base ^ rng.integers(0, 4, (H, W, 3), dtype=np.uint8)
+        if fmt == "png":
+            paths.append(outputs.write_png(os.path.join(td, f"f{i:05d}.png"), img, level=6))
+        else:
+            from PIL import Image
+            p = os.path.join(td, f"f{i:05d}.jpg")
+            Image.fromarray(img[..., ::-1]).save(p, "JPEG", quality=90, subsampling=2)
+            paths.append(p)
+    return paths
+
+
+def _single_thread_ms(paths, res):
+    """whole decode of one frame on one thread; for JPEG files, where the library has the split route, also its host half alone"""
+    lib = L.load()
+    bufs = [open(p, "rb").read() for p in paths[:8]]
+    frame_io.decode_image(bufs[0])
+    t0 = time.perf_counter()
+    for b in bufs:
+        frame_io.decode_image(b)
+    res["decode_ms_per_frame_1_thread"] = (time.perf_counter() - t0) / len(bufs) * 1e3
+    if "sd_jpeg_decode_coefficients" in L.SIGNATURES and all(b[:2] == b"\xff\xd8" for b in bufs):
+        d = L.sd_jpeg_frame_desc()
+        assert lib.sd_jpeg_decode_coefficients(bufs[0], len(bufs[0]), None, 0, C.byref(d)) == L.SD_OK
+        h, w = d.oriented_size()
+        coef = np.empty(frame_io.FrameFeeder.coef_stride_bytes(h, w) // 2, np.int16)
+        lib.sd_jpeg_decode_coefficients(bufs[0], len(bufs[0]), coef.ctypes.data_as(C.c_void_p), coef.nbytes, C.byref(d))
+        t0 = time.perf_counter()
+        for b in bufs:
+            assert lib.sd_jpeg_decode_coefficients(b, len(b), coef.ctypes.data_as(C.c_void_p), coef.nbytes, C.byref(d)) == L.SD_OK
+        res["coefficients_ms_per_frame_1_thread"] = (time.perf_counter() - t0) / len(bufs) * 1e3
+
+
+def _kernel_ms_per_batch(eng, paths, workers, res):
+    """HIP-event time of Engine.jpeg_reconstruct (the two kernels, four launches each for 32 frames) on one resident batch"""
+    lib = L.load()
+    n = min(32, len(paths))
+    with open(paths[0], "rb") as f:
+        h, w = frame_io.image_size(f.read())
+    stride = frame_io.FrameFeeder.coef_stride_bytes(h, w)
+    coef = torch.empty((n, stride // 2), dtype=torch.int16, pin_memory=True)
+    descs = (L.sd_jpeg_frame_desc * n)()
+    arr = (C.c_char_p * n)(*[os.fsencode(p) for p in paths[:n]])
+    t0 = time.perf_counter()
+    assert lib.sd_decode_files_jpeg_coef(arr, n, h, w, C.c_void_p(coef.data_ptr()), stride, descs, workers, None) == L.SD_OK
+    res["coefficients_ms_per_batch_native"] = (time.perf_counter() - t0) * 1e3
+    cdev = coef.cuda()
+    out = eng.jpeg_reconstruct(cdev, descs)
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(7):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        eng.jpeg_reconstruct(cdev, descs, out=out)
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    res["reconstruct_kernels_ms_per_batch"] = {"frames": n, "median": float(np.median(times)), "min": float(min(times)), "max": float(max(times))}
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=256)
-    ap.add_argument("--workers", type=int, default=min(128, os.cpu_count() or 8))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r03_feed_rate.json"))
+    ap.add_argument("--workers", type=int, default=frame_io.default_decode_workers())
+    ap.add_argument("--format", choices=("png", "jpeg"), default="png")
+    ap.add_argument("--jpeg", choices=("host", "device"), default="host")
+    ap.add_argument("--frames-dir", default=None, help="time the *.png / *.jpg / *.jpeg files of this directory (one size) instead of generating frames")
+    ap.add_argument("--repeats", type=int, default=3, help="timed passes of the feeder after one warm pass")
+    ap.add_argument("--out", default=None, help="write the JSON record here (default: print only)")
     a = ap.parse_args()
-    H, W = 1024, 2048
-    rng = np.random.default_rng(0)
-    res = {"frame": [H, W, 3], "host_cpus": os.cpu_count(), "workers": a.workers}
     with tempfile.TemporaryDirectory() as td:
-        # street-like content: smooth gradients + texture noise (PNG of pure noise does not compress; real frames do, ~2.2 MB each)
-        yy, xx = np.mgrid[0:H, 0:W]
-        paths = []
-        for i in range(a.frames):
-            base = np.stack([(yy // 3 + xx // 5 + 7 * i) % 256, (xx // 4 + 3 * i) % 256, (yy // 2 + xx // 7) % 256], -1).astype(np.uint8)
-            img = base ^ rng.integers(0, 4, (H, W, 3), dtype=np.uint8)
-            paths.append(outputs.write_png(os.path.join(td, f"f{i:05d}.png"), img, level=6))
-        res["png_bytes_mean"] = float(np.mean([os.path.getsize(p) for p in paths]))
-        t0 = time.perf_counter()
-        for p in paths[:8]:
-            frame_io.imread(p)
-        res["decode_ms_per_frame_1_thread"] = (time.perf_counter() - t0) / 8 * 1e3
-        with ThreadPoolExecutor(a.workers) as ex:
-            list(ex.map(frame_io.imread, paths[:a.workers]))            # warm
-            t0 = time.perf_counter()
-            list(ex.map(frame_io.imread, paths))
-            res["decode_fps_python_thread_pool"] = a.frames / (time.perf_counter() - t0)
-        # the native batch reader (what FrameFeeder calls): all files -> one host buffer, `workers` C++ threads
-        import ctypes as C
-        from semantic_depth_amd import _lib as L
+        if a.frames_dir:
+            paths = sorted(p for e in ("*.png", "*.jpg", "*.jpeg") for p in glob.glob(os.path.join(a.frames_dir, e)))
+            if not paths:
+                raise SystemExit(f"no frames in {a.frames_dir}")
+            paths = (paths * (-(-a.frames // len(paths))))[:a.frames]      # (cycled to --frames: the page cache holds them either way)
+        else:
+            paths = _generate(td, a.frames, a.format)
+        with open(paths[0], "rb") as f:
+            H, W = frame_io.image_size(f.read())
+        res = {"frame": [H, W, 3], "frames": len(paths), "distinct_files": len(set(paths)), "host_cpus": os.cpu_count(), "workers": a.workers,
+               "format": "dir" if a.frames_dir else a.format, "jpeg": a.jpeg, "file_bytes_mean": float(np.mean([os.path.getsize(p) for p in set(paths)]))}
+        all_png = all(p.lower().endswith(".png") for p in paths)
+        if all_png:
+            res["png_bytes_mean"] = res["file_bytes_mean"]                  # (the key of the earlier PNG records)
+        _single_thread_ms(paths, res)
+        if all_png:                                                         # the Python-level pool of the earlier PNG records
+            from concurrent.futures import ThreadPoolExecutor
+            with ThreadPoolExecutor(a.workers) as ex:
+                list(ex.map(frame_io.imread, paths[:a.workers]))            # warm
+                t0 = time.perf_counter()
+                list(ex.map(frame_io.imread, paths))
+                res["decode_fps_python_thread_pool"] = len(paths) / (time.perf_counter() - t0)
+        # the native batch reader (what FrameFeeder calls): files -> one host buffer, `workers` C++ threads (PNG: all frames, as the
+        # earlier records; JPEG frames may be 36 MB each decoded, so at most 64 of them)
         lib = L.load()
-        hostbuf = np.empty((a.frames, H, W, 3), np.uint8)
-        arr = (C.c_char_p * a.frames)(*[p.encode() for p in paths])
+        nb = len(paths) if all_png else min(len(paths), 64)
+        hostbuf = np.empty((nb, H, W, 3), np.uint8)
+        arr = (C.c_char_p * nb)(*[os.fsencode(p) for p in paths[:nb]])
         for _ in range(2):
             t0 = time.perf_counter()
-            st = lib.sd_decode_files_bgr(arr, a.frames, H, W, hostbuf.ctypes.data_as(C.c_void_p), H * W * 3, a.workers, None)
+            st = lib.sd_decode_files_bgr(arr, nb, H, W, hostbuf.ctypes.data_as(C.c_void_p), H * W * 3, a.workers, None)
             dt = time.perf_counter() - t0
         assert st == 0
-        res["decode_fps_native_batch"] = a.frames / dt
+        res["decode_fps_native_batch"] = nb / dt
+        del hostbuf
         if torch.cuda.is_available():
             host = torch.empty((32, H, W, 3), dtype=torch.uint8, pin_memory=True)
             dev = torch.empty((32, H, W, 3), dtype=torch.uint8, device="cuda")
@@ -74,23 +154,33 @@ def main():
             res["upload_gb_per_s"] = host.numel() / dt / 1e9
             res["upload_fps"] = 32 / dt
             eng = Engine(512, 1024, 32, "resnet50", precision="bf16x2")
-            for fr, lo in frame_io.FrameFeeder(paths[:64], 32, "cuda", a.workers):        # warm (pinned staging allocation)
-                pass
             eng.resize_cubic(dev); torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(5):
                 eng.resize_cubic(dev)
             torch.cuda.synchronize()
             res["resize_fps"] = 32 * 5 / (time.perf_counter() - t0)
-            t0 = time.perf_counter()
-            n = 0
-            for fr, lo in frame_io.FrameFeeder(paths, 32, "cuda", a.workers):
-                eng.resize_cubic(fr)
-                n += fr.shape[0]
-            torch.cuda.synchronize()
-            res["feeder_fps_decode_upload_resize"] = n / (time.perf_counter() - t0)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    json.dump(res, open(a.out, "w"), indent=1)
+            del host, dev
+            kw = {"jpeg": "device", "engine": eng} if a.jpeg == "device" else {}      # (nothing the parent commit's feeder lacks in host mode)
+            if a.jpeg == "device":
+                _kernel_ms_per_batch(eng, paths, a.workers, res)
+            rates = []
+            for rep in range(a.repeats + 1):                                          # pass 0 warms (pinned staging allocation, page cache)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                n = 0
+                with frame_io.FrameFeeder(paths if rep else paths[:64], 32, "cuda", a.workers, **kw) as feeder:
+                    for fr, lo in feeder:
+                        eng.resize_cubic(fr)
+                        n += fr.shape[0]
+                torch.cuda.synchronize()
+                if rep:
+                    rates.append(n / (time.perf_counter() - t0))
+            res["feeder_fps_decode_upload_resize"] = float(np.median(rates))
+            res["feeder_fps_passes"] = rates
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
     print(json.dumps(res, indent=1))
 
 

@@ -4,6 +4,9 @@
 // Round 3's byte-level mutations missed two structural holes (an over-subscribed DHT, a second SOF): kinds 6-9 below rewrite JPEG segments
 // (DHT count bytes, duplicated / inserted SOF / SOS / DRI segments, SOF0 <-> SOF2 swaps); tests/test_frame_io.py::_crafted_jpegs holds the PoCs.
 // Mutated JPEG / PNG files go through the C-ABI decoders from exact-size heap copies; nothing may crash or read out of bounds.
+// JPEG mutations also go through the split route's two host entry points (sd_jpeg_decode_coefficients, sd_jpeg_reconstruct_bgr_host): the two
+// routes must accept the same files and, where both do, write the same pixels.  Seed it with non-interleaved sequential files too (one scan
+// per component; tests/jpeg_cases.py::accepted_crafted_jpegs): only there can a mutation leave a component without a scan.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -74,7 +77,34 @@ int main(int argc, char** argv) {
             uint8_t* oc = (uint8_t*)malloc(cap ? cap : 1);
             sd_status s = sd_image_decode_bgr(fc, f.size(), oc, cap, &h, &w);
             if (s == SD_OK) ++ok; else ++bad;
-            free(oc); free(fc);
+            if (jpg) {
+                // the split route on the same mutation: coefficient decoder into an exact-size (or too small) heap buffer, then the host
+                // reconstruction from it; the two routes must agree on what they accept when neither is short of room
+                sd_jpeg_frame_desc d;
+                const sd_status sq = sd_jpeg_decode_coefficients(fc, f.size(), nullptr, 0, &d);
+                if (sq == SD_OK) {
+                    size_t elems = 0;
+                    for (int i = 0; i < d.ncomp; ++i) elems += (size_t)d.blocks_w[i] * d.blocks_h[i] * 64;
+                    const size_t pix = (size_t)d.height * d.width * 3;
+                    if (elems * 2 <= (256u << 20)) {
+                        const size_t ccap = (it & 7) == 7 ? (size_t)(rng() % 4096) : elems * 2;
+                        int16_t* cc = (int16_t*)malloc(ccap ? ccap : 1);
+                        const sd_status sc = sd_jpeg_decode_coefficients(fc, f.size(), cc, ccap, &d);
+                        if (sc == SD_OK) {
+                            uint8_t* rc = (uint8_t*)malloc(pix);
+                            const sd_status sr = sd_jpeg_reconstruct_bgr_host(cc, &d, rc, pix);
+                            if (sr != SD_OK) { printf("reconstruction refused what the coefficient decoder wrote (%s, it %d)\n", argv[a], it); return 3; }
+                            if (cap >= pix && s != SD_OK) { printf("routes disagree (%s, it %d)\n", argv[a], it); return 3; }
+                            // both accepted with room enough: the same pixels, byte for byte
+                            if (cap >= pix && s == SD_OK && memcmp(rc, oc, pix) != 0) { printf("routes accept but differ in pixels (%s, it %d)\n", argv[a], it); return 3; }
+                            free(rc);
+                        } else if (ccap == elems * 2 && cap >= pix && s == SD_OK) { printf("routes disagree (%s, it %d)\n", argv[a], it); return 3; }
+                        free(cc);
+                    }
+                }
+            }
+            free(oc);
+            free(fc);
         }
     }
     printf("decoded %ld, rejected %ld\n", ok, bad);

@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libsemdepth.so")
 
 SD_OK = 0
+SD_ERR_INVALID, SD_ERR_HIP, SD_ERR_STATE, SD_ERR_NOTFOUND, SD_ERR_FORMAT = -1, -2, -3, -4, -5
 SD_ENC_VGG, SD_ENC_RESNET50 = 0, 1
 SD_NET_FCN8S, SD_NET_MONODEPTH = 0, 1
 SD_PREC_F32, SD_PREC_BF16X2, SD_PREC_MIXED, SD_PREC_PLAN, SD_PREC_BF16X3, SD_PREC_F16X2 = 0, 1, 2, 3, 4, 5
@@ -48,6 +49,20 @@ class sd_profile_bucket(C.Structure):
     _fields_ = [("kernel", C.c_char * 64), ("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+class sd_jpeg_frame_desc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("ncomp", C.c_int32), ("hmax", C.c_int32), ("vmax", C.c_int32),
+                ("orientation", C.c_int32), ("adobe_transform", C.c_int32), ("reserved", C.c_int32), ("blocks_w", C.c_int32 * 3),
+                ("blocks_h", C.c_int32 * 3), ("coef_offset", C.c_int64 * 3), ("qt", (C.c_uint16 * 64) * 3)]
+
+    def coef_elems(self) -> int:
+        """int16 elements of the frame's coefficient buffer"""
+        return sum(self.blocks_w[i] * self.blocks_h[i] * 64 for i in range(self.ncomp))
+
+    def oriented_size(self) -> tuple:
+        """(height, width) after the EXIF orientation"""
+        return (self.width, self.height) if self.orientation >= 5 else (self.height, self.width)
+
+
 # every symbol include/semdepth.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _H = C.c_void_p
@@ -72,6 +87,12 @@ SIGNATURES = {
     "sd_jpeg_decode_bgr": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sd_image_decode_bgr": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "sd_decode_files_bgr": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, C.POINTER(C.c_int)]),
+    "sd_jpeg_decode_coefficients": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(sd_jpeg_frame_desc)]),
+    "sd_jpeg_reconstruct_bgr_host": (C.c_int, [_P, C.POINTER(sd_jpeg_frame_desc), _P, C.c_size_t]),
+    "sd_decode_files_jpeg_coef": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(sd_jpeg_frame_desc),
+                                            C.c_int, C.POINTER(C.c_int)]),
+    "sd_jpeg_reconstruct_workspace": (C.c_int, [C.POINTER(sd_jpeg_frame_desc), C.c_int, C.POINTER(C.c_size_t)]),
+    "sd_jpeg_reconstruct_bgr": (C.c_int, [_H, _P, C.c_size_t, C.POINTER(sd_jpeg_frame_desc), C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P]),
     "sd_png_encode_bgr_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, C.c_int,
                                           C.POINTER(C.c_int)]),
     "sd_ply_format_rows": (C.c_int64, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int]),

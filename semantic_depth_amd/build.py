@@ -33,6 +33,7 @@ SOURCES = [
     ("ops_misc.hip", []),
     ("resize.hip", []),
     ("compose.hip", []),
+    ("jpeg_gpu.hip", []),
     ("fuse.hip", ["-ffp-contract=off"]),
     ("pcl.hip", ["-ffp-contract=off"]),
     ("plan.cpp", []),
@@ -41,7 +42,7 @@ SOURCES = [
     ("host_jpeg.cpp", []),
     ("host_ply.cpp", []),
 ]
-HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", os.path.join("..", "..", "include", "semdepth.h")]
+HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
 
 
 def _hipcc() -> str:

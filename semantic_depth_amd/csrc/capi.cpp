@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "jpeg_gpu.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -360,6 +361,7 @@ const char* sd_status_string(sd_status s) {
         case SD_ERR_HIP: return "HIP error";
         case SD_ERR_STATE: return "invalid state";
         case SD_ERR_NOTFOUND: return "not found";
+        case SD_ERR_FORMAT: return "not a JPEG file";
         default: return "unknown";
     }
 }
@@ -657,6 +659,37 @@ sd_status sd_resize_cubic_u8(sd_handle* h, const uint8_t* src, int B, int src_h,
     const sd_status st = upload_resize_tables(h, h->o_rsz, h->rsz_key, h->rsz_host, src_h, src_w, dst_h, dst_w, s, &xi, &xa, &yi, &ya);
     if (st != SD_OK) return st;
     HIPCHK(h, launch_resize_cubic_u8(src, dst, B, src_h, src_w, dst_h, dst_w, channels, xi, xa, yi, ya, s));
+    return SD_OK;
+}
+
+sd_status sd_jpeg_reconstruct_workspace(const sd_jpeg_frame_desc* descs_host, int B, size_t* bytes_out) {
+    if (!descs_host || B <= 0 || !bytes_out) return SD_ERR_INVALID;
+    for (int b = 0; b < B; ++b)
+        if (!sdjpeg::desc_ok(descs_host[b])) return SD_ERR_INVALID;
+    *bytes_out = jpeg_workspace_bytes(descs_host, B);
+    return SD_OK;
+}
+
+sd_status sd_jpeg_reconstruct_bgr(sd_handle* h, const int16_t* coef_dev, size_t frame_stride_bytes, const sd_jpeg_frame_desc* descs_host, int B,
+                                  uint8_t* bgr_dev, size_t bgr_frame_stride, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!h || !coef_dev || !descs_host || B <= 0 || !bgr_dev || !workspace_dev)
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_reconstruct_bgr: bad arguments");
+    // the kernels read a block as 16-byte pieces and store plane rows as 8-byte pieces
+    if ((reinterpret_cast<uintptr_t>(coef_dev) & 15) || (frame_stride_bytes & 15) || (reinterpret_cast<uintptr_t>(workspace_dev) & 15))
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_reconstruct_bgr: coef_dev, frame_stride_bytes and workspace_dev must be multiples of 16");
+    // every index the kernels form follows from a consistent descriptor and these three capacities: nothing is launched otherwise
+    for (int b = 0; b < B; ++b) {
+        const sd_jpeg_frame_desc& d = descs_host[b];
+        if (!sdjpeg::desc_ok(d)) return fail(h, SD_ERR_INVALID, "sd_jpeg_reconstruct_bgr: descriptor " + std::to_string(b) + " is not self-consistent");
+        if (sdjpeg::desc_coef_elems(d) * sizeof(int16_t) > frame_stride_bytes)
+            return fail(h, SD_ERR_INVALID, "sd_jpeg_reconstruct_bgr: frame " + std::to_string(b) + " has more coefficients than frame_stride_bytes");
+        if ((size_t)d.height * d.width * 3 > bgr_frame_stride)
+            return fail(h, SD_ERR_INVALID, "sd_jpeg_reconstruct_bgr: frame " + std::to_string(b) + " is larger than bgr_frame_stride");
+    }
+    if (workspace_bytes < jpeg_workspace_bytes(descs_host, B))
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_reconstruct_bgr: workspace smaller than sd_jpeg_reconstruct_workspace reports");
+    HIPCHK(h, launch_jpeg_reconstruct(coef_dev, frame_stride_bytes / sizeof(int16_t), descs_host, B, bgr_dev, bgr_frame_stride,
+                                      static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
     return SD_OK;
 }
 

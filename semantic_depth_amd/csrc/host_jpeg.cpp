@@ -11,6 +11,7 @@
 // Output: u8 [height, width, 3] BGR.  Pinned in tests/test_frame_io.py against Pillow (libjpeg-turbo, same defaults) bit for bit.
 // Arithmetic-coded, lossless, 12-bit, CMYK and other sampling ratios are refused with SD_ERR_INVALID.
 #include "../../include/semdepth.h"
+#include "jpeg_common.hpp"
 
 #include <cstdint>
 #include <cstring>
@@ -65,6 +66,7 @@ struct Comp {
     int pred = 0;
     std::vector<uint8_t> plane;
     std::vector<int16_t> coef;     // progressive: quantised coefficients of every block (natural order), accumulated over the scans
+    int16_t* cf = nullptr;         // where the scans accumulate: coef.data(), or this component's part of the caller's buffer (coefficient route)
 };
 
 struct BitReader {
@@ -105,76 +107,7 @@ inline int decode_sym(BitReader& br, const Huff& h) {
     return -1;
 }
 
-// jidctint.c (libjpeg 6b / libjpeg-turbo, DCTSIZE 8): accurate integer inverse DCT on dequantised coefficients, output
-// level-shifted by +128 and range-limited to 0..255
-#define FIXC(x) ((int32_t)((x) * 8192 + 0.5))
-inline int32_t descale(int64_t x, int n) { return (int32_t)((x + ((int64_t)1 << (n - 1))) >> n); }
-void idct_islow(const int32_t* in, uint8_t* out, int stride) {
-    constexpr int CB = 13, P1 = 2;
-    const int32_t F0_298631336 = 2446, F0_390180644 = 3196, F0_541196100 = 4433, F0_765366865 = 6270, F0_899976223 = 7373,
-                  F1_175875602 = 9633, F1_501321110 = 12299, F1_847759065 = 15137, F1_961570560 = 16069, F2_053119869 = 16819,
-                  F2_562915447 = 20995, F3_072711026 = 25172;
-    int32_t ws[64];
-    for (int c = 0; c < 8; ++c) {
-        const int32_t* ip = in + c;
-        int32_t* wp = ws + c;
-        if (!(ip[8] | ip[16] | ip[24] | ip[32] | ip[40] | ip[48] | ip[56])) {
-            const int32_t dc = ip[0] * (1 << P1);
-            for (int r = 0; r < 8; ++r) wp[8 * r] = dc;
-            continue;
-        }
-        int64_t z2 = ip[16], z3 = ip[48];
-        int64_t z1 = (z2 + z3) * F0_541196100;
-        int64_t tmp2 = z1 + z3 * (-F1_847759065);
-        int64_t tmp3 = z1 + z2 * F0_765366865;
-        z2 = ip[0]; z3 = ip[32];
-        int64_t tmp0 = (z2 + z3) * (1 << CB);
-        int64_t tmp1 = (z2 - z3) * (1 << CB);
-        const int64_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-        tmp0 = ip[56]; tmp1 = ip[40]; tmp2 = ip[24]; tmp3 = ip[8];
-        z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
-        int64_t z4 = tmp1 + tmp3;
-        const int64_t z5 = (z3 + z4) * F1_175875602;
-        tmp0 *= F0_298631336; tmp1 *= F2_053119869; tmp2 *= F3_072711026; tmp3 *= F1_501321110;
-        z1 *= -F0_899976223; z2 *= -F2_562915447; z3 *= -F1_961570560; z4 *= -F0_390180644;
-        z3 += z5; z4 += z5;
-        tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
-        wp[0] = descale(tmp10 + tmp3, CB - P1);  wp[56] = descale(tmp10 - tmp3, CB - P1);
-        wp[8] = descale(tmp11 + tmp2, CB - P1);  wp[48] = descale(tmp11 - tmp2, CB - P1);
-        wp[16] = descale(tmp12 + tmp1, CB - P1); wp[40] = descale(tmp12 - tmp1, CB - P1);
-        wp[24] = descale(tmp13 + tmp0, CB - P1); wp[32] = descale(tmp13 - tmp0, CB - P1);
-    }
-    auto clamp = [](int32_t v) { v += 128; return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); };
-    for (int r = 0; r < 8; ++r) {
-        const int32_t* wp = ws + 8 * r;
-        uint8_t* o = out + (size_t)r * stride;
-        if (!(wp[1] | wp[2] | wp[3] | wp[4] | wp[5] | wp[6] | wp[7])) {
-            const uint8_t dc = clamp(descale(wp[0], P1 + 3));
-            for (int c = 0; c < 8; ++c) o[c] = dc;
-            continue;
-        }
-        int64_t z2 = wp[2], z3 = wp[6];
-        int64_t z1 = (z2 + z3) * F0_541196100;
-        int64_t tmp2 = z1 + z3 * (-F1_847759065);
-        int64_t tmp3 = z1 + z2 * F0_765366865;
-        int64_t tmp0 = ((int64_t)wp[0] + wp[4]) * (1 << CB);
-        int64_t tmp1 = ((int64_t)wp[0] - wp[4]) * (1 << CB);
-        const int64_t tmp10 = tmp0 + tmp3, tmp13 = tmp0 - tmp3, tmp11 = tmp1 + tmp2, tmp12 = tmp1 - tmp2;
-        tmp0 = wp[7]; tmp1 = wp[5]; tmp2 = wp[3]; tmp3 = wp[1];
-        z1 = tmp0 + tmp3; z2 = tmp1 + tmp2; z3 = tmp0 + tmp2;
-        int64_t z4 = tmp1 + tmp3;
-        const int64_t z5 = (z3 + z4) * F1_175875602;
-        tmp0 *= F0_298631336; tmp1 *= F2_053119869; tmp2 *= F3_072711026; tmp3 *= F1_501321110;
-        z1 *= -F0_899976223; z2 *= -F2_562915447; z3 *= -F1_961570560; z4 *= -F0_390180644;
-        z3 += z5; z4 += z5;
-        tmp0 += z1 + z3; tmp1 += z2 + z4; tmp2 += z2 + z3; tmp3 += z1 + z4;
-        constexpr int S = CB + P1 + 3;
-        o[0] = clamp(descale(tmp10 + tmp3, S)); o[7] = clamp(descale(tmp10 - tmp3, S));
-        o[1] = clamp(descale(tmp11 + tmp2, S)); o[6] = clamp(descale(tmp11 - tmp2, S));
-        o[2] = clamp(descale(tmp12 + tmp1, S)); o[5] = clamp(descale(tmp12 - tmp1, S));
-        o[3] = clamp(descale(tmp13 + tmp0, S)); o[4] = clamp(descale(tmp13 - tmp0, S));
-    }
-}
+using sdjpeg::idct_islow;       // jpeg_common.hpp: the one inverse DCT of the host and the device route
 
 inline uint16_t rd16(const uint8_t* p) { return (uint16_t)((p[0] << 8) | p[1]); }
 
@@ -222,6 +155,36 @@ struct Decoder {
     }
 
     size_t cap_bytes = 0;                                  // capacity of the caller's output buffer (checked at the frame header)
+    // coefficient route (sd_jpeg_decode_coefficients): the blocks' quantised coefficients go to the caller's buffer, no plane exists
+    int16_t* coef_ext = nullptr;
+    bool allocated = false;
+    uint16_t qt_used[3][64] = {};                          // the table each component's coefficients are to be multiplied by
+    bool scanned[3] = {false, false, false};               // sequential file: a scan has covered the component
+
+    void geometry() {
+        for (int i = 0; i < ncomp; ++i) {
+            Comp& c = comp[i];
+            c.bw = sdjpeg::blocks_w(W, hmax, c.h); c.bh = sdjpeg::blocks_h(H, vmax, c.v);
+            c.pw = c.bw * 8; c.ph = c.bh * 8;
+            c.dw = (W * c.h + hmax - 1) / hmax; c.dh = (H * c.v + vmax - 1) / vmax;
+        }
+    }
+    size_t coef_elems() const {
+        size_t n = 0;
+        for (int i = 0; i < ncomp; ++i) n += (size_t)comp[i].bw * comp[i].bh * 64;
+        return n;
+    }
+    void fill_desc(sd_jpeg_frame_desc* d) const {
+        std::memset(d, 0, sizeof(*d));
+        d->height = H; d->width = W; d->ncomp = ncomp; d->hmax = hmax; d->vmax = vmax;
+        d->orientation = orientation; d->adobe_transform = adobe_transform;
+        int64_t off = 0;
+        for (int i = 0; i < ncomp; ++i) {
+            d->blocks_w[i] = comp[i].bw; d->blocks_h[i] = comp[i].bh; d->coef_offset[i] = off;
+            off += (int64_t)comp[i].bw * comp[i].bh * 64;
+            std::memcpy(d->qt[i], qt_used[i], sizeof(qt_used[i]));
+        }
+    }
     sd_status parse(bool decode) {
         if (len < 4 || f[0] != 0xFF || f[1] != 0xD8) return SD_ERR_INVALID;
         size_t p = 2;
@@ -271,7 +234,7 @@ struct Decoder {
                 H = rd16(s + 1); W = rd16(s + 3); ncomp = s[5];
                 if (H <= 0 || W <= 0 || (ncomp != 1 && ncomp != 3) || sn < 6 + 3 * (size_t)ncomp) return SD_ERR_INVALID;
                 if ((size_t)H * (size_t)W > ((size_t)1 << 28)) return SD_ERR_INVALID;      // (256 Mpixel: refuse absurd headers before allocating planes)
-                if (decode && cap_bytes < (size_t)H * W * 3) return SD_ERR_INVALID;       // the caller's buffer bounds what a header can make us allocate
+                if (decode && !coef_ext && cap_bytes < (size_t)H * W * 3) return SD_ERR_INVALID;       // the caller's buffer bounds what a header can make us allocate
                 for (int i = 0; i < ncomp; ++i) {
                     comp[i].id = s[6 + 3 * i]; comp[i].h = s[7 + 3 * i] >> 4; comp[i].v = s[7 + 3 * i] & 15; comp[i].tq = s[8 + 3 * i];
                     if (comp[i].h < 1 || comp[i].v < 1 || comp[i].tq > 3) return SD_ERR_INVALID;
@@ -283,6 +246,8 @@ struct Decoder {
                     if (comp[0].h != hmax || comp[0].v != vmax || comp[1].h != 1 || comp[1].v != 1 || comp[2].h != 1 || comp[2].v != 1) return SD_ERR_INVALID;
                     if (!((hmax == 1 && vmax == 1) || (hmax == 2 && vmax == 1) || (hmax == 2 && vmax == 2))) return SD_ERR_INVALID;
                 }
+                geometry();
+                if (decode && coef_ext && cap_bytes < coef_elems() * sizeof(int16_t)) return SD_ERR_INVALID;      // (the same bound on the coefficient route)
                 sof = true;
                 if (!decode) { /* keep scanning for APP1 only until SOS */ }
             } else if (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
@@ -310,22 +275,25 @@ struct Decoder {
     }
 
     void alloc_planes() {
-        const int mcux = (W + 8 * hmax - 1) / (8 * hmax), mcuy = (H + 8 * vmax - 1) / (8 * vmax);
+        if (allocated) return;
+        allocated = true;
+        if (coef_ext) {                                    // no plane: every block of the padded planes starts as zeros in the caller's buffer
+            size_t off = 0;
+            for (int i = 0; i < ncomp; ++i) { comp[i].cf = coef_ext + off; off += (size_t)comp[i].bw * comp[i].bh * 64; }
+            std::memset(coef_ext, 0, off * sizeof(int16_t));
+            return;
+        }
         for (int i = 0; i < ncomp; ++i) {
             Comp& c = comp[i];
-            if (!c.plane.empty()) continue;
-            c.bw = mcux * c.h; c.bh = mcuy * c.v;
-            c.pw = c.bw * 8; c.ph = c.bh * 8;
-            c.dw = (W * c.h + hmax - 1) / hmax; c.dh = (H * c.v + vmax - 1) / vmax;
             c.plane.assign((size_t)c.pw * c.ph, 0);
-            if (progressive) c.coef.assign((size_t)c.bw * c.bh * 64, 0);
+            if (progressive) { c.coef.assign((size_t)c.bw * c.bh * 64, 0); c.cf = c.coef.data(); }
         }
     }
 
     // ---- progressive scans (T.81 annex G; libjpeg jdphuff.c): coefficients accumulate in Comp::coef, the inverse DCT runs at the end
     int eobrun = 0;
     bool prog_dc(BitReader& br, Comp& c, int bx, int by, int Ah, int Al) {
-        int16_t* blk = (bx < c.bw && by < c.bh) ? &c.coef[((size_t)by * c.bw + bx) * 64] : nullptr;
+        int16_t* blk = (bx < c.bw && by < c.bh) ? &c.cf[((size_t)by * c.bw + bx) * 64] : nullptr;
         if (Ah == 0) {
             const Huff& hd = dc[c.td];
             if (!hd.present) return false;
@@ -341,7 +309,7 @@ struct Decoder {
     }
     bool prog_ac(BitReader& br, Comp& c, int bx, int by, int Ss, int Se, int Ah, int Al) {
         if (bx >= c.bw || by >= c.bh) return false;
-        int16_t* blk = &c.coef[((size_t)by * c.bw + bx) * 64];
+        int16_t* blk = &c.cf[((size_t)by * c.bw + bx) * 64];
         const Huff& ha = ac[c.ta];
         if (!ha.present) return false;
         if (Ah == 0) {
@@ -394,17 +362,48 @@ struct Decoder {
         }
         return true;
     }
-    void prog_finish() {
+    // dequantise + inverse DCT of every block of component i from its coefficients (the end of a progressive file; the whole of
+    // sd_jpeg_reconstruct_bgr_host's first stage)
+    void idct_component(int i, const int16_t* cf, const uint16_t* q) {
         int32_t tmp[64];
-        for (int i = 0; i < ncomp; ++i) {
-            Comp& c = comp[i];
-            for (int by = 0; by < c.bh; ++by)
-                for (int bx = 0; bx < c.bw; ++bx) {
-                    const int16_t* blk = &c.coef[((size_t)by * c.bw + bx) * 64];
-                    for (int k = 0; k < 64; ++k) tmp[k] = (int32_t)blk[k] * (int32_t)qt[c.tq][k];
-                    idct_islow(tmp, c.plane.data() + (size_t)by * 8 * c.pw + (size_t)bx * 8, c.pw);
-                }
+        Comp& c = comp[i];
+        for (int by = 0; by < c.bh; ++by)
+            for (int bx = 0; bx < c.bw; ++bx) {
+                const int16_t* blk = &cf[((size_t)by * c.bw + bx) * 64];
+                for (int k = 0; k < 64; ++k) tmp[k] = (int32_t)blk[k] * (int32_t)q[k];
+                idct_islow(tmp, c.plane.data() + (size_t)by * 8 * c.pw + (size_t)bx * 8, c.pw);
+            }
+    }
+    void prog_finish() {
+        for (int i = 0; i < ncomp; ++i) idct_component(i, comp[i].cf, qt[comp[i].tq]);
+    }
+
+    // coefficient route of a sequential file: block() with the transform taken out -- the same symbols, the same DC predictor, the same
+    // refusals; the block's 64 quantised coefficients REPLACE what an earlier scan of the component left there, as the transform would
+    bool block_store(BitReader& br, Comp& c, int bx, int by) {
+        const Huff& hd = dc[c.td];
+        const Huff& ha = ac[c.ta];
+        if (!hd.present || !ha.present || !qt_ok[c.tq]) return false;
+        int16_t coef[64];
+        std::memset(coef, 0, sizeof(coef));
+        const int t = decode_sym(br, hd);
+        if (t < 0 || t > 15) return false;
+        const int diff = t ? extend(br.get(t), t) : 0;
+        c.pred += diff;
+        if (c.pred < -32767 || c.pred > 32767) return false;
+        coef[0] = (int16_t)c.pred;
+        for (int k = 1; k < 64;) {
+            const int rs = decode_sym(br, ha);
+            if (rs < 0) return false;
+            const int r = rs >> 4, s = rs & 15;
+            if (!s) { if (r == 15) { k += 16; continue; } break; }
+            k += r;
+            if (k > 63) return false;
+            coef[kZigzag[k]] = (int16_t)extend(br.get(s), s);
+            ++k;
         }
+        if (bx < c.bw && by < c.bh) std::memcpy(&c.cf[((size_t)by * c.bw + bx) * 64], coef, sizeof(coef));
+        return true;
     }
 
     bool block(BitReader& br, Comp& c, int bx, int by) {
@@ -448,6 +447,9 @@ struct Decoder {
             sc[i] = c;
         }
         alloc_planes();
+        // a sequential scan multiplies by the tables in force while it is decoded; the coefficient route hands that table on
+        if (coef_ext && !progressive)
+            for (int i = 0; i < ns; ++i) { std::memcpy(qt_used[sc[i] - comp], qt[sc[i]->tq], sizeof(qt_used[0])); scanned[sc[i] - comp] = true; }
         const int Ss = s[1 + 2 * ns], Se = s[2 + 2 * ns], Ah = s[3 + 2 * ns] >> 4, Al = s[3 + 2 * ns] & 15;
         if (progressive && (Ss > Se || Se > 63 || (Ss == 0 && Se != 0) || (Ss > 0 && ns != 1) || Al > 13)) return SD_ERR_INVALID;
         eobrun = 0;
@@ -472,7 +474,7 @@ struct Decoder {
                     for (int i = 0; i < ns; ++i) sc[i]->pred = 0;
                 }
                 auto one = [&](Comp& c, int bx, int by) {
-                    if (!progressive) return block(br, c, bx, by);
+                    if (!progressive) return coef_ext ? block_store(br, c, bx, by) : block(br, c, bx, by);
                     return Ss == 0 ? prog_dc(br, c, bx, by, Ah, Al) : prog_ac(br, c, bx, by, Ss, Se, Ah, Al);
                 };
                 if (ns == 1) {
@@ -552,6 +554,50 @@ struct Decoder {
             for (int i = 0; i < ncomp; ++i) if (!qt_ok[comp[i].tq] || comp[i].coef.empty()) return SD_ERR_INVALID;
             prog_finish();
         }
+        return emit_bgr(out);
+    }
+
+    sd_status decode_coefficients(int16_t* out, size_t cap, sd_jpeg_frame_desc* desc) {
+        coef_ext = out;
+        cap_bytes = cap;
+        const sd_status st = parse(true);
+        if (st != SD_OK) return st;
+        if (!allocated) return SD_ERR_INVALID;                        // no scan
+        if (progressive)
+            for (int i = 0; i < ncomp; ++i) {
+                if (!qt_ok[comp[i].tq]) return SD_ERR_INVALID;
+                std::memcpy(qt_used[i], qt[comp[i].tq], sizeof(qt_used[i]));     // a progressive file is dequantised at its end
+            }
+        // A sequential file need not scan every component (non-interleaved scans, the file cut between two of them).  The one-call decoder
+        // never transforms a block of such a component, so its plane keeps the initial sample 0 -- not the 128 that zero coefficients
+        // transform to.  DC = -1024 under a table of ones is the block that transforms to exactly 0 everywhere: the DC-only shortcuts give
+        // descale(-1024 * 4, 5) = -128, and the level shift makes that 0.  Progressive files transform every block on both routes.
+        if (!progressive)
+            for (int i = 0; i < ncomp; ++i) {
+                if (scanned[i]) continue;
+                for (int k = 0; k < 64; ++k) qt_used[i][k] = 1;
+                const size_t nblk = (size_t)comp[i].bw * comp[i].bh;
+                for (size_t b = 0; b < nblk; ++b) comp[i].cf[b * 64] = -1024;
+            }
+        fill_desc(desc);
+        return SD_OK;
+    }
+
+    // the back half from a coefficient buffer: the planes of a descriptor's geometry, every block transformed, then emit_bgr
+    sd_status reconstruct(const int16_t* coef, const sd_jpeg_frame_desc& d, uint8_t* out, size_t cap) {
+        if (!sdjpeg::desc_ok(d) || cap < (size_t)d.height * d.width * 3) return SD_ERR_INVALID;
+        H = d.height; W = d.width; ncomp = d.ncomp; hmax = d.hmax; vmax = d.vmax; orientation = d.orientation; adobe_transform = d.adobe_transform;
+        for (int i = 0; i < ncomp; ++i) { comp[i].h = i ? 1 : hmax; comp[i].v = i ? 1 : vmax; }
+        geometry();
+        for (int i = 0; i < ncomp; ++i) {
+            comp[i].plane.assign((size_t)comp[i].pw * comp[i].ph, 0);
+            idct_component(i, coef + d.coef_offset[i], d.qt[i]);
+        }
+        return emit_bgr(out);
+    }
+
+    // planes -> BGR: fancy chroma upsampling, YCbCr -> RGB (or the Adobe pass-through, or the gray replication), EXIF orientation
+    sd_status emit_bgr(uint8_t* out) {
         std::vector<uint8_t> bgr;
         const bool direct = orientation == 1;
         uint8_t* dst = out;
@@ -626,6 +672,38 @@ extern "C" sd_status sd_jpeg_decode_bgr(const uint8_t* file_host, size_t len, ui
         const sd_status st = d.decode(bgr_out_host, out_capacity);
         if (st == SD_OK) d.dims(height_out, width_out);
         return st;
+    } catch (...) {
+        return SD_ERR_INVALID;
+    }
+}
+
+extern "C" sd_status sd_jpeg_decode_coefficients(const uint8_t* file_host, size_t len, int16_t* coef_out_host, size_t capacity_bytes,
+                                                 sd_jpeg_frame_desc* desc_out) {
+    if (!file_host || !desc_out) return SD_ERR_INVALID;
+    try {
+        Decoder d;
+        d.f = file_host; d.len = len;
+        if (!coef_out_host) {
+            const sd_status st = d.parse(false);
+            if (st == SD_OK) {                               // (the tables read so far: final only after the full call)
+                for (int i = 0; i < d.ncomp; ++i) std::memcpy(d.qt_used[i], d.qt[d.comp[i].tq], sizeof(d.qt_used[i]));
+                d.fill_desc(desc_out);
+            }
+            return st;
+        }
+        return d.decode_coefficients(coef_out_host, capacity_bytes, desc_out);
+    } catch (...) {
+        return SD_ERR_INVALID;
+    }
+}
+
+extern "C" sd_status sd_jpeg_reconstruct_bgr_host(const int16_t* coef_host, const sd_jpeg_frame_desc* desc, uint8_t* bgr_out_host,
+                                                  size_t out_capacity) {
+    if (!coef_host || !desc || !bgr_out_host) return SD_ERR_INVALID;
+    try {
+        Decoder d;
+        d.f = nullptr; d.len = 0;
+        return d.reconstruct(coef_host, *desc, bgr_out_host, out_capacity);
     } catch (...) {
         return SD_ERR_INVALID;
     }

@@ -213,6 +213,52 @@ extern "C" sd_status sd_decode_files_bgr(const char* const* paths, int n, int he
     return failed.load() ? SD_ERR_INVALID : SD_OK;
 }
 
+// the same pool for the split JPEG route: file i -> quantised coefficients + descriptor (sd_jpeg_decode_coefficients); a file that is
+// not a JPEG is reported as SD_ERR_FORMAT and left to sd_decode_files_bgr
+extern "C" sd_status sd_decode_files_jpeg_coef(const char* const* paths, int n, int height, int width, int16_t* coef_out_host,
+                                               size_t frame_stride_bytes, sd_jpeg_frame_desc* descs_out, int threads, int* status_out) {
+    if (!paths || n < 0 || height <= 0 || width <= 0 || !coef_out_host || !descs_out || (frame_stride_bytes & 1)) return SD_ERR_INVALID;
+    if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
+    threads = threads < 1 ? 1 : (threads > n ? (n > 0 ? n : 1) : threads);
+    std::atomic<int> next(0), failed(0);
+    auto work = [&]() {
+        std::vector<uint8_t> file;
+        for (;;) {
+            const int i = next.fetch_add(1);
+            if (i >= n) break;
+            sd_status st = SD_ERR_NOTFOUND;
+            try {
+                if (paths[i] && read_file(paths[i], file)) {
+                    if (file.size() < 2 || file[0] != 0xFF || file[1] != 0xD8) st = SD_ERR_FORMAT;
+                    else {
+                        sd_jpeg_frame_desc d;
+                        st = sd_jpeg_decode_coefficients(file.data(), file.size(), nullptr, 0, &d);
+                        if (st == SD_OK) {
+                            const bool swap = d.orientation >= 5;
+                            if ((swap ? d.width : d.height) != height || (swap ? d.height : d.width) != width) st = SD_ERR_INVALID;
+                        }
+                        if (st == SD_OK)
+                            st = sd_jpeg_decode_coefficients(file.data(), file.size(), coef_out_host + (size_t)i * (frame_stride_bytes / 2),
+                                                             frame_stride_bytes, &descs_out[i]);
+                    }
+                }
+            } catch (...) {
+                st = SD_ERR_INVALID;
+            }
+            if (status_out) status_out[i] = st;
+            if (st != SD_OK && st != SD_ERR_FORMAT) failed.fetch_add(1);
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        for (int t = 1; t < threads; ++t) pool.emplace_back(work);
+    } catch (...) {
+    }
+    work();
+    for (auto& th : pool) th.join();
+    return failed.load() ? SD_ERR_INVALID : SD_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // The writer of the sequence tool's result images (cv2.imwrite at seq:336): BGR -> RGB rows with filter type 0, one zlib
 // stream deflated in pieces of a few rows (no whole-frame raw copy), one IDAT per deflate output block, on native threads.

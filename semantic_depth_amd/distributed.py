@@ -94,15 +94,19 @@ def run_sequence(load_frames, n_frames: int, step, batch: int = 32, group=None, 
     return out
 
 
-def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", workers: int = 0, outputs=None) -> torch.Tensor:
+def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", workers: int = 0, outputs=None, jpeg: str = "host",
+                       engine=None) -> torch.Tensor:
     """run_sequence on FILES (semantic_depth_cityscapes_sequence.py:689-701 reads ``sorted(glob(input_folder))`` frame by frame): rank r
     decodes ONLY its shard of the sorted list -- frame_io.FrameFeeder: one native call per batch into pinned staging, upload one batch
     ahead, ``workers`` decode threads (default: this rank's share of the node's CPUs, frame_io.default_decode_workers) -- and hands every
     batch to ``step(frames_on_device, first_global_index)``; one all_gather of the records at the end.
     ``outputs`` (default: ``step.outputs``, set by ``make_engine_step(..., outputs=)``): an outputs.SequenceOutputs the step feeds; this
     rank writes the files of its shard only, and the manifest last -- 'ok', or 'range_error' / 'error' when the run raised (the files
-    written before are then not valid outputs; the exception still propagates)."""
+    written before are then not valid outputs; the exception still propagates).
+    ``jpeg`` ("host" | "device") and ``engine`` go to the feeder: with "device" the JPEG frames are only entropy-decoded on the host and
+    reconstructed on the GPU by ``engine`` (default: ``step.engine``, set by make_engine_step); the frames are the same bytes."""
     from .frame_io import FrameFeeder
+    engine = engine if engine is not None else getattr(step, "engine", None)
     paths = sorted(paths)
     n_frames = len(paths)
     world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -116,7 +120,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     try:
         parts = []
         if hi > lo:
-            with FrameFeeder(paths[lo:hi], batch, device=device, workers=workers) as feeder:
+            with FrameFeeder(paths[lo:hi], batch, device=device, workers=workers, jpeg=jpeg, engine=engine if jpeg == "device" else None) as feeder:
                 for frames, first in feeder:
                     rec = step(frames, lo + first)
                     assert rec.dtype == torch.uint8 and tuple(rec.shape) == (frames.shape[0], RECORD_BYTES), (rec.dtype, rec.shape)
@@ -187,5 +191,6 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     # to give at the end -- no rank can raise alone here and leave the others in the all_gather)
     step.finish = None if getattr(engine, "on_range", "raise") == "recompute" else getattr(engine, "check_range", None)
     step.outputs = outputs
+    step.engine = engine
     step.recomputed = recomputed
     return step

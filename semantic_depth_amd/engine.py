@@ -315,6 +315,30 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_resize_cubic_u8")
         return out
 
+    def jpeg_reconstruct(self, coef: torch.Tensor, descs, out: torch.Tensor | None = None) -> torch.Tensor:
+        """the device half of the split JPEG route (sd_jpeg_reconstruct_bgr): ``coef`` int16 [B, stride] device tensor of quantised
+        coefficients as sd_jpeg_decode_coefficients / sd_decode_files_jpeg_coef lay them out, ``descs`` a ctypes array of B
+        _lib.sd_jpeg_frame_desc -> u8 [B,h,w,3] BGR after the EXIF orientation, the bytes of frame_io.decode_jpeg.  Two kernels per eight
+        frames on the current stream, no synchronisation; the workspace (the padded component planes) is a torch allocation."""
+        assert coef.dtype == torch.int16 and coef.is_cuda and coef.is_contiguous() and coef.dim() == 2
+        B = coef.shape[0]
+        if B < 1 or len(descs) < B:
+            raise ValueError("jpeg_reconstruct: one descriptor per frame")
+        h, w = descs[0].oriented_size()
+        if any(descs[i].oriented_size() != (h, w) for i in range(B)):
+            raise ValueError("jpeg_reconstruct: the frames of a batch share one size after the orientation")
+        if out is None:
+            out = torch.empty((B, h, w, 3), dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, h, w, 3)
+        need = C.c_size_t()
+        st = self.lib.sd_jpeg_reconstruct_workspace(descs, B, C.byref(need))
+        L.check(self.lib, None, st, "sd_jpeg_reconstruct_workspace")
+        ws = torch.empty((max(need.value, 16),), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_jpeg_reconstruct_bgr(self.h, _ptr(coef), coef.shape[1] * 2, descs, B, _ptr(out), h * w * 3, _ptr(ws), need.value,
+                                              self._stream())
+        L.check(self.lib, self.h, st, "sd_jpeg_reconstruct_bgr")
+        return out
+
     def compose_result_frames(self, frames: torch.Tensor, road: torch.Tensor, fence: torch.Tensor, records: torch.Tensor, out_h: int, out_w: int,
                               road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, out: torch.Tensor | None = None) -> torch.Tensor:
         """the sequence tool's result image (semantic_depth_cityscapes_sequence.py:303-336) for B device frames in one launch

@@ -1,15 +1,19 @@
 """Input stage, host side: the frame reader that replaces ``cv2.imread`` (semantic_depth.py:105; seq:123) and a
 feeder that keeps the GPU supplied.
 
-    imread(path)            8-bit PNG -> u8 [h,w,3] BGR, exactly cv2.imread's IMREAD_COLOR result (PNG is lossless): ONE native call
-                            (sd_png_decode_bgr: chunk walk, zlib inflate, scanline reconstruction, BGR shuffle, palette)
+    imread(path)            8-bit PNG or Huffman JPEG -> u8 [h,w,3] BGR, exactly cv2.imread's IMREAD_COLOR result: ONE native call
+                            (sd_png_decode_bgr: chunk walk, zlib inflate, scanline reconstruction, BGR shuffle, palette;
+                            sd_jpeg_decode_bgr: libjpeg's default decode path and the EXIF orientation, restated)
     FrameFeeder             the sorted file list (seq:689) batch by batch: ONE native call per batch (sd_decode_files_bgr, C++ threads)
                             reads and decodes straight into a pinned staging buffer, one batch ahead of the GPU; the cubic resize to
                             the network shape happens ON the GPU (Engine.resize_cubic), so the host never touches a pixel after the decode
 
-Decode stays on the host on purpose: DEFLATE and the PNG predictors are serial byte recurrences; a frame costs a few
-milliseconds of one core and the GPU box has hundreds (scripts/feed_rate.py measures decode, pinned H2D and resize rates
-against the benchmarked frames/s; DESIGN.md quotes them).  JPEG is not decoded here (the reference's inputs are PNG).
+PNG decode stays on the host on purpose: DEFLATE and the PNG predictors are serial byte recurrences; a frame costs a few
+milliseconds of one core (scripts/feed_rate.py measures decode, pinned H2D and resize rates against the benchmarked
+frames/s; DESIGN.md quotes them).  JPEG frames (the reference's own example frame is one) have two routes: ``jpeg="host"``, the
+default, decodes them completely on the host threads as well; ``jpeg="device"`` keeps only the serial part there -- the Huffman
+decoder, to quantised coefficients (sd_decode_files_jpeg_coef) -- and runs the inverse DCT, the chroma upsampling, the colour
+conversion and the EXIF orientation on the GPU (Engine.jpeg_reconstruct), byte for byte the host route's frames.
 """
 from __future__ import annotations
 
@@ -134,12 +138,26 @@ def default_decode_workers() -> int:
 class FrameFeeder:
     """iterate over (frames u8 [n,h,w,3] on ``device``, first global index) for the sorted ``paths``: every batch is read and decoded
     by ONE native call (sd_decode_files_bgr: ``workers`` C++ threads, no interpreter lock) straight into a pinned staging buffer,
-    uploaded asynchronously, one batch ahead of the consumer (two staging buffers)."""
+    uploaded asynchronously, one batch ahead of the consumer (two staging buffers).
+    ``jpeg="device"`` (needs ``engine``, an engine.Engine whose handle launches the kernels, and a GPU ``device``): the JPEG files of a
+    batch are only entropy-decoded on the host (sd_decode_files_jpeg_coef into a pinned int16 staging buffer, one batch ahead as well);
+    each frame's coefficients are uploaded asynchronously and Engine.jpeg_reconstruct writes the frames into the same u8 [n,h,w,3]
+    device tensor behind the upload, on the current stream.  PNG files of such a batch go the BGR way into that tensor.  The frames,
+    indices and batch boundaries are those of ``jpeg="host"``."""
 
-    def __init__(self, paths, batch: int, device="cuda", workers: int = 0):
+    def __init__(self, paths, batch: int, device="cuda", workers: int = 0, jpeg: str = "host", engine=None):
         import os
         import torch
         self.paths, self.batch, self.device = list(paths), batch, torch.device(device)
+        if jpeg not in ("host", "device"):
+            raise ValueError(f"FrameFeeder: jpeg must be 'host' or 'device', not {jpeg!r}")
+        if jpeg == "device" and self.device.type != "cuda":
+            raise ValueError("FrameFeeder: jpeg='device' reconstructs the frames on the GPU; device='cpu' has none")
+        if jpeg == "device" and engine is None:
+            raise ValueError("FrameFeeder: jpeg='device' needs engine= (the handle that launches the reconstruction kernels)")
+        self.jpeg, self.engine = jpeg, engine
+        self._pinned_coef = [None, None]
+        self._pinned_png = [None, None]
         self.workers = workers if workers > 0 else default_decode_workers()
         self._torch = torch
         self._pinned = [None, None]
@@ -147,6 +165,8 @@ class FrameFeeder:
 
     def close(self):
         self._pinned = [None, None]
+        self._pinned_coef = [None, None]
+        self._pinned_png = [None, None]
 
     def __enter__(self):
         return self
@@ -170,6 +190,86 @@ class FrameFeeder:
             raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
         return buf[:n]
 
+    @staticmethod
+    def _header_size(path) -> tuple:
+        """(h, w) after the orientation from the head of the file: the frame header and the EXIF segment come before the first scan, so
+        256 KiB nearly always hold them; the whole file is read only when they do not"""
+        with open(path, "rb") as f:
+            try:
+                return image_size(f.read(256 << 10))
+            except ValueError:
+                f.seek(0)
+                return image_size(f.read())
+
+    @staticmethod
+    def coef_stride_bytes(h: int, w: int) -> int:
+        """bytes that hold the coefficients of any JPEG frame this reader takes whose size after the orientation is h x w: three
+        components at the full rate, padded to whole 16 x 16 MCUs (4:4:4 needs 3 planes of 8-padded size, 4:2:0 1.5 of 16-padded
+        size; the bound is symmetric in h and w, so it covers the transposing orientations), rounded up to the 16 bytes the kernels load"""
+        return 3 * (-(-h // 16) * 16) * (-(-w // 16) * 16) * 2
+
+    def _decode_coef_into(self, slot: int, lo: int, hi: int):
+        """device route, host part of one batch: -> (pinned int16 [n, stride / 2] coefficients, descriptors, [(i, pinned BGR frame)]
+        of the files that are not JPEGs, (h, w))"""
+        torch = self._torch
+        h, w = self._header_size(self.paths[lo])          # the header pass: the batch's frame size fixes the staging stride
+        stride = self.coef_stride_bytes(h, w)
+        n = hi - lo
+        buf = self._pinned_coef[slot]
+        if buf is None or buf.shape[1] != stride // 2 or buf.shape[0] < n:
+            buf = self._pinned_coef[slot] = torch.empty((self.batch, stride // 2), dtype=torch.int16, pin_memory=True)
+        arr = (C.c_char_p * n)(*[os_fsencode(p) for p in self.paths[lo:hi]])
+        status = (C.c_int * n)()
+        descs = (L.sd_jpeg_frame_desc * n)()
+        st = self._lib.sd_decode_files_jpeg_coef(arr, n, h, w, C.c_void_p(buf.data_ptr()), stride, descs, self.workers, status)
+        if st != L.SD_OK:
+            bad = [(self.paths[lo + i], status[i]) for i in range(n) if status[i] not in (L.SD_OK, L.SD_ERR_FORMAT)]
+            raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
+        others = [i for i in range(n) if status[i] == L.SD_ERR_FORMAT]
+        png = []
+        if others:                                        # not JPEGs: the BGR route, into a pinned buffer of their own
+            pb = self._pinned_png[slot]
+            if pb is None or tuple(pb.shape[1:3]) != (h, w):
+                pb = self._pinned_png[slot] = torch.empty((self.batch, h, w, 3), dtype=torch.uint8, pin_memory=True)
+            k = len(others)
+            arr2 = (C.c_char_p * k)(*[os_fsencode(self.paths[lo + i]) for i in others])
+            status2 = (C.c_int * k)()
+            if self._lib.sd_decode_files_bgr(arr2, k, h, w, C.c_void_p(pb.data_ptr()), h * w * 3, self.workers, status2) != L.SD_OK:
+                bad = [(self.paths[lo + i], status2[j]) for j, i in enumerate(others) if status2[j] != L.SD_OK]
+                raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
+            png = [(i, pb[j]) for j, i in enumerate(others)]
+        return buf[:n], descs, png, (h, w)
+
+    def _reconstruct(self, host):
+        """device route, GPU part of one batch, all on the current stream: per-frame asynchronous uploads of the coefficients each
+        frame really has (a 4:2:0 frame has half of a 4:4:4 frame's), the two kernels, the PNG frames' uploads"""
+        torch = self._torch
+        coef, descs, png, (h, w) = host
+        n = coef.shape[0]
+        dev = torch.empty((n, h, w, 3), dtype=torch.uint8, device=self.device)
+        is_png = {i for i, _ in png}
+        jp = [i for i in range(n) if i not in is_png]
+        if jp:
+            cdev = torch.empty((len(jp), coef.shape[1]), dtype=torch.int16, device=self.device)
+            sub = (L.sd_jpeg_frame_desc * len(jp))()
+            for j, i in enumerate(jp):
+                used = descs[i].coef_elems()
+                cdev[j, :used].copy_(coef[i, :used], non_blocking=True)
+                sub[j] = descs[i]
+            # a run of consecutive JPEG frames is a contiguous slice of the batch tensor: the kernels write straight into it (a batch
+            # without PNG files is one run), and nothing but the coefficient copies crosses the bus
+            j0 = 0
+            while j0 < len(jp):
+                j1 = j0 + 1
+                while j1 < len(jp) and jp[j1] == jp[j1 - 1] + 1:
+                    j1 += 1
+                run = (L.sd_jpeg_frame_desc * (j1 - j0))(*[sub[j] for j in range(j0, j1)])
+                self.engine.jpeg_reconstruct(cdev[j0:j1], run, out=dev[jp[j0]:jp[j0] + (j1 - j0)])
+                j0 = j1
+        for i, frame in png:
+            dev[i].copy_(frame, non_blocking=True)
+        return dev
+
     def __iter__(self):
         torch = self._torch
         n = len(self.paths)
@@ -177,7 +277,8 @@ class FrameFeeder:
         if not ranges:
             return
         with ThreadPoolExecutor(max_workers=1) as ahead:
-            fut = ahead.submit(self._decode_into, 0, *ranges[0])
+            decode = self._decode_coef_into if self.jpeg == "device" else self._decode_into
+            fut = ahead.submit(decode, 0, *ranges[0])
             events = [None, None]
             for k, (lo, hi) in enumerate(ranges):
                 host = fut.result()
@@ -185,8 +286,8 @@ class FrameFeeder:
                     slot = (k + 1) & 1
                     if events[slot] is not None:
                         events[slot].synchronize()          # the upload out of that staging buffer (two batches ago) has finished
-                    fut = ahead.submit(self._decode_into, slot, *ranges[k + 1])
-                dev = host.to(self.device, non_blocking=True)
+                    fut = ahead.submit(decode, slot, *ranges[k + 1])
+                dev = self._reconstruct(host) if self.jpeg == "device" else host.to(self.device, non_blocking=True)
                 if self.device.type == "cuda":
                     events[k & 1] = torch.cuda.Event()
                     events[k & 1].record()
