@@ -386,6 +386,24 @@ sd_status sd_saturation_count(sd_handle* h, uint64_t* count_out, int reset);
  * Results do not depend on it (the tiles a workgroup walks change, not their arithmetic). */
 sd_status sd_set_reserved_cus(sd_handle* h, int n);
 
+/* Small-batch forms (SD_PREC_F16X2 only, opt-in).  Every GEMM block is chosen from the output tiles of a FULL pass of the handle, so that a
+ * frame's bits do not depend on the call it is computed in.  On a handle whose full pass is one or two frames the deep GEMM layers (FCN-8s fc6 /
+ * fc7, the res5 1x1 layers of monodepth-resnet50) have 16-32 tiles for 256 CUs.  on != 0 runs such a layer split along K: S slices per
+ * output tile (the k-range form of the LDS-DMA ring, f32 partial sums in the workspace) and one reduce launch that adds the slices in ascending
+ * order and applies the layer's epilogue.  The order of summation changes, so the last bits differ from the default handle's (same error
+ * against a float64 reference); results stay deterministic and independent of the call size.  On a handle where no layer qualifies nothing changes.
+ * Call it before sd_bind_memory (SD_ERR_STATE afterwards): sd_query_memory then reports the workspace with the partial-sum scratch.
+ * SD_ERR_INVALID on a handle of another precision. */
+sd_status sd_set_small_batch(sd_handle* h, int on);
+/* The rule, device-free: the slice count S (1 = not split) of a GEMM with `rows` output pixels in a full pass, `cout` output channels and a
+ * padded K axis of `kpad` on a chip of `cus` CUs.  tiles = ceil(rows / 256) * (cout / 256); a layer with cout % 256 != 0 or 8 * tiles > cus is not
+ * split (measured: every layer that gained covers at most an eighth of the CUs; at a quarter and above the unsplit launch is as fast); S is the smallest value with tiles * S >= cus, capped at 16 and at (kpad / 32) / 8 (a slice keeps at least 8 k-tiles of 32);
+ * a layer the caps leave below S = 4 is not split either (measured as well).
+ * k_tiles_per_slice_out (nullable, int[16]): the S slice lengths in k-tiles -- contiguous ranges in this order, sum = kpad / 32. */
+int sd_small_batch_split(long rows, int cout, int kpad, int cus, int* k_tiles_per_slice_out);
+/* the layers of `net` this handle runs split, as "layer:S,layer:S" (empty: none); SD_ERR_INVALID when cap is too small */
+sd_status sd_small_batch_plan(const sd_handle* h, sd_net net, char* layers_out, size_t cap);
+
 /* the same count without a device synchronisation: an 8-byte device-to-host copy enqueued on `stream` behind the work already on it
  * (host_dst = pinned host memory of the caller).  The host-side classes use it to turn a range violation into an ERROR of the call that
  * produced it instead of a counter somebody has to poll (semantic_depth_amd/engine.py Engine.check_range). */

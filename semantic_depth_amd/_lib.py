@@ -121,6 +121,9 @@ SIGNATURES = {
     "sd_saturation_frames": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "sd_saturation_settle": (C.c_int, [_H, C.c_int, C.c_void_p]),
     "sd_set_reserved_cus": (C.c_int, [_H, C.c_int]),
+    "sd_set_small_batch": (C.c_int, [_H, C.c_int]),
+    "sd_small_batch_split": (C.c_int, [C.c_long, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "sd_small_batch_plan": (C.c_int, [_H, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None

@@ -36,10 +36,11 @@ DEFAULT_ON_RANGE = "raise"
 
 
 def shared_engine(H: int, W: int, device: int = 0, precision: str = DEFAULT_PRECISION, encoder: str | None = None, max_batch: int = 1,
-                  on_range: str = DEFAULT_ON_RANGE) -> Engine:
+                  on_range: str = DEFAULT_ON_RANGE, small_batch: bool = False) -> Engine:
     """the registered Engine for this geometry; created on first use.  ``encoder`` None = whatever is registered (or 'vgg',
-    the reference's default --monodepth_encoder, semantic_depth.py:721-722)."""
-    key = (int(H), int(W), int(device), precision, RC.check_mode(on_range))
+    the reference's default --monodepth_encoder, semantic_depth.py:721-722).  ``small_batch`` (Engine(small_batch=), 'f16x2' only): the
+    split-K forms of the deep GEMM layers for one-frame calls; part of the key like on_range."""
+    key = (int(H), int(W), int(device), precision, RC.check_mode(on_range), bool(small_batch))
     per = _engines.setdefault(key, {})
     if encoder is None:
         if per:
@@ -47,7 +48,7 @@ def shared_engine(H: int, W: int, device: int = 0, precision: str = DEFAULT_PREC
         encoder = "vgg"
     eng = per.get(encoder)
     if eng is None or eng.max_batch < max_batch:
-        eng = Engine(H, W, max_batch, encoder, device, precision=precision, on_range=on_range)
+        eng = Engine(H, W, max_batch, encoder, device, precision=precision, on_range=on_range, small_batch=small_batch)
         eng._api_loaded = {}
         per[encoder] = eng
     return eng
@@ -55,7 +56,7 @@ def shared_engine(H: int, W: int, device: int = 0, precision: str = DEFAULT_PREC
 
 def register_engine(engine: Engine):
     """make an existing Engine the shared one for its geometry (bench / batched drivers build theirs with max_batch > 1)."""
-    key = (engine.H, engine.W, engine.device.index or 0, engine.precision, engine.on_range)
+    key = (engine.H, engine.W, engine.device.index or 0, engine.precision, engine.on_range, bool(getattr(engine, "small_batch", False)))
     if not hasattr(engine, "_api_loaded"):
         engine._api_loaded = {}
     _engines.setdefault(key, {})[engine.encoder] = engine
@@ -100,15 +101,17 @@ def _ensure_loaded(engine: Engine, net: int, weights: dict):
 class SegmentFrame:
     """SegmentFrame(input_shape, model_var_dir, use_frozen, use_xla, CUDA_DEVICE_NUMBER) — semantic_depth.py:464-469.
     ``model_var_dir``: dict / .npz of FCN-8s weights (weights.fcn8s_weight_shapes).  use_frozen / use_xla are accepted
-    and ignored (TF graph details).  ``on_range`` (Engine(on_range=)): 'raise' or 'recompute' a frame that leaves the fp16 range."""
+    and ignored (TF graph details).  ``on_range`` (Engine(on_range=)): 'raise' or 'recompute' a frame that leaves the fp16 range.
+    ``small_batch`` (Engine(small_batch=)): the split-K forms of the deep GEMM layers, for the one-frame calls of this class."""
 
     def __init__(self, input_shape, model_var_dir, use_frozen=True, use_xla=False, CUDA_DEVICE_NUMBER="0", engine: Engine | None = None,
-                 precision: str = DEFAULT_PRECISION, on_range: str = DEFAULT_ON_RANGE):
+                 precision: str = DEFAULT_PRECISION, on_range: str = DEFAULT_ON_RANGE, small_batch: bool = False):
         self.input_shape = tuple(input_shape)
         self.model_var_dir = model_var_dir
         self.CUDA_DEVICE_NUMBER = CUDA_DEVICE_NUMBER
         self.precision = precision
         self.on_range = RC.check_mode(on_range)
+        self.small_batch = bool(small_batch)
         self._weights = _load_weight_arg(model_var_dir)
         self._engine = engine
 
@@ -118,7 +121,7 @@ class SegmentFrame:
         shared Engine"""
         if self._engine is None:
             self._engine = shared_engine(self.input_shape[0], self.input_shape[1], int(self.CUDA_DEVICE_NUMBER), self.precision,
-                                         on_range=self.on_range)
+                                         on_range=self.on_range, small_batch=self.small_batch)
         _ensure_loaded(self._engine, L.SD_NET_FCN8S, self._weights)
         return self._engine
 
@@ -144,10 +147,11 @@ class SegmentFrame:
 
 class DepthFrame:
     """DepthFrame(is_city, encoder, input_height, input_width, checkpoint_path, f) — semantic_depth.py:575-624.
-    ``checkpoint_path``: dict / .npz of monodepth weights.  ``on_range``: as SegmentFrame."""
+    ``checkpoint_path``: dict / .npz of monodepth weights.  ``on_range``, ``small_batch``: as SegmentFrame."""
 
     def __init__(self, is_city=False, encoder="vgg", input_height=256, input_width=512, checkpoint_path=None, f=None,
-                 engine: Engine | None = None, precision: str = DEFAULT_PRECISION, device: int = 0, on_range: str = DEFAULT_ON_RANGE):
+                 engine: Engine | None = None, precision: str = DEFAULT_PRECISION, device: int = 0, on_range: str = DEFAULT_ON_RANGE,
+                 small_batch: bool = False):
         self.is_city, self.encoder = is_city, encoder
         self.input_height, self.input_width = input_height, input_width
         self.f = float(f) if f is not None else None
@@ -159,7 +163,8 @@ class DepthFrame:
             self.cx, self.cy, self.b = 314.05519001, 124.09658151, 1
             if self.f is None:
                 self.f = 380
-        self._engine = engine or shared_engine(input_height, input_width, device, precision, encoder, on_range=RC.check_mode(on_range))
+        self._engine = engine or shared_engine(input_height, input_width, device, precision, encoder, on_range=RC.check_mode(on_range),
+                                                small_batch=small_batch)
         if self._engine.encoder != encoder or (self._engine.H, self._engine.W) != (input_height, input_width):
             raise ValueError(f"engine is {self._engine.encoder} {self._engine.H}x{self._engine.W}, DepthFrame wants {encoder} "
                              f"{input_height}x{input_width}")

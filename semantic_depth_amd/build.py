@@ -26,6 +26,7 @@ SOURCES = [
     ("conv_dma_v4.hip", []),
     ("conv_dma_v5.hip", []),
     ("conv_dma3.hip", []),
+    ("splitk_reduce.hip", []),
     ("conv_direct.hip", []),
     ("conv_direct3.hip", []),
     ("dec_tail.hip", []),

@@ -40,6 +40,8 @@ struct sd_handle {
     size_t ws_bytes = 0;
     int last_fcn_images = 0, last_mono_images = 0;
     int reserve_cus = 0;            // sd_set_reserved_cus: CUs the persistent conv launches leave free
+    int small_batch = 0, cus = 0;   // sd_set_small_batch: the split-K forms of the under-filled GEMM layers; the CU count its rule reads (latched with it)
+    size_t o_splitk = 0;            // workspace: the partial sums of the largest split layer (0 bytes without the switch)
     std::vector<CamDev> cams_stage;
     std::map<std::pair<int, int>, std::vector<float>> bias_host;   // (net, slot) -> host copy, for bias slots that are summed
     std::map<std::pair<int, int>, std::vector<float>> w_host;      // (net, slot) -> f32 tensor of the SD_PREC_F16X2 slots that share a weight scale (sd_load_weight)
@@ -75,6 +77,43 @@ NetPlan& plan_of(sd_handle* h, sd_net net) { return net == SD_NET_FCN8S ? h->fcn
 const NetPlan& plan_of(const sd_handle* h, sd_net net) { return net == SD_NET_FCN8S ? h->fcn : h->mono; }
 char* warena(sd_handle* h, sd_net net) { return net == SD_NET_FCN8S ? h->wf : h->wm; }
 
+// conv_dma3.hip's precomputed gathers of an OP_CONV (ConvParams::flat / noup): a property of the plan and the handle's switches
+void dma3_gather(const sd_handle* h, const NetPlan& p, const OpDesc& op, int& flat, int& noup) {
+    const bool ph3 = op.scheme == SC_BF16X3 || op.scheme == SC_HS;     // the phased 256 x 256 GEMM block of conv_dma3.hip exists for these two
+    flat = (ph3 && op.k == 1 && !op.fold && !op.up[0] && !(op.nsrc > 1 && op.up[1]) && op.nsrc <= 2 && !(h->sw & SW_NO_FLAT)) ? 1 : 0;
+    noup = (ph3 && op.nsrc == 1 && !(h->sw & SW_NO_FLAT)) ? 1 : 0;       // (conv_dma3's precomputed gather: ONE source geometry)
+    for (int j = 0; j < op.nsrc; ++j) {      // (32-bit byte offsets inside a plane of every source; strides 1 or 2)
+        const TensorDesc& t = p.tensors[op.src[j]];
+        if ((size_t)p.images * t.H * t.W * t.C * 2 >= ((size_t)1 << 32)) flat = noup = 0;
+        // (a folded op keeps up[0] = 1 from the plan, but its table reads the source at its own resolution: tap layers without upsample)
+        if ((op.up[j] && !op.fold) || op.sstride[j] < 1 || op.sstride[j] > 2) noup = 0;
+    }
+}
+
+// sd_set_small_batch: slices of the K axis this op runs in on this handle (1 = not split).  Reads what the handle fixes -- the images of a full
+// pass, the layer, the CU count -- never a call.  Candidates: OP_CONV GEMMs of the three-product engine with an all-vec K axis, no fused pool, no
+// fold, no sub-planar output, Cout % 256 == 0, that conv_dma3's ring can carry with a precomputed gather (1x1 layers, single-source tap layers)
+int op_ksplit(const sd_handle* h, const NetPlan& p, const OpDesc& op) {
+    if (!h->small_batch || op.kind != OP_CONV || op.scheme != SC_HS || (h->sw & SW_NO_DMA)) return 1;
+    const TensorDesc& d = p.tensors[op.dst];
+    if (!op.vec || op.Kvec != op.Kpad || op.fuse_pool || op.fold || d.planar16 || op.residual >= 0 || d.C % 256 || p.weights[op.w].CoutPad != d.C) return 1;
+    int flat, noup;
+    dma3_gather(h, p, op, flat, noup);
+    if (!flat && !noup) return 1;
+    if (!flat && !(op.k >= 3 && op.sstride[0] == 1)) return 1;       // (the tap layers the HS ring takes: k x k, stride 1 -- conv_dma3_eligible)
+    return conv_splitk_slices((long)p.images * d.H * d.W, d.C, op.Kpad, h->cus);
+}
+
+size_t splitk_scratch_bytes(const sd_handle* h) {
+    size_t mx = 0;
+    for (const NetPlan* p : {&h->fcn, &h->mono})
+        for (const OpDesc& op : p->ops) {
+            const int S = op_ksplit(h, *p, op);
+            if (S > 1) { const TensorDesc& d = p->tensors[op.dst]; mx = std::max(mx, (size_t)S * p->images * d.H * d.W * d.C * sizeof(float)); }
+        }
+    return mx;
+}
+
 void carve_workspace(sd_handle* h) {
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t r = off; off += al(bytes); return r; };
@@ -95,6 +134,7 @@ void carve_workspace(sd_handle* h) {
     h->o_cmp = take(cmp_scratch_bytes(h->max_batch));
     h->o_rsz = take((size_t)RSZ_MAX * 16 * sizeof(int));          // resize tap tables: [RSZ_MAX][4] x idx | x weight | y idx | y weight
     h->o_rsz_cmp = take((size_t)RSZ_MAX * 16 * sizeof(int));      // the same layout for sd_compose_result_frames
+    h->o_splitk = take(splitk_scratch_bytes(h));                  // (last: the other offsets do not depend on the switch)
     h->ws_bytes = off;
 }
 
@@ -161,7 +201,8 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, 
     };
     // a conv launch in a profiling bracket: its start event is the end event of the conv launched right before it when nothing else came between
     // (sd_handle::prof_pool).  M x Nc: the record's GEMM extent; `kernel` names the launch for the record
-    auto bracketed = [&](const OpDesc& op, hipError_t& e, int M, int Nc, auto&& launch, auto&& kernel) -> sd_status {
+    auto bracketed = [&](const OpDesc& op, hipError_t& e, int M, int Nc, auto&& launch, auto&& kernel, double extra_bytes = -1.0) -> sd_status {
+        // (extra_bytes >= 0: a launch that carries none of the op's algorithmic work -- the reduce half of a split-K layer: its record holds these bytes)
         if (!h->prof) { e = launch(); return SD_OK; }
         hipEvent_t ea = h->prof_last, eb = nullptr;
         if (!ea) { if (!(ea = prof_event(h))) return fail(h, SD_ERR_HIP, "hipEventCreate"); hipEventRecord(ea, s); }
@@ -169,7 +210,7 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, 
         e = launch();
         hipEventRecord(eb, s);
         h->prof_last = eb;
-        h->prof_recs.push_back({kernel(), op.flops * N / p.images, ea, eb, op.name.c_str(), M, Nc, op.K, op_bytes(op)});
+        h->prof_recs.push_back({kernel(), extra_bytes >= 0 ? 0.0 : op.flops * N / p.images, ea, eb, op.name.c_str(), M, Nc, op.K, extra_bytes >= 0 ? extra_bytes : op_bytes(op)});
         return SD_OK;
     };
     for (const WeightSlot& wsl : p.weights)
@@ -219,15 +260,20 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, 
                 if (ph3 && !op.fold && op.nsrc == 1 && op.vec && op.Kvec == op.Kpad && op.k >= 3 && op.sstride[0] == 1 && !op.up[0] && !c.pool &&
                     op.Kpad == op.k * op.k * s0.C && c.Wout > 0 && 256 % c.Wout == 0 && N % (256 / c.Wout) == 0 && !(h->sw & SW_NO_ROWSKIP))
                     c.rowgrp = 256 / c.Wout;
-                c.flat = (ph3 && op.k == 1 && !op.fold && !op.up[0] && !(op.nsrc > 1 && op.up[1]) && op.nsrc <= 2 && !(h->sw & SW_NO_FLAT)) ? 1 : 0;
-                c.noup = (ph3 && op.nsrc == 1 && !(h->sw & SW_NO_FLAT)) ? 1 : 0;       // (conv_dma3's precomputed gather: ONE source geometry)
-                for (int j = 0; j < op.nsrc; ++j) {      // (32-bit byte offsets inside a plane of every source; strides 1 or 2)
-                    if (PL(op.src[j]) * 2 >= ((size_t)1 << 32)) c.flat = c.noup = 0;
-                    // (a folded op keeps up[0] = 1 from the plan, but its table reads the source at its own resolution: tap layers without upsample)
-                    if ((op.up[j] && !op.fold) || op.sstride[j] < 1 || op.sstride[j] > 2) c.noup = 0;
-                }
+                dma3_gather(h, p, op, c.flat, c.noup);
                 if (op.fold) {          // (conv_dma3.hip: the GEMM's pixel space is the source itself)
                     c.fold = 1; c.simple = 0; c.Hin = s0.H; c.Win = s0.W; c.Hout = s0.H; c.Wout = s0.W; c.kh = c.kw = 2;
+                }
+                if (const int S = op_ksplit(h, p, op); S > 1) {
+                    // sd_set_small_batch: the k-range form of the HS ring into the partial-sum scratch, then the reduce launch with the layer's epilogue
+                    // (no row groups: a slice is a contiguous range of the whole K axis)
+                    c.rowgrp = 0; c.ksplit = S; c.partial = reinterpret_cast<float*>(h->ws + h->o_splitk);
+                    const int M = N * c.Hout * c.Wout;
+                    st = bracketed(op, e, M, d.C, [&] { return launch_conv_splitk(c, s); }, [&] { return conv_splitk_kernel_name(c); });
+                    if (st != SD_OK || e != hipSuccess) break;
+                    st = bracketed(op, e, M, d.C, [&] { return launch_splitk_reduce(c, s); }, [&] { return "splitk_reduce_kernel"; },
+                                   (double)M * d.C * (S * sizeof(float) + elem_bytes(d.fmt)));
+                    break;
                 }
                 const bool dma3 = split && conv_dma3_eligible(c) && !(h->sw & SW_NO_DMA);
                 const bool dma = !dma3 && split && conv_dma_variant(c) != 0 && !(h->sw & SW_NO_DMA);
@@ -1042,6 +1088,45 @@ sd_status sd_saturation_count(sd_handle* h, uint64_t* count_out, int reset) {
         HIPCHK(h, hipMemset(sat_orphans(h), 0, sizeof(uint32_t)));      // (a part of the global count)
     }
     return SD_OK;
+}
+
+sd_status sd_set_small_batch(sd_handle* h, int on) {
+    if (!h) return SD_ERR_INVALID;
+    if (h->prec != (int)SD_PREC_F16X2) return fail(h, SD_ERR_INVALID, "sd_set_small_batch: the split-K forms exist for SD_PREC_F16X2 only");
+    if (h->bound) return fail(h, SD_ERR_STATE, "sd_set_small_batch: call it before sd_bind_memory (the workspace changes)");
+    if (on && !h->cus) {
+        // the CU count the rule reads, latched once: the device's, or (no device: planning on a host) the MI355X's 256
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || n <= 0) { (void)hipGetLastError(); n = 256; }
+        h->cus = n;
+    }
+    h->small_batch = on ? 1 : 0;
+    carve_workspace(h);
+    return SD_OK;
+}
+
+int sd_small_batch_split(long rows, int cout, int kpad, int cus, int* k_tiles_per_slice_out) {
+    const int S = conv_splitk_slices(rows, cout, kpad, cus);
+    if (k_tiles_per_slice_out)
+        for (int i = 0; i < S; ++i) {
+            int first, count;
+            conv_splitk_range(kpad / 32, S, i, first, count);
+            k_tiles_per_slice_out[i] = S > 1 ? count : (kpad > 0 ? kpad / 32 : 0);
+        }
+    return S;
+}
+
+sd_status sd_small_batch_plan(const sd_handle* h, sd_net net, char* layers_out, size_t cap) {
+    if (!h || !layers_out || !cap) return SD_ERR_INVALID;
+    const NetPlan& p = plan_of(h, net);
+    std::string out;
+    for (const OpDesc& op : p.ops) {
+        const int S = op_ksplit(h, p, op);
+        if (S > 1) out += (out.empty() ? "" : ",") + op.name + ":" + std::to_string(S);
+    }
+    std::strncpy(layers_out, out.c_str(), cap - 1);
+    layers_out[cap - 1] = 0;
+    return out.size() + 1 > cap ? SD_ERR_INVALID : SD_OK;
 }
 
 sd_status sd_set_reserved_cus(sd_handle* h, int n) {

@@ -16,6 +16,7 @@
 // weight ring -- 144 KB, two phases of look-ahead; PMC showed the MFMA pipes 56 % busy with a third of the wave cycles parked in waits.)
 // 8 waves as 2 x 4, wave tile 128 pixels x 64 channels (acc 128 VGPRs); general gather through the KEntry table (any kernel size, stride,
 // concatenated sources); epilogue = conv_dma.hip's X3 epilogue.
+#include <algorithm>
 #include <cstdlib>
 #include "kernels.hpp"
 #include "split_fmt.hpp"
@@ -78,8 +79,11 @@ constexpr int G3_ROW = G3_NT * 64 + 16;
 // 32-clock MFMAs): -3 % on the layers of this kernel, +1 % end to end (profiles/r05_mfma16_ab.txt, r05_conv_dma3_hooks.txt).  Its sums differ in the last bits from the
 // 32x32x16 form's (SEMDEPTH_MFMA32), as this block's always did from conv_dma.hip's: which of the two blocks a layer takes is decided per ENGINE, not per call
 // (conv_dma3_eligible).  The three-product (HS) form takes it for its 1x1 layers (-1.9 %) and stays on 32x32x16 for fc6 (2 % slower there).
-template <int MODE, bool HS = false, bool S16 = false>
-__global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, int M, int tilesM, int tilesN) {
+// KS (sd_set_small_batch; HS, MODE 1 / 2 without row groups): the k-range form.  blockIdx.y is a slice of the K axis (conv_splitk_range: contiguous
+// k-tile ranges that cover it exactly once); the cursor starts at the slice's first k-tile and runs its count through the unchanged ring, and the raw
+// epilogue stores the f32 accumulators to ConvParams::partial [slice][M][Cout] for splitk_reduce.hip -- no alpha, bias, activation or split.
+template <int MODE, bool HS, bool S16, bool KS>
+__device__ __forceinline__ void conv_dma3_body(const ConvParams& p, int M, int tilesM, int tilesN) {
     constexpr int NPL = HS ? 2 : 3;                          // planes per operand
     static_assert(G3_NW * NPL * 32 * G3_ROW <= G3_LDS * 16, "epilogue slabs fit in the ring");
     __shared__ __attribute__((aligned(16))) u32x4 lds[G3_LDS];
@@ -146,7 +150,8 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
         const int dlo = oy_t < p.pad ? -oy_t : -p.pad, dhi = p.Hout - 1 - oy_t < p.pad ? p.Hout - 1 - oy_t : p.pad;
         taps = p.kh * p.kw; t0 = (dlo + p.pad) * p.kw; nt = (dhi - dlo + 1) * p.kw;
     }
-    const int ktiles = (p.Kpad / 32 / taps) * nt;             // k-tiles this tile runs
+    int ktiles = (p.Kpad / 32 / taps) * nt;                   // k-tiles this tile runs
+    if constexpr (KS) conv_splitk_range(p.Kpad / 32, p.ksplit, (int)blockIdx.y, t0, ktiles);       // (taps = nt = all of them: the cursor never wraps)
     // cursor over them: actual k-tile index and position inside the window
     struct KCur { int idx, tt; };
     auto knext = [&](KCur c) { ++c.idx; if (++c.tt == nt) { c.tt = 0; c.idx += taps - nt; } return c; };
@@ -528,6 +533,26 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
     // ---- epilogue: bias + activation in f32, exact three-way split, LDS transpose (one slab per plane and wave), 16-byte runs ----
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if constexpr (KS) {
+        // raw epilogue: four consecutive channels of one pixel per lane and accumulator tuple, straight from the registers as one 16-byte store
+        // (S16: pixel 16 b + (lane & 15) of the 32, channels 16 r4 + 4 (lane >> 4); 32x32x16: pixel lane & 31, channels 32 b + 8 r4 + 4 (lane >> 5))
+        float* const part = p.partial + (size_t)blockIdx.y * (size_t)M * p.Cout;
+        const int m0 = bm0 + wm0, n0 = bn0 + wn0;
+#pragma unroll
+        for (int a = 0; a < G3_MT; ++a)
+#pragma unroll
+            for (int b = 0; b < G3_NT; ++b)
+#pragma unroll
+                for (int r4 = 0; r4 < 4; ++r4) {
+                    const int nl = S16 ? r4 * 16 + 4 * (lane >> 4) : b * 32 + 8 * r4 + 4 * (lane >> 5);
+                    const int mo = m0 + a * 32 + (S16 ? b * 16 + (lane & 15) : (lane & 31));
+                    f32x4 v;
+                    if constexpr (S16) v = acc16[2 * a + b][r4];
+                    else v = f32x4{acc[a][b][4 * r4], acc[a][b][4 * r4 + 1], acc[a][b][4 * r4 + 2], acc[a][b][4 * r4 + 3]};
+                    if (mo < M) *reinterpret_cast<f32x4*>(part + (size_t)mo * p.Cout + n0 + nl) = v;
+                }
+        return;
+    }
     // (the epilogue's per-lane values are formed from an opaque copy of the lane id: nothing of it is hoisted above the k-loop, whose registers are all taken)
     int lane_e = lane;
     asm volatile("" : "+v"(lane_e));
@@ -606,6 +631,16 @@ __global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, i
     else ep3(ActTag<ACT_NONE>{});
 }
 
+template <int MODE, bool HS = false, bool S16 = false>
+__global__ __launch_bounds__(512, 1) void conv_dma3_kernel(const ConvParams p, int M, int tilesM, int tilesN) {
+    conv_dma3_body<MODE, HS, S16, false>(p, M, tilesM, tilesN);
+}
+// the k-range form of the HS ring (grid: tiles x slices)
+template <int MODE, bool S16>
+__global__ __launch_bounds__(512, 1) void conv_splitk_hs_kernel(const ConvParams p, int M, int tilesM, int tilesN) {
+    conv_dma3_body<MODE, true, S16, true>(p, M, tilesM, tilesN);
+}
+
 int conv_dma3_mode(const ConvParams& p);
 // layers the 256 x 256 phased block takes: bf16 x 3, all-vec K axis, Cout a multiple of 256 and enough blocks to occupy the chip
 bool conv_dma3_eligible(const ConvParams& p) {
@@ -635,6 +670,47 @@ const char* conv_dma3_kernel_name(const ConvParams& p) {
     static const char* const hs[3] = {"conv_dma_hs_phased_kernel<0>", "conv_dma_hs_phased_kernel<1>", "conv_dma_hs_phased_kernel<2>"};
     if (p.sw & SW_PROFILE_VERBOSE) return (p.scheme == SC_HS ? hs : x3)[conv_dma3_mode(p)];
     return p.scheme == SC_HS ? "conv_dma_hs_phased_kernel" : "conv_dma3_kernel";
+}
+
+// Split-K (sd_set_small_batch).  The rule reads what a handle fixes and nothing of a call: the rows of a FULL pass, the layer's shape, the CU count.
+// A GEMM whose 256 x 256 tiles cover at most an eighth of the CUs is cut into the smallest S with tiles * S >= CUs, capped at 16 and so that a
+// slice keeps at least 8 k-tiles of 32 (the ring's prologue and drain are ~3 k-tiles of latency: shorter slices run mostly outside the steady state).
+// The eighth is what was measured (profiles/latency_b1.json, latency_b1_rule_tiles_below_cus.json): every layer that won has 16 or 32 tiles and ran on
+// conv_split before; the 33-63-tile band, which the two-stage conv_dma block carries, has no measured shape and stays out; the layers with 64-128 tiles (res3 / res4 block tails of one frame at 512 x 1024, S = 2-4) ran
+// as fast or faster unsplit -- the second launch and the partial sums' round trip cost what the extra workgroups win --, as did the 16-tile layer
+// whose short K axis caps it at S = 2 (res3_4's tail); every layer with <= 32 tiles and S >= 4 won.
+int conv_splitk_slices(long rows, int cout, int kpad, int cus) {
+    if (rows <= 0 || cout <= 0 || cout % G3_BN || kpad <= 0 || kpad % 32 || cus <= 0) return 1;
+    const long tiles = ((rows + G3_BM - 1) / G3_BM) * (cout / G3_BN);
+    if (tiles * 8 > cus) return 1;
+    long S = (cus + tiles - 1) / tiles;
+    S = std::min(S, std::min(16L, (long)(kpad / 32) / 8));
+    return S < 4 ? 1 : (int)S;         // (measured: the layers the caps left at S = 2 or 3 lost to their unsplit launch)
+}
+
+const char* conv_splitk_kernel_name(const ConvParams& p) {
+    if (p.sw & SW_PROFILE_VERBOSE) return conv_dma3_mode(p) == 1 ? "conv_splitk_hs_kernel<1>" : "conv_splitk_hs_kernel<2>";
+    return "conv_splitk_hs_kernel";
+}
+
+// the GEMM half of a split layer: partial[s] = the accumulators of slice s (splitk_reduce.hip adds them up and applies the epilogue)
+hipError_t launch_conv_splitk(const ConvParams& p, hipStream_t s) {
+    const int mode = conv_dma3_mode(p);
+    if (p.scheme != SC_HS || !p.vec || !p.zero16 || p.pool || p.out_planar16 || p.residual || p.fold || p.rowgrp || p.Cout % G3_BN || p.CoutPad != p.Cout ||
+        (mode != 1 && mode != 2) || !p.partial || p.ksplit < 2 || p.ksplit > 16 || (p.Kpad / 32) / p.ksplit < 8)
+        return hipErrorInvalidValue;
+    const long M = (long)p.N * p.Hout * p.Wout;
+    const int tilesM = (int)((M + G3_BM - 1) / G3_BM), tilesN = p.Cout / G3_BN;
+    const dim3 grid((unsigned)(tilesM * tilesN), (unsigned)p.ksplit);
+    // (the forms of the unsplit HS layers: 16x16x32 MFMAs for the 1x1 layers, 32x32x16 for the tap layers)
+    const bool s16 = !(p.sw & SW_MFMA32);
+    if (mode == 1) {
+        if (s16) hipLaunchKernelGGL((conv_splitk_hs_kernel<1, true>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN);
+        else hipLaunchKernelGGL((conv_splitk_hs_kernel<1, false>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN);
+    } else {
+        hipLaunchKernelGGL((conv_splitk_hs_kernel<2, false>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN);
+    }
+    return hipGetLastError();
 }
 
 hipError_t launch_conv_dma3(const ConvParams& p, hipStream_t s) {

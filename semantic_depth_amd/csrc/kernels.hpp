@@ -108,7 +108,19 @@ struct ConvParams {
     int rowgrp;        // > 0 (conv_dma3.hip): the GEMM's pixels are ordered (image group of rowgrp images, row, image, column) with rowgrp * Wout = 256,
                        // so that a 256-pixel tile is ONE output row of rowgrp images and skips the k-tiles of the taps whose input row is zero
                        // padding (fc6: 7x7 on 16 rows, 10.7 % of the k-tiles).  Results are bit-identical to the plain order.
+    int ksplit;        // > 1 (sd_set_small_batch; conv_splitk_hs_kernel + splitk_reduce.hip): slices of the K axis (conv_splitk_range)
+    float* partial;    // split-K: f32 partial sums [ksplit][M][Cout] in the workspace, written by the GEMM and read by the reduce launch
 };
+// slice `s` of `S` over `kt` k-tiles: contiguous ranges, as even as possible (the first kt % S slices are one k-tile longer), covering [0, kt) once
+__host__ __device__ inline void conv_splitk_range(int kt, int S, int s, int& first, int& count) {
+    const int base = kt / S, rem = kt - base * S;
+    first = s * base + (s < rem ? s : rem);
+    count = base + (s < rem ? 1 : 0);
+}
+int conv_splitk_slices(long rows, int cout, int kpad, int cus);      // conv_dma3.hip: the rule (1 = not split)
+hipError_t launch_conv_splitk(const ConvParams& p, hipStream_t s);   // conv_dma3.hip: the k-range form of the HS ring -> ConvParams::partial
+const char* conv_splitk_kernel_name(const ConvParams& p);
+hipError_t launch_splitk_reduce(const ConvParams& p, hipStream_t s); // splitk_reduce.hip: sum of the slices + the HS epilogue
 hipError_t launch_conv_igemm(const ConvParams& p, hipStream_t s);
 const char* conv_igemm_kernel_name(const ConvParams& p);
 // split-bf16 engine (conv_split.hip): wt = two bf16 planes [Kpad/8][CoutPad][8] (hi, then lo)
