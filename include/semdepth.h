@@ -401,6 +401,19 @@ sd_status sd_set_small_batch(sd_handle* h, int on);
  * a layer the caps leave below S = 4 is not split either (measured as well).
  * k_tiles_per_slice_out (nullable, int[16]): the S slice lengths in k-tiles -- contiguous ranges in this order, sum = kpad / 32. */
 int sd_small_batch_split(long rows, int cout, int kpad, int cus, int* k_tiles_per_slice_out);
+/* Level 2 (sd_set_small_batch(h, 2); 0 = off and 1 = the GEMM layers above stay what they are, a value above 2 is SD_ERR_INVALID; same guards): level 1 plus
+ * the under-filled 3x3 DIRECT conv layers.  The direct kernel walks work items = (16 x 32-pixel tile) x (pass of 64 output channels), each over the layer's whole
+ * chunk axis (a chunk = 16 input channels x 9 taps); at one frame conv5_x has 8-32 items for 256 CUs.  Level 2 runs such a layer as S contiguous chunk ranges per
+ * item (conv_direct_splitc_hs_kernel, f32 partial sums at conv resolution in the same workspace region) and one reduce launch (splitc_reduce_kernel) that adds
+ * the slices in ascending order and applies the layer's epilogue -- alpha, bias, activation, the fused 2x2 max pool, the HS split with the per-frame clamp
+ * attribution.  Candidates: the 64-channel-pass HS form, not upsample-folded, not the all-upsampled instantiation, no padded channels.
+ * The rule, device-free: S (1 = not split) of a layer with `items` work items in a FULL pass -- (W / 32) * ceil(H / 16) * images * passes at conv resolution --
+ * and `nchunks` chunks on a chip of `cus` CUs.  S = 1 when items >= cus; otherwise S is the smallest value with items * S >= cus, capped at 16 and at
+ * nchunks / 4 (a slice keeps at least 4 chunks).  Measured (profiles/latency_b1_direct.json; the table is in DESIGN section 4): a layer is admitted when
+ * 2 * items <= cus, and above a quarter of the chip (4 * items > cus) only with nchunks >= 16 -- every admitted layer gained more than its default launch's
+ * spread (conv5_x of one frame: 0.13 -> 0.04 ms), the two half-filled layers with 4-5 chunks per slice did not and left the rule.
+ * chunks_per_slice_out (nullable, int[16]): the S slice lengths in chunks -- contiguous ranges in this order, longer ones first, sum = nchunks. */
+int sd_small_batch_split_direct(long items, int nchunks, int cus, int* chunks_per_slice_out);
 /* the layers of `net` this handle runs split, as "layer:S,layer:S" (empty: none); SD_ERR_INVALID when cap is too small */
 sd_status sd_small_batch_plan(const sd_handle* h, sd_net net, char* layers_out, size_t cap);
 

@@ -1,7 +1,11 @@
 """One-frame latency of the f16x2 engine on a max_batch = 1 handle, default against small_batch (Engine(small_batch=True): split-K forms of the
 under-filled GEMM layers), in ONE process on ONE box, the two handles interleaved.
 
-    python scripts/latency_b1.py [--repeats 20] [--warmup 3] [--out profiles/latency_b1.json]
+    python scripts/latency_b1.py [--repeats 20] [--warmup 3] [--out profiles/latency_b1.json] [--level 1]
+
+--level 2 (Engine(small_batch=2): level 1 plus the chunk-split 3x3 direct layers): THREE handles interleaved -- default, level 1 ("level1") and level 2
+("small_batch") --, the watched layers are every layer either plan lists plus conv3_x / conv4_x / conv5_x, every record carries the level-1 time beside the
+default's and level 2's, and the output goes to profiles/latency_b1_direct.json.
 
 Configurations: 256 x 512 with the vgg encoder (the reference's defaults) and 512 x 1024 with resnet50.  Each runs in a child process of its
 own under `timeout -k 10`; a configuration that fails ends the run (nothing is retried).  Reported per configuration, for both handles:
@@ -63,7 +67,10 @@ def layer_records(text):
     return out
 
 
-def run_config(idx, repeats, warmup):
+VGG_DIRECT = {f"conv{b}_{i}" for b in (3, 4, 5) for i in (1, 2, 3)}
+
+
+def run_config(idx, repeats, warmup, level=1):
     os.environ["SEMDEPTH_PROFILE_VERBOSE"] = "1"
     import numpy as np
     import torch
@@ -78,13 +85,16 @@ def run_config(idx, repeats, warmup):
     cams = [Camera(W / 2, H / 2, 1000.0, 1.0, float(W))]
     wf, wm = Wt.make_fcn8s_weights(1, decoder_std=0.05, bias_std=0.1), Wt.make_monodepth_weights(enc, 2, bias_std=0.05)
     engines = {}
-    for name, sb in (("default", False), ("small_batch", True)):
+    for name, sb in (("default", False), ("small_batch", True)) if level == 1 else (("default", False), ("level1", 1), ("small_batch", level)):
         e = Engine(H, W, 1, enc, precision="f16x2", small_batch=sb)
         e.load_weights(L.SD_NET_FCN8S, wf)
         e.load_weights(L.SD_NET_MONODEPTH, wm)
         engines[name] = e
     plan = engines["small_batch"].small_batch_plan()
     watched = set(plan["fcn8s"]) | set(plan["monodepth"]) | {"fc6", "fc7"}
+    if level > 1:
+        plan1 = engines["level1"].small_batch_plan()
+        watched |= set(plan1["fcn8s"]) | set(plan1["monodepth"]) | VGG_DIRECT
     calls = {"fcn8s_forward": lambda e: e.fcn8s_forward(frame), "monodepth_forward": lambda e: e.monodepth_forward(frame),
              "process_batch": lambda e: e.process_batch(frame, cams)}
     for _ in range(warmup):
@@ -126,11 +136,21 @@ def run_config(idx, repeats, warmup):
         r = meta[layer]["default"]
         flops, wbytes = 2.0 * r["M"] * r["N"] * r["K"], 4.0 * r["N"] * r["K"]       # (fp16 hi + lo plane of every weight)
         S = {**plan["fcn8s"], **plan["monodepth"]}.get(layer, 1)
+        if level > 1:
+            # the criterion is level 2's gain over the handle WITHOUT the direct split where that is what changed the layer: a GEMM layer level 1 already split
+            # is judged against the default as before, and its level-1 time shows that level 2 left it alone
+            l1 = stat(layers["level1"][layer])
+            direct = layer not in plan1["fcn8s"] and layer not in plan1["monodepth"]
+            table.append(dict(layer=layer, S=S, direct=bool(direct and S > 1), M=r["M"], N=r["N"], K=r["K"], default_ms=d, level1_ms=l1, small_batch_ms=s,
+                              default_kernels=meta[layer]["default"]["kernels"], small_batch_kernels=meta[layer]["small_batch"]["kernels"],
+                              floor_weights_ms=wbytes / HBM_BPS * 1e3, floor_mfma_ms=flops / MFMA_FLOPS * 1e3,
+                              keeps=bool(S > 1 and d["median"] - s["median"] > d["max"] - d["min"])))
+            continue
         table.append(dict(layer=layer, S=S, M=r["M"], N=r["N"], K=r["K"], default_ms=d, small_batch_ms=s,
                           default_kernels=meta[layer]["default"]["kernels"], small_batch_kernels=meta[layer]["small_batch"]["kernels"],
                           floor_weights_ms=wbytes / HBM_BPS * 1e3, floor_mfma_ms=flops / MFMA_FLOPS * 1e3,
                           keeps=bool(S > 1 and d["median"] - s["median"] > d["max"] - d["min"])))
-    res = dict(H=H, W=W, encoder=enc, precision="f16x2", max_batch=1, repeats=repeats, warmup=warmup, device=torch.cuda.get_device_name(0),
+    res = dict(H=H, W=W, encoder=enc, precision="f16x2", max_batch=1, level=level, repeats=repeats, warmup=warmup, device=torch.cuda.get_device_name(0),
                split_plan=plan, layers=table, end_to_end_ms={n: {c: stat(v) for c, v in per.items()} for n, per in e2e.items()})
     d, s = res["end_to_end_ms"]["default"]["fcn8s_forward"], res["end_to_end_ms"]["small_batch"]["fcn8s_forward"]
     res["fcn8s_forward_faster"] = bool(d["median"] - s["median"] > d["max"] - d["min"])
@@ -146,21 +166,22 @@ def main():
     ap.add_argument("--out", default=None, help="default profiles/latency_b1.json; required with --config")
     ap.add_argument("--config", type=int, default=None, help="run ONE configuration in this process (what the parent starts)")
     ap.add_argument("--step-timeout", type=int, default=420)
+    ap.add_argument("--level", type=int, default=1, choices=(1, 2), help="the small_batch level of the second handle; 2 adds a level-1 handle beside the default")
     a = ap.parse_args()
     if a.repeats < 20:
         ap.error("at least 20 timed repeats")
     if a.config is not None and a.out is None:
         ap.error("--config writes ONE configuration's record: name its file with --out")
-    a.out = a.out or os.path.join(ROOT, "profiles", "latency_b1.json")
+    a.out = a.out or os.path.join(ROOT, "profiles", "latency_b1.json" if a.level == 1 else "latency_b1_direct.json")
     if a.config is not None:
-        json.dump(run_config(a.config, a.repeats, a.warmup), open(a.out, "w"), indent=1)
+        json.dump(run_config(a.config, a.repeats, a.warmup, a.level), open(a.out, "w"), indent=1)
         return 0
     results = []
     for i in range(len(CONFIGS)):
         with tempfile.TemporaryDirectory() as td:
             part = os.path.join(td, "part.json")
             cmd = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--config", str(i), "--repeats", str(a.repeats),
-                   "--warmup", str(a.warmup), "--out", part]
+                   "--warmup", str(a.warmup), "--out", part, "--level", str(a.level)]
             rc = subprocess.run(cmd).returncode
             if rc != 0:          # a fault, an abort or the time limit: nothing more is started on the GPU
                 print(f"configuration {CONFIGS[i]} ended with status {rc}: stopping", file=sys.stderr)
@@ -171,9 +192,9 @@ def main():
               open(a.out, "w"), indent=1)
     for r in results:
         print(f"{r['H']}x{r['W']} {r['encoder']}: " + ", ".join(
-            f"{c} {r['end_to_end_ms']['default'][c]['median']:.3f} -> {r['end_to_end_ms']['small_batch'][c]['median']:.3f} ms" for c in r["end_to_end_ms"]["default"]))
+            f"{c} " + " -> ".join(f"{per[c]['median']:.3f}" for per in r["end_to_end_ms"].values()) + " ms" for c in r["end_to_end_ms"]["default"]))
         for t in r["layers"]:
-            print(f"   {t['layer']:22s} S={t['S']:<2d} {t['default_ms']['median']:.4f} -> {t['small_batch_ms']['median']:.4f} ms  "
+            print(f"   {t['layer']:22s} S={t['S']:<2d} {t['default_ms']['median']:.4f} (spread {t['default_ms']['max'] - t['default_ms']['min']:.4f}) -> {t['small_batch_ms']['median']:.4f} ms  "
                   f"(floors: weights {t['floor_weights_ms']:.4f}, mfma {t['floor_mfma_ms']:.4f})  {'keeps' if t['keeps'] else ('-' if t['S'] == 1 else 'NO GAIN')}")
     return 0
 

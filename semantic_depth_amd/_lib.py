@@ -123,6 +123,7 @@ SIGNATURES = {
     "sd_set_reserved_cus": (C.c_int, [_H, C.c_int]),
     "sd_set_small_batch": (C.c_int, [_H, C.c_int]),
     "sd_small_batch_split": (C.c_int, [C.c_long, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "sd_small_batch_split_direct": (C.c_int, [C.c_long, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "sd_small_batch_plan": (C.c_int, [_H, C.c_int, C.c_char_p, C.c_size_t]),
 }
 

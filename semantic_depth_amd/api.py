@@ -36,11 +36,12 @@ DEFAULT_ON_RANGE = "raise"
 
 
 def shared_engine(H: int, W: int, device: int = 0, precision: str = DEFAULT_PRECISION, encoder: str | None = None, max_batch: int = 1,
-                  on_range: str = DEFAULT_ON_RANGE, small_batch: bool = False) -> Engine:
+                  on_range: str = DEFAULT_ON_RANGE, small_batch: bool | int = False) -> Engine:
     """the registered Engine for this geometry; created on first use.  ``encoder`` None = whatever is registered (or 'vgg',
     the reference's default --monodepth_encoder, semantic_depth.py:721-722).  ``small_batch`` (Engine(small_batch=), 'f16x2' only): the
-    split-K forms of the deep GEMM layers for one-frame calls; part of the key like on_range."""
-    key = (int(H), int(W), int(device), precision, RC.check_mode(on_range), bool(small_batch))
+    split-K forms of the deep GEMM layers for one-frame calls (2: also the chunk-split direct 3x3 layers); its level is part of the key like on_range
+    (True and 1 are the same engine)."""
+    key = (int(H), int(W), int(device), precision, RC.check_mode(on_range), int(small_batch))
     per = _engines.setdefault(key, {})
     if encoder is None:
         if per:
@@ -56,7 +57,7 @@ def shared_engine(H: int, W: int, device: int = 0, precision: str = DEFAULT_PREC
 
 def register_engine(engine: Engine):
     """make an existing Engine the shared one for its geometry (bench / batched drivers build theirs with max_batch > 1)."""
-    key = (engine.H, engine.W, engine.device.index or 0, engine.precision, engine.on_range, bool(getattr(engine, "small_batch", False)))
+    key = (engine.H, engine.W, engine.device.index or 0, engine.precision, engine.on_range, int(getattr(engine, "small_batch_level", 0)))
     if not hasattr(engine, "_api_loaded"):
         engine._api_loaded = {}
     _engines.setdefault(key, {})[engine.encoder] = engine
@@ -102,16 +103,17 @@ class SegmentFrame:
     """SegmentFrame(input_shape, model_var_dir, use_frozen, use_xla, CUDA_DEVICE_NUMBER) — semantic_depth.py:464-469.
     ``model_var_dir``: dict / .npz of FCN-8s weights (weights.fcn8s_weight_shapes).  use_frozen / use_xla are accepted
     and ignored (TF graph details).  ``on_range`` (Engine(on_range=)): 'raise' or 'recompute' a frame that leaves the fp16 range.
-    ``small_batch`` (Engine(small_batch=)): the split-K forms of the deep GEMM layers, for the one-frame calls of this class."""
+    ``small_batch`` (Engine(small_batch=)): the split-K forms of the deep GEMM layers, for the one-frame calls of this class; 2 adds the chunk-split
+    direct 3x3 layers."""
 
     def __init__(self, input_shape, model_var_dir, use_frozen=True, use_xla=False, CUDA_DEVICE_NUMBER="0", engine: Engine | None = None,
-                 precision: str = DEFAULT_PRECISION, on_range: str = DEFAULT_ON_RANGE, small_batch: bool = False):
+                 precision: str = DEFAULT_PRECISION, on_range: str = DEFAULT_ON_RANGE, small_batch: bool | int = False):
         self.input_shape = tuple(input_shape)
         self.model_var_dir = model_var_dir
         self.CUDA_DEVICE_NUMBER = CUDA_DEVICE_NUMBER
         self.precision = precision
         self.on_range = RC.check_mode(on_range)
-        self.small_batch = bool(small_batch)
+        self.small_batch = int(small_batch)
         self._weights = _load_weight_arg(model_var_dir)
         self._engine = engine
 
@@ -151,7 +153,7 @@ class DepthFrame:
 
     def __init__(self, is_city=False, encoder="vgg", input_height=256, input_width=512, checkpoint_path=None, f=None,
                  engine: Engine | None = None, precision: str = DEFAULT_PRECISION, device: int = 0, on_range: str = DEFAULT_ON_RANGE,
-                 small_batch: bool = False):
+                 small_batch: bool | int = False):
         self.is_city, self.encoder = is_city, encoder
         self.input_height, self.input_width = input_height, input_width
         self.f = float(f) if f is not None else None

@@ -104,12 +104,30 @@ int op_ksplit(const sd_handle* h, const NetPlan& p, const OpDesc& op) {
     return conv_splitk_slices((long)p.images * d.H * d.W, d.C, op.Kpad, h->cus);
 }
 
+// sd_set_small_batch level 2: slices of the chunk axis this op runs in on this handle (1 = not split).  Like op_ksplit it reads what the handle fixes.  Candidates:
+// OP_CONV_DIRECT layers of the three-product engine in the 64-channel-pass form (fused 2x2 pool and concatenated sources included), not folded, not the
+// all-upsampled (source-resolution tile) instantiation, no padded channels.  The output may be sub-planar (the hand-off between two direct layers: conv4_1 ->
+// conv4_2 -> conv4_3): the reduce launch writes either layout.  (SEMDEPTH_DISABLE=direct: the planner makes no such op)
+int op_dsplit(const sd_handle* h, const NetPlan& p, const OpDesc& op) {
+    if (h->small_batch < 2 || op.kind != OP_CONV_DIRECT || op.scheme != SC_HS) return 1;
+    const TensorDesc& d = p.tensors[op.dst];
+    if (d.fmt != PL_HS || op.nsplit < 1 || d.C != 64 * op.nsplit || op.fold || (d.Ctf > 0 && d.Ctf < d.C)) return 1;
+    const int H = d.H << op.fuse_pool, W = d.W << op.fuse_pool;        // conv resolution
+    bool all_up = true;
+    for (int i = 0; i < op.nsrc; ++i) all_up = all_up && op.up[i] == 1;
+    if (all_up && !(H & 1) && !(W & 1)) return 1;
+    return conv_splitc_slices(conv_direct_items(W, H, p.images, op.nsplit), op.nchunks, h->cus);
+}
+
 size_t splitk_scratch_bytes(const sd_handle* h) {
     size_t mx = 0;
     for (const NetPlan* p : {&h->fcn, &h->mono})
         for (const OpDesc& op : p->ops) {
+            const TensorDesc& d = p->tensors[op.dst];
             const int S = op_ksplit(h, *p, op);
-            if (S > 1) { const TensorDesc& d = p->tensors[op.dst]; mx = std::max(mx, (size_t)S * p->images * d.H * d.W * d.C * sizeof(float)); }
+            if (S > 1) mx = std::max(mx, (size_t)S * p->images * d.H * d.W * d.C * sizeof(float));
+            const int Sd = op_dsplit(h, *p, op);        // (partials at conv resolution: before a fused pool)
+            if (Sd > 1) mx = std::max(mx, (size_t)Sd * p->images * (d.H << op.fuse_pool) * (d.W << op.fuse_pool) * d.C * sizeof(float));
         }
     return mx;
 }
@@ -306,6 +324,15 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, 
                 c.sw = h->sw; c.reserve_cus = h->reserve_cus;
                 c.sat = sat_counter(h);
                 const bool x3 = op.scheme == SC_BF16X3;
+                if (const int S = op_dsplit(h, p, op); S > 1) {
+                    // sd_set_small_batch level 2: the chunk-range form into the partial-sum scratch, then the reduce launch with the layer's epilogue
+                    c.csplit = S; c.partial = reinterpret_cast<float*>(h->ws + h->o_splitk);
+                    st = bracketed(op, e, N * c.H * c.W, d.C, [&] { return launch_conv_direct_splitc(c, s); }, [&] { return "conv_direct_splitc_hs_kernel"; });
+                    if (st != SD_OK || e != hipSuccess) break;
+                    st = bracketed(op, e, N * c.H * c.W, d.C, [&] { return launch_splitc_reduce(c, s); }, [&] { return "splitc_reduce_kernel"; },
+                                   (double)N * d.C * ((double)c.H * c.W * S * sizeof(float) + (double)d.H * d.W * elem_bytes(d.fmt)));
+                    break;
+                }
                 st = bracketed(op, e, N * c.H * c.W, d.C, [&] { return x3 ? launch_conv_direct3(c, s) : launch_conv_direct(c, s); },
                                [&] { return x3 ? conv_direct3_kernel_name(c) : conv_direct_kernel_name(c); });
                 break;
@@ -1092,6 +1119,7 @@ sd_status sd_saturation_count(sd_handle* h, uint64_t* count_out, int reset) {
 
 sd_status sd_set_small_batch(sd_handle* h, int on) {
     if (!h) return SD_ERR_INVALID;
+    if (on > 2) return fail(h, SD_ERR_INVALID, "sd_set_small_batch: levels 0 (off), 1 (split-K GEMM layers) and 2 (1 + chunk-split direct 3x3 layers)");
     if (h->prec != (int)SD_PREC_F16X2) return fail(h, SD_ERR_INVALID, "sd_set_small_batch: the split-K forms exist for SD_PREC_F16X2 only");
     if (h->bound) return fail(h, SD_ERR_STATE, "sd_set_small_batch: call it before sd_bind_memory (the workspace changes)");
     if (on && !h->cus) {
@@ -1100,7 +1128,7 @@ sd_status sd_set_small_batch(sd_handle* h, int on) {
         if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess || n <= 0) { (void)hipGetLastError(); n = 256; }
         h->cus = n;
     }
-    h->small_batch = on ? 1 : 0;
+    h->small_batch = on < 0 ? 1 : on;       // (any other non-zero value has always meant "on")
     carve_workspace(h);
     return SD_OK;
 }
@@ -1116,12 +1144,23 @@ int sd_small_batch_split(long rows, int cout, int kpad, int cus, int* k_tiles_pe
     return S;
 }
 
+int sd_small_batch_split_direct(long items, int nchunks, int cus, int* chunks_per_slice_out) {
+    const int S = conv_splitc_slices(items, nchunks, cus);
+    if (chunks_per_slice_out)
+        for (int i = 0; i < S; ++i) {
+            int first, count;
+            conv_splitk_range(nchunks, S, i, first, count);
+            chunks_per_slice_out[i] = S > 1 ? count : (nchunks > 0 ? nchunks : 0);
+        }
+    return S;
+}
+
 sd_status sd_small_batch_plan(const sd_handle* h, sd_net net, char* layers_out, size_t cap) {
     if (!h || !layers_out || !cap) return SD_ERR_INVALID;
     const NetPlan& p = plan_of(h, net);
     std::string out;
     for (const OpDesc& op : p.ops) {
-        const int S = op_ksplit(h, p, op);
+        const int Sk = op_ksplit(h, p, op), S = Sk > 1 ? Sk : op_dsplit(h, p, op);
         if (S > 1) out += (out.empty() ? "" : ",") + op.name + ":" + std::to_string(S);
     }
     std::strncpy(layers_out, out.c_str(), cap - 1);

@@ -76,8 +76,13 @@ __device__ __forceinline__ DirectChunk load_chunk(const DirectChunk* ptr) {
 // 9, but 4 instead of 9 MFMA groups per output pixel.  Wave w owns parity w & 3 and the source rows 4 (w >> 2) .. + 3 of the tile: its two 32-pixel MFMA column groups
 // are 2 source rows x 16 source columns each (the fragment scheme of conv_direct3.hip's fold).  The X fragments of a chunk (2 column shifts x 4 row offsets x 2 planes)
 // are read once and stay in registers; a chunk is 4 NB MFMA groups, so the DMA slots go out two per group.
-template <int NB, int MT, bool F16, bool N16 = false, bool UP = false, bool W1 = false, bool X2 = false, bool H2 = false, bool FOLD = false>
+// SPLITC (with H2, NB = 2, not UP / FOLD / N16; sd_set_small_batch level 2, profiled as conv_direct_splitc_hs_kernel): the chunk-range form.  A work item is
+// (tile, slice, pass): it walks the contiguous chunk range conv_splitk_range(nchunks, csplit, slice) only -- the issue cursor too, so the first chunk of the next
+// item's range still lands under this item's epilogue -- and stores its raw f32 accumulators to ConvDirectParams::partial[slice][pixel][Cstride] at conv
+// resolution; alpha, bias, activation, pool, split and clamp belong to splitc_reduce_kernel.  The passes of one (tile, slice) stay neighbouring items.
+template <int NB, int MT, bool F16, bool N16 = false, bool UP = false, bool W1 = false, bool X2 = false, bool H2 = false, bool FOLD = false, bool SPLITC = false>
 __global__ __launch_bounds__(512, (N16 && MT == 1) ? 2 : 1) void conv_direct_kernel(const ConvDirectParams p) {
+    static_assert(!SPLITC || (H2 && NB == 2 && MT == 2 && !N16 && !UP && !FOLD), "the chunk-range form exists for the 64-channel-pass HS kernel");
     static_assert(!N16 || NB == 1, "N16 is a variant of the 32-channel kernel");
     static_assert(!H2 || (F16 && X2 && !W1), "H2 is the fp16 form with both planes of both operands");
     static_assert(!FOLD || (H2 && UP && !N16 && MT == 2), "the folded form: three-product engine, source-resolution tiles");
@@ -109,13 +114,21 @@ __global__ __launch_bounds__(512, (N16 && MT == 1) ? 2 : 1) void conv_direct_ker
     const int frow = lane & 31, fk = lane >> 5;
 
     // work item = (tile, pass of <= 64 output channels); the passes of a tile are neighbouring items
-    const int items = total * p.nsplit;
-    struct Tile { int img, ty0, tx0, half; };
+    const int items = SPLITC ? total * p.nsplit * p.csplit : total * p.nsplit;
+    struct Tile { int img, ty0, tx0, half, slice, c0, c1; };     // (slice, chunks [c0, c1): SPLITC only)
     auto tile_of = [&](int it) {
         if ((items & 7) == 0) it = (it & 7) * (items >> 3) + (it >> 3);     // neighbouring items (shared halos) on one XCD
         Tile r;
         int tid = it / p.nsplit;
         r.half = it - tid * p.nsplit;
+        if constexpr (SPLITC) {
+            const int t2 = tid / p.csplit;
+            int cnt;
+            r.slice = tid - t2 * p.csplit;
+            conv_splitk_range(p.nchunks, p.csplit, r.slice, r.c0, cnt);
+            r.c1 = r.c0 + cnt;
+            tid = t2;
+        }
         const int bx = tid % tiles_x; tid /= tiles_x;
         r.tx0 = bx * D_TW; r.ty0 = (tid % tiles_y) * D_TH; r.img = tid / tiles_y;
         return r;
@@ -211,10 +224,20 @@ __global__ __launch_bounds__(512, (N16 && MT == 1) ? 2 : 1) void conv_direct_ker
     int itid = tid, ic = 0;
     Tile icur = cur;
     set_tile(icur);
+    if constexpr (SPLITC) ic = icur.c0;
     auto advance = [&]() {
-        if (++ic == p.nchunks) { ic = 0; itid += gridDim.x; if (itid < items) { icur = tile_of(itid); set_tile(icur); } }
+        if constexpr (SPLITC) {
+            if (++ic == icur.c1) { itid += gridDim.x; if (itid < items) { icur = tile_of(itid); set_tile(icur); ic = icur.c0; } }
+        } else {
+            if (++ic == p.nchunks) { ic = 0; itid += gridDim.x; if (itid < items) { icur = tile_of(itid); set_tile(icur); } }
+        }
     };
-    {
+    if constexpr (SPLITC) {
+        const ChunkCtx k = begin_chunk(load_chunk(p.chunks + ic), icur, ic, 0);
+#pragma unroll
+        for (int sidx = 0; sidx < NSLOT; ++sidx) slot(k, sidx);
+        advance();
+    } else {
         const ChunkCtx k = begin_chunk(load_chunk(p.chunks), icur, 0, 0);
 #pragma unroll
         for (int sidx = 0; sidx < NSLOT; ++sidx) slot(k, sidx);
@@ -235,7 +258,8 @@ __global__ __launch_bounds__(512, (N16 && MT == 1) ? 2 : 1) void conv_direct_ker
         for (int a = 0; a < MT; ++a)
 #pragma unroll
             for (int pb = 0; pb < 2; ++pb) acc16[a][pb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int c = 0; c < p.nchunks; ++c, ++g) {
+        const int nck = SPLITC ? cur.c1 - cur.c0 : p.nchunks;       // chunks this item walks
+        for (int c = 0; c < nck; ++c, ++g) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();          // stage g has landed for every wave; everyone is done with stage g-1
             const bool more = itid < items;        // item g + 1 exists: its DMAs go into stage (g + 1) & 1 during this chunk
@@ -394,6 +418,24 @@ __global__ __launch_bounds__(512, (N16 && MT == 1) ? 2 : 1) void conv_direct_ker
 
         // ---- epilogue: bias + activation, split once, LDS transpose (in the stage just consumed; the other one is being
         //      filled for the next tile), 16-byte runs of 8 channels per pixel and plane ----
+        if constexpr (SPLITC) {
+            // the raw accumulators of this (tile, slice, pass): lane = pixel frow of the wave's row, channels 8 r4 + 4 fk .. + 3 of the pass -- one 16-byte store each,
+            // the two lanes of a pixel 32 contiguous bytes, the 8 stores of a lane the pass's 256 bytes of its pixel.  No LDS: nothing waits for the other waves.
+            // Rows of a partial last tile are not stored (the reduce never reads them)
+#pragma unroll
+            for (int a = 0; a < MT; ++a) {
+                const int y = cur.ty0 + MT * wave + a;
+                if (y >= p.H) continue;
+                float* o = p.partial + ((size_t)cur.slice * p.N * p.H * p.W + (size_t)(cur.img * p.H + y) * p.W + cur.tx0 + frow) * p.Cstride + half * 64 + 4 * fk;
+#pragma unroll
+                for (int r4 = 0; r4 < 4 * NB; ++r4) {
+                    const int nb = r4 >> 2, q = r4 & 3;
+                    *reinterpret_cast<f32x4*>(o + 8 * r4) = (f32x4){acc[a][nb][4 * q], acc[a][nb][4 * q + 1], acc[a][nb][4 * q + 2], acc[a][nb][4 * q + 3]};
+                }
+            }
+            if (tid + (int)gridDim.x < items) cur = tile_of(tid + gridDim.x);
+            continue;
+        }
         __builtin_amdgcn_s_barrier();
         auto epilogue = [&](auto tag, auto otag) {
             constexpr int ACT = decltype(tag)::value;
@@ -602,7 +644,7 @@ hipError_t launch_conv_direct(const ConvDirectParams& p, hipStream_t s) {
     // every source behind a x2 upsample: source-resolution halo tiles (48 KiB of LDS for N16 with 16-row tiles: they stay)
     const bool up = p.all_up && !(p.H & 1) && !(p.W & 1);
     const int th = n16 && !up ? 8 : 16;
-    const int tiles = (p.W / D_TW) * ((p.H + th - 1) / th) * p.N * p.nsplit;
+    const int tiles = (int)conv_direct_items(p.W, p.H, p.N, p.nsplit, th);
     // persistent grid: as many workgroups as the instantiation keeps resident (1-3 per CU, by LDS and registers)
 #define SD_DIRECT_(NB_, MT_, F16_, N16_, UP_, W1_, X2_, ...) \
     do { static int per_cu = 0; \
@@ -637,6 +679,40 @@ hipError_t launch_conv_direct(const ConvDirectParams& p, hipStream_t s) {
 #undef SD_DIRECT_H2
 #undef SD_DIRECT_
 #undef SD_DIRECT
+    return hipGetLastError();
+}
+
+// sd_set_small_batch level 2, the rule (semdepth.h sd_small_batch_split_direct): slices of the chunk axis of a layer with `items` work items in a FULL pass and
+// `nchunks` 16-channel chunks on a chip of `cus` CUs.  Fixed by reasoning: a layer with items >= cus fills the chip; S is the smallest value with items * S >= cus,
+// at most 16, and a slice keeps at least 4 chunks (36 MFMA groups per product plane: below it the two-stage ring's prologue dominates).  Measured
+// (profiles/latency_b1_direct.json): a layer is admitted when 2 * items <= cus, and above a quarter of the chip (4 * items > cus, where S = 2) only
+// with at least 16 chunks -- the two half-filled layers with 4-5 chunks per slice (conv2_2 of a 256 x 512 frame, iconv3 of a 512 x 1024 one) gained nothing, conv4_x with
+// 8-16 per slice did
+int conv_splitc_slices(long items, int nchunks, int cus) {
+    if (items <= 0 || nchunks <= 0 || cus <= 0 || items >= cus || 2 * items > cus || (4 * items > cus && nchunks < 16)) return 1;
+    long S = (cus + items - 1) / items;
+    if (S > 16) S = 16;
+    if (S > nchunks / 4) S = nchunks / 4;
+    return S < 2 ? 1 : (int)S;
+}
+
+// the chunk-range form of the 64-channel-pass HS kernel: the same persistent grid rule over (tile, slice, pass) items
+hipError_t launch_conv_direct_splitc(const ConvDirectParams& p, hipStream_t s) {
+    if (p.scheme != SC_HS || p.out_fmt != PL_HS || p.Cout != 64 || p.nsplit < 1 || p.nsplit > 8 || p.W % D_TW || p.rows_per_wave != 2 || p.fold || p.nreal ||
+        (p.all_up && !(p.H & 1) && !(p.W & 1)) || (p.pool && ((p.H & 1) || (p.W & 1))) || p.csplit < 2 || p.csplit > 16 || p.nchunks / p.csplit < 1 || !p.partial)
+        return hipErrorInvalidValue;
+    static int cus = 0, per_cu = 0;
+    if (!cus) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
+        cus = prop.multiProcessorCount;
+    }
+    auto* const kern = conv_direct_kernel<2, 2, true, false, false, false, true, true, false, true>;
+    if (!per_cu && (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 512, 0) != hipSuccess || per_cu < 1)) per_cu = 1;
+    const long items = conv_direct_items(p.W, p.H, p.N, p.nsplit) * p.csplit;
+    const long slots = (long)(cus - p.reserve_cus > 0 ? cus - p.reserve_cus : 1) * per_cu;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(items < slots ? items : slots)), dim3(512), 0, s, p);
     return hipGetLastError();
 }
 

@@ -237,7 +237,14 @@ struct ConvDirectParams {
     unsigned sw;                 // Switch bits of the handle
     int reserve_cus;             // the persistent grid is (CUs - reserve_cus) workgroups (ConvParams::reserve_cus)
     unsigned long long* sat;     // DEVICE counter of fp16-saturated output values (split_fmt.hpp sat_report; sd_saturation_count)
+    int csplit;                  // > 1 (sd_set_small_batch level 2; conv_direct_splitc_hs_kernel + splitc_reduce_kernel): slices of the chunk axis (conv_splitk_range over nchunks)
+    float* partial;              // chunk split: f32 partial sums [csplit][N * H * W][Cstride] at conv (pre-pool) resolution in the workspace
 };
+// work items of a direct launch: (32-pixel-wide tile of th rows) x (pass of <= 64 output channels).  The launcher's grid and the chunk-split rule both count with it
+inline long conv_direct_items(int W, int H, int images, int nsplit, int th = 16) { return (long)(W / 32) * ((H + th - 1) / th) * images * nsplit; }
+int conv_splitc_slices(long items, int nchunks, int cus);               // conv_direct.hip: the rule of the chunk split (1 = not split)
+hipError_t launch_conv_direct_splitc(const ConvDirectParams& p, hipStream_t s);   // conv_direct.hip: the chunk-range form of the 64-channel-pass HS kernel -> ConvDirectParams::partial
+hipError_t launch_splitc_reduce(const ConvDirectParams& p, hipStream_t s);        // splitk_reduce.hip: sum of the slices + the direct kernel's HS epilogue (incl. the fused pool)
 hipError_t launch_conv_direct3(const ConvDirectParams& p, hipStream_t s);       // conv_direct3.hip: the bf16 x 3 form (SD_PREC_BF16X3)
 const char* conv_direct3_kernel_name(const ConvDirectParams& p);
 hipError_t launch_conv_direct(const ConvDirectParams& p, hipStream_t s);

@@ -86,7 +86,7 @@ FP16_PLANE_ENGINES = ("f16x2", "f16x2x2", "mixed", "plan")
 
 class Engine:
     def __init__(self, H: int, W: int, max_batch: int = 1, encoder: str = "resnet50", device: int = 0, precision: str = "f32",
-                 plan: tuple[str, str] | None = None, range_check: bool = True, on_range: str = "raise", small_batch: bool = False):
+                 plan: tuple[str, str] | None = None, range_check: bool = True, on_range: str = "raise", small_batch: bool | int = False):
         """precision: 'f32' (exact f32 MFMA), 'bf16x3' (fp32-grade on the bf16 MFMA: every f32 operand as three bf16 planes that sum to it
         exactly, 6 MFMA products), 'f16x2' (fp32-grade on 3 fp16 MFMA products: activations as fp16 hi + 2^11-scaled lo planes, weights as fp16 hi + lo of
         w * 2^k, k per layer), 'bf16x2' (3 bf16 MFMA products, ~1e-5), 'mixed' (monodepth on 2 fp16 products), 'plan' (per-layer
@@ -102,8 +102,13 @@ class Engine:
         small_batch ('f16x2' only; sd_set_small_batch): the GEMM layers whose full pass has at most an eighth as many 256 x 256 output tiles as the chip has
         CUs (fc6 / fc7 and the res5 1x1 layers of a max_batch = 1 handle; sd_small_batch_split is the rule) run split along K, S slices per tile plus a reduce launch
         (``small_batch_plan()`` lists layer -> S).  Their sums are formed in another order, so the last bits differ from the default
-        handle's; on a handle where no layer qualifies nothing changes.  The 'bf16x3' companion of on_range='recompute' is not split."""
+        handle's; on a handle where no layer qualifies nothing changes.  The 'bf16x3' companion of on_range='recompute' is not split.
+        small_batch=2 (level 2; True means 1): level 1 plus the under-filled 3x3 direct conv layers (conv4_x / conv5_x of FCN-8s, the deep encoder and iconv layers
+        of monodepth; sd_small_batch_split_direct is the rule) split along their input-channel chunks, S contiguous chunk ranges per tile plus a reduce launch
+        that applies the layer's epilogue, fused 2x2 pool included.  ``small_batch_level`` holds the level, ``small_batch`` stays its truth value."""
         RC.check_mode(on_range)
+        if int(small_batch) not in (0, 1, 2):
+            raise ValueError("small_batch is False / True or the level 0, 1 or 2")
         if small_batch and precision not in ("f16x2", "f16x2x2"):
             raise ValueError("small_batch needs precision='f16x2'")
         if not torch.cuda.is_available():
@@ -125,9 +130,9 @@ class Engine:
             st = self.lib.sd_create(C.byref(h), device, H, W, max_batch, enc, prec)
         L.check(self.lib, None, st, f"sd_create(H={H}, W={W}, max_batch={max_batch}, {encoder}, {precision}, plan={plan})")
         self.h = h
-        self.small_batch = bool(small_batch)
+        self.small_batch, self.small_batch_level = bool(small_batch), int(small_batch)
         if small_batch:
-            L.check(self.lib, h, self.lib.sd_set_small_batch(h, 1), "sd_set_small_batch")
+            L.check(self.lib, h, self.lib.sd_set_small_batch(h, int(small_batch)), "sd_set_small_batch")
         fw, mw, ws = C.c_size_t(), C.c_size_t(), C.c_size_t()
         L.check(self.lib, h, self.lib.sd_query_memory(h, C.byref(fw), C.byref(mw), C.byref(ws)), "sd_query_memory")
         self.bytes = dict(fcn_weights=fw.value, mono_weights=mw.value, workspace=ws.value)
@@ -536,8 +541,8 @@ class Engine:
         return out
 
     def small_batch_plan(self) -> dict:
-        """{net: {layer: S}}: the GEMM layers a small_batch handle runs split along K and their slice counts (empty without the switch, or
-        where every layer's full pass already fills the chip)"""
+        """{net: {layer: S}}: the GEMM layers a small_batch handle runs split along K -- at level 2 also the direct 3x3 layers it runs split along
+        their chunk axis -- and their slice counts (empty without the switch, or where every layer's full pass already fills the chip)"""
         out = {}
         for name, net in (("fcn8s", L.SD_NET_FCN8S), ("monodepth", L.SD_NET_MONODEPTH)):
             buf = C.create_string_buffer(8192)
