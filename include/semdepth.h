@@ -252,6 +252,48 @@ sd_status sd_jpeg_reconstruct_bgr(sd_handle* h, const int16_t* coef_dev, size_t 
 sd_status sd_png_encode_bgr_files(const char* const* paths, int n, int height, int width, const uint8_t* frames_host, size_t frame_stride,
                                   int level, int threads, int* status_out);
 
+/* ---- result images, device route: the GPU makes each frame's complete zlib stream, the host wraps it in PNG chunks ----
+ * The stream format, fixed here (C = 32768):
+ *   filtered bytes   filtered row y is the byte 4 followed by the Paeth residuals (PNG filter type 4, bpp 3, pixels outside the image
+ *                    count as 0) of the row's RGB bytes -- the BGR -> RGB swap is part of the read.  The filtered frame is the flat
+ *                    sequence of height * (1 + 3 * width) bytes.
+ *   chunks           the sequence is cut every C bytes, wherever that falls (inside a row, inside a pixel); the last chunk is shorter.
+ *                    Chunks are coded independently: no token refers to a byte of another chunk, the first byte of a chunk is a literal.
+ *   tokens           inside a chunk a maximal run of n >= 4 equal bytes is one literal followed by distance-1 matches over the other
+ *                    n - 1 bytes: matches of 258 while more than 258 bytes remain or exactly 258 do, then one match of 3..257, or 1..2
+ *                    literals when that few bytes remain.  Every other byte is a literal.
+ *   a chunk          one non-final dynamic-Huffman block (BTYPE 10).  Literal/length code: Huffman lengths of the chunk's token histogram
+ *                    (end-of-block counted once), limited to 15 bits; HLIT covers up to the last used symbol.  Two distance codes, 0 and
+ *                    1, of length 1 each (a complete tree; a match sends the one bit of code 0).  The code lengths travel as plain
+ *                    values 0..15 (no repeat codes 16/17/18) under a code-length code limited to 7 bits, all 19 of whose lengths are
+ *                    sent.  Behind the end-of-block symbol an empty non-final stored block pads to a byte boundary: 000, zero bits,
+ *                    00 00 FF FF.  When the dynamic block (header through end-of-block, in whole bytes) is not smaller than len + 5, the
+ *                    chunk is instead one stored block 00 LEN NLEN bytes followed by the same empty stored block (00 00 00 FF FF).
+ *                    The code construction (two-queue Huffman over the symbols sorted by (count, symbol), leaf before internal node at
+ *                    equal weight; depths clamped to the limit and the Kraft sum repaired on the per-length counts; longest lengths to
+ *                    the rarest symbols; canonical codes) is semantic_depth_amd/csrc/png_deflate.hpp, which host and device both run.
+ *   the stream       78 01, the chunks in order, 01 00 00 FF FF (the final, empty stored block), the big-endian Adler-32 of the
+ *                    filtered bytes.  At most 2 + sum(len_c + 16) + 16 bytes for any frame content.
+ * sd_png_encode_workspace: the device workspace sd_png_encode_bgr needs for B frames of height x width and the smallest stream_stride it
+ * accepts (that bound).  SD_ERR_INVALID for B < 1 or an extent outside 1..16384. */
+sd_status sd_png_encode_workspace(int B, int height, int width, size_t* workspace_bytes, size_t* stream_stride);
+/* DEVICE: frames u8 [B,height,width,3] BGR (frame b at frames_dev + b * frame_stride) -> frame b's stream at streams_dev + b * stream_stride,
+ * its byte count in sizes_dev[b] (u64).  Bytes of a frame's slot behind its size are not written.  Three launches (one workgroup per
+ * chunk; the layout of each frame; the chunks gathered) enqueued on `stream`, no synchronisation; the handle need not be bound.
+ * SD_ERR_INVALID, nothing launched: an extent outside 1..16384, B < 1, frame_stride < height * width * 3, stream_stride below the bound,
+ * workspace_bytes below sd_png_encode_workspace, a workspace that is not 16-byte aligned. */
+sd_status sd_png_encode_bgr(sd_handle* h, const uint8_t* frames_dev, size_t frame_stride, int B, int height, int width, uint8_t* streams_dev,
+                            size_t stream_stride, uint64_t* sizes_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* HOST: the CPU statement of sd_png_encode_bgr for one frame: the same bytes.  *size_out = bytes written to out_host; SD_ERR_INVALID for an
+ * extent outside 1..16384 or a stream larger than cap (the bound of sd_png_encode_workspace always suffices). */
+sd_status sd_png_encode_zlib_host(const uint8_t* frame_host, int height, int width, uint8_t* out_host, size_t cap, size_t* size_out);
+/* HOST: n finished streams (stream i at streams_host + i * stream_stride, sizes_host[i] bytes) -> the 8-bit RGB PNG files paths[i]:
+ * signature, IHDR, the stream in IDAT chunks of at most 1 MiB, IEND, each with its CRC-32, on `threads` native threads (<= 0: one per host
+ * CPU).  status_out and the return value as sd_png_encode_bgr_files (SD_ERR_NOTFOUND: the file could not be written); a size beyond
+ * stream_stride is SD_ERR_INVALID before anything is written. */
+sd_status sd_png_write_streams_files(const char* const* paths, int n, int height, int width, const uint8_t* streams_host, size_t stream_stride,
+                                     const uint64_t* sizes_host, int threads, int* status_out);
+
 /* HOST helper of the PLY writer that replaces semantic_depth_lib/point_cloud_2_ply.py:70 (numpy.savetxt(fh, rows, "%f %f %f %d %d %d")):
  * n vertex rows "x y z r g b\n" -- coordinates as "%f" % float(v) prints them (fixed, six decimals, correctly rounded; nan / inf /
  * -inf), colours as integers -- into out[0 .. cap).  xyz f64 [n,3], rgb int64 [n,3], HOST memory; threads <= 0: one per core, at most

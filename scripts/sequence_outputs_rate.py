@@ -1,11 +1,15 @@
 """frames/s of distributed.run_sequence_files on 1024 x 2048 PNG frames with the sequence tool's files off and on (one GPU).
 
     python scripts/sequence_outputs_rate.py [--frames 128] [--batch 32] [--precision f16x2] [--level 1] [--threads 0]
+                                            [--png host|device|both] [--repeats 5] [--no-ply]
 
 Setup as bench.py --config 5 (smooth random frames, seeded weights, the monodepth bias calibrated so that the median depth is the
 measuring depth); the frames are written once, untimed.  Each run is timed from the first decode to the last file written
 (SequenceOutputs.close).  Prints one JSON line: both rates, whether the records agree, the bytes written and the host threads of
-the writer and of the decoder.
+the writer and of the decoder.  --png chooses where the result images are compressed (SequenceOutputs(png=)); with "both" the two
+routes are timed interleaved, --repeats times each, and the line also carries each route's rates (median, min, max), the image bytes
+copied device-to-host per frame, the PNG bytes per frame, and whether the device route is faster by the rule of DESIGN section 4
+(median(device) - median(host) > max(host) - min(host)).
 """
 import argparse
 import json
@@ -28,6 +32,9 @@ def main():
     ap.add_argument("--precision", default="f16x2")
     ap.add_argument("--level", type=int, default=1)
     ap.add_argument("--threads", type=int, default=0)
+    ap.add_argument("--png", choices=("host", "device", "both"), default="host", help="where the result images are compressed")
+    ap.add_argument("--repeats", type=int, default=5, help="timed runs per route with --png both")
+    ap.add_argument("--no-ply", dest="ply", action="store_false", help="no road PLYs (images and overlay items only)")
     ap.add_argument("--keep", action="store_true", help="keep the written files (default: removed)")
     args = ap.parse_args()
 
@@ -70,28 +77,65 @@ def main():
 
         threads = args.threads if args.threads > 0 else default_decode_workers()
 
-        def run(with_outputs, frame_paths, tag):
+        def run(with_outputs, frame_paths, tag, png="host"):
             outs = None
             if with_outputs:
                 outs = outputs.SequenceOutputs(os.path.join(work, tag), outputs.sequence_names(frame_paths), depth=prm.depth, level=args.level,
-                                               threads=threads)
+                                               threads=threads, ply=args.ply, png=png)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             rec = run_sequence_files(frame_paths, make_engine_step(eng, lambda i: cam, prm, outputs=outs), batch=B, device="cuda")
             torch.cuda.synchronize()
             return time.perf_counter() - t0, rec
 
-        run(True, paths[:B], "warm_on")                  # (warm-up: tables, pinned staging, allocator)
+        def png_bytes(tag):
+            d = os.path.join(work, tag, outputs.SEQ_IMG_DIR)
+            return sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d) if f.endswith(".png"))
+
+        def stream_bytes(tag):
+            """bytes of the zlib streams inside the device route's files: a file is signature (8), IHDR (25), IEND (12) and one 12-byte
+            IDAT frame per MiB of its stream"""
+            d = os.path.join(work, tag, outputs.SEQ_IMG_DIR)
+            total = 0
+            for f in os.listdir(d):
+                if f.endswith(".png"):
+                    body, k = os.path.getsize(os.path.join(d, f)) - 45, 1
+                    while body - 12 * k > k << 20:
+                        k += 1
+                    total += body - 12 * k
+            return total
+
+        routes = ("host", "device") if args.png == "both" else (args.png,)
+        for r in routes:
+            run(True, paths[:B], "warm_on_" + r, r)      # (warm-up: tables, pinned staging, allocator)
         run(False, paths[:B], "warm_off")
         t_off, rec_off = run(False, paths, "off")
-        t_on, rec_on = run(True, paths, "on")
+        times = {r: [] for r in routes}
+        same = True
+        for k in range(args.repeats if args.png == "both" else 1):
+            for r in routes:
+                tag = "on_" + r
+                shutil.rmtree(os.path.join(work, tag), ignore_errors=True)
+                t, rec_on = run(True, paths, tag, r)
+                times[r].append(t)
+                same = same and bool(torch.equal(rec_on.cpu(), rec_off.cpu()))
         found = int(rec_on.cpu().numpy().view(RW_DTYPE)["found"].sum())
-        out_dir = os.path.join(work, "on")
+        out_dir = os.path.join(work, "on_" + routes[-1])
         nbytes = sum(os.path.getsize(os.path.join(dp, f)) for dp, _, fs in os.walk(out_dir) for f in fs)
-        print(json.dumps(dict(frames=args.frames, batch=B, precision=args.precision, png_level=args.level,
-                              fps_outputs_off=round(args.frames / t_off, 1), fps_outputs_on=round(args.frames / t_on, 1),
-                              records_identical=bool(torch.equal(rec_on.cpu(), rec_off.cpu())), found=found, bytes_written=nbytes,
-                              writer_threads=threads, decode_threads=default_decode_workers(), host_cpus=len(os.sched_getaffinity(0)))))
+        line = dict(frames=args.frames, batch=B, precision=args.precision, png_level=args.level, png=args.png, ply=args.ply,
+                    fps_outputs_off=round(args.frames / t_off, 1), fps_outputs_on=round(args.frames / float(np.median(times[routes[-1]])), 1),
+                    records_identical=same, found=found, bytes_written=nbytes,
+                    writer_threads=threads, decode_threads=default_decode_workers(), host_cpus=len(os.sched_getaffinity(0)))
+        if args.png == "both":
+            fps = {r: sorted(args.frames / t for t in times[r]) for r in routes}
+            line["routes"] = {r: dict(fps=[round(v, 1) for v in fps[r]], median=round(float(np.median(fps[r])), 1), min=round(fps[r][0], 1),
+                                      max=round(fps[r][-1], 1), png_bytes_per_frame=png_bytes("on_" + r) // args.frames) for r in routes}
+            line["routes"]["host"]["d2h_image_bytes_per_frame"] = 2 * H * 2 * W * 3
+            line["routes"]["device"]["d2h_image_bytes_per_frame"] = stream_bytes("on_device") // args.frames + 8      # (+ the u64 size)
+            h_, d_ = line["routes"]["host"], line["routes"]["device"]
+            line["device_faster"] = bool(d_["median"] - h_["median"] > h_["max"] - h_["min"])
+            line["png_size_device_over_host"] = round(d_["png_bytes_per_frame"] / h_["png_bytes_per_frame"], 4)
+        print(json.dumps(line))
         eng.close()
     finally:
         if args.keep:

@@ -95,6 +95,11 @@ SIGNATURES = {
     "sd_jpeg_reconstruct_bgr": (C.c_int, [_H, _P, C.c_size_t, C.POINTER(sd_jpeg_frame_desc), C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P]),
     "sd_png_encode_bgr_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, C.c_int,
                                           C.POINTER(C.c_int)]),
+    "sd_png_encode_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "sd_png_encode_bgr": (C.c_int, [_H, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
+    "sd_png_encode_zlib_host": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sd_png_write_streams_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_int,
+                                             C.POINTER(C.c_int)]),
     "sd_ply_format_rows": (C.c_int64, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int]),
     "sd_post_process": (C.c_int, [_H, _P, C.c_int, _P, _P]),
     "sd_resize_cubic_u8": (C.c_int, [_H, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),

@@ -35,6 +35,7 @@ SOURCES = [
     ("resize.hip", []),
     ("compose.hip", []),
     ("jpeg_gpu.hip", []),
+    ("png_gpu.hip", []),
     ("fuse.hip", ["-ffp-contract=off"]),
     ("pcl.hip", ["-ffp-contract=off"]),
     ("plan.cpp", []),
@@ -43,7 +44,7 @@ SOURCES = [
     ("host_jpeg.cpp", []),
     ("host_ply.cpp", []),
 ]
-HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
+HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
 
 
 def _hipcc() -> str:

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "jpeg_gpu.hpp"
+#include "png_gpu.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -763,6 +764,32 @@ sd_status sd_jpeg_reconstruct_bgr(sd_handle* h, const int16_t* coef_dev, size_t 
         return fail(h, SD_ERR_INVALID, "sd_jpeg_reconstruct_bgr: workspace smaller than sd_jpeg_reconstruct_workspace reports");
     HIPCHK(h, launch_jpeg_reconstruct(coef_dev, frame_stride_bytes / sizeof(int16_t), descs_host, B, bgr_dev, bgr_frame_stride,
                                       static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
+    return SD_OK;
+}
+
+sd_status sd_png_encode_workspace(int B, int height, int width, size_t* workspace_bytes, size_t* stream_stride) {
+    if (B < 1 || B > 65535 || height < 1 || width < 1 || height > sdpng::kMaxExtent || width > sdpng::kMaxExtent) return SD_ERR_INVALID;
+    if (workspace_bytes) *workspace_bytes = png_workspace_bytes(B, height, width);
+    if (stream_stride) *stream_stride = sdpng::stream_bound(height, width);
+    return SD_OK;
+}
+
+sd_status sd_png_encode_bgr(sd_handle* h, const uint8_t* frames_dev, size_t frame_stride, int B, int height, int width, uint8_t* streams_dev,
+                            size_t stream_stride, uint64_t* sizes_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!h || !frames_dev || !streams_dev || !sizes_dev || !workspace_dev || B < 1 || B > 65535)
+        return fail(h, SD_ERR_INVALID, "sd_png_encode_bgr: bad arguments");
+    if (height < 1 || width < 1 || height > sdpng::kMaxExtent || width > sdpng::kMaxExtent)
+        return fail(h, SD_ERR_INVALID, "sd_png_encode_bgr: extents must be 1..16384");
+    // every index the kernels form follows from the extents and these capacities: nothing is launched otherwise
+    if (frame_stride < (size_t)height * width * 3) return fail(h, SD_ERR_INVALID, "sd_png_encode_bgr: frame_stride below height * width * 3");
+    if (stream_stride < sdpng::stream_bound(height, width))
+        return fail(h, SD_ERR_INVALID, "sd_png_encode_bgr: stream_stride below the bound sd_png_encode_workspace reports");
+    if (workspace_bytes < png_workspace_bytes(B, height, width))
+        return fail(h, SD_ERR_INVALID, "sd_png_encode_bgr: workspace smaller than sd_png_encode_workspace reports");
+    if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(sizes_dev) & 7))
+        return fail(h, SD_ERR_INVALID, "sd_png_encode_bgr: workspace_dev must be 16-byte, sizes_dev 8-byte aligned");
+    HIPCHK(h, launch_png_encode(frames_dev, frame_stride, B, height, width, streams_dev, stream_stride, sizes_dev,
+                                static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
     return SD_OK;
 }
 

@@ -356,3 +356,160 @@ extern "C" sd_status sd_png_encode_bgr_files(const char* const* paths, int n, in
     for (auto& th : pool) th.join();
     return failed.load() ? SD_ERR_INVALID : SD_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The device route of the result images (png_gpu.hip makes one zlib stream per frame on the GPU): the CPU statement of that
+// encoder -- the same functions of png_deflate.hpp, walked by one loop -- and the writer that wraps finished streams in PNG
+// chunks on native threads.
+// ---------------------------------------------------------------------------------------------------------------------
+#include "png_deflate.hpp"
+
+namespace {
+
+struct ByteSink {
+    std::vector<uint8_t>& out;
+    uint64_t acc = 0;
+    int nacc = 0;
+    void put(uint32_t v, int n) {
+        acc |= (uint64_t)v << nacc;
+        nacc += n;
+        while (nacc >= 8) { out.push_back((uint8_t)acc); acc >>= 8; nacc -= 8; }
+    }
+    void align() { if (nacc > 0) { out.push_back((uint8_t)acc); acc = 0; nacc = 0; } }
+};
+
+// f(position, token, byte value) for every token of the chunk d[0..len), run by run
+template <class F>
+void chunk_tokens(const uint8_t* d, uint32_t len, F&& f) {
+    for (uint32_t s = 0; s < len;) {
+        uint32_t e = s + 1;
+        while (e < len && d[e] == d[s]) ++e;
+        for (uint32_t p = 0; p < e - s; ++p) {
+            const int tok = sdpng::run_token(e - s, p);
+            if (tok) f(s + p, tok, d[s]);
+        }
+        s = e;
+    }
+}
+
+void encode_zlib(const uint8_t* frame, int h, int w, std::vector<uint8_t>& out) {
+    using namespace sdpng;
+    const size_t total = filtered_len(h, w), rowlen = 1 + 3 * (size_t)w;
+    out.clear();
+    out.reserve(stream_bound(h, w));
+    out.push_back(0x78);
+    out.push_back(0x01);
+    std::vector<uint8_t> d(kChunk);
+    uint32_t adler_a = 1, adler_b = 0;
+    HuffScratch sc;
+    ChunkCodes cc;
+    for (size_t g0 = 0; g0 < total; g0 += kChunk) {
+        const uint32_t len = (uint32_t)std::min<size_t>(kChunk, total - g0);
+        uint32_t y = (uint32_t)(g0 / rowlen), k = (uint32_t)(g0 - (size_t)y * rowlen);
+        uint64_t sa = 0, sb = 0;
+        for (uint32_t i = 0; i < len; ++i) {
+            d[i] = filtered_byte(frame, w, y, k);
+            sa += d[i];
+            sb += (uint64_t)(len - i) * d[i];
+            if (++k == rowlen) { k = 0; ++y; }
+        }
+        adler_append(adler_a, adler_b, len, (uint32_t)(sa % kAdlerMod), (uint32_t)(sb % kAdlerMod));
+        uint32_t hist[kLitSyms] = {0};
+        chunk_tokens(d.data(), len, [&](uint32_t, int tok, uint8_t v) {
+            int eb, ev;
+            hist[tok == 1 ? (int)v : length_symbol(tok, &eb, &ev)]++;
+        });
+        hist[kEob] = 1;
+        const int n = sort_keys(hist, kLitSyms, sc.key);
+        build_chunk_codes(hist, n, sc, cc);
+        const size_t before = out.size();
+        if (chunk_is_dynamic(cc, len)) {
+            ByteSink sink{out};
+            write_block_header(sink, cc);
+            chunk_tokens(d.data(), len, [&](uint32_t, int tok, uint8_t v) {
+                int nb;
+                const uint32_t bits = token_bits(cc, tok, v, &nb);
+                sink.put(bits, nb);
+            });
+            sink.put(cc.llcode[kEob], cc.ll[kEob]);
+            sink.put(0, 3);                              // the empty stored block: BFINAL 0, BTYPE 00, padding, LEN 0, NLEN FFFF
+            sink.align();
+        } else {
+            const uint8_t head[5] = {0, (uint8_t)len, (uint8_t)(len >> 8), (uint8_t)~len, (uint8_t)(~len >> 8)};
+            out.insert(out.end(), head, head + 5);
+            out.insert(out.end(), d.begin(), d.begin() + len);
+            out.push_back(0);
+        }
+        const uint8_t sync[4] = {0, 0, 0xFF, 0xFF};
+        out.insert(out.end(), sync, sync + 4);
+        if (out.size() - before != chunk_coded_bytes(cc, len)) throw 0;       // (the size the device lays the stream out with)
+    }
+    const uint32_t adler = (adler_b << 16) | adler_a;
+    const uint8_t tail[9] = {1, 0, 0, 0xFF, 0xFF, (uint8_t)(adler >> 24), (uint8_t)(adler >> 16), (uint8_t)(adler >> 8), (uint8_t)adler};
+    out.insert(out.end(), tail, tail + 9);
+}
+
+sd_status png_stream_file(const char* path, int h, int w, const uint8_t* stream, size_t size) {
+    FILE* fp = std::fopen(path, "wb");
+    if (!fp) return SD_ERR_NOTFOUND;
+    bool ok = std::fwrite(kPngSig, 1, 8, fp) == 8;
+    uint8_t ihdr[13];
+    put_be32(ihdr, (uint32_t)w);
+    put_be32(ihdr + 4, (uint32_t)h);
+    ihdr[8] = 8; ihdr[9] = 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
+    ok = ok && write_chunk(fp, "IHDR", ihdr, 13);
+    const size_t piece = (size_t)1 << 20;                                      // one IDAT per MiB of the stream
+    for (size_t p = 0; ok && p < size; p += piece) ok = write_chunk(fp, "IDAT", stream + p, (uint32_t)std::min(piece, size - p));
+    ok = ok && write_chunk(fp, "IEND", nullptr, 0);
+    ok = (std::fclose(fp) == 0) && ok;
+    return ok ? SD_OK : SD_ERR_NOTFOUND;
+}
+
+}  // namespace
+
+extern "C" sd_status sd_png_encode_zlib_host(const uint8_t* frame_host, int height, int width, uint8_t* out_host, size_t cap, size_t* size_out) {
+    if (!frame_host || !out_host || !size_out || height < 1 || width < 1 || height > sdpng::kMaxExtent || width > sdpng::kMaxExtent)
+        return SD_ERR_INVALID;
+    try {
+        std::vector<uint8_t> out;
+        encode_zlib(frame_host, height, width, out);
+        if (out.size() > cap) return SD_ERR_INVALID;
+        std::memcpy(out_host, out.data(), out.size());
+        *size_out = out.size();
+        return SD_OK;
+    } catch (...) {
+        return SD_ERR_INVALID;
+    }
+}
+
+extern "C" sd_status sd_png_write_streams_files(const char* const* paths, int n, int height, int width, const uint8_t* streams_host,
+                                                size_t stream_stride, const uint64_t* sizes_host, int threads, int* status_out) {
+    if (!paths || n < 0 || height <= 0 || width <= 0 || (n > 0 && (!streams_host || !sizes_host))) return SD_ERR_INVALID;
+    for (int i = 0; i < n; ++i)
+        if (sizes_host[i] > stream_stride) return SD_ERR_INVALID;
+    if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
+    threads = threads < 1 ? 1 : (threads > n ? (n > 0 ? n : 1) : threads);
+    std::atomic<int> next(0), failed(0);
+    auto work = [&]() {
+        for (;;) {
+            const int i = next.fetch_add(1);
+            if (i >= n) break;
+            sd_status st = SD_ERR_NOTFOUND;
+            try {
+                if (paths[i]) st = png_stream_file(paths[i], height, width, streams_host + (size_t)i * stream_stride, (size_t)sizes_host[i]);
+            } catch (...) {
+                st = SD_ERR_INVALID;
+            }
+            if (status_out) status_out[i] = st;
+            if (st != SD_OK) failed.fetch_add(1);
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        for (int t = 1; t < threads; ++t) pool.emplace_back(work);
+    } catch (...) {
+    }
+    work();
+    for (auto& th : pool) th.join();
+    return failed.load() ? SD_ERR_INVALID : SD_OK;
+}

@@ -373,6 +373,24 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_compose_result_frames")
         return out
 
+    def encode_png(self, images: torch.Tensor):
+        """the device half of the result-image writer (sd_png_encode_bgr): u8 [B,h,w,3] BGR device ``images`` -> (``streams`` u8 [B,stride],
+        ``sizes`` i64 [B]) device tensors: frame b's complete zlib stream (Paeth rows, run matches, one dynamic-Huffman block per 32 KiB chunk;
+        include/semdepth.h) is ``streams[b, :sizes[b]]``, the bytes behind it are not written.  outputs.write_png_streams wraps the streams in
+        PNG chunks.  Three launches on the current stream, no synchronisation; the workspace is a torch allocation."""
+        assert images.dtype == torch.uint8 and images.is_cuda and images.is_contiguous() and images.dim() == 4 and images.shape[3] == 3
+        B, h, w = (int(v) for v in images.shape[:3])
+        need, stride = C.c_size_t(), C.c_size_t()
+        st = self.lib.sd_png_encode_workspace(B, h, w, C.byref(need), C.byref(stride))
+        L.check(self.lib, None, st, "sd_png_encode_workspace")
+        streams = torch.empty((B, stride.value), dtype=torch.uint8, device=self.device)
+        sizes = torch.empty((B,), dtype=torch.int64, device=self.device)
+        ws = torch.empty((need.value,), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_png_encode_bgr(self.h, _ptr(images), h * w * 3, B, h, w, _ptr(streams), stride.value, _ptr(sizes), _ptr(ws), need.value,
+                                        self._stream())
+        L.check(self.lib, self.h, st, "sd_png_encode_bgr")
+        return streams, sizes
+
     def post_process(self, disp_raw: torch.Tensor):
         B = disp_raw.shape[0]
         assert disp_raw.dtype == torch.float32 and tuple(disp_raw.shape[1:]) == (2, self.H, self.W) and disp_raw.is_contiguous()

@@ -360,6 +360,30 @@ def write_png_batch(paths, frames_bgr, level: int = 1, threads: int = 0) -> list
     return list(paths)
 
 
+def write_png_streams(paths, streams, sizes, h: int, w: int, threads: int = 0) -> list:
+    """the files of the device route: ``streams`` u8 [n,stride] and ``sizes`` [n] (host arrays: Engine.encode_png's tensors, copied) are
+    finished zlib streams of h x w RGB frames; ONE native call (sd_png_write_streams_files, ``threads`` C++ threads, 0 = one per CPU) wraps
+    each in signature, IHDR, IDAT chunks and IEND and writes it to paths[i].  Returns the paths."""
+    import ctypes as C
+
+    from . import _lib as L
+    a = np.ascontiguousarray(streams, dtype=np.uint8)
+    sz = np.ascontiguousarray(sizes).astype(np.uint64)
+    if a.ndim != 2 or a.shape[0] != len(paths) or sz.shape != (len(paths),):
+        raise ValueError(f"streams must be u8 [n,stride] and sizes [n] with n = len(paths), got {a.shape}, {sz.shape} for {len(paths)} paths")
+    n = len(paths)
+    if n == 0:
+        return []
+    arr = (C.c_char_p * n)(*[os.fsencode(p) for p in paths])
+    status = (C.c_int * n)()
+    st = L.load().sd_png_write_streams_files(arr, n, int(h), int(w), a.ctypes.data_as(C.c_void_p), a.shape[1], sz.ctypes.data_as(C.c_void_p),
+                                             int(threads), status)
+    if st != L.SD_OK:
+        bad = [(paths[i], status[i]) for i in range(n) if status[i] != L.SD_OK]
+        raise OSError(f"write_png_streams: {len(bad) or n} image(s) could not be written (status {st}): {bad[:3]}")
+    return list(paths)
+
+
 def rw_ply_bytes(road3D, road_colors, left_pt_rw=None, right_pt_rw=None) -> bytes:
     """the bytes of ``<name>_rw.ply`` (seq:357-361): PointCloud2Ply(road3D, road_colors, ...) plus, when the line was found (both end
     points given, [1,3] each), create_3Dline_from_3Dpoints(left, right, [250,0,0]), after prepare_and_save_point_cloud's minimum-z filter.
@@ -379,7 +403,8 @@ class SequenceOutputs:
     """what the sequence tool writes for every frame (seq:303-361), fed batch by batch by the step of ``make_engine_step(..., outputs=)``:
 
         <directory>/result_sequence_imgs/<name>.png           the overlay at the original frame size, 25 % banner when the line was found
-                                                              (``images``; Engine.compose_result_frames on the GPU, sd_png_encode_bgr_files)
+                                                              (``images``; Engine.compose_result_frames on the GPU, sd_png_encode_bgr_files
+                                                              or, with png="device", Engine.encode_png and sd_png_write_streams_files)
         <directory>/result_sequence_imgs/<name>_overlay.json  the banner and the cv2.putText items of overlay_items_sequence (``items``;
                                                               glyphs are not rasterised, module docstring)
         <directory>/result_sequence_ply/<name>_rw.ply         the denoised road cloud + the red road-width line (``ply``; rw_ply_bytes)
@@ -388,15 +413,19 @@ class SequenceOutputs:
     ``names``: output names of the WHOLE sorted frame list (sequence_names), indexed by global frame index.  submit() takes the device
     tensors of one batch, copies them into pinned staging on a side stream behind an event of the current stream, and writes them on
     worker threads -- at most two batches in flight -- with the per-pixel and per-point work in native code (no interpreter lock).
-    ``threads``: native encoder threads per batch and PLY writer threads (0: frame_io.default_decode_workers())."""
+    ``threads``: native encoder threads per batch and PLY writer threads (0: frame_io.default_decode_workers()).
+    ``png``: "host" (default) copies the raw images to the host and deflates them there (sd_png_encode_bgr_files at ``level``); "device"
+    takes each frame's finished zlib stream from the GPU (Engine.encode_png, submit(png_streams=)): the sizes are copied first, then each
+    stream's exact byte count, and the host only writes the PNG chunks (sd_png_write_streams_files).  Same names, manifest and pixels."""
 
     def __init__(self, directory: str, names, depth: float = 10.0, images: bool = True, ply: bool = True, items: bool = True, level: int = 1,
-                 threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64):
+                 threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, png: str = "host"):
         from concurrent.futures import ThreadPoolExecutor
 
         from .frame_io import default_decode_workers
         if not 0 <= level <= 9:
             raise ValueError("PNG compression level must be 0..9")
+        self.set_png(png)
         self.directory, self.names, self.depth = directory, list(names), float(depth)
         self.images, self.ply, self.items, self.level = bool(images), bool(ply), bool(items), int(level)
         self.road_color, self.fence_color, self.alpha = tuple(road_color), tuple(fence_color), int(alpha)
@@ -415,14 +444,23 @@ class SequenceOutputs:
         self.recomputed: list[int] = []                               # global indices of the frames recomputed on bf16x3 (on_range='recompute')
 
     # ---------------------------------------------------------------- driver interface
+    def set_png(self, png: str):
+        """where the result images are compressed: "host" or "device" (before the first batch)"""
+        if png not in ("host", "device"):
+            raise ValueError(f"png must be 'host' or 'device', got {png!r}")
+        if getattr(self, "_k", 0):
+            raise RuntimeError("SequenceOutputs.set_png after the first batch")
+        self.png = png
+
     def begin(self, rank: int, world: int, lo: int, hi: int):
         """the shard [lo, hi) this rank writes (run_sequence_files calls it before the first batch)"""
         self.rank, self.world, self.shard = int(rank), int(world), (int(lo), int(hi))
 
-    def submit(self, lo: int, records, size: tuple, images=None, final=None):
+    def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None):
         """one batch: ``records`` u8 [n,104] (sd_rw_result), ``size`` = (h, w) of the original frames, ``images`` u8 [n,h,w,3] (the composed
         result images) or None, ``final`` = dict(xyz f32 [n,cap,3], rgb u8 [n,cap,3], n i32 [n]) (process_batch(want_final=True)'s
-        road_final) or None.  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
+        road_final) or None, ``png_streams`` = (streams u8 [n,stride], sizes i64 [n]) of Engine.encode_png in place of ``images`` on the
+        device route.  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
         tensors of every step)."""
         import torch
         if self.manifest is not None:
@@ -430,8 +468,8 @@ class SequenceOutputs:
         n = int(records.shape[0])
         if lo < 0 or lo + n > len(self.names):
             raise ValueError(f"frames {lo}..{lo + n - 1} are beyond the {len(self.names)} names")
-        if self.images and images is None or self.ply and final is None:
-            raise ValueError("SequenceOutputs: this batch lacks the images / final road clouds the outputs ask for")
+        if self.images and (png_streams if self.png == "device" else images) is None or self.ply and final is None:
+            raise ValueError("SequenceOutputs: this batch lacks the images (png='device': the streams) / final road clouds the outputs ask for")
         while len(self._jobs) >= 2:                                    # at most two batches in flight
             self._files.extend(self._jobs.pop(0).result())
         slot = self._k & 1
@@ -442,7 +480,11 @@ class SequenceOutputs:
                 self._streams = [torch.cuda.Stream(records.device), torch.cuda.Stream(records.device)]
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream(records.device))
-        self._jobs.append(self._batches.submit(self._write_batch, slot, lo, records, tuple(size), images, final, ev))
+        if self.png == "device":
+            images = None
+        else:
+            png_streams = None
+        self._jobs.append(self._batches.submit(self._write_batch, slot, lo, records, tuple(size), images, final, ev, png_streams))
 
     def mark_recomputed(self, frames):
         """global frame indices whose outputs came from the bf16x3 recompute (make_engine_step(on_range='recompute')): the manifest lists
@@ -483,18 +525,23 @@ class SequenceOutputs:
             buf = self._staging[slot][key] = torch.empty(max(numel, 1), dtype=dtype, pin_memory=pin)
         return buf[:numel].view(*shape)
 
-    def _to_host(self, slot, lo, records, images, final, ev):
-        """numpy views of the batch (device tensors: copied into pinned staging on this slot's side stream behind ``ev``)"""
+    def _to_host(self, slot, lo, records, images, final, ev, png_streams=None):
+        """numpy views of the batch (device tensors: copied into pinned staging on this slot's side stream behind ``ev``): records, images,
+        clouds and, from ``png_streams``, (streams [n,stride], sizes [n]) of which only streams[i, :sizes[i]] was copied"""
         import torch
+
+        def host(t):
+            return np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t)
+
         if ev is None:
             rec = records.numpy() if isinstance(records, torch.Tensor) else np.asarray(records)
             img = None if images is None else (images.numpy() if isinstance(images, torch.Tensor) else np.asarray(images))
             clouds = None
             if final is not None:
-                cnt = np.asarray(final["n"].cpu() if isinstance(final["n"], torch.Tensor) else final["n"])
-                xyz, rgb = (np.asarray(final[k].cpu() if isinstance(final[k], torch.Tensor) else final[k]) for k in ("xyz", "rgb"))
+                cnt = host(final["n"])
+                xyz, rgb = (host(final[k]) for k in ("xyz", "rgb"))
                 clouds = [(xyz[i, :cnt[i]], rgb[i, :cnt[i]]) for i in range(len(cnt))]
-            return rec, img, clouds
+            return rec, img, clouds, None if png_streams is None else (host(png_streams[0]), host(png_streams[1]))
         s = self._streams[slot]
         with torch.cuda.stream(s):
             s.wait_event(ev)
@@ -504,12 +551,22 @@ class SequenceOutputs:
             if images is not None:
                 img = self._pinned(slot, "img", tuple(images.shape), torch.uint8, True)
                 img.copy_(images, non_blocking=True)
-            cnt = None
+            cnt = psz = None
             if final is not None:
                 cnt = self._pinned(slot, "n", tuple(final["n"].shape), torch.int32, True)
                 cnt.copy_(final["n"], non_blocking=True)
+            if png_streams is not None:                                # phase one: the sizes; phase two: each stream's exact bytes
+                psz = self._pinned(slot, "png_sizes", tuple(png_streams[1].shape), torch.int64, True)
+                psz.copy_(png_streams[1], non_blocking=True)
             s.synchronize()
-            clouds = None
+            clouds = png = None
+            if png_streams is not None:
+                streams = png_streams[0]
+                pbuf = self._pinned(slot, "png", tuple(streams.shape), torch.uint8, True)
+                pn = psz.numpy()
+                for i in range(len(pn)):
+                    pbuf[i, :int(pn[i])].copy_(streams[i, :int(pn[i])], non_blocking=True)
+                png = (pbuf.numpy(), pn)
             if final is not None:
                 cn = cnt.numpy().astype(np.int64)
                 off = np.concatenate([[0], np.cumsum(cn)])
@@ -519,14 +576,15 @@ class SequenceOutputs:
                     if cn[i]:
                         xyz[off[i]:off[i + 1]].copy_(final["xyz"][i, :cn[i]], non_blocking=True)
                         rgb[off[i]:off[i + 1]].copy_(final["rgb"][i, :cn[i]], non_blocking=True)
-                s.synchronize()
                 xn, rn = xyz.numpy(), rgb.numpy()
                 clouds = [(xn[off[i]:off[i + 1]], rn[off[i]:off[i + 1]]) for i in range(len(cn))]
-        return rec.numpy(), None if img is None else img.numpy(), clouds
+            if final is not None or png_streams is not None:
+                s.synchronize()
+        return rec.numpy(), None if img is None else img.numpy(), clouds, png
 
-    def _write_batch(self, slot, lo, records, size, images, final, ev):
+    def _write_batch(self, slot, lo, records, size, images, final, ev, png_streams=None):
         from .engine import RW_DTYPE
-        rec_u8, img, clouds = self._to_host(slot, lo, records, images, final, ev)
+        rec_u8, img, clouds, png = self._to_host(slot, lo, records, images, final, ev, png_streams)
         recs = np.ascontiguousarray(rec_u8).view(RW_DTYPE).reshape(-1)
         n = len(recs)
         names = self.names[lo:lo + n]
@@ -560,7 +618,9 @@ class SequenceOutputs:
                 futs.append(self._writers.submit(write_ply, i))
             if self.items:
                 futs.append(self._writers.submit(write_items, i))
-        if self.images:
+        if self.images and self.png == "device":
+            files.extend(write_png_streams([os.path.join(self.img_dir, "{}.png".format(nm)) for nm in names], png[0], png[1], h, w, self.threads))
+        elif self.images:
             assert img.shape == (n, h, w, 3), (img.shape, (n, h, w))
             files.extend(write_png_batch([os.path.join(self.img_dir, "{}.png".format(nm)) for nm in names], img, self.level, self.threads))
         files.extend(f.result() for f in futs)
