@@ -133,6 +133,11 @@ const char* sd_last_error(const sd_handle* h);
 /* ---------------------------------------------------------------- memory + weights
  * replaces SegmentFrame.restore_model / DepthFrame.restore_model (semantic_depth.py:498-541, :627-653) */
 sd_status sd_query_memory(const sd_handle* h, size_t* fcn_weight_bytes, size_t* mono_weight_bytes, size_t* workspace_bytes);
+/* The arenas may hold anything when they are bound (fresh hipMalloc memory, the remains of another handle, NaN patterns): sd_bind_memory clears the
+ * few regions the library reads before it writes them (a zero page, the clamp counters) and uploads the gather tables; every other byte a kernel reads
+ * -- padded channels, rows of a partial tile, images beyond B, the padding of a weight slot, partial sums, halos -- was written by sd_load_weight or by
+ * a kernel of the same call.  Results therefore depend neither on the arenas' contents at bind time nor on the calls made before
+ * (tests/test_gpu_state_independence.py binds 0xFF- and 0x7B-filled arenas). */
 sd_status sd_bind_memory(sd_handle* h, void* fcn_weights_dev, void* mono_weights_dev, void* workspace_dev);
 int sd_weight_count(const sd_handle* h, sd_net net);
 /* name_out: >= 64 bytes; shape_out: 4 x int64 in TensorFlow layout (conv HWIO, transposed conv HWOI, bias [C]) */

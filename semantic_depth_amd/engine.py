@@ -86,7 +86,8 @@ FP16_PLANE_ENGINES = ("f16x2", "f16x2x2", "mixed", "plan")
 
 class Engine:
     def __init__(self, H: int, W: int, max_batch: int = 1, encoder: str = "resnet50", device: int = 0, precision: str = "f32",
-                 plan: tuple[str, str] | None = None, range_check: bool = True, on_range: str = "raise", small_batch: bool | int = False):
+                 plan: tuple[str, str] | None = None, range_check: bool = True, on_range: str = "raise", small_batch: bool | int = False,
+                 arena_fill: int = 0):
         """precision: 'f32' (exact f32 MFMA), 'bf16x3' (fp32-grade on the bf16 MFMA: every f32 operand as three bf16 planes that sum to it
         exactly, 6 MFMA products), 'f16x2' (fp32-grade on 3 fp16 MFMA products: activations as fp16 hi + 2^11-scaled lo planes, weights as fp16 hi + lo of
         w * 2^k, k per layer), 'bf16x2' (3 bf16 MFMA products, ~1e-5), 'mixed' (monodepth on 2 fp16 products), 'plan' (per-layer
@@ -105,8 +106,12 @@ class Engine:
         handle's; on a handle where no layer qualifies nothing changes.  The 'bf16x3' companion of on_range='recompute' is not split.
         small_batch=2 (level 2; True means 1): level 1 plus the under-filled 3x3 direct conv layers (conv4_x / conv5_x of FCN-8s, the deep encoder and iconv layers
         of monodepth; sd_small_batch_split_direct is the rule) split along their input-channel chunks, S contiguous chunk ranges per tile plus a reduce launch
-        that applies the layer's epilogue, fused 2x2 pool included.  ``small_batch_level`` holds the level, ``small_batch`` stays its truth value."""
+        that applies the layer's epilogue, fused 2x2 pool included.  ``small_batch_level`` holds the level, ``small_batch`` stays its truth value.
+        arena_fill: the byte (0..255) the three arenas hold when they are bound; 0 is the zero fill this class has always used.  Results must not depend on
+        it (sd_bind_memory: "the arenas may hold anything"): tests/test_gpu_state_independence.py binds NaN- and huge-valued arenas through it."""
         RC.check_mode(on_range)
+        if not 0 <= int(arena_fill) <= 255:
+            raise ValueError("arena_fill is a byte, 0..255")
         if int(small_batch) not in (0, 1, 2):
             raise ValueError("small_batch is False / True or the level 0, 1 or 2")
         if small_batch and precision not in ("f16x2", "f16x2x2"):
@@ -136,10 +141,10 @@ class Engine:
         fw, mw, ws = C.c_size_t(), C.c_size_t(), C.c_size_t()
         L.check(self.lib, h, self.lib.sd_query_memory(h, C.byref(fw), C.byref(mw), C.byref(ws)), "sd_query_memory")
         self.bytes = dict(fcn_weights=fw.value, mono_weights=mw.value, workspace=ws.value)
-        # arenas: torch owns the memory; zero-filled so that never-written padding is finite
-        self._wf = torch.zeros(fw.value, dtype=torch.uint8, device=self.device)
-        self._wm = torch.zeros(mw.value, dtype=torch.uint8, device=self.device)
-        self._ws = torch.zeros(ws.value, dtype=torch.uint8, device=self.device)
+        # arenas: torch owns the memory; every byte holds arena_fill when they are bound (0: never-written padding is finite)
+        self._wf = torch.full((fw.value,), int(arena_fill), dtype=torch.uint8, device=self.device)
+        self._wm = torch.full((mw.value,), int(arena_fill), dtype=torch.uint8, device=self.device)
+        self._ws = torch.full((ws.value,), int(arena_fill), dtype=torch.uint8, device=self.device)
         L.check(self.lib, h, self.lib.sd_bind_memory(h, _ptr(self._wf), _ptr(self._wm), _ptr(self._ws)), "sd_bind_memory")
         self.cap = H * W
         self.pass_frames = int(self.lib.sd_pass_frames(h))        # frames per network pass, as the handle latched it at sd_create
