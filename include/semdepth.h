@@ -305,6 +305,42 @@ sd_status sd_png_write_streams_files(const char* const* paths, int n, int height
  * 16.  Returns the number of bytes written, or SD_ERR_INVALID (bad argument, or cap too small: cap / n bytes must hold any row). */
 int64_t sd_ply_format_rows(const double* xyz_host, const int64_t* rgb_host, int64_t n, char* out_host, int64_t cap, int threads);
 
+/* ---- road PLYs, device route: the GPU writes the text of every frame's <name>_rw.ply, the host only writes the bytes to the files ----
+ * The text of one frame is outputs.rw_ply_bytes(xyz as float64, rgb, left, right) byte for byte:
+ *   rows      the n cloud points in order, then -- when record.found != 0 -- the 1001 points of the road-width line, in float64 without
+ *             contraction: L = (double)left_pt, R = (double)right_pt, L.y += 0.01, R.y += 0.01, v = R - L; line row 0 is L, line row 1 + i
+ *             is L + (i * 0.001) * v for i = 0..999 (a product, then a sum); colour 250 0 0.
+ *   filter    zmin = the minimum z of all rows; a row is kept iff z > zmin (every row at the minimum goes; no row: no vertex).
+ *   a row     "%f %f %f %d %d %d\n": "%f" of the double, six decimals, correctly rounded (half-even on the exact binary value), the sign
+ *             printed whenever the sign bit is set; at most SD_PLY_ROW_CAP bytes.
+ *   header    PointCloud2Ply.ply_header with the count of kept rows (four-space indents, four trailing spaces), at most SD_PLY_HEADER_CAP bytes.
+ * The digits are semantic_depth_amd/csrc/ply_format.hpp (integer arithmetic only), which host and device both run.
+ * flags      0: the frame's text was produced.  1: not formatted -- a cloud or line coordinate or an end point of a found record is not
+ *            finite or has |v| >= 2^31, or n_dev[b] is outside 0..cap; the caller writes such a frame through the host route
+ *            (sd_ply_format_rows).  2: the text would pass text_capacity.  A flagged frame has size 0. */
+#define SD_PLY_ROW_CAP 69
+#define SD_PLY_HEADER_CAP 209
+#define SD_PLY_LINE_ROWS 1001
+/* the device workspace sd_ply_format_rw needs for B frames of clouds of `cap` points, and the text capacity that holds any content:
+ * B * (SD_PLY_HEADER_CAP + (cap + SD_PLY_LINE_ROWS) * SD_PLY_ROW_CAP).  SD_ERR_INVALID for B < 1, B > 65535 or cap < 0. */
+sd_status sd_ply_format_workspace(int B, int cap, size_t* workspace_bytes, size_t* text_bound);
+/* DEVICE: xyz f32 [B,cap,3], rgb u8 [B,cap,3], n i32 [B] (sd_road_width's final clouds) and records [B] -> the files PACKED back to back:
+ * frame b's file is text_dev[offsets_dev[b] .. offsets_dev[b+1]), offsets_dev[0] = 0, so that offsets_dev[B] bytes cross to the host in one
+ * copy.  text_capacity may be below the bound: a frame whose text would pass it gets flag 2 and size 0, and the frames behind it still
+ * pack correctly.  Bytes at and behind offsets_dev[B] are never written.  The result does not depend on the workspace's contents or on the
+ * order in which workgroups arrive (no floating-point atomics).  Five launches (minimum z and range test per 256-row block; per frame;
+ * the kept rows' exact length per block; one workgroup that lays out blocks, frames, flags and headers; the rows) enqueued on `stream`,
+ * no synchronisation; the handle need not be bound.  SD_ERR_INVALID, nothing launched: B < 1, cap < 0, a null pointer, workspace_bytes
+ * below sd_ply_format_workspace, a workspace that is not 16-byte aligned, offsets_dev not 8-byte aligned. */
+sd_status sd_ply_format_rw(sd_handle* h, const float* xyz_dev, const uint8_t* rgb_dev, const int32_t* n_dev, int B, int cap,
+                           const sd_rw_result* records_dev, uint8_t* text_dev, size_t text_capacity, uint64_t* offsets_dev, int32_t* flags_dev,
+                           void* workspace_dev, size_t workspace_bytes, void* stream);
+/* HOST: the CPU statement of sd_ply_format_rw for one frame (xyz f32 [n,3], rgb u8 [n,3], one record): the same bytes into out_host[0 .. cap),
+ * *size_out = their count, *flag_out = 0; or *flag_out = 1 and *size_out = 0 under the rule above.  SD_ERR_INVALID: n < 0, a null pointer,
+ * or a text longer than cap (SD_PLY_HEADER_CAP + (n + SD_PLY_LINE_ROWS) * SD_PLY_ROW_CAP always suffices). */
+sd_status sd_ply_format_rw_host(const float* xyz_host, const uint8_t* rgb_host, int n, const sd_rw_result* record, uint8_t* out_host, size_t cap,
+                                size_t* size_out, int32_t* flag_out);
+
 /* DepthFrame.post_processing alone, semantic_depth.py:656-664: disp_raw f32 [B,2,H,W] -> disp_pp f32 [B,H,W] */
 sd_status sd_post_process(sd_handle* h, const float* disp_raw, int B, float* disp_pp, void* stream);
 

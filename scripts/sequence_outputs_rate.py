@@ -1,7 +1,7 @@
 """frames/s of distributed.run_sequence_files on 1024 x 2048 PNG frames with the sequence tool's files off and on (one GPU).
 
     python scripts/sequence_outputs_rate.py [--frames 128] [--batch 32] [--precision f16x2] [--level 1] [--threads 0]
-                                            [--png host|device|both] [--repeats 5] [--no-ply]
+                                            [--png host|device|both] [--ply host|device|both] [--repeats 5] [--no-ply]
 
 Setup as bench.py --config 5 (smooth random frames, seeded weights, the monodepth bias calibrated so that the median depth is the
 measuring depth); the frames are written once, untimed.  Each run is timed from the first decode to the last file written
@@ -9,7 +9,9 @@ measuring depth); the frames are written once, untimed.  Each run is timed from 
 the writer and of the decoder.  --png chooses where the result images are compressed (SequenceOutputs(png=)); with "both" the two
 routes are timed interleaved, --repeats times each, and the line also carries each route's rates (median, min, max), the image bytes
 copied device-to-host per frame, the PNG bytes per frame, and whether the device route is faster by the rule of DESIGN section 4
-(median(device) - median(host) > max(host) - min(host)).
+(median(device) - median(host) > max(host) - min(host)).  --ply chooses where the road PLYs are formatted (SequenceOutputs(ply=)) in the
+same way: with "both" (and one --png route) the two PLY routes are timed interleaved, and the line carries each route's rates, the PLY
+bytes per frame (on the device route: the text copied device-to-host) and the raw cloud bytes per frame (15 B per point, the host route's copy).
 """
 import argparse
 import json
@@ -33,10 +35,16 @@ def main():
     ap.add_argument("--level", type=int, default=1)
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--png", choices=("host", "device", "both"), default="host", help="where the result images are compressed")
-    ap.add_argument("--repeats", type=int, default=5, help="timed runs per route with --png both")
+    ap.add_argument("--ply", dest="ply_route", choices=("host", "device", "both"), default="host", help="where the road PLYs are formatted")
+    ap.add_argument("--repeats", type=int, default=5, help="timed runs per route with --png both / --ply both")
     ap.add_argument("--no-ply", dest="ply", action="store_false", help="no road PLYs (images and overlay items only)")
     ap.add_argument("--keep", action="store_true", help="keep the written files (default: removed)")
     args = ap.parse_args()
+    if args.png == "both" and args.ply_route == "both":
+        ap.error("--png both and --ply both: vary one route at a time")
+    if args.ply_route != "host" and not args.ply:
+        ap.error("--ply device / both with --no-ply")
+    vary_ply = args.ply_route == "both"
 
     import torch
 
@@ -77,11 +85,12 @@ def main():
 
         threads = args.threads if args.threads > 0 else default_decode_workers()
 
-        def run(with_outputs, frame_paths, tag, png="host"):
+        def run(with_outputs, frame_paths, tag, route="host"):
             outs = None
             if with_outputs:
+                png, ply = (args.png, route) if vary_ply else (route, args.ply_route)
                 outs = outputs.SequenceOutputs(os.path.join(work, tag), outputs.sequence_names(frame_paths), depth=prm.depth, level=args.level,
-                                               threads=threads, ply=args.ply, png=png)
+                                               threads=threads, ply=ply if args.ply else False, png=png)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             rec = run_sequence_files(frame_paths, make_engine_step(eng, lambda i: cam, prm, outputs=outs), batch=B, device="cuda")
@@ -105,14 +114,19 @@ def main():
                     total += body - 12 * k
             return total
 
-        routes = ("host", "device") if args.png == "both" else (args.png,)
+        def ply_bytes(tag):
+            d = os.path.join(work, tag, outputs.SEQ_PLY_DIR)
+            return sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d) if f.endswith(".ply"))
+
+        both = args.png == "both" or vary_ply
+        routes = ("host", "device") if both else (args.png,)
         for r in routes:
             run(True, paths[:B], "warm_on_" + r, r)      # (warm-up: tables, pinned staging, allocator)
         run(False, paths[:B], "warm_off")
         t_off, rec_off = run(False, paths, "off")
         times = {r: [] for r in routes}
         same = True
-        for k in range(args.repeats if args.png == "both" else 1):
+        for k in range(args.repeats if both else 1):
             for r in routes:
                 tag = "on_" + r
                 shutil.rmtree(os.path.join(work, tag), ignore_errors=True)
@@ -122,7 +136,7 @@ def main():
         found = int(rec_on.cpu().numpy().view(RW_DTYPE)["found"].sum())
         out_dir = os.path.join(work, "on_" + routes[-1])
         nbytes = sum(os.path.getsize(os.path.join(dp, f)) for dp, _, fs in os.walk(out_dir) for f in fs)
-        line = dict(frames=args.frames, batch=B, precision=args.precision, png_level=args.level, png=args.png, ply=args.ply,
+        line = dict(frames=args.frames, batch=B, precision=args.precision, png_level=args.level, png=args.png, ply=args.ply, ply_route=args.ply_route,
                     fps_outputs_off=round(args.frames / t_off, 1), fps_outputs_on=round(args.frames / float(np.median(times[routes[-1]])), 1),
                     records_identical=same, found=found, bytes_written=nbytes,
                     writer_threads=threads, decode_threads=default_decode_workers(), host_cpus=len(os.sched_getaffinity(0)))
@@ -135,6 +149,19 @@ def main():
             h_, d_ = line["routes"]["host"], line["routes"]["device"]
             line["device_faster"] = bool(d_["median"] - h_["median"] > h_["max"] - h_["min"])
             line["png_size_device_over_host"] = round(d_["png_bytes_per_frame"] / h_["png_bytes_per_frame"], 4)
+        if vary_ply:
+            fps = {r: sorted(args.frames / t for t in times[r]) for r in routes}
+            line["routes"] = {r: dict(fps=[round(v, 1) for v in fps[r]], median=round(float(np.median(fps[r])), 1), min=round(fps[r][0], 1),
+                                      max=round(fps[r][-1], 1), ply_bytes_per_frame=ply_bytes("on_" + r) // args.frames) for r in routes}
+            n_final = rec_on.cpu().numpy().view(RW_DTYPE)["n_ror"].astype(np.int64)
+            line["routes"]["host"]["d2h_ply_bytes_per_frame"] = int(n_final.sum()) * 15 // args.frames + 4            # (+ the i32 count)
+            line["routes"]["device"]["d2h_ply_bytes_per_frame"] = line["routes"]["device"]["ply_bytes_per_frame"] + 12  # (+ offset and flag)
+            line["ply_fallback"] = len(json.load(open(os.path.join(work, "on_device", "manifest_rank0.json")))["ply_fallback"])
+            h_, d_ = line["routes"]["host"], line["routes"]["device"]
+            line["device_faster"] = bool(d_["median"] - h_["median"] > h_["max"] - h_["min"])
+            line["files_identical"] = all(
+                open(os.path.join(work, "on_host", outputs.SEQ_PLY_DIR, f), "rb").read() == open(os.path.join(work, "on_device", outputs.SEQ_PLY_DIR, f), "rb").read()
+                for f in sorted(os.listdir(os.path.join(work, "on_host", outputs.SEQ_PLY_DIR))))
         print(json.dumps(line))
         eng.close()
     finally:

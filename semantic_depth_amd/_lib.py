@@ -15,6 +15,7 @@ SD_OK = 0
 SD_ERR_INVALID, SD_ERR_HIP, SD_ERR_STATE, SD_ERR_NOTFOUND, SD_ERR_FORMAT = -1, -2, -3, -4, -5
 SD_ENC_VGG, SD_ENC_RESNET50 = 0, 1
 SD_NET_FCN8S, SD_NET_MONODEPTH = 0, 1
+SD_PLY_ROW_CAP, SD_PLY_HEADER_CAP, SD_PLY_LINE_ROWS = 69, 209, 1001
 SD_PREC_F32, SD_PREC_BF16X2, SD_PREC_MIXED, SD_PREC_PLAN, SD_PREC_BF16X3, SD_PREC_F16X2 = 0, 1, 2, 3, 4, 5
 
 
@@ -101,6 +102,9 @@ SIGNATURES = {
     "sd_png_write_streams_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_int,
                                              C.POINTER(C.c_int)]),
     "sd_ply_format_rows": (C.c_int64, [_P, _P, C.c_int64, _P, C.c_int64, C.c_int]),
+    "sd_ply_format_workspace": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "sd_ply_format_rw": (C.c_int, [_H, _P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _P]),
+    "sd_ply_format_rw_host": (C.c_int, [_P, _P, C.c_int, C.POINTER(sd_rw_result), _P, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     "sd_post_process": (C.c_int, [_H, _P, C.c_int, _P, _P]),
     "sd_resize_cubic_u8": (C.c_int, [_H, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
     "sd_compose_result_frames": (C.c_int, [_H, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),

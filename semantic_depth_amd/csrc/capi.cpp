@@ -14,6 +14,7 @@
 
 #include "jpeg_gpu.hpp"
 #include "png_gpu.hpp"
+#include "ply_gpu.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -789,6 +790,35 @@ sd_status sd_png_encode_bgr(sd_handle* h, const uint8_t* frames_dev, size_t fram
     if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(sizes_dev) & 7))
         return fail(h, SD_ERR_INVALID, "sd_png_encode_bgr: workspace_dev must be 16-byte, sizes_dev 8-byte aligned");
     HIPCHK(h, launch_png_encode(frames_dev, frame_stride, B, height, width, streams_dev, stream_stride, sizes_dev,
+                                static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
+    return SD_OK;
+}
+
+static_assert(SD_PLY_ROW_CAP == sdply::kRowCap && SD_PLY_HEADER_CAP == sdply::kHeaderCap && SD_PLY_LINE_ROWS == sdply::kLineRows,
+              "include/semdepth.h and ply_format.hpp disagree");
+constexpr int kPlyMaxCap = 0x7fffffff - sdply::kLineRows - sdply::kBlockRows;      // row indices stay in an int
+
+sd_status sd_ply_format_workspace(int B, int cap, size_t* workspace_bytes, size_t* text_bound) {
+    if (B < 1 || B > 65535 || cap < 0 || cap > kPlyMaxCap) return SD_ERR_INVALID;
+    if (workspace_bytes) *workspace_bytes = ply_workspace_bytes(B, cap);
+    if (text_bound) *text_bound = ply_text_bound(B, cap);
+    return SD_OK;
+}
+
+sd_status sd_ply_format_rw(sd_handle* h, const float* xyz_dev, const uint8_t* rgb_dev, const int32_t* n_dev, int B, int cap,
+                           const sd_rw_result* records_dev, uint8_t* text_dev, size_t text_capacity, uint64_t* offsets_dev, int32_t* flags_dev,
+                           void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!h || !xyz_dev || !rgb_dev || !n_dev || !records_dev || !text_dev || !offsets_dev || !flags_dev || !workspace_dev)
+        return fail(h, SD_ERR_INVALID, "sd_ply_format_rw: null pointer");
+    if (B < 1 || B > 65535 || cap < 0 || cap > kPlyMaxCap) return fail(h, SD_ERR_INVALID, "sd_ply_format_rw: B must be 1..65535, cap >= 0");
+    // every index the kernels form follows from B, cap and these capacities: nothing is launched otherwise
+    if (workspace_bytes < ply_workspace_bytes(B, cap))
+        return fail(h, SD_ERR_INVALID, "sd_ply_format_rw: workspace smaller than sd_ply_format_workspace reports");
+    if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(offsets_dev) & 7) ||
+        (reinterpret_cast<uintptr_t>(flags_dev) & 3) || (reinterpret_cast<uintptr_t>(xyz_dev) & 3) || (reinterpret_cast<uintptr_t>(n_dev) & 3) ||
+        (reinterpret_cast<uintptr_t>(records_dev) & 7))
+        return fail(h, SD_ERR_INVALID, "sd_ply_format_rw: workspace_dev must be 16-byte, offsets_dev and records_dev 8-byte, the rest naturally aligned");
+    HIPCHK(h, launch_ply_format(xyz_dev, rgb_dev, n_dev, B, cap, records_dev, text_dev, text_capacity, offsets_dev, flags_dev,
                                 static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
     return SD_OK;
 }

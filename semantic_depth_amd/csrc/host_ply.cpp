@@ -3,6 +3,7 @@
 // in Python (0.4 s for a 150 k-point cloud); this is the same text from std::to_chars -- correctly rounded fixed notation with six
 // decimals, what "%f" % float(v) prints -- on a few threads.  No handle, no GPU.
 #include "../../include/semdepth.h"
+#include "ply_format.hpp"
 
 #include <charconv>
 #include <cmath>
@@ -68,4 +69,51 @@ extern "C" int64_t sd_ply_format_rows(const double* xyz, const int64_t* rgb, int
         w += len[t];
     }
     return w;
+}
+
+// ---- the host statement of the device route (sd_ply_format_rw): one frame, a single walk over the coder of ply_format.hpp ----
+static_assert(SD_PLY_ROW_CAP == sdply::kRowCap && SD_PLY_HEADER_CAP == sdply::kHeaderCap && SD_PLY_LINE_ROWS == sdply::kLineRows,
+              "include/semdepth.h and ply_format.hpp disagree");
+
+extern "C" sd_status sd_ply_format_rw_host(const float* xyz_host, const uint8_t* rgb_host, int n, const sd_rw_result* record, uint8_t* out_host,
+                                           size_t cap, size_t* size_out, int32_t* flag_out) {
+    using namespace sdply;
+    if (n < 0 || !record || !size_out || !flag_out || (n > 0 && (!xyz_host || !rgb_host)) || (cap > 0 && !out_host)) return SD_ERR_INVALID;
+    *size_out = 0;
+    *flag_out = 0;
+    const Frame f = make_frame(xyz_host, rgb_host, n, n, record->left_pt, record->right_pt, record->found);
+    double p[3];
+    uint8_t c[3];
+    // the minimum z of all rows and the range test
+    bool bad = f.bad;
+    double zmin = __builtin_huge_val();
+    for (int r = 0; r < f.rows; ++r) {
+        row_point(f, r, p, c);
+        bad = bad || !in_range(p[0]) || !in_range(p[1]) || !in_range(p[2]);
+        zmin = p[2] < zmin ? p[2] : zmin;
+    }
+    if (bad) {
+        *flag_out = 1;
+        return SD_OK;
+    }
+    // the kept rows and their exact length
+    uint32_t count = 0;
+    size_t body = 0;
+    for (int r = 0; r < f.rows; ++r) {
+        row_point(f, r, p, c);
+        if (!(p[2] > zmin)) continue;
+        ++count;
+        body += (size_t)row_len(make_row(p, c));
+    }
+    const int hdr = header_len(count);
+    if ((size_t)hdr + body > cap) return SD_ERR_INVALID;
+    for (int i = 0; i < hdr; ++i) out_host[i] = header_byte(i, count);
+    uint8_t* q = out_host + hdr;
+    for (int r = 0; r < f.rows; ++r) {
+        row_point(f, r, p, c);
+        if (!(p[2] > zmin)) continue;
+        q += put_row(q, make_row(p, c));
+    }
+    *size_out = (size_t)(q - out_host);
+    return SD_OK;
 }

@@ -95,7 +95,7 @@ def run_sequence(load_frames, n_frames: int, step, batch: int = 32, group=None, 
 
 
 def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", workers: int = 0, outputs=None, jpeg: str = "host",
-                       engine=None, png: str | None = None) -> torch.Tensor:
+                       engine=None, png: str | None = None, ply: str | None = None) -> torch.Tensor:
     """run_sequence on FILES (semantic_depth_cityscapes_sequence.py:689-701 reads ``sorted(glob(input_folder))`` frame by frame): rank r
     decodes ONLY its shard of the sorted list -- frame_io.FrameFeeder: one native call per batch into pinned staging, upload one batch
     ahead, ``workers`` decode threads (default: this rank's share of the node's CPUs, frame_io.default_decode_workers) -- and hands every
@@ -106,7 +106,9 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     ``jpeg`` ("host" | "device") and ``engine`` go to the feeder: with "device" the JPEG frames are only entropy-decoded on the host and
     reconstructed on the GPU by ``engine`` (default: ``step.engine``, set by make_engine_step); the frames are the same bytes.
     ``png`` ("host" | "device", None = what the SequenceOutputs was built with): where the result images are compressed
-    (SequenceOutputs.set_png; "device" needs the step of make_engine_step, which encodes the streams on the GPU)."""
+    (SequenceOutputs.set_png; "device" needs the step of make_engine_step, which encodes the streams on the GPU).
+    ``ply`` ("host" | "device", None = what the SequenceOutputs was built with): where the road PLYs are formatted (SequenceOutputs.set_ply;
+    "device" needs the step of make_engine_step, which formats the text on the GPU)."""
     from .frame_io import FrameFeeder
     engine = engine if engine is not None else getattr(step, "engine", None)
     paths = sorted(paths)
@@ -120,6 +122,8 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
             raise ValueError(f"SequenceOutputs has {len(outputs.names)} names for {n_frames} frames")
         if png is not None:
             outputs.set_png(png)
+        if ply is not None:
+            outputs.set_ply(ply)
         outputs.begin(rank, world, lo, hi)
     try:
         parts = []
@@ -146,7 +150,8 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     return out
 
 
-def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outputs=None, on_range: str | None = None, png: str | None = None):
+def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outputs=None, on_range: str | None = None, png: str | None = None,
+                     ply: str | None = None):
     """``step`` for run_sequence on a real Engine: host or device u8 frames of any size -> (cubic resize to the network shape on
     the GPU, semantic_depth_cityscapes_sequence.py:123-130) -> Engine.process_batch -> record buffer.
     ``camera_of(global_frame_index) -> engine.Camera`` (the sequence tool: cx = 1048.64/4·s, cy = 519.277/4·s, disp_mult = 3800).
@@ -157,7 +162,10 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     are recomputed on bf16x3 inside process_batch, so every batch's records, images and PLYs are final before gather_records and no rank
     raises from ``step.finish`` for them; ``step.recomputed`` (and the manifest's 'recomputed' names) lists those frames.
     ``png`` ("host" | "device", None = what ``outputs`` was built with): with "device" Engine.encode_png turns the composed images into
-    zlib streams on the step's stream, right behind the compose launch, and only the streams' bytes travel to the host."""
+    zlib streams on the step's stream, right behind the compose launch, and only the streams' bytes travel to the host.
+    ``ply`` ("host" | "device", None = what ``outputs`` was built with): with "device" Engine.format_rw_ply turns the final road clouds and
+    the records into the text of the ``_rw.ply`` files on the step's stream, and only that text travels to the host (the raw cloud of a
+    frame the device did not format still does: SequenceOutputs)."""
     from .engine import RoadWidthParams
     from .recompute import check_mode
 
@@ -166,6 +174,8 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     prm = params or RoadWidthParams()
     if png is not None and outputs is not None:
         outputs.set_png(png)
+    if ply is not None and outputs is not None:
+        outputs.set_ply(ply)
     recomputed: list[int] = []
 
     def note(lo):
@@ -189,13 +199,16 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
         note(lo)
         rec = out["records"]
         images = None
+        more = {}
+        if outputs.ply and getattr(outputs, "ply_route", "host") == "device":     # the text of the PLY files, on the step's stream
+            more["ply_text"] = engine.format_rw_ply(out["road_final"], rec)
         if outputs.images:
             images = engine.compose_result_frames(fr, out["seg"]["road"], out["seg"]["fence"], rec, size[0], size[1], outputs.road_color,
                                                   outputs.fence_color, outputs.alpha)
             if getattr(outputs, "png", "host") == "device":        # the zlib streams right behind the compose launch, on the step's stream
-                outputs.submit(lo, rec, size, final=out.get("road_final"), png_streams=engine.encode_png(images))
+                outputs.submit(lo, rec, size, final=out.get("road_final"), png_streams=engine.encode_png(images), **more)
                 return rec
-        outputs.submit(lo, rec, size, images=images, final=out.get("road_final"))
+        outputs.submit(lo, rec, size, images=images, final=out.get("road_final"), **more)
         return rec
 
     # ('recompute': every clamp in a stored output is attributed to its frame and that frame recomputed, so the step has no verdict left

@@ -396,6 +396,41 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_png_encode_bgr")
         return streams, sizes
 
+    def format_rw_ply(self, final: dict, records: torch.Tensor, capacity: int | None = None, out: torch.Tensor | None = None):
+        """the device half of the road PLY writer (sd_ply_format_rw): ``final`` = process_batch(want_final=True)'s road_final (xyz f32 [B,cap,3],
+        rgb u8 [B,cap,3], n i32 [B]) and ``records`` u8 [B,104] (sd_rw_result) -> (``text`` u8 [capacity], ``offsets`` i64 [B+1], ``flags`` i32 [B])
+        device tensors: frame b's ``<name>_rw.ply`` is ``text[offsets[b]:offsets[b+1]]``, the bytes of outputs.rw_ply_bytes; the files are packed
+        back to back and nothing at or behind ``offsets[B]`` is written.  flags[b] = 1: the frame holds a non-finite value or |v| >= 2^31 and
+        was not formatted (write it through rw_ply_bytes); 2: its text would pass ``capacity``; both have size 0.
+        ``capacity`` None: the bound for the clouds' ``cap`` dimension, B * (209 + (cap + 1001) * 69) bytes -- about 1.2 GB at B = 32 and
+        512 x 1024 -- unless ``out`` (a u8 device tensor to write into) gives it; a smaller capacity is legal (flag 2).  Five launches on the
+        current stream, no synchronisation; the workspace is a torch allocation."""
+        xyz, rgb, n = final["xyz"], final.get("rgb"), final["n"]
+        if rgb is None:
+            raise ValueError("format_rw_ply needs the colours of the road cloud (final['rgb'] is None)")
+        assert xyz.dtype == torch.float32 and xyz.is_cuda and xyz.is_contiguous() and xyz.dim() == 3 and xyz.shape[2] == 3
+        B, cap = int(xyz.shape[0]), int(xyz.shape[1])
+        assert rgb.dtype == torch.uint8 and rgb.is_cuda and rgb.is_contiguous() and tuple(rgb.shape) == (B, cap, 3)
+        assert n.dtype == torch.int32 and n.is_cuda and n.is_contiguous() and tuple(n.shape) == (B,)
+        assert records.dtype == torch.uint8 and records.is_cuda and records.is_contiguous() and tuple(records.shape) == (B, RW_DTYPE.itemsize)
+        need, bound = C.c_size_t(), C.c_size_t()
+        st = self.lib.sd_ply_format_workspace(B, cap, C.byref(need), C.byref(bound))
+        L.check(self.lib, None, st, "sd_ply_format_workspace")
+        if out is not None:
+            assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.dim() == 1
+            capacity = int(out.numel()) if capacity is None else int(capacity)
+            assert capacity <= out.numel()
+        else:
+            capacity = bound.value if capacity is None else int(capacity)
+            out = torch.empty((max(capacity, 1),), dtype=torch.uint8, device=self.device)
+        offsets = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
+        flags = torch.empty((B,), dtype=torch.int32, device=self.device)
+        ws = torch.empty((need.value,), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_ply_format_rw(self.h, _ptr(xyz), _ptr(rgb), _ptr(n), B, cap, _ptr(records), _ptr(out), capacity, _ptr(offsets), _ptr(flags),
+                                       _ptr(ws), need.value, self._stream())
+        L.check(self.lib, self.h, st, "sd_ply_format_rw")
+        return out[:capacity], offsets, flags
+
     def post_process(self, disp_raw: torch.Tensor):
         B = disp_raw.shape[0]
         assert disp_raw.dtype == torch.float32 and tuple(disp_raw.shape[1:]) == (2, self.H, self.W) and disp_raw.is_contiguous()

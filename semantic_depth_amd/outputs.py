@@ -416,9 +416,14 @@ class SequenceOutputs:
     ``threads``: native encoder threads per batch and PLY writer threads (0: frame_io.default_decode_workers()).
     ``png``: "host" (default) copies the raw images to the host and deflates them there (sd_png_encode_bgr_files at ``level``); "device"
     takes each frame's finished zlib stream from the GPU (Engine.encode_png, submit(png_streams=)): the sizes are copied first, then each
-    stream's exact byte count, and the host only writes the PNG chunks (sd_png_write_streams_files).  Same names, manifest and pixels."""
+    stream's exact byte count, and the host only writes the PNG chunks (sd_png_write_streams_files).  Same names, manifest and pixels.
+    ``ply``: False (no PLY files), True / "host" (default: the raw clouds are copied to the host and formatted there, rw_ply_bytes) or "device":
+    the step hands submit(ply_text=) the finished text of every file (Engine.format_rw_ply); the offsets and flags are copied first, then
+    text[:offsets[n]] in one copy, and the host only writes each slice.  A frame the device did not format (a non-zero flag: a non-finite
+    coordinate or |v| >= 2^31) has its raw cloud copied and goes through rw_ply_bytes; the manifest names those frames under 'ply_fallback'.
+    Same names and the same bytes."""
 
-    def __init__(self, directory: str, names, depth: float = 10.0, images: bool = True, ply: bool = True, items: bool = True, level: int = 1,
+    def __init__(self, directory: str, names, depth: float = 10.0, images: bool = True, ply: bool | str = True, items: bool = True, level: int = 1,
                  threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, png: str = "host"):
         from concurrent.futures import ThreadPoolExecutor
 
@@ -426,6 +431,7 @@ class SequenceOutputs:
         if not 0 <= level <= 9:
             raise ValueError("PNG compression level must be 0..9")
         self.set_png(png)
+        self.set_ply("host" if isinstance(ply, bool) else ply)
         self.directory, self.names, self.depth = directory, list(names), float(depth)
         self.images, self.ply, self.items, self.level = bool(images), bool(ply), bool(items), int(level)
         self.road_color, self.fence_color, self.alpha = tuple(road_color), tuple(fence_color), int(alpha)
@@ -442,6 +448,7 @@ class SequenceOutputs:
         self._streams = None
         self.manifest = None
         self.recomputed: list[int] = []                               # global indices of the frames recomputed on bf16x3 (on_range='recompute')
+        self.ply_fallback: list[int] = []                             # global indices of the frames ply="device" sent through rw_ply_bytes
 
     # ---------------------------------------------------------------- driver interface
     def set_png(self, png: str):
@@ -452,15 +459,25 @@ class SequenceOutputs:
             raise RuntimeError("SequenceOutputs.set_png after the first batch")
         self.png = png
 
+    def set_ply(self, ply: str):
+        """where the road PLYs are formatted: "host" or "device" (before the first batch; whether they are written at all is ``ply`` of the
+        constructor, kept in ``self.ply``)"""
+        if ply not in ("host", "device") or isinstance(ply, bool):
+            raise ValueError(f"ply must be 'host' or 'device', got {ply!r}")
+        if getattr(self, "_k", 0):
+            raise RuntimeError("SequenceOutputs.set_ply after the first batch")
+        self.ply_route = ply
+
     def begin(self, rank: int, world: int, lo: int, hi: int):
         """the shard [lo, hi) this rank writes (run_sequence_files calls it before the first batch)"""
         self.rank, self.world, self.shard = int(rank), int(world), (int(lo), int(hi))
 
-    def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None):
+    def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None, ply_text=None):
         """one batch: ``records`` u8 [n,104] (sd_rw_result), ``size`` = (h, w) of the original frames, ``images`` u8 [n,h,w,3] (the composed
         result images) or None, ``final`` = dict(xyz f32 [n,cap,3], rgb u8 [n,cap,3], n i32 [n]) (process_batch(want_final=True)'s
         road_final) or None, ``png_streams`` = (streams u8 [n,stride], sizes i64 [n]) of Engine.encode_png in place of ``images`` on the
-        device route.  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
+        device route, ``ply_text`` = (text u8 [capacity], offsets i64 [n+1], flags i32 [n]) of Engine.format_rw_ply on the ply="device" route
+        (beside ``final``, which the flagged frames are written from).  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
         tensors of every step)."""
         import torch
         if self.manifest is not None:
@@ -470,6 +487,10 @@ class SequenceOutputs:
             raise ValueError(f"frames {lo}..{lo + n - 1} are beyond the {len(self.names)} names")
         if self.images and (png_streams if self.png == "device" else images) is None or self.ply and final is None:
             raise ValueError("SequenceOutputs: this batch lacks the images (png='device': the streams) / final road clouds the outputs ask for")
+        if self.ply and self.ply_route == "device" and ply_text is None:
+            raise ValueError("SequenceOutputs: ply='device' needs the text of Engine.format_rw_ply (submit(ply_text=))")
+        if not self.ply or self.ply_route != "device":
+            ply_text = None
         while len(self._jobs) >= 2:                                    # at most two batches in flight
             self._files.extend(self._jobs.pop(0).result())
         slot = self._k & 1
@@ -484,7 +505,7 @@ class SequenceOutputs:
             images = None
         else:
             png_streams = None
-        self._jobs.append(self._batches.submit(self._write_batch, slot, lo, records, tuple(size), images, final, ev, png_streams))
+        self._jobs.append(self._batches.submit(self._write_batch, slot, lo, records, tuple(size), images, final, ev, png_streams, ply_text))
 
     def mark_recomputed(self, frames):
         """global frame indices whose outputs came from the bf16x3 recompute (make_engine_step(on_range='recompute')): the manifest lists
@@ -511,7 +532,9 @@ class SequenceOutputs:
         files = sorted(os.path.relpath(p, self.directory) for p in self._files)
         with open(self.manifest, "w") as f:
             json.dump(dict(rank=self.rank, world=self.world, frames=list(self.shard), status=status, valid=status == "ok", files=files,
-                           recomputed=[self.names[i] for i in sorted(set(self.recomputed))]), f, indent=1)
+                           recomputed=[self.names[i] for i in sorted(set(self.recomputed))],
+                           **(dict(ply_fallback=[self.names[i] for i in sorted(set(self.ply_fallback))]) if self.ply and self.ply_route == "device" else {})),
+                      f, indent=1)
         if err is not None:
             raise err
         return self.manifest
@@ -525,9 +548,11 @@ class SequenceOutputs:
             buf = self._staging[slot][key] = torch.empty(max(numel, 1), dtype=dtype, pin_memory=pin)
         return buf[:numel].view(*shape)
 
-    def _to_host(self, slot, lo, records, images, final, ev, png_streams=None):
+    def _to_host(self, slot, lo, records, images, final, ev, png_streams=None, ply_text=None):
         """numpy views of the batch (device tensors: copied into pinned staging on this slot's side stream behind ``ev``): records, images,
-        clouds and, from ``png_streams``, (streams [n,stride], sizes [n]) of which only streams[i, :sizes[i]] was copied"""
+        clouds, from ``png_streams`` (streams [n,stride], sizes [n]) of which only streams[i, :sizes[i]] was copied, and from ``ply_text``
+        (text [offsets[n]], offsets [n+1], flags [n]); with ``ply_text`` only the clouds of the frames with a non-zero flag are copied
+        (the others are None)"""
         import torch
 
         def host(t):
@@ -541,7 +566,8 @@ class SequenceOutputs:
                 cnt = host(final["n"])
                 xyz, rgb = (host(final[k]) for k in ("xyz", "rgb"))
                 clouds = [(xyz[i, :cnt[i]], rgb[i, :cnt[i]]) for i in range(len(cnt))]
-            return rec, img, clouds, None if png_streams is None else (host(png_streams[0]), host(png_streams[1]))
+            return (rec, img, clouds, None if png_streams is None else (host(png_streams[0]), host(png_streams[1])),
+                    None if ply_text is None else tuple(host(t) for t in ply_text))
         s = self._streams[slot]
         with torch.cuda.stream(s):
             s.wait_event(ev)
@@ -551,15 +577,26 @@ class SequenceOutputs:
             if images is not None:
                 img = self._pinned(slot, "img", tuple(images.shape), torch.uint8, True)
                 img.copy_(images, non_blocking=True)
-            cnt = psz = None
+            cnt = psz = poff = pflg = None
             if final is not None:
                 cnt = self._pinned(slot, "n", tuple(final["n"].shape), torch.int32, True)
                 cnt.copy_(final["n"], non_blocking=True)
             if png_streams is not None:                                # phase one: the sizes; phase two: each stream's exact bytes
                 psz = self._pinned(slot, "png_sizes", tuple(png_streams[1].shape), torch.int64, True)
                 psz.copy_(png_streams[1], non_blocking=True)
+            if ply_text is not None:                                   # phase one: offsets and flags; phase two: the produced bytes, one copy
+                poff = self._pinned(slot, "ply_offsets", tuple(ply_text[1].shape), torch.int64, True)
+                poff.copy_(ply_text[1], non_blocking=True)
+                pflg = self._pinned(slot, "ply_flags", tuple(ply_text[2].shape), torch.int32, True)
+                pflg.copy_(ply_text[2], non_blocking=True)
             s.synchronize()
-            clouds = png = None
+            clouds = png = ply = None
+            if ply_text is not None:
+                total = int(poff[-1])
+                tbuf = self._pinned(slot, "ply_text", (total,), torch.uint8, True)
+                if total:
+                    tbuf.copy_(ply_text[0][:total], non_blocking=True)
+                ply = (tbuf.numpy(), poff.numpy(), pflg.numpy())
             if png_streams is not None:
                 streams = png_streams[0]
                 pbuf = self._pinned(slot, "png", tuple(streams.shape), torch.uint8, True)
@@ -569,6 +606,8 @@ class SequenceOutputs:
                 png = (pbuf.numpy(), pn)
             if final is not None:
                 cn = cnt.numpy().astype(np.int64)
+                if ply is not None:                                    # only the frames the device did not format travel raw
+                    cn = np.where(ply[2] != 0, cn, 0)
                 off = np.concatenate([[0], np.cumsum(cn)])
                 xyz = self._pinned(slot, "xyz", (int(off[-1]), 3), torch.float32, True)
                 rgb = self._pinned(slot, "rgb", (int(off[-1]), 3), torch.uint8, True)
@@ -577,14 +616,14 @@ class SequenceOutputs:
                         xyz[off[i]:off[i + 1]].copy_(final["xyz"][i, :cn[i]], non_blocking=True)
                         rgb[off[i]:off[i + 1]].copy_(final["rgb"][i, :cn[i]], non_blocking=True)
                 xn, rn = xyz.numpy(), rgb.numpy()
-                clouds = [(xn[off[i]:off[i + 1]], rn[off[i]:off[i + 1]]) for i in range(len(cn))]
+                clouds = [(xn[off[i]:off[i + 1]], rn[off[i]:off[i + 1]]) if ply is None or ply[2][i] != 0 else None for i in range(len(cn))]
             if final is not None or png_streams is not None:
                 s.synchronize()
-        return rec.numpy(), None if img is None else img.numpy(), clouds, png
+        return rec.numpy(), None if img is None else img.numpy(), clouds, png, ply
 
-    def _write_batch(self, slot, lo, records, size, images, final, ev, png_streams=None):
+    def _write_batch(self, slot, lo, records, size, images, final, ev, png_streams=None, ply_text=None):
         from .engine import RW_DTYPE
-        rec_u8, img, clouds, png = self._to_host(slot, lo, records, images, final, ev, png_streams)
+        rec_u8, img, clouds, png, ply = self._to_host(slot, lo, records, images, final, ev, png_streams, ply_text)
         recs = np.ascontiguousarray(rec_u8).view(RW_DTYPE).reshape(-1)
         n = len(recs)
         names = self.names[lo:lo + n]
@@ -598,6 +637,10 @@ class SequenceOutputs:
 
         def write_ply(i):
             path = os.path.join(self.ply_dir, "{}_rw.ply".format(names[i]))
+            if ply is not None and ply[2][i] == 0:                     # the device route: the slice is the file
+                with open(path, "wb") as f:
+                    f.write(ply[0][int(ply[1][i]):int(ply[1][i + 1])].data)
+                return path
             left, right = ends(recs[i])
             xyz, rgb = clouds[i]
             with open(path, "wb") as f:
@@ -613,6 +656,8 @@ class SequenceOutputs:
                 json.dump(dict(banner=banner, items=items), f)
             return path
 
+        if self.ply and ply is not None:
+            self.ply_fallback.extend(lo + i for i in range(n) if ply[2][i] != 0)
         for i in range(n):
             if self.ply:
                 futs.append(self._writers.submit(write_ply, i))

@@ -1,6 +1,8 @@
 """Drop-in for the reference's ``semantic_depth_lib/point_cloud_2_ply.py``: ASCII PLY export of a coloured
 point cloud.  Host-side output formatting, no GPU work (the rows come from the library's host helper sd_ply_format_rows); byte-identical
 files (tests/test_ply.py pins it against the reference's own class and against numpy.savetxt).
+(This module itself does no GPU work.  The sequence tool's ``_rw.ply`` files have an opt-in device route beside it -- sd_ply_format_rw /
+Engine.format_rw_ply / SequenceOutputs(ply="device"), csrc/ply_gpu.hip -- which produces the bytes of this module's header and rows.)
 
 Format quirks kept on purpose (point_cloud_2_ply.py:38-49, :70, :88): every header line after the first is indented by four
 spaces exactly as the reference's triple-quoted literal is, rows are ``%f %f %f %d %d %d``, and
