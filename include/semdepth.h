@@ -341,6 +341,65 @@ sd_status sd_ply_format_rw(sd_handle* h, const float* xyz_dev, const uint8_t* rg
 sd_status sd_ply_format_rw_host(const float* xyz_host, const uint8_t* rgb_host, int n, const sd_rw_result* record, uint8_t* out_host, size_t cap,
                                 size_t* size_out, int32_t* flag_out);
 
+/* ---- result images, the banner text: rasterised on the GPU between sd_compose_result_frames and the PNG encoder (opt-in) ----
+ * The reference draws its numbers with cv2.putText (fontFace 16 = italic | Hershey simplex; OpenCV ignores the italic bit for simplex).
+ * OpenCV's glyph tables are not reproduced: the project draws a stroke font of its own (constructed by scripts/make_text_font.py from
+ * straight strokes and sampled ellipse arcs; no vertex list of Hershey's or any other font) with a rule of its own, both stated once, for
+ * host and device, in semantic_depth_amd/csrc/text_draw.hpp.  No pixel identity with OpenCV is claimed; no anti-aliasing.
+ *   font      integer unit grid, baseline y = 0, y up, cap height 21, x-height 14, descenders to -7; every vertex of a glyph lies in
+ *             [0, advance] x [-7, 21], advance <= 24; a glyph is at most SD_TEXT_MAX_SEGS straight segments.  Glyphs: space, 0-9, A-Z, a-z
+ *             and . , : ; ' - + / ( ) % =; every other byte draws one box glyph.
+ *   an item   text (len <= SD_TEXT_MAX_BYTES bytes), org = the baseline-left corner in pixels, scale_q8 = lround(fontScale * 256), the
+ *             colour in the image's channel order, thickness.  Caps: 1 <= scale_q8 <= SD_TEXT_MAX_SCALE_Q8, 1 <= thickness <=
+ *             SD_TEXT_MAX_THICKNESS, |org| <= SD_TEXT_MAX_ORG, image extents 1..16384.
+ *   the rule  in 1/256 pixel: vertex (ux, uy) of the glyph at pen position p (the sum of the advances before it) is X = org_x * 256 +
+ *             (p + ux) * scale_q8, Y = org_y * 256 - uy * scale_q8; pixel (px, py) has its centre at (px * 256, py * 256) and takes the
+ *             item's colour iff its squared distance to some segment of the item is <= (thickness * 128)^2, decided in exact integer
+ *             arithmetic (a degenerate segment is a disc).  Pixels outside the image are clipped, items are drawn in list order, and
+ *             a pixel no item paints is never written.
+ *   numbers   "%.2f" as Python's "{:.2f}".format(v): half-even on the exact binary value, the sign whenever the sign bit is set ("-0.00"),
+ *             nan, inf, -inf; a finite |v| >= 2^31 draws inf / -inf (the _overlay.json keeps Python's string).
+ *   sequence layout (outputs.overlay_items_sequence): found != 0 -- "At <depth> m depth:" at (int(0.36 w), int(0.05 h)), scale 2.2;
+ *             "<-left_pt[0]>m to road's left end" at (int(0.05 w), int(0.13 h)), "<right_pt[0]>m to road's right end" at (int(0.5 w),
+ *             int(0.13 h)), "Road's width: <width> m" at (int(0.35 w), int(0.22 h)), scale 2; white, thickness 2.  found == 0 -- "Cannot
+ *             compute width of road at <depth> m depth:" at (int(0.28 w), int(0.035 h)), scale 2.2, green (0, 255, 0).  The origins are
+ *             products in doubles, truncated.  <depth> is the caller's string, at most 23 bytes. */
+#define SD_TEXT_MAX_BYTES 64
+#define SD_TEXT_MAX_SEGS 32
+#define SD_TEXT_MAX_ITEMS 4
+#define SD_TEXT_MAX_SCALE_Q8 4096
+#define SD_TEXT_MAX_THICKNESS 32
+#define SD_TEXT_MAX_ORG 32768
+typedef struct {
+    uint8_t text[SD_TEXT_MAX_BYTES];
+    int32_t len;
+    int32_t org_x, org_y;
+    int32_t scale_q8;
+    int32_t thickness;
+    uint8_t bgr[3];        /* the three bytes stored into a painted pixel, in the image's channel order */
+    uint8_t reserved;      /* 0 */
+} sd_text_item;
+/* the device workspace sd_text_draw_rw needs for B frames; 0 for B < 1 or B > 65535 */
+size_t sd_text_workspace_bytes(int B);
+/* DEVICE: draws the sequence layout of records_dev[b] (B records, read on the device: no host synchronisation) into dst_dev u8
+ * [B,dst_h,dst_w,3] IN PLACE; only painted pixels are written.  depth_text: the NUL-terminated "{:.2f}".format(depth) of the caller.  Two
+ * launches on `stream` (one workgroup per frame formats the numbers and lays the items out in the workspace; 64 x 16 pixel tiles of every
+ * item's box test their pixels against the segments of the glyphs in reach); every workspace byte that is read was written by the same call, so
+ * the result does not depend on the workspace's contents.  The handle need not be bound.  SD_ERR_INVALID, nothing launched: a null pointer,
+ * B < 1 or B > 65535, an extent outside 1..16384, depth_text longer than 23 bytes, workspace_bytes below sd_text_workspace_bytes(B), a
+ * workspace that is not 16-byte aligned, records_dev not 8-byte aligned. */
+sd_status sd_text_draw_rw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int dst_w, const sd_rw_result* records_dev, const char* depth_text,
+                          void* workspace_dev, size_t workspace_bytes, void* stream);
+/* HOST: the items sd_text_draw_rw draws for one record on a dst_h x dst_w image, as data: items_out[0 .. *n_out), *n_out <= SD_TEXT_MAX_ITEMS;
+ * every byte of a returned item is defined (text is zero-filled behind len).  SD_ERR_INVALID as above. */
+sd_status sd_text_items_rw_host(const sd_rw_result* record, const char* depth_text, int dst_h, int dst_w, sd_text_item* items_out, int* n_out);
+/* HOST: the same rule for any n >= 0 items on img_host u8 [h,w,3], in list order.  SD_ERR_INVALID, nothing drawn: a null pointer, an extent
+ * outside 1..16384, an item outside the caps above. */
+sd_status sd_text_draw_host(uint8_t* img_host, int h, int w, const sd_text_item* items, int n);
+/* HOST: the font as data: the segments {x0, y0, x1, y1} of byte `code` (0..255) into segs_out[0 .. 4 * *n_out), *n_out <= SD_TEXT_MAX_SEGS,
+ * and its advance.  SD_ERR_INVALID: a null pointer or a code outside 0..255. */
+sd_status sd_text_glyph(int code, int8_t* segs_out, int* n_out, int* advance_out);
+
 /* DepthFrame.post_processing alone, semantic_depth.py:656-664: disp_raw f32 [B,2,H,W] -> disp_pp f32 [B,H,W] */
 sd_status sd_post_process(sd_handle* h, const float* disp_raw, int B, float* disp_pp, void* stream);
 

@@ -37,6 +37,7 @@ SOURCES = [
     ("jpeg_gpu.hip", []),
     ("png_gpu.hip", []),
     ("ply_gpu.hip", ["-ffp-contract=off"]),
+    ("text_gpu.hip", []),
     ("fuse.hip", ["-ffp-contract=off"]),
     ("pcl.hip", ["-ffp-contract=off"]),
     ("plan.cpp", []),
@@ -44,8 +45,9 @@ SOURCES = [
     ("host_png.cpp", []),
     ("host_jpeg.cpp", []),
     ("host_ply.cpp", []),
+    ("host_text.cpp", []),
 ]
-HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", "ply_format.hpp", "ply_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
+HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", "ply_format.hpp", "ply_gpu.hpp", "text_draw.hpp", "text_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
 
 
 def _hipcc() -> str:

@@ -15,6 +15,7 @@
 #include "jpeg_gpu.hpp"
 #include "png_gpu.hpp"
 #include "ply_gpu.hpp"
+#include "text_gpu.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -820,6 +821,25 @@ sd_status sd_ply_format_rw(sd_handle* h, const float* xyz_dev, const uint8_t* rg
         return fail(h, SD_ERR_INVALID, "sd_ply_format_rw: workspace_dev must be 16-byte, offsets_dev and records_dev 8-byte, the rest naturally aligned");
     HIPCHK(h, launch_ply_format(xyz_dev, rgb_dev, n_dev, B, cap, records_dev, text_dev, text_capacity, offsets_dev, flags_dev,
                                 static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
+    return SD_OK;
+}
+
+size_t sd_text_workspace_bytes(int B) { return B < 1 || B > 65535 ? 0 : text_workspace_bytes(B); }
+
+sd_status sd_text_draw_rw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int dst_w, const sd_rw_result* records_dev, const char* depth_text,
+                          void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!h || !dst_dev || !records_dev || !depth_text || !workspace_dev) return fail(h, SD_ERR_INVALID, "sd_text_draw_rw: null pointer");
+    if (B < 1 || B > 65535) return fail(h, SD_ERR_INVALID, "sd_text_draw_rw: B must be 1..65535");
+    if (dst_h < 1 || dst_w < 1 || dst_h > sdtext::kMaxExtent || dst_w > sdtext::kMaxExtent)
+        return fail(h, SD_ERR_INVALID, "sd_text_draw_rw: extents must be 1..16384");
+    const size_t dlen = strnlen(depth_text, sdtext::kMaxDepthBytes + 1);
+    if (dlen > (size_t)sdtext::kMaxDepthBytes) return fail(h, SD_ERR_INVALID, "sd_text_draw_rw: depth_text longer than 23 bytes");
+    // every index the kernels form follows from B, the extents and this capacity: nothing is launched otherwise
+    if (workspace_bytes < text_workspace_bytes(B)) return fail(h, SD_ERR_INVALID, "sd_text_draw_rw: workspace smaller than sd_text_workspace_bytes reports");
+    if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(records_dev) & 7))
+        return fail(h, SD_ERR_INVALID, "sd_text_draw_rw: workspace_dev must be 16-byte, records_dev 8-byte aligned");
+    HIPCHK(h, launch_text_draw_rw(dst_dev, B, dst_h, dst_w, records_dev, reinterpret_cast<const uint8_t*>(depth_text), (int)dlen,
+                                  static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
     return SD_OK;
 }
 

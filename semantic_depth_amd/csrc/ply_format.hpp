@@ -47,11 +47,12 @@ SDPLY_HD int put_u32(uint8_t* p, uint32_t v) {
     return d;
 }
 
-// "%f" of an in_range double: the sign bit, the integer part and the six decimals, rounded half-even on the exact binary value
+// "%f" of an in_range double: the sign bit, the integer part and the six decimals, rounded half-even on the exact binary value.
+// fixed_dec is the same for any number of decimals up to six (unit = 10^decimals): "%.2f" of text_draw.hpp is fixed_dec(v, 100).
 struct Fixed {
     uint32_t ip, frac, neg;
 };
-SDPLY_HD Fixed fixed6(double v) {
+SDPLY_HD Fixed fixed_dec(double v, uint32_t unit) {
     const uint64_t u = dbits(v);
     Fixed f;
     f.neg = (uint32_t)(u >> 63);
@@ -61,24 +62,25 @@ SDPLY_HD Fixed fixed6(double v) {
     if (e == 0) return f;                                // zero, or below 2^-1022
     const uint64_t mant = (u & ((1ull << 52) - 1)) | (1ull << 52);
     const int k = 1075 - e;                              // |v| = mant * 2^-k; in_range: k >= 22
-    if (k >= 74) return f;                               // mant * 10^6 < 2^73 <= 2^(k-1): below half a unit of the sixth decimal
+    if (k >= 74) return f;                               // mant * unit <= mant * 10^6 < 2^73 <= 2^(k-1): below half a unit of the last decimal
     uint64_t mf = mant;
     if (k <= 52) {
         f.ip = (uint32_t)(mant >> k);
         mf = mant & ((1ull << k) - 1);
     }
     const unsigned __int128 one = 1;
-    const unsigned __int128 p = (unsigned __int128)mf * 1000000u;        // < 2^73
-    uint32_t q = (uint32_t)(p >> k);                                     // <= 10^6 - 1 (k <= 52) or <= 1 (k >= 53 ... 73)
+    const unsigned __int128 p = (unsigned __int128)mf * unit;            // < 2^73
+    uint32_t q = (uint32_t)(p >> k);                                     // <= unit - 1 (k <= 52) or <= 1 (k >= 53 ... 73)
     const unsigned __int128 rem = p & ((one << k) - 1), half = one << (k - 1);
     if (rem > half || (rem == half && (q & 1u))) ++q;
-    if (q == 1000000u) {                                 // the carry out of the fraction
+    if (q == unit) {                                     // the carry out of the fraction
         q = 0;
         ++f.ip;
     }
     f.frac = q;
     return f;
 }
+SDPLY_HD Fixed fixed6(double v) { return fixed_dec(v, 1000000u); }
 SDPLY_HD int fixed_len(const Fixed& f) { return (int)f.neg + u32_digits(f.ip) + 7; }
 SDPLY_HD int put_fixed(uint8_t* p, const Fixed& f) {
     int n = 0;

@@ -95,7 +95,7 @@ def run_sequence(load_frames, n_frames: int, step, batch: int = 32, group=None, 
 
 
 def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", workers: int = 0, outputs=None, jpeg: str = "host",
-                       engine=None, png: str | None = None, ply: str | None = None) -> torch.Tensor:
+                       engine=None, png: str | None = None, ply: str | None = None, text: str | None = None) -> torch.Tensor:
     """run_sequence on FILES (semantic_depth_cityscapes_sequence.py:689-701 reads ``sorted(glob(input_folder))`` frame by frame): rank r
     decodes ONLY its shard of the sorted list -- frame_io.FrameFeeder: one native call per batch into pinned staging, upload one batch
     ahead, ``workers`` decode threads (default: this rank's share of the node's CPUs, frame_io.default_decode_workers) -- and hands every
@@ -108,7 +108,9 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     ``png`` ("host" | "device", None = what the SequenceOutputs was built with): where the result images are compressed
     (SequenceOutputs.set_png; "device" needs the step of make_engine_step, which encodes the streams on the GPU).
     ``ply`` ("host" | "device", None = what the SequenceOutputs was built with): where the road PLYs are formatted (SequenceOutputs.set_ply;
-    "device" needs the step of make_engine_step, which formats the text on the GPU)."""
+    "device" needs the step of make_engine_step, which formats the text on the GPU).
+    ``text`` ("json" | "draw", None = what the SequenceOutputs was built with): whether the banner text is rasterised into the result images
+    (SequenceOutputs.set_text; "draw" needs the step of make_engine_step, which draws it on the GPU)."""
     from .frame_io import FrameFeeder
     engine = engine if engine is not None else getattr(step, "engine", None)
     paths = sorted(paths)
@@ -124,6 +126,8 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
             outputs.set_png(png)
         if ply is not None:
             outputs.set_ply(ply)
+        if text is not None:
+            outputs.set_text(text)
         outputs.begin(rank, world, lo, hi)
     try:
         parts = []
@@ -151,7 +155,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
 
 
 def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outputs=None, on_range: str | None = None, png: str | None = None,
-                     ply: str | None = None):
+                     ply: str | None = None, text: str | None = None):
     """``step`` for run_sequence on a real Engine: host or device u8 frames of any size -> (cubic resize to the network shape on
     the GPU, semantic_depth_cityscapes_sequence.py:123-130) -> Engine.process_batch -> record buffer.
     ``camera_of(global_frame_index) -> engine.Camera`` (the sequence tool: cx = 1048.64/4·s, cy = 519.277/4·s, disp_mult = 3800).
@@ -165,7 +169,10 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     zlib streams on the step's stream, right behind the compose launch, and only the streams' bytes travel to the host.
     ``ply`` ("host" | "device", None = what ``outputs`` was built with): with "device" Engine.format_rw_ply turns the final road clouds and
     the records into the text of the ``_rw.ply`` files on the step's stream, and only that text travels to the host (the raw cloud of a
-    frame the device did not format still does: SequenceOutputs)."""
+    frame the device did not format still does: SequenceOutputs).
+    ``text`` ("json" | "draw", None = what ``outputs`` was built with): with "draw" Engine.draw_result_text rasterises the banner text into
+    the composed images on the step's stream, right behind the compose launch -- before Engine.encode_png on the device PNG route, before
+    the copy to the host on the other -- so both routes write it; the ``_overlay.json`` files are written as before."""
     from .engine import RoadWidthParams
     from .recompute import check_mode
 
@@ -176,6 +183,8 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
         outputs.set_png(png)
     if ply is not None and outputs is not None:
         outputs.set_ply(ply)
+    if text is not None and outputs is not None:
+        outputs.set_text(text)
     recomputed: list[int] = []
 
     def note(lo):
@@ -205,6 +214,8 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
         if outputs.images:
             images = engine.compose_result_frames(fr, out["seg"]["road"], out["seg"]["fence"], rec, size[0], size[1], outputs.road_color,
                                                   outputs.fence_color, outputs.alpha)
+            if getattr(outputs, "text", "json") == "draw":         # the banner text, on the step's stream, before either PNG route reads the images
+                engine.draw_result_text(images, rec, outputs.depth)
             if getattr(outputs, "png", "host") == "device":        # the zlib streams right behind the compose launch, on the step's stream
                 outputs.submit(lo, rec, size, final=out.get("road_final"), png_streams=engine.encode_png(images), **more)
                 return rec

@@ -378,6 +378,22 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_compose_result_frames")
         return out
 
+    def draw_result_text(self, images: torch.Tensor, records: torch.Tensor, depth: float) -> torch.Tensor:
+        """the text of the sequence tool's result images (seq:303-336: "At 10.00 m depth:", the two distances to the road's ends and "Road's
+        width: 4.41 m", or the green "Cannot compute ..." line) drawn IN PLACE into u8 [B,h,w,3] device ``images`` (compose_result_frames'
+        output) from ``records`` u8 [B,104] (sd_rw_result), read on the device; ``depth`` is formatted here as "{:.2f}".  The strokes are the
+        project's own font and raster rule (include/semdepth.h; not cv2.putText's pixels), the same pixels outputs.draw_text paints for
+        overlay_items_sequence's items.  Two launches on the current stream, no synchronisation; the workspace is a torch allocation.
+        Returns ``images``."""
+        assert images.dtype == torch.uint8 and images.is_cuda and images.is_contiguous() and images.dim() == 4 and images.shape[3] == 3
+        B, h, w = (int(v) for v in images.shape[:3])
+        assert records.dtype == torch.uint8 and records.is_cuda and records.is_contiguous() and tuple(records.shape) == (B, RW_DTYPE.itemsize)
+        need = self.lib.sd_text_workspace_bytes(B)
+        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_text_draw_rw(self.h, _ptr(images), B, h, w, _ptr(records), "{:.2f}".format(depth).encode(), _ptr(ws), need, self._stream())
+        L.check(self.lib, self.h, st, "sd_text_draw_rw")
+        return images
+
     def encode_png(self, images: torch.Tensor):
         """the device half of the result-image writer (sd_png_encode_bgr): u8 [B,h,w,3] BGR device ``images`` -> (``streams`` u8 [B,stride],
         ``sizes`` i64 [B]) device tensors: frame b's complete zlib stream (Paeth rows, run matches, one dynamic-Huffman block per 32 KiB chunk;

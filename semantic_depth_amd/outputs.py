@@ -2,6 +2,7 @@
 
     write_times / write_distances   <- semantic_depth.py:445-458  (``<name>_times.txt`` / ``<name>_distances.txt``)
     overlay_items / draw_overlay    <- semantic_depth.py:339-406  (banner + the text the reference draws; seq:301-327)
+    draw_text                       <- the cv2.putText calls of :352-401 / seq:313-327 on the project's own stroke font (opt-in, text="draw")
     save_frame_outputs              <- semantic_depth.py:339-441  (``_only_segmentation.png``, the annotated ``.png``, ``_ROAD`` / ``_FENCE`` /
                                        combined / ``_ALL`` PLY files, incl. the three visualisation planes of the combined cloud)
     road_plane_grid / fence_plane_grids <- the ``plane3D`` arrays of :215-219, :294-309 rebuilt through the reference's own pcl call sequence
@@ -11,10 +12,13 @@
                                        ``result_sequence_ply/<name>_rw.ply``), written from the batched driver (distributed.run_sequence_files)
 
 The text files are byte-identical to what the reference's own statements write (tests/test_outputs.py holds fixtures produced
-by executing those statements, extracted from the reference by ``tests/golden/make_golden.py``).  Glyph rendering of
-``cv2.putText`` (Hershey fonts, part of OpenCV) is NOT reproduced: ``draw_overlay`` paints the banner rectangle and returns
+by executing those statements, extracted from the reference by ``tests/golden/make_golden.py``).  The PIXELS of
+``cv2.putText`` (Hershey fonts, part of OpenCV) are NOT reproduced: ``draw_overlay`` paints the banner rectangle and returns
 the text items (string, origin, scale, colour, thickness) the reference passes to putText; they are also written next to the
-image as ``<name>_overlay.json``.
+image as ``<name>_overlay.json``.  By default that is all.  With ``text="draw"`` (save_frame_outputs, SequenceOutputs,
+make_engine_step) the items are also rasterised into the image, with a stroke font and an exact-integer raster rule of the
+project's own (include/semdepth.h, csrc/text_draw.hpp): ``draw_text`` on the host (sd_text_draw_host), Engine.draw_result_text on
+the GPU for the sequence tool.  The strings, origins, scales, colours and thicknesses are the reference's; the glyph shapes are not.
 """
 from __future__ import annotations
 
@@ -109,6 +113,45 @@ def draw_overlay(segmented_frame: np.ndarray, banner, items):
     return img, items
 
 
+def _check_text(text: str) -> str:
+    if text not in ("json", "draw"):
+        raise ValueError(f"text must be 'json' or 'draw', got {text!r}")
+    return text
+
+
+def text_items(items):
+    """overlay_items' dicts as a ctypes array of _lib.sd_text_item: the string's bytes (latin-1, at most 64), org, lround(fontScale * 256),
+    the colour's three values in the order given (the image's channel order), thickness"""
+    from . import _lib as L
+    arr = (L.sd_text_item * max(len(items), 1))()
+    for a, it in zip(arr, items):
+        raw = it["text"].encode("latin-1", "replace")
+        if len(raw) > L.SD_TEXT_MAX_BYTES:
+            raise ValueError(f"draw_text: {it['text']!r} is longer than {L.SD_TEXT_MAX_BYTES} bytes")
+        a.text[:len(raw)] = raw
+        a.len = len(raw)
+        a.org_x, a.org_y = int(it["org"][0]), int(it["org"][1])
+        a.scale_q8 = int(np.floor(float(it["fontScale"]) * 256 + 0.5))
+        a.thickness = int(it["thickness"])
+        a.bgr[:] = [int(c) for c in it["color"]]
+    return arr
+
+
+def draw_text(img: np.ndarray, items) -> np.ndarray:
+    """the cv2.putText calls the items stand for, rasterised into a copy of u8 [h,w,3] ``img`` in list order on the project's own stroke font
+    (sd_text_draw_host: the rule of include/semdepth.h, the pixels Engine.draw_result_text paints on the GPU -- not OpenCV's)."""
+    import ctypes as C
+
+    from . import _lib as L
+    out = np.array(img, dtype=np.uint8, order="C", copy=True)
+    if out.ndim != 3 or out.shape[2] != 3:
+        raise ValueError(f"draw_text: the image must be u8 [h,w,3], got {out.shape}")
+    st = L.load().sd_text_draw_host(out.ctypes.data_as(C.c_void_p), out.shape[0], out.shape[1], text_items(items), len(items))
+    if st != L.SD_OK:
+        raise ValueError(f"draw_text: an item or the image is outside the caps of include/semdepth.h (status {st})")
+    return out
+
+
 def write_png(path: str, img_bgr: np.ndarray, level: int = 3) -> str:
     """8-bit PNG of a BGR (cv2 convention) or single-channel image; filter type 0 rows, one IDAT."""
     a = np.ascontiguousarray(img_bgr, dtype=np.uint8)
@@ -188,11 +231,15 @@ def resize_to_original(segmented_frame: np.ndarray, original_width: int, origina
 
 def save_frame_outputs(output_name: str, res: dict, depth: float, approach: str = "rw", segmented_frame: np.ndarray | None = None,
                        is_city: bool = False, times: dict | None = None, road_plane3D=None, road_colors_plane=None,
-                       points3D_all=None, colors_all=None, original_size: tuple | None = None, params=None, fence_params=None):
+                       points3D_all=None, colors_all=None, original_size: tuple | None = None, params=None, fence_params=None,
+                       text: str = "json"):
     """what FrameProcessor.process_frame writes when --save_data is set (semantic_depth.py:339-458), from the dict
     ``api.FrameProcessor.process_frame(..., want_clouds=True)`` returns.  Returns the list of files written.
     ``original_size`` = (original_height, original_width): the overlay is cubic-resized back to it before anything is drawn (:341);
-    ``params`` / ``fence_params`` (engine.RoadWidthParams / FenceParams): the chain literals the visualisation planes are rebuilt with."""
+    ``params`` / ``fence_params`` (engine.RoadWidthParams / FenceParams): the chain literals the visualisation planes are rebuilt with.
+    ``text``: "json" (default) leaves the banner of the annotated image empty; "draw" rasterises the items into it (draw_text).  The
+    ``_overlay.json`` is written either way."""
+    _check_text(text)
     files = []
     rec = res["record"]
     if not rec["found"]:
@@ -216,6 +263,8 @@ def save_frame_outputs(output_name: str, res: dict, depth: float, approach: str 
         banner, items = overlay_items(w, h, depth, is_city, left_rw, right_rw, dist_rw, "both" if both else "rw",
                                       left_f2f if both else None, right_f2f if both else None, res.get("dist_f2f"))
         img, items = draw_overlay(segmented_frame, banner, items)
+        if text == "draw":
+            img = draw_text(img, items)
         files.append(write_png("{}.png".format(output_name), img))
         with open("{}_overlay.json".format(output_name), "w") as f:
             json.dump(dict(banner=banner, items=items), f)
@@ -406,7 +455,7 @@ class SequenceOutputs:
                                                               (``images``; Engine.compose_result_frames on the GPU, sd_png_encode_bgr_files
                                                               or, with png="device", Engine.encode_png and sd_png_write_streams_files)
         <directory>/result_sequence_imgs/<name>_overlay.json  the banner and the cv2.putText items of overlay_items_sequence (``items``;
-                                                              glyphs are not rasterised, module docstring)
+                                                              rasterised into the image only with text="draw", module docstring)
         <directory>/result_sequence_ply/<name>_rw.ply         the denoised road cloud + the red road-width line (``ply``; rw_ply_bytes)
         <directory>/manifest_rank<r>.json                     written last by close(): the files of this rank and 'ok' / 'range_error' / 'error'
 
@@ -421,16 +470,19 @@ class SequenceOutputs:
     the step hands submit(ply_text=) the finished text of every file (Engine.format_rw_ply); the offsets and flags are copied first, then
     text[:offsets[n]] in one copy, and the host only writes each slice.  A frame the device did not format (a non-zero flag: a non-finite
     coordinate or |v| >= 2^31) has its raw cloud copied and goes through rw_ply_bytes; the manifest names those frames under 'ply_fallback'.
-    Same names and the same bytes."""
+    Same names and the same bytes.
+    ``text``: "json" (default: the banner of the images stays empty, the text is in the ``_overlay.json`` files) or "draw": the step of
+    make_engine_step also rasterises it into the composed images on the GPU (Engine.draw_result_text) before they reach either PNG route."""
 
     def __init__(self, directory: str, names, depth: float = 10.0, images: bool = True, ply: bool | str = True, items: bool = True, level: int = 1,
-                 threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, png: str = "host"):
+                 threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, png: str = "host", text: str = "json"):
         from concurrent.futures import ThreadPoolExecutor
 
         from .frame_io import default_decode_workers
         if not 0 <= level <= 9:
             raise ValueError("PNG compression level must be 0..9")
         self.set_png(png)
+        self.set_text(text)
         self.set_ply("host" if isinstance(ply, bool) else ply)
         self.directory, self.names, self.depth = directory, list(names), float(depth)
         self.images, self.ply, self.items, self.level = bool(images), bool(ply), bool(items), int(level)
@@ -458,6 +510,13 @@ class SequenceOutputs:
         if getattr(self, "_k", 0):
             raise RuntimeError("SequenceOutputs.set_png after the first batch")
         self.png = png
+
+    def set_text(self, text: str):
+        """whether the banner text is drawn into the result images: "json" or "draw" (before the first batch)"""
+        _check_text(text)
+        if getattr(self, "_k", 0):
+            raise RuntimeError("SequenceOutputs.set_text after the first batch")
+        self.text = text
 
     def set_ply(self, ply: str):
         """where the road PLYs are formatted: "host" or "device" (before the first batch; whether they are written at all is ``ply`` of the
