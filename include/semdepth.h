@@ -400,6 +400,59 @@ sd_status sd_text_draw_host(uint8_t* img_host, int h, int w, const sd_text_item*
  * and its advance.  SD_ERR_INVALID: a null pointer or a code outside 0..255. */
 sd_status sd_text_glyph(int code, int8_t* segs_out, int* n_out, int* advance_out);
 
+/* ---- rendered clouds: every frame's road cloud and road-width line drawn to a top-view image on the GPU (opt-in) ----
+ * The reference renders each <name>_rw.ply with Open3D's OpenGL visualiser behind a saved pinhole camera (utils/render_ply.py).  Open3D's
+ * pixels are not reproduced: the project draws z-buffered square points with a rule of its own, stated once, for host and device, in
+ * semantic_depth_amd/csrc/render_rule.hpp.  No pixel identity with Open3D is claimed; no anti-aliasing.
+ *   rows      the rows of the frame's _rw.ply before its filter: the n cloud points in order, then -- when record.found != 0 -- the 1001
+ *             points of the road-width line (the device PLY route's rule above, the same function of ply_format.hpp), colour 250 0 0.  Row
+ *             index i = the cloud index, or n + the line index.
+ *   filter    zmin = the minimum world z over the rows whose three coordinates are all finite; a row is drawn iff its three coordinates are
+ *             finite and z > zmin (every row at the minimum goes).  Non-finite rows are skipped and do not flag the frame.
+ *   camera    sd_render_camera, Open3D's convention (x right, y down, z forward).  Caps: every double finite, z_near > 0, width and
+ *             height 1..SD_RENDER_MAX_EXTENT, point_size 1..SD_RENDER_MAX_POINT.
+ *   project   in doubles, no contraction, in this order: X = ((e00 x + e01 y) + e02 z) + e03, Y and Z likewise from rows 1 and 2 of ext;
+ *             dropped unless Z >= z_near; u = fx (X / Z) + cx, v = fy (Y / Z) + cy; dropped unless -s <= u < width + s and
+ *             -s <= v < height + s, s = point_size (a NaN fails the comparisons; the test comes before any cast); px = (int)floor(u),
+ *             py = (int)floor(v).
+ *   splat     columns px - (s - 1) / 2 .. px + s / 2 and the same range of rows around py (integer divisions), clipped to the image.
+ *   depth     key = ((uint64)bits of (float)Z << 32) | row index.  Z > 0, so the float's bits order as an unsigned integer: a pixel takes
+ *             the colour of the covering row with the smallest key -- the nearest row, and among equal depths the lowest row index.  A
+ *             pixel no row covers takes `background`.
+ *   output    u8 [height,width,3] in BGR, the channel order of sd_compose_result_frames: a cloud colour (r, g, b) is stored b, g, r.
+ * flags      0: rendered.  1: n_dev[b] is outside 0..cap; the image is background only. */
+#define SD_RENDER_MAX_EXTENT 16384
+#define SD_RENDER_MAX_POINT 16
+typedef struct {
+    double ext[12];        /* world -> camera, row-major 3 x 4 */
+    double fx, fy, cx, cy; /* pinhole intrinsics */
+    double z_near;         /* finite, > 0 */
+    int32_t width, height; /* 1..SD_RENDER_MAX_EXTENT */
+    int32_t point_size;    /* 1..SD_RENDER_MAX_POINT */
+    uint8_t background[3]; /* in the image's channel order */
+    uint8_t reserved;      /* 0 */
+} sd_render_camera;
+/* the device workspace sd_render_rw needs for B frames of clouds of `cap` points behind this camera: the depth keys, 8 bytes per pixel per
+ * frame, and the minimum-z slots.  SD_ERR_INVALID for B < 1, B > 65535, cap < 0, a null pointer or a camera outside the caps. */
+sd_status sd_render_workspace(int B, int cap, const sd_render_camera* cam_host, size_t* workspace_bytes);
+/* DEVICE: xyz f32 [B,cap,3], rgb u8 [B,cap,3], n i32 [B] (sd_road_width's final clouds) and records [B] -> dst_dev u8 [B,height,width,3] BGR,
+ * every byte written, and flags_dev i32 [B].  The camera is read on the HOST and passed by value to the kernels.  Five launches on `stream`
+ * (minimum z per 256-row block; per frame, with the flags; the keys cleared to all ones; one lane per row projects it once and issues a
+ * 64-bit integer atomic minimum per covered pixel; one lane per four pixels resolves the keys to colours and stores three aligned words), no
+ * host synchronisation, no floating-point atomics: the minimum of integers does not depend on the order in which workgroups arrive, and
+ * every workspace byte that is read was written by the same call.  The handle need not be bound.  SD_ERR_INVALID, nothing launched: a null
+ * pointer, B < 1, B > 65535, cap < 0, a camera outside the caps or with a non-finite field, workspace_bytes below sd_render_workspace, a
+ * workspace that is not 16-byte aligned, records_dev not 8-byte aligned, xyz_dev, n_dev, flags_dev or dst_dev not 4-byte aligned. */
+sd_status sd_render_rw(sd_handle* h, const float* xyz_dev, const uint8_t* rgb_dev, const int32_t* n_dev, int B, int cap,
+                       const sd_rw_result* records_dev, const sd_render_camera* cam_host, uint8_t* dst_dev, int32_t* flags_dev,
+                       void* workspace_dev, size_t workspace_bytes, void* stream);
+/* HOST: the CPU statement of sd_render_rw for one frame (xyz f32 [n,3], rgb u8 [n,3], one record; the cloud's capacity is n): one plain loop
+ * over the rows with a host key buffer -> out_host u8 [height,width,3], *flag_out = 0.  n < 0 stands for a count outside the cloud:
+ * *flag_out = 1 and the image is background only.  SD_ERR_INVALID, nothing written: a null pointer (xyz_host and rgb_host may be null for
+ * n <= 0) or a camera outside the caps. */
+sd_status sd_render_rw_host(const float* xyz_host, const uint8_t* rgb_host, int n, const sd_rw_result* record, const sd_render_camera* cam,
+                            uint8_t* out_host, int32_t* flag_out);
+
 /* DepthFrame.post_processing alone, semantic_depth.py:656-664: disp_raw f32 [B,2,H,W] -> disp_pp f32 [B,H,W] */
 sd_status sd_post_process(sd_handle* h, const float* disp_raw, int B, float* disp_pp, void* stream);
 

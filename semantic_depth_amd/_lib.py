@@ -17,6 +17,7 @@ SD_ENC_VGG, SD_ENC_RESNET50 = 0, 1
 SD_NET_FCN8S, SD_NET_MONODEPTH = 0, 1
 SD_PLY_ROW_CAP, SD_PLY_HEADER_CAP, SD_PLY_LINE_ROWS = 69, 209, 1001
 SD_TEXT_MAX_BYTES, SD_TEXT_MAX_SEGS, SD_TEXT_MAX_ITEMS, SD_TEXT_MAX_SCALE_Q8, SD_TEXT_MAX_THICKNESS, SD_TEXT_MAX_ORG = 64, 32, 4, 4096, 32, 32768
+SD_RENDER_MAX_EXTENT, SD_RENDER_MAX_POINT = 16384, 16
 SD_PREC_F32, SD_PREC_BF16X2, SD_PREC_MIXED, SD_PREC_PLAN, SD_PREC_BF16X3, SD_PREC_F16X2 = 0, 1, 2, 3, 4, 5
 
 
@@ -40,6 +41,12 @@ class sd_rw_result(C.Structure):
 class sd_text_item(C.Structure):
     _fields_ = [("text", C.c_uint8 * 64), ("len", C.c_int32), ("org_x", C.c_int32), ("org_y", C.c_int32), ("scale_q8", C.c_int32),
                 ("thickness", C.c_int32), ("bgr", C.c_uint8 * 3), ("reserved", C.c_uint8)]
+
+
+class sd_render_camera(C.Structure):
+    _fields_ = [("ext", C.c_double * 12), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("z_near", C.c_double), ("width", C.c_int32), ("height", C.c_int32), ("point_size", C.c_int32),
+                ("background", C.c_uint8 * 3), ("reserved", C.c_uint8)]
 
 
 class sd_f2f_params(C.Structure):
@@ -116,6 +123,9 @@ SIGNATURES = {
     "sd_text_items_rw_host": (C.c_int, [C.POINTER(sd_rw_result), C.c_char_p, C.c_int, C.c_int, C.POINTER(sd_text_item), C.POINTER(C.c_int)]),
     "sd_text_draw_host": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(sd_text_item), C.c_int]),
     "sd_text_glyph": (C.c_int, [C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "sd_render_workspace": (C.c_int, [C.c_int, C.c_int, C.POINTER(sd_render_camera), C.POINTER(C.c_size_t)]),
+    "sd_render_rw": (C.c_int, [_H, _P, _P, _P, C.c_int, C.c_int, _P, C.POINTER(sd_render_camera), _P, _P, _P, C.c_size_t, _P]),
+    "sd_render_rw_host": (C.c_int, [_P, _P, C.c_int, C.POINTER(sd_rw_result), C.POINTER(sd_render_camera), _P, C.POINTER(C.c_int32)]),
     "sd_post_process": (C.c_int, [_H, _P, C.c_int, _P, _P]),
     "sd_resize_cubic_u8": (C.c_int, [_H, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
     "sd_compose_result_frames": (C.c_int, [_H, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),

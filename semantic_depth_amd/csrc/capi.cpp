@@ -16,6 +16,7 @@
 #include "png_gpu.hpp"
 #include "ply_gpu.hpp"
 #include "text_gpu.hpp"
+#include "render_gpu.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -840,6 +841,33 @@ sd_status sd_text_draw_rw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int 
         return fail(h, SD_ERR_INVALID, "sd_text_draw_rw: workspace_dev must be 16-byte, records_dev 8-byte aligned");
     HIPCHK(h, launch_text_draw_rw(dst_dev, B, dst_h, dst_w, records_dev, reinterpret_cast<const uint8_t*>(depth_text), (int)dlen,
                                   static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
+    return SD_OK;
+}
+
+sd_status sd_render_workspace(int B, int cap, const sd_render_camera* cam_host, size_t* workspace_bytes) {
+    if (B < 1 || B > 65535 || cap < 0 || cap > kPlyMaxCap || !cam_host || !workspace_bytes || !sdrender::valid_camera(*cam_host)) return SD_ERR_INVALID;
+    *workspace_bytes = render_workspace_bytes(B, cap, *cam_host);
+    return SD_OK;
+}
+
+sd_status sd_render_rw(sd_handle* h, const float* xyz_dev, const uint8_t* rgb_dev, const int32_t* n_dev, int B, int cap,
+                       const sd_rw_result* records_dev, const sd_render_camera* cam_host, uint8_t* dst_dev, int32_t* flags_dev,
+                       void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!h || !xyz_dev || !rgb_dev || !n_dev || !records_dev || !cam_host || !dst_dev || !flags_dev || !workspace_dev)
+        return fail(h, SD_ERR_INVALID, "sd_render_rw: null pointer");
+    if (B < 1 || B > 65535 || cap < 0 || cap > kPlyMaxCap) return fail(h, SD_ERR_INVALID, "sd_render_rw: B must be 1..65535, cap >= 0");
+    const sd_render_camera cam = *cam_host;           // read once, here: the kernels get this copy by value
+    if (!sdrender::valid_camera(cam))
+        return fail(h, SD_ERR_INVALID, "sd_render_rw: camera outside the caps (finite fields, z_near > 0, extents 1..16384, point_size 1..16)");
+    // every index the kernels form follows from B, cap, the camera's extents and this capacity: nothing is launched otherwise
+    if (workspace_bytes < render_workspace_bytes(B, cap, cam))
+        return fail(h, SD_ERR_INVALID, "sd_render_rw: workspace smaller than sd_render_workspace reports");
+    if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(records_dev) & 7) ||
+        (reinterpret_cast<uintptr_t>(flags_dev) & 3) || (reinterpret_cast<uintptr_t>(xyz_dev) & 3) || (reinterpret_cast<uintptr_t>(n_dev) & 3) ||
+        (reinterpret_cast<uintptr_t>(dst_dev) & 3))
+        return fail(h, SD_ERR_INVALID, "sd_render_rw: workspace_dev must be 16-byte, records_dev 8-byte, xyz_dev, n_dev, flags_dev and dst_dev 4-byte aligned");
+    HIPCHK(h, launch_render_rw(xyz_dev, rgb_dev, n_dev, B, cap, records_dev, cam, dst_dev, flags_dev, static_cast<uint8_t*>(workspace_dev),
+                               (hipStream_t)stream));
     return SD_OK;
 }
 

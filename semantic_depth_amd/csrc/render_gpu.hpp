@@ -1,0 +1,22 @@
+// rendered clouds on the device (render_gpu.hip): launcher and workspace layout, used by capi.cpp
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "../../include/semdepth.h"
+#include "render_rule.hpp"
+
+namespace sd {
+
+// workspace of B frames: the depth keys u64 [B,height,width] first (16-byte aligned with the workspace), then per 256-row block its minimum
+// z (f64) and per frame the minimum z (f64)
+inline size_t render_key_count(int B, const sd_render_camera& cam) { return (size_t)B * (size_t)cam.height * (size_t)cam.width; }
+inline size_t render_workspace_bytes(int B, int cap, const sd_render_camera& cam) {
+    return (render_key_count(B, cam) + (size_t)B * sdply::blocks_per_frame(cap) + (size_t)B) * sizeof(uint64_t) + 64;
+}
+
+// xyz f32 [B,cap,3], rgb u8 [B,cap,3], n i32 [B], records [B] -> dst u8 [B,height,width,3] BGR, flags i32 [B].  The caller has checked B, cap,
+// the camera, the pointers and the workspace.  Five launches on s, no synchronisation.
+hipError_t launch_render_rw(const float* xyz, const uint8_t* rgb, const int32_t* n, int B, int cap, const sd_rw_result* records,
+                            const sd_render_camera& cam, uint8_t* dst, int32_t* flags, uint8_t* workspace, hipStream_t s);
+
+}  // namespace sd

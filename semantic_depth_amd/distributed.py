@@ -95,7 +95,7 @@ def run_sequence(load_frames, n_frames: int, step, batch: int = 32, group=None, 
 
 
 def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", workers: int = 0, outputs=None, jpeg: str = "host",
-                       engine=None, png: str | None = None, ply: str | None = None, text: str | None = None) -> torch.Tensor:
+                       engine=None, png: str | None = None, ply: str | None = None, text: str | None = None, render=None) -> torch.Tensor:
     """run_sequence on FILES (semantic_depth_cityscapes_sequence.py:689-701 reads ``sorted(glob(input_folder))`` frame by frame): rank r
     decodes ONLY its shard of the sorted list -- frame_io.FrameFeeder: one native call per batch into pinned staging, upload one batch
     ahead, ``workers`` decode threads (default: this rank's share of the node's CPUs, frame_io.default_decode_workers) -- and hands every
@@ -110,7 +110,9 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     ``ply`` ("host" | "device", None = what the SequenceOutputs was built with): where the road PLYs are formatted (SequenceOutputs.set_ply;
     "device" needs the step of make_engine_step, which formats the text on the GPU).
     ``text`` ("json" | "draw", None = what the SequenceOutputs was built with): whether the banner text is rasterised into the result images
-    (SequenceOutputs.set_text; "draw" needs the step of make_engine_step, which draws it on the GPU)."""
+    (SequenceOutputs.set_text; "draw" needs the step of make_engine_step, which draws it on the GPU).
+    ``render`` (an outputs.RenderCamera, None = what the SequenceOutputs was built with): the view every frame's road cloud is rendered from
+    (SequenceOutputs.set_render; needs the step of make_engine_step, which renders on the GPU)."""
     from .frame_io import FrameFeeder
     engine = engine if engine is not None else getattr(step, "engine", None)
     paths = sorted(paths)
@@ -128,6 +130,8 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
             outputs.set_ply(ply)
         if text is not None:
             outputs.set_text(text)
+        if render is not None:
+            outputs.set_render(render)
         outputs.begin(rank, world, lo, hi)
     try:
         parts = []
@@ -155,7 +159,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
 
 
 def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outputs=None, on_range: str | None = None, png: str | None = None,
-                     ply: str | None = None, text: str | None = None):
+                     ply: str | None = None, text: str | None = None, render=None):
     """``step`` for run_sequence on a real Engine: host or device u8 frames of any size -> (cubic resize to the network shape on
     the GPU, semantic_depth_cityscapes_sequence.py:123-130) -> Engine.process_batch -> record buffer.
     ``camera_of(global_frame_index) -> engine.Camera`` (the sequence tool: cx = 1048.64/4·s, cy = 519.277/4·s, disp_mult = 3800).
@@ -172,7 +176,10 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     frame the device did not format still does: SequenceOutputs).
     ``text`` ("json" | "draw", None = what ``outputs`` was built with): with "draw" Engine.draw_result_text rasterises the banner text into
     the composed images on the step's stream, right behind the compose launch -- before Engine.encode_png on the device PNG route, before
-    the copy to the host on the other -- so both routes write it; the ``_overlay.json`` files are written as before."""
+    the copy to the host on the other -- so both routes write it; the ``_overlay.json`` files are written as before.
+    ``render`` (an outputs.RenderCamera, None = what ``outputs`` was built with): with a camera process_batch keeps the final road clouds even
+    when no PLY is asked for, and Engine.render_rw draws them and the road-width line behind that camera on the step's stream, behind the road
+    chain; the ``<name>_render.png`` files go through the PNG route chosen (png="device": Engine.encode_png on the renders)."""
     from .engine import RoadWidthParams
     from .recompute import check_mode
 
@@ -185,6 +192,8 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
         outputs.set_ply(ply)
     if text is not None and outputs is not None:
         outputs.set_text(text)
+    if render is not None and outputs is not None:
+        outputs.set_render(render)
     recomputed: list[int] = []
 
     def note(lo):
@@ -204,22 +213,29 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
             rec = engine.process_batch(fr, cams, prm, approach=approach)["records"]
             note(lo)
             return rec
-        out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.ply)
+        camera = getattr(outputs, "render", None)
+        out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.ply or camera is not None)
         note(lo)
         rec = out["records"]
         images = None
         more = {}
         if outputs.ply and getattr(outputs, "ply_route", "host") == "device":     # the text of the PLY files, on the step's stream
             more["ply_text"] = engine.format_rw_ply(out["road_final"], rec)
+        if camera is not None:                                     # the rendered clouds, on the step's stream, behind the road chain
+            renders = engine.render_rw(out["road_final"], rec, camera)[0]
+            if getattr(outputs, "png", "host") == "device":
+                more["render_streams"] = engine.encode_png(renders)
+            else:
+                more["renders"] = renders
         if outputs.images:
             images = engine.compose_result_frames(fr, out["seg"]["road"], out["seg"]["fence"], rec, size[0], size[1], outputs.road_color,
                                                   outputs.fence_color, outputs.alpha)
             if getattr(outputs, "text", "json") == "draw":         # the banner text, on the step's stream, before either PNG route reads the images
                 engine.draw_result_text(images, rec, outputs.depth)
             if getattr(outputs, "png", "host") == "device":        # the zlib streams right behind the compose launch, on the step's stream
-                outputs.submit(lo, rec, size, final=out.get("road_final"), png_streams=engine.encode_png(images), **more)
+                outputs.submit(lo, rec, size, final=out.get("road_final") if outputs.ply else None, png_streams=engine.encode_png(images), **more)
                 return rec
-        outputs.submit(lo, rec, size, images=images, final=out.get("road_final"), **more)
+        outputs.submit(lo, rec, size, images=images, final=out.get("road_final") if outputs.ply else None, **more)
         return rec
 
     # ('recompute': every clamp in a stored output is attributed to its frame and that frame recomputed, so the step has no verdict left

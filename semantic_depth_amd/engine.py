@@ -447,6 +447,35 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_ply_format_rw")
         return out[:capacity], offsets, flags
 
+    def render_rw(self, final: dict, records: torch.Tensor, camera, out: torch.Tensor | None = None):
+        """the rendered view of every frame's ``_rw.ply`` (sd_render_rw): ``final`` = process_batch(want_final=True)'s road_final (xyz f32
+        [B,cap,3], rgb u8 [B,cap,3], n i32 [B]), ``records`` u8 [B,104] (sd_rw_result) and ``camera`` (outputs.RenderCamera) -> (``images`` u8
+        [B,height,width,3] BGR, ``flags`` i32 [B]) device tensors: the n cloud points and, on a found frame, the 1001 points of the road-width
+        line, behind the file's minimum-z filter, as z-buffered squares of ``camera.point_size`` pixels (the rule of include/semdepth.h; the
+        bytes of outputs.render_rw, not Open3D's pixels).  flags[b] = 1: n[b] is outside 0..cap and the image is background only.  Five
+        launches on the current stream, no synchronisation; the workspace (8 bytes per pixel per frame) is a torch allocation."""
+        xyz, rgb, n = final["xyz"], final.get("rgb"), final["n"]
+        if rgb is None:
+            raise ValueError("render_rw needs the colours of the road cloud (final['rgb'] is None)")
+        assert xyz.dtype == torch.float32 and xyz.is_cuda and xyz.is_contiguous() and xyz.dim() == 3 and xyz.shape[2] == 3
+        B, cap = int(xyz.shape[0]), int(xyz.shape[1])
+        assert rgb.dtype == torch.uint8 and rgb.is_cuda and rgb.is_contiguous() and tuple(rgb.shape) == (B, cap, 3)
+        assert n.dtype == torch.int32 and n.is_cuda and n.is_contiguous() and tuple(n.shape) == (B,)
+        assert records.dtype == torch.uint8 and records.is_cuda and records.is_contiguous() and tuple(records.shape) == (B, RW_DTYPE.itemsize)
+        cam = camera.struct()
+        need = C.c_size_t()
+        st = self.lib.sd_render_workspace(B, cap, C.byref(cam), C.byref(need))
+        L.check(self.lib, None, st, "sd_render_workspace")
+        if out is None:
+            out = torch.empty((B, cam.height, cam.width, 3), dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, cam.height, cam.width, 3), out.shape
+        flags = torch.empty((B,), dtype=torch.int32, device=self.device)
+        ws = torch.empty((need.value,), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_render_rw(self.h, _ptr(xyz), _ptr(rgb), _ptr(n), B, cap, _ptr(records), C.byref(cam), _ptr(out), _ptr(flags), _ptr(ws), need.value,
+                                   self._stream())
+        L.check(self.lib, self.h, st, "sd_render_rw")
+        return out, flags
+
     def post_process(self, disp_raw: torch.Tensor):
         B = disp_raw.shape[0]
         assert disp_raw.dtype == torch.float32 and tuple(disp_raw.shape[1:]) == (2, self.H, self.W) and disp_raw.is_contiguous()

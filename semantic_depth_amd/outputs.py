@@ -2,6 +2,8 @@
 
     write_times / write_distances   <- semantic_depth.py:445-458  (``<name>_times.txt`` / ``<name>_distances.txt``)
     overlay_items / draw_overlay    <- semantic_depth.py:339-406  (banner + the text the reference draws; seq:301-327)
+    render_rw / RenderCamera        <- utils/render_ply.py (every _rw.ply behind a saved Open3D pinhole camera) as z-buffered square points
+                                       with a rule of the project's own (opt-in, render=camera; not Open3D's OpenGL pixels)
     draw_text                       <- the cv2.putText calls of :352-401 / seq:313-327 on the project's own stroke font (opt-in, text="draw")
     save_frame_outputs              <- semantic_depth.py:339-441  (``_only_segmentation.png``, the annotated ``.png``, ``_ROAD`` / ``_FENCE`` /
                                        combined / ``_ALL`` PLY files, incl. the three visualisation planes of the combined cloud)
@@ -22,6 +24,7 @@ the GPU for the sequence tool.  The strings, origins, scales, colours and thickn
 """
 from __future__ import annotations
 
+import dataclasses
 import json
 import os
 import struct
@@ -152,6 +155,111 @@ def draw_text(img: np.ndarray, items) -> np.ndarray:
     return out
 
 
+# ------------------------------------------------------------------------------------------------ rendered clouds
+@dataclasses.dataclass(frozen=True)
+class RenderCamera:
+    """the pinhole camera of the rendered clouds (sd_render_camera, include/semdepth.h): ``ext`` = world -> camera, row-major 3 x 4 (twelve
+    numbers; Open3D's convention: x right, y down, z forward), the intrinsics, the near plane, the image size, the side of a point's square in
+    pixels and the background in the image's channel order.  point_size 5 and a white background are Open3D's defaults."""
+    ext: tuple
+    fx: float
+    fy: float
+    cx: float
+    cy: float
+    width: int
+    height: int
+    z_near: float = 0.1
+    point_size: int = 5
+    background: tuple = (255, 255, 255)
+
+    def __post_init__(self):
+        object.__setattr__(self, "ext", tuple(float(v) for v in np.asarray(self.ext, np.float64).reshape(-1)))
+        object.__setattr__(self, "background", tuple(int(v) for v in self.background))
+        if len(self.ext) != 12 or len(self.background) != 3:
+            raise ValueError("RenderCamera: ext holds twelve numbers (3 x 4, row-major), background three")
+
+    def struct(self):
+        """the camera as a _lib.sd_render_camera"""
+        from . import _lib as L
+        c = L.sd_render_camera()
+        c.ext[:] = self.ext
+        c.fx, c.fy, c.cx, c.cy, c.z_near = float(self.fx), float(self.fy), float(self.cx), float(self.cy), float(self.z_near)
+        c.width, c.height, c.point_size = int(self.width), int(self.height), int(self.point_size)
+        c.background[:] = self.background
+        return c
+
+    @classmethod
+    def from_open3d_json(cls, path: str, z_near: float = 0.1, point_size: int = 5, background=(255, 255, 255)) -> "RenderCamera":
+        """Open3D's PinholeCameraParameters file (write_pinhole_camera_parameters; the reference's ``top.json``): ``extrinsic`` = 16 numbers,
+        the 4 x 4 world -> camera matrix COLUMN by column, ``intrinsic.intrinsic_matrix`` = 9 numbers, column by column, and
+        ``intrinsic.width`` / ``height``.  The file has no near plane, point size or background: they are arguments."""
+        with open(path) as f:
+            d = json.load(f)
+        e = np.asarray(d["extrinsic"], np.float64).reshape(4, 4).T
+        k = np.asarray(d["intrinsic"]["intrinsic_matrix"], np.float64).reshape(3, 3).T
+        return cls(ext=tuple(e[:3].reshape(-1)), fx=float(k[0, 0]), fy=float(k[1, 1]), cx=float(k[0, 2]), cy=float(k[1, 2]),
+                   width=int(d["intrinsic"]["width"]), height=int(d["intrinsic"]["height"]), z_near=z_near, point_size=point_size,
+                   background=tuple(background))
+
+    def to_open3d_json(self, path: str) -> str:
+        """the same file; read_pinhole_camera_parameters of Open3D takes it"""
+        e = np.concatenate([np.asarray(self.ext, np.float64).reshape(3, 4), [[0.0, 0.0, 0.0, 1.0]]])
+        k = np.array([[self.fx, 0.0, self.cx], [0.0, self.fy, self.cy], [0.0, 0.0, 1.0]])
+        with open(path, "w") as f:
+            json.dump({"class_name": "PinholeCameraParameters", "extrinsic": [float(v) for v in e.T.reshape(-1)],
+                       "intrinsic": {"height": int(self.height), "intrinsic_matrix": [float(v) for v in k.T.reshape(-1)], "width": int(self.width)},
+                       "version_major": 1, "version_minor": 0}, f, indent=1)
+        return path
+
+
+def top_camera(width: int = 512, height: int = 512, centre=(0.0, 0.0, 20.0), altitude: float = 40.0, fov_deg: float = 60.0, z_near: float = 0.1,
+               point_size: int = 5, background=(255, 255, 255)) -> RenderCamera:
+    """a top view of the road (the reference ships no ``top.json``): the camera sits at ``centre`` - altitude * (world y) -- world y points
+    down, so that is above the road -- and looks along +y; image x is world x and image up is world +z, so far is at the top.
+    fx = fy = (width / 2) / tan(fov / 2), cx = width / 2 - 0.5, cy = height / 2 - 0.5: ``centre`` lands on the central pixel."""
+    c = np.asarray(centre, np.float64)
+    rot = np.array([[1.0, 0.0, 0.0], [0.0, 0.0, -1.0], [0.0, 1.0, 0.0]])       # rows: the camera's x (world x), y (down = world -z), z (world +y)
+    pos = c - float(altitude) * np.array([0.0, 1.0, 0.0])
+    ext = np.concatenate([rot, (-rot @ pos)[:, None]], axis=1)
+    f = (width / 2.0) / np.tan(np.deg2rad(fov_deg) / 2.0)
+    return RenderCamera(ext=tuple(ext.reshape(-1)), fx=float(f), fy=float(f), cx=width / 2.0 - 0.5, cy=height / 2.0 - 0.5, width=int(width),
+                        height=int(height), z_near=z_near, point_size=point_size, background=tuple(background))
+
+
+def _check_render(render):
+    if render is not None and not isinstance(render, RenderCamera):
+        raise ValueError(f"render must be None or an outputs.RenderCamera, got {render!r}")
+    return render
+
+
+def render_rw(xyz, rgb, left_pt=None, right_pt=None, camera: RenderCamera | None = None, return_flag: bool = False):
+    """the rendered view of one frame's ``_rw.ply`` on the host (sd_render_rw_host: the rule of include/semdepth.h, the pixels
+    Engine.render_rw draws on the GPU -- not Open3D's): ``xyz`` [n,3] and ``rgb`` [n,3] of the final road cloud (taken as f32 / u8),
+    ``left_pt`` / ``right_pt`` the end points of the road-width line or None when none was found -> u8 [height,width,3] BGR."""
+    import ctypes as C
+
+    from . import _lib as L
+    from .engine import RW_DTYPE
+    if camera is None:
+        camera = top_camera()
+    _check_render(camera)
+    p = np.ascontiguousarray(np.asarray(xyz, np.float32).reshape(-1, 3))
+    c = np.ascontiguousarray(np.asarray(rgb, np.uint8).reshape(-1, 3))
+    if len(p) != len(c):
+        raise ValueError(f"render_rw: {len(p)} points and {len(c)} colours")
+    rec = np.zeros((), RW_DTYPE)
+    if left_pt is not None and right_pt is not None:
+        rec["found"] = 1
+        rec["left_pt"], rec["right_pt"] = np.asarray(left_pt, np.float32).reshape(3), np.asarray(right_pt, np.float32).reshape(3)
+    out = np.empty((camera.height, camera.width, 3), np.uint8)
+    flag = C.c_int32()
+    st = L.load().sd_render_rw_host(p.ctypes.data_as(C.c_void_p), c.ctypes.data_as(C.c_void_p), len(p), C.byref(L.sd_rw_result.from_buffer_copy(rec.tobytes())),
+                                    C.byref(camera.struct()), out.ctypes.data_as(C.c_void_p), C.byref(flag))
+    if st != L.SD_OK:
+        raise ValueError(f"render_rw: the camera is outside the caps of include/semdepth.h (status {st})")
+    return (out, flag.value) if return_flag else out
+
+
 def write_png(path: str, img_bgr: np.ndarray, level: int = 3) -> str:
     """8-bit PNG of a BGR (cv2 convention) or single-channel image; filter type 0 rows, one IDAT."""
     a = np.ascontiguousarray(img_bgr, dtype=np.uint8)
@@ -232,14 +340,17 @@ def resize_to_original(segmented_frame: np.ndarray, original_width: int, origina
 def save_frame_outputs(output_name: str, res: dict, depth: float, approach: str = "rw", segmented_frame: np.ndarray | None = None,
                        is_city: bool = False, times: dict | None = None, road_plane3D=None, road_colors_plane=None,
                        points3D_all=None, colors_all=None, original_size: tuple | None = None, params=None, fence_params=None,
-                       text: str = "json"):
+                       text: str = "json", render: RenderCamera | None = None):
     """what FrameProcessor.process_frame writes when --save_data is set (semantic_depth.py:339-458), from the dict
     ``api.FrameProcessor.process_frame(..., want_clouds=True)`` returns.  Returns the list of files written.
     ``original_size`` = (original_height, original_width): the overlay is cubic-resized back to it before anything is drawn (:341);
     ``params`` / ``fence_params`` (engine.RoadWidthParams / FenceParams): the chain literals the visualisation planes are rebuilt with.
     ``text``: "json" (default) leaves the banner of the annotated image empty; "draw" rasterises the items into it (draw_text).  The
-    ``_overlay.json`` is written either way."""
+    ``_overlay.json`` is written either way.
+    ``render``: None (default) or a RenderCamera: also ``<output_name>_render.png``, the final road cloud and the road-width line of the
+    record behind that camera (render_rw, the host statement of the sequence tool's rendered clouds)."""
     _check_text(text)
+    _check_render(render)
     files = []
     rec = res["record"]
     if not rec["found"]:
@@ -269,6 +380,8 @@ def save_frame_outputs(output_name: str, res: dict, depth: float, approach: str 
         with open("{}_overlay.json".format(output_name), "w") as f:
             json.dump(dict(banner=banner, items=items), f)
         files.append("{}_overlay.json".format(output_name))
+    if render is not None:
+        files.append(write_png("{}_render.png".format(output_name), render_rw(res["road3D_final"], res["road_colors_final"], rec["left_pt"], rec["right_pt"], render)))
     road3D, road_colors = res["road3D_final"].astype(np.float64), res["road_colors_final"]
     pc = PointCloud2Ply(road3D, road_colors, "{}_ROAD".format(output_name))                 # :408-410
     pc.prepare_and_save_point_cloud()
@@ -379,6 +492,7 @@ def focal_sweep(process, input_frames: dict, frame_depther, focal_lengths=(380, 
 
 # ------------------------------------------------------------------------------------------------ the sequence tool's files
 SEQ_IMG_DIR, SEQ_PLY_DIR = "result_sequence_imgs", "result_sequence_ply"          # semantic_depth_cityscapes_sequence.py:671-680
+SEQ_RENDER_DIR = "rendered_sequence"                                              # utils/render_ply.py's output folder
 
 
 def sequence_names(paths) -> list:
@@ -457,6 +571,7 @@ class SequenceOutputs:
         <directory>/result_sequence_imgs/<name>_overlay.json  the banner and the cv2.putText items of overlay_items_sequence (``items``;
                                                               rasterised into the image only with text="draw", module docstring)
         <directory>/result_sequence_ply/<name>_rw.ply         the denoised road cloud + the red road-width line (``ply``; rw_ply_bytes)
+        <directory>/rendered_sequence/<name>_render.png       only with render=: the top view of the _rw.ply's rows (``render``)
         <directory>/manifest_rank<r>.json                     written last by close(): the files of this rank and 'ok' / 'range_error' / 'error'
 
     ``names``: output names of the WHOLE sorted frame list (sequence_names), indexed by global frame index.  submit() takes the device
@@ -472,10 +587,15 @@ class SequenceOutputs:
     coordinate or |v| >= 2^31) has its raw cloud copied and goes through rw_ply_bytes; the manifest names those frames under 'ply_fallback'.
     Same names and the same bytes.
     ``text``: "json" (default: the banner of the images stays empty, the text is in the ``_overlay.json`` files) or "draw": the step of
-    make_engine_step also rasterises it into the composed images on the GPU (Engine.draw_result_text) before they reach either PNG route."""
+    make_engine_step also rasterises it into the composed images on the GPU (Engine.draw_result_text) before they reach either PNG route.
+    ``render``: None (default: nothing more is written, the manifest is what it was) or a RenderCamera: the step of make_engine_step also
+    draws every frame's final road cloud and road-width line behind that camera on the GPU (Engine.render_rw, submit(renders=) or, with
+    png="device", submit(render_streams=)) and the writer stores ``<name>_render.png`` through the PNG route chosen; the manifest names
+    those files under 'render'."""
 
     def __init__(self, directory: str, names, depth: float = 10.0, images: bool = True, ply: bool | str = True, items: bool = True, level: int = 1,
-                 threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, png: str = "host", text: str = "json"):
+                 threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, png: str = "host", text: str = "json",
+                 render: RenderCamera | None = None):
         from concurrent.futures import ThreadPoolExecutor
 
         from .frame_io import default_decode_workers
@@ -484,11 +604,13 @@ class SequenceOutputs:
         self.set_png(png)
         self.set_text(text)
         self.set_ply("host" if isinstance(ply, bool) else ply)
+        self.set_render(render)
         self.directory, self.names, self.depth = directory, list(names), float(depth)
         self.images, self.ply, self.items, self.level = bool(images), bool(ply), bool(items), int(level)
         self.road_color, self.fence_color, self.alpha = tuple(road_color), tuple(fence_color), int(alpha)
         self.threads = threads if threads > 0 else default_decode_workers()
         self.img_dir, self.ply_dir = os.path.join(directory, SEQ_IMG_DIR), os.path.join(directory, SEQ_PLY_DIR)
+        self.render_dir = os.path.join(directory, SEQ_RENDER_DIR)
         for d, on in ((self.img_dir, self.images or self.items), (self.ply_dir, self.ply)):
             if on:
                 os.makedirs(d, exist_ok=True)
@@ -527,16 +649,24 @@ class SequenceOutputs:
             raise RuntimeError("SequenceOutputs.set_ply after the first batch")
         self.ply_route = ply
 
+    def set_render(self, render):
+        """whether the road clouds are rendered: None or the RenderCamera of the view (before the first batch)"""
+        _check_render(render)
+        if getattr(self, "_k", 0):
+            raise RuntimeError("SequenceOutputs.set_render after the first batch")
+        self.render = render
+
     def begin(self, rank: int, world: int, lo: int, hi: int):
         """the shard [lo, hi) this rank writes (run_sequence_files calls it before the first batch)"""
         self.rank, self.world, self.shard = int(rank), int(world), (int(lo), int(hi))
 
-    def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None, ply_text=None):
+    def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None, ply_text=None, renders=None, render_streams=None):
         """one batch: ``records`` u8 [n,104] (sd_rw_result), ``size`` = (h, w) of the original frames, ``images`` u8 [n,h,w,3] (the composed
         result images) or None, ``final`` = dict(xyz f32 [n,cap,3], rgb u8 [n,cap,3], n i32 [n]) (process_batch(want_final=True)'s
         road_final) or None, ``png_streams`` = (streams u8 [n,stride], sizes i64 [n]) of Engine.encode_png in place of ``images`` on the
         device route, ``ply_text`` = (text u8 [capacity], offsets i64 [n+1], flags i32 [n]) of Engine.format_rw_ply on the ply="device" route
-        (beside ``final``, which the flagged frames are written from).  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
+        (beside ``final``, which the flagged frames are written from), ``renders`` = u8 [n,height,width,3] of Engine.render_rw with render= (or
+        ``render_streams`` = Engine.encode_png of them on the png="device" route).  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
         tensors of every step)."""
         import torch
         if self.manifest is not None:
@@ -550,6 +680,14 @@ class SequenceOutputs:
             raise ValueError("SequenceOutputs: ply='device' needs the text of Engine.format_rw_ply (submit(ply_text=))")
         if not self.ply or self.ply_route != "device":
             ply_text = None
+        if self.render is not None and (render_streams if self.png == "device" else renders) is None:
+            raise ValueError("SequenceOutputs: render= needs the images of Engine.render_rw (submit(renders=); png='device': render_streams=)")
+        if self.render is None:
+            renders = render_streams = None
+        elif self.png == "device":
+            renders = None
+        else:
+            render_streams = None
         while len(self._jobs) >= 2:                                    # at most two batches in flight
             self._files.extend(self._jobs.pop(0).result())
         slot = self._k & 1
@@ -564,7 +702,8 @@ class SequenceOutputs:
             images = None
         else:
             png_streams = None
-        self._jobs.append(self._batches.submit(self._write_batch, slot, lo, records, tuple(size), images, final, ev, png_streams, ply_text))
+        self._jobs.append(self._batches.submit(self._write_batch, slot, lo, records, tuple(size), images, final, ev, png_streams, ply_text, renders,
+                                               render_streams))
 
     def mark_recomputed(self, frames):
         """global frame indices whose outputs came from the bf16x3 recompute (make_engine_step(on_range='recompute')): the manifest lists
@@ -592,7 +731,8 @@ class SequenceOutputs:
         with open(self.manifest, "w") as f:
             json.dump(dict(rank=self.rank, world=self.world, frames=list(self.shard), status=status, valid=status == "ok", files=files,
                            recomputed=[self.names[i] for i in sorted(set(self.recomputed))],
-                           **(dict(ply_fallback=[self.names[i] for i in sorted(set(self.ply_fallback))]) if self.ply and self.ply_route == "device" else {})),
+                           **(dict(ply_fallback=[self.names[i] for i in sorted(set(self.ply_fallback))]) if self.ply and self.ply_route == "device" else {}),
+                           **(dict(render=[f for f in files if f.startswith(SEQ_RENDER_DIR + os.sep)]) if self.render is not None else {})),
                       f, indent=1)
         if err is not None:
             raise err
@@ -607,11 +747,11 @@ class SequenceOutputs:
             buf = self._staging[slot][key] = torch.empty(max(numel, 1), dtype=dtype, pin_memory=pin)
         return buf[:numel].view(*shape)
 
-    def _to_host(self, slot, lo, records, images, final, ev, png_streams=None, ply_text=None):
+    def _to_host(self, slot, lo, records, images, final, ev, png_streams=None, ply_text=None, renders=None, render_streams=None):
         """numpy views of the batch (device tensors: copied into pinned staging on this slot's side stream behind ``ev``): records, images,
         clouds, from ``png_streams`` (streams [n,stride], sizes [n]) of which only streams[i, :sizes[i]] was copied, and from ``ply_text``
         (text [offsets[n]], offsets [n+1], flags [n]); with ``ply_text`` only the clouds of the frames with a non-zero flag are copied
-        (the others are None)"""
+        (the others are None); ``renders`` and ``render_streams`` travel like ``images`` and ``png_streams`` and come back last"""
         import torch
 
         def host(t):
@@ -626,7 +766,8 @@ class SequenceOutputs:
                 xyz, rgb = (host(final[k]) for k in ("xyz", "rgb"))
                 clouds = [(xyz[i, :cnt[i]], rgb[i, :cnt[i]]) for i in range(len(cnt))]
             return (rec, img, clouds, None if png_streams is None else (host(png_streams[0]), host(png_streams[1])),
-                    None if ply_text is None else tuple(host(t) for t in ply_text))
+                    None if ply_text is None else tuple(host(t) for t in ply_text), None if renders is None else host(renders),
+                    None if render_streams is None else (host(render_streams[0]), host(render_streams[1])))
         s = self._streams[slot]
         with torch.cuda.stream(s):
             s.wait_event(ev)
@@ -636,7 +777,14 @@ class SequenceOutputs:
             if images is not None:
                 img = self._pinned(slot, "img", tuple(images.shape), torch.uint8, True)
                 img.copy_(images, non_blocking=True)
-            cnt = psz = poff = pflg = None
+            rnd = None
+            if renders is not None:
+                rnd = self._pinned(slot, "render", tuple(renders.shape), torch.uint8, True)
+                rnd.copy_(renders, non_blocking=True)
+            cnt = psz = poff = pflg = rsz = None
+            if render_streams is not None:
+                rsz = self._pinned(slot, "render_sizes", tuple(render_streams[1].shape), torch.int64, True)
+                rsz.copy_(render_streams[1], non_blocking=True)
             if final is not None:
                 cnt = self._pinned(slot, "n", tuple(final["n"].shape), torch.int32, True)
                 cnt.copy_(final["n"], non_blocking=True)
@@ -649,7 +797,13 @@ class SequenceOutputs:
                 pflg = self._pinned(slot, "ply_flags", tuple(ply_text[2].shape), torch.int32, True)
                 pflg.copy_(ply_text[2], non_blocking=True)
             s.synchronize()
-            clouds = png = ply = None
+            clouds = png = ply = rpng = None
+            if render_streams is not None:
+                rbuf = self._pinned(slot, "render_png", tuple(render_streams[0].shape), torch.uint8, True)
+                rn = rsz.numpy()
+                for i in range(len(rn)):
+                    rbuf[i, :int(rn[i])].copy_(render_streams[0][i, :int(rn[i])], non_blocking=True)
+                rpng = (rbuf.numpy(), rn)
             if ply_text is not None:
                 total = int(poff[-1])
                 tbuf = self._pinned(slot, "ply_text", (total,), torch.uint8, True)
@@ -676,13 +830,13 @@ class SequenceOutputs:
                         rgb[off[i]:off[i + 1]].copy_(final["rgb"][i, :cn[i]], non_blocking=True)
                 xn, rn = xyz.numpy(), rgb.numpy()
                 clouds = [(xn[off[i]:off[i + 1]], rn[off[i]:off[i + 1]]) if ply is None or ply[2][i] != 0 else None for i in range(len(cn))]
-            if final is not None or png_streams is not None:
+            if final is not None or png_streams is not None or render_streams is not None:
                 s.synchronize()
-        return rec.numpy(), None if img is None else img.numpy(), clouds, png, ply
+        return rec.numpy(), None if img is None else img.numpy(), clouds, png, ply, None if rnd is None else rnd.numpy(), rpng
 
-    def _write_batch(self, slot, lo, records, size, images, final, ev, png_streams=None, ply_text=None):
+    def _write_batch(self, slot, lo, records, size, images, final, ev, png_streams=None, ply_text=None, renders=None, render_streams=None):
         from .engine import RW_DTYPE
-        rec_u8, img, clouds, png, ply = self._to_host(slot, lo, records, images, final, ev, png_streams, ply_text)
+        rec_u8, img, clouds, png, ply, rnd, rpng = self._to_host(slot, lo, records, images, final, ev, png_streams, ply_text, renders, render_streams)
         recs = np.ascontiguousarray(rec_u8).view(RW_DTYPE).reshape(-1)
         n = len(recs)
         names = self.names[lo:lo + n]
@@ -727,5 +881,14 @@ class SequenceOutputs:
         elif self.images:
             assert img.shape == (n, h, w, 3), (img.shape, (n, h, w))
             files.extend(write_png_batch([os.path.join(self.img_dir, "{}.png".format(nm)) for nm in names], img, self.level, self.threads))
+        if self.render is not None:
+            os.makedirs(self.render_dir, exist_ok=True)
+            paths = [os.path.join(self.render_dir, "{}_render.png".format(nm)) for nm in names]
+            rh, rw = self.render.height, self.render.width
+            if rpng is not None:
+                files.extend(write_png_streams(paths, rpng[0], rpng[1], rh, rw, self.threads))
+            else:
+                assert rnd.shape == (n, rh, rw, 3), (rnd.shape, (n, rh, rw))
+                files.extend(write_png_batch(paths, rnd, self.level, self.threads))
         files.extend(f.result() for f in futs)
         return files
