@@ -299,6 +299,46 @@ sd_status sd_png_encode_zlib_host(const uint8_t* frame_host, int height, int wid
 sd_status sd_png_write_streams_files(const char* const* paths, int n, int height, int width, const uint8_t* streams_host, size_t stream_stride,
                                      const uint64_t* sizes_host, int threads, int* status_out);
 
+/* ---- result video: every frame a complete baseline JPEG file made on the GPU, the host only concatenates them into a Motion-JPEG AVI ----
+ * The file format, fixed here (the coder itself is semantic_depth_amd/csrc/jpeg_enc.hpp, integer arithmetic that host and device both run):
+ *   the file         JFIF, baseline sequential (SOF0), 8 bits, three components Y Cb Cr, Y sampled 2x2 and the chroma 1x1 (4:2:0), one
+ *                    interleaved scan.  Markers in order: SOI, APP0 (JFIF 1.01, density 1:1, no unit), DQT (tables 0 and 1), SOF0, DHT (DC 0,
+ *                    AC 0, DC 1, AC 1), DRI, SOS, entropy-coded data, EOI.  The header is 613 bytes for every frame.
+ *   colour           from the BGR bytes, 16-bit fixed point:  Y = (19595 R + 38470 G + 7471 B + 32768) >> 16,
+ *                    Cb = (-11059 R - 21709 G + 32768 B + 8421375) >> 16,  Cr = (32768 R - 27439 G - 5329 B + 8421375) >> 16
+ *                    (8421375 = (128 << 16) + 32767).
+ *   planes           padded to a multiple of 16 by replicating the last column and the last row; the chroma planes are the 2x2 box
+ *                    (a + b + c + d + 2) >> 2 of the padded planes.
+ *   transform        samples - 128 through the separable integer forward DCT with 13-bit constants (rows first, 2 extra bits kept between
+ *                    the passes); its outputs are the orthonormal DCT's coefficients times 8.
+ *   quantisation     the ITU T.81 Annex K luminance / chrominance tables under the IJG quality rule: s = quality < 50 ? 5000 / quality :
+ *                    200 - 2 quality, entry = (base s + 50) / 100 clamped to 1..255.  A coefficient c (times 8) and d = 8 entry give
+ *                    (|c| + d / 2) / d with the sign of c: half away from zero.  Zigzag order.
+ *   entropy coding   the four typical Huffman tables of Annex K, fixed.  DRI = the MCUs of one MCU row: every MCU row starts byte-aligned
+ *                    with the DC predictors 0, ends padded with 1-bits and is followed by RSTm, m = row mod 8; the last row by EOI instead.
+ *                    FF bytes of the coded data are followed by 00; runs of 16 zeros are ZRL; EOB is omitted when coefficient 63 is
+ *                    non-zero.
+ *   the bound        a block is at most 22 + 63 * 26 = 1660 bits (DC category <= 11: 11 + 11 bits; 63 AC symbols of category <= 10: 16 + 10
+ *                    bits), counted as 208 bytes; an MCU row is at most 2 * 208 * 6 * ceil(width / 16) + 2 bytes (every byte stuffed, the
+ *                    padding inside the last byte, the marker), a file at most 613 + ceil(height / 16) of those.
+ * sd_jpeg_encode_workspace: the device workspace sd_jpeg_encode_bgr needs for B frames of height x width (12 bytes per MCU row) and that
+ * bound, the largest stream_stride anyone needs.  SD_ERR_INVALID for B < 1 or an extent outside 1..16384. */
+sd_status sd_jpeg_encode_workspace(int B, int height, int width, size_t* workspace_bytes, size_t* stream_bound);
+/* DEVICE: frames u8 [B,height,width,3] BGR (frame b at frames_dev + b * frame_stride) -> frame b's file at streams_dev + b * stream_stride,
+ * its byte count in sizes_dev[b] (u64), flags_dev[b] (i32) = 0.  Bytes of a frame's slot behind its size are not written.  A stream_stride
+ * below the bound is legal: a frame whose file would pass it gets size 0 and flag 1 and nothing of its slot is written; the other frames
+ * are unaffected.  Three launches (every MCU row coded for its size; the layout and header of each frame; every MCU row coded into place)
+ * enqueued on `stream`, no synchronisation; the handle need not be bound.  SD_ERR_INVALID, nothing launched: an extent outside 1..16384,
+ * B < 1, quality outside 1..100, frame_stride < height * width * 3, stream_stride < 613 (the header), workspace_bytes below
+ * sd_jpeg_encode_workspace, a workspace that is not 16-byte aligned. */
+sd_status sd_jpeg_encode_bgr(sd_handle* h, const uint8_t* frames_dev, size_t frame_stride, int B, int height, int width, int quality,
+                             uint8_t* streams_dev, size_t stream_stride, uint64_t* sizes_dev, int32_t* flags_dev, void* workspace_dev,
+                             size_t workspace_bytes, void* stream);
+/* HOST: the CPU statement of sd_jpeg_encode_bgr for one frame: the same bytes, from one plain loop.  *size_out = bytes written to out_host;
+ * SD_ERR_INVALID (nothing written) for a null pointer, an extent outside 1..16384, a quality outside 1..100 or a file larger than cap (the
+ * bound of sd_jpeg_encode_workspace always suffices). */
+sd_status sd_jpeg_encode_bgr_host(const uint8_t* frame_host, int height, int width, int quality, uint8_t* out_host, size_t cap, size_t* size_out);
+
 /* HOST helper of the PLY writer that replaces semantic_depth_lib/point_cloud_2_ply.py:70 (numpy.savetxt(fh, rows, "%f %f %f %d %d %d")):
  * n vertex rows "x y z r g b\n" -- coordinates as "%f" % float(v) prints them (fixed, six decimals, correctly rounded; nan / inf /
  * -inf), colours as integers -- into out[0 .. cap).  xyz f64 [n,3], rgb int64 [n,3], HOST memory; threads <= 0: one per core, at most

@@ -2,6 +2,7 @@
 
     python scripts/sequence_outputs_rate.py [--frames 128] [--batch 32] [--precision f16x2] [--level 1] [--threads 0]
                                             [--png host|device|both] [--ply host|device|both] [--repeats 5] [--no-ply]
+                                            [--video off|device|host]
 
 Setup as bench.py --config 5 (smooth random frames, seeded weights, the monodepth bias calibrated so that the median depth is the
 measuring depth); the frames are written once, untimed.  Each run is timed from the first decode to the last file written
@@ -12,6 +13,8 @@ copied device-to-host per frame, the PNG bytes per frame, and whether the device
 (median(device) - median(host) > max(host) - min(host)).  --ply chooses where the road PLYs are formatted (SequenceOutputs(ply=)) in the
 same way: with "both" (and one --png route) the two PLY routes are timed interleaved, and the line carries each route's rates, the PLY
 bytes per frame (on the device route: the text copied device-to-host) and the raw cloud bytes per frame (15 B per point, the host route's copy).
+--video device|host also writes the result video (SequenceOutputs(video=outputs.Video(route=...))) in every run with files on; the line then
+carries the route and the bytes of the AVI files per frame.  Compare against the same command without it.
 """
 import argparse
 import json
@@ -38,6 +41,7 @@ def main():
     ap.add_argument("--ply", dest="ply_route", choices=("host", "device", "both"), default="host", help="where the road PLYs are formatted")
     ap.add_argument("--repeats", type=int, default=5, help="timed runs per route with --png both / --ply both")
     ap.add_argument("--no-ply", dest="ply", action="store_false", help="no road PLYs (images and overlay items only)")
+    ap.add_argument("--video", choices=("off", "device", "host"), default="off", help="also write the result video (Motion-JPEG AVI) on this route")
     ap.add_argument("--keep", action="store_true", help="keep the written files (default: removed)")
     args = ap.parse_args()
     if args.png == "both" and args.ply_route == "both":
@@ -90,7 +94,8 @@ def main():
             if with_outputs:
                 png, ply = (args.png, route) if vary_ply else (route, args.ply_route)
                 outs = outputs.SequenceOutputs(os.path.join(work, tag), outputs.sequence_names(frame_paths), depth=prm.depth, level=args.level,
-                                               threads=threads, ply=ply if args.ply else False, png=png)
+                                               threads=threads, ply=ply if args.ply else False, png=png,
+                                               video=None if args.video == "off" else outputs.Video(route=args.video))
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             rec = run_sequence_files(frame_paths, make_engine_step(eng, lambda i: cam, prm, outputs=outs), batch=B, device="cuda")
@@ -162,6 +167,10 @@ def main():
             line["files_identical"] = all(
                 open(os.path.join(work, "on_host", outputs.SEQ_PLY_DIR, f), "rb").read() == open(os.path.join(work, "on_device", outputs.SEQ_PLY_DIR, f), "rb").read()
                 for f in sorted(os.listdir(os.path.join(work, "on_host", outputs.SEQ_PLY_DIR))))
+        if args.video != "off":
+            tags = [d for d in sorted(os.listdir(work)) if d.startswith("on")]
+            avi = [os.path.join(work, tags[-1], f) for f in sorted(os.listdir(os.path.join(work, tags[-1]))) if f.endswith(".avi")]
+            line["video"] = dict(route=args.video, files=len(avi), avi_bytes_per_frame=sum(os.path.getsize(f) for f in avi) // args.frames)
         print(json.dumps(line))
         eng.close()
     finally:

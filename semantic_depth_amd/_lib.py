@@ -111,6 +111,9 @@ SIGNATURES = {
                                           C.POINTER(C.c_int)]),
     "sd_png_encode_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "sd_png_encode_bgr": (C.c_int, [_H, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
+    "sd_jpeg_encode_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "sd_jpeg_encode_bgr": (C.c_int, [_H, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _P]),
+    "sd_jpeg_encode_bgr_host": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sd_png_encode_zlib_host": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sd_png_write_streams_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, C.c_int,
                                              C.POINTER(C.c_int)]),

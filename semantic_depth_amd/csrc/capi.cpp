@@ -14,6 +14,7 @@
 
 #include "jpeg_gpu.hpp"
 #include "png_gpu.hpp"
+#include "jpeg_enc_gpu.hpp"
 #include "ply_gpu.hpp"
 #include "text_gpu.hpp"
 #include "render_gpu.hpp"
@@ -793,6 +794,33 @@ sd_status sd_png_encode_bgr(sd_handle* h, const uint8_t* frames_dev, size_t fram
         return fail(h, SD_ERR_INVALID, "sd_png_encode_bgr: workspace_dev must be 16-byte, sizes_dev 8-byte aligned");
     HIPCHK(h, launch_png_encode(frames_dev, frame_stride, B, height, width, streams_dev, stream_stride, sizes_dev,
                                 static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
+    return SD_OK;
+}
+
+sd_status sd_jpeg_encode_workspace(int B, int height, int width, size_t* workspace_bytes, size_t* stream_bound) {
+    if (B < 1 || B > 65535 || height < 1 || width < 1 || height > sdjenc::kMaxExtent || width > sdjenc::kMaxExtent) return SD_ERR_INVALID;
+    if (workspace_bytes) *workspace_bytes = jpeg_enc_workspace_bytes(B, height);
+    if (stream_bound) *stream_bound = sdjenc::stream_bound(height, width);
+    return SD_OK;
+}
+
+sd_status sd_jpeg_encode_bgr(sd_handle* h, const uint8_t* frames_dev, size_t frame_stride, int B, int height, int width, int quality,
+                             uint8_t* streams_dev, size_t stream_stride, uint64_t* sizes_dev, int32_t* flags_dev, void* workspace_dev,
+                             size_t workspace_bytes, void* stream) {
+    if (!h || !frames_dev || !streams_dev || !sizes_dev || !flags_dev || !workspace_dev || B < 1 || B > 65535)
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_encode_bgr: bad arguments");
+    if (height < 1 || width < 1 || height > sdjenc::kMaxExtent || width > sdjenc::kMaxExtent)
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_encode_bgr: extents must be 1..16384");
+    if (quality < 1 || quality > 100) return fail(h, SD_ERR_INVALID, "sd_jpeg_encode_bgr: quality must be 1..100");
+    // every index the kernels form follows from the extents and these capacities: nothing is launched otherwise
+    if (frame_stride < (size_t)height * width * 3) return fail(h, SD_ERR_INVALID, "sd_jpeg_encode_bgr: frame_stride below height * width * 3");
+    if (stream_stride < (size_t)sdjenc::kHeaderLen) return fail(h, SD_ERR_INVALID, "sd_jpeg_encode_bgr: stream_stride below the header's 613 bytes");
+    if (workspace_bytes < jpeg_enc_workspace_bytes(B, height))
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_encode_bgr: workspace smaller than sd_jpeg_encode_workspace reports");
+    if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(sizes_dev) & 7) || (reinterpret_cast<uintptr_t>(flags_dev) & 3))
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_encode_bgr: workspace_dev must be 16-byte, sizes_dev 8-byte, flags_dev 4-byte aligned");
+    HIPCHK(h, launch_jpeg_encode(frames_dev, frame_stride, B, height, width, quality, streams_dev, stream_stride, sizes_dev, flags_dev,
+                                 static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
     return SD_OK;
 }
 

@@ -95,7 +95,7 @@ def run_sequence(load_frames, n_frames: int, step, batch: int = 32, group=None, 
 
 
 def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", workers: int = 0, outputs=None, jpeg: str = "host",
-                       engine=None, png: str | None = None, ply: str | None = None, text: str | None = None, render=None) -> torch.Tensor:
+                       engine=None, png: str | None = None, ply: str | None = None, text: str | None = None, render=None, video=None) -> torch.Tensor:
     """run_sequence on FILES (semantic_depth_cityscapes_sequence.py:689-701 reads ``sorted(glob(input_folder))`` frame by frame): rank r
     decodes ONLY its shard of the sorted list -- frame_io.FrameFeeder: one native call per batch into pinned staging, upload one batch
     ahead, ``workers`` decode threads (default: this rank's share of the node's CPUs, frame_io.default_decode_workers) -- and hands every
@@ -112,7 +112,9 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     ``text`` ("json" | "draw", None = what the SequenceOutputs was built with): whether the banner text is rasterised into the result images
     (SequenceOutputs.set_text; "draw" needs the step of make_engine_step, which draws it on the GPU).
     ``render`` (an outputs.RenderCamera, None = what the SequenceOutputs was built with): the view every frame's road cloud is rendered from
-    (SequenceOutputs.set_render; needs the step of make_engine_step, which renders on the GPU)."""
+    (SequenceOutputs.set_render; needs the step of make_engine_step, which renders on the GPU).
+    ``video`` (an outputs.Video, None = what the SequenceOutputs was built with): the result images also become a Motion-JPEG AVI
+    (SequenceOutputs.set_video; its "device" route needs the step of make_engine_step, which encodes the frames on the GPU)."""
     from .frame_io import FrameFeeder
     engine = engine if engine is not None else getattr(step, "engine", None)
     paths = sorted(paths)
@@ -132,6 +134,8 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
             outputs.set_text(text)
         if render is not None:
             outputs.set_render(render)
+        if video is not None:
+            outputs.set_video(video)
         outputs.begin(rank, world, lo, hi)
     try:
         parts = []
@@ -159,7 +163,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
 
 
 def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outputs=None, on_range: str | None = None, png: str | None = None,
-                     ply: str | None = None, text: str | None = None, render=None):
+                     ply: str | None = None, text: str | None = None, render=None, video=None):
     """``step`` for run_sequence on a real Engine: host or device u8 frames of any size -> (cubic resize to the network shape on
     the GPU, semantic_depth_cityscapes_sequence.py:123-130) -> Engine.process_batch -> record buffer.
     ``camera_of(global_frame_index) -> engine.Camera`` (the sequence tool: cx = 1048.64/4·s, cy = 519.277/4·s, disp_mult = 3800).
@@ -179,7 +183,11 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     the copy to the host on the other -- so both routes write it; the ``_overlay.json`` files are written as before.
     ``render`` (an outputs.RenderCamera, None = what ``outputs`` was built with): with a camera process_batch keeps the final road clouds even
     when no PLY is asked for, and Engine.render_rw draws them and the road-width line behind that camera on the step's stream, behind the road
-    chain; the ``<name>_render.png`` files go through the PNG route chosen (png="device": Engine.encode_png on the renders)."""
+    chain; the ``<name>_render.png`` files go through the PNG route chosen (png="device": Engine.encode_png on the renders).
+    ``video`` (an outputs.Video, None = what ``outputs`` was built with): the composed images -- composed for this alone when ``outputs.images``
+    is off -- also become the frames of the result video; on its "device" route Engine.encode_jpeg makes every frame's JPEG file on the step's
+    stream, behind Engine.draw_result_text, with a stream stride of half the raw image (a frame that needs more is flagged and encoded on the
+    host from its raw copy)."""
     from .engine import RoadWidthParams
     from .recompute import check_mode
 
@@ -194,6 +202,8 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
         outputs.set_text(text)
     if render is not None and outputs is not None:
         outputs.set_render(render)
+    if video is not None and outputs is not None:
+        outputs.set_video(video)
     recomputed: list[int] = []
 
     def note(lo):
@@ -227,13 +237,17 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
                 more["render_streams"] = engine.encode_png(renders)
             else:
                 more["renders"] = renders
-        if outputs.images:
+        vid = getattr(outputs, "video", None)
+        if outputs.images or vid is not None:
             images = engine.compose_result_frames(fr, out["seg"]["road"], out["seg"]["fence"], rec, size[0], size[1], outputs.road_color,
                                                   outputs.fence_color, outputs.alpha)
             if getattr(outputs, "text", "json") == "draw":         # the banner text, on the step's stream, before either PNG route reads the images
                 engine.draw_result_text(images, rec, outputs.depth)
-            if getattr(outputs, "png", "host") == "device":        # the zlib streams right behind the compose launch, on the step's stream
-                outputs.submit(lo, rec, size, final=out.get("road_final") if outputs.ply else None, png_streams=engine.encode_png(images), **more)
+            if vid is not None and vid.route == "device":          # the frames of the video, behind the text, on the step's stream
+                more["video_streams"] = engine.encode_jpeg(images, vid.quality, stream_stride=1024 + size[0] * size[1] * 3 // 2)
+            if outputs.images and getattr(outputs, "png", "host") == "device":        # the zlib streams right behind the compose launch, on the step's stream
+                outputs.submit(lo, rec, size, images=images if vid is not None else None, final=out.get("road_final") if outputs.ply else None,
+                               png_streams=engine.encode_png(images), **more)
                 return rec
         outputs.submit(lo, rec, size, images=images, final=out.get("road_final") if outputs.ply else None, **more)
         return rec

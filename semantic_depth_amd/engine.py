@@ -412,6 +412,28 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_png_encode_bgr")
         return streams, sizes
 
+    def encode_jpeg(self, images: torch.Tensor, quality: int = 90, stream_stride: int | None = None):
+        """the device half of the result video (sd_jpeg_encode_bgr): u8 [n,h,w,3] BGR device ``images`` -> (``streams`` u8 [n,stride], ``sizes``
+        i64 [n], ``flags`` i32 [n]) device tensors: frame b's complete baseline JPEG file (4:2:0, the Annex K tables at the IJG ``quality``
+        1..100, one restart interval per MCU row; include/semdepth.h) is ``streams[b, :sizes[b]]``, the bytes behind it are not written.
+        ``stream_stride`` None: the bound for any content (about 10 bytes per pixel); a smaller one is legal: a frame whose file would pass it
+        has size 0 and flag 1 (encode it with outputs.encode_jpeg_host).  Three launches on the current stream, no synchronisation; the
+        workspace is a torch allocation."""
+        assert images.dtype == torch.uint8 and images.is_cuda and images.is_contiguous() and images.dim() == 4 and images.shape[3] == 3
+        B, h, w = (int(v) for v in images.shape[:3])
+        need, bound = C.c_size_t(), C.c_size_t()
+        st = self.lib.sd_jpeg_encode_workspace(B, h, w, C.byref(need), C.byref(bound))
+        L.check(self.lib, None, st, "sd_jpeg_encode_workspace")
+        stride = bound.value if stream_stride is None else int(stream_stride)
+        streams = torch.empty((B, stride), dtype=torch.uint8, device=self.device)
+        sizes = torch.empty((B,), dtype=torch.int64, device=self.device)
+        flags = torch.empty((B,), dtype=torch.int32, device=self.device)
+        ws = torch.empty((need.value,), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_jpeg_encode_bgr(self.h, _ptr(images), h * w * 3, B, h, w, int(quality), _ptr(streams), stride, _ptr(sizes), _ptr(flags),
+                                         _ptr(ws), need.value, self._stream())
+        L.check(self.lib, self.h, st, "sd_jpeg_encode_bgr")
+        return streams, sizes, flags
+
     def format_rw_ply(self, final: dict, records: torch.Tensor, capacity: int | None = None, out: torch.Tensor | None = None):
         """the device half of the road PLY writer (sd_ply_format_rw): ``final`` = process_batch(want_final=True)'s road_final (xyz f32 [B,cap,3],
         rgb u8 [B,cap,3], n i32 [B]) and ``records`` u8 [B,104] (sd_rw_result) -> (``text`` u8 [capacity], ``offsets`` i64 [B+1], ``flags`` i32 [B])

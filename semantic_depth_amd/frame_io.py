@@ -85,6 +85,80 @@ def imread(path: str) -> np.ndarray:
     return decode_png(buf) if buf[:8] == _SIG else decode_image(buf)
 
 
+def _avi_chunks(f, start: int, end: int):
+    """(fourcc, payload offset, payload size) of the chunks in [start, end) of an open RIFF file"""
+    import struct
+    pos = start
+    while pos + 8 <= end:
+        f.seek(pos)
+        head = f.read(8)
+        if len(head) < 8:
+            return
+        cc, size = head[:4], struct.unpack("<I", head[4:])[0]
+        yield cc, pos + 8, size
+        pos += 8 + size + (size & 1)
+
+
+def _avi_layout(f):
+    """(avih fields, strh fields, offset of the 'movi' fourcc, (offset, size) of the idx1 payload or None) of an open AVI file"""
+    import struct
+    f.seek(0)
+    head = f.read(12)
+    if len(head) < 12 or head[:4] != b"RIFF" or head[8:] != b"AVI ":
+        raise ValueError("not a RIFF AVI file")
+    end = 8 + struct.unpack("<I", head[4:8])[0]
+    avih = strh = movi = idx1 = None
+    for cc, off, size in _avi_chunks(f, 12, end):
+        f.seek(off)
+        if cc == b"LIST":
+            kind = f.read(4)
+            if kind == b"movi":
+                movi = off
+            elif kind == b"hdrl":
+                for c2, o2, s2 in _avi_chunks(f, off + 4, off + size):
+                    f.seek(o2)
+                    if c2 == b"avih":
+                        avih = struct.unpack("<14I", f.read(56))
+                    elif c2 == b"LIST" and f.read(4) == b"strl" and strh is None:
+                        for c3, o3, s3 in _avi_chunks(f, o2 + 4, o2 + s2):
+                            if c3 == b"strh":
+                                f.seek(o3)
+                                strh = struct.unpack("<4s4sIHHIIIIIIII4h", f.read(56))
+        elif cc == b"idx1":
+            idx1 = (off, size)
+    if avih is None or strh is None or movi is None:
+        raise ValueError("AVI file without avih / strh / movi")
+    return avih, strh, movi, idx1
+
+
+def avi_info(path: str) -> dict:
+    """width, height, frames, rate and scale (frames per second = rate / scale) and the stream handler of an AVI file's first stream"""
+    with open(path, "rb") as f:
+        avih, strh, _, _ = _avi_layout(f)
+    return dict(width=int(avih[8]), height=int(avih[9]), frames=int(strh[9]), rate=int(strh[7]), scale=int(strh[6]), handler=strh[1])
+
+
+def avi_frames(path: str):
+    """the frames of a Motion-JPEG AVI (outputs.MjpegAviWriter's files) as byte strings -- each a complete JPEG file, decode_jpeg reads it --
+    in index order, read through idx1 (offsets relative to the 'movi' fourcc)"""
+    import struct
+    with open(path, "rb") as f:
+        _, _, movi, idx1 = _avi_layout(f)
+        if idx1 is None:
+            raise ValueError("AVI file without an idx1 index")
+        f.seek(idx1[0])
+        index = f.read(idx1[1])
+        for k in range(0, len(index) - 15, 16):
+            cc, _flags, off, size = struct.unpack("<4sIII", index[k:k + 16])
+            if cc[2:] not in (b"dc", b"db"):
+                continue
+            f.seek(movi + off)
+            head = f.read(8)
+            if head[:4] != cc or struct.unpack("<I", head[4:])[0] != size:
+                raise ValueError(f"AVI index entry {k // 16} does not point at its chunk")
+            yield f.read(size)
+
+
 def _cgroup_cpu_quota():
     """CPUs the cgroup quota allows (v2: cpu.max "<quota> <period>" | "max <period>"; v1: cpu.cfs_quota_us / cpu.cfs_period_us), or None"""
     try:

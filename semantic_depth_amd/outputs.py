@@ -495,6 +495,164 @@ SEQ_IMG_DIR, SEQ_PLY_DIR = "result_sequence_imgs", "result_sequence_ply"        
 SEQ_RENDER_DIR = "rendered_sequence"                                              # utils/render_ply.py's output folder
 
 
+# ------------------------------------------------------------------------------------------------ result video
+@dataclasses.dataclass(frozen=True)
+class Video:
+    """the result video of the sequence tool (opt-in, SequenceOutputs(video=)): the composed result images as a Motion-JPEG AVI at ``fps``
+    frames per second, every frame a baseline JPEG file at the IJG ``quality`` 1..100 (the format of include/semdepth.h).  ``route``:
+    "device" (Engine.encode_jpeg makes the files on the GPU, only their bytes travel) or "host" (the raw images travel and
+    sd_jpeg_encode_bgr_host makes the same bytes on the writer threads)."""
+    fps: float = 30.0
+    quality: int = 90
+    route: str = "device"
+
+    def __post_init__(self):
+        object.__setattr__(self, "fps", float(self.fps))
+        object.__setattr__(self, "quality", int(self.quality))
+        if not (self.fps > 0 and np.isfinite(self.fps)):
+            raise ValueError(f"Video: fps must be a positive number, got {self.fps!r}")
+        if not 1 <= self.quality <= 100:
+            raise ValueError(f"Video: quality must be 1..100, got {self.quality!r}")
+        if self.route not in ("device", "host"):
+            raise ValueError(f"Video: route must be 'device' or 'host', got {self.route!r}")
+
+
+def _check_video(video):
+    if video is not None and not isinstance(video, Video):
+        raise ValueError(f"video must be None or an outputs.Video, got {video!r}")
+    return video
+
+
+def encode_jpeg_host(img_bgr: np.ndarray, quality: int = 90) -> bytes:
+    """one u8 [h,w,3] BGR image -> the bytes of its baseline JPEG file (sd_jpeg_encode_bgr_host: the CPU statement of Engine.encode_jpeg,
+    the same bytes)"""
+    import ctypes as C
+
+    from . import _lib as L
+    a = np.ascontiguousarray(img_bgr, dtype=np.uint8)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"image must be u8 [h,w,3], got {a.shape}")
+    h, w = a.shape[:2]
+    lib = L.load()
+    bound, size = C.c_size_t(), C.c_size_t()
+    if lib.sd_jpeg_encode_workspace(1, h, w, None, C.byref(bound)) != L.SD_OK:
+        raise ValueError(f"encode_jpeg_host: extents must be 1..16384, got {h} x {w}")
+    out = np.empty(bound.value, np.uint8)
+    st = lib.sd_jpeg_encode_bgr_host(a.ctypes.data_as(C.c_void_p), h, w, int(quality), out.ctypes.data_as(C.c_void_p), out.size, C.byref(size))
+    if st != L.SD_OK:
+        raise ValueError(f"encode_jpeg_host: refused (status {st}; quality must be 1..100)")
+    return out[:size.value].tobytes()
+
+
+AVI_RIFF_LIMIT = 2 ** 31 - 2 ** 24          # a part is closed before its RIFF chunk would pass this
+
+
+class MjpegAviWriter:
+    """a Motion-JPEG AVI written frame by frame: RIFF 'AVI ' = LIST hdrl (avih; LIST strl (strh 'vids' / 'MJPG', strf = a 40-byte
+    BITMAPINFOHEADER)), LIST movi (one '00dc' chunk per frame, padded to even length) and idx1 (one key-frame entry per chunk, offsets
+    relative to the 'movi' fourcc).  ``append(jpeg_bytes)`` adds a frame (a complete JPEG file of width x height), ``close()`` writes the
+    index and patches the counts and sizes of the headers.  Before the RIFF chunk would pass 2^31 - 2^24 bytes the file is closed and the
+    frames continue in ``<stem>_part<k>.avi`` (k = 1, 2, ...); ``paths`` lists the files written, in order.  fps becomes the rational
+    dwRate / dwScale with a denominator of at most 1001 (29.97 -> 30000 / 1001)."""
+    HEADER_BYTES = 224                      # everything in front of the first '00dc' chunk; the 'movi' fourcc is at 220
+
+    def __init__(self, path: str, width: int, height: int, fps: float = 30.0, _max_riff_bytes: int = AVI_RIFF_LIMIT):
+        from fractions import Fraction
+        if not (1 <= int(width) <= 65535 and 1 <= int(height) <= 65535):
+            raise ValueError("MjpegAviWriter: width and height must be 1..65535")
+        if not (float(fps) > 0 and np.isfinite(float(fps))):
+            raise ValueError("MjpegAviWriter: fps must be a positive number")
+        fr = Fraction(float(fps)).limit_denominator(1001)
+        if fr <= 0:
+            raise ValueError("MjpegAviWriter: fps too small")
+        self.rate, self.scale = fr.numerator, fr.denominator
+        self.width, self.height, self.fps = int(width), int(height), float(fps)
+        self.stem, self.ext = os.path.splitext(path)
+        self.limit = int(_max_riff_bytes)
+        self.paths, self.frames = [], 0
+        self._f = None
+        self._open(path)
+
+    def _header(self, nframes: int, movi_bytes: int, riff_bytes: int, max_chunk: int) -> bytes:
+        usec = int(round(1e6 * self.scale / self.rate))
+        bps = int(min(2 ** 32 - 1, max_chunk * self.rate // self.scale + 1)) if nframes else 0
+        avih = struct.pack("<14I", usec, bps, 0, 0x10, nframes, 0, 1, max_chunk, self.width, self.height, 0, 0, 0, 0)
+        strh = struct.pack("<4s4sIHHIIIIIIII4h", b"vids", b"MJPG", 0, 0, 0, 0, self.scale, self.rate, 0, nframes, max_chunk, 0xFFFFFFFF, 0,
+                           0, 0, self.width, self.height)
+        strf = struct.pack("<IiiHH4sIiiII", 40, self.width, self.height, 1, 24, b"MJPG", self.width * self.height * 3, 0, 0, 0, 0)
+        strl = b"strl" + b"strh" + struct.pack("<I", len(strh)) + strh + b"strf" + struct.pack("<I", len(strf)) + strf
+        hdrl = b"hdrl" + b"avih" + struct.pack("<I", len(avih)) + avih + b"LIST" + struct.pack("<I", len(strl)) + strl
+        out = (b"RIFF" + struct.pack("<I", riff_bytes) + b"AVI " + b"LIST" + struct.pack("<I", len(hdrl)) + hdrl +
+               b"LIST" + struct.pack("<I", movi_bytes) + b"movi")
+        assert len(out) == self.HEADER_BYTES, len(out)
+        return out
+
+    def _open(self, path: str):
+        self._f = open(path, "wb")
+        self.paths.append(path)
+        self._index, self._movi, self._max_chunk = [], 4, 0            # _movi: bytes of the LIST movi payload so far ('movi' itself: 4)
+        self._f.write(self._header(0, 4, 0, 0))
+
+    def _riff_bytes(self, movi: int, entries: int) -> int:
+        return self.HEADER_BYTES - 8 - 4 + movi + 8 + 16 * entries
+
+    def _close_part(self):
+        f, self._f = self._f, None
+        idx = b"".join(struct.pack("<4sIII", b"00dc", 0x10, off, size) for off, size in self._index)
+        f.write(b"idx1" + struct.pack("<I", len(idx)) + idx)
+        f.seek(0)
+        f.write(self._header(len(self._index), self._movi, self._riff_bytes(self._movi, len(self._index)), self._max_chunk))
+        f.close()
+
+    def append(self, jpeg: bytes):
+        if self._f is None:
+            raise RuntimeError("MjpegAviWriter.append after close")
+        data = bytes(jpeg) if not isinstance(jpeg, (bytes, bytearray, memoryview)) else jpeg
+        n = len(data)
+        padded = n + (n & 1)
+        if self._index and self._riff_bytes(self._movi + 8 + padded, len(self._index) + 1) > self.limit:
+            self._close_part()
+            self._open("{}_part{}{}".format(self.stem, len(self.paths), self.ext))
+        self._index.append((self._movi, n))
+        self._f.write(b"00dc" + struct.pack("<I", n))
+        self._f.write(data)
+        if n & 1:
+            self._f.write(b"\0")
+        self._movi += 8 + padded
+        self._max_chunk = max(self._max_chunk, n)
+        self.frames += 1
+
+    def close(self) -> list:
+        if self._f is not None:
+            self._close_part()
+        return list(self.paths)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def join_mjpeg_avi(paths, out: str, _max_riff_bytes: int = AVI_RIFF_LIMIT) -> list:
+    """the frames of the Motion-JPEG AVIs ``paths`` (the parts of a rolled-over file, the shards of the ranks), in that order, re-muxed into
+    ``out`` (and ``<stem>_part<k>.avi`` when it rolls over itself): the chunks are copied, nothing is decoded.  Size and frame rate are the
+    first file's; a file of another size is refused.  Returns the files written."""
+    from .frame_io import avi_frames, avi_info
+    paths = list(paths)
+    if not paths:
+        raise ValueError("join_mjpeg_avi: no input")
+    first = avi_info(paths[0])
+    with MjpegAviWriter(out, first["width"], first["height"], first["rate"] / first["scale"], _max_riff_bytes=_max_riff_bytes) as wr:
+        for p in paths:
+            info = avi_info(p)
+            if (info["width"], info["height"]) != (first["width"], first["height"]):
+                raise ValueError(f"join_mjpeg_avi: {p} is {info['width']} x {info['height']}, the first file {first['width']} x {first['height']}")
+            for frame in avi_frames(p):
+                wr.append(frame)
+    return wr.paths
+
+
 def sequence_names(paths) -> list:
     """``output_name`` of every frame in the order the sequence tool visits them (seq:689-699): basename without extension of
     ``sorted(paths)``"""
@@ -572,6 +730,8 @@ class SequenceOutputs:
                                                               rasterised into the image only with text="draw", module docstring)
         <directory>/result_sequence_ply/<name>_rw.ply         the denoised road cloud + the red road-width line (``ply``; rw_ply_bytes)
         <directory>/rendered_sequence/<name>_render.png       only with render=: the top view of the _rw.ply's rows (``render``)
+        <directory>/result_imgs.avi                           only with video=: the result images as a Motion-JPEG AVI (``video``;
+                                                              result_imgs_rank<r>.avi when world > 1, _part<k> when a file rolls over)
         <directory>/manifest_rank<r>.json                     written last by close(): the files of this rank and 'ok' / 'range_error' / 'error'
 
     ``names``: output names of the WHOLE sorted frame list (sequence_names), indexed by global frame index.  submit() takes the device
@@ -591,11 +751,19 @@ class SequenceOutputs:
     ``render``: None (default: nothing more is written, the manifest is what it was) or a RenderCamera: the step of make_engine_step also
     draws every frame's final road cloud and road-width line behind that camera on the GPU (Engine.render_rw, submit(renders=) or, with
     png="device", submit(render_streams=)) and the writer stores ``<name>_render.png`` through the PNG route chosen; the manifest names
-    those files under 'render'."""
+    those files under 'render'.
+    ``video``: None (default: nothing more is written, the manifest is what it was) or a Video: the composed result images -- the very
+    images of the PNGs, banner text included with text="draw" -- also become the frames of ``result_imgs.avi``, in global frame order
+    although two batches are in flight (the appends are serialised by batch index).  route "device": the step of make_engine_step hands
+    submit(video_streams=) the finished JPEG files of Engine.encode_jpeg; sizes and flags are copied first, then each file's exact bytes; a
+    flagged frame (its file passed the stream stride) is encoded on the host from a raw copy of that frame and named under 'video_fallback'.
+    route "host": the raw images travel and sd_jpeg_encode_bgr_host makes the same bytes on the writer threads; it needs png="host".
+    Works with images=False too (submit still gets the images then).  The manifest names the files under 'video'."""
 
     def __init__(self, directory: str, names, depth: float = 10.0, images: bool = True, ply: bool | str = True, items: bool = True, level: int = 1,
                  threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, png: str = "host", text: str = "json",
-                 render: RenderCamera | None = None):
+                 render: RenderCamera | None = None, video: Video | None = None):
+        import threading
         from concurrent.futures import ThreadPoolExecutor
 
         from .frame_io import default_decode_workers
@@ -605,6 +773,7 @@ class SequenceOutputs:
         self.set_text(text)
         self.set_ply("host" if isinstance(ply, bool) else ply)
         self.set_render(render)
+        self.set_video(video)
         self.directory, self.names, self.depth = directory, list(names), float(depth)
         self.images, self.ply, self.items, self.level = bool(images), bool(ply), bool(items), int(level)
         self.road_color, self.fence_color, self.alpha = tuple(road_color), tuple(fence_color), int(alpha)
@@ -623,6 +792,8 @@ class SequenceOutputs:
         self.manifest = None
         self.recomputed: list[int] = []                               # global indices of the frames recomputed on bf16x3 (on_range='recompute')
         self.ply_fallback: list[int] = []                             # global indices of the frames ply="device" sent through rw_ply_bytes
+        self.video_fallback: list[int] = []                           # global indices of the frames video route "device" encoded on the host
+        self._video_writer, self._video_next, self._video_turn = None, 0, threading.Condition()
 
     # ---------------------------------------------------------------- driver interface
     def set_png(self, png: str):
@@ -631,6 +802,8 @@ class SequenceOutputs:
             raise ValueError(f"png must be 'host' or 'device', got {png!r}")
         if getattr(self, "_k", 0):
             raise RuntimeError("SequenceOutputs.set_png after the first batch")
+        if png == "device" and getattr(self, "video", None) is not None and self.video.route == "host":
+            raise ValueError("Video(route='host') needs png='host': with png='device' no raw image reaches the host")
         self.png = png
 
     def set_text(self, text: str):
@@ -656,17 +829,29 @@ class SequenceOutputs:
             raise RuntimeError("SequenceOutputs.set_render after the first batch")
         self.render = render
 
+    def set_video(self, video):
+        """whether the result images also become a Motion-JPEG AVI: None or a Video (before the first batch)"""
+        _check_video(video)
+        if getattr(self, "_k", 0):
+            raise RuntimeError("SequenceOutputs.set_video after the first batch")
+        if video is not None and video.route == "host" and getattr(self, "png", "host") == "device":
+            raise ValueError("Video(route='host') needs png='host': with png='device' no raw image reaches the host")
+        self.video = video
+
     def begin(self, rank: int, world: int, lo: int, hi: int):
         """the shard [lo, hi) this rank writes (run_sequence_files calls it before the first batch)"""
         self.rank, self.world, self.shard = int(rank), int(world), (int(lo), int(hi))
 
-    def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None, ply_text=None, renders=None, render_streams=None):
+    def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None, ply_text=None, renders=None, render_streams=None,
+               video_streams=None):
         """one batch: ``records`` u8 [n,104] (sd_rw_result), ``size`` = (h, w) of the original frames, ``images`` u8 [n,h,w,3] (the composed
         result images) or None, ``final`` = dict(xyz f32 [n,cap,3], rgb u8 [n,cap,3], n i32 [n]) (process_batch(want_final=True)'s
         road_final) or None, ``png_streams`` = (streams u8 [n,stride], sizes i64 [n]) of Engine.encode_png in place of ``images`` on the
         device route, ``ply_text`` = (text u8 [capacity], offsets i64 [n+1], flags i32 [n]) of Engine.format_rw_ply on the ply="device" route
         (beside ``final``, which the flagged frames are written from), ``renders`` = u8 [n,height,width,3] of Engine.render_rw with render= (or
-        ``render_streams`` = Engine.encode_png of them on the png="device" route).  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
+        ``render_streams`` = Engine.encode_png of them on the png="device" route), ``video_streams`` = (streams u8 [n,stride], sizes i64 [n], flags
+        i32 [n]) of Engine.encode_jpeg with video= on its "device" route (beside ``images``, which a flagged frame is encoded from; its "host"
+        route needs only ``images``).  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
         tensors of every step)."""
         import torch
         if self.manifest is not None:
@@ -688,6 +873,13 @@ class SequenceOutputs:
             renders = None
         else:
             render_streams = None
+        video = None
+        if self.video is not None:
+            if self.video.route == "device" and video_streams is None:
+                raise ValueError("SequenceOutputs: video route 'device' needs the files of Engine.encode_jpeg (submit(video_streams=))")
+            if self.video.route == "host" and images is None:
+                raise ValueError("SequenceOutputs: video route 'host' needs the raw images (submit(images=))")
+            video = (self._k, images, video_streams if self.video.route == "device" else None)
         while len(self._jobs) >= 2:                                    # at most two batches in flight
             self._files.extend(self._jobs.pop(0).result())
         slot = self._k & 1
@@ -702,8 +894,10 @@ class SequenceOutputs:
             images = None
         else:
             png_streams = None
+        if not self.images and self.video is not None and self.video.route == "device":
+            images = None                                              # (composed for the video only: no raw image travels)
         self._jobs.append(self._batches.submit(self._write_batch, slot, lo, records, tuple(size), images, final, ev, png_streams, ply_text, renders,
-                                               render_streams))
+                                               render_streams, video))
 
     def mark_recomputed(self, frames):
         """global frame indices whose outputs came from the bf16x3 recompute (make_engine_step(on_range='recompute')): the manifest lists
@@ -724,6 +918,10 @@ class SequenceOutputs:
         self._jobs = []
         self._batches.shutdown()
         self._writers.shutdown()
+        video_files = []
+        if self._video_writer is not None:
+            video_files = self._video_writer.close()
+            self._files.extend(video_files)
         if err is not None and status == "ok":
             status = "error"
         self.manifest = os.path.join(self.directory, "manifest_rank{}.json".format(self.rank))
@@ -732,7 +930,9 @@ class SequenceOutputs:
             json.dump(dict(rank=self.rank, world=self.world, frames=list(self.shard), status=status, valid=status == "ok", files=files,
                            recomputed=[self.names[i] for i in sorted(set(self.recomputed))],
                            **(dict(ply_fallback=[self.names[i] for i in sorted(set(self.ply_fallback))]) if self.ply and self.ply_route == "device" else {}),
-                           **(dict(render=[f for f in files if f.startswith(SEQ_RENDER_DIR + os.sep)]) if self.render is not None else {})),
+                           **(dict(render=[f for f in files if f.startswith(SEQ_RENDER_DIR + os.sep)]) if self.render is not None else {}),
+                           **(dict(video=[os.path.relpath(p, self.directory) for p in video_files],
+                                   video_fallback=[self.names[i] for i in sorted(set(self.video_fallback))]) if self.video is not None else {})),
                       f, indent=1)
         if err is not None:
             raise err
@@ -834,7 +1034,94 @@ class SequenceOutputs:
                 s.synchronize()
         return rec.numpy(), None if img is None else img.numpy(), clouds, png, ply, None if rnd is None else rnd.numpy(), rpng
 
-    def _write_batch(self, slot, lo, records, size, images, final, ev, png_streams=None, ply_text=None, renders=None, render_streams=None):
+    def _video_frames(self, slot, lo, img, video, ev):
+        """the JPEG files of one batch's frames, in order: route "host": ``img`` (the raw images, already on the host) through
+        sd_jpeg_encode_bgr_host on the writer threads; route "device": sizes and flags cross first, then each file's exact bytes on this
+        slot's side stream; a flagged frame is copied raw and encoded on the host"""
+        import torch
+        _, vimg, vstreams = video
+        q = self.video.quality
+        if vstreams is None:
+            return list(self._writers.map(lambda a: encode_jpeg_host(a, q), list(img)))
+
+        def host(t):
+            return np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t)
+
+        streams, sizes, flags = vstreams
+        if ev is None or not isinstance(streams, torch.Tensor) or not streams.is_cuda:
+            st, sz, fl = host(streams), host(sizes), host(flags)
+            raw = {i: host(vimg[i]) for i in range(len(sz)) if fl[i] != 0}
+        else:
+            s = self._streams[slot]
+            with torch.cuda.stream(s):
+                s.wait_event(ev)
+                vsz = self._pinned(slot, "video_sizes", tuple(sizes.shape), torch.int64, True)
+                vsz.copy_(sizes, non_blocking=True)
+                vfl = self._pinned(slot, "video_flags", tuple(flags.shape), torch.int32, True)
+                vfl.copy_(flags, non_blocking=True)
+                s.synchronize()
+                sz, fl = vsz.numpy(), vfl.numpy()
+                total = int(sz.sum())
+                vbuf = self._pinned(slot, "video", (max(total, 1),), torch.uint8, True)
+                off = np.concatenate([[0], np.cumsum(sz)]).astype(np.int64)
+                raw = {}
+                for i in range(len(sz)):
+                    if fl[i] != 0:
+                        if vimg is None:
+                            raise ValueError("SequenceOutputs: a flagged video frame needs the raw images (submit(images=))")
+                        raw[i] = self._pinned(slot, f"video_raw{i}", tuple(vimg[i].shape), torch.uint8, True)
+                        raw[i].copy_(vimg[i], non_blocking=True)
+                    elif sz[i]:
+                        vbuf[int(off[i]):int(off[i + 1])].copy_(streams[i, :int(sz[i])], non_blocking=True)
+                s.synchronize()
+                raw = {i: t.numpy() for i, t in raw.items()}
+                flat = vbuf.numpy()
+                st = None
+        out = []
+        for i in range(len(sz)):
+            if fl[i] != 0:
+                self.video_fallback.append(lo + i)
+                out.append(encode_jpeg_host(raw[i], q))
+            elif st is not None:
+                out.append(st[i, :int(sz[i])].tobytes())
+            else:
+                out.append(flat[int(off[i]):int(off[i + 1])].tobytes())
+        return out
+
+    def _video_batch(self, slot, lo, size, img, video, ev):
+        """encode or fetch this batch's frames, then append them when it is this batch's turn (batches finish in any order)"""
+        frames = None
+        try:
+            frames = self._video_frames(slot, lo, img, video, ev)
+        finally:
+            with self._video_turn:
+                while self._video_next != video[0]:
+                    self._video_turn.wait()
+                try:
+                    if frames is not None:
+                        if self._video_writer is None:
+                            name = "result_imgs.avi" if self.world == 1 else "result_imgs_rank{}.avi".format(self.rank)
+                            self._video_writer = MjpegAviWriter(os.path.join(self.directory, name), size[1], size[0], self.video.fps)
+                        for fr in frames:
+                            self._video_writer.append(fr)
+                finally:
+                    self._video_next += 1
+                    self._video_turn.notify_all()
+
+    def _write_batch(self, slot, lo, records, size, images, final, ev, png_streams=None, ply_text=None, renders=None, render_streams=None, video=None):
+        try:
+            return self._write_batch_files(slot, lo, records, size, images, final, ev, png_streams, ply_text, renders, render_streams, video)
+        except BaseException:
+            if video is not None:                                      # (the batches behind this one must not wait for its turn for ever)
+                with self._video_turn:
+                    while self._video_next < video[0]:
+                        self._video_turn.wait()
+                    if self._video_next == video[0]:
+                        self._video_next += 1
+                        self._video_turn.notify_all()
+            raise
+
+    def _write_batch_files(self, slot, lo, records, size, images, final, ev, png_streams, ply_text, renders, render_streams, video):
         from .engine import RW_DTYPE
         rec_u8, img, clouds, png, ply, rnd, rpng = self._to_host(slot, lo, records, images, final, ev, png_streams, ply_text, renders, render_streams)
         recs = np.ascontiguousarray(rec_u8).view(RW_DTYPE).reshape(-1)
@@ -890,5 +1177,7 @@ class SequenceOutputs:
             else:
                 assert rnd.shape == (n, rh, rw, 3), (rnd.shape, (n, rh, rw))
                 files.extend(write_png_batch(paths, rnd, self.level, self.threads))
+        if video is not None:
+            self._video_batch(slot, lo, size, img, video, ev)
         files.extend(f.result() for f in futs)
         return files
