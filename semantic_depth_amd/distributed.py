@@ -105,16 +105,9 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     written before are then not valid outputs; the exception still propagates).
     ``jpeg`` ("host" | "device") and ``engine`` go to the feeder: with "device" the JPEG frames are only entropy-decoded on the host and
     reconstructed on the GPU by ``engine`` (default: ``step.engine``, set by make_engine_step); the frames are the same bytes.
-    ``png`` ("host" | "device", None = what the SequenceOutputs was built with): where the result images are compressed
-    (SequenceOutputs.set_png; "device" needs the step of make_engine_step, which encodes the streams on the GPU).
-    ``ply`` ("host" | "device", None = what the SequenceOutputs was built with): where the road PLYs are formatted (SequenceOutputs.set_ply;
-    "device" needs the step of make_engine_step, which formats the text on the GPU).
-    ``text`` ("json" | "draw", None = what the SequenceOutputs was built with): whether the banner text is rasterised into the result images
-    (SequenceOutputs.set_text; "draw" needs the step of make_engine_step, which draws it on the GPU).
-    ``render`` (an outputs.RenderCamera, None = what the SequenceOutputs was built with): the view every frame's road cloud is rendered from
-    (SequenceOutputs.set_render; needs the step of make_engine_step, which renders on the GPU).
-    ``video`` (an outputs.Video, None = what the SequenceOutputs was built with): the result images also become a Motion-JPEG AVI
-    (SequenceOutputs.set_video; its "device" route needs the step of make_engine_step, which encodes the frames on the GPU)."""
+    ``png``, ``ply``, ``text``, ``render``, ``video`` (None = what the SequenceOutputs was built with) go to SequenceOutputs.configure before
+    the first batch: the choices are described there, and what the step of make_engine_step does for each -- all but png="host",
+    ply="host", text="json" and Video(route="host") need that step -- in its own docstring."""
     from .frame_io import FrameFeeder
     engine = engine if engine is not None else getattr(step, "engine", None)
     paths = sorted(paths)
@@ -126,16 +119,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     if outputs is not None:
         if len(outputs.names) != n_frames:
             raise ValueError(f"SequenceOutputs has {len(outputs.names)} names for {n_frames} frames")
-        if png is not None:
-            outputs.set_png(png)
-        if ply is not None:
-            outputs.set_ply(ply)
-        if text is not None:
-            outputs.set_text(text)
-        if render is not None:
-            outputs.set_render(render)
-        if video is not None:
-            outputs.set_video(video)
+        outputs.configure(png, ply, text, render, video)
         outputs.begin(rank, world, lo, hi)
     try:
         parts = []
@@ -173,37 +157,29 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     ``on_range`` (None = the engine's own mode; else it must match Engine(on_range=)): with 'recompute' the frames that left the fp16 range
     are recomputed on bf16x3 inside process_batch, so every batch's records, images and PLYs are final before gather_records and no rank
     raises from ``step.finish`` for them; ``step.recomputed`` (and the manifest's 'recomputed' names) lists those frames.
-    ``png`` ("host" | "device", None = what ``outputs`` was built with): with "device" Engine.encode_png turns the composed images into
-    zlib streams on the step's stream, right behind the compose launch, and only the streams' bytes travel to the host.
-    ``ply`` ("host" | "device", None = what ``outputs`` was built with): with "device" Engine.format_rw_ply turns the final road clouds and
-    the records into the text of the ``_rw.ply`` files on the step's stream, and only that text travels to the host (the raw cloud of a
-    frame the device did not format still does: SequenceOutputs).
-    ``text`` ("json" | "draw", None = what ``outputs`` was built with): with "draw" Engine.draw_result_text rasterises the banner text into
-    the composed images on the step's stream, right behind the compose launch -- before Engine.encode_png on the device PNG route, before
-    the copy to the host on the other -- so both routes write it; the ``_overlay.json`` files are written as before.
-    ``render`` (an outputs.RenderCamera, None = what ``outputs`` was built with): with a camera process_batch keeps the final road clouds even
-    when no PLY is asked for, and Engine.render_rw draws them and the road-width line behind that camera on the step's stream, behind the road
-    chain; the ``<name>_render.png`` files go through the PNG route chosen (png="device": Engine.encode_png on the renders).
-    ``video`` (an outputs.Video, None = what ``outputs`` was built with): the composed images -- composed for this alone when ``outputs.images``
-    is off -- also become the frames of the result video; on its "device" route Engine.encode_jpeg makes every frame's JPEG file on the step's
-    stream, behind Engine.draw_result_text, with a stream stride of half the raw image (a frame that needs more is flagged and encoded on the
-    host from its raw copy)."""
+    ``png``, ``ply``, ``text``, ``render``, ``video`` (None = what ``outputs`` was built with) go to SequenceOutputs.configure, which
+    describes the choices; what the step does for each, all on its own stream:
+    png="device": Engine.encode_png turns the composed images into zlib streams right behind the compose launch (behind the text and the
+    video frames when those are on), and only the streams' bytes travel to the host.
+    ply="device": Engine.format_rw_ply turns the final road clouds and the records into the text of the ``_rw.ply`` files, and only that
+    text travels to the host (the raw cloud of a frame the device did not format still does).
+    text="draw": Engine.draw_result_text rasterises the banner text into the composed images right behind the compose launch -- before
+    Engine.encode_png on the device PNG route, before the copy to the host on the other -- so both routes write it; the ``_overlay.json``
+    files are written as before.
+    render=camera: process_batch keeps the final road clouds even when no PLY is asked for, and Engine.render_rw draws them and the
+    road-width line behind that camera, behind the road chain; the ``<name>_render.png`` files go through the PNG route chosen
+    (png="device": Engine.encode_png on the renders).
+    video=Video: the composed images -- composed for this alone when ``outputs.images`` is off -- also become the frames of the result
+    video; on its "device" route Engine.encode_jpeg makes every frame's JPEG file behind Engine.draw_result_text, with a stream stride of
+    half the raw image (a frame that needs more is flagged and encoded on the host from its raw copy)."""
     from .engine import RoadWidthParams
     from .recompute import check_mode
 
     if on_range is not None and check_mode(on_range) != getattr(engine, "on_range", "raise"):
         raise ValueError(f"make_engine_step(on_range={on_range!r}) on an engine built with on_range={getattr(engine, 'on_range', 'raise')!r}")
     prm = params or RoadWidthParams()
-    if png is not None and outputs is not None:
-        outputs.set_png(png)
-    if ply is not None and outputs is not None:
-        outputs.set_ply(ply)
-    if text is not None and outputs is not None:
-        outputs.set_text(text)
-    if render is not None and outputs is not None:
-        outputs.set_render(render)
-    if video is not None and outputs is not None:
-        outputs.set_video(video)
+    if outputs is not None:
+        outputs.configure(png, ply, text, render, video)
     recomputed: list[int] = []
 
     def note(lo):
@@ -223,32 +199,29 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
             rec = engine.process_batch(fr, cams, prm, approach=approach)["records"]
             note(lo)
             return rec
-        camera = getattr(outputs, "render", None)
+        camera, vid, device_png = outputs.render, outputs.video, outputs.png == "device"
         out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.ply or camera is not None)
         note(lo)
         rec = out["records"]
         images = None
         more = {}
-        if outputs.ply and getattr(outputs, "ply_route", "host") == "device":     # the text of the PLY files, on the step's stream
+        if outputs.ply and outputs.ply_route == "device":           # the text of the PLY files
             more["ply_text"] = engine.format_rw_ply(out["road_final"], rec)
-        if camera is not None:                                     # the rendered clouds, on the step's stream, behind the road chain
+        if camera is not None:                                     # the rendered clouds, behind the road chain
             renders = engine.render_rw(out["road_final"], rec, camera)[0]
-            if getattr(outputs, "png", "host") == "device":
+            if device_png:
                 more["render_streams"] = engine.encode_png(renders)
             else:
                 more["renders"] = renders
-        vid = getattr(outputs, "video", None)
         if outputs.images or vid is not None:
             images = engine.compose_result_frames(fr, out["seg"]["road"], out["seg"]["fence"], rec, size[0], size[1], outputs.road_color,
                                                   outputs.fence_color, outputs.alpha)
-            if getattr(outputs, "text", "json") == "draw":         # the banner text, on the step's stream, before either PNG route reads the images
+            if outputs.text == "draw":                             # the banner text, before anything reads the images
                 engine.draw_result_text(images, rec, outputs.depth)
-            if vid is not None and vid.route == "device":          # the frames of the video, behind the text, on the step's stream
+            if vid is not None and vid.route == "device":          # the frames of the video, behind the text
                 more["video_streams"] = engine.encode_jpeg(images, vid.quality, stream_stride=1024 + size[0] * size[1] * 3 // 2)
-            if outputs.images and getattr(outputs, "png", "host") == "device":        # the zlib streams right behind the compose launch, on the step's stream
-                outputs.submit(lo, rec, size, images=images if vid is not None else None, final=out.get("road_final") if outputs.ply else None,
-                               png_streams=engine.encode_png(images), **more)
-                return rec
+            if outputs.images and device_png:                      # the zlib streams, behind the compose launch
+                more["png_streams"] = engine.encode_png(images)
         outputs.submit(lo, rec, size, images=images, final=out.get("road_final") if outputs.ply else None, **more)
         return rec
 

@@ -24,6 +24,7 @@ the GPU for the sequence tool.  The strings, origins, scales, colours and thickn
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import json
 import os
@@ -720,6 +721,131 @@ def rw_ply_bytes(road3D, road_colors, left_pt_rw=None, right_pt_rw=None) -> byte
     return PointCloud2Ply.ply_header.format(vertex_count=len(pts)).encode() + format_rows(pts, col, threads=1)
 
 
+@dataclasses.dataclass
+class _Batch:
+    """one batch as submit() accepted it: device or host tensors, the payloads of the routes that are off already None"""
+    slot: int                               # which of the two in-flight slots (stager, pinned buffers) it travels through
+    k: int                                  # batch index: its turn in the video
+    lo: int
+    size: tuple
+    ev: object                              # an event of the producing stream, None for a host batch
+    records: object
+    images: object = None
+    final: object = None
+    png_streams: object = None
+    ply_text: object = None
+    renders: object = None
+    render_streams: object = None
+    video_streams: object = None
+
+
+@dataclasses.dataclass
+class _HostBatch:
+    """numpy views of a _Batch on the host (pinned staging or the host tensors themselves), valid until its slot's next batch"""
+    records: np.ndarray
+    images: np.ndarray | None = None        # the raw images, when they travel whole
+    clouds: list | None = None              # per frame (xyz, rgb), None for a frame whose text the device formatted
+    png: np.ndarray | None = None           # [n,stride] zlib streams, png[i, :png_sizes[i]] copied
+    png_sizes: np.ndarray | None = None
+    ply_text: np.ndarray | None = None      # frame i's file is ply_text[ply_offsets[i]:ply_offsets[i + 1]] where ply_flags[i] == 0
+    ply_offsets: np.ndarray | None = None
+    ply_flags: np.ndarray | None = None
+    renders: np.ndarray | None = None
+    render_png: np.ndarray | None = None
+    render_sizes: np.ndarray | None = None
+    video: np.ndarray | None = None         # [n,stride] JPEG files, video[i, :video_sizes[i]] copied where video_flags[i] == 0
+    video_sizes: np.ndarray | None = None
+    video_flags: np.ndarray | None = None
+    video_raw: dict = dataclasses.field(default_factory=dict)      # frame -> raw image of a flagged video frame
+
+
+class _Stager:
+    """the device-to-host transfer of one in-flight slot of SequenceOutputs: pinned buffers that only grow, a side stream, and the wait for
+    the batch's event.  Inside ``with stager.behind(ev):`` every method returns a numpy view: of a pinned copy enqueued on the side stream
+    (valid after the next ``sync()``) for a device tensor, of the input itself, without a copy, for a host tensor, a numpy array or a host
+    batch (``ev`` None)."""
+
+    def __init__(self):
+        self._buffers, self._stream, self._ev = {}, None, None
+
+    def event(self, t):
+        """an event on the current stream of ``t``'s device for behind() to wait for; None when ``t`` is on the host"""
+        import torch
+        if not t.is_cuda:
+            return None
+        if self._stream is None:
+            self._stream = torch.cuda.Stream(t.device)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(t.device))
+        return ev
+
+    @contextlib.contextmanager
+    def behind(self, ev):
+        import torch
+        self._ev = ev
+        if ev is None:
+            yield
+            return
+        with torch.cuda.stream(self._stream):
+            self._stream.wait_event(ev)
+            yield
+
+    def sync(self):
+        if self._ev is not None:
+            self._stream.synchronize()
+
+    def _pinned(self, key: str, shape, dtype):
+        import torch
+        buf = self._buffers.get(key)
+        numel = int(np.prod(shape))
+        if buf is None or buf.numel() < numel or buf.dtype != dtype:
+            buf = self._buffers[key] = torch.empty(max(numel, 1), dtype=dtype, pin_memory=True)
+        return buf[:numel].view(*shape)
+
+    def _on_host(self, t):
+        import torch
+        if self._ev is not None and isinstance(t, torch.Tensor) and t.is_cuda:
+            return None
+        return np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t)
+
+    def fixed(self, key: str, t):
+        """a tensor whose shape is known (None stays None)"""
+        if t is None:
+            return None
+        a = self._on_host(t)
+        if a is None:
+            buf = self._pinned(key, tuple(t.shape), t.dtype)
+            buf.copy_(t, non_blocking=True)
+            a = buf.numpy()
+        return a
+
+    def rows(self, key: str, src, sizes):
+        """``src`` [n,stride] of which only src[i, :sizes[i]] is meaningful (``sizes``: on the host) -> an [n,stride] view; only those bytes
+        are copied, a row of size 0 not at all"""
+        a = self._on_host(src)
+        if a is None:
+            buf = self._pinned(key, tuple(src.shape), src.dtype)
+            for i, size in enumerate(sizes):
+                if size:
+                    buf[i, :int(size)].copy_(src[i, :int(size)], non_blocking=True)
+            a = buf.numpy()
+        return a
+
+    def ragged(self, key: str, src, counts):
+        """``src`` [n,cap,...] -> the list of src[i, :counts[i]] (``counts``: on the host); device rows are packed back to back into one
+        pinned buffer of sum(counts) rows, a row of count 0 is not copied"""
+        a = self._on_host(src)
+        if a is not None:
+            return [a[i, :c] for i, c in enumerate(counts)]
+        off = np.concatenate([[0], np.cumsum(counts)])
+        buf = self._pinned(key, (int(off[-1]),) + tuple(src.shape[2:]), src.dtype)
+        for i, c in enumerate(counts):
+            if c:
+                buf[off[i]:off[i + 1]].copy_(src[i, :c], non_blocking=True)
+        a = buf.numpy()
+        return [a[off[i]:off[i + 1]] for i in range(len(counts))]
+
+
 class SequenceOutputs:
     """what the sequence tool writes for every frame (seq:303-361), fed batch by batch by the step of ``make_engine_step(..., outputs=)``:
 
@@ -738,6 +864,9 @@ class SequenceOutputs:
     tensors of one batch, copies them into pinned staging on a side stream behind an event of the current stream, and writes them on
     worker threads -- at most two batches in flight -- with the per-pixel and per-point work in native code (no interpreter lock).
     ``threads``: native encoder threads per batch and PLY writer threads (0: frame_io.default_decode_workers()).
+    The five choices that follow can also be made after construction and before the first batch, by configure() (all at once; what
+    make_engine_step and run_sequence_files do with their keywords of the same names) or by set_png / set_ply / set_text / set_render /
+    set_video; the "device" routes, text="draw", render= and video= need the step of make_engine_step, which does the GPU half.
     ``png``: "host" (default) copies the raw images to the host and deflates them there (sd_png_encode_bgr_files at ``level``); "device"
     takes each frame's finished zlib stream from the GPU (Engine.encode_png, submit(png_streams=)): the sizes are copied first, then each
     stream's exact byte count, and the host only writes the PNG chunks (sd_png_write_streams_files).  Same names, manifest and pixels.
@@ -745,7 +874,8 @@ class SequenceOutputs:
     the step hands submit(ply_text=) the finished text of every file (Engine.format_rw_ply); the offsets and flags are copied first, then
     text[:offsets[n]] in one copy, and the host only writes each slice.  A frame the device did not format (a non-zero flag: a non-finite
     coordinate or |v| >= 2^31) has its raw cloud copied and goes through rw_ply_bytes; the manifest names those frames under 'ply_fallback'.
-    Same names and the same bytes.
+    Same names and the same bytes.  (Whether PLYs are written at all stays what the constructor was given, ``self.ply``; the route is
+    ``self.ply_route``.)
     ``text``: "json" (default: the banner of the images stays empty, the text is in the ``_overlay.json`` files) or "draw": the step of
     make_engine_step also rasterises it into the composed images on the GPU (Engine.draw_result_text) before they reach either PNG route.
     ``render``: None (default: nothing more is written, the manifest is what it was) or a RenderCamera: the step of make_engine_step also
@@ -760,6 +890,8 @@ class SequenceOutputs:
     route "host": the raw images travel and sd_jpeg_encode_bgr_host makes the same bytes on the writer threads; it needs png="host".
     Works with images=False too (submit still gets the images then).  The manifest names the files under 'video'."""
 
+    png, ply_route, text, render, video, _k = "host", "host", "json", None, None, 0          # (what configure() starts from)
+
     def __init__(self, directory: str, names, depth: float = 10.0, images: bool = True, ply: bool | str = True, items: bool = True, level: int = 1,
                  threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, png: str = "host", text: str = "json",
                  render: RenderCamera | None = None, video: Video | None = None):
@@ -769,11 +901,9 @@ class SequenceOutputs:
         from .frame_io import default_decode_workers
         if not 0 <= level <= 9:
             raise ValueError("PNG compression level must be 0..9")
-        self.set_png(png)
-        self.set_text(text)
-        self.set_ply("host" if isinstance(ply, bool) else ply)
-        self.set_render(render)
-        self.set_video(video)
+        if png is None or ply is None or text is None:                # (None leaves a choice as it is only in configure)
+            raise ValueError(f"png, ply and text must be given, got {png!r}, {ply!r}, {text!r}")
+        self.configure(png, "host" if isinstance(ply, bool) else ply, text, render, video)
         self.directory, self.names, self.depth = directory, list(names), float(depth)
         self.images, self.ply, self.items, self.level = bool(images), bool(ply), bool(items), int(level)
         self.road_color, self.fence_color, self.alpha = tuple(road_color), tuple(fence_color), int(alpha)
@@ -786,9 +916,8 @@ class SequenceOutputs:
         self.rank, self.world, self.shard = 0, 1, (0, len(self.names))
         self._batches = ThreadPoolExecutor(max_workers=2)           # one per batch in flight
         self._writers = ThreadPoolExecutor(max_workers=self.threads)  # PLY / JSON files of a batch
-        self._jobs, self._k, self._files = [], 0, []
-        self._staging = [dict(), dict()]                             # pinned host buffers per in-flight slot
-        self._streams = None
+        self._jobs, self._files = [], []
+        self._stagers = [_Stager(), _Stager()]                       # one per in-flight slot
         self.manifest = None
         self.recomputed: list[int] = []                               # global indices of the frames recomputed on bf16x3 (on_range='recompute')
         self.ply_fallback: list[int] = []                             # global indices of the frames ply="device" sent through rw_ply_bytes
@@ -796,51 +925,56 @@ class SequenceOutputs:
         self._video_writer, self._video_next, self._video_turn = None, 0, threading.Condition()
 
     # ---------------------------------------------------------------- driver interface
-    def set_png(self, png: str):
-        """where the result images are compressed: "host" or "device" (before the first batch)"""
+    def configure(self, png: str | None = None, ply: str | None = None, text: str | None = None, render=None, video=None):
+        """choose the routes described in the class docstring, before the first batch: ``png`` and ``ply`` "host" or "device", ``text`` "json"
+        or "draw", ``render`` a RenderCamera, ``video`` a Video; None leaves a choice as it is.  Nothing changes when the resulting
+        combination is refused."""
+        png = self.png if png is None else png
+        ply = self.ply_route if ply is None else ply
+        text = self.text if text is None else text
+        render = self.render if render is None else render
+        video = self.video if video is None else video
         if png not in ("host", "device"):
             raise ValueError(f"png must be 'host' or 'device', got {png!r}")
-        if getattr(self, "_k", 0):
-            raise RuntimeError("SequenceOutputs.set_png after the first batch")
-        if png == "device" and getattr(self, "video", None) is not None and self.video.route == "host":
+        if ply not in ("host", "device") or isinstance(ply, bool):
+            raise ValueError(f"ply must be 'host' or 'device', got {ply!r}")
+        _check_text(text)
+        _check_render(render)
+        _check_video(video)
+        if self._k:
+            raise RuntimeError("SequenceOutputs.configure after the first batch")
+        if png == "device" and video is not None and video.route == "host":
             raise ValueError("Video(route='host') needs png='host': with png='device' no raw image reaches the host")
-        self.png = png
+        self.png, self.ply_route, self.text, self.render, self.video = png, ply, text, render, video
+
+    def set_png(self, png: str):
+        """where the result images are compressed: "host" or "device" (before the first batch)"""
+        self.configure(png=png)
+
+    def set_ply(self, ply: str):
+        """where the road PLYs are formatted: "host" or "device" (before the first batch)"""
+        self.configure(ply=ply)
 
     def set_text(self, text: str):
         """whether the banner text is drawn into the result images: "json" or "draw" (before the first batch)"""
-        _check_text(text)
-        if getattr(self, "_k", 0):
-            raise RuntimeError("SequenceOutputs.set_text after the first batch")
-        self.text = text
-
-    def set_ply(self, ply: str):
-        """where the road PLYs are formatted: "host" or "device" (before the first batch; whether they are written at all is ``ply`` of the
-        constructor, kept in ``self.ply``)"""
-        if ply not in ("host", "device") or isinstance(ply, bool):
-            raise ValueError(f"ply must be 'host' or 'device', got {ply!r}")
-        if getattr(self, "_k", 0):
-            raise RuntimeError("SequenceOutputs.set_ply after the first batch")
-        self.ply_route = ply
+        self.configure(text=text)
 
     def set_render(self, render):
-        """whether the road clouds are rendered: None or the RenderCamera of the view (before the first batch)"""
-        _check_render(render)
-        if getattr(self, "_k", 0):
-            raise RuntimeError("SequenceOutputs.set_render after the first batch")
-        self.render = render
+        """the RenderCamera the road clouds are rendered from (before the first batch)"""
+        self.configure(render=render)
 
     def set_video(self, video):
-        """whether the result images also become a Motion-JPEG AVI: None or a Video (before the first batch)"""
-        _check_video(video)
-        if getattr(self, "_k", 0):
-            raise RuntimeError("SequenceOutputs.set_video after the first batch")
-        if video is not None and video.route == "host" and getattr(self, "png", "host") == "device":
-            raise ValueError("Video(route='host') needs png='host': with png='device' no raw image reaches the host")
-        self.video = video
+        """the Video the result images also become (before the first batch)"""
+        self.configure(video=video)
 
     def begin(self, rank: int, world: int, lo: int, hi: int):
         """the shard [lo, hi) this rank writes (run_sequence_files calls it before the first batch)"""
         self.rank, self.world, self.shard = int(rank), int(world), (int(lo), int(hi))
+
+    @property
+    def _images_travel(self) -> bool:
+        """whether the raw images cross to the host whole: for the host PNG route or the host video route"""
+        return self.png == "host" and (self.images or self.video is not None and self.video.route == "host")
 
     def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None, ply_text=None, renders=None, render_streams=None,
                video_streams=None):
@@ -853,51 +987,35 @@ class SequenceOutputs:
         i32 [n]) of Engine.encode_jpeg with video= on its "device" route (beside ``images``, which a flagged frame is encoded from; its "host"
         route needs only ``images``).  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
         tensors of every step)."""
-        import torch
         if self.manifest is not None:
             raise RuntimeError("SequenceOutputs.submit after close")
         n = int(records.shape[0])
+        device_png, device_video = self.png == "device", self.video is not None and self.video.route == "device"
         if lo < 0 or lo + n > len(self.names):
             raise ValueError(f"frames {lo}..{lo + n - 1} are beyond the {len(self.names)} names")
-        if self.images and (png_streams if self.png == "device" else images) is None or self.ply and final is None:
+        if self.images and (png_streams if device_png else images) is None or self.ply and final is None:
             raise ValueError("SequenceOutputs: this batch lacks the images (png='device': the streams) / final road clouds the outputs ask for")
         if self.ply and self.ply_route == "device" and ply_text is None:
             raise ValueError("SequenceOutputs: ply='device' needs the text of Engine.format_rw_ply (submit(ply_text=))")
-        if not self.ply or self.ply_route != "device":
-            ply_text = None
-        if self.render is not None and (render_streams if self.png == "device" else renders) is None:
+        if self.render is not None and (render_streams if device_png else renders) is None:
             raise ValueError("SequenceOutputs: render= needs the images of Engine.render_rw (submit(renders=); png='device': render_streams=)")
-        if self.render is None:
-            renders = render_streams = None
-        elif self.png == "device":
-            renders = None
-        else:
-            render_streams = None
-        video = None
-        if self.video is not None:
-            if self.video.route == "device" and video_streams is None:
-                raise ValueError("SequenceOutputs: video route 'device' needs the files of Engine.encode_jpeg (submit(video_streams=))")
-            if self.video.route == "host" and images is None:
-                raise ValueError("SequenceOutputs: video route 'host' needs the raw images (submit(images=))")
-            video = (self._k, images, video_streams if self.video.route == "device" else None)
+        if device_video and video_streams is None:
+            raise ValueError("SequenceOutputs: video route 'device' needs the files of Engine.encode_jpeg (submit(video_streams=))")
+        if self.video is not None and not device_video and images is None:
+            raise ValueError("SequenceOutputs: video route 'host' needs the raw images (submit(images=))")
         while len(self._jobs) >= 2:                                    # at most two batches in flight
             self._files.extend(self._jobs.pop(0).result())
         slot = self._k & 1
+        batch = _Batch(slot, self._k, lo, tuple(size), self._stagers[slot].event(records), records,
+                       images=images if self._images_travel or device_video else None,      # (device video: a flagged frame is encoded from its raw image)
+                       final=final,
+                       png_streams=png_streams if device_png else None,
+                       ply_text=ply_text if self.ply and self.ply_route == "device" else None,
+                       renders=renders if self.render is not None and not device_png else None,
+                       render_streams=render_streams if self.render is not None and device_png else None,
+                       video_streams=video_streams if device_video else None)
         self._k += 1
-        ev = None
-        if records.is_cuda:
-            if self._streams is None:
-                self._streams = [torch.cuda.Stream(records.device), torch.cuda.Stream(records.device)]
-            ev = torch.cuda.Event()
-            ev.record(torch.cuda.current_stream(records.device))
-        if self.png == "device":
-            images = None
-        else:
-            png_streams = None
-        if not self.images and self.video is not None and self.video.route == "device":
-            images = None                                              # (composed for the video only: no raw image travels)
-        self._jobs.append(self._batches.submit(self._write_batch, slot, lo, records, tuple(size), images, final, ev, png_streams, ply_text, renders,
-                                               render_streams, video))
+        self._jobs.append(self._batches.submit(self._write_batch, batch))
 
     def mark_recomputed(self, frames):
         """global frame indices whose outputs came from the bf16x3 recompute (make_engine_step(on_range='recompute')): the manifest lists
@@ -926,258 +1044,151 @@ class SequenceOutputs:
             status = "error"
         self.manifest = os.path.join(self.directory, "manifest_rank{}.json".format(self.rank))
         files = sorted(os.path.relpath(p, self.directory) for p in self._files)
+
+        def named(frames):
+            return [self.names[i] for i in sorted(set(frames))]
+
+        manifest = dict(rank=self.rank, world=self.world, frames=list(self.shard), status=status, valid=status == "ok", files=files,
+                        recomputed=named(self.recomputed))
+        if self.ply and self.ply_route == "device":
+            manifest["ply_fallback"] = named(self.ply_fallback)
+        if self.render is not None:
+            manifest["render"] = [f for f in files if f.startswith(SEQ_RENDER_DIR + os.sep)]
+        if self.video is not None:
+            manifest["video"] = [os.path.relpath(p, self.directory) for p in video_files]
+            manifest["video_fallback"] = named(self.video_fallback)
         with open(self.manifest, "w") as f:
-            json.dump(dict(rank=self.rank, world=self.world, frames=list(self.shard), status=status, valid=status == "ok", files=files,
-                           recomputed=[self.names[i] for i in sorted(set(self.recomputed))],
-                           **(dict(ply_fallback=[self.names[i] for i in sorted(set(self.ply_fallback))]) if self.ply and self.ply_route == "device" else {}),
-                           **(dict(render=[f for f in files if f.startswith(SEQ_RENDER_DIR + os.sep)]) if self.render is not None else {}),
-                           **(dict(video=[os.path.relpath(p, self.directory) for p in video_files],
-                                   video_fallback=[self.names[i] for i in sorted(set(self.video_fallback))]) if self.video is not None else {})),
-                      f, indent=1)
+            json.dump(manifest, f, indent=1)
         if err is not None:
             raise err
         return self.manifest
 
     # ---------------------------------------------------------------- worker side
-    def _pinned(self, slot: int, key: str, shape, dtype, pin: bool):
-        import torch
-        buf = self._staging[slot].get(key)
-        numel = int(np.prod(shape))
-        if buf is None or buf.numel() < numel or buf.dtype != dtype:
-            buf = self._staging[slot][key] = torch.empty(max(numel, 1), dtype=dtype, pin_memory=pin)
-        return buf[:numel].view(*shape)
+    def _fetch(self, b: _Batch) -> _HostBatch:
+        """the batch on the host, through its slot's stager, in two phases: first everything whose shape is known -- records, whole
+        images, renders, and the counts, sizes, offsets and flags -- then, once those are there, exactly what they call for: each stream's
+        bytes, the text in front of offsets[n], the clouds of the frames the device did not format (all of them without ``ply_text``) and
+        the raw image of a flagged video frame"""
+        st = self._stagers[b.slot]
+        with st.behind(b.ev):
+            host = _HostBatch(st.fixed("rec", b.records), images=st.fixed("img", b.images if self._images_travel else None),
+                              renders=st.fixed("render", b.renders))
+            counts = None if b.final is None else st.fixed("n", b.final["n"])
+            if b.png_streams is not None:
+                host.png_sizes = st.fixed("png_sizes", b.png_streams[1])
+            if b.render_streams is not None:
+                host.render_sizes = st.fixed("render_sizes", b.render_streams[1])
+            if b.ply_text is not None:
+                host.ply_offsets, host.ply_flags = st.fixed("ply_offsets", b.ply_text[1]), st.fixed("ply_flags", b.ply_text[2])
+            if b.video_streams is not None:
+                host.video_sizes, host.video_flags = st.fixed("video_sizes", b.video_streams[1]), st.fixed("video_flags", b.video_streams[2])
+            st.sync()
+            if b.png_streams is not None:
+                host.png = st.rows("png", b.png_streams[0], host.png_sizes)
+            if b.render_streams is not None:
+                host.render_png = st.rows("render_png", b.render_streams[0], host.render_sizes)
+            if b.ply_text is not None:
+                host.ply_text = st.fixed("ply_text", b.ply_text[0][:int(host.ply_offsets[-1])])
+            if b.final is not None:
+                raw = np.ones(len(counts), bool) if b.ply_text is None else host.ply_flags != 0
+                cn = np.where(raw, counts, 0).astype(np.int64)
+                xyz, rgb = st.ragged("xyz", b.final["xyz"], cn), st.ragged("rgb", b.final["rgb"], cn)
+                host.clouds = [(xyz[i], rgb[i]) if raw[i] else None for i in range(len(cn))]
+            if b.video_streams is not None:
+                host.video = st.rows("video", b.video_streams[0], np.where(host.video_flags != 0, 0, host.video_sizes))
+                for i in np.flatnonzero(host.video_flags):
+                    if b.images is None:
+                        raise ValueError("SequenceOutputs: a flagged video frame needs the raw images (submit(images=))")
+                    host.video_raw[int(i)] = host.images[i] if host.images is not None else st.fixed(f"video_raw{i}", b.images[i])
+            st.sync()
+        return host
 
-    def _to_host(self, slot, lo, records, images, final, ev, png_streams=None, ply_text=None, renders=None, render_streams=None):
-        """numpy views of the batch (device tensors: copied into pinned staging on this slot's side stream behind ``ev``): records, images,
-        clouds, from ``png_streams`` (streams [n,stride], sizes [n]) of which only streams[i, :sizes[i]] was copied, and from ``ply_text``
-        (text [offsets[n]], offsets [n+1], flags [n]); with ``ply_text`` only the clouds of the frames with a non-zero flag are copied
-        (the others are None); ``renders`` and ``render_streams`` travel like ``images`` and ``png_streams`` and come back last"""
-        import torch
-
-        def host(t):
-            return np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t)
-
-        if ev is None:
-            rec = records.numpy() if isinstance(records, torch.Tensor) else np.asarray(records)
-            img = None if images is None else (images.numpy() if isinstance(images, torch.Tensor) else np.asarray(images))
-            clouds = None
-            if final is not None:
-                cnt = host(final["n"])
-                xyz, rgb = (host(final[k]) for k in ("xyz", "rgb"))
-                clouds = [(xyz[i, :cnt[i]], rgb[i, :cnt[i]]) for i in range(len(cnt))]
-            return (rec, img, clouds, None if png_streams is None else (host(png_streams[0]), host(png_streams[1])),
-                    None if ply_text is None else tuple(host(t) for t in ply_text), None if renders is None else host(renders),
-                    None if render_streams is None else (host(render_streams[0]), host(render_streams[1])))
-        s = self._streams[slot]
-        with torch.cuda.stream(s):
-            s.wait_event(ev)
-            rec = self._pinned(slot, "rec", tuple(records.shape), torch.uint8, True)
-            rec.copy_(records, non_blocking=True)
-            img = None
-            if images is not None:
-                img = self._pinned(slot, "img", tuple(images.shape), torch.uint8, True)
-                img.copy_(images, non_blocking=True)
-            rnd = None
-            if renders is not None:
-                rnd = self._pinned(slot, "render", tuple(renders.shape), torch.uint8, True)
-                rnd.copy_(renders, non_blocking=True)
-            cnt = psz = poff = pflg = rsz = None
-            if render_streams is not None:
-                rsz = self._pinned(slot, "render_sizes", tuple(render_streams[1].shape), torch.int64, True)
-                rsz.copy_(render_streams[1], non_blocking=True)
-            if final is not None:
-                cnt = self._pinned(slot, "n", tuple(final["n"].shape), torch.int32, True)
-                cnt.copy_(final["n"], non_blocking=True)
-            if png_streams is not None:                                # phase one: the sizes; phase two: each stream's exact bytes
-                psz = self._pinned(slot, "png_sizes", tuple(png_streams[1].shape), torch.int64, True)
-                psz.copy_(png_streams[1], non_blocking=True)
-            if ply_text is not None:                                   # phase one: offsets and flags; phase two: the produced bytes, one copy
-                poff = self._pinned(slot, "ply_offsets", tuple(ply_text[1].shape), torch.int64, True)
-                poff.copy_(ply_text[1], non_blocking=True)
-                pflg = self._pinned(slot, "ply_flags", tuple(ply_text[2].shape), torch.int32, True)
-                pflg.copy_(ply_text[2], non_blocking=True)
-            s.synchronize()
-            clouds = png = ply = rpng = None
-            if render_streams is not None:
-                rbuf = self._pinned(slot, "render_png", tuple(render_streams[0].shape), torch.uint8, True)
-                rn = rsz.numpy()
-                for i in range(len(rn)):
-                    rbuf[i, :int(rn[i])].copy_(render_streams[0][i, :int(rn[i])], non_blocking=True)
-                rpng = (rbuf.numpy(), rn)
-            if ply_text is not None:
-                total = int(poff[-1])
-                tbuf = self._pinned(slot, "ply_text", (total,), torch.uint8, True)
-                if total:
-                    tbuf.copy_(ply_text[0][:total], non_blocking=True)
-                ply = (tbuf.numpy(), poff.numpy(), pflg.numpy())
-            if png_streams is not None:
-                streams = png_streams[0]
-                pbuf = self._pinned(slot, "png", tuple(streams.shape), torch.uint8, True)
-                pn = psz.numpy()
-                for i in range(len(pn)):
-                    pbuf[i, :int(pn[i])].copy_(streams[i, :int(pn[i])], non_blocking=True)
-                png = (pbuf.numpy(), pn)
-            if final is not None:
-                cn = cnt.numpy().astype(np.int64)
-                if ply is not None:                                    # only the frames the device did not format travel raw
-                    cn = np.where(ply[2] != 0, cn, 0)
-                off = np.concatenate([[0], np.cumsum(cn)])
-                xyz = self._pinned(slot, "xyz", (int(off[-1]), 3), torch.float32, True)
-                rgb = self._pinned(slot, "rgb", (int(off[-1]), 3), torch.uint8, True)
-                for i in range(len(cn)):
-                    if cn[i]:
-                        xyz[off[i]:off[i + 1]].copy_(final["xyz"][i, :cn[i]], non_blocking=True)
-                        rgb[off[i]:off[i + 1]].copy_(final["rgb"][i, :cn[i]], non_blocking=True)
-                xn, rn = xyz.numpy(), rgb.numpy()
-                clouds = [(xn[off[i]:off[i + 1]], rn[off[i]:off[i + 1]]) if ply is None or ply[2][i] != 0 else None for i in range(len(cn))]
-            if final is not None or png_streams is not None or render_streams is not None:
-                s.synchronize()
-        return rec.numpy(), None if img is None else img.numpy(), clouds, png, ply, None if rnd is None else rnd.numpy(), rpng
-
-    def _video_frames(self, slot, lo, img, video, ev):
-        """the JPEG files of one batch's frames, in order: route "host": ``img`` (the raw images, already on the host) through
-        sd_jpeg_encode_bgr_host on the writer threads; route "device": sizes and flags cross first, then each file's exact bytes on this
-        slot's side stream; a flagged frame is copied raw and encoded on the host"""
-        import torch
-        _, vimg, vstreams = video
+    def _video_frames(self, b: _Batch, host: _HostBatch) -> list:
+        """the JPEG files of the batch's frames, in order: route "host": the raw images through sd_jpeg_encode_bgr_host on the writer
+        threads; route "device": the files as they came, a flagged frame encoded here from its raw image"""
         q = self.video.quality
-        if vstreams is None:
-            return list(self._writers.map(lambda a: encode_jpeg_host(a, q), list(img)))
+        if host.video is None:
+            return list(self._writers.map(lambda a: encode_jpeg_host(a, q), list(host.images)))
+        self.video_fallback.extend(b.lo + i for i in sorted(host.video_raw))
+        return [encode_jpeg_host(host.video_raw[i], q) if i in host.video_raw else host.video[i, :int(size)].tobytes()
+                for i, size in enumerate(host.video_sizes)]
 
-        def host(t):
-            return np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t)
-
-        streams, sizes, flags = vstreams
-        if ev is None or not isinstance(streams, torch.Tensor) or not streams.is_cuda:
-            st, sz, fl = host(streams), host(sizes), host(flags)
-            raw = {i: host(vimg[i]) for i in range(len(sz)) if fl[i] != 0}
-        else:
-            s = self._streams[slot]
-            with torch.cuda.stream(s):
-                s.wait_event(ev)
-                vsz = self._pinned(slot, "video_sizes", tuple(sizes.shape), torch.int64, True)
-                vsz.copy_(sizes, non_blocking=True)
-                vfl = self._pinned(slot, "video_flags", tuple(flags.shape), torch.int32, True)
-                vfl.copy_(flags, non_blocking=True)
-                s.synchronize()
-                sz, fl = vsz.numpy(), vfl.numpy()
-                total = int(sz.sum())
-                vbuf = self._pinned(slot, "video", (max(total, 1),), torch.uint8, True)
-                off = np.concatenate([[0], np.cumsum(sz)]).astype(np.int64)
-                raw = {}
-                for i in range(len(sz)):
-                    if fl[i] != 0:
-                        if vimg is None:
-                            raise ValueError("SequenceOutputs: a flagged video frame needs the raw images (submit(images=))")
-                        raw[i] = self._pinned(slot, f"video_raw{i}", tuple(vimg[i].shape), torch.uint8, True)
-                        raw[i].copy_(vimg[i], non_blocking=True)
-                    elif sz[i]:
-                        vbuf[int(off[i]):int(off[i + 1])].copy_(streams[i, :int(sz[i])], non_blocking=True)
-                s.synchronize()
-                raw = {i: t.numpy() for i, t in raw.items()}
-                flat = vbuf.numpy()
-                st = None
-        out = []
-        for i in range(len(sz)):
-            if fl[i] != 0:
-                self.video_fallback.append(lo + i)
-                out.append(encode_jpeg_host(raw[i], q))
-            elif st is not None:
-                out.append(st[i, :int(sz[i])].tobytes())
-            else:
-                out.append(flat[int(off[i]):int(off[i + 1])].tobytes())
-        return out
-
-    def _video_batch(self, slot, lo, size, img, video, ev):
-        """encode or fetch this batch's frames, then append them when it is this batch's turn (batches finish in any order)"""
+    def _write_batch(self, b: _Batch) -> list:
+        from .engine import RW_DTYPE
         frames = None
         try:
-            frames = self._video_frames(slot, lo, img, video, ev)
-        finally:
-            with self._video_turn:
-                while self._video_next != video[0]:
-                    self._video_turn.wait()
-                try:
-                    if frames is not None:
-                        if self._video_writer is None:
-                            name = "result_imgs.avi" if self.world == 1 else "result_imgs_rank{}.avi".format(self.rank)
-                            self._video_writer = MjpegAviWriter(os.path.join(self.directory, name), size[1], size[0], self.video.fps)
-                        for fr in frames:
-                            self._video_writer.append(fr)
-                finally:
-                    self._video_next += 1
-                    self._video_turn.notify_all()
+            host = self._fetch(b)
+            recs = np.ascontiguousarray(host.records).view(RW_DTYPE).reshape(-1)
+            n = len(recs)
+            names = self.names[b.lo:b.lo + n]
+            h, w = b.size
+            files, futs = [], []
 
-    def _write_batch(self, slot, lo, records, size, images, final, ev, png_streams=None, ply_text=None, renders=None, render_streams=None, video=None):
-        try:
-            return self._write_batch_files(slot, lo, records, size, images, final, ev, png_streams, ply_text, renders, render_streams, video)
-        except BaseException:
-            if video is not None:                                      # (the batches behind this one must not wait for its turn for ever)
+            def ends(r):
+                if not r["found"]:
+                    return None, None
+                return r["left_pt"].astype(np.float64)[None, :], r["right_pt"].astype(np.float64)[None, :]
+
+            def write_ply(i):
+                path = os.path.join(self.ply_dir, "{}_rw.ply".format(names[i]))
+                if host.clouds[i] is None:                             # the device route: the slice is the file
+                    with open(path, "wb") as f:
+                        f.write(host.ply_text[int(host.ply_offsets[i]):int(host.ply_offsets[i + 1])].data)
+                    return path
+                left, right = ends(recs[i])
+                xyz, rgb = host.clouds[i]
+                with open(path, "wb") as f:
+                    f.write(rw_ply_bytes(xyz.astype(np.float64), rgb, left, right))
+                return path
+
+            def write_items(i):
+                r = recs[i]
+                left, right = ends(r)
+                banner, items = overlay_items_sequence(w, h, self.depth, bool(r["found"]), left, right, float(r["width"]) if r["found"] else None)
+                path = os.path.join(self.img_dir, "{}_overlay.json".format(names[i]))
+                with open(path, "w") as f:
+                    json.dump(dict(banner=banner, items=items), f)
+                return path
+
+            if host.ply_flags is not None:
+                self.ply_fallback.extend(b.lo + i for i in range(n) if host.ply_flags[i] != 0)
+            for i in range(n):
+                if self.ply:
+                    futs.append(self._writers.submit(write_ply, i))
+                if self.items:
+                    futs.append(self._writers.submit(write_items, i))
+            if self.images and self.png == "device":
+                files.extend(write_png_streams([os.path.join(self.img_dir, "{}.png".format(nm)) for nm in names], host.png, host.png_sizes, h, w,
+                                               self.threads))
+            elif self.images:
+                assert host.images.shape == (n, h, w, 3), (host.images.shape, (n, h, w))
+                files.extend(write_png_batch([os.path.join(self.img_dir, "{}.png".format(nm)) for nm in names], host.images, self.level, self.threads))
+            if self.render is not None:
+                os.makedirs(self.render_dir, exist_ok=True)
+                paths = [os.path.join(self.render_dir, "{}_render.png".format(nm)) for nm in names]
+                rh, rw = self.render.height, self.render.width
+                if host.render_png is not None:
+                    files.extend(write_png_streams(paths, host.render_png, host.render_sizes, rh, rw, self.threads))
+                else:
+                    assert host.renders.shape == (n, rh, rw, 3), (host.renders.shape, (n, rh, rw))
+                    files.extend(write_png_batch(paths, host.renders, self.level, self.threads))
+            if self.video is not None:
+                frames = self._video_frames(b, host)
+            files.extend(f.result() for f in futs)
+            return files
+        finally:
+            if self.video is not None:
+                # this batch's turn in the video (batches finish in any order; the frames go in in batch order): taken and passed on exactly
+                # once, whatever raised above -- ``frames`` is then None, nothing is appended, and the batches behind do not wait for ever
                 with self._video_turn:
-                    while self._video_next < video[0]:
-                        self._video_turn.wait()
-                    if self._video_next == video[0]:
+                    self._video_turn.wait_for(lambda: self._video_next == b.k)
+                    try:
+                        if frames is not None:
+                            if self._video_writer is None:
+                                name = "result_imgs.avi" if self.world == 1 else "result_imgs_rank{}.avi".format(self.rank)
+                                self._video_writer = MjpegAviWriter(os.path.join(self.directory, name), b.size[1], b.size[0], self.video.fps)
+                            for fr in frames:
+                                self._video_writer.append(fr)
+                    finally:
                         self._video_next += 1
                         self._video_turn.notify_all()
-            raise
-
-    def _write_batch_files(self, slot, lo, records, size, images, final, ev, png_streams, ply_text, renders, render_streams, video):
-        from .engine import RW_DTYPE
-        rec_u8, img, clouds, png, ply, rnd, rpng = self._to_host(slot, lo, records, images, final, ev, png_streams, ply_text, renders, render_streams)
-        recs = np.ascontiguousarray(rec_u8).view(RW_DTYPE).reshape(-1)
-        n = len(recs)
-        names = self.names[lo:lo + n]
-        h, w = size
-        files, futs = [], []
-
-        def ends(r):
-            if not r["found"]:
-                return None, None
-            return r["left_pt"].astype(np.float64)[None, :], r["right_pt"].astype(np.float64)[None, :]
-
-        def write_ply(i):
-            path = os.path.join(self.ply_dir, "{}_rw.ply".format(names[i]))
-            if ply is not None and ply[2][i] == 0:                     # the device route: the slice is the file
-                with open(path, "wb") as f:
-                    f.write(ply[0][int(ply[1][i]):int(ply[1][i + 1])].data)
-                return path
-            left, right = ends(recs[i])
-            xyz, rgb = clouds[i]
-            with open(path, "wb") as f:
-                f.write(rw_ply_bytes(xyz.astype(np.float64), rgb, left, right))
-            return path
-
-        def write_items(i):
-            r = recs[i]
-            left, right = ends(r)
-            banner, items = overlay_items_sequence(w, h, self.depth, bool(r["found"]), left, right, float(r["width"]) if r["found"] else None)
-            path = os.path.join(self.img_dir, "{}_overlay.json".format(names[i]))
-            with open(path, "w") as f:
-                json.dump(dict(banner=banner, items=items), f)
-            return path
-
-        if self.ply and ply is not None:
-            self.ply_fallback.extend(lo + i for i in range(n) if ply[2][i] != 0)
-        for i in range(n):
-            if self.ply:
-                futs.append(self._writers.submit(write_ply, i))
-            if self.items:
-                futs.append(self._writers.submit(write_items, i))
-        if self.images and self.png == "device":
-            files.extend(write_png_streams([os.path.join(self.img_dir, "{}.png".format(nm)) for nm in names], png[0], png[1], h, w, self.threads))
-        elif self.images:
-            assert img.shape == (n, h, w, 3), (img.shape, (n, h, w))
-            files.extend(write_png_batch([os.path.join(self.img_dir, "{}.png".format(nm)) for nm in names], img, self.level, self.threads))
-        if self.render is not None:
-            os.makedirs(self.render_dir, exist_ok=True)
-            paths = [os.path.join(self.render_dir, "{}_render.png".format(nm)) for nm in names]
-            rh, rw = self.render.height, self.render.width
-            if rpng is not None:
-                files.extend(write_png_streams(paths, rpng[0], rpng[1], rh, rw, self.threads))
-            else:
-                assert rnd.shape == (n, rh, rw, 3), (rnd.shape, (n, rh, rw))
-                files.extend(write_png_batch(paths, rnd, self.level, self.threads))
-        if video is not None:
-            self._video_batch(slot, lo, size, img, video, ev)
-        files.extend(f.result() for f in futs)
-        return files
