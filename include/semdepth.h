@@ -249,6 +249,87 @@ sd_status sd_jpeg_reconstruct_workspace(const sd_jpeg_frame_desc* descs_host, in
  * frame_stride_bytes, a frame beyond bgr_frame_stride, workspace_bytes below sd_jpeg_reconstruct_workspace -- nothing is launched. */
 sd_status sd_jpeg_reconstruct_bgr(sd_handle* h, const int16_t* coef_dev, size_t frame_stride_bytes, const sd_jpeg_frame_desc* descs_host, int B,
                                   uint8_t* bgr_dev, size_t bgr_frame_stride, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* ---- JPEG frames, entropy route: the host only finds the restart markers, the GPU decodes the Huffman code, one restart interval per lane ----
+ * The Huffman recurrence is serial only inside a restart interval: at every RSTn marker the bit stream is byte-aligned and the DC
+ * predictors are reset, so the intervals of a sequential scan are independent jobs once their byte ranges are known.  A file is ELIGIBLE
+ * when all of this holds (anything else goes through sd_jpeg_decode_coefficients, whose marker hunting is not restated anywhere):
+ *   - SOF0 or SOF1, 8-bit, and the header parse of sd_jpeg_decode_bgr accepts it (the scan's tables are defined before the scan);
+ *   - exactly one SOS, covering all components (1 or 3) interleaved, in the frame header's order;
+ *   - DRI > 0;
+ *   - walking the scan data from its start, every 0xFF is followed by 0x00, by the expected RSTk (k counting 0..7 cyclically), or -- after
+ *     exactly ceil(mcus / DRI) intervals -- by EOI as the last two bytes of the file.
+ * Progressive, multi-scan, non-interleaved, DRI-less and truncated files, fill bytes and stray markers are ineligible.
+ *
+ * sd_jpeg_huff_table: one Huffman table in the decodable form of the host decoder (T.81 F.2.2.3 plus a 9-bit look-ahead): look[i] =
+ * (length << 8) | symbol for the code that prefixes the 9 bits i, 0 when it is longer than 9 bits; mincode / maxcode / valptr per code
+ * length 1..16 (maxcode -1: no code of that length), vals the symbols in code order.
+ * sd_jpeg_entropy_frame: the scan of one file.  eligible 0: nothing else is promised.  mcus_x / mcus_y: MCUs per row / column;
+ * restart_interval: DRI, MCUs per interval; n_intervals = ceil(mcus_x * mcus_y / DRI); per component the sampling factors and the
+ * table ids Td / Ta (the frame's table array holds DC table Td in slot Td and AC table Ta in slot 4 + Ta; slots the scan does not name
+ * are zero); scan_begin / scan_end: the file offsets of the first scan byte and of the 0xFF of EOI.
+ * sd_jpeg_interval: the bytes [begin, end) of one restart interval as offsets FROM scan_begin; end is the 0xFF of the closing marker. */
+#define SD_JPEG_ENTROPY_TABLES 8
+typedef struct {
+    uint16_t look[512];
+    int32_t mincode[17], maxcode[18], valptr[17];
+    uint8_t vals[256];
+} sd_jpeg_huff_table;
+typedef struct {
+    int32_t eligible;
+    int32_t ncomp;
+    int32_t mcus_x, mcus_y;
+    int32_t restart_interval;
+    int32_t n_intervals;
+    int32_t comp_h[3], comp_v[3], comp_dc[3], comp_ac[3];
+    uint32_t scan_begin, scan_end;
+} sd_jpeg_entropy_frame;
+typedef struct {
+    uint32_t begin, end;
+} sd_jpeg_interval;
+/* HOST: the plan of one file: a header parse and a byte scan for the markers, no bit work.  Writes *desc_out (for an eligible file every
+ * byte of what sd_jpeg_decode_coefficients writes), *frame_out, tables_out[SD_JPEG_ENTROPY_TABLES] (built and validated as the host
+ * decoder builds its own) and the first frame_out->n_intervals entries of intervals_out.  SD_OK with eligible 0 for a JPEG that is not
+ * eligible; SD_ERR_FORMAT for a file that does not begin with SOI; SD_ERR_INVALID for NULL arguments, a file of 2 GiB or more, or an
+ * eligible file with more than interval_cap intervals (n_intervals says how many it has).  *frame_out is cleared first: eligible is 0
+ * on every return but SD_OK for an eligible file. */
+sd_status sd_jpeg_entropy_plan(const uint8_t* file_host, size_t len, sd_jpeg_frame_desc* desc_out, sd_jpeg_entropy_frame* frame_out,
+                               sd_jpeg_huff_table* tables_out, sd_jpeg_interval* intervals_out, size_t interval_cap);
+/* HOST: the batch form beside sd_decode_files_jpeg_coef: reads n files on `threads` native threads (<= 0: one per host CPU), plans each
+ * and copies the scan bytes [scan_begin, scan_end) of an eligible file to bytes_out_host + i * byte_stride (e.g. a pinned staging
+ * buffer), its records to descs_out[i], frames_out[i], tables_out + i * SD_JPEG_ENTROPY_TABLES and intervals_out + i * interval_stride.
+ * height x width is the size AFTER the orientation every frame must have.  status_out (nullable, int[n]): SD_ERR_NOTFOUND unreadable
+ * file; SD_ERR_FORMAT a readable file that is not a JPEG; SD_ERR_INVALID an eligible JPEG of another size, with more scan bytes than
+ * byte_stride or more intervals than interval_stride (eligible is 0 then); SD_OK otherwise, eligible or not.  Returns SD_OK when every
+ * status is SD_OK or SD_ERR_FORMAT, else SD_ERR_INVALID. */
+sd_status sd_plan_files_jpeg_entropy(const char* const* paths, int n, int height, int width, uint8_t* bytes_out_host, size_t byte_stride,
+                                     sd_jpeg_frame_desc* descs_out, sd_jpeg_entropy_frame* frames_out, sd_jpeg_huff_table* tables_out,
+                                     sd_jpeg_interval* intervals_out, size_t interval_stride, int threads, int* status_out);
+/* HOST: the CPU statement of sd_jpeg_entropy_decode: the same checks, then a plain loop over the intervals calling the same function
+ * (semantic_depth_amd/csrc/jpeg_entropy.hpp).  Frame b's scan bytes are at bytes_host + b * byte_stride.  For every eligible frame it
+ * clears the frame's coefficients (the descriptor's element count, nothing behind them) at coef_out_host + b * coef_stride_bytes and
+ * writes what sd_jpeg_decode_coefficients writes; status_out[b] = 0, or the refusal of the first refused interval (1 undecodable symbol,
+ * 2 DC category above 15, 3 DC predictor outside +-32767, 4 run past coefficient 63) -- the frame is then to be decoded by
+ * sd_jpeg_decode_coefficients, which refuses it as well.  Ineligible frames: status 0, coefficients untouched. */
+sd_status sd_jpeg_entropy_decode_host(const uint8_t* bytes_host, size_t byte_stride, const sd_jpeg_frame_desc* descs, const sd_jpeg_entropy_frame* frames,
+                                      const sd_jpeg_interval* intervals, size_t interval_stride, const sd_jpeg_huff_table* tables, int B,
+                                      int16_t* coef_out_host, size_t coef_stride_bytes, int32_t* status_out);
+/* bytes of device workspace sd_jpeg_entropy_decode needs (the uploaded records, tables and interval ranges) */
+sd_status sd_jpeg_entropy_workspace(int B, size_t interval_stride, size_t* bytes_out);
+/* DEVICE: B frames' scan bytes (frame b at bytes_dev + b * byte_stride) -> their quantised coefficients at coef_dev + b *
+ * coef_stride_bytes as sd_jpeg_entropy_decode_host writes them, and status_dev[b]: 0 exactly where that function writes 0, otherwise
+ * the refusal code of ONE of the frame's refused intervals (the lanes store without ordering; only non-zero is promised, not the first
+ * interval's code); ineligible frames are skipped.  The records,
+ * tables and ranges are HOST arrays: they are checked, then uploaded into workspace_dev by asynchronous copies on `stream` (pinned
+ * arrays must stay unchanged until the stream has passed the call).  One kernel clears the eligible frames' coefficients, one decodes:
+ * a lane per restart interval, 64 intervals of one frame per workgroup, the frame's named tables staged in LDS.  Enqueued on `stream`,
+ * no synchronisation; the handle need not be bound.  SD_ERR_INVALID, and nothing is launched or copied: bytes_dev, byte_stride, coef_dev,
+ * coef_stride_bytes or workspace_dev not multiples of 16; a record that disagrees with its descriptor; coefficients beyond
+ * coef_stride_bytes; an interval range outside byte_stride; more intervals than interval_stride; a table not in decodable form;
+ * workspace_bytes below sd_jpeg_entropy_workspace. */
+sd_status sd_jpeg_entropy_decode(sd_handle* h, const uint8_t* bytes_dev, size_t byte_stride, const sd_jpeg_frame_desc* descs_host,
+                                 const sd_jpeg_entropy_frame* frames_host, const sd_jpeg_interval* intervals_host, size_t interval_stride,
+                                 const sd_jpeg_huff_table* tables_host, int B, int16_t* coef_dev, size_t coef_stride_bytes,
+                                 int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 /* HOST: the writer behind the sequence tool's cv2.imwrite('<dir>/<name>.png', frame) (seq:336): encodes n u8 [height,width,3] BGR frames at
  * frames_host + i * frame_stride as 8-bit RGB PNGs (filter type 0 rows, one zlib stream at `level` 0..9) and writes them to paths[i], on
  * `threads` native threads (<= 0: one per host CPU).  Pixel-exact, not byte-identical to OpenCV's file: sd_png_decode_bgr reads each

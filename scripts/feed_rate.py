@@ -4,11 +4,16 @@ frames/s?  Measures, for frames of one size (default: generated Cityscapes-sized
   upload    pinned host -> HBM copy of decoded frames
   resize    Engine.resize_cubic to 512 x 1024 on the GPU
   feeder    frame_io.FrameFeeder end to end (decode + pinned upload + resize, one batch ahead), best and median of --repeats passes
-    python scripts/feed_rate.py [--frames 256] [--workers N] [--format png|jpeg] [--jpeg host|device] [--frames-dir DIR] [--out FILE]
+    python scripts/feed_rate.py [--frames 256] [--workers N] [--format png|jpeg] [--jpeg host|device|device_entropy] [--frames-dir DIR] [--out FILE]
+                                [--size HxW] [--restart-rows N] [--encoder pillow|own] [--compare]
 --frames-dir times the *.png / *.jpg files of a directory instead of generating frames (JPEG frames cannot be written here without
 Pillow, which a GPU box may lack: write them elsewhere and ship them).  --jpeg device feeds through FrameFeeder(jpeg="device"): Huffman
 decoding on the host, reconstruction on the GPU; the script passes jpeg= only then, so --jpeg host also runs in a tree that lacks the
-split route (the parent commit's, for an A/B of the host route).  Nothing is written unless --out is given.
+split route (the parent commit's, for an A/B of the host route).  --jpeg device_entropy feeds through FrameFeeder(jpeg="device_entropy"):
+the host only finds the restart markers, the GPU decodes the Huffman code; it needs files with restart intervals: --restart-rows 1 makes
+Pillow write them, --encoder own writes the frames with the project's encoder (one interval per MCU row).  --compare runs the three JPEG
+routes on the same files in one process, interleaved pass by pass, and adds the plan's single-thread time and the HIP-event time of
+Engine.jpeg_entropy_decode.  Nothing is written unless --out is given.
 """
 import argparse
 import ctypes as C
@@ -29,8 +34,8 @@ from semantic_depth_amd import frame_io, outputs            # noqa: E402
 from semantic_depth_amd.engine import Engine                # noqa: E402
 
 
-def _generate(td, n, fmt):
-    H, W = 1024, 2048
+def _generate(td, n, fmt, size=(1024, 2048), restart_rows=0, encoder="pillow"):
+    H, W = size
     rng = np.random.default_rng(0)
     # street-like content: smooth gradients + texture noise (PNG of pure noise does not compress; real frames do, ~2.2 MB each)
     yy, xx = np.mgrid[0:H, 0:W]
@@ -41,9 +46,13 @@ def _generate(td, n, fmt):
         if fmt == "png":
             paths.append(outputs.write_png(os.path.join(td, f"f{i:05d}.png"), img, level=6))
         else:
-            from PIL import Image
             p = os.path.join(td, f"f{i:05d}.jpg")
-            Image.fromarray(img[..., ::-1]).save(p, "JPEG", quality=90, subsampling=2)
+            if encoder == "own":
+                open(p, "wb").write(outputs.encode_jpeg_host(img, 90))
+            else:
+                from PIL import Image
+                kw = {"restart_marker_rows": restart_rows} if restart_rows else {}
+                Image.fromarray(img[..., ::-1]).save(p, "JPEG", quality=90, subsampling=2, **kw)
             paths.append(p)
     return paths
 
@@ -96,12 +105,72 @@ def _kernel_ms_per_batch(eng, paths, workers, res):
     res["reconstruct_kernels_ms_per_batch"] = {"frames": n, "median": float(np.median(times)), "min": float(min(times)), "max": float(max(times))}
 
 
+def _entropy_measurements(eng, paths, workers, res):
+    """the plan's host time per frame on one thread (against coefficients_ms_per_frame_1_thread on the same files) and the HIP-event
+    time of Engine.jpeg_entropy_decode on one resident batch: the uploads of the records, the clearing kernel and the decoding kernel"""
+    lib = L.load()
+    bufs = [open(p, "rb").read() for p in paths[:8]]
+    cap = 1 << 16
+    d, fr = L.sd_jpeg_frame_desc(), L.sd_jpeg_entropy_frame()
+    tables, iv = (L.sd_jpeg_huff_table * L.SD_JPEG_ENTROPY_TABLES)(), (L.sd_jpeg_interval * cap)()
+    for rep in range(2):
+        t0 = time.perf_counter()
+        for b in bufs:
+            assert lib.sd_jpeg_entropy_plan(b, len(b), C.byref(d), C.byref(fr), tables, iv, cap) == L.SD_OK and fr.eligible
+        res["plan_ms_per_frame_1_thread"] = (time.perf_counter() - t0) / len(bufs) * 1e3
+    res["intervals_per_frame"] = int(fr.n_intervals)
+    n = min(32, len(paths))
+    feeder = frame_io.FrameFeeder(paths[:n], n, "cuda", workers, jpeg="device_entropy", engine=eng)
+    t0 = time.perf_counter()
+    host = feeder._plan_into(0, 0, n)
+    res["plan_ms_per_batch_native"] = (time.perf_counter() - t0) * 1e3
+    assert len(host["eligible"]) == n
+    used = max(int(host["frames"][i].scan_end - host["frames"][i].scan_begin) for i in range(n))
+    used = -(-used // 16) * 16
+    res["scan_bytes_per_frame_max"] = used
+    sdev = host["pinned"]["bytes"][:n, :used].cuda()
+    h, w = host["size"]
+    out = torch.empty((n, frame_io.FrameFeeder.coef_stride_bytes(h, w) // 2), dtype=torch.int16, device="cuda")
+    args = (sdev, host["descs"], host["frames"], host["tables"], host["intervals"], host["ivs"])
+    _, status = eng.jpeg_entropy_decode(*args, out=out)
+    torch.cuda.synchronize()
+    assert int(status.abs().sum()) == 0
+    times = []
+    for _ in range(7):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        eng.jpeg_entropy_decode(*args, out=out, status=status)
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b))
+    res["entropy_decode_ms_per_batch"] = {"frames": n, "median": float(np.median(times)), "min": float(min(times)), "max": float(max(times))}
+    feeder.close()
+
+
+def _feeder_pass(eng, paths, workers, route):
+    kw = {"jpeg": route, "engine": eng} if route != "host" else {}
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    n = 0
+    with frame_io.FrameFeeder(paths, 32, "cuda", workers, **kw) as feeder:
+        for fr, lo in feeder:
+            eng.resize_cubic(fr)
+            n += fr.shape[0]
+        fallbacks = len(feeder.entropy_fallback)
+    torch.cuda.synchronize()
+    return n / (time.perf_counter() - t0), fallbacks
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--workers", type=int, default=frame_io.default_decode_workers())
     ap.add_argument("--format", choices=("png", "jpeg"), default="png")
-    ap.add_argument("--jpeg", choices=("host", "device"), default="host")
+    ap.add_argument("--jpeg", choices=("host", "device", "device_entropy"), default="host")
+    ap.add_argument("--size", default="1024x2048", help="HxW of the generated frames")
+    ap.add_argument("--restart-rows", type=int, default=0, help="generated JPEG frames: Pillow's restart_marker_rows (0: no restart intervals)")
+    ap.add_argument("--encoder", choices=("pillow", "own"), default="pillow", help="generated JPEG frames: Pillow, or the project's encoder")
+    ap.add_argument("--compare", action="store_true", help="JPEG frames: the three routes interleaved in this process, plan and kernel times")
     ap.add_argument("--frames-dir", default=None, help="time the *.png / *.jpg / *.jpeg files of this directory (one size) instead of generating frames")
     ap.add_argument("--repeats", type=int, default=3, help="timed passes of the feeder after one warm pass")
     ap.add_argument("--out", default=None, help="write the JSON record here (default: print only)")
@@ -113,7 +182,9 @@ def main():
                 raise SystemExit(f"no frames in {a.frames_dir}")
             paths = (paths * (-(-a.frames // len(paths))))[:a.frames]      # (cycled to --frames: the page cache holds them either way)
         else:
-            paths = _generate(td, a.frames, a.format)
+            distinct = min(a.frames, 32) if a.compare else a.frames           # (--compare cycles 32 distinct files)
+            paths = _generate(td, distinct, a.format, tuple(int(v) for v in a.size.split("x")), a.restart_rows, a.encoder)
+            paths = (paths * (-(-a.frames // len(paths))))[:a.frames]
         with open(paths[0], "rb") as f:
             H, W = frame_io.image_size(f.read())
         res = {"frame": [H, W, 3], "frames": len(paths), "distinct_files": len(set(paths)), "host_cpus": os.cpu_count(), "workers": a.workers,
@@ -161,9 +232,22 @@ def main():
             torch.cuda.synchronize()
             res["resize_fps"] = 32 * 5 / (time.perf_counter() - t0)
             del host, dev
-            kw = {"jpeg": "device", "engine": eng} if a.jpeg == "device" else {}      # (nothing the parent commit's feeder lacks in host mode)
-            if a.jpeg == "device":
+            kw = {"jpeg": a.jpeg, "engine": eng} if a.jpeg != "host" else {}          # (nothing the parent commit's feeder lacks in host mode)
+            if a.jpeg != "host" or a.compare:
                 _kernel_ms_per_batch(eng, paths, a.workers, res)
+            if a.jpeg == "device_entropy" or a.compare:
+                _entropy_measurements(eng, paths, a.workers, res)
+            if a.compare:                                                             # the three routes, pass by pass, in this process
+                routes = ("host", "device", "device_entropy")
+                rates = {r: [] for r in routes}
+                for rep in range(a.repeats + 1):
+                    for r in routes:
+                        fps, fb = _feeder_pass(eng, paths if rep else paths[:64], a.workers, r)
+                        if rep:
+                            rates[r].append(fps)
+                        if r == "device_entropy":
+                            res["entropy_fallback_frames"] = fb
+                res["compare_feeder_fps"] = {r: {"median": float(np.median(v)), "passes": v} for r, v in rates.items()}
             rates = []
             for rep in range(a.repeats + 1):                                          # pass 0 warms (pinned staging allocation, page cache)
                 torch.cuda.synchronize()

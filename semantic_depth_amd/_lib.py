@@ -77,6 +77,24 @@ class sd_jpeg_frame_desc(C.Structure):
         return (self.width, self.height) if self.orientation >= 5 else (self.height, self.width)
 
 
+SD_JPEG_ENTROPY_TABLES = 8
+
+
+class sd_jpeg_huff_table(C.Structure):
+    _fields_ = [("look", C.c_uint16 * 512), ("mincode", C.c_int32 * 17), ("maxcode", C.c_int32 * 18), ("valptr", C.c_int32 * 17),
+                ("vals", C.c_uint8 * 256)]
+
+
+class sd_jpeg_entropy_frame(C.Structure):
+    _fields_ = [("eligible", C.c_int32), ("ncomp", C.c_int32), ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("restart_interval", C.c_int32),
+                ("n_intervals", C.c_int32), ("comp_h", C.c_int32 * 3), ("comp_v", C.c_int32 * 3), ("comp_dc", C.c_int32 * 3),
+                ("comp_ac", C.c_int32 * 3), ("scan_begin", C.c_uint32), ("scan_end", C.c_uint32)]
+
+
+class sd_jpeg_interval(C.Structure):
+    _fields_ = [("begin", C.c_uint32), ("end", C.c_uint32)]
+
+
 # every symbol include/semdepth.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _H = C.c_void_p
@@ -107,6 +125,12 @@ SIGNATURES = {
                                             C.c_int, C.POINTER(C.c_int)]),
     "sd_jpeg_reconstruct_workspace": (C.c_int, [C.POINTER(sd_jpeg_frame_desc), C.c_int, C.POINTER(C.c_size_t)]),
     "sd_jpeg_reconstruct_bgr": (C.c_int, [_H, _P, C.c_size_t, C.POINTER(sd_jpeg_frame_desc), C.c_int, _P, C.c_size_t, _P, C.c_size_t, _P]),
+    "sd_jpeg_entropy_plan": (C.c_int, [_P, C.c_size_t, C.POINTER(sd_jpeg_frame_desc), C.POINTER(sd_jpeg_entropy_frame), _P, _P, C.c_size_t]),
+    "sd_plan_files_jpeg_entropy": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P, _P, C.c_size_t, C.c_int,
+                                             C.POINTER(C.c_int)]),
+    "sd_jpeg_entropy_decode_host": (C.c_int, [_P, C.c_size_t, _P, _P, _P, C.c_size_t, _P, C.c_int, _P, C.c_size_t, _P]),
+    "sd_jpeg_entropy_workspace": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sd_jpeg_entropy_decode": (C.c_int, [_H, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _P, C.c_int, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
     "sd_png_encode_bgr_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, C.c_int,
                                           C.POINTER(C.c_int)]),
     "sd_png_encode_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

@@ -37,6 +37,7 @@ SOURCES = [
     ("jpeg_gpu.hip", []),
     ("png_gpu.hip", []),
     ("jpeg_enc_gpu.hip", []),
+    ("jpeg_entropy_gpu.hip", []),
     ("ply_gpu.hip", ["-ffp-contract=off"]),
     ("text_gpu.hip", []),
     ("render_gpu.hip", ["-ffp-contract=off"]),
@@ -46,12 +47,13 @@ SOURCES = [
     ("capi.cpp", []),
     ("host_png.cpp", []),
     ("host_jpeg.cpp", []),
+    ("host_jpeg_entropy.cpp", []),
     ("host_ply.cpp", []),
     ("host_text.cpp", []),
     ("host_render.cpp", ["-ffp-contract=off"]),
     ("host_jpeg_enc.cpp", []),
 ]
-HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", "jpeg_enc.hpp", "jpeg_enc_gpu.hpp", "ply_format.hpp", "ply_gpu.hpp", "text_draw.hpp", "text_gpu.hpp", "render_rule.hpp", "render_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
+HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", "jpeg_enc.hpp", "jpeg_enc_gpu.hpp", "jpeg_entropy.hpp", "jpeg_entropy_gpu.hpp", "ply_format.hpp", "ply_gpu.hpp", "text_draw.hpp", "text_gpu.hpp", "render_rule.hpp", "render_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
 
 
 def _hipcc() -> str:

@@ -15,6 +15,7 @@
 #include "jpeg_gpu.hpp"
 #include "png_gpu.hpp"
 #include "jpeg_enc_gpu.hpp"
+#include "jpeg_entropy_gpu.hpp"
 #include "ply_gpu.hpp"
 #include "text_gpu.hpp"
 #include "render_gpu.hpp"
@@ -768,6 +769,34 @@ sd_status sd_jpeg_reconstruct_bgr(sd_handle* h, const int16_t* coef_dev, size_t 
         return fail(h, SD_ERR_INVALID, "sd_jpeg_reconstruct_bgr: workspace smaller than sd_jpeg_reconstruct_workspace reports");
     HIPCHK(h, launch_jpeg_reconstruct(coef_dev, frame_stride_bytes / sizeof(int16_t), descs_host, B, bgr_dev, bgr_frame_stride,
                                       static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
+    return SD_OK;
+}
+
+sd_status sd_jpeg_entropy_workspace(int B, size_t interval_stride, size_t* bytes_out) {
+    if (B < 1 || B > 65535 || interval_stride < 1 || interval_stride > ((size_t)1 << 24) || !bytes_out) return SD_ERR_INVALID;
+    *bytes_out = jpeg_entropy_workspace_bytes(B, interval_stride);
+    return SD_OK;
+}
+
+sd_status sd_jpeg_entropy_decode(sd_handle* h, const uint8_t* bytes_dev, size_t byte_stride, const sd_jpeg_frame_desc* descs_host,
+                                 const sd_jpeg_entropy_frame* frames_host, const sd_jpeg_interval* intervals_host, size_t interval_stride,
+                                 const sd_jpeg_huff_table* tables_host, int B, int16_t* coef_dev, size_t coef_stride_bytes, int32_t* status_dev,
+                                 void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!h || !bytes_dev || !descs_host || !frames_host || !intervals_host || !tables_host || B < 1 || B > 65535 || !coef_dev || !status_dev ||
+        !workspace_dev || interval_stride < 1 || interval_stride > ((size_t)1 << 24))
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_entropy_decode: bad arguments");
+    // the lanes fetch aligned dwords of the scan bytes and the clearing kernel stores 16-byte pieces
+    if ((reinterpret_cast<uintptr_t>(bytes_dev) & 15) || (byte_stride & 15) || (reinterpret_cast<uintptr_t>(coef_dev) & 15) || (coef_stride_bytes & 15) ||
+        (reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(status_dev) & 3))
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_entropy_decode: bytes_dev, byte_stride, coef_dev, coef_stride_bytes and workspace_dev must be multiples of 16");
+    // every index the kernels form follows from records that agree with their descriptors and these capacities: nothing is launched otherwise
+    const char* why = "";
+    if (!sdjent::args_ok(byte_stride, descs_host, frames_host, intervals_host, interval_stride, tables_host, B, coef_stride_bytes, &why))
+        return fail(h, SD_ERR_INVALID, std::string("sd_jpeg_entropy_decode: ") + why);
+    if (workspace_bytes < jpeg_entropy_workspace_bytes(B, interval_stride))
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_entropy_decode: workspace smaller than sd_jpeg_entropy_workspace reports");
+    HIPCHK(h, launch_jpeg_entropy_decode(bytes_dev, byte_stride, descs_host, frames_host, intervals_host, interval_stride, tables_host, B, coef_dev,
+                                         coef_stride_bytes / sizeof(int16_t), status_dev, static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
     return SD_OK;
 }
 

@@ -160,6 +160,7 @@ struct Decoder {
     bool allocated = false;
     uint16_t qt_used[3][64] = {};                          // the table each component's coefficients are to be multiplied by
     bool scanned[3] = {false, false, false};               // sequential file: a scan has covered the component
+    const uint8_t* sos = nullptr; size_t sos_len = 0, sos_data = 0;      // the first SOS: its header, and the file offset of its entropy data
 
     void geometry() {
         for (int i = 0; i < ncomp; ++i) {
@@ -262,6 +263,7 @@ struct Decoder {
                 if (sn >= 12 && std::memcmp(s, "Adobe", 5) == 0) adobe_transform = s[11];
             } else if (m == 0xDA) {                          // SOS
                 if (!sof) return SD_ERR_INVALID;
+                sos = s; sos_len = sn; sos_data = p + n;         // (the entropy plan reads the scan header from here)
                 if (!decode) return SD_OK;
                 size_t next = 0;
                 const sd_status st = scan(s, sn, p + n, next);
@@ -583,6 +585,73 @@ struct Decoder {
         return SD_OK;
     }
 
+    // The plan of the entropy route (sd_jpeg_entropy_plan): the header parse above up to the first SOS, the scan header as scan() reads
+    // it, and a byte walk over the scan data that accepts nothing but stuffed FFs, the expected RSTk and the closing EOI.  Wherever
+    // scan()'s marker hunting could matter the file is left to scan(): eligible stays 0.
+    sd_status plan(sd_jpeg_frame_desc* desc, sd_jpeg_entropy_frame* fr, sd_jpeg_huff_table* tables, sd_jpeg_interval* iv, size_t iv_cap) {
+        std::memset(desc, 0, sizeof(*desc));
+        std::memset(fr, 0, sizeof(*fr));
+        std::memset(tables, 0, sizeof(*tables) * SD_JPEG_ENTROPY_TABLES);
+        if (parse(false) != SD_OK || !sos || progressive || restart <= 0) return SD_OK;
+        if (sos_len < 1) return SD_OK;                                 // (an empty SOS segment may end at the file's end: nothing to read)
+        const int ns = sos[0];
+        if (ns != ncomp || sos_len < 1 + 2 * (size_t)ns + 3) return SD_OK;
+        for (int i = 0; i < ncomp; ++i) {
+            // the scan names the components in the frame header's order, and no two components share an id (scan() resolves ids by search)
+            if (sos[1 + 2 * i] != comp[i].id) return SD_OK;
+            for (int j = 0; j < i; ++j) if (comp[j].id == comp[i].id) return SD_OK;
+            comp[i].td = sos[2 + 2 * i] >> 4; comp[i].ta = sos[2 + 2 * i] & 15;
+            if (comp[i].td > 3 || comp[i].ta > 3) return SD_OK;
+            if (!dc[comp[i].td].present || !ac[comp[i].ta].present || !qt_ok[comp[i].tq]) return SD_OK;      // (block_store() refuses these)
+        }
+        const int mcus_x = (W + 8 * hmax - 1) / (8 * hmax), mcus_y = (H + 8 * vmax - 1) / (8 * vmax);
+        const int64_t total = (int64_t)mcus_x * mcus_y, n_iv = (total + restart - 1) / restart;
+        // the walk: memchr finds the FFs, everything between them is data
+        size_t pos = sos_data, begin = sos_data;
+        int64_t count = 0;
+        bool closed = false;
+        while (pos < len) {
+            const uint8_t* q = static_cast<const uint8_t*>(std::memchr(f + pos, 0xFF, len - pos));
+            if (!q) break;
+            const size_t at = (size_t)(q - f);
+            if (at + 1 >= len) break;
+            const int m = f[at + 1];
+            if (m == 0x00) { pos = at + 2; continue; }
+            const bool last = count + 1 == n_iv;
+            if (!last && m == 0xD0 + (int)(count & 7)) {
+                if ((size_t)count < iv_cap) { iv[count].begin = (uint32_t)(begin - sos_data); iv[count].end = (uint32_t)(at - sos_data); }
+                ++count;
+                begin = pos = at + 2;
+                continue;
+            }
+            if (last && m == 0xD9 && at + 2 == len) {
+                if ((size_t)count < iv_cap) { iv[count].begin = (uint32_t)(begin - sos_data); iv[count].end = (uint32_t)(at - sos_data); }
+                ++count;
+                fr->scan_begin = (uint32_t)sos_data; fr->scan_end = (uint32_t)at;
+                closed = true;
+            }
+            break;
+        }
+        if (!closed) return SD_OK;
+        for (int i = 0; i < ncomp; ++i) std::memcpy(qt_used[i], qt[comp[i].tq], sizeof(qt_used[i]));
+        fill_desc(desc);
+        fr->ncomp = ncomp; fr->mcus_x = mcus_x; fr->mcus_y = mcus_y; fr->restart_interval = restart; fr->n_intervals = (int32_t)n_iv;
+        for (int i = 0; i < ncomp; ++i) {
+            fr->comp_h[i] = comp[i].h; fr->comp_v[i] = comp[i].v; fr->comp_dc[i] = comp[i].td; fr->comp_ac[i] = comp[i].ta;
+            for (int k = 0; k < 2; ++k) {
+                const Huff& h = k ? ac[comp[i].ta] : dc[comp[i].td];
+                sd_jpeg_huff_table& t = tables[k ? 4 + comp[i].ta : comp[i].td];
+                std::memcpy(t.look, h.look, sizeof(t.look));
+                std::memcpy(t.vals, h.vals, sizeof(t.vals));
+                for (int l = 1; l <= 16; ++l) { t.mincode[l] = h.mincode[l]; t.maxcode[l] = h.maxcode[l]; t.valptr[l] = h.valptr[l]; }
+                t.maxcode[17] = h.maxcode[17];
+            }
+        }
+        if ((size_t)n_iv > iv_cap) return SD_ERR_INVALID;            // (eligible stays 0; n_intervals says what the file needs)
+        fr->eligible = 1;
+        return SD_OK;
+    }
+
     // the back half from a coefficient buffer: the planes of a descriptor's geometry, every block transformed, then emit_bgr
     sd_status reconstruct(const int16_t* coef, const sd_jpeg_frame_desc& d, uint8_t* out, size_t cap) {
         if (!sdjpeg::desc_ok(d) || cap < (size_t)d.height * d.width * 3) return SD_ERR_INVALID;
@@ -692,6 +761,20 @@ extern "C" sd_status sd_jpeg_decode_coefficients(const uint8_t* file_host, size_
             return st;
         }
         return d.decode_coefficients(coef_out_host, capacity_bytes, desc_out);
+    } catch (...) {
+        return SD_ERR_INVALID;
+    }
+}
+
+extern "C" sd_status sd_jpeg_entropy_plan(const uint8_t* file_host, size_t len, sd_jpeg_frame_desc* desc_out, sd_jpeg_entropy_frame* frame_out,
+                                          sd_jpeg_huff_table* tables_out, sd_jpeg_interval* intervals_out, size_t interval_cap) {
+    if (frame_out) std::memset(frame_out, 0, sizeof(*frame_out));       // eligible is 0 on every return but the eligible one
+    if (!file_host || !desc_out || !frame_out || !tables_out || (!intervals_out && interval_cap) || len >= ((size_t)1 << 31)) return SD_ERR_INVALID;
+    if (len < 2 || file_host[0] != 0xFF || file_host[1] != 0xD8) return SD_ERR_FORMAT;
+    try {
+        Decoder d;
+        d.f = file_host; d.len = len;
+        return d.plan(desc_out, frame_out, tables_out, intervals_out, interval_cap);
     } catch (...) {
         return SD_ERR_INVALID;
     }

@@ -103,8 +103,11 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     ``outputs`` (default: ``step.outputs``, set by ``make_engine_step(..., outputs=)``): an outputs.SequenceOutputs the step feeds; this
     rank writes the files of its shard only, and the manifest last -- 'ok', or 'range_error' / 'error' when the run raised (the files
     written before are then not valid outputs; the exception still propagates).
-    ``jpeg`` ("host" | "device") and ``engine`` go to the feeder: with "device" the JPEG frames are only entropy-decoded on the host and
-    reconstructed on the GPU by ``engine`` (default: ``step.engine``, set by make_engine_step); the frames are the same bytes.
+    ``jpeg`` ("host" | "device" | "device_entropy") and ``engine`` go to the feeder: with "device" the JPEG frames are only entropy-decoded on
+    the host and reconstructed on the GPU by ``engine`` (default: ``step.engine``, set by make_engine_step); with "device_entropy" the files
+    that have restart intervals (one interleaved sequential scan, DRI > 0, nothing but stuffed bytes and the expected RSTk markers in it) are
+    entropy-decoded on the GPU as well, the host only finds their markers, and every other JPEG falls back to the host decoder
+    (FrameFeeder.entropy_fallback names them); the frames are the same bytes on all three.
     ``png``, ``ply``, ``text``, ``render``, ``video`` (None = what the SequenceOutputs was built with) go to SequenceOutputs.configure before
     the first batch: the choices are described there, and what the step of make_engine_step does for each -- all but png="host",
     ply="host", text="json" and Video(route="host") need that step -- in its own docstring."""
@@ -124,7 +127,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     try:
         parts = []
         if hi > lo:
-            with FrameFeeder(paths[lo:hi], batch, device=device, workers=workers, jpeg=jpeg, engine=engine if jpeg == "device" else None) as feeder:
+            with FrameFeeder(paths[lo:hi], batch, device=device, workers=workers, jpeg=jpeg, engine=engine if jpeg != "host" else None) as feeder:
                 for frames, first in feeder:
                     rec = step(frames, lo + first)
                     assert rec.dtype == torch.uint8 and tuple(rec.shape) == (frames.shape[0], RECORD_BYTES), (rec.dtype, rec.shape)

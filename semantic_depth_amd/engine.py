@@ -75,6 +75,11 @@ def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _raw(a):
+    """the address of a ctypes array"""
+    return C.cast(a, C.c_void_p)
+
+
 class RangeError(L.SdError):
     """an activation left the range of the fp16 planes of a reduced-plane engine (|v| > 65504, or NaN): the outputs of the call are not the
     network's.  The fp32 reference has no such failure mode; run these weights with precision='bf16x3' or 'f32'."""
@@ -357,6 +362,37 @@ class Engine:
                                               self._stream())
         L.check(self.lib, self.h, st, "sd_jpeg_reconstruct_bgr")
         return out
+
+    def jpeg_entropy_decode(self, scan: torch.Tensor, descs, frames, tables, intervals, interval_stride: int, coef_stride: int | None = None,
+                            out: torch.Tensor | None = None, status: torch.Tensor | None = None):
+        """the device half of the entropy JPEG route (sd_jpeg_entropy_decode): ``scan`` u8 [B, byte_stride] device tensor of the frames'
+        scan bytes (byte_stride a multiple of 16) plus the plan records of sd_jpeg_entropy_plan / sd_plan_files_jpeg_entropy -- ``descs``
+        B _lib.sd_jpeg_frame_desc, ``frames`` B _lib.sd_jpeg_entropy_frame, ``tables`` B * 8 _lib.sd_jpeg_huff_table, ``intervals``
+        B * interval_stride _lib.sd_jpeg_interval, all HOST ctypes arrays -> (coef int16 [B, coef_stride], status int32 [B]) device
+        tensors: the coefficients sd_jpeg_decode_coefficients writes for every eligible frame (Engine.jpeg_reconstruct takes them as they
+        are) and a non-zero status word for a frame whose stream was refused; ineligible frames keep what ``out`` held.  One lane per
+        restart interval, on the current stream, no synchronisation: the host arrays must stay unchanged until the stream has passed
+        the call when they are pinned.  ``coef_stride`` (int16 elements, a multiple of 8) defaults to the largest frame's need."""
+        assert scan.dtype == torch.uint8 and scan.is_cuda and scan.is_contiguous() and scan.dim() == 2
+        B = scan.shape[0]
+        if B < 1 or len(descs) < B or len(frames) < B:
+            raise ValueError("jpeg_entropy_decode: one descriptor and one record per frame")
+        if coef_stride is None:
+            coef_stride = out.shape[1] if out is not None else max(-(-descs[i].coef_elems() // 8) * 8 for i in range(B))
+        if out is None:
+            out = torch.empty((B, coef_stride), dtype=torch.int16, device=self.device)
+        if status is None:
+            status = torch.empty((B,), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int16 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, coef_stride)
+        assert status.dtype == torch.int32 and status.is_cuda and status.is_contiguous() and status.numel() >= B
+        need = C.c_size_t()
+        st = self.lib.sd_jpeg_entropy_workspace(B, interval_stride, C.byref(need))
+        L.check(self.lib, None, st, "sd_jpeg_entropy_workspace")
+        ws = torch.empty((need.value,), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_jpeg_entropy_decode(self.h, _ptr(scan), scan.shape[1], _raw(descs), _raw(frames), _raw(intervals), interval_stride,
+                                             _raw(tables), B, _ptr(out), coef_stride * 2, _ptr(status), _ptr(ws), need.value, self._stream())
+        L.check(self.lib, self.h, st, "sd_jpeg_entropy_decode")
+        return out, status
 
     def compose_result_frames(self, frames: torch.Tensor, road: torch.Tensor, fence: torch.Tensor, records: torch.Tensor, out_h: int, out_w: int,
                               road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, out: torch.Tensor | None = None) -> torch.Tensor:
