@@ -22,6 +22,10 @@ Pinning status:
                         SavedModel) and the monodepth body (mrharicot/monodepth, unpinned copy)
                         are absent from the reference tree: PARITY UNPINNED, restated from the
                         published architectures.
+  * oracle.layers     — the two graphs of oracle.nets layer by layer, each layer a function of named input tensors, with a derived
+                        per-element error bound (tests/test_gpu_layers.py checks every GPU layer alone against it).  PINNED to
+                        oracle.nets: tests/test_layer_check_cpu.py asserts that the chained layers reproduce nets.fcn8s_forward /
+                        nets.monodepth_forward in float64 bit for bit, and that the layer list names every op of nets.py once.
   * oracle.o3d        — Open3D legacy statistical/radius outlier removal [UPSTREAM, version
                         unpinned, not in requirements.txt]: PARITY UNPINNED.
 """
