@@ -221,8 +221,9 @@ __device__ float block_median_fast(F val, int n, Lds& L, MedLds& M) {
     for (int o = 32; o > 0; o >>= 1) { below += __shfl_xor(below, o); nanf |= __shfl_xor(nanf, o); }
     if ((tid & 63) == 0) { atomicAdd(&M.below, below); if (nanf) atomicOr(&M.nan, 1u); }
     __syncthreads();
-    const unsigned cnt = M.cnt, bel = M.below;
-    if (M.nan) return __uint_as_float(0x7fc00000u);
+    const unsigned cnt = M.cnt, bel = M.below, has_nan = M.nan;
+    __syncthreads();               // all have read the totals: the NaN exit below has no barrier behind it, and a caller's next median resets M
+    if (has_nan) return __uint_as_float(0x7fc00000u);
     if (cnt > MED_CAP || r1 < bel || r2 >= bel + cnt) return block_median(val, n, L);       // bracket missed: exact fallback
     auto bval = [&](int j) { return key2f(M.buf[j]); };
     const float a = block_select(bval, (int)cnt, r1 - bel, L);
@@ -581,7 +582,8 @@ hipError_t launch_mad_filter(CloudView in, CloudOut out, int B, int cap, int axi
 // ------------------------------------------------------------------------------------------ K22 plane fit
 // pcl.remove_noise_by_fitting_plane (pcl.py:84-209): least squares dep = C0*u + C1*v + C2 in float64
 // (the reference calls scipy.linalg.lstsq on float64 columns; here: centred normal equations, float64,
-// deterministic reduction order), then keep |C0*u + C1*v - dep + C2| < thr (float64).
+// deterministic reduction order), then keep |C0*u + C1*v - dep + C2| < thr (float64).  A rank-deficient cloud (< 3 points,
+// or (u, v) collinear: det == 0 or rounding noise) is outside the parity contract -- lstsq returns the minimum-norm solution.
 template <bool COMPACT>
 __global__ __launch_bounds__(TB) void plane_filter_kernel(CloudView in, CloudOut out, int cap, int axis, double thr, double* coeff, double* params) {
     FRAME_VIEW();

@@ -293,7 +293,8 @@ def test_extract_pcls_and_mean_bit_exact(pcl, mini):
 
 
 def test_fence_chain_golden_and_oracle(pcl, mini, golden_dir):
-    """fence chain + fence-to-fence: mini scene vs the reference-captured arrays, 512x1024 fence scene vs digests."""
+    """fence chain + fence-to-fence: mini scene vs the reference-captured arrays, 512x1024 fence scene vs digests.
+    The pcl mirror of the mini part runs the multi-block forms; the in-place single-workgroup forms are held by test_gpu_pcl_chains.py."""
     from oracle import pipeline as op
     from semantic_depth_amd.engine import FenceParams
     e = pcl._eng()
