@@ -597,6 +597,24 @@ sd_status sd_postprocess_fuse_backproject(sd_handle* h, const float* disp_raw, f
                                           float* road_xyz, uint8_t* road_rgb, int32_t* n_road, float* fence_xyz, uint8_t* fence_rgb,
                                           int32_t* n_fence, void* stream);
 
+/* The calibration mode's inner loop, semantic_depth.py:854-906 (every frame once per trial focal length), behind ONE network pass:
+ * sd_fuse_backproject for B frames under T trial cameras each, in one count + scan + write.  cams_host[t * B + b] is frame b's camera
+ * of trial t (HOST pointer).  Slot s = t * B + b of road_xyz f32 [T*B,cap,3], road_rgb u8 [T*B,cap,3] (nullable) and n_road i32 [T*B]
+ * receives, bit for bit, what sd_fuse_backproject writes for frame b with that camera: the full count (also when it passes cap), rows
+ * [0, min(n, cap)); rows behind that are not written.  The fence outputs are nullable as a group (fence_rgb alone may be NULL too).
+ * The masks are counted and scanned once per frame; a kept pixel loads its disparity and colour once and is projected through the
+ * frame's T cameras.  The cameras, block counts and offsets live in workspace_dev (sd_fuse_sweep_workspace bytes for the handle's
+ * H x W; 0 = bad arguments); every workspace byte that is read is written by the same call.  Enqueued on `stream`, no synchronisation;
+ * the handle need not be bound.  SD_ERR_INVALID, nothing launched: a null disp_pp, road_mask, cams_host, road_xyz, n_road or
+ * workspace_dev; B < 1, T < 1, T * B > 65535, cap < 1; fence_xyz without fence_mask or n_fence; a colour output without frames;
+ * workspace_bytes below sd_fuse_sweep_workspace; a workspace that is not 16-byte aligned. */
+size_t sd_fuse_sweep_workspace(int B, int T, int H, int W);
+sd_status sd_fuse_backproject_sweep(sd_handle* h, const float* disp_pp, const uint8_t* road_mask, const uint8_t* fence_mask,
+                                    const uint8_t* frames, const sd_camera* cams_host /* [T][B] */, int B, int T, int cap,
+                                    float* road_xyz, uint8_t* road_rgb, int32_t* n_road,
+                                    float* fence_xyz, uint8_t* fence_rgb, int32_t* n_fence,
+                                    void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* the road chain of FrameProcessor.process_frame, semantic_depth.py:203-259 (seq:180-238):
  * z-cut -> MAD(y) -> MAD(x) -> plane fit -> [Open3D statistical + radius] -> end points -> width.
  * road_xyz f32 [B,cap,3], n_road i32 [B] (device).  road_rgb (nullable) u8 [B,cap,3]: the colours the reference carries

@@ -158,6 +158,9 @@ SIGNATURES = {
     "sd_compose_result_frames": (C.c_int, [_H, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
     "sd_fuse_backproject": (C.c_int, [_H, _P, _P, _P, _P, C.POINTER(sd_camera), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sd_postprocess_fuse_backproject": (C.c_int, [_H, _P, _P, _P, _P, _P, C.POINTER(sd_camera), C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "sd_fuse_sweep_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "sd_fuse_backproject_sweep": (C.c_int, [_H, _P, _P, _P, _P, C.POINTER(sd_camera), C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P,
+                                            C.c_size_t, _P]),
     "sd_road_width": (C.c_int, [_H, _P, _P, _P, C.c_int, C.c_int, C.POINTER(sd_rw_params), _P, _P, _P, _P, _P]),
     "sd_fence_to_fence": (C.c_int, [_H, _P, _P, _P, C.c_int, C.c_int, _P, C.POINTER(sd_f2f_params), _P, _P, _P, _P, _P, _P]),
     "sd_pcl_extract_pcls": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),

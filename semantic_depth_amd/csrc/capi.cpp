@@ -49,6 +49,7 @@ struct sd_handle {
     int small_batch = 0, cus = 0;   // sd_set_small_batch: the split-K forms of the under-filled GEMM layers; the CU count its rule reads (latched with it)
     size_t o_splitk = 0;            // workspace: the partial sums of the largest split layer (0 bytes without the switch)
     std::vector<CamDev> cams_stage;
+    std::vector<CamDev> sweep_stage;     // sd_fuse_backproject_sweep: the [T][B] records of the last call (source of its upload)
     std::map<std::pair<int, int>, std::vector<float>> bias_host;   // (net, slot) -> host copy, for bias slots that are summed
     std::map<std::pair<int, int>, std::vector<float>> w_host;      // (net, slot) -> f32 tensor of the SD_PREC_F16X2 slots that share a weight scale (sd_load_weight)
     std::string err;
@@ -1035,6 +1036,42 @@ sd_status sd_postprocess_fuse_backproject(sd_handle* h, const float* disp_raw, f
     }
     return fuse_impl(h, nullptr, disp_raw, disp_pp_out, road, fence, frames, cams, B, cap, nullptr, road_xyz, road_rgb, n_road, fence_xyz,
                      fence_rgb, n_fence, stream);
+}
+
+size_t sd_fuse_sweep_workspace(int B, int T, int H, int W) {
+    if (B < 1 || T < 1 || H < 1 || W < 1 || (long long)T * B > 65535) return 0;
+    return fuse_sweep_workspace_bytes(B, T, H, W);
+}
+
+sd_status sd_fuse_backproject_sweep(sd_handle* h, const float* disp_pp, const uint8_t* road, const uint8_t* fence, const uint8_t* frames,
+                                    const sd_camera* cams, int B, int T, int cap, float* road_xyz, uint8_t* road_rgb, int32_t* n_road,
+                                    float* fence_xyz, uint8_t* fence_rgb, int32_t* n_fence, void* workspace_dev, size_t workspace_bytes,
+                                    void* stream) {
+    if (!h || !disp_pp || !road || !cams || !road_xyz || !n_road || !workspace_dev)
+        return fail(h, SD_ERR_INVALID, "sd_fuse_backproject_sweep: null pointer");
+    if (B < 1 || T < 1 || (long long)T * B > 65535 || cap < 1)
+        return fail(h, SD_ERR_INVALID, "sd_fuse_backproject_sweep: B, T and cap must be >= 1 and T * B at most 65535");
+    if (fence_xyz ? (!fence || !n_fence) : (fence_rgb != nullptr))
+        return fail(h, SD_ERR_INVALID, "sd_fuse_backproject_sweep: the fence cloud needs its mask and its counter, its colours need the cloud");
+    if ((road_rgb || fence_rgb) && !frames) return fail(h, SD_ERR_INVALID, "sd_fuse_backproject_sweep: a colour output needs frames");
+    // every index the kernels form follows from B, T, cap, the handle's H x W and this capacity: nothing is launched otherwise
+    if (workspace_bytes < fuse_sweep_workspace_bytes(B, T, h->H, h->W))
+        return fail(h, SD_ERR_INVALID, "sd_fuse_backproject_sweep: workspace smaller than sd_fuse_sweep_workspace reports");
+    if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(disp_pp) & 3) || (reinterpret_cast<uintptr_t>(road_xyz) & 3) ||
+        (reinterpret_cast<uintptr_t>(fence_xyz) & 3) || (reinterpret_cast<uintptr_t>(n_road) & 3) || (reinterpret_cast<uintptr_t>(n_fence) & 3))
+        return fail(h, SD_ERR_INVALID, "sd_fuse_backproject_sweep: workspace_dev must be 16-byte, the float and counter arrays 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    SweepParams p{};
+    p.disp_pp = disp_pp; p.road = road; p.fence = fence_xyz ? fence : nullptr; p.frames = (road_rgb || fence_rgb) ? frames : nullptr;
+    p.B = B; p.T = T; p.H = h->H; p.W = h->W; p.cap = cap; p.sw = h->sw;
+    p.road_xyz = road_xyz; p.road_rgb = road_rgb; p.n_road = n_road;
+    p.fence_xyz = fence_xyz; p.fence_rgb = fence_rgb; p.n_fence = fence_xyz ? n_fence : nullptr;
+    fuse_sweep_layout(p, static_cast<uint8_t*>(workspace_dev));
+    h->sweep_stage.resize((size_t)T * B);
+    for (size_t i = 0; i < (size_t)T * B; ++i) h->sweep_stage[i] = make_cam(cams[i]);
+    HIPCHK(h, hipMemcpyAsync(const_cast<CamDev*>(p.cams), h->sweep_stage.data(), sizeof(CamDev) * (size_t)T * B, hipMemcpyHostToDevice, s));
+    HIPCHK(h, launch_fuse_sweep(p, s));
+    return SD_OK;
 }
 
 sd_status sd_road_width(sd_handle* h, const float* road_xyz, const uint8_t* road_rgb, const int32_t* n_road, int B, int cap,

@@ -566,4 +566,180 @@ hipError_t launch_fuse(const FuseParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Camera sweep (the calibration mode, semantic_depth.py:843-944: every frame once per trial focal length): T trial cameras per frame
+// behind ONE compaction.  The masks, the disparity, the colours and the row-major rank of a kept pixel do not depend on the camera, so
+// the count and scan launches above run once per frame (fuse_count4_kernel / fuse_count_kernel, fuse_scan_kernel) and the write kernel
+// below projects each kept pixel through the frame's T cameras: slot t * B + b receives what fuse_write_kernel writes for frame b with
+// camera cams[t][b], bit for bit (the same expressions, the sparse-Q form under fuse_onepass_kernel's guard).
+//   * a kept pixel loads its mask, disparity and colour once; the cameras come from LDS in tiles of SWEEP_TC records, staged once per
+//     workgroup and read at a wave-uniform address (a broadcast)
+//   * positions come from the wave prefix as in fuse_write4_kernel: consecutive kept pixels write consecutive rows of a slot, a point
+//     is one 12-byte store
+//   * the last block of a frame knows the frame's totals (its offset + its own count) and writes them to the T slots' counters
+// Workspace (the caller's; every byte read is written by the same call): [T][B] CamDev | blk_counts [B][nblk][2] | blk_offsets [B][nblk][2].
+constexpr int SWEEP_TC = 32;
+struct SweepCam { double q[16]; float mult; int sparse; };      // CamDev + "Q has make_cam's zero pattern"
+static size_t sweep_align16(size_t v) { return (v + 15) & ~(size_t)15; }
+static size_t sweep_blk_bytes(int B, int H, int W) { return sweep_align16((size_t)B * (((size_t)H * W + 255) / 256) * 2 * sizeof(int32_t)); }
+size_t fuse_sweep_workspace_bytes(int B, int T, int H, int W) {
+    return sweep_align16((size_t)T * B * sizeof(CamDev)) + 2 * sweep_blk_bytes(B, H, W);
+}
+void fuse_sweep_layout(SweepParams& p, uint8_t* ws) {
+    p.cams = reinterpret_cast<CamDev*>(ws);
+    ws += sweep_align16((size_t)p.T * p.B * sizeof(CamDev));
+    p.blk_counts = reinterpret_cast<int32_t*>(ws);
+    p.blk_offsets = reinterpret_cast<int32_t*>(ws + sweep_blk_bytes(p.B, p.H, p.W));
+}
+
+// PPT pixels per thread: 4 (W % 4 == 0, aligned inputs: the loads of fuse_write4_kernel) or 1 (any geometry)
+template <int PPT>
+__global__ __launch_bounds__(256) void fuse_sweep_write_kernel(const SweepParams p, int npix, int nblk) {
+    const int b = blockIdx.y, blk = blockIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i0 = (blk * 256 + threadIdx.x) * PPT;             // this thread's first pixel
+    const bool in = i0 < npix;
+    const size_t g0 = (size_t)b * npix + (size_t)i0;
+    unsigned mr = 0, mf = 0;                                     // one byte per pixel, as fuse_write4_kernel
+    if (in) {
+        if constexpr (PPT == 4) {
+            mr = *reinterpret_cast<const unsigned*>(p.road + g0);
+            if (p.fence) mf = *reinterpret_cast<const unsigned*>(p.fence + g0);
+        } else {
+            mr = p.road[g0];
+            if (p.fence) mf = p.fence[g0];
+        }
+    }
+    const int cr = nz_bytes(mr), cf = nz_bytes(mf);
+    int pre_r, tot_r, pre_f, tot_f;
+    wave_prefix_total(cr, lane, pre_r, tot_r);
+    wave_prefix_total(cf, lane, pre_f, tot_f);
+    __shared__ int wr[4], wf[4];
+    __shared__ SweepCam cam_s[SWEEP_TC];
+    if (lane == 0) { wr[wave] = tot_r; wf[wave] = tot_f; }
+    __syncthreads();
+    const int blk_r = wr[0] + wr[1] + wr[2] + wr[3], blk_f = wf[0] + wf[1] + wf[2] + wf[3];
+    const int32_t* off = p.blk_offsets + ((size_t)b * nblk + blk) * 2;
+    const int off_r = off[0], off_f = off[1];
+    if (blk == nblk - 1) {                                       // the frame's totals, to every trial's slot
+        for (int t = threadIdx.x; t < p.T; t += 256) {
+            p.n_road[(size_t)t * p.B + b] = off_r + blk_r;
+            if (p.n_fence) p.n_fence[(size_t)t * p.B + b] = off_f + blk_f;
+        }
+    }
+    if (blk_r + blk_f == 0) return;                              // (uniform over the block: no barrier is skipped by a part of it)
+    int pos_r = off_r + pre_r, pos_f = off_f + pre_f;
+    for (int w = 0; w < wave; ++w) { pos_r += wr[w]; pos_f += wf[w]; }
+    // ---- the camera-independent part of this thread's kept pixels, once ----
+    const bool kept = (mr | mf) != 0u;
+    float dv[PPT];
+    unsigned rgb[PPT];                                           // R | G << 8 | B << 16: colours = cv2.cvtColor(frame, BGR2RGB), semantic_depth.py:161
+#pragma unroll
+    for (int k = 0; k < PPT; ++k) { dv[k] = 0.f; rgb[k] = 0u; }
+    int y = 0, x0 = 0;
+    if (kept) {
+        y = i0 / p.W; x0 = i0 - y * p.W;
+        if constexpr (PPT == 4) {
+            const float4 dq = *reinterpret_cast<const float4*>(p.disp_pp + g0);
+            dv[0] = dq.x; dv[1] = dq.y; dv[2] = dq.z; dv[3] = dq.w;
+            if (p.frames) {
+                const unsigned* fp = reinterpret_cast<const unsigned*>(p.frames + g0 * 3);
+                const unsigned f0 = fp[0], f1 = fp[1], f2 = fp[2];
+                const unsigned long long lo64 = ((unsigned long long)f1 << 32) | f0, hi64 = ((unsigned long long)f2 << 32) | f1;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {                    // bytes 3k .. 3k+2 of the 12 frame bytes: B, G, R
+                    const unsigned bgr = k < 2 ? (unsigned)(lo64 >> (24 * k)) : (unsigned)(hi64 >> (24 * k - 32));
+                    rgb[k] = ((bgr >> 16) & 0xffu) | (bgr & 0xff00u) | ((bgr & 0xffu) << 16);
+                }
+            }
+        } else {
+            dv[0] = p.disp_pp[g0];
+            if (p.frames) { const uint8_t* fp = p.frames + g0 * 3; rgb[0] = (unsigned)fp[2] | ((unsigned)fp[1] << 8) | ((unsigned)fp[0] << 16); }
+        }
+    }
+    const double yd = (double)y;
+    for (int t0 = 0; t0 < p.T; t0 += SWEEP_TC) {
+        const int nt = p.T - t0 < SWEEP_TC ? p.T - t0 : SWEEP_TC;
+        if (t0) __syncthreads();                                 // the previous tile has been read
+        if ((int)threadIdx.x < nt) {
+            const CamDev c = p.cams[(size_t)(t0 + threadIdx.x) * p.B + b];
+            SweepCam sc;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) sc.q[j] = c.q[j];
+            sc.mult = c.mult;
+            const double* q = c.q;
+            sc.sparse = q[0] == 1.0 && q[1] == 0.0 && q[2] == 0.0 && q[4] == 0.0 && q[5] == -1.0 && q[6] == 0.0 && q[8] == 0.0 && q[9] == 0.0 &&
+                        q[10] == 0.0 && q[12] == 0.0 && q[13] == 0.0 && q[15] == 0.0;
+            cam_s[threadIdx.x] = sc;
+        }
+        __syncthreads();
+        if (!kept) continue;
+        for (int t = 0; t < nt; ++t) {
+            const SweepCam& cam = cam_s[t];
+            const double* q = cam.q;
+            const size_t slot = ((size_t)(t0 + t) * p.B + b) * (size_t)p.cap;
+            F1Vec3* const oxr = reinterpret_cast<F1Vec3*>(p.road_xyz) + slot;
+            F1Vec3* const oxf = p.fence_xyz ? reinterpret_cast<F1Vec3*>(p.fence_xyz) + slot : nullptr;
+            int pr = pos_r, pf = pos_f;
+#pragma unroll
+            for (int k = 0; k < PPT; ++k) {
+                const bool r = (mr >> (8 * k)) & 0xffu, f = (mf >> (8 * k)) & 0xffu;
+                if (!r && !f) continue;
+                // disparity = disp_pp * multiplier in float32 (semantic_depth.py:145; seq:146); cv2.reprojectImageTo3D as fuse_write_kernel:
+                // homg = Q*(x,y,d,1) in double, left to right; numerators narrowed to float, multiplied by the double 1/W, narrowed again
+                const float dpx = dv[k] * cam.mult;
+                const double xd = (double)(x0 + k), d = (double)dpx;
+                double Wh, n0, n1, n2;
+                if (cam.sparse && fabsf(dpx) < INFINITY) {
+                    // Q of make_cam and a finite disparity: the zero products and the additions of +0.0 drop out without changing a bit
+                    // (fuse_onepass_kernel)
+                    Wh = 0.0 + q[14] * d;
+                    n0 = xd + q[3];
+                    n1 = (0.0 - yd) + q[7];
+                    n2 = q[11];
+                } else {
+                    Wh = ((q[12] * xd + q[13] * yd) + q[14] * d) + q[15];
+                    n0 = ((q[0] * xd + q[1] * yd) + q[2] * d) + q[3];
+                    n1 = ((q[4] * xd + q[5] * yd) + q[6] * d) + q[7];
+                    n2 = ((q[8] * xd + q[9] * yd) + q[10] * d) + q[11];
+                }
+                const double iW = 1.0 / Wh;                     // Vec3f /= double is a multiply by 1./alpha (core/matx.hpp)
+                const F1Vec3 pt{(float)((double)(float)n0 * iW), (float)((double)(float)n1 * iW), (float)((double)(float)n2 * iW)};
+                if (r) {
+                    if (pr < p.cap) {
+                        oxr[pr] = pt;
+                        if (p.road_rgb) { uint8_t* c = p.road_rgb + (slot + pr) * 3; c[0] = (uint8_t)rgb[k]; c[1] = (uint8_t)(rgb[k] >> 8); c[2] = (uint8_t)(rgb[k] >> 16); }
+                    }
+                    ++pr;
+                }
+                if (f && oxf) {
+                    if (pf < p.cap) {
+                        oxf[pf] = pt;
+                        if (p.fence_rgb) { uint8_t* c = p.fence_rgb + (slot + pf) * 3; c[0] = (uint8_t)rgb[k]; c[1] = (uint8_t)(rgb[k] >> 8); c[2] = (uint8_t)(rgb[k] >> 16); }
+                    }
+                    ++pf;
+                }
+            }
+        }
+    }
+}
+
+hipError_t launch_fuse_sweep(const SweepParams& p, hipStream_t s) {
+    const int npix = p.H * p.W;
+    const auto al = [](const void* q, uintptr_t a) { return (reinterpret_cast<uintptr_t>(q) & (a - 1)) == 0; };
+    const bool four = p.W % 4 == 0 && !(p.sw & SW_NO_FUSE4) && al(p.disp_pp, 16) && al(p.road, 4) && al(p.fence, 4) && al(p.frames, 4);
+    if (four) {
+        const int nblk = (npix + 1023) / 1024;
+        hipLaunchKernelGGL(fuse_count4_kernel, dim3(nblk, p.B), dim3(256), 0, s, p.road, p.fence, npix, nblk, p.blk_counts);
+        hipLaunchKernelGGL(fuse_scan_kernel, dim3(p.B), dim3(1024), 0, s, p.blk_counts, p.blk_offsets, nblk, (int32_t*)nullptr, (int32_t*)nullptr);
+        hipLaunchKernelGGL(fuse_sweep_write_kernel<4>, dim3(nblk, p.B), dim3(256), 0, s, p, npix, nblk);
+    } else {
+        const int nblk = (npix + 255) / 256;
+        hipLaunchKernelGGL(fuse_count_kernel, dim3(nblk, p.B), dim3(256), 0, s, p.road, p.fence, npix, nblk, p.blk_counts);
+        hipLaunchKernelGGL(fuse_scan_kernel, dim3(p.B), dim3(1024), 0, s, p.blk_counts, p.blk_offsets, nblk, (int32_t*)nullptr, (int32_t*)nullptr);
+        hipLaunchKernelGGL(fuse_sweep_write_kernel<1>, dim3(nblk, p.B), dim3(256), 0, s, p, npix, nblk);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace sd

@@ -357,6 +357,21 @@ size_t fuse_onepass_scratch_bytes(int B, int H, int W);
 bool fuse_onepass_eligible(const FuseParams& p);
 size_t fuse_scratch_bytes(int B, int H, int W);
 hipError_t launch_fuse(const FuseParams& p, hipStream_t s);
+// camera sweep (fuse.hip fuse_sweep_write_kernel): T trial cameras per frame behind one count + scan; slot t * B + b of the outputs
+struct SweepParams {
+    const float* disp_pp;      // [B,H,W]
+    const uint8_t* road; const uint8_t* fence; const uint8_t* frames;    // fence, frames nullable
+    const CamDev* cams;        // device [T][B] (in the caller's workspace)
+    int B, T, H, W, cap;
+    float* road_xyz; uint8_t* road_rgb; int32_t* n_road;                 // [T*B,cap,3], [T*B,cap,3] nullable, [T*B]
+    float* fence_xyz; uint8_t* fence_rgb; int32_t* n_fence;              // nullable as a group
+    int32_t* blk_counts;       // workspace [B][nblk][2]
+    int32_t* blk_offsets;      // workspace [B][nblk][2]
+    unsigned sw;               // Switch bits of the handle (SW_NO_FUSE4: one pixel per thread)
+};
+size_t fuse_sweep_workspace_bytes(int B, int T, int H, int W);
+void fuse_sweep_layout(SweepParams& p, uint8_t* workspace);             // sets cams, blk_counts, blk_offsets from B, T, H, W
+hipError_t launch_fuse_sweep(const SweepParams& p, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // road-width tail (pcl.hip; -ffp-contract=off)

@@ -71,6 +71,17 @@ class Camera:
     disp_mult: float
 
 
+def sweep_chunks(B: int, T: int, max_batch: int) -> list:
+    """the trial ranges [(t0, t1), ...] Engine.sweep_tail walks: max(1, max_batch // B) trials per chunk, so that no chain call
+    carries more than max_batch (trial, frame) slots.  B > max_batch is refused: a chain call takes at most max_batch slots."""
+    if B < 1 or T < 1:
+        raise ValueError(f"a sweep needs at least one frame and one trial, got B={B}, T={T}")
+    if B > max_batch:
+        raise ValueError(f"a sweep of B={B} frames needs max_batch >= B, the engine has {max_batch}")
+    per = max(1, max_batch // B)
+    return [(t0, min(T, t0 + per)) for t0 in range(0, T, per)]
+
+
 def _ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -585,6 +596,51 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_postprocess_fuse_backproject")
         return out
 
+    def _sweep_buffers(self, slots: int, B: int, T: int, cap: int, rgb: bool, fence_group: bool) -> dict:
+        """the fuse dict of ``slots`` (trial, frame) slots plus the workspace of a T-trial launch over B frames"""
+        dev = self.device
+        out = dict(dense=None)
+        for k, on in (("road", True), ("fence", fence_group)):
+            out[f"{k}_xyz"] = torch.empty((slots, cap, 3), dtype=torch.float32, device=dev) if on else None
+            out[f"{k}_rgb"] = torch.empty((slots, cap, 3), dtype=torch.uint8, device=dev) if (on and rgb) else None
+            out[f"n_{k}"] = torch.empty((slots,), dtype=torch.int32, device=dev) if on else None
+        nbytes = int(self.lib.sd_fuse_sweep_workspace(B, T, self.H, self.W))
+        if nbytes == 0:
+            raise ValueError(f"sd_fuse_sweep_workspace refuses B={B}, T={T} (T * B is at most 65535)")
+        out["workspace"] = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+        return out
+
+    def _fuse_sweep_into(self, buf: dict, disp_pp, road, fence, frames, cams) -> dict:
+        """one sd_fuse_backproject_sweep launch of len(cams) trials into the first T * B slots of ``buf`` (_sweep_buffers); returns views"""
+        B, T = disp_pp.shape[0], len(cams)
+        if any(len(row) != B for row in cams):
+            raise ValueError(f"cams must be T lists of B={B} cameras")
+        n = T * B
+        cap = buf["road_xyz"].shape[1]
+        if n > buf["road_xyz"].shape[0]:
+            raise ValueError(f"{T} trials of {B} frames do not fit buffers of {buf['road_xyz'].shape[0]} slots")
+        assert disp_pp.dtype == torch.float32 and disp_pp.is_contiguous() and tuple(disp_pp.shape) == (B, self.H, self.W), disp_pp.shape
+        for m in (road, fence):
+            assert m is None or (m.dtype == torch.uint8 and m.is_contiguous() and tuple(m.shape) == (B, self.H, self.W)), m.shape
+        assert frames is None or self._frames(frames) == B
+        carr = (L.sd_camera * n)(*[L.sd_camera(c.cx, c.cy, c.f, c.b, c.disp_mult) for row in cams for c in row])
+        out = {k: (v[:n] if v is not None else None) for k, v in buf.items() if k != "workspace"}
+        ws = buf["workspace"]
+        st = self.lib.sd_fuse_backproject_sweep(self.h, _ptr(disp_pp), _ptr(road), _ptr(fence if out["fence_xyz"] is not None else None),
+                                                _ptr(frames), carr, B, T, cap, _ptr(out["road_xyz"]), _ptr(out["road_rgb"]), _ptr(out["n_road"]),
+                                                _ptr(out["fence_xyz"]), _ptr(out["fence_rgb"]), _ptr(out["n_fence"]), _ptr(ws), ws.numel(),
+                                                self._stream())
+        L.check(self.lib, self.h, st, "sd_fuse_backproject_sweep")
+        return out
+
+    def fuse_backproject_sweep(self, disp_pp, road, fence, frames, cams, cap: int | None = None, want_rgb: bool = True, want_fence: bool = True):
+        """fuse_backproject for B frames under T trial cameras each, behind ONE compaction (sd_fuse_backproject_sweep): ``cams`` is a list
+        of T lists of B Camera.  Returns the fuse dict with a leading T * B axis: slot t * B + b holds, bit for bit, what fuse_backproject
+        gives frame b with cams[t][b]."""
+        B, T = disp_pp.shape[0], len(cams)
+        buf = self._sweep_buffers(T * B, B, T, cap or self.cap, want_rgb and frames is not None, want_fence and fence is not None)
+        return self._fuse_sweep_into(buf, disp_pp, road, fence, frames, cams)
+
     def road_width(self, road_xyz, n_road, params: RoadWidthParams = RoadWidthParams(), want_final: bool = False, road_rgb=None):
         """road chain (semantic_depth.py:203-259).  ``road_rgb`` (u8 [B,cap,3], optional): the colours the reference carries
         through every filter.  want_final: also return the denoised cloud -> (records, xyz, n) or, with colours,
@@ -671,6 +727,44 @@ class Engine:
             else:
                 out["f2f"] = f2
         return out
+
+    # ------------------------------------------------------------------ camera sweep (the calibration mode, semantic_depth.py:843-944)
+    def sweep_tail(self, disp_pp, road, fence, frames, cams, params: RoadWidthParams = RoadWidthParams(), approach: str = "rw",
+                   fence_params: FenceParams | None = None, colours: bool = False):
+        """everything behind the networks for B frames under T trial cameras each (``cams``: T lists of B Camera): the trials are walked in
+        chunks of max(1, max_batch // B) (sweep_chunks), per chunk one sweep launch, one road_width and -- approach == 'both' -- one
+        fence_to_fence over the chunk's (trial, frame) slots, all into one set of buffers.  One RoadWidthParams / FenceParams per sweep.
+        Returns dict(records, f2f): DEVICE buffers of T * B sd_rw_result / sd_f2f_result (f2f None unless 'both'), slot t * B + b, the bytes
+        fuse_backproject + road_width + fence_to_fence give frame b with cams[t][b]; nothing is read back here (Engine.records /
+        f2f_records read them, once)."""
+        if approach not in ("rw", "both"):
+            raise ValueError("approach must be 'rw' or 'both' (semantic_depth.py:743-745)")
+        B, T = disp_pp.shape[0], len(cams)
+        chunks = sweep_chunks(B, T, self.max_batch)
+        per = chunks[0][1] - chunks[0][0]
+        both = approach == "both"
+        rgb = colours and frames is not None
+        buf = self._sweep_buffers(per * B, B, per, self.cap, rgb, both)
+        records = torch.empty((T * B, RW_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        f2f = torch.empty((T * B, F2F_DTYPE.itemsize), dtype=torch.uint8, device=self.device) if both else None
+        fp = fence_params or FenceParams(depth=params.depth)
+        for t0, t1 in chunks:
+            fz = self._fuse_sweep_into(buf, disp_pp, road, fence, frames if rgb else None, cams[t0:t1])
+            rw = self.road_width(fz["road_xyz"], fz["n_road"], params, road_rgb=fz["road_rgb"])
+            records[t0 * B:t1 * B].copy_(rw)
+            if both:
+                f2f[t0 * B:t1 * B].copy_(self.fence_to_fence(fz["fence_xyz"], fz["n_fence"], rw, fp, fence_rgb=fz["fence_rgb"]))
+        return dict(records=records, f2f=f2f)
+
+    def camera_sweep(self, frames: torch.Tensor, cams, params: RoadWidthParams = RoadWidthParams(), approach: str = "rw",
+                     fence_params: FenceParams | None = None, colours: bool = False):
+        """process_batch for B frames under T trial cameras each with ONE pass of each network: the cameras enter the path only behind the
+        networks, so fcn8s_forward and monodepth_forward run once (the public methods: on_range and the range check as everywhere else)
+        and sweep_tail does the rest.  Returns dict(seg, disp_pp, records, f2f); records / f2f as sweep_tail."""
+        seg = self.fcn8s_forward(frames)
+        disp_pp = self.monodepth_forward(frames)
+        tail = self.sweep_tail(disp_pp, seg["road"], seg["fence"], frames, cams, params, approach, fence_params, colours)
+        return dict(seg=seg, disp_pp=disp_pp, records=tail["records"], f2f=tail["f2f"])
 
     # ------------------------------------------------------------------ introspection
     def net_tensor(self, net: int, name: str) -> torch.Tensor:

@@ -9,6 +9,7 @@
                                        combined / ``_ALL`` PLY files, incl. the three visualisation planes of the combined cloud)
     road_plane_grid / fence_plane_grids <- the ``plane3D`` arrays of :215-219, :294-309 rebuilt through the reference's own pcl call sequence
     focal_sweep                     <- semantic_depth.py:854-944  (``results/<f>/data.txt``, ``best_focal_lengths.txt``)
+    focal_sweep_batched             the same files behind one network pass per frame (Engine.camera_sweep)
     write_png                       <- cv2.imwrite(...png) at :406 (zlib-deflated 8-bit RGB; pixel-identical, not byte-identical)
     SequenceOutputs                 <- the files of the sequence tool, semantic_depth_cityscapes_sequence.py:303-361 (``result_sequence_imgs/<name>.png``,
                                        ``result_sequence_ply/<name>_rw.ply``), written from the batched driver (distributed.run_sequence_files)
@@ -489,6 +490,75 @@ def focal_sweep(process, input_frames: dict, frame_depther, focal_lengths=(380, 
         fh.write("Best f fence2fence:  {}\n".format(best["f2f"][1]))
         fh.write("Best f overall:      {}\n".format(best["overall"][1]))
     return dict(best_f_rw=best["rw"][1], best_f_f2f=best["f2f"][1], best_f_overall=best["overall"][1], per_f=per_f)
+
+
+def sweep_cameras(frame_depther, focal_lengths, multipliers) -> list:
+    """cams[t][b] = ``frame_depther.camera(multipliers[b])`` with f = focal_lengths[t]; ``frame_depther.f`` is left alone"""
+    return [[dataclasses.replace(frame_depther.camera(m), f=f) for m in multipliers] for f in focal_lengths]
+
+
+def sweep_distances_batched(frames: dict, input_frames: dict, frame_segmenter, frame_depther, focal_lengths, depth: float = 10.0,
+                            approach: str = "both", disp_multiplier=None, params=None, fence_params=None) -> dict:
+    """(focal length, frame name) -> (dist_rw, dist_f2f) as FrameProcessor.process_frame reports them (None where found == 0 / ok == 0),
+    with ONE pass of each network per frame: each batch of frames (at most the engine's max_batch; 1 is legal and simply gets no trial
+    batching) goes through Engine.camera_sweep, the trial focal lengths as a batch axis of the tail.  ``frames``: name -> u8 BGR frame
+    of any size (cubic-resized to the network shape like process_frame does); a frame's disparity multiplier is its original width,
+    or ``disp_multiplier``."""
+    import torch
+
+    from .engine import Engine, FenceParams, RoadWidthParams
+    focal_lengths = list(focal_lengths)
+    e = frame_depther.engine
+    if getattr(frame_segmenter, "_engine", e) is None and (e.H, e.W) == tuple(frame_segmenter.input_shape):
+        frame_segmenter._engine = e                           # built independently of the DepthFrame: join its Engine (as FrameProcessor)
+    if frame_segmenter.engine is not e:
+        raise ValueError("the batched sweep needs the segmenter and the depther on one Engine")
+    params = params or RoadWidthParams(depth=depth)
+    fence_params = fence_params or FenceParams(depth=depth)
+    names = sorted(input_frames)
+    dists = {}
+    for b0 in range(0, len(names), e.max_batch):
+        batch = names[b0:b0 + e.max_batch]
+        fr, mults = [], []
+        for name in batch:
+            frame = np.ascontiguousarray(frames[name], dtype=np.uint8)
+            mults.append(disp_multiplier if disp_multiplier is not None else frame.shape[1])
+            t = torch.from_numpy(frame)[None].to(e.device)
+            fr.append(t if tuple(t.shape[1:3]) == (e.H, e.W) else e.resize_cubic(t))
+        out = e.camera_sweep(torch.cat(fr).contiguous(), sweep_cameras(frame_depther, focal_lengths, mults), params, approach=approach,
+                             fence_params=fence_params)
+        recs = Engine.records(out["records"])                 # the one read-back of the batch: every trial's record
+        f2fs = Engine.f2f_records(out["f2f"]) if out.get("f2f") is not None else None
+        e.check_range()
+        for t, f in enumerate(focal_lengths):
+            for b, name in enumerate(batch):
+                rec = recs[t * len(batch) + b]
+                f2 = f2fs[t * len(batch) + b] if f2fs is not None else None
+                dists[(f, name)] = (float(rec["width"]) if rec["found"] else None, float(f2["dist"]) if (f2 is not None and f2["ok"]) else None)
+    return dists
+
+
+def focal_sweep_batched(frames: dict, input_frames: dict, frame_segmenter, frame_depther, focal_lengths=(380, 580),
+                        results_directory: str = "results", depth: float = 10.0, approach: str = "both", disp_multiplier=None, params=None,
+                        fence_params=None):
+    """focal_sweep over FrameProcessor.process_frame behind one network pass per frame (sweep_distances_batched): the same
+    ``<results>/<f>/data.txt``, ``best_focal_lengths.txt`` and returned dict -- focal_sweep itself writes them, fed from the table --
+    without touching ``frame_depther.f``.  A (focal length, frame) without a distance (the reference and focal_sweep die there on
+    ``abs(real - None)``) raises ValueError before any file is written."""
+    focal_lengths = list(focal_lengths)
+    dists = sweep_distances_batched(frames, input_frames, frame_segmenter, frame_depther, focal_lengths, depth, approach, disp_multiplier,
+                                    params, fence_params)
+    for f in focal_lengths:
+        for name in sorted(input_frames):
+            for what, v in zip(("road width", "fence-to-fence distance"), dists[(f, name)]):
+                if v is None:
+                    raise ValueError(f"focal_sweep_batched: no {what} for focal length {f}, frame {name!r}")
+
+    class Trial:                                              # stands in for the operator whose f focal_sweep reassigns per trial
+        f = None
+
+    trial = Trial()
+    return focal_sweep(lambda name: dists[(trial.f, name)], input_frames, trial, focal_lengths, results_directory)
 
 
 # ------------------------------------------------------------------------------------------------ the sequence tool's files
