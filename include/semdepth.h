@@ -650,6 +650,50 @@ sd_status sd_fence_to_fence(sd_handle* h, const float* fence_xyz, const uint8_t*
                             const sd_rw_result* road, const sd_f2f_params* params_host, sd_f2f_result* results,
                             float* left_xyz, uint8_t* left_rgb, float* right_xyz, uint8_t* right_rgb, void* stream);
 
+/* ---------------------------------------------------------------- depth profile
+ * The depth (sd_rw_params.depth, sd_f2f_params.depth) enters the road chain only in its last step and the fence chain only in the two
+ * plane intersections.  These calls take the ONE denoised cloud (sd_road_width's final_xyz / n_final) and the ONE set of planes per
+ * frame and give the road record and the fence-to-fence distance at D depths, without running the chains again.
+ *
+ * sd_road_width_profile: results[b][i] holds, bit for bit, the width, x_left, x_right, left_pt, right_pt and found that sd_road_width's
+ * last step writes for frame b's cloud with params.depth = depths[i] (the same window and depth_offset); n_window is the number of rows
+ * inside that window.  depths_host may come in any order and may repeat.  Two launches on `stream`, no global atomics and no
+ * synchronisation; every byte of every record is written, and every workspace byte that is read is written by the same call
+ * (sd_rw_profile_workspace bytes; 0 = bad arguments).  The handle need not be bound and its max_batch / cap do not matter.
+ * SD_ERR_INVALID, nothing launched: a null pointer; B < 1 or B > 65535; cap < 1; D outside 1..SD_PROFILE_MAX_DEPTHS; a non-finite depth,
+ * window or depth_offset; window <= 0; workspace_bytes below sd_rw_profile_workspace; a workspace that is not 16-byte aligned, float /
+ * counter arrays that are not 4-byte or results that are not 8-byte aligned.
+ * sd_road_width_profile_host: the same records for one HOST cloud of n >= 0 rows (xyz_host may be NULL when n == 0).
+ *
+ * sd_f2f_profile: results[b][i] holds the dist, left_pt, right_pt and ok that sd_fence_to_fence gives frame b with params.depth =
+ * depths[i] (z = -depths[i]; no depth_offset there), from road[b].plane and f2f[b].plane_left / plane_right / counts[5], counts[6].
+ * A NaN in these records is the quiet NaN 0x7ff8000000000000 whatever the processor's own 0 / 0 looks like.  One launch, every byte
+ * written.  SD_ERR_INVALID: a null pointer, B < 1 or B > 65535, D outside 1..SD_PROFILE_MAX_DEPTHS, a non-finite depth, records that are
+ * not 8-byte aligned.  sd_f2f_profile_host: the same records for ONE frame's two HOST records. */
+#define SD_PROFILE_MAX_DEPTHS 256
+typedef struct {
+    double width;                      /* as sd_rw_result */
+    float x_left, x_right;
+    float left_pt[3], right_pt[3];
+    int32_t found;
+    int32_t n_window;                  /* rows inside the window of this depth */
+} sd_rw_depth_result;                  /* 48 bytes */
+typedef struct {
+    double dist;                       /* as sd_f2f_result */
+    double left_pt[3], right_pt[3];
+    int32_t ok, reserved;              /* reserved = 0 */
+} sd_f2f_depth_result;                 /* 64 bytes */
+size_t sd_rw_profile_workspace(int B, int cap, int D);
+sd_status sd_road_width_profile(sd_handle* h, const float* xyz_dev /* [B,cap,3] */, const int32_t* n_dev /* [B] */, int B, int cap,
+                                const double* depths_host, int D, double window, double depth_offset,
+                                sd_rw_depth_result* results_dev /* [B][D] */, void* workspace_dev, size_t workspace_bytes, void* stream);
+sd_status sd_road_width_profile_host(const float* xyz_host, int n, const double* depths, int D, double window, double depth_offset,
+                                     sd_rw_depth_result* results_host /* [D] */);
+sd_status sd_f2f_profile(sd_handle* h, const sd_rw_result* road_dev, const sd_f2f_result* f2f_dev, int B, const double* depths_host, int D,
+                         sd_f2f_depth_result* results_dev /* [B][D] */, void* stream);
+sd_status sd_f2f_profile_host(const sd_rw_result* road, const sd_f2f_result* f2f, const double* depths, int D,
+                              sd_f2f_depth_result* results_host /* [D] */);
+
 /* ---------------------------------------------------------------- pcl.py, function by function
  * (semantic_depth_lib/pcl.py; one cloud per call: xyz f32 [n,3], rgb u8 [n,3] nullable, n on the host).
  * Outputs keep the input row order.  *n_out is a DEVICE int32. */

@@ -18,6 +18,7 @@ SD_NET_FCN8S, SD_NET_MONODEPTH = 0, 1
 SD_PLY_ROW_CAP, SD_PLY_HEADER_CAP, SD_PLY_LINE_ROWS = 69, 209, 1001
 SD_TEXT_MAX_BYTES, SD_TEXT_MAX_SEGS, SD_TEXT_MAX_ITEMS, SD_TEXT_MAX_SCALE_Q8, SD_TEXT_MAX_THICKNESS, SD_TEXT_MAX_ORG = 64, 32, 4, 4096, 32, 32768
 SD_RENDER_MAX_EXTENT, SD_RENDER_MAX_POINT = 16384, 16
+SD_PROFILE_MAX_DEPTHS = 256
 SD_PREC_F32, SD_PREC_BF16X2, SD_PREC_MIXED, SD_PREC_PLAN, SD_PREC_BF16X3, SD_PREC_F16X2 = 0, 1, 2, 3, 4, 5
 
 
@@ -57,6 +58,15 @@ class sd_f2f_params(C.Structure):
 class sd_f2f_result(C.Structure):
     _fields_ = [("dist", C.c_double), ("left_pt", C.c_double * 3), ("right_pt", C.c_double * 3), ("plane_left", C.c_double * 4),
                 ("plane_right", C.c_double * 4), ("counts", C.c_int32 * 7), ("ok", C.c_int32)]
+
+
+class sd_rw_depth_result(C.Structure):
+    _fields_ = [("width", C.c_double), ("x_left", C.c_float), ("x_right", C.c_float), ("left_pt", C.c_float * 3),
+                ("right_pt", C.c_float * 3), ("found", C.c_int32), ("n_window", C.c_int32)]
+
+
+class sd_f2f_depth_result(C.Structure):
+    _fields_ = [("dist", C.c_double), ("left_pt", C.c_double * 3), ("right_pt", C.c_double * 3), ("ok", C.c_int32), ("reserved", C.c_int32)]
 
 
 class sd_profile_bucket(C.Structure):
@@ -163,6 +173,11 @@ SIGNATURES = {
                                             C.c_size_t, _P]),
     "sd_road_width": (C.c_int, [_H, _P, _P, _P, C.c_int, C.c_int, C.POINTER(sd_rw_params), _P, _P, _P, _P, _P]),
     "sd_fence_to_fence": (C.c_int, [_H, _P, _P, _P, C.c_int, C.c_int, _P, C.POINTER(sd_f2f_params), _P, _P, _P, _P, _P, _P]),
+    "sd_rw_profile_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "sd_road_width_profile": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_double, C.c_double, _P, _P, C.c_size_t, _P]),
+    "sd_road_width_profile_host": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_double, _P]),
+    "sd_f2f_profile": (C.c_int, [_H, _P, _P, C.c_int, _P, C.c_int, _P, _P]),
+    "sd_f2f_profile_host": (C.c_int, [_P, _P, _P, C.c_int, _P]),
     "sd_pcl_extract_pcls": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sd_pcl_remove_from_to": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P]),
     "sd_pcl_remove_noise_by_mad": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P, _P]),

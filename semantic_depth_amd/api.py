@@ -233,8 +233,10 @@ class FrameProcessor:
 
     def __init__(self, frame_segmenter: SegmentFrame, frame_depther: DepthFrame, depth: float = 10.0,
                  disp_multiplier: float | None = None, params: RoadWidthParams | None = None, approach: str = "rw",
-                 fence_params: FenceParams | None = None, on_range: str | None = None):
-        """``on_range``: None = whatever the operators' engines do; 'raise' / 'recompute' = what they must do (a mismatch is an error: the
+                 fence_params: FenceParams | None = None, on_range: str | None = None, depths=None):
+        """``depths`` (None = off): also the depth profile of every frame -- the road record and, with approach 'both', the fence-to-fence
+        distance at each of these depths, from the one denoised cloud and the one set of planes (Engine.road_width_profile / f2f_profile).
+        ``on_range``: None = whatever the operators' engines do; 'raise' / 'recompute' = what they must do (a mismatch is an error: the
         shared engines are built by SegmentFrame / DepthFrame(on_range=))"""
         self.frame_segmenter, self.frame_depther = frame_segmenter, frame_depther
         if on_range is not None:
@@ -245,6 +247,7 @@ class FrameProcessor:
                     raise ValueError(f"FrameProcessor(on_range={on_range!r}) over an operator whose engine does {want!r}: "
                                      "build SegmentFrame / DepthFrame with the same on_range")
         self.depth = depth
+        self.depths = None if depths is None else [float(v) for v in np.asarray(depths, dtype=np.float64).reshape(-1)]
         self.approach = approach
         self.disp_multiplier = disp_multiplier
         self.params = params or RoadWidthParams(depth=depth)
@@ -265,20 +268,29 @@ class FrameProcessor:
             fr = e.resize_cubic(fr)
         cams = [d.camera(mult)]
         if es is e:
-            out = e.process_batch(fr, cams, self.params, approach=self.approach, fence_params=self.fence_params, want_final=want_clouds)
+            if self.depths is None:
+                out = e.process_batch(fr, cams, self.params, approach=self.approach, fence_params=self.fence_params, want_final=want_clouds)
+            else:
+                out = e.process_batch(fr, cams, self.params, approach=self.approach, fence_params=self.fence_params, want_final=want_clouds,
+                                      depths=self.depths)
         else:
             # two Engines (different geometry registries): FCN-8s on the segmenter's, everything else on the depther's
             seg = es.fcn8s_forward(fr)
             disp_pp = e.monodepth_forward(fr)
             fz = e.fuse_backproject(disp_pp, seg["road"], seg["fence"], fr, cams)
-            rw = e.road_width(fz["road_xyz"], fz["n_road"], self.params, want_final=want_clouds, road_rgb=fz["road_rgb"])
-            out = dict(seg=seg, disp_pp=disp_pp, fuse=fz, records=rw[0] if want_clouds else rw, f2f=None)
+            keep = want_clouds or self.depths is not None
+            rw = e.road_width(fz["road_xyz"], fz["n_road"], self.params, want_final=keep, road_rgb=fz["road_rgb"])
+            out = dict(seg=seg, disp_pp=disp_pp, fuse=fz, records=rw[0] if keep else rw, f2f=None)
             if want_clouds:
                 out["road_final"] = dict(xyz=rw[1], rgb=rw[2], n=rw[3])
+            if self.depths is not None:
+                out["profile"] = e.road_width_profile(rw[1], rw[3], self.depths, self.params)
             if self.approach == "both":
                 f2 = e.fence_to_fence(fz["fence_xyz"], fz["n_fence"], out["records"], self.fence_params, fence_rgb=fz["fence_rgb"],
                                       want_clouds=want_clouds)
                 out["f2f"], out["fence_final"] = f2 if want_clouds else (f2, None)
+                if self.depths is not None:
+                    out["f2f_profile"] = e.f2f_profile(out["records"], out["f2f"], self.depths)
         rec = Engine.records(out["records"])[0]
         e.check_range()
         if es is not e:
@@ -293,6 +305,17 @@ class FrameProcessor:
             f2 = Engine.f2f_records(out["f2f"])[0]
             res["f2f_record"] = f2
             res["dist_f2f"] = float(f2["dist"]) if f2["ok"] else None      # semantic_depth.py:327
+        if self.depths is not None:
+            rows = Engine.profile_records(out["profile"])[0]
+            f2p = Engine.f2f_profile_records(out["f2f_profile"])[0] if out.get("f2f_profile") is not None else None
+            res["profile"] = []
+            for i, dv in enumerate(self.depths):
+                r = rows[i]
+                row = dict(depth=dv, found=int(r["found"]), width=float(r["width"]), x_left=float(r["x_left"]), x_right=float(r["x_right"]),
+                           n_window=int(r["n_window"]))
+                if f2p is not None:
+                    row["dist_f2f"] = float(f2p[i]["dist"]) if f2p[i]["ok"] else None
+                res["profile"].append(row)
         if want_clouds:
             n_f = int(out["fuse"]["n_fence"][0].item()) if out["fuse"].get("n_fence") is not None else 0
             if n_f and out["fuse"].get("fence_xyz") is not None:   # the gathered fence cloud (semantic_depth.py:186-187): the save path

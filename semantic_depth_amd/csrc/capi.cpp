@@ -19,6 +19,7 @@
 #include "ply_gpu.hpp"
 #include "text_gpu.hpp"
 #include "render_gpu.hpp"
+#include "rw_profile_gpu.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -50,6 +51,7 @@ struct sd_handle {
     size_t o_splitk = 0;            // workspace: the partial sums of the largest split layer (0 bytes without the switch)
     std::vector<CamDev> cams_stage;
     std::vector<CamDev> sweep_stage;     // sd_fuse_backproject_sweep: the [T][B] records of the last call (source of its upload)
+    std::vector<sdrwp::Window> rwp_stage;    // sd_road_width_profile: the sorted windows of the last call (source of its upload)
     std::map<std::pair<int, int>, std::vector<float>> bias_host;   // (net, slot) -> host copy, for bias slots that are summed
     std::map<std::pair<int, int>, std::vector<float>> w_host;      // (net, slot) -> f32 tensor of the SD_PREC_F16X2 slots that share a weight scale (sd_load_weight)
     std::string err;
@@ -1156,6 +1158,47 @@ sd_status sd_fence_to_fence(sd_handle* h, const float* fence_xyz, const uint8_t*
     for (int j = 0; j < 7; ++j)
         HIPCHK(h, hipMemcpyAsync(packed + (size_t)j * B, C(j), (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, launch_f2f(p_road, p_left, p_right, B, prm->depth, packed, reinterpret_cast<F2fResultDev*>(results), s));
+    return SD_OK;
+}
+
+sd_status sd_road_width_profile(sd_handle* h, const float* xyz_dev, const int32_t* n_dev, int B, int cap, const double* depths_host, int D,
+                                double window, double depth_offset, sd_rw_depth_result* results_dev, void* workspace_dev, size_t workspace_bytes,
+                                void* stream) {
+    if (!h || !xyz_dev || !n_dev || !depths_host || !results_dev || !workspace_dev)
+        return fail(h, SD_ERR_INVALID, "sd_road_width_profile: null pointer");
+    if (B < 1 || B > 65535 || cap < 1 || D < 1 || D > SD_PROFILE_MAX_DEPTHS)
+        return fail(h, SD_ERR_INVALID, "sd_road_width_profile: B in 1..65535, cap >= 1 and D in 1..SD_PROFILE_MAX_DEPTHS");
+    if (!std::isfinite(window) || !std::isfinite(depth_offset) || !(window > 0))
+        return fail(h, SD_ERR_INVALID, "sd_road_width_profile: window must be finite and > 0, depth_offset finite");
+    for (int i = 0; i < D; ++i)
+        if (!std::isfinite(depths_host[i])) return fail(h, SD_ERR_INVALID, "sd_road_width_profile: a depth is not finite");
+    // every index the kernels form follows from B, cap, D and this capacity: nothing is launched otherwise
+    if (workspace_bytes < sdrwp::workspace_bytes(B, cap, D))
+        return fail(h, SD_ERR_INVALID, "sd_road_width_profile: workspace smaller than sd_rw_profile_workspace reports");
+    if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(xyz_dev) & 3) || (reinterpret_cast<uintptr_t>(n_dev) & 3) ||
+        (reinterpret_cast<uintptr_t>(results_dev) & 7))
+        return fail(h, SD_ERR_INVALID, "sd_road_width_profile: workspace_dev must be 16-byte, results_dev 8-byte, the float and counter arrays 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    h->rwp_stage.resize((size_t)D);
+    sdrwp::sorted_windows(depths_host, D, window, depth_offset, h->rwp_stage.data());
+    HIPCHK(h, hipMemcpyAsync(workspace_dev, h->rwp_stage.data(), sizeof(sdrwp::Window) * (size_t)D, hipMemcpyHostToDevice, s));
+    HIPCHK(h, launch_rw_profile(xyz_dev, n_dev, B, cap, D, workspace_dev, results_dev, s));
+    return SD_OK;
+}
+
+sd_status sd_f2f_profile(sd_handle* h, const sd_rw_result* road_dev, const sd_f2f_result* f2f_dev, int B, const double* depths_host, int D,
+                         sd_f2f_depth_result* results_dev, void* stream) {
+    if (!h || !road_dev || !f2f_dev || !depths_host || !results_dev) return fail(h, SD_ERR_INVALID, "sd_f2f_profile: null pointer");
+    if (B < 1 || B > 65535 || D < 1 || D > SD_PROFILE_MAX_DEPTHS)
+        return fail(h, SD_ERR_INVALID, "sd_f2f_profile: B in 1..65535 and D in 1..SD_PROFILE_MAX_DEPTHS");
+    if ((reinterpret_cast<uintptr_t>(road_dev) & 7) || (reinterpret_cast<uintptr_t>(f2f_dev) & 7) || (reinterpret_cast<uintptr_t>(results_dev) & 7))
+        return fail(h, SD_ERR_INVALID, "sd_f2f_profile: the record arrays must be 8-byte aligned");
+    F2fDepths depths{};
+    for (int i = 0; i < D; ++i) {
+        if (!std::isfinite(depths_host[i])) return fail(h, SD_ERR_INVALID, "sd_f2f_profile: a depth is not finite");
+        depths.d[i] = depths_host[i];
+    }
+    HIPCHK(h, launch_f2f_profile(road_dev, f2f_dev, B, depths, D, results_dev, (hipStream_t)stream));
     return SD_OK;
 }
 

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include "kernels.hpp"
+#include "rw_profile.hpp"
 
 namespace sd {
 
@@ -790,26 +791,15 @@ hipError_t launch_extract_pcls(CloudView in, CloudOut outl, CloudOut outr, int B
 }
 
 // pcl.planes_intersection_at_certain_depth (pcl.py:212-237) for the two fence planes against the road plane, and the
-// fence-to-fence distance (semantic_depth.py:321-328).  Cramer's rule in float64 (the reference inverts the 2x2 with LAPACK).
+// fence-to-fence distance (semantic_depth.py:321-328): sdrwp::fence_solve, shared with the depth profile.
 __global__ void f2f_kernel(const double* road_plane, const double* left_plane, const double* right_plane, int B, double depth,
                            const int32_t* cnt, F2fResultDev* out) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     F2fResultDev r;
-    const double z = -depth;
-    const double* rp = road_plane + (size_t)b * 4;
     const double* pl[2] = {left_plane + (size_t)b * 4, right_plane + (size_t)b * 4};
     double pt[2][3];
-    for (int s = 0; s < 2; ++s) {
-        const double a = rp[0], bb = rp[1], c = pl[s][0], d = pl[s][1];
-        const double e = -(rp[2] * z + rp[3]), f = -(pl[s][2] * z + pl[s][3]);
-        const double det = a * d - bb * c;
-        pt[s][0] = (e * d - bb * f) / det;
-        pt[s][1] = (a * f - e * c) / det;
-        pt[s][2] = z;
-    }
-    const double dx = pt[0][0] - pt[1][0], dy = pt[0][1] - pt[1][1], dz = pt[0][2] - pt[1][2];
-    r.dist = sqrt(dx * dx + dy * dy + dz * dz);
+    r.dist = sdrwp::fence_solve(road_plane + (size_t)b * 4, pl[0], pl[1], -depth, pt);      // (one statement of the solve: rw_profile.hpp)
     for (int j = 0; j < 3; ++j) { r.left_pt[j] = pt[0][j]; r.right_pt[j] = pt[1][j]; }
     for (int j = 0; j < 4; ++j) { r.plane_left[j] = pl[0][j]; r.plane_right[j] = pl[1][j]; }
     for (int j = 0; j < 7; ++j) r.counts[j] = cnt[(size_t)j * B + b];

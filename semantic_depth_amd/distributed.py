@@ -150,7 +150,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
 
 
 def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outputs=None, on_range: str | None = None, png: str | None = None,
-                     ply: str | None = None, text: str | None = None, render=None, video=None):
+                     ply: str | None = None, text: str | None = None, render=None, video=None, depths=None):
     """``step`` for run_sequence on a real Engine: host or device u8 frames of any size -> (cubic resize to the network shape on
     the GPU, semantic_depth_cityscapes_sequence.py:123-130) -> Engine.process_batch -> record buffer.
     ``camera_of(global_frame_index) -> engine.Camera`` (the sequence tool: cx = 1048.64/4·s, cy = 519.277/4·s, disp_mult = 3800).
@@ -174,7 +174,11 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     (png="device": Engine.encode_png on the renders).
     video=Video: the composed images -- composed for this alone when ``outputs.images`` is off -- also become the frames of the result
     video; on its "device" route Engine.encode_jpeg makes every frame's JPEG file behind Engine.draw_result_text, with a stream stride of
-    half the raw image (a frame that needs more is flagged and encoded on the host from its raw copy)."""
+    half the raw image (a frame that needs more is flagged and encoded on the host from its raw copy).
+    ``depths`` (None = what ``outputs`` was built with, SequenceOutputs(profile=); else it becomes the outputs' profile, and must agree with
+    one already chosen): process_batch(depths=) adds every frame's depth profile -- two launches behind the road chain, one more with
+    approach 'both' -- and the record tensors travel to ``outputs.submit`` with the batch's other small records.  Without ``outputs`` the
+    step returns the records only and ``depths`` asks for nothing."""
     from .engine import RoadWidthParams
     from .recompute import check_mode
 
@@ -183,6 +187,12 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     prm = params or RoadWidthParams()
     if outputs is not None:
         outputs.configure(png, ply, text, render, video)
+        if depths is not None:
+            want = [float(d) for d in np.asarray(depths, dtype=np.float64).reshape(-1)]
+            if outputs.profile is None:
+                outputs.set_profile(want)
+            elif list(outputs.profile) != want:
+                raise ValueError("make_engine_step(depths=) disagrees with SequenceOutputs(profile=)")
     recomputed: list[int] = []
 
     def note(lo):
@@ -203,11 +213,15 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
             note(lo)
             return rec
         camera, vid, device_png = outputs.render, outputs.video, outputs.png == "device"
-        out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.ply or camera is not None)
+        if outputs.profile is None:
+            out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.ply or camera is not None)
+        else:
+            out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.ply or camera is not None, depths=outputs.profile)
+            more_profile = dict(profile=out["profile"], f2f_profile=out.get("f2f_profile"))
         note(lo)
         rec = out["records"]
         images = None
-        more = {}
+        more = {} if outputs.profile is None else more_profile
         if outputs.ply and outputs.ply_route == "device":           # the text of the PLY files
             more["ply_text"] = engine.format_rw_ply(out["road_final"], rec)
         if camera is not None:                                     # the rendered clouds, behind the road chain

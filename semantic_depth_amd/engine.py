@@ -23,6 +23,12 @@ assert RW_DTYPE.itemsize == C.sizeof(L.sd_rw_result)
 F2F_DTYPE = np.dtype([("dist", "<f8"), ("left_pt", "<f8", 3), ("right_pt", "<f8", 3), ("plane_left", "<f8", 4), ("plane_right", "<f8", 4),
                       ("counts", "<i4", 7), ("ok", "<i4")])
 assert F2F_DTYPE.itemsize == C.sizeof(L.sd_f2f_result)
+# the depth profile's records (sd_rw_depth_result, sd_f2f_depth_result): one per (frame, depth)
+RWP_DTYPE = np.dtype([("width", "<f8"), ("x_left", "<f4"), ("x_right", "<f4"), ("left_pt", "<f4", 3), ("right_pt", "<f4", 3),
+                      ("found", "<i4"), ("n_window", "<i4")])
+assert RWP_DTYPE.itemsize == C.sizeof(L.sd_rw_depth_result) == 48
+F2FP_DTYPE = np.dtype([("dist", "<f8"), ("left_pt", "<f8", 3), ("right_pt", "<f8", 3), ("ok", "<i4"), ("reserved", "<i4")])
+assert F2FP_DTYPE.itemsize == C.sizeof(L.sd_f2f_depth_result) == 64
 
 
 @dataclass
@@ -174,6 +180,7 @@ class Engine:
         self._companion = None
         self._warned = False
         self.last_recomputed: list[int] = []
+        self._profile_ws: dict = {}                               # road_width_profile: (B, cap, D) -> workspace tensor
 
     def close(self):
         if getattr(self, "_companion", None) is not None:
@@ -678,6 +685,65 @@ class Engine:
         return (res, cl) if want_clouds else res
 
     @staticmethod
+    def _depth_array(depths):
+        d = np.ascontiguousarray(np.asarray(depths, dtype=np.float64).reshape(-1))
+        if not 1 <= d.size <= L.SD_PROFILE_MAX_DEPTHS:
+            raise ValueError(f"a depth profile takes 1..{L.SD_PROFILE_MAX_DEPTHS} depths, got {d.size}")
+        return d
+
+    def road_width_profile(self, xyz: torch.Tensor, n: torch.Tensor, depths, params: RoadWidthParams = RoadWidthParams(),
+                           out: torch.Tensor | None = None) -> torch.Tensor:
+        """the road record at D depths from ONE cloud per frame (sd_road_width_profile): ``xyz`` f32 [B,cap,3] and ``n`` i32 [B] are any
+        device cloud, normally road_width(want_final=True)'s denoised one; ``depths`` in any order, repeats allowed.  Returns a device u8
+        [B, D, 48] buffer of sd_rw_depth_result: entry [b, i] holds the width, x_left, x_right, end points and found that road_width gives
+        frame b with ``params.depth = depths[i]`` (window and depth_offset come from ``params``) plus n_window, the rows inside that
+        window.  Two launches on the current stream, no synchronisation; the workspace is cached per (B, cap, D)."""
+        assert xyz.dtype == torch.float32 and xyz.is_cuda and xyz.is_contiguous() and xyz.dim() == 3 and xyz.shape[2] == 3, xyz.shape
+        B, cap = int(xyz.shape[0]), int(xyz.shape[1])
+        assert n.dtype == torch.int32 and n.is_cuda and n.is_contiguous() and tuple(n.shape) == (B,)
+        d = self._depth_array(depths)
+        D = int(d.size)
+        need = int(self.lib.sd_rw_profile_workspace(B, cap, D))
+        if need == 0:
+            raise ValueError(f"sd_rw_profile_workspace refuses B={B}, cap={cap}, D={D}")
+        ws = self._profile_ws.get((B, cap, D))
+        if ws is None:
+            ws = self._profile_ws[(B, cap, D)] = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        if out is None:
+            out = torch.empty((B, D, RWP_DTYPE.itemsize), dtype=torch.uint8, device=self.device)     # (every byte of a record is written)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, D, RWP_DTYPE.itemsize), out.shape
+        prm = params.to_c()
+        st = self.lib.sd_road_width_profile(self.h, _ptr(xyz), _ptr(n), B, cap, d.ctypes.data_as(C.c_void_p), D, prm.window, prm.depth_offset,
+                                            _ptr(out), _ptr(ws), need, self._stream())
+        L.check(self.lib, self.h, st, "sd_road_width_profile")
+        return out
+
+    def f2f_profile(self, road_records: torch.Tensor, f2f_records: torch.Tensor, depths, out: torch.Tensor | None = None) -> torch.Tensor:
+        """the fence-to-fence distance at D depths from ONE set of planes per frame (sd_f2f_profile): ``road_records`` u8 [B,104]
+        (road_width) and ``f2f_records`` u8 [B,168] (fence_to_fence) device buffers -> device u8 [B, D, 64] of sd_f2f_depth_result:
+        entry [b, i] holds the dist, points and ok fence_to_fence gives frame b with ``FenceParams(depth=depths[i])``.  One launch."""
+        B = int(road_records.shape[0])
+        for t, sz in ((road_records, RW_DTYPE.itemsize), (f2f_records, F2F_DTYPE.itemsize)):
+            assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, sz), t.shape
+        d = self._depth_array(depths)
+        D = int(d.size)
+        if out is None:
+            out = torch.empty((B, D, F2FP_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, D, F2FP_DTYPE.itemsize), out.shape
+        st = self.lib.sd_f2f_profile(self.h, _ptr(road_records), _ptr(f2f_records), B, d.ctypes.data_as(C.c_void_p), D, _ptr(out), self._stream())
+        L.check(self.lib, self.h, st, "sd_f2f_profile")
+        return out
+
+    @staticmethod
+    def profile_records(res: torch.Tensor) -> np.ndarray:
+        """device [B, D, 48] profile buffer -> structured array [B, D] (synchronises)."""
+        return res.cpu().numpy().view(RWP_DTYPE).reshape(res.shape[0], res.shape[1])
+
+    @staticmethod
+    def f2f_profile_records(res: torch.Tensor) -> np.ndarray:
+        return res.cpu().numpy().view(F2FP_DTYPE).reshape(res.shape[0], res.shape[1])
+
+    @staticmethod
     def f2f_records(res: torch.Tensor) -> np.ndarray:
         return res.cpu().numpy().view(F2F_DTYPE).reshape(-1)
 
@@ -688,20 +754,24 @@ class Engine:
 
     # ------------------------------------------------------------------ whole path
     def process_batch(self, frames: torch.Tensor, cams, params: RoadWidthParams = RoadWidthParams(), approach: str = "rw",
-                      fence_params: FenceParams | None = None, colours: bool = True, want_final: bool = False):
+                      fence_params: FenceParams | None = None, colours: bool = True, want_final: bool = False, depths=None):
         """FrameProcessor.process_frame for B frames at once (semantic_depth.py:98-334; seq:117-298): seg + depth + fusion +
         road chain (+ the fence chain and fence-to-fence distance when ``approach == 'both'``, :273-334).  ``colours``: carry
         the RGB of every point through the filters like the reference does (they feed only the PLY outputs).
+        ``depths`` (None = off): also the depth profile of every frame, from the one denoised cloud and the one set of planes the chains
+        leave: ``profile`` u8 [B, D, 48] (road_width_profile) and, with approach 'both', ``f2f_profile`` u8 [B, D, 64] (f2f_profile).
         Returns device tensors: seg, disp_pp, fuse, records (sd_rw_result), f2f (sd_f2f_result or None) [, final clouds]."""
         if approach not in ("rw", "both"):
             raise ValueError("approach must be 'rw' or 'both' (semantic_depth.py:743-745)")
         cams = list(cams)
-        out = self._process_batch(frames, cams, params, approach, fence_params, colours, want_final)
+        if depths is not None:
+            depths = self._depth_array(depths)
+        out = self._process_batch(frames, cams, params, approach, fence_params, colours, want_final, depths)
         # ('recompute': ONE per-frame read behind both networks and the tail; the companion reruns the whole path on the flagged frames)
         return self._settle(frames, out, lambda e, f: e.process_batch(f, [cams[i] for i in self.last_recomputed], params, approach,
-                                                                      fence_params, colours, want_final))
+                                                                      fence_params, colours, want_final, depths))
 
-    def _process_batch(self, frames, cams, params, approach, fence_params, colours, want_final):
+    def _process_batch(self, frames, cams, params, approach, fence_params, colours, want_final, depths=None):
         seg = self._fcn8s(frames)
         if frames.shape[0] <= self.pass_frames:
             # the raw disparity pair stays in the activation arena: post-processing, back-projection and both gathers in ONE launch
@@ -712,10 +782,15 @@ class Engine:
             disp_pp = self._mono(frames, False, True)
             fz = self.fuse_backproject(disp_pp, seg["road"], seg["fence"], frames, cams, want_rgb=colours)
         out = dict(seg=seg, disp_pp=disp_pp, fuse=fz, f2f=None)
-        rw = self.road_width(fz["road_xyz"], fz["n_road"], params, want_final=want_final, road_rgb=fz["road_rgb"] if colours else None)
-        if want_final:
+        # (a depth profile reads the denoised cloud: the chain runs once and keeps it, whether or not the caller asked for it)
+        keep = want_final or depths is not None
+        rw = self.road_width(fz["road_xyz"], fz["n_road"], params, want_final=keep, road_rgb=fz["road_rgb"] if colours else None)
+        if keep:
             out["records"] = rw[0]
-            out["road_final"] = dict(xyz=rw[1], rgb=rw[2] if colours else None, n=rw[-1])
+            if want_final:
+                out["road_final"] = dict(xyz=rw[1], rgb=rw[2] if colours else None, n=rw[-1])
+            if depths is not None:
+                out["profile"] = self.road_width_profile(rw[1], rw[-1], depths, params)
         else:
             out["records"] = rw
         if approach == "both":
@@ -726,6 +801,8 @@ class Engine:
                 out["f2f"], out["fence_final"] = f2
             else:
                 out["f2f"] = f2
+            if depths is not None:
+                out["f2f_profile"] = self.f2f_profile(out["records"], out["f2f"], depths)
         return out
 
     # ------------------------------------------------------------------ camera sweep (the calibration mode, semantic_depth.py:843-944)

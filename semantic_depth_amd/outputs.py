@@ -65,6 +65,37 @@ def write_distances(output_name: str, dist_rw, dist_f2f) -> str:
     return path
 
 
+PROFILE_COLUMNS = ("depth", "found", "width", "x_left", "x_right", "n_window")
+
+
+def profile_text(depths, rows, dist_f2f=None) -> str:
+    """the text of a depth-profile file: ``# depth found width x_left x_right n_window`` (``dist_f2f`` behind it when given), then one row
+    per depth in the caller's order; numbers as numpy.savetxt(fmt='%1.4f') formats the calibration tables, found / n_window as integers,
+    a missing value as ``nan``.  ``rows[i]`` is indexable by those names (a record of Engine.profile_records or a dict)."""
+    if len(rows) != len(depths) or (dist_f2f is not None and len(dist_f2f) != len(depths)):
+        raise ValueError("a depth profile has one row per depth")
+    lines = ["# " + " ".join(PROFILE_COLUMNS + (("dist_f2f",) if dist_f2f is not None else ()))]
+    for i, d in enumerate(depths):
+        r = rows[i]
+        found = int(r["found"])
+        vals = [float(r[k]) if found else float("nan") for k in ("width", "x_left", "x_right")]
+        line = "%1.4f %d %1.4f %1.4f %1.4f %d" % (float(d), found, vals[0], vals[1], vals[2], int(r["n_window"]))
+        if dist_f2f is not None:
+            v = dist_f2f[i]
+            line += " %1.4f" % (float("nan") if v is None else float(v))
+        lines.append(line)
+    return "\n".join(lines) + "\n"
+
+
+def write_profile(path: str, depths, rw_rows, f2f_rows=None) -> str:
+    """one depth-profile text file (profile_text): ``rw_rows`` the D records of one frame (Engine.profile_records(...)[b]), ``f2f_rows``
+    (optional) its D fence records (Engine.f2f_profile_records(...)[b]): dist_f2f is their dist, ``nan`` where ok == 0."""
+    dist = None if f2f_rows is None else [float(r["dist"]) if int(r["ok"]) else None for r in f2f_rows]
+    with open(path, "w") as f:
+        f.write(profile_text(depths, rw_rows, dist))
+    return path
+
+
 # ------------------------------------------------------------------------------------------------ overlay
 def overlay_items(w: int, h: int, depth: float, is_city: bool, left_pt_rw, right_pt_rw, dist_rw, approach: str = "rw",
                   left_pt_f2f=None, right_pt_f2f=None, dist_f2f=None):
@@ -342,7 +373,7 @@ def resize_to_original(segmented_frame: np.ndarray, original_width: int, origina
 def save_frame_outputs(output_name: str, res: dict, depth: float, approach: str = "rw", segmented_frame: np.ndarray | None = None,
                        is_city: bool = False, times: dict | None = None, road_plane3D=None, road_colors_plane=None,
                        points3D_all=None, colors_all=None, original_size: tuple | None = None, params=None, fence_params=None,
-                       text: str = "json", render: RenderCamera | None = None):
+                       text: str = "json", render: RenderCamera | None = None, profile=None):
     """what FrameProcessor.process_frame writes when --save_data is set (semantic_depth.py:339-458), from the dict
     ``api.FrameProcessor.process_frame(..., want_clouds=True)`` returns.  Returns the list of files written.
     ``original_size`` = (original_height, original_width): the overlay is cubic-resized back to it before anything is drawn (:341);
@@ -350,7 +381,9 @@ def save_frame_outputs(output_name: str, res: dict, depth: float, approach: str 
     ``text``: "json" (default) leaves the banner of the annotated image empty; "draw" rasterises the items into it (draw_text).  The
     ``_overlay.json`` is written either way.
     ``render``: None (default) or a RenderCamera: also ``<output_name>_render.png``, the final road cloud and the road-width line of the
-    record behind that camera (render_rw, the host statement of the sequence tool's rendered clouds)."""
+    record behind that camera (render_rw, the host statement of the sequence tool's rendered clouds).
+    ``profile``: None (default) or the depth profile of the frame (``res["profile"]`` of FrameProcessor(depths=); True takes it from
+    ``res``): also ``<output_name>_profile.txt`` (profile_text)."""
     _check_text(text)
     _check_render(render)
     files = []
@@ -423,6 +456,12 @@ def save_frame_outputs(output_name: str, res: dict, depth: float, approach: str 
     if times is not None:
         files.append(write_times(output_name, times))
     files.append(write_distances(output_name, dist_rw, res.get("dist_f2f")))
+    if profile is not None and profile is not False:
+        rows = res["profile"] if profile is True else profile
+        dist = [r["dist_f2f"] for r in rows] if rows and "dist_f2f" in rows[0] else None
+        with open("{}_profile.txt".format(output_name), "w") as f:
+            f.write(profile_text([r["depth"] for r in rows], rows, dist))
+        files.append("{}_profile.txt".format(output_name))
     return files
 
 
@@ -563,6 +602,7 @@ def focal_sweep_batched(frames: dict, input_frames: dict, frame_segmenter, frame
 
 # ------------------------------------------------------------------------------------------------ the sequence tool's files
 SEQ_IMG_DIR, SEQ_PLY_DIR = "result_sequence_imgs", "result_sequence_ply"          # semantic_depth_cityscapes_sequence.py:671-680
+SEQ_PROFILE_DIR = "result_sequence_profile"                                       # the per-frame depth profiles (SequenceOutputs(profile=))
 SEQ_RENDER_DIR = "rendered_sequence"                                              # utils/render_ply.py's output folder
 
 
@@ -807,6 +847,8 @@ class _Batch:
     renders: object = None
     render_streams: object = None
     video_streams: object = None
+    profile: object = None
+    f2f_profile: object = None
 
 
 @dataclasses.dataclass
@@ -827,6 +869,8 @@ class _HostBatch:
     video_sizes: np.ndarray | None = None
     video_flags: np.ndarray | None = None
     video_raw: dict = dataclasses.field(default_factory=dict)      # frame -> raw image of a flagged video frame
+    profile: np.ndarray | None = None       # [n,D,48] depth-profile records
+    f2f_profile: np.ndarray | None = None   # [n,D,64]
 
 
 class _Stager:
@@ -928,6 +972,7 @@ class SequenceOutputs:
         <directory>/rendered_sequence/<name>_render.png       only with render=: the top view of the _rw.ply's rows (``render``)
         <directory>/result_imgs.avi                           only with video=: the result images as a Motion-JPEG AVI (``video``;
                                                               result_imgs_rank<r>.avi when world > 1, _part<k> when a file rolls over)
+        <directory>/result_sequence_profile/<name>.txt        only with profile=: the frame's depth profile (``profile``; profile_text)
         <directory>/manifest_rank<r>.json                     written last by close(): the files of this rank and 'ok' / 'range_error' / 'error'
 
     ``names``: output names of the WHOLE sorted frame list (sequence_names), indexed by global frame index.  submit() takes the device
@@ -958,13 +1003,17 @@ class SequenceOutputs:
     submit(video_streams=) the finished JPEG files of Engine.encode_jpeg; sizes and flags are copied first, then each file's exact bytes; a
     flagged frame (its file passed the stream stride) is encoded on the host from a raw copy of that frame and named under 'video_fallback'.
     route "host": the raw images travel and sd_jpeg_encode_bgr_host makes the same bytes on the writer threads; it needs png="host".
-    Works with images=False too (submit still gets the images then).  The manifest names the files under 'video'."""
+    Works with images=False too (submit still gets the images then).  The manifest names the files under 'video'.
+    ``profile``: None (default: nothing more is written, copied or launched, the manifest is what it was) or the list of depths of a depth
+    profile: the step of make_engine_step asks process_batch for it (``depths=``) and hands submit(profile=, f2f_profile=) the [n,D,48] /
+    [n,D,64] record tensors, which travel with the batch's other small records in the first phase of the staged transfer; the writer stores
+    ``result_sequence_profile/<name>.txt`` per frame.  The manifest names the depths under 'profile_depths' and the files under 'profile'."""
 
     png, ply_route, text, render, video, _k = "host", "host", "json", None, None, 0          # (what configure() starts from)
 
     def __init__(self, directory: str, names, depth: float = 10.0, images: bool = True, ply: bool | str = True, items: bool = True, level: int = 1,
                  threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, png: str = "host", text: str = "json",
-                 render: RenderCamera | None = None, video: Video | None = None):
+                 render: RenderCamera | None = None, video: Video | None = None, profile=None):
         import threading
         from concurrent.futures import ThreadPoolExecutor
 
@@ -980,6 +1029,9 @@ class SequenceOutputs:
         self.threads = threads if threads > 0 else default_decode_workers()
         self.img_dir, self.ply_dir = os.path.join(directory, SEQ_IMG_DIR), os.path.join(directory, SEQ_PLY_DIR)
         self.render_dir = os.path.join(directory, SEQ_RENDER_DIR)
+        self.profile_dir = os.path.join(directory, SEQ_PROFILE_DIR)
+        self.profile = None
+        self.set_profile(profile)
         for d, on in ((self.img_dir, self.images or self.items), (self.ply_dir, self.ply)):
             if on:
                 os.makedirs(d, exist_ok=True)
@@ -1037,6 +1089,16 @@ class SequenceOutputs:
         """the Video the result images also become (before the first batch)"""
         self.configure(video=video)
 
+    def set_profile(self, depths):
+        """the depths of the per-frame depth profile, or None for no profile (before the first batch)"""
+        if self._k:
+            raise RuntimeError("SequenceOutputs.set_profile after the first batch")
+        if depths is not None:
+            depths = [float(d) for d in np.asarray(depths, dtype=np.float64).reshape(-1)]
+            if not depths or not all(np.isfinite(depths)):
+                raise ValueError("profile must be a non-empty list of finite depths")
+        self.profile = depths
+
     def begin(self, rank: int, world: int, lo: int, hi: int):
         """the shard [lo, hi) this rank writes (run_sequence_files calls it before the first batch)"""
         self.rank, self.world, self.shard = int(rank), int(world), (int(lo), int(hi))
@@ -1047,7 +1109,7 @@ class SequenceOutputs:
         return self.png == "host" and (self.images or self.video is not None and self.video.route == "host")
 
     def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None, ply_text=None, renders=None, render_streams=None,
-               video_streams=None):
+               video_streams=None, profile=None, f2f_profile=None):
         """one batch: ``records`` u8 [n,104] (sd_rw_result), ``size`` = (h, w) of the original frames, ``images`` u8 [n,h,w,3] (the composed
         result images) or None, ``final`` = dict(xyz f32 [n,cap,3], rgb u8 [n,cap,3], n i32 [n]) (process_batch(want_final=True)'s
         road_final) or None, ``png_streams`` = (streams u8 [n,stride], sizes i64 [n]) of Engine.encode_png in place of ``images`` on the
@@ -1055,7 +1117,8 @@ class SequenceOutputs:
         (beside ``final``, which the flagged frames are written from), ``renders`` = u8 [n,height,width,3] of Engine.render_rw with render= (or
         ``render_streams`` = Engine.encode_png of them on the png="device" route), ``video_streams`` = (streams u8 [n,stride], sizes i64 [n], flags
         i32 [n]) of Engine.encode_jpeg with video= on its "device" route (beside ``images``, which a flagged frame is encoded from; its "host"
-        route needs only ``images``).  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
+        route needs only ``images``), ``profile`` = u8 [n,D,48] of Engine.road_width_profile (process_batch(depths=)'s ``profile``) with
+        profile=, ``f2f_profile`` = u8 [n,D,64] beside it (optional: the dist_f2f column).  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
         tensors of every step)."""
         if self.manifest is not None:
             raise RuntimeError("SequenceOutputs.submit after close")
@@ -1073,6 +1136,8 @@ class SequenceOutputs:
             raise ValueError("SequenceOutputs: video route 'device' needs the files of Engine.encode_jpeg (submit(video_streams=))")
         if self.video is not None and not device_video and images is None:
             raise ValueError("SequenceOutputs: video route 'host' needs the raw images (submit(images=))")
+        if self.profile is not None and (profile is None or tuple(profile.shape[:2]) != (n, len(self.profile))):
+            raise ValueError("SequenceOutputs: profile= needs the [n, D, 48] records of Engine.road_width_profile (submit(profile=))")
         while len(self._jobs) >= 2:                                    # at most two batches in flight
             self._files.extend(self._jobs.pop(0).result())
         slot = self._k & 1
@@ -1083,7 +1148,9 @@ class SequenceOutputs:
                        ply_text=ply_text if self.ply and self.ply_route == "device" else None,
                        renders=renders if self.render is not None and not device_png else None,
                        render_streams=render_streams if self.render is not None and device_png else None,
-                       video_streams=video_streams if device_video else None)
+                       video_streams=video_streams if device_video else None,
+                       profile=profile if self.profile is not None else None,
+                       f2f_profile=f2f_profile if self.profile is not None else None)
         self._k += 1
         self._jobs.append(self._batches.submit(self._write_batch, batch))
 
@@ -1127,6 +1194,9 @@ class SequenceOutputs:
         if self.video is not None:
             manifest["video"] = [os.path.relpath(p, self.directory) for p in video_files]
             manifest["video_fallback"] = named(self.video_fallback)
+        if self.profile is not None:
+            manifest["profile_depths"] = list(self.profile)
+            manifest["profile"] = [f for f in files if f.startswith(SEQ_PROFILE_DIR + os.sep)]
         with open(self.manifest, "w") as f:
             json.dump(manifest, f, indent=1)
         if err is not None:
@@ -1142,7 +1212,8 @@ class SequenceOutputs:
         st = self._stagers[b.slot]
         with st.behind(b.ev):
             host = _HostBatch(st.fixed("rec", b.records), images=st.fixed("img", b.images if self._images_travel else None),
-                              renders=st.fixed("render", b.renders))
+                              renders=st.fixed("render", b.renders), profile=st.fixed("profile", b.profile),
+                              f2f_profile=st.fixed("f2f_profile", b.f2f_profile))
             counts = None if b.final is None else st.fixed("n", b.final["n"])
             if b.png_streams is not None:
                 host.png_sizes = st.fixed("png_sizes", b.png_streams[1])
@@ -1220,6 +1291,15 @@ class SequenceOutputs:
                     json.dump(dict(banner=banner, items=items), f)
                 return path
 
+            def write_profile_file(i):
+                from .engine import F2FP_DTYPE, RWP_DTYPE
+                rows = np.ascontiguousarray(host.profile[i]).view(RWP_DTYPE).reshape(-1)
+                f2 = None if host.f2f_profile is None else np.ascontiguousarray(host.f2f_profile[i]).view(F2FP_DTYPE).reshape(-1)
+                return write_profile(os.path.join(self.profile_dir, "{}.txt".format(names[i])), self.profile, rows, f2)
+
+            if host.profile is not None:
+                os.makedirs(self.profile_dir, exist_ok=True)
+                futs.extend(self._writers.submit(write_profile_file, i) for i in range(n))
             if host.ply_flags is not None:
                 self.ply_fallback.extend(b.lo + i for i in range(n) if host.ply_flags[i] != 0)
             for i in range(n):
