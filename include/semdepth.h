@@ -14,6 +14,41 @@
  *     (PyTorch-ROCm in the Python host) allocates the weight and workspace arenas whose sizes
  *     sd_query_memory() reports and binds them with sd_bind_memory().
  *   - images are NHWC, row-major, channel order as the caller supplies it (the reference feeds BGR).
+ *
+ * Streams
+ *   Calls on one handle are enqueued from ONE host thread: the handle keeps host-side state (the camera stage, the look-back epoch
+ *   of the one-pass fusion, the frame count of the last monodepth pass) that follows the order of the calls, not of the streams.
+ *   Two streams of one handle may be in flight in exactly one arrangement, the one bench.py times: the NETWORK calls
+ *   (sd_fcn8s_forward, sd_monodepth_forward) of a batch on one stream while the TAIL calls of the batch before it run on another.
+ *   Tail calls are sd_postprocess_fuse_backproject / sd_fuse_backproject, sd_road_width, sd_fence_to_fence and the profile calls
+ *   (sd_road_width_profile, sd_f2f_profile); all tail calls of all batches go to one stream.  The caller's only obligation: the
+ *   fusion that reads the raw pair in the arena (sd_postprocess_fuse_backproject with disp_raw == NULL) is ordered AFTER the
+ *   sd_monodepth_forward that wrote the pair and BEFORE the next sd_monodepth_forward (an event each way).  Tensors the caller owns
+ *   (masks, frames, clouds, records) are the caller's to order.  Every other call (sd_resize_cubic_u8 aside, which touches only
+ *   o_rsz) belongs on the stream of its family, or behind a synchronisation.
+ *   The workspace regions (carve_workspace in capi.cpp) and the call families that touch them -- net = network calls, tail = tail calls:
+ *     o_fcn       FCN-8s activations                          net (sd_fcn8s_forward) reads + writes; sd_net_tensor reads
+ *     o_mono      monodepth activations                       net (sd_monodepth_forward) reads + writes; sd_net_tensor reads
+ *       raw pair  the plan's output tensor inside o_mono      net (sd_monodepth_forward) writes; tail (fusion from the arena) reads
+ *     o_fuse      block counts / offsets of the fusion        tail (fusion, the count-scan-write forms) reads + writes
+ *     o_fuse1     look-back words + tickets, one-pass fusion  tail (fusion) reads + writes; zeroed on its stream every 1023 launches
+ *     o_cams      device copy of the cameras                  tail (fusion) writes when the cameras changed, reads
+ *     o_bufA, o_bufB  point ping-pong of the chains           tail (sd_road_width, sd_fence_to_fence) reads + writes
+ *     o_rgbA, o_rgbB  colour ping-pong of the chains          tail (sd_road_width, sd_fence_to_fence) reads + writes
+ *     o_cnt       per-stage counts (slots 1-6 road, 8-14 fence)  tail (sd_road_width, sd_fence_to_fence) reads + writes
+ *     o_plane     road plane coefficients                     tail (sd_road_width) reads + writes
+ *     o_o3d       Open3D filter scratch / left fence cloud    tail (sd_road_width, sd_fence_to_fence) reads + writes
+ *     o_cmp       ordered-compaction scratch                  tail (sd_road_width) reads + writes; the sd_pcl_* / sd_o3d_* calls too
+ *     o_misc      +0     scalar slot                          the single-cloud sd_pcl_* / sd_o3d_* calls write + read; neither family
+ *                 +256   zero page (to +4096)                 net reads; NOTHING writes after sd_bind_memory
+ *                 +4096  f2f counts [7][B]                    tail (sd_fence_to_fence) reads + writes
+ *                 then   f2f planes [3][B][4]                 tail (sd_fence_to_fence) reads + writes
+ *                 then   clamp counters                       net reads + writes (atomics, the per-frame fold); the sd_saturation_* calls (net's stream)
+ *     o_rsz       tap tables of sd_resize_cubic_u8            sd_resize_cubic_u8 only
+ *     o_rsz_cmp   tap tables of sd_compose_result_frames      sd_compose_result_frames only
+ *     o_splitk    partial sums of the split layers            net reads + writes (sd_set_small_batch handles)
+ *   The profile calls use the caller's workspace and none of these regions.  The two families share the raw pair and nothing else;
+ *   tests/two_stream_cases.py holds this table per call and checks the benchmark's event choreography against it.
  */
 #ifndef SEMDEPTH_H
 #define SEMDEPTH_H

@@ -19,7 +19,7 @@ from oracle import fusion, nets, pipeline
 from semantic_depth_amd import _lib as L
 from semantic_depth_amd import weights as Wt
 from semantic_depth_amd.engine import Camera, Engine, FenceParams, RoadWidthParams
-from gpu_common import assert_close, dev, engine, err_report, relerr
+from gpu_common import _check_records_against_oracle, assert_close, dev, engine, err_report, relerr
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3          # north_star: "within 1e-3 relative fp32 tolerance"
@@ -189,37 +189,6 @@ def _camera_at_10m(disp_pp, mult=float(W)):
     """a camera that puts the median disparity at 10 m, so that the z-cut / depth window / Open3D filters all see points"""
     d0 = float(disp_pp.median().item()) * mult
     return Camera(W / 2 - 0.5, H / 2 - 0.5, 10.0 * d0, 1.0, mult)
-
-
-def _check_records_against_oracle(eng, frames_np, out, raw, cam, prm, colours=True):
-    """oracle.pipeline.frame_tail fed the GPU's own raw disparity pairs and masks must reproduce every field of the records"""
-    recs = Engine.records(out["records"])
-    cam_d = dict(cx=cam.cx, cy=cam.cy, f=cam.f, b=cam.b, disp_mult=cam.disp_mult)
-    found = 0
-    for b in range(frames_np.shape[0]):
-        road = out["seg"]["road"][b].cpu().numpy().astype(bool)
-        fence = out["seg"]["fence"][b].cpu().numpy().astype(bool)
-        ref = pipeline.frame_tail(raw[b].cpu().numpy(), road, fence, frames_np[b], cam_d, pipeline.RoadWidthParams(**{
-            k: getattr(prm, k) for k in ("depth", "z_cut", "mad_y", "mad_x", "plane_thr", "sor_k", "sor_ratio", "ror_n", "ror_r", "depth_offset", "use_o3d")}))
-        assert np.array_equal(out["disp_pp"][b].cpu().numpy(), ref["disp_pp"]), b
-        n = int(out["fuse"]["n_road"][b])
-        assert n == ref["road3d"].shape[0], b
-        assert np.array_equal(out["fuse"]["road_xyz"][b, :n].cpu().numpy(), ref["road3d"]), b
-        if colours:
-            assert np.array_equal(out["fuse"]["road_rgb"][b, :n].cpu().numpy(), ref["road_rgb"]), b
-        nf = int(out["fuse"]["n_fence"][b])
-        assert nf == ref["fence3d"].shape[0] and np.array_equal(out["fuse"]["fence_xyz"][b, :nf].cpu().numpy(), ref["fence3d"]), b
-        rw, r = ref["rw"], recs[b]
-        got = [int(r[k]) for k in ("n_road", "n_zcut", "n_mad_y", "n_mad_x", "n_plane", "n_sor", "n_ror")]
-        want = [rw[k] for k in ("n_in", "n_zcut", "n_mad_y", "n_mad_x", "n_plane", "n_sor", "n_ror")]
-        assert got == want, (b, got, want)
-        assert bool(r["found"]) == rw["found"], b
-        if rw["found"]:
-            found += 1
-            assert float(r["width"]) == rw["width"] and float(r["x_left"]) == rw["x_left"] and float(r["x_right"]) == rw["x_right"], b
-        if rw["plane"] is not None:
-            np.testing.assert_allclose(r["plane"], [rw["plane"][k] for k in ("Cx", "Cy", "Cz", "C")], rtol=1e-8, atol=1e-10)
-    return recs, found
 
 
 # (the benchmarked batch of 32 on the headline engine and on the plan leg; the other engines on 8: the CPU oracle tail costs ~1 s per frame,
