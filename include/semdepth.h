@@ -365,6 +365,48 @@ sd_status sd_jpeg_entropy_decode(sd_handle* h, const uint8_t* bytes_dev, size_t 
                                  const sd_jpeg_entropy_frame* frames_host, const sd_jpeg_interval* intervals_host, size_t interval_stride,
                                  const sd_jpeg_huff_table* tables_host, int B, int16_t* coef_dev, size_t coef_stride_bytes,
                                  int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* ---- PNG frames, split route: the host only inflates, the GPU reconstructs the scanlines ----
+ * What the reconstruction of one PNG frame needs besides its filtered scanlines.  channels is the bytes per pixel of the 8-bit colour type
+ * (0 -> 1, 2 -> 3, 3 -> 1, 4 -> 2, 6 -> 4); palette holds the PLTE entries as the file has them (R, G, B), zero past palette_entries;
+ * palette_entries is 0 for every colour type but 3. */
+typedef struct {
+    int32_t height, width;
+    int32_t channels, color_type;
+    int32_t palette_entries;
+    int32_t reserved;                 /* 0 */
+    uint8_t palette[256][3];
+} sd_png_frame_desc;
+/* HOST: the front half of sd_png_decode_bgr.  Walks the chunks and inflates the IDAT stream straight into rows_out_host: height rows of one
+ * filter byte plus width * channels filtered bytes, exactly height * (1 + width * channels) bytes.  Checks that the stream has exactly
+ * that length, that every row's filter byte is <= 4 and that a colour type 3 file has a PLTE chunk.  rows_out_host NULL: fills only
+ * *desc_out from the header (palette_entries and palette are final only after a full call).  capacity below the byte count:
+ * SD_ERR_INVALID before anything is written.  sd_png_unfilter_bgr on the rows (plus the palette lookup) gives the bytes of
+ * sd_png_decode_bgr.  Accepts and refuses exactly the files sd_png_decode_bgr does, with one exception: a palette index beyond the
+ * palette shows only after the reconstruction (sd_png_reconstruct_bgr flags it). */
+sd_status sd_png_inflate_rows(const uint8_t* file_host, size_t len, uint8_t* rows_out_host, size_t capacity, sd_png_frame_desc* desc_out);
+/* HOST: the batch reader beside sd_decode_files_bgr for the split PNG route: file i -> its filtered rows at rows_out_host + i * frame_stride
+ * (e.g. a pinned staging buffer) and descs_out[i], on `threads` native threads (<= 0: one per host CPU).  status_out (nullable, int[n]):
+ * SD_ERR_NOTFOUND unreadable file; SD_ERR_FORMAT a readable file without the PNG signature (nothing written for it: send it down the
+ * other routes); SD_ERR_INVALID a PNG that is refused, has another size or needs more than frame_stride.  Returns SD_OK when every
+ * status is SD_OK or SD_ERR_FORMAT, else SD_ERR_INVALID. */
+sd_status sd_inflate_files_png(const char* const* paths, int n, int height, int width, uint8_t* rows_out_host, size_t frame_stride,
+                               sd_png_frame_desc* descs_out, int threads, int* status_out);
+/* bytes of device workspace sd_png_reconstruct_bgr needs for B frames (the uploaded descriptors) */
+sd_status sd_png_reconstruct_workspace(int B, size_t* bytes_out);
+/* DEVICE: B frames' filtered rows (frame b at rows_dev + b * frame_stride, laid out as sd_png_inflate_rows writes them) -> u8
+ * [height,width,3] BGR at bgr_out_dev + b * out_stride, the bytes of sd_png_decode_bgr, and status_dev[b] (int32 [B], every word written
+ * by the call): 0, or non-zero for a colour type 3 frame with an index beyond its palette (such a pixel takes palette entry 0).  The
+ * frames share height x width (1..16384 each); channels, colour type and palette are per frame.  descs_host is a HOST array: checked, then
+ * uploaded into workspace_dev by ONE asynchronous copy on `stream` (a pinned array must stay unchanged until the stream has passed the
+ * call).  One kernel, one workgroup per frame: a lane per row of a 64-row band, the bands of a frame pipelined across the workgroup's
+ * waves (semantic_depth_amd/csrc/png_in_gpu.hip).  Enqueued on `stream`, no synchronisation; the handle need not be bound.
+ * SD_ERR_INVALID, and nothing is launched or copied: an extent outside 1..16384; rows_dev, frame_stride or workspace_dev not multiples
+ * of 16; frame_stride below a frame's height * (1 + width * channels) rounded up to 16; out_stride below height * width * 3; a
+ * descriptor of another size, with channels that are not its colour type's or more than 256 palette entries; workspace_bytes below
+ * sd_png_reconstruct_workspace.  A filter byte above 4 is the host's to refuse (sd_png_inflate_rows does); the kernel reads it as 4. */
+sd_status sd_png_reconstruct_bgr(sd_handle* h, const uint8_t* rows_dev, size_t frame_stride, const sd_png_frame_desc* descs_host, int B,
+                                 int height, int width, uint8_t* bgr_out_dev, size_t out_stride, int32_t* status_dev, void* workspace_dev,
+                                 size_t workspace_bytes, void* stream);
 /* HOST: the writer behind the sequence tool's cv2.imwrite('<dir>/<name>.png', frame) (seq:336): encodes n u8 [height,width,3] BGR frames at
  * frames_host + i * frame_stride as 8-bit RGB PNGs (filter type 0 rows, one zlib stream at `level` 0..9) and writes them to paths[i], on
  * `threads` native threads (<= 0: one per host CPU).  Pixel-exact, not byte-identical to OpenCV's file: sd_png_decode_bgr reads each

@@ -87,6 +87,15 @@ class sd_jpeg_frame_desc(C.Structure):
         return (self.width, self.height) if self.orientation >= 5 else (self.height, self.width)
 
 
+class sd_png_frame_desc(C.Structure):
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32), ("color_type", C.c_int32),
+                ("palette_entries", C.c_int32), ("reserved", C.c_int32), ("palette", (C.c_uint8 * 3) * 256)]
+
+    def rows_bytes(self) -> int:
+        """bytes of the frame's filtered rows: a filter byte plus width * channels bytes per row"""
+        return self.height * (1 + self.width * self.channels)
+
+
 SD_JPEG_ENTROPY_TABLES = 8
 
 
@@ -141,6 +150,12 @@ SIGNATURES = {
     "sd_jpeg_entropy_decode_host": (C.c_int, [_P, C.c_size_t, _P, _P, _P, C.c_size_t, _P, C.c_int, _P, C.c_size_t, _P]),
     "sd_jpeg_entropy_workspace": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sd_jpeg_entropy_decode": (C.c_int, [_H, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _P, C.c_int, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
+    "sd_png_inflate_rows": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(sd_png_frame_desc)]),
+    "sd_inflate_files_png": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(sd_png_frame_desc), C.c_int,
+                                       C.POINTER(C.c_int)]),
+    "sd_png_reconstruct_workspace": (C.c_int, [C.c_int, C.POINTER(C.c_size_t)]),
+    "sd_png_reconstruct_bgr": (C.c_int, [_H, _P, C.c_size_t, C.POINTER(sd_png_frame_desc), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P,
+                                         C.c_size_t, _P]),
     "sd_png_encode_bgr_files": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.c_int, C.c_int,
                                           C.POINTER(C.c_int)]),
     "sd_png_encode_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),

@@ -38,6 +38,7 @@ SOURCES = [
     ("png_gpu.hip", []),
     ("jpeg_enc_gpu.hip", []),
     ("jpeg_entropy_gpu.hip", []),
+    ("png_in_gpu.hip", []),
     ("ply_gpu.hip", ["-ffp-contract=off"]),
     ("text_gpu.hip", []),
     ("render_gpu.hip", ["-ffp-contract=off"]),
@@ -55,7 +56,7 @@ SOURCES = [
     ("host_jpeg_enc.cpp", []),
     ("host_rw_profile.cpp", ["-ffp-contract=off"]),
 ]
-HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", "jpeg_enc.hpp", "jpeg_enc_gpu.hpp", "jpeg_entropy.hpp", "jpeg_entropy_gpu.hpp", "ply_format.hpp", "ply_gpu.hpp", "text_draw.hpp", "text_gpu.hpp", "render_rule.hpp", "render_gpu.hpp", "rw_profile.hpp", "rw_profile_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
+HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", "jpeg_enc.hpp", "jpeg_enc_gpu.hpp", "jpeg_entropy.hpp", "jpeg_entropy_gpu.hpp", "png_unfilter.hpp", "png_in_gpu.hpp", "ply_format.hpp", "ply_gpu.hpp", "text_draw.hpp", "text_gpu.hpp", "render_rule.hpp", "render_gpu.hpp", "rw_profile.hpp", "rw_profile_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
 
 
 def _hipcc() -> str:

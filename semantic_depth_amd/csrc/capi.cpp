@@ -16,6 +16,7 @@
 #include "png_gpu.hpp"
 #include "jpeg_enc_gpu.hpp"
 #include "jpeg_entropy_gpu.hpp"
+#include "png_in_gpu.hpp"
 #include "ply_gpu.hpp"
 #include "text_gpu.hpp"
 #include "render_gpu.hpp"
@@ -500,7 +501,7 @@ static sd_status create_impl(sd_handle** out, int device, int H, int W, int max_
     {
         const std::string bad = sd_disable_unknown();
         if (!bad.empty()) {
-            std::fprintf(stderr, "sd_create: SEMDEPTH_DISABLE names no switch '%s' (dma dma3 direct stem fold tail1 pool_fuse planar n16 fuse1 fuse4 flat rowskip dma_big mfma16)\n", bad.c_str());
+            std::fprintf(stderr, "sd_create: SEMDEPTH_DISABLE names no switch '%s' (dma dma3 direct stem fold tail1 pool_fuse planar n16 fuse1 fuse4 flat rowskip dma_big mfma16 png_waves)\n", bad.c_str());
             return SD_ERR_INVALID;
         }
     }
@@ -800,6 +801,30 @@ sd_status sd_jpeg_entropy_decode(sd_handle* h, const uint8_t* bytes_dev, size_t 
         return fail(h, SD_ERR_INVALID, "sd_jpeg_entropy_decode: workspace smaller than sd_jpeg_entropy_workspace reports");
     HIPCHK(h, launch_jpeg_entropy_decode(bytes_dev, byte_stride, descs_host, frames_host, intervals_host, interval_stride, tables_host, B, coef_dev,
                                          coef_stride_bytes / sizeof(int16_t), status_dev, static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
+    return SD_OK;
+}
+
+sd_status sd_png_reconstruct_workspace(int B, size_t* bytes_out) {
+    if (B < 1 || B > 65535 || !bytes_out) return SD_ERR_INVALID;
+    *bytes_out = png_in_workspace_bytes(B);
+    return SD_OK;
+}
+
+sd_status sd_png_reconstruct_bgr(sd_handle* h, const uint8_t* rows_dev, size_t frame_stride, const sd_png_frame_desc* descs_host, int B, int height,
+                                 int width, uint8_t* bgr_out_dev, size_t out_stride, int32_t* status_dev, void* workspace_dev, size_t workspace_bytes,
+                                 void* stream) {
+    if (!h || !rows_dev || !descs_host || !bgr_out_dev || !status_dev || !workspace_dev)
+        return fail(h, SD_ERR_INVALID, "sd_png_reconstruct_bgr: bad arguments");
+    // the lanes fetch aligned 16-byte pieces of their rows
+    if ((reinterpret_cast<uintptr_t>(rows_dev) & 15) || (reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(status_dev) & 3))
+        return fail(h, SD_ERR_INVALID, "sd_png_reconstruct_bgr: rows_dev, frame_stride and workspace_dev must be multiples of 16");
+    // every index the kernel forms follows from descriptors of the call's size and these capacities: nothing is launched otherwise
+    const char* why = "";
+    if (!png_in_args_ok(frame_stride, descs_host, B, height, width, out_stride, &why)) return fail(h, SD_ERR_INVALID, std::string("sd_png_reconstruct_bgr: ") + why);
+    if (workspace_bytes < png_in_workspace_bytes(B))
+        return fail(h, SD_ERR_INVALID, "sd_png_reconstruct_bgr: workspace smaller than sd_png_reconstruct_workspace reports");
+    HIPCHK(h, launch_png_reconstruct(rows_dev, frame_stride, descs_host, B, height, width, bgr_out_dev, out_stride, status_dev,
+                                     static_cast<uint8_t*>(workspace_dev), (h->sw & SW_PNG_ONE_WAVE) ? 1 : sdpngin::kWaves, (hipStream_t)stream));
     return SD_OK;
 }
 

@@ -1,8 +1,10 @@
 // Host-side helper of the input stage: PNG scanline reconstruction for the frame reader that replaces
 // cv2.imread (semantic_depth.py:105, semantic_depth_cityscapes_sequence.py:123).  The DEFLATE stream is inflated by zlib
 // (Python's zlib module, which releases the GIL); what remains per frame is this serial byte recurrence (PNG spec §9,
-// filter types 0-4) plus the channel shuffle to OpenCV's 3-channel BGR layout.  No GPU work: a 2048 x 1024 RGB frame is
-// 6 MB and the Paeth/Average predictors are a dependency chain along each row — host cores do it while the GPU computes.
+// filter types 0-4) plus the channel shuffle to OpenCV's 3-channel BGR layout.  On the default route (FrameFeeder(png="host"))
+// there is no GPU work: the Paeth/Average predictors are a dependency chain along each row and host cores run it while the GPU
+// computes.  The opt-in split route (png="device": sd_png_inflate_rows / sd_inflate_files_png below) leaves only the chunk walk and
+// the inflate here and hands the recurrence to png_in_gpu.hip, a row per lane; sd_png_unfilter_bgr stays the yardstick of both.
 #include "../../include/semdepth.h"
 
 #include <cstdlib>
@@ -240,6 +242,114 @@ extern "C" sd_status sd_decode_files_jpeg_coef(const char* const* paths, int n, 
                         if (st == SD_OK)
                             st = sd_jpeg_decode_coefficients(file.data(), file.size(), coef_out_host + (size_t)i * (frame_stride_bytes / 2),
                                                              frame_stride_bytes, &descs_out[i]);
+                    }
+                }
+            } catch (...) {
+                st = SD_ERR_INVALID;
+            }
+            if (status_out) status_out[i] = st;
+            if (st != SD_OK && st != SD_ERR_FORMAT) failed.fetch_add(1);
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        for (int t = 1; t < threads; ++t) pool.emplace_back(work);
+    } catch (...) {
+    }
+    work();
+    for (auto& th : pool) th.join();
+    return failed.load() ? SD_ERR_INVALID : SD_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The split PNG route (FrameFeeder(png="device")): the host keeps the serial part -- chunk walk and inflate, straight into the
+// caller's (pinned) staging -- and png_in_gpu.hip runs the scanline recurrence, the channel map and the palette lookup for the
+// whole batch.  The same png_head and the same walk as png_decode above; what png_decode learns from sd_png_unfilter_bgr (a
+// filter byte above 4) is checked here with one byte read per row, so the device never sees a row type it cannot name.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+
+sd_status png_inflate(const uint8_t* f, size_t len, uint8_t* rows, size_t cap, sd_png_frame_desc* desc) {
+    PngHead hd;
+    if (!png_head(f, len, hd)) return SD_ERR_INVALID;
+    if (desc) {
+        std::memset(desc, 0, sizeof(*desc));
+        desc->height = hd.h; desc->width = hd.w; desc->channels = hd.channels; desc->color_type = hd.ctype;
+    }
+    if (!rows) return SD_OK;                                    // (descriptor query)
+    const size_t row_len = 1 + (size_t)hd.w * hd.channels, raw_len = (size_t)hd.h * row_len;
+    if (cap < raw_len || raw_len > 0xFFFFFFFFu) return SD_ERR_INVALID;      // before anything is written
+    z_stream zs;
+    std::memset(&zs, 0, sizeof(zs));
+    if (inflateInit(&zs) != Z_OK) return SD_ERR_INVALID;
+    zs.next_out = rows;
+    zs.avail_out = (uInt)raw_len;
+    const uint8_t* plte = nullptr;
+    size_t plte_n = 0;
+    bool done = false, ok = true;
+    for (size_t p = 8; p + 12 <= len && !done;) {
+        const uint32_t n = be32(f + p);
+        if (p + 12 + (size_t)n > len) { ok = false; break; }
+        const uint8_t* tag = f + p + 4;
+        const uint8_t* body = f + p + 8;
+        if (!std::memcmp(tag, "IDAT", 4)) {
+            zs.next_in = const_cast<Bytef*>(body);
+            zs.avail_in = n;
+            const int r = inflate(&zs, Z_NO_FLUSH);
+            if (r != Z_OK && r != Z_STREAM_END) { ok = false; break; }
+        } else if (!std::memcmp(tag, "PLTE", 4)) {
+            plte = body; plte_n = n / 3;
+        } else if (!std::memcmp(tag, "IEND", 4)) {
+            done = true;
+        }
+        p += 12 + (size_t)n;
+    }
+    const bool full = zs.total_out == raw_len;
+    inflateEnd(&zs);
+    if (!ok || !full) return SD_ERR_INVALID;
+    for (int y = 0; y < hd.h; ++y)
+        if (rows[(size_t)y * row_len] > 4) return SD_ERR_INVALID;
+    if (hd.ctype == 3) {
+        if (!plte) return SD_ERR_INVALID;
+        if (desc) {
+            const size_t k = plte_n < 256 ? plte_n : 256;       // (an index is a byte: entries past 255 are never named)
+            desc->palette_entries = (int32_t)k;
+            std::memcpy(desc->palette, plte, 3 * k);
+        }
+    }
+    return SD_OK;
+}
+
+}  // namespace
+
+extern "C" sd_status sd_png_inflate_rows(const uint8_t* file_host, size_t len, uint8_t* rows_out_host, size_t capacity, sd_png_frame_desc* desc_out) {
+    try {
+        return png_inflate(file_host, len, rows_out_host, capacity, desc_out);
+    } catch (...) {
+        return SD_ERR_INVALID;
+    }
+}
+
+extern "C" sd_status sd_inflate_files_png(const char* const* paths, int n, int height, int width, uint8_t* rows_out_host, size_t frame_stride,
+                                          sd_png_frame_desc* descs_out, int threads, int* status_out) {
+    if (!paths || n < 0 || height <= 0 || width <= 0 || !rows_out_host || !descs_out) return SD_ERR_INVALID;
+    if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
+    threads = threads < 1 ? 1 : (threads > n ? (n > 0 ? n : 1) : threads);
+    std::atomic<int> next(0), failed(0);
+    auto work = [&]() {
+        std::vector<uint8_t> file;
+        for (;;) {
+            const int i = next.fetch_add(1);
+            if (i >= n) break;
+            sd_status st = SD_ERR_NOTFOUND;
+            try {
+                if (paths[i] && read_file(paths[i], file)) {
+                    if (file.size() < 8 || std::memcmp(file.data(), kPngSig, 8) != 0) st = SD_ERR_FORMAT;
+                    else {
+                        sd_png_frame_desc d;
+                        st = png_inflate(file.data(), file.size(), nullptr, 0, &d);
+                        if (st == SD_OK && (d.height != height || d.width != width)) st = SD_ERR_INVALID;
+                        if (st == SD_OK) st = png_inflate(file.data(), file.size(), rows_out_host + (size_t)i * frame_stride, frame_stride, &descs_out[i]);
                     }
                 }
             } catch (...) {

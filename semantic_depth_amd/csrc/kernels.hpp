@@ -18,7 +18,8 @@ enum Switch : unsigned {
     SW_NO_TAIL1 = 1u << 18,      // SEMDEPTH_NO_TAIL1: upconv1 / iconv1 / disp1 of the bf16 x 3 monodepth as three launches (plan-time switch)
     SW_NO_ROWSKIP = 1u << 19,    // SEMDEPTH_NO_ROWSKIP: conv_dma3 without the row-grouped pixel order (ConvParams::rowgrp)
     SW_NO_FLAT = 1u << 20,       // SEMDEPTH_NO_FLAT: conv_dma3's 1x1 layers through the general gather
-    SW_MFMA32 = 1u << 22         // SEMDEPTH_MFMA32: conv_dma3's bf16 x 3 layers on 32x32x16 MFMAs instead of 16x16x32 (round 5; conv_dma3.hip "S16")
+    SW_MFMA32 = 1u << 22,        // SEMDEPTH_MFMA32: conv_dma3's bf16 x 3 layers on 32x32x16 MFMAs instead of 16x16x32 (round 5; conv_dma3.hip "S16")
+    SW_PNG_ONE_WAVE = 1u << 23   // SEMDEPTH_DISABLE=png_waves: sd_png_reconstruct_bgr walks a frame's bands with ONE wave instead of pipelining them across 16
 };
 unsigned latch_switches();      // plan.cpp
 bool sd_disabled(const char* what);   // plan.cpp: is `what` in SEMDEPTH_DISABLE?

@@ -10,7 +10,7 @@
 namespace sd {
 
 // SEMDEPTH_DISABLE=name[,name...]: the ONE run-time variable that switches specialised kernels off in favour of the generic ones behind them (parity tests, A/B
-// runs).  Names: dma dma3 direct stem fold tail1 pool_fuse planar n16 fuse1 fuse4 flat rowskip dma_big mfma16.  Read when a handle is created (plan + switches),
+// runs).  Names: dma dma3 direct stem fold tail1 pool_fuse planar n16 fuse1 fuse4 flat rowskip dma_big mfma16 png_waves.  Read when a handle is created (plan + switches),
 // latch_switches adds SEMDEPTH_PROFILE_VERBOSE=1 to the same switch word.
 bool sd_disabled(const char* what) {
     const char* e = std::getenv("SEMDEPTH_DISABLE");
@@ -26,7 +26,7 @@ bool sd_disabled(const char* what) {
 }
 // the first token of SEMDEPTH_DISABLE that names nothing (a typo must not silently leave the specialised kernel on): sd_create refuses the handle
 std::string sd_disable_unknown() {
-    static const char* const known[] = {"dma", "dma3", "direct", "stem", "fold", "tail1", "pool_fuse", "planar", "n16", "fuse1", "fuse4", "flat", "rowskip", "dma_big", "mfma16"};
+    static const char* const known[] = {"dma", "dma3", "direct", "stem", "fold", "tail1", "pool_fuse", "planar", "n16", "fuse1", "fuse4", "flat", "rowskip", "dma_big", "mfma16", "png_waves"};
     const char* e = std::getenv("SEMDEPTH_DISABLE");
     if (!e) return "";
     for (const char* p = e; *p;) {
@@ -42,7 +42,7 @@ std::string sd_disable_unknown() {
 unsigned latch_switches() {
     static const struct { const char* name; unsigned bit; } tab[] = {
         {"n16", SW_NO_N16}, {"dma_big", SW_NO_DMA_BIG}, {"stem", SW_NO_STEM}, {"fuse4", SW_NO_FUSE4}, {"dma", SW_NO_DMA}, {"fuse1", SW_NO_FUSE1},
-        {"dma3", SW_NO_DMA3}, {"fold", SW_NO_FOLD}, {"tail1", SW_NO_TAIL1}, {"rowskip", SW_NO_ROWSKIP}, {"flat", SW_NO_FLAT}, {"mfma16", SW_MFMA32}};
+        {"dma3", SW_NO_DMA3}, {"fold", SW_NO_FOLD}, {"tail1", SW_NO_TAIL1}, {"rowskip", SW_NO_ROWSKIP}, {"flat", SW_NO_FLAT}, {"mfma16", SW_MFMA32}, {"png_waves", SW_PNG_ONE_WAVE}};
     unsigned sw = 0;
     for (const auto& e : tab)
         if (sd_disabled(e.name)) sw |= e.bit;

@@ -95,7 +95,8 @@ def run_sequence(load_frames, n_frames: int, step, batch: int = 32, group=None, 
 
 
 def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", workers: int = 0, outputs=None, jpeg: str = "host",
-                       engine=None, png: str | None = None, ply: str | None = None, text: str | None = None, render=None, video=None) -> torch.Tensor:
+                       engine=None, png: str | None = None, ply: str | None = None, text: str | None = None, render=None, video=None,
+                       png_in: str | None = None) -> torch.Tensor:
     """run_sequence on FILES (semantic_depth_cityscapes_sequence.py:689-701 reads ``sorted(glob(input_folder))`` frame by frame): rank r
     decodes ONLY its shard of the sorted list -- frame_io.FrameFeeder: one native call per batch into pinned staging, upload one batch
     ahead, ``workers`` decode threads (default: this rank's share of the node's CPUs, frame_io.default_decode_workers) -- and hands every
@@ -108,6 +109,8 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     that have restart intervals (one interleaved sequential scan, DRI > 0, nothing but stuffed bytes and the expected RSTk markers in it) are
     entropy-decoded on the GPU as well, the host only finds their markers, and every other JPEG falls back to the host decoder
     (FrameFeeder.entropy_fallback names them); the frames are the same bytes on all three.
+    ``png_in`` (None = "host" | "device") is the feeder's ``png=`` (``png`` here already names the output writer): with "device" the PNG
+    frames are only inflated on the host and their scanlines reconstructed on the GPU by ``engine``; the frames are the same bytes.
     ``png``, ``ply``, ``text``, ``render``, ``video`` (None = what the SequenceOutputs was built with) go to SequenceOutputs.configure before
     the first batch: the choices are described there, and what the step of make_engine_step does for each -- all but png="host",
     ply="host", text="json" and Video(route="host") need that step -- in its own docstring."""
@@ -127,7 +130,9 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     try:
         parts = []
         if hi > lo:
-            with FrameFeeder(paths[lo:hi], batch, device=device, workers=workers, jpeg=jpeg, engine=engine if jpeg != "host" else None) as feeder:
+            png_in = png_in if png_in is not None else "host"
+            with FrameFeeder(paths[lo:hi], batch, device=device, workers=workers, jpeg=jpeg,
+                             engine=engine if jpeg != "host" or png_in != "host" else None, png=png_in) as feeder:
                 for frames, first in feeder:
                     rec = step(frames, lo + first)
                     assert rec.dtype == torch.uint8 and tuple(rec.shape) == (frames.shape[0], RECORD_BYTES), (rec.dtype, rec.shape)

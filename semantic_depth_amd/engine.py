@@ -381,6 +381,35 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_jpeg_reconstruct_bgr")
         return out
 
+    def png_reconstruct(self, rows: torch.Tensor, descs, out: torch.Tensor | None = None, status: torch.Tensor | None = None):
+        """the device half of the split PNG route (sd_png_reconstruct_bgr): ``rows`` u8 [B, frame_stride] device tensor of the frames'
+        filtered scanlines as sd_png_inflate_rows / sd_inflate_files_png lay them out (frame_stride a multiple of 16 that holds the
+        widest frame's rows rounded up to 16), ``descs`` a HOST ctypes array of B _lib.sd_png_frame_desc of one height x width ->
+        (frames u8 [B,h,w,3] BGR, status int32 [B]) device tensors: the bytes of frame_io.decode_png, and a non-zero status word for a
+        palette frame with an index beyond its palette (such pixels take entry 0).  One kernel, one workgroup per frame, on the current
+        stream, no synchronisation: a pinned ``descs`` must stay unchanged until the stream has passed the call."""
+        assert rows.dtype == torch.uint8 and rows.is_cuda and rows.is_contiguous() and rows.dim() == 2
+        B = rows.shape[0]
+        if B < 1 or len(descs) < B:
+            raise ValueError("png_reconstruct: one descriptor per frame")
+        h, w = descs[0].height, descs[0].width
+        if any((descs[i].height, descs[i].width) != (h, w) for i in range(B)):
+            raise ValueError("png_reconstruct: the frames of a batch share one size")
+        if out is None:
+            out = torch.empty((B, h, w, 3), dtype=torch.uint8, device=self.device)
+        if status is None:
+            status = torch.empty((B,), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, h, w, 3)
+        assert status.dtype == torch.int32 and status.is_cuda and status.is_contiguous() and status.numel() >= B
+        need = C.c_size_t()
+        st = self.lib.sd_png_reconstruct_workspace(B, C.byref(need))
+        L.check(self.lib, None, st, "sd_png_reconstruct_workspace")
+        ws = torch.empty((need.value,), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_png_reconstruct_bgr(self.h, _ptr(rows), rows.shape[1], descs, B, h, w, _ptr(out), h * w * 3, _ptr(status), _ptr(ws),
+                                             need.value, self._stream())
+        L.check(self.lib, self.h, st, "sd_png_reconstruct_bgr")
+        return out, status
+
     def jpeg_entropy_decode(self, scan: torch.Tensor, descs, frames, tables, intervals, interval_stride: int, coef_stride: int | None = None,
                             out: torch.Tensor | None = None, status: torch.Tensor | None = None):
         """the device half of the entropy JPEG route (sd_jpeg_entropy_decode): ``scan`` u8 [B, byte_stride] device tensor of the frames'

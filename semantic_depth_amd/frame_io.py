@@ -8,9 +8,11 @@ feeder that keeps the GPU supplied.
                             reads and decodes straight into a pinned staging buffer, one batch ahead of the GPU; the cubic resize to
                             the network shape happens ON the GPU (Engine.resize_cubic), so the host never touches a pixel after the decode
 
-PNG decode stays on the host on purpose: DEFLATE and the PNG predictors are serial byte recurrences; a frame costs a few
+PNG decode stays on the host by default: DEFLATE and the PNG predictors are serial byte recurrences; a frame costs a few
 milliseconds of one core (scripts/feed_rate.py measures decode, pinned H2D and resize rates against the benchmarked
-frames/s; DESIGN.md quotes them).  JPEG frames (the reference's own example frame is one) have two routes: ``jpeg="host"``, the
+frames/s; DESIGN.md quotes them).  ``png="device"`` keeps only the chunk walk and the inflate there (sd_inflate_files_png) and runs
+the predictors -- a row per lane, the rows of a frame one pixel behind each other --, the channel shuffle and the palette lookup on
+the GPU (Engine.png_reconstruct), byte for byte the host route's frames.  JPEG frames (the reference's own example frame is one) have two routes: ``jpeg="host"``, the
 default, decodes them completely on the host threads as well; ``jpeg="device"`` keeps only the serial part there -- the Huffman
 decoder, to quantised coefficients (sd_decode_files_jpeg_coef) -- and runs the inverse DCT, the chroma upsampling, the colour
 conversion and the EXIF orientation on the GPU (Engine.jpeg_reconstruct), byte for byte the host route's frames;
@@ -233,12 +235,29 @@ class FrameFeeder:
     host decoder during the last iteration.  The kernel's per-frame status words come back through pinned memory on a copy stream of
     the feeder's own: the feeder waits on that stream, never on the compute stream.  Frames, indices, batch boundaries and the PNG
     handling are those of the other routes.  It takes the Huffman decoder off the host threads; it is not the faster feeder yet: with one
-    interval per MCU row it measured slower than ``jpeg="device"`` at 512x1024, 1024x2048 and 3024x4032."""
+    interval per MCU row it measured slower than ``jpeg="device"`` at 512x1024, 1024x2048 and 3024x4032.
+    ``png="device"`` (same needs; combines with every ``jpeg=`` choice): the worker thread only walks the chunks of the batch's PNG
+    files and inflates their IDAT streams into pinned staging (sd_inflate_files_png), one batch ahead as well.  The filtered scanlines
+    go up as they are -- about the byte count of the BGR frame -- and Engine.png_reconstruct runs the filter recurrence, the channel
+    map and the palette lookup on the GPU, a run of consecutive PNG frames per launch, straight into the batch tensor.  The files that
+    are not PNGs go down the ``jpeg=`` route.  Frames, indices and batch boundaries are those of ``png="host"``; a file the inflate
+    refuses, and a palette frame the kernel flags for an index beyond its palette, raise what the host route raises.  The status words
+    are read back only for a batch that holds a palette frame, on the same copy stream ("PNG reconstruction on the
+    device")."""
 
-    def __init__(self, paths, batch: int, device="cuda", workers: int = 0, jpeg: str = "host", engine=None):
+    def __init__(self, paths, batch: int, device="cuda", workers: int = 0, jpeg: str = "host", engine=None, png: str = "host"):
         import os
         import torch
         self.paths, self.batch, self.device = list(paths), batch, torch.device(device)
+        if png not in ("host", "device"):
+            raise ValueError(f"FrameFeeder: png must be 'host' or 'device', not {png!r}")
+        if png != "host" and self.device.type != "cuda":
+            raise ValueError(f"FrameFeeder: png={png!r} reconstructs the frames on the GPU; device='cpu' has none")
+        if png != "host" and engine is None:
+            raise ValueError(f"FrameFeeder: png={png!r} needs engine= (the handle that launches the reconstruction kernels)")
+        self.png = png
+        self._pinned_rows = [None, None]
+        self._others = [None, None]           # png="device": per staging slot, the feeder that takes the batch's files that are not PNGs
         if jpeg not in ("host", "device", "device_entropy"):
             raise ValueError(f"FrameFeeder: jpeg must be 'host', 'device' or 'device_entropy', not {jpeg!r}")
         if jpeg != "host" and self.device.type != "cuda":
@@ -261,6 +280,11 @@ class FrameFeeder:
         self._pinned_coef = [None, None]
         self._pinned_png = [None, None]
         self._pinned_ent = [None, None]
+        self._pinned_rows = [None, None]
+        for f in self._others:
+            if f is not None:
+                f.close()
+        self._others = [None, None]
 
     def __enter__(self):
         return self
@@ -501,6 +525,105 @@ class FrameFeeder:
             dev[i].copy_(frame, non_blocking=True)
         return dev
 
+    @staticmethod
+    def png_rows_stride(h: int, w: int) -> int:
+        """bytes that hold the filtered rows of any 8-bit PNG frame of h x w: a filter byte plus four channels per row, rounded up to the
+        16 bytes the kernel loads"""
+        return -(-(h * (1 + 4 * w)) // 16) * 16
+
+    def _inflate_into(self, slot: int, lo: int, hi: int):
+        """PNG device route, host part of one batch: the chunk walk and the inflate of every PNG file into pinned staging
+        (sd_inflate_files_png); the files that are not PNGs go down the ``jpeg=`` route of a feeder of their own"""
+        torch = self._torch
+        h, w = self._header_size(self.paths[lo])
+        stride = self.png_rows_stride(h, w)
+        n = hi - lo
+        st_ = self._pinned_rows[slot]
+        if st_ is None or st_["rows"].shape[1] != stride:
+            st_ = self._pinned_rows[slot] = dict(
+                rows=torch.empty((self.batch, stride), dtype=torch.uint8, pin_memory=True),
+                descs=torch.empty((self.batch * C.sizeof(L.sd_png_frame_desc),), dtype=torch.uint8, pin_memory=True),
+                status=torch.empty((self.batch,), dtype=torch.int32, pin_memory=True))
+        # the descriptors live in the pinned buffer: the C call uploads them with an asynchronous copy, and a slot is not inflated into
+        # again before the event of its last batch has passed
+        descs = (L.sd_png_frame_desc * n).from_address(st_["descs"].data_ptr())
+        arr = (C.c_char_p * n)(*[os_fsencode(p) for p in self.paths[lo:hi]])
+        status = (C.c_int * n)()
+        st = self._lib.sd_inflate_files_png(arr, n, h, w, C.c_void_p(st_["rows"].data_ptr()), stride, descs, self.workers, status)
+        if st != L.SD_OK:
+            bad = [(self.paths[lo + i], status[i]) for i in range(n) if status[i] not in (L.SD_OK, L.SD_ERR_FORMAT)]
+            raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
+        others = [i for i in range(n) if status[i] == L.SD_ERR_FORMAT]
+        rest = None
+        if others:
+            sub = self._others[slot]
+            if sub is None:
+                sub = self._others[slot] = FrameFeeder([], self.batch, device=self.device, workers=self.workers, jpeg=self.jpeg,
+                                                       engine=self.engine if self.jpeg != "host" else None)
+            sub.paths = [self.paths[lo + i] for i in others]
+            stage = {"host": sub._decode_into, "device": sub._decode_coef_into, "device_entropy": sub._plan_into}[self.jpeg]
+            rest = stage(slot, 0, len(others))
+            rh, rw = tuple(rest.shape[1:3]) if self.jpeg == "host" else (rest[3] if self.jpeg == "device" else rest["size"])
+            if (rh, rw) != (h, w):
+                bad = [(p, L.SD_ERR_INVALID) for p in sub.paths]
+                raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
+        return dict(n=n, lo=lo, size=(h, w), pinned=st_, descs=descs, others=others, rest=rest, slot=slot)
+
+    def _png_reconstruct(self, host):
+        """PNG device route, GPU part of one batch on the current stream: the uploads of the rows each frame really has, one kernel per
+        run of consecutive PNG frames writing straight into the batch tensor, the status words' way back on the feeder's copy stream when
+        the batch holds a palette frame, then the frames of the other files"""
+        torch = self._torch
+        n, lo, (h, w), pin, descs = host["n"], host["lo"], host["size"], host["pinned"], host["descs"]
+        dev = torch.empty((n, h, w, 3), dtype=torch.uint8, device=self.device)
+        others = set(host["others"])
+        pg = [i for i in range(n) if i not in others]
+        status = None
+        if pg:
+            stride = pin["rows"].shape[1]
+            rdev = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
+            status = torch.zeros((n,), dtype=torch.int32, device=self.device)
+            for i in pg:
+                used = -(-descs[i].rows_bytes() // 16) * 16
+                rdev[i, :used].copy_(pin["rows"][i, :used], non_blocking=True)
+            size = C.sizeof(L.sd_png_frame_desc)
+            j0 = 0
+            while j0 < len(pg):                                 # a run of consecutive PNG frames is a contiguous slice of the batch tensor
+                j1 = j0 + 1
+                while j1 < len(pg) and pg[j1] == pg[j1 - 1] + 1:
+                    j1 += 1
+                i0, m = pg[j0], j1 - j0
+                run = (L.sd_png_frame_desc * m).from_address(pin["descs"].data_ptr() + i0 * size)
+                self.engine.png_reconstruct(rdev[i0:i0 + m], run, out=dev[i0:i0 + m], status=status[i0:i0 + m])
+                j0 = j1
+        palette = [i for i in pg if descs[i].color_type == 3]
+        if palette:                                             # only an index beyond the palette can be flagged
+            if self._copy_stream is None:
+                self._copy_stream = torch.cuda.Stream(self.device)
+            done = torch.cuda.Event()
+            done.record()
+            with torch.cuda.stream(self._copy_stream):
+                self._copy_stream.wait_event(done)
+                pin["status"][:n].copy_(status, non_blocking=True)
+            status.record_stream(self._copy_stream)
+        if host["others"]:
+            sub = self._others[host["slot"]]
+            rest = host["rest"]
+            if self.jpeg == "host":
+                rdev2 = rest.to(self.device, non_blocking=True)
+            else:
+                rdev2 = (sub._reconstruct if self.jpeg == "device" else sub._entropy_reconstruct)(rest)
+                self.entropy_fallback += [(lo + host["others"][j], why) for j, why in sub.entropy_fallback]
+                sub.entropy_fallback = []
+            for j, i in enumerate(host["others"]):
+                dev[i].copy_(rdev2[j], non_blocking=True)
+        if palette:
+            self._copy_stream.synchronize()                     # the feeder's own stream: the status words are in pinned memory now
+            bad = [(self.paths[lo + i], L.SD_ERR_INVALID) for i in palette if int(pin["status"][i]) != 0]
+            if bad:                                             # what the host route raises for a file with an index beyond its palette
+                raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
+        return dev
+
     def __iter__(self):
         torch = self._torch
         n = len(self.paths)
@@ -510,6 +633,8 @@ class FrameFeeder:
         with ThreadPoolExecutor(max_workers=1) as ahead:
             decode = {"host": self._decode_into, "device": self._decode_coef_into, "device_entropy": self._plan_into}[self.jpeg]
             rebuild = {"device": self._reconstruct, "device_entropy": self._entropy_reconstruct}.get(self.jpeg)
+            if self.png == "device":
+                decode, rebuild = self._inflate_into, self._png_reconstruct
             self.entropy_fallback = []
             fut = ahead.submit(decode, 0, *ranges[0])
             events = [None, None]
