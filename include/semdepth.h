@@ -771,6 +771,43 @@ sd_status sd_f2f_profile(sd_handle* h, const sd_rw_result* road_dev, const sd_f2
 sd_status sd_f2f_profile_host(const sd_rw_result* road, const sd_f2f_result* f2f, const double* depths, int D,
                               sd_f2f_depth_result* results_host /* [D] */);
 
+/* ---------------------------------------------------------------- scoring the segmentation (fcn8s/fcn.py test mode, FCN.inference :384-492)
+ * The test mode resizes the frame AND the label image with scipy.misc.imresize(img, image_shape) (:408, :412), which for uint8 input is
+ * PIL.Image.resize((W, H), BILINEAR) -- not the cv2.resize cubic of sd_resize_cubic_u8 -- and scores argmax against
+ * helper.prepare_ground_truth (:149-177) with tf.metrics.mean_iou, whose state is a count matrix.
+ *
+ * sd_resize_pil_bilinear_u8: Pillow's ImagingResample for 8-bit images with the bilinear filter, bit for bit (csrc/pil_resample.hpp states
+ * the rule: a window that grows with the downscale factor, 22-bit fixed-point weights made on the host in double, horizontal then vertical
+ * pass with the uint8 rounding between them).  src_dev: B frames of src_h x src_w pixels whose first bytes lie pixel_stride bytes apart
+ * (rows and frames packed: src_w * pixel_stride and src_h * src_w * pixel_stride bytes); `channels` (1 or 3, <= pixel_stride <= 4) bytes
+ * are taken per pixel, so channel 0 of a [H,W,3] label frame is read in place with pixel_stride 3, channels 1.  dst_dev: u8
+ * [B,dst_h,dst_w,channels]; reverse != 0 stores the channels in reverse order (the readers deliver BGR, the test mode feeds RGB).
+ * Two launches on `stream` (one when dst_h == src_h), no synchronisation, integer arithmetic only.  Every workspace byte the result depends on
+ * is written by the same call (sd_resize_pil_workspace bytes, 16-byte aligned); the handle need not be bound.
+ * SD_ERR_INVALID, nothing launched: a null pointer; B < 1 or B > 65535; channels not 1 or 3; pixel_stride < channels or > 4; a source or
+ * destination extent outside 1..16384; a downscale factor above 32 on an axis (src > 32 * dst; the window would pass 65 taps); a
+ * workspace that is too small or not 16-byte aligned.  Upscaling (windows of 1 or 2 taps) is accepted.
+ * sd_resize_pil_bilinear_u8_host: the same bytes for HOST arrays (no B limit).
+ *
+ * sd_seg_confusion: counts_dev int64 [B][10] += per frame b the 3 x 3 matrix [label class][predicted class] in cells 0..8, where the
+ * label class is table_host[labels[b][y][x]] (256 bytes, values 0..2: road 0, fence 1, everything else 2 -- prepare_ground_truth as a
+ * table) and the predicted class pred[b][y][x] (the argmax of sd_fcn8s_forward).  A prediction above 2 is counted in no cell of the matrix
+ * but in cell 9 of its frame, for the caller to turn into an error.  The caller zeroes counts_dev or keeps accumulating into it.  One
+ * launch: ballots and population counts per wave, one sum per workgroup, at most ten 64-bit atomic adds per workgroup; integer sums, so
+ * the result does not depend on their order.  The handle need not be bound.
+ * SD_ERR_INVALID: a null pointer; B < 1 or B > 65535; height or width outside 1..16384; a table value above 2; counts_dev not 8-byte
+ * aligned.  sd_seg_confusion_host: the same counts for HOST arrays (no B limit). */
+sd_status sd_resize_pil_workspace(int B, int src_h, int src_w, int dst_h, int dst_w, int channels, size_t* bytes_out);
+sd_status sd_resize_pil_bilinear_u8(sd_handle* h, const uint8_t* src_dev, int B, int src_h, int src_w, int pixel_stride, int channels, int reverse,
+                                    uint8_t* dst_dev /* [B,dst_h,dst_w,channels] */, int dst_h, int dst_w, void* workspace_dev,
+                                    size_t workspace_bytes, void* stream);
+sd_status sd_resize_pil_bilinear_u8_host(const uint8_t* src, int B, int src_h, int src_w, int pixel_stride, int channels, int reverse,
+                                         uint8_t* dst, int dst_h, int dst_w);
+sd_status sd_seg_confusion(sd_handle* h, const uint8_t* pred_dev /* [B,height,width] */, const uint8_t* labels_dev /* [B,height,width] */, int B,
+                           int height, int width, const uint8_t* table_host /* [256] */, int64_t* counts_dev /* [B][10] */, void* stream);
+sd_status sd_seg_confusion_host(const uint8_t* pred, const uint8_t* labels, int B, int height, int width, const uint8_t* table /* [256] */,
+                                int64_t* counts /* [B][10] */);
+
 /* ---------------------------------------------------------------- pcl.py, function by function
  * (semantic_depth_lib/pcl.py; one cloud per call: xyz f32 [n,3], rgb u8 [n,3] nullable, n on the host).
  * Outputs keep the input row order.  *n_out is a DEVICE int32. */

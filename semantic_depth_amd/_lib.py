@@ -19,6 +19,7 @@ SD_PLY_ROW_CAP, SD_PLY_HEADER_CAP, SD_PLY_LINE_ROWS = 69, 209, 1001
 SD_TEXT_MAX_BYTES, SD_TEXT_MAX_SEGS, SD_TEXT_MAX_ITEMS, SD_TEXT_MAX_SCALE_Q8, SD_TEXT_MAX_THICKNESS, SD_TEXT_MAX_ORG = 64, 32, 4, 4096, 32, 32768
 SD_RENDER_MAX_EXTENT, SD_RENDER_MAX_POINT = 16384, 16
 SD_PROFILE_MAX_DEPTHS = 256
+SD_SEG_CELLS = 10      # sd_seg_confusion: counters per frame, the 3 x 3 matrix and the predictions above 2
 SD_PREC_F32, SD_PREC_BF16X2, SD_PREC_MIXED, SD_PREC_PLAN, SD_PREC_BF16X3, SD_PREC_F16X2 = 0, 1, 2, 3, 4, 5
 
 
@@ -193,6 +194,11 @@ SIGNATURES = {
     "sd_road_width_profile_host": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_double, _P]),
     "sd_f2f_profile": (C.c_int, [_H, _P, _P, C.c_int, _P, C.c_int, _P, _P]),
     "sd_f2f_profile_host": (C.c_int, [_P, _P, _P, C.c_int, _P]),
+    "sd_resize_pil_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "sd_resize_pil_bilinear_u8": (C.c_int, [_H, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "sd_resize_pil_bilinear_u8_host": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
+    "sd_seg_confusion": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "sd_seg_confusion_host": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "sd_pcl_extract_pcls": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sd_pcl_remove_from_to": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P]),
     "sd_pcl_remove_noise_by_mad": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P, _P]),

@@ -21,6 +21,7 @@
 #include "text_gpu.hpp"
 #include "render_gpu.hpp"
 #include "rw_profile_gpu.hpp"
+#include "seg_eval_gpu.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -53,6 +54,7 @@ struct sd_handle {
     std::vector<CamDev> cams_stage;
     std::vector<CamDev> sweep_stage;     // sd_fuse_backproject_sweep: the [T][B] records of the last call (source of its upload)
     std::vector<sdrwp::Window> rwp_stage;    // sd_road_width_profile: the sorted windows of the last call (source of its upload)
+    sdpil::Windows pil_x, pil_y;             // sd_resize_pil_bilinear_u8: the windows of the last call (source of its uploads)
     std::map<std::pair<int, int>, std::vector<float>> bias_host;   // (net, slot) -> host copy, for bias slots that are summed
     std::map<std::pair<int, int>, std::vector<float>> w_host;      // (net, slot) -> f32 tensor of the SD_PREC_F16X2 slots that share a weight scale (sd_load_weight)
     std::string err;
@@ -1224,6 +1226,47 @@ sd_status sd_f2f_profile(sd_handle* h, const sd_rw_result* road_dev, const sd_f2
         depths.d[i] = depths_host[i];
     }
     HIPCHK(h, launch_f2f_profile(road_dev, f2f_dev, B, depths, D, results_dev, (hipStream_t)stream));
+    return SD_OK;
+}
+
+sd_status sd_resize_pil_bilinear_u8(sd_handle* h, const uint8_t* src_dev, int B, int src_h, int src_w, int pixel_stride, int channels, int reverse,
+                                    uint8_t* dst_dev, int dst_h, int dst_w, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!h || !src_dev || !dst_dev || !workspace_dev) return fail(h, SD_ERR_INVALID, "sd_resize_pil_bilinear_u8: null pointer");
+    if (B < 1 || B > 65535 || (channels != 1 && channels != 3) || pixel_stride < channels || pixel_stride > 4)
+        return fail(h, SD_ERR_INVALID, "sd_resize_pil_bilinear_u8: B in 1..65535, channels 1 or 3, channels <= pixel_stride <= 4");
+    if (!sdpil::axis_ok(src_h, dst_h) || !sdpil::axis_ok(src_w, dst_w))
+        return fail(h, SD_ERR_INVALID, "sd_resize_pil_bilinear_u8: extents in 1..16384 and a downscale factor of at most 32 per axis");
+    // every index the kernels form follows from these sizes, the windows made below and this capacity: nothing is launched otherwise
+    if (workspace_bytes < sdpil::workspace_bytes(B, src_h, src_w, dst_h, dst_w, channels) || (reinterpret_cast<uintptr_t>(workspace_dev) & 15))
+        return fail(h, SD_ERR_INVALID, "sd_resize_pil_bilinear_u8: workspace smaller than sd_resize_pil_workspace reports, or not 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    // (a second call overwrites the windows the first call's copies read: pageable sources are staged before hipMemcpyAsync returns)
+    sdpil::pil_windows(src_w, dst_w, h->pil_x);
+    sdpil::pil_windows(src_h, dst_h, h->pil_y);
+    if (h->pil_x.taps > sdpil::taps_bound(src_w, dst_w) || h->pil_y.taps > sdpil::taps_bound(src_h, dst_h))
+        return fail(h, SD_ERR_STATE, "sd_resize_pil_bilinear_u8: a window is longer than its bound");
+    uint8_t* ws = static_cast<uint8_t*>(workspace_dev);
+    const size_t tx = sdpil::tables_bytes(src_w, dst_w);
+    HIPCHK(h, hipMemcpyAsync(ws, h->pil_x.bounds.data(), h->pil_x.bounds.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(ws + sdpil::al16((size_t)dst_w * 8), h->pil_x.k.data(), h->pil_x.k.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(ws + tx, h->pil_y.bounds.data(), h->pil_y.bounds.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(ws + tx + sdpil::al16((size_t)dst_h * 8), h->pil_y.k.data(), h->pil_y.k.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, launch_pil_resample_u8(src_dev, B, src_h, src_w, pixel_stride, channels, reverse ? 1 : 0, dst_dev, dst_h, dst_w, h->pil_x, ws, s));
+    return SD_OK;
+}
+
+sd_status sd_seg_confusion(sd_handle* h, const uint8_t* pred_dev, const uint8_t* labels_dev, int B, int height, int width, const uint8_t* table_host,
+                           int64_t* counts_dev, void* stream) {
+    if (!h || !pred_dev || !labels_dev || !table_host || !counts_dev) return fail(h, SD_ERR_INVALID, "sd_seg_confusion: null pointer");
+    if (B < 1 || B > 65535 || height < 1 || width < 1 || height > sdpil::kMaxExtent || width > sdpil::kMaxExtent)
+        return fail(h, SD_ERR_INVALID, "sd_seg_confusion: B in 1..65535, height and width in 1..16384");
+    if (reinterpret_cast<uintptr_t>(counts_dev) & 7) return fail(h, SD_ERR_INVALID, "sd_seg_confusion: counts_dev must be 8-byte aligned");
+    SegTable table;
+    for (int i = 0; i < 256; ++i) {
+        if (table_host[i] > 2) return fail(h, SD_ERR_INVALID, "sd_seg_confusion: a table value above 2 (classes are 0, 1, 2)");
+        table.v[i] = table_host[i];
+    }
+    HIPCHK(h, launch_seg_confusion(pred_dev, labels_dev, B, height, width, table, counts_dev, (hipStream_t)stream));
     return SD_OK;
 }
 

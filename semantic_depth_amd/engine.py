@@ -357,6 +357,51 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_resize_cubic_u8")
         return out
 
+    def resize_pil(self, frames: torch.Tensor, out_h: int | None = None, out_w: int | None = None, channels: int | None = None,
+                   pixel_stride: int | None = None, reverse: bool = False) -> torch.Tensor:
+        """scipy.misc.imresize(frame, (out_h, out_w)) of the FCN test mode (fcn8s/fcn.py:408,412) = PIL.Image.resize((out_w, out_h), BILINEAR)
+        for u8 [B,h,w,S] (or [B,h,w], S = 1) device frames, bit for bit (sd_resize_pil_bilinear_u8) -> u8 [B,out_h,out_w,channels].
+        ``pixel_stride`` (default S) bytes lie between pixels and ``channels`` (1 or 3, default S) of them are taken: channel 0 of a
+        reader's [B,h,w,3] label frame is resampled in place with channels=1.  ``reverse`` stores the channels in reverse order (the
+        readers deliver BGR, the test mode feeds RGB).  Two launches on the current stream, no synchronisation; the workspace (the windows
+        and the uint8 intermediate between the passes) is a torch allocation."""
+        out_h, out_w = out_h or self.H, out_w or self.W
+        assert frames.dtype == torch.uint8 and frames.is_cuda and frames.is_contiguous() and frames.dim() in (3, 4)
+        B, sh, sw = (int(v) for v in frames.shape[:3])
+        S = int(frames.shape[3]) if frames.dim() == 4 else 1
+        pixel_stride = pixel_stride or S
+        channels = channels or S
+        if pixel_stride != S:
+            raise ValueError(f"resize_pil: pixel_stride {pixel_stride} is not the frames' last extent {S}")
+        need = C.c_size_t()
+        st = self.lib.sd_resize_pil_workspace(B, sh, sw, out_h, out_w, channels, C.byref(need))
+        L.check(self.lib, None, st, f"sd_resize_pil_workspace({B}, {sh}x{sw} -> {out_h}x{out_w}, channels={channels})")
+        out = torch.empty((B, out_h, out_w, channels), dtype=torch.uint8, device=self.device)
+        ws = torch.empty((need.value,), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_resize_pil_bilinear_u8(self.h, _ptr(frames), B, sh, sw, pixel_stride, channels, int(bool(reverse)), _ptr(out), out_h, out_w,
+                                                _ptr(ws), need.value, self._stream())
+        L.check(self.lib, self.h, st, "sd_resize_pil_bilinear_u8")
+        return out
+
+    def seg_confusion(self, pred: torch.Tensor, labels: torch.Tensor, table, out: torch.Tensor | None = None) -> torch.Tensor:
+        """the state of tf.metrics.mean_iou per frame (sd_seg_confusion): ``pred`` u8 [B,h,w] (fcn8s_forward's argmax, 0..2) against
+        ``labels`` u8 [B,h,w] label ids through ``table`` (256 bytes, label id -> class 0..2; evaluate.label_table) ADDED into ``out``
+        int64 [B,10] (zeros when None): cells 0..8 are the 3 x 3 matrix [label class][predicted class], cell 9 counts the predictions
+        above 2, which enter no cell of the matrix.  One launch on the current stream, no synchronisation."""
+        for t in (pred, labels):
+            assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.dim() == 3, t.shape
+        assert pred.shape == labels.shape, (pred.shape, labels.shape)
+        B, h, w = (int(v) for v in pred.shape)
+        tab = np.ascontiguousarray(table, dtype=np.uint8)
+        if tab.shape != (256,):
+            raise ValueError("seg_confusion: the table holds 256 bytes")
+        if out is None:
+            out = torch.zeros((B, L.SD_SEG_CELLS), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.int64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, L.SD_SEG_CELLS), out.shape
+        st = self.lib.sd_seg_confusion(self.h, _ptr(pred), _ptr(labels), B, h, w, tab.ctypes.data_as(C.c_void_p), _ptr(out), self._stream())
+        L.check(self.lib, self.h, st, "sd_seg_confusion")
+        return out
+
     def jpeg_reconstruct(self, coef: torch.Tensor, descs, out: torch.Tensor | None = None) -> torch.Tensor:
         """the device half of the split JPEG route (sd_jpeg_reconstruct_bgr): ``coef`` int16 [B, stride] device tensor of quantised
         coefficients as sd_jpeg_decode_coefficients / sd_decode_files_jpeg_coef lay them out, ``descs`` a ctypes array of B
