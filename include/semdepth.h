@@ -808,6 +808,48 @@ sd_status sd_seg_confusion(sd_handle* h, const uint8_t* pred_dev /* [B,height,wi
 sd_status sd_seg_confusion_host(const uint8_t* pred, const uint8_t* labels, int B, int height, int width, const uint8_t* table /* [256] */,
                                 int64_t* counts /* [B][10] */);
 
+/* ---------------------------------------------------------------- the disparity image of a frame (semantic_depth.py:681-683)
+ * DepthFrame.disp_to_image is scipy.misc.imresize(disp_pp, [h, w]) followed by plt.imsave(name + "_disp.png", img, cmap='gray')
+ * (cmap='plasma' commented out beside it).  The rule, per frame b of a float32 [B, height, width] map (csrc/disp_image_rule.hpp states it
+ * for host and device); mult[b] is the frame's disparity multiplier (:145), 1.0 when the pointer is NULL:
+ *   1. v = d * mult[b] in float32.
+ *   2. lo, hi = minimum and maximum of the FINITE v of the frame; cs = hi - lo in float32; cs == 0, or a frame with no finite value, means
+ *      cs = 1 (and lo = 0 when nothing is finite); scale = (float)(255.0 / (double)cs).
+ *   3. byte = (int)(clip((v - lo) * scale, 0, 255) + 0.5f), the difference and the product each rounded to float32 and never contracted into
+ *      an fma: scipy's bytescale with the arithmetic of the numpy of the reference's time (an f32 array against a scalar stays f32)
+ *      [UPSTREAM, unpinned].  A non-finite v gives byte 0 and sets flags[b] = 1; otherwise flags[b] = 0.  (hi - lo beyond the float32
+ *      range makes scale 0 and the product of an infinite difference not a number: byte 0.)
+ *   4. Pillow's bilinear resample of the [height, width] byte image to [out_h, out_w] (sd_resize_pil_bilinear_u8's arithmetic, one
+ *      channel, shrinking and its support included); equal sizes mean a copy.
+ *   5. lo8, hi8 = minimum and maximum of the RESIZED byte image of the frame; hi8 == lo8 gives index 0 for every pixel, otherwise
+ *      idx = min(255, 256 * (p - lo8) / (hi8 - lo8)) in integers (floor).  This is matplotlib's float32 Normalize followed by int(x * 256)
+ *      with 256 mapped to 255, for every (p, lo8, hi8): 256 a / b with b <= 255 is never within a float32 rounding of an integer it does
+ *      not hit.  A constant image leaves as entry 0 of the table: black for gray, (12, 7, 134) for plasma.
+ *   6. colour = table[cmap][idx], table = matplotlib.colormaps[cmap](np.arange(256), bytes=True)[:, :3], kept as data.  gray is NOT the
+ *      identity: it is trunc(i / 255 * 255) in double, one below i at 24 entries (33, 37, 41, ..., 244).
+ *   7. out: u8 [B, out_h, out_w, 3] in the channel order the PNG routes take (BGR).  imsave writes RGBA with alpha 255; the files here are
+ *      8-bit RGB: pixels are pinned, not file bytes.
+ * sd_disp_image: disp_dev f32 [B,height,width] (4-byte aligned; 16-byte aligned maps with height * width % 4 == 0 are read four floats per
+ * lane), mult_host NULL or B floats on the HOST, out_bgr_dev any alignment (4-byte aligned with out_h * out_w % 4 == 0: dword stores),
+ * flags_dev i32 [B].  Five launches on `stream` plus the resample's (none when the sizes agree), no synchronisation, no allocation: a
+ * per-frame minimum / maximum over several workgroups combined by 32-bit integer atomics on an order-preserving key (no dependence on
+ * grid size or arrival order), the byte pass, the resample, the minimum / maximum of the resized bytes, the colour pass.  Every workspace
+ * byte the result depends on is written by the same call (sd_disp_image_workspace bytes, 16-byte aligned); the handle need not be bound.
+ * SD_ERR_INVALID, nothing launched: a null pointer (mult_host excepted); B < 1 or B > 65535; a cmap that is not one of the two; an extent
+ * below 1 or beyond what the resample accepts (1..16384, a downscale factor of at most 32 per axis); a workspace that is too small or not
+ * 16-byte aligned; disp_dev or flags_dev not 4-byte aligned.
+ * sd_disp_image_host: the same bytes and flags for HOST arrays (no B limit, no handle, no GPU).
+ * sd_disp_colormap: the 256 entries of a map as R, G, B bytes. */
+#define SD_CMAP_GRAY 0
+#define SD_CMAP_PLASMA 1
+sd_status sd_disp_image_workspace(int B, int height, int width, int out_h, int out_w, size_t* bytes_out);
+sd_status sd_disp_image(sd_handle* h, const float* disp_dev, const float* mult_host /* nullable */, int B, int height, int width, int out_h,
+                        int out_w, int cmap, uint8_t* out_bgr_dev /* [B,out_h,out_w,3] */, int32_t* flags_dev /* [B] */, void* workspace_dev,
+                        size_t workspace_bytes, void* stream);
+sd_status sd_disp_image_host(const float* disp, const float* mult /* nullable */, int B, int height, int width, int out_h, int out_w, int cmap,
+                             uint8_t* out_bgr /* [B,out_h,out_w,3] */, int32_t* flags /* [B] */);
+sd_status sd_disp_colormap(int cmap, uint8_t* rgb_out /* [768] */);
+
 /* ---------------------------------------------------------------- pcl.py, function by function
  * (semantic_depth_lib/pcl.py; one cloud per call: xyz f32 [n,3], rgb u8 [n,3] nullable, n on the host).
  * Outputs keep the input row order.  *n_out is a DEVICE int32. */

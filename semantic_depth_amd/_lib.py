@@ -20,6 +20,7 @@ SD_TEXT_MAX_BYTES, SD_TEXT_MAX_SEGS, SD_TEXT_MAX_ITEMS, SD_TEXT_MAX_SCALE_Q8, SD
 SD_RENDER_MAX_EXTENT, SD_RENDER_MAX_POINT = 16384, 16
 SD_PROFILE_MAX_DEPTHS = 256
 SD_SEG_CELLS = 10      # sd_seg_confusion: counters per frame, the 3 x 3 matrix and the predictions above 2
+SD_CMAP_GRAY, SD_CMAP_PLASMA = 0, 1      # sd_disp_image: the two colour maps
 SD_PREC_F32, SD_PREC_BF16X2, SD_PREC_MIXED, SD_PREC_PLAN, SD_PREC_BF16X3, SD_PREC_F16X2 = 0, 1, 2, 3, 4, 5
 
 
@@ -199,6 +200,10 @@ SIGNATURES = {
     "sd_resize_pil_bilinear_u8_host": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "sd_seg_confusion": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "sd_seg_confusion_host": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "sd_disp_image_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "sd_disp_image": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_size_t, _P]),
+    "sd_disp_image_host": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "sd_disp_colormap": (C.c_int, [C.c_int, _P]),
     "sd_pcl_extract_pcls": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sd_pcl_remove_from_to": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P]),
     "sd_pcl_remove_noise_by_mad": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, C.c_double, _P, _P, _P, _P, _P]),

@@ -197,7 +197,8 @@ class DepthFrame:
         min)`` truncated after + 0.5) followed by PIL's bilinear resize; imsave maps the uint8 image linearly onto the gray colormap,
         i.e. min -> 0, max -> 255 again.  Written as an 8-bit gray PNG ``<output_name>_disp.png``; returns its path.  PIL's resampling
         arithmetic (bilinear with antialiasing support when shrinking) is restated as plain bilinear interpolation at pixel centres --
-        the reference only ever enlarges the map here (network size -> original frame size)."""
+        the reference only ever enlarges the map here (network size -> original frame size).  The reference's own pixels (Pillow's
+        resample bit for bit, matplotlib's normalisation and colour tables, 'gray' or 'plasma') are outputs.write_disp_image's."""
         from .outputs import write_png
         d = np.asarray(disp_pp, dtype=np.float64).squeeze()
         lo, hi = float(d.min()), float(d.max())

@@ -22,6 +22,7 @@
 #include "render_gpu.hpp"
 #include "rw_profile_gpu.hpp"
 #include "seg_eval_gpu.hpp"
+#include "disp_image_gpu.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
 
@@ -55,6 +56,8 @@ struct sd_handle {
     std::vector<CamDev> sweep_stage;     // sd_fuse_backproject_sweep: the [T][B] records of the last call (source of its upload)
     std::vector<sdrwp::Window> rwp_stage;    // sd_road_width_profile: the sorted windows of the last call (source of its upload)
     sdpil::Windows pil_x, pil_y;             // sd_resize_pil_bilinear_u8: the windows of the last call (source of its uploads)
+    sdpil::Windows disp_x, disp_y;           // sd_disp_image: the same for its resample
+    std::vector<float> disp_mult;            // sd_disp_image: the multipliers of the last call (source of their upload)
     std::map<std::pair<int, int>, std::vector<float>> bias_host;   // (net, slot) -> host copy, for bias slots that are summed
     std::map<std::pair<int, int>, std::vector<float>> w_host;      // (net, slot) -> f32 tensor of the SD_PREC_F16X2 slots that share a weight scale (sd_load_weight)
     std::string err;
@@ -1252,6 +1255,42 @@ sd_status sd_resize_pil_bilinear_u8(sd_handle* h, const uint8_t* src_dev, int B,
     HIPCHK(h, hipMemcpyAsync(ws + tx, h->pil_y.bounds.data(), h->pil_y.bounds.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHK(h, hipMemcpyAsync(ws + tx + sdpil::al16((size_t)dst_h * 8), h->pil_y.k.data(), h->pil_y.k.size() * 4, hipMemcpyHostToDevice, s));
     HIPCHK(h, launch_pil_resample_u8(src_dev, B, src_h, src_w, pixel_stride, channels, reverse ? 1 : 0, dst_dev, dst_h, dst_w, h->pil_x, ws, s));
+    return SD_OK;
+}
+
+sd_status sd_disp_image(sd_handle* h, const float* disp_dev, const float* mult_host, int B, int height, int width, int out_h, int out_w, int cmap,
+                        uint8_t* out_bgr_dev, int32_t* flags_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!h || !disp_dev || !out_bgr_dev || !flags_dev || !workspace_dev) return fail(h, SD_ERR_INVALID, "sd_disp_image: null pointer");
+    if (B < 1 || B > 65535 || !sddisp::valid_map(cmap))
+        return fail(h, SD_ERR_INVALID, "sd_disp_image: B in 1..65535, cmap SD_CMAP_GRAY or SD_CMAP_PLASMA");
+    if (height < 1 || width < 1 || out_h < 1 || out_w < 1 || !sddisp::valid_sizes(height, width, out_h, out_w))
+        return fail(h, SD_ERR_INVALID, "sd_disp_image: extents in 1..16384 and a downscale factor of at most 32 per axis");
+    // every index the kernels form follows from these sizes, the windows made below and this capacity: nothing is launched otherwise
+    const sddisp::Layout l = sddisp::layout(B, height, width, out_h, out_w);
+    if (workspace_bytes < l.total || (reinterpret_cast<uintptr_t>(workspace_dev) & 15))
+        return fail(h, SD_ERR_INVALID, "sd_disp_image: workspace smaller than sd_disp_image_workspace reports, or not 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(disp_dev) & 3) || (reinterpret_cast<uintptr_t>(flags_dev) & 3))
+        return fail(h, SD_ERR_INVALID, "sd_disp_image: disp_dev and flags_dev must be 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t* ws = static_cast<uint8_t*>(workspace_dev);
+    const bool resize = sddisp::resized(height, width, out_h, out_w);
+    if (resize) {
+        sdpil::pil_windows(width, out_w, h->disp_x);
+        sdpil::pil_windows(height, out_h, h->disp_y);
+        if (h->disp_x.taps > sdpil::taps_bound(width, out_w) || h->disp_y.taps > sdpil::taps_bound(height, out_h))
+            return fail(h, SD_ERR_STATE, "sd_disp_image: a window is longer than its bound");
+        uint8_t* pw = ws + l.pil;
+        const size_t tx = sdpil::tables_bytes(width, out_w);
+        HIPCHK(h, hipMemcpyAsync(pw, h->disp_x.bounds.data(), h->disp_x.bounds.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(pw + sdpil::al16((size_t)out_w * 8), h->disp_x.k.data(), h->disp_x.k.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(pw + tx, h->disp_y.bounds.data(), h->disp_y.bounds.size() * 4, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(pw + tx + sdpil::al16((size_t)out_h * 8), h->disp_y.k.data(), h->disp_y.k.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    if (mult_host) {
+        h->disp_mult.assign(mult_host, mult_host + B);
+        HIPCHK(h, hipMemcpyAsync(ws + l.mult, h->disp_mult.data(), (size_t)B * sizeof(float), hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(h, launch_disp_image(disp_dev, B, height, width, out_h, out_w, cmap, mult_host ? 1 : 0, out_bgr_dev, flags_dev, h->disp_x, ws, s));
     return SD_OK;
 }
 

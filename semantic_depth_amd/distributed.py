@@ -96,7 +96,7 @@ def run_sequence(load_frames, n_frames: int, step, batch: int = 32, group=None, 
 
 def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", workers: int = 0, outputs=None, jpeg: str = "host",
                        engine=None, png: str | None = None, ply: str | None = None, text: str | None = None, render=None, video=None,
-                       png_in: str | None = None) -> torch.Tensor:
+                       png_in: str | None = None, disp: str | None = None) -> torch.Tensor:
     """run_sequence on FILES (semantic_depth_cityscapes_sequence.py:689-701 reads ``sorted(glob(input_folder))`` frame by frame): rank r
     decodes ONLY its shard of the sorted list -- frame_io.FrameFeeder: one native call per batch into pinned staging, upload one batch
     ahead, ``workers`` decode threads (default: this rank's share of the node's CPUs, frame_io.default_decode_workers) -- and hands every
@@ -111,8 +111,8 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     (FrameFeeder.entropy_fallback names them); the frames are the same bytes on all three.
     ``png_in`` (None = "host" | "device") is the feeder's ``png=`` (``png`` here already names the output writer): with "device" the PNG
     frames are only inflated on the host and their scanlines reconstructed on the GPU by ``engine``; the frames are the same bytes.
-    ``png``, ``ply``, ``text``, ``render``, ``video`` (None = what the SequenceOutputs was built with) go to SequenceOutputs.configure before
-    the first batch: the choices are described there, and what the step of make_engine_step does for each -- all but png="host",
+    ``png``, ``ply``, ``text``, ``render``, ``video``, ``disp`` (None = what the SequenceOutputs was built with) go to SequenceOutputs.configure
+    before the first batch: the choices are described there, and what the step of make_engine_step does for each -- all but png="host",
     ply="host", text="json" and Video(route="host") need that step -- in its own docstring."""
     from .frame_io import FrameFeeder
     engine = engine if engine is not None else getattr(step, "engine", None)
@@ -125,7 +125,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     if outputs is not None:
         if len(outputs.names) != n_frames:
             raise ValueError(f"SequenceOutputs has {len(outputs.names)} names for {n_frames} frames")
-        outputs.configure(png, ply, text, render, video)
+        outputs.configure(png, ply, text, render, video, disp)
         outputs.begin(rank, world, lo, hi)
     try:
         parts = []
@@ -155,7 +155,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
 
 
 def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outputs=None, on_range: str | None = None, png: str | None = None,
-                     ply: str | None = None, text: str | None = None, render=None, video=None, depths=None):
+                     ply: str | None = None, text: str | None = None, render=None, video=None, depths=None, disp: str | None = None):
     """``step`` for run_sequence on a real Engine: host or device u8 frames of any size -> (cubic resize to the network shape on
     the GPU, semantic_depth_cityscapes_sequence.py:123-130) -> Engine.process_batch -> record buffer.
     ``camera_of(global_frame_index) -> engine.Camera`` (the sequence tool: cx = 1048.64/4·s, cy = 519.277/4·s, disp_mult = 3800).
@@ -183,7 +183,11 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     ``depths`` (None = what ``outputs`` was built with, SequenceOutputs(profile=); else it becomes the outputs' profile, and must agree with
     one already chosen): process_batch(depths=) adds every frame's depth profile -- two launches behind the road chain, one more with
     approach 'both' -- and the record tensors travel to ``outputs.submit`` with the batch's other small records.  Without ``outputs`` the
-    step returns the records only and ``depths`` asks for nothing."""
+    step returns the records only and ``depths`` asks for nothing.
+    ``disp`` (None = what ``outputs`` was built with; "gray" or "plasma"): Engine.disparity_image turns process_batch's ``disp_pp`` into the
+    disparity image of every frame at the original frame size, with the frames' Camera.disp_mult as multipliers -- five launches plus the
+    resample's two, behind the networks -- and the ``<name>_disp.png`` files go through the PNG route chosen (png="device":
+    Engine.encode_png on the images).  With None nothing is launched."""
     from .engine import RoadWidthParams
     from .recompute import check_mode
 
@@ -191,7 +195,7 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
         raise ValueError(f"make_engine_step(on_range={on_range!r}) on an engine built with on_range={getattr(engine, 'on_range', 'raise')!r}")
     prm = params or RoadWidthParams()
     if outputs is not None:
-        outputs.configure(png, ply, text, render, video)
+        outputs.configure(png, ply, text, render, video, disp)
         if depths is not None:
             want = [float(d) for d in np.asarray(depths, dtype=np.float64).reshape(-1)]
             if outputs.profile is None:
@@ -235,6 +239,12 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
                 more["render_streams"] = engine.encode_png(renders)
             else:
                 more["renders"] = renders
+        if outputs.disp is not None:                               # the disparity images, behind the networks
+            dimg, more["disp_flags"] = engine.disparity_image(out["disp_pp"], size[0], size[1], outputs.disp, mults=[c.disp_mult for c in cams])
+            if device_png:
+                more["disp_streams"] = engine.encode_png(dimg)
+            else:
+                more["disp_images"] = dimg
         if outputs.images or vid is not None:
             images = engine.compose_result_frames(fr, out["seg"]["road"], out["seg"]["fence"], rec, size[0], size[1], outputs.road_color,
                                                   outputs.fence_color, outputs.alpha)

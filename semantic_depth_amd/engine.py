@@ -626,6 +626,39 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_render_rw")
         return out, flags
 
+    def disparity_image(self, disp: torch.Tensor, out_h: int, out_w: int, cmap: str = "gray", mults=None, out: torch.Tensor | None = None):
+        """DepthFrame.disp_to_image (semantic_depth.py:681-683: scipy.misc.imresize(disp, [h, w]) then plt.imsave(cmap=)) for f32
+        [B,h,w] device ``disp`` (process_batch's ``disp_pp``) -> (``images`` u8 [B,out_h,out_w,3] BGR, ``flags`` i32 [B]) device tensors
+        (sd_disp_image: the rule of include/semdepth.h, the bytes of outputs.disparity_image): per frame the map times ``mults[b]`` (host
+        numbers, the frames' Camera.disp_mult; None: 1) is byte-scaled over its finite range, resampled with Pillow's bilinear filter,
+        normalised over the range of the resized bytes and looked up in matplotlib's ``cmap`` table ("gray" or "plasma").  flags[b] = 1:
+        frame b holds a non-finite value, which became byte 0.  ``out``: a contiguous u8 tensor of that shape to write into (any byte
+        offset: a base that is not 4-byte aligned takes the byte-store form of the colour pass).  Five launches plus the resample's on the
+        current stream, no synchronisation; the workspace is a torch allocation."""
+        from .outputs import DISP_MAPS
+        if cmap not in DISP_MAPS:
+            raise ValueError(f"cmap must be 'gray' or 'plasma', got {cmap!r}")
+        assert disp.dtype == torch.float32 and disp.is_cuda and disp.is_contiguous() and disp.dim() == 3, (disp.dtype, disp.shape)
+        B, h, w = (int(v) for v in disp.shape)
+        out_h, out_w = int(out_h), int(out_w)
+        m = None
+        if mults is not None:
+            m = np.ascontiguousarray(mults, dtype=np.float32).reshape(-1)
+            if m.shape != (B,):
+                raise ValueError(f"disparity_image: {m.size} multipliers for {B} frames")
+        need = C.c_size_t()
+        st = self.lib.sd_disp_image_workspace(B, h, w, out_h, out_w, C.byref(need))
+        L.check(self.lib, None, st, f"sd_disp_image_workspace({B}, {h}x{w} -> {out_h}x{out_w})")
+        if out is None:
+            out = torch.empty((B, out_h, out_w, 3), dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, out_h, out_w, 3), out.shape
+        flags = torch.empty((B,), dtype=torch.int32, device=self.device)
+        ws = torch.empty((need.value,), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_disp_image(self.h, _ptr(disp), None if m is None else m.ctypes.data_as(C.c_void_p), B, h, w, out_h, out_w,
+                                    DISP_MAPS.index(cmap), _ptr(out), _ptr(flags), _ptr(ws), need.value, self._stream())
+        L.check(self.lib, self.h, st, "sd_disp_image")
+        return out, flags
+
     def post_process(self, disp_raw: torch.Tensor):
         B = disp_raw.shape[0]
         assert disp_raw.dtype == torch.float32 and tuple(disp_raw.shape[1:]) == (2, self.H, self.W) and disp_raw.is_contiguous()

@@ -11,6 +11,7 @@
     focal_sweep                     <- semantic_depth.py:854-944  (``results/<f>/data.txt``, ``best_focal_lengths.txt``)
     focal_sweep_batched             the same files behind one network pass per frame (Engine.camera_sweep)
     write_png                       <- cv2.imwrite(...png) at :406 (zlib-deflated 8-bit RGB; pixel-identical, not byte-identical)
+    disparity_image / write_disp_image <- semantic_depth.py:681-683 (``<name>_disp.png``: scipy.misc.imresize + plt.imsave, pixel for pixel)
     SequenceOutputs                 <- the files of the sequence tool, semantic_depth_cityscapes_sequence.py:303-361 (``result_sequence_imgs/<name>.png``,
                                        ``result_sequence_ply/<name>_rw.ply``), written from the batched driver (distributed.run_sequence_files)
 
@@ -291,6 +292,69 @@ def render_rw(xyz, rgb, left_pt=None, right_pt=None, camera: RenderCamera | None
     if st != L.SD_OK:
         raise ValueError(f"render_rw: the camera is outside the caps of include/semdepth.h (status {st})")
     return (out, flag.value) if return_flag else out
+
+
+# ------------------------------------------------------------------------------------------------ disparity images
+DISP_MAPS = ("gray", "plasma")              # SD_CMAP_GRAY, SD_CMAP_PLASMA: the reference's choice and its commented-out one (monodepth's own)
+
+
+def _check_disp(disp):
+    if disp is not None and disp not in DISP_MAPS:
+        raise ValueError(f"disp must be None, 'gray' or 'plasma', got {disp!r}")
+    return disp
+
+
+def disp_colormap(cmap: str = "gray") -> np.ndarray:
+    """the 256 entries of a colour map as u8 [256,3] RGB (sd_disp_colormap: matplotlib's table, kept as data)"""
+    import ctypes as C
+
+    from . import _lib as L
+    if cmap not in DISP_MAPS:
+        raise ValueError(f"cmap must be 'gray' or 'plasma', got {cmap!r}")
+    out = np.empty((256, 3), np.uint8)
+    st = L.load().sd_disp_colormap(DISP_MAPS.index(cmap), out.ctypes.data_as(C.c_void_p))
+    assert st == L.SD_OK, st
+    return out
+
+
+def disparity_image(disp, out_h: int, out_w: int, cmap: str = "gray", mults=None):
+    """DepthFrame.disp_to_image (semantic_depth.py:681-683: scipy.misc.imresize(disp, [h, w]) then plt.imsave(cmap=)) for
+    f32 [B,h,w] (or [h,w]) ``disp`` on the host (sd_disp_image_host: the rule of include/semdepth.h, the bytes Engine.disparity_image
+    makes on the GPU): per frame the map times ``mults[b]`` (None: 1) is byte-scaled over its finite range, resampled with Pillow's bilinear
+    filter to out_h x out_w, normalised over the range of the resized bytes and looked up in matplotlib's ``cmap`` table.  Returns
+    (``images`` u8 [B,out_h,out_w,3] BGR, ``flags`` i32 [B]; flags[b] = 1: frame b holds a non-finite value, which became byte 0)."""
+    import ctypes as C
+
+    from . import _lib as L
+    if cmap not in DISP_MAPS:
+        raise ValueError(f"cmap must be 'gray' or 'plasma', got {cmap!r}")
+    d = np.ascontiguousarray(disp, dtype=np.float32)
+    if d.ndim == 2:
+        d = d[None]
+    if d.ndim != 3:
+        raise ValueError(f"disparity_image: the maps must be f32 [B,h,w] or [h,w], got {d.shape}")
+    B, h, w = d.shape
+    m = None
+    if mults is not None:
+        m = np.ascontiguousarray(mults, dtype=np.float32).reshape(-1)
+        if m.shape != (B,):
+            raise ValueError(f"disparity_image: {m.size} multipliers for {B} frames")
+    out = np.empty((B, int(out_h), int(out_w), 3), np.uint8)
+    flags = np.empty((B,), np.int32)
+    st = L.load().sd_disp_image_host(d.ctypes.data_as(C.c_void_p), None if m is None else m.ctypes.data_as(C.c_void_p), B, h, w, int(out_h), int(out_w),
+                                     DISP_MAPS.index(cmap), out.ctypes.data_as(C.c_void_p), flags.ctypes.data_as(C.c_void_p))
+    if st != L.SD_OK:
+        raise ValueError(f"disparity_image: {h}x{w} -> {out_h}x{out_w} is outside what the resample accepts (extents 1..16384, a downscale "
+                         f"factor of at most 32; status {st})")
+    return out, flags
+
+
+def write_disp_image(output_name: str, disp, h: int, w: int, cmap: str = "gray", mult: float = 1.0) -> str:
+    """``<output_name>_disp.png`` of semantic_depth.py:681-683 for one f32 [H,W] map: disparity_image at h x w through write_png (8-bit
+    RGB; imsave's pixels, not its RGBA file bytes)"""
+    d = np.asarray(disp, dtype=np.float32).squeeze()
+    img, _ = disparity_image(d, h, w, cmap, [mult])
+    return write_png("{}_disp.png".format(output_name), img[0])
 
 
 def write_png(path: str, img_bgr: np.ndarray, level: int = 3) -> str:
@@ -604,6 +668,7 @@ def focal_sweep_batched(frames: dict, input_frames: dict, frame_segmenter, frame
 SEQ_IMG_DIR, SEQ_PLY_DIR = "result_sequence_imgs", "result_sequence_ply"          # semantic_depth_cityscapes_sequence.py:671-680
 SEQ_PROFILE_DIR = "result_sequence_profile"                                       # the per-frame depth profiles (SequenceOutputs(profile=))
 SEQ_RENDER_DIR = "rendered_sequence"                                              # utils/render_ply.py's output folder
+SEQ_DISP_DIR = "result_sequence_disp"                                             # the per-frame disparity images (SequenceOutputs(disp=))
 
 
 # ------------------------------------------------------------------------------------------------ result video
@@ -849,6 +914,9 @@ class _Batch:
     video_streams: object = None
     profile: object = None
     f2f_profile: object = None
+    disp_images: object = None
+    disp_streams: object = None
+    disp_flags: object = None
 
 
 @dataclasses.dataclass
@@ -871,6 +939,10 @@ class _HostBatch:
     video_raw: dict = dataclasses.field(default_factory=dict)      # frame -> raw image of a flagged video frame
     profile: np.ndarray | None = None       # [n,D,48] depth-profile records
     f2f_profile: np.ndarray | None = None   # [n,D,64]
+    disp_images: np.ndarray | None = None   # [n,h,w,3] disparity images, when they travel whole
+    disp_png: np.ndarray | None = None      # [n,stride] zlib streams of them, disp_png[i, :disp_sizes[i]] copied
+    disp_sizes: np.ndarray | None = None
+    disp_flags: np.ndarray | None = None    # [n] non-zero: the frame's map held a non-finite value
 
 
 class _Stager:
@@ -973,15 +1045,16 @@ class SequenceOutputs:
         <directory>/result_imgs.avi                           only with video=: the result images as a Motion-JPEG AVI (``video``;
                                                               result_imgs_rank<r>.avi when world > 1, _part<k> when a file rolls over)
         <directory>/result_sequence_profile/<name>.txt        only with profile=: the frame's depth profile (``profile``; profile_text)
+        <directory>/result_sequence_disp/<name>_disp.png      only with disp=: the frame's disparity image (``disp``; disparity_image)
         <directory>/manifest_rank<r>.json                     written last by close(): the files of this rank and 'ok' / 'range_error' / 'error'
 
     ``names``: output names of the WHOLE sorted frame list (sequence_names), indexed by global frame index.  submit() takes the device
     tensors of one batch, copies them into pinned staging on a side stream behind an event of the current stream, and writes them on
     worker threads -- at most two batches in flight -- with the per-pixel and per-point work in native code (no interpreter lock).
     ``threads``: native encoder threads per batch and PLY writer threads (0: frame_io.default_decode_workers()).
-    The five choices that follow can also be made after construction and before the first batch, by configure() (all at once; what
+    The choices that follow can also be made after construction and before the first batch, by configure() (all at once; what
     make_engine_step and run_sequence_files do with their keywords of the same names) or by set_png / set_ply / set_text / set_render /
-    set_video; the "device" routes, text="draw", render= and video= need the step of make_engine_step, which does the GPU half.
+    set_video / set_disp; the "device" routes, text="draw", render= and video= need the step of make_engine_step, which does the GPU half.
     ``png``: "host" (default) copies the raw images to the host and deflates them there (sd_png_encode_bgr_files at ``level``); "device"
     takes each frame's finished zlib stream from the GPU (Engine.encode_png, submit(png_streams=)): the sizes are copied first, then each
     stream's exact byte count, and the host only writes the PNG chunks (sd_png_write_streams_files).  Same names, manifest and pixels.
@@ -1007,13 +1080,19 @@ class SequenceOutputs:
     ``profile``: None (default: nothing more is written, copied or launched, the manifest is what it was) or the list of depths of a depth
     profile: the step of make_engine_step asks process_batch for it (``depths=``) and hands submit(profile=, f2f_profile=) the [n,D,48] /
     [n,D,64] record tensors, which travel with the batch's other small records in the first phase of the staged transfer; the writer stores
-    ``result_sequence_profile/<name>.txt`` per frame.  The manifest names the depths under 'profile_depths' and the files under 'profile'."""
+    ``result_sequence_profile/<name>.txt`` per frame.  The manifest names the depths under 'profile_depths' and the files under 'profile'.
+    ``disp``: None (default: nothing more is written, copied or launched, the manifest is what it was), "gray" or "plasma": the step of
+    make_engine_step also turns every frame's post-processed disparity map into the image of DepthFrame.disp_to_image
+    (semantic_depth.py:681-683) at the original frame size on the GPU (Engine.disparity_image, submit(disp_images=, disp_flags=) or, with
+    png="device", submit(disp_streams=)); the images or streams travel in the staged transfer as the renders do and the writer stores
+    ``result_sequence_disp/<name>_disp.png`` through the PNG route chosen.  The manifest names those files under 'disp' and the frames
+    whose map held a non-finite value (it became byte 0) under 'disp_nonfinite'.  Works with images=False too."""
 
-    png, ply_route, text, render, video, _k = "host", "host", "json", None, None, 0          # (what configure() starts from)
+    png, ply_route, text, render, video, disp, _k = "host", "host", "json", None, None, None, 0    # (what configure() starts from)
 
     def __init__(self, directory: str, names, depth: float = 10.0, images: bool = True, ply: bool | str = True, items: bool = True, level: int = 1,
                  threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, png: str = "host", text: str = "json",
-                 render: RenderCamera | None = None, video: Video | None = None, profile=None):
+                 render: RenderCamera | None = None, video: Video | None = None, profile=None, disp: str | None = None):
         import threading
         from concurrent.futures import ThreadPoolExecutor
 
@@ -1022,7 +1101,7 @@ class SequenceOutputs:
             raise ValueError("PNG compression level must be 0..9")
         if png is None or ply is None or text is None:                # (None leaves a choice as it is only in configure)
             raise ValueError(f"png, ply and text must be given, got {png!r}, {ply!r}, {text!r}")
-        self.configure(png, "host" if isinstance(ply, bool) else ply, text, render, video)
+        self.configure(png, "host" if isinstance(ply, bool) else ply, text, render, video, disp)
         self.directory, self.names, self.depth = directory, list(names), float(depth)
         self.images, self.ply, self.items, self.level = bool(images), bool(ply), bool(items), int(level)
         self.road_color, self.fence_color, self.alpha = tuple(road_color), tuple(fence_color), int(alpha)
@@ -1030,6 +1109,7 @@ class SequenceOutputs:
         self.img_dir, self.ply_dir = os.path.join(directory, SEQ_IMG_DIR), os.path.join(directory, SEQ_PLY_DIR)
         self.render_dir = os.path.join(directory, SEQ_RENDER_DIR)
         self.profile_dir = os.path.join(directory, SEQ_PROFILE_DIR)
+        self.disp_dir = os.path.join(directory, SEQ_DISP_DIR)
         self.profile = None
         self.set_profile(profile)
         for d, on in ((self.img_dir, self.images or self.items), (self.ply_dir, self.ply)):
@@ -1044,18 +1124,20 @@ class SequenceOutputs:
         self.recomputed: list[int] = []                               # global indices of the frames recomputed on bf16x3 (on_range='recompute')
         self.ply_fallback: list[int] = []                             # global indices of the frames ply="device" sent through rw_ply_bytes
         self.video_fallback: list[int] = []                           # global indices of the frames video route "device" encoded on the host
+        self.disp_nonfinite: list[int] = []                           # global indices of the frames whose disparity map held a non-finite value
         self._video_writer, self._video_next, self._video_turn = None, 0, threading.Condition()
 
     # ---------------------------------------------------------------- driver interface
-    def configure(self, png: str | None = None, ply: str | None = None, text: str | None = None, render=None, video=None):
+    def configure(self, png: str | None = None, ply: str | None = None, text: str | None = None, render=None, video=None, disp: str | None = None):
         """choose the routes described in the class docstring, before the first batch: ``png`` and ``ply`` "host" or "device", ``text`` "json"
-        or "draw", ``render`` a RenderCamera, ``video`` a Video; None leaves a choice as it is.  Nothing changes when the resulting
-        combination is refused."""
+        or "draw", ``render`` a RenderCamera, ``video`` a Video, ``disp`` "gray" or "plasma"; None leaves a choice as it is.  Nothing changes
+        when the resulting combination is refused."""
         png = self.png if png is None else png
         ply = self.ply_route if ply is None else ply
         text = self.text if text is None else text
         render = self.render if render is None else render
         video = self.video if video is None else video
+        disp = self.disp if disp is None else disp
         if png not in ("host", "device"):
             raise ValueError(f"png must be 'host' or 'device', got {png!r}")
         if ply not in ("host", "device") or isinstance(ply, bool):
@@ -1063,11 +1145,12 @@ class SequenceOutputs:
         _check_text(text)
         _check_render(render)
         _check_video(video)
+        _check_disp(disp)
         if self._k:
             raise RuntimeError("SequenceOutputs.configure after the first batch")
         if png == "device" and video is not None and video.route == "host":
             raise ValueError("Video(route='host') needs png='host': with png='device' no raw image reaches the host")
-        self.png, self.ply_route, self.text, self.render, self.video = png, ply, text, render, video
+        self.png, self.ply_route, self.text, self.render, self.video, self.disp = png, ply, text, render, video, disp
 
     def set_png(self, png: str):
         """where the result images are compressed: "host" or "device" (before the first batch)"""
@@ -1089,6 +1172,10 @@ class SequenceOutputs:
         """the Video the result images also become (before the first batch)"""
         self.configure(video=video)
 
+    def set_disp(self, disp: str):
+        """the colour map of the per-frame disparity images: "gray" or "plasma" (before the first batch)"""
+        self.configure(disp=disp)
+
     def set_profile(self, depths):
         """the depths of the per-frame depth profile, or None for no profile (before the first batch)"""
         if self._k:
@@ -1109,7 +1196,7 @@ class SequenceOutputs:
         return self.png == "host" and (self.images or self.video is not None and self.video.route == "host")
 
     def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None, ply_text=None, renders=None, render_streams=None,
-               video_streams=None, profile=None, f2f_profile=None):
+               video_streams=None, profile=None, f2f_profile=None, disp_images=None, disp_streams=None, disp_flags=None):
         """one batch: ``records`` u8 [n,104] (sd_rw_result), ``size`` = (h, w) of the original frames, ``images`` u8 [n,h,w,3] (the composed
         result images) or None, ``final`` = dict(xyz f32 [n,cap,3], rgb u8 [n,cap,3], n i32 [n]) (process_batch(want_final=True)'s
         road_final) or None, ``png_streams`` = (streams u8 [n,stride], sizes i64 [n]) of Engine.encode_png in place of ``images`` on the
@@ -1118,7 +1205,9 @@ class SequenceOutputs:
         ``render_streams`` = Engine.encode_png of them on the png="device" route), ``video_streams`` = (streams u8 [n,stride], sizes i64 [n], flags
         i32 [n]) of Engine.encode_jpeg with video= on its "device" route (beside ``images``, which a flagged frame is encoded from; its "host"
         route needs only ``images``), ``profile`` = u8 [n,D,48] of Engine.road_width_profile (process_batch(depths=)'s ``profile``) with
-        profile=, ``f2f_profile`` = u8 [n,D,64] beside it (optional: the dist_f2f column).  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
+        profile=, ``f2f_profile`` = u8 [n,D,64] beside it (optional: the dist_f2f column), ``disp_images`` = u8 [n,h,w,3] of
+        Engine.disparity_image with disp= (or ``disp_streams`` = Engine.encode_png of them on the png="device" route) and ``disp_flags`` =
+        its i32 [n] flags beside either (optional: the manifest's 'disp_nonfinite').  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
         tensors of every step)."""
         if self.manifest is not None:
             raise RuntimeError("SequenceOutputs.submit after close")
@@ -1138,6 +1227,8 @@ class SequenceOutputs:
             raise ValueError("SequenceOutputs: video route 'host' needs the raw images (submit(images=))")
         if self.profile is not None and (profile is None or tuple(profile.shape[:2]) != (n, len(self.profile))):
             raise ValueError("SequenceOutputs: profile= needs the [n, D, 48] records of Engine.road_width_profile (submit(profile=))")
+        if _check_disp(self.disp) is not None and (disp_streams if device_png else disp_images) is None:
+            raise ValueError("SequenceOutputs: disp= needs the images of Engine.disparity_image (submit(disp_images=); png='device': disp_streams=)")
         while len(self._jobs) >= 2:                                    # at most two batches in flight
             self._files.extend(self._jobs.pop(0).result())
         slot = self._k & 1
@@ -1150,7 +1241,10 @@ class SequenceOutputs:
                        render_streams=render_streams if self.render is not None and device_png else None,
                        video_streams=video_streams if device_video else None,
                        profile=profile if self.profile is not None else None,
-                       f2f_profile=f2f_profile if self.profile is not None else None)
+                       f2f_profile=f2f_profile if self.profile is not None else None,
+                       disp_images=disp_images if self.disp is not None and not device_png else None,
+                       disp_streams=disp_streams if self.disp is not None and device_png else None,
+                       disp_flags=disp_flags if self.disp is not None else None)
         self._k += 1
         self._jobs.append(self._batches.submit(self._write_batch, batch))
 
@@ -1197,6 +1291,9 @@ class SequenceOutputs:
         if self.profile is not None:
             manifest["profile_depths"] = list(self.profile)
             manifest["profile"] = [f for f in files if f.startswith(SEQ_PROFILE_DIR + os.sep)]
+        if self.disp is not None:
+            manifest["disp"] = [f for f in files if f.startswith(SEQ_DISP_DIR + os.sep)]
+            manifest["disp_nonfinite"] = named(self.disp_nonfinite)
         with open(self.manifest, "w") as f:
             json.dump(manifest, f, indent=1)
         if err is not None:
@@ -1213,12 +1310,15 @@ class SequenceOutputs:
         with st.behind(b.ev):
             host = _HostBatch(st.fixed("rec", b.records), images=st.fixed("img", b.images if self._images_travel else None),
                               renders=st.fixed("render", b.renders), profile=st.fixed("profile", b.profile),
-                              f2f_profile=st.fixed("f2f_profile", b.f2f_profile))
+                              f2f_profile=st.fixed("f2f_profile", b.f2f_profile), disp_images=st.fixed("disp", b.disp_images),
+                              disp_flags=st.fixed("disp_flags", b.disp_flags))
             counts = None if b.final is None else st.fixed("n", b.final["n"])
             if b.png_streams is not None:
                 host.png_sizes = st.fixed("png_sizes", b.png_streams[1])
             if b.render_streams is not None:
                 host.render_sizes = st.fixed("render_sizes", b.render_streams[1])
+            if b.disp_streams is not None:
+                host.disp_sizes = st.fixed("disp_sizes", b.disp_streams[1])
             if b.ply_text is not None:
                 host.ply_offsets, host.ply_flags = st.fixed("ply_offsets", b.ply_text[1]), st.fixed("ply_flags", b.ply_text[2])
             if b.video_streams is not None:
@@ -1228,6 +1328,8 @@ class SequenceOutputs:
                 host.png = st.rows("png", b.png_streams[0], host.png_sizes)
             if b.render_streams is not None:
                 host.render_png = st.rows("render_png", b.render_streams[0], host.render_sizes)
+            if b.disp_streams is not None:
+                host.disp_png = st.rows("disp_png", b.disp_streams[0], host.disp_sizes)
             if b.ply_text is not None:
                 host.ply_text = st.fixed("ply_text", b.ply_text[0][:int(host.ply_offsets[-1])])
             if b.final is not None:
@@ -1322,6 +1424,16 @@ class SequenceOutputs:
                 else:
                     assert host.renders.shape == (n, rh, rw, 3), (host.renders.shape, (n, rh, rw))
                     files.extend(write_png_batch(paths, host.renders, self.level, self.threads))
+            if self.disp is not None:
+                os.makedirs(self.disp_dir, exist_ok=True)
+                paths = [os.path.join(self.disp_dir, "{}_disp.png".format(nm)) for nm in names]
+                if host.disp_flags is not None:
+                    self.disp_nonfinite.extend(b.lo + i for i in range(n) if host.disp_flags[i] != 0)
+                if host.disp_png is not None:
+                    files.extend(write_png_streams(paths, host.disp_png, host.disp_sizes, h, w, self.threads))
+                else:
+                    assert host.disp_images.shape == (n, h, w, 3), (host.disp_images.shape, (n, h, w))
+                    files.extend(write_png_batch(paths, host.disp_images, self.level, self.threads))
             if self.video is not None:
                 frames = self._video_frames(b, host)
             files.extend(f.result() for f in futs)
