@@ -5,8 +5,12 @@ addressing and output rounding.
 
     python scripts/layer_check.py > profiles/layer_check_worst_ratios.txt
 
-writes one line per (engine, geometry, kernel label): the worst |delta| / bound and the layer it occurred in.  tests/test_gpu_layers.py imports
-CASES / run_case() from here and asserts what this prints.
+writes one line per (engine, geometry, kernel label): the worst |delta| / bound, the layer it occurred in and the output maps (height x width) the
+label ran on, and one comment line per case with its seconds.  tests/test_gpu_layers.py imports CASES / run_case() from here and asserts what this
+prints (but for the seconds: a case at a size that is no power of two may not take longer than the slowest 256 x 512 case of 8 frames, and since
+seconds compare within one run only, main() here checks that over its own run and a pytest run of single cases does not).  Beside the power-of-two frame sizes the cases hold 192 x 256, 320 x 192 and 384 x 128 (vgg), a pass fed 3 frames on a handle of 4 and the
+small-batch forms at 192 x 256, and fc6 / fc7 alone at 192 x 1024 with 16 frames (_odd_cases): partial row tiles behind full ones, maps 3 and 5 pixels high or wide, GEMMs whose M is no multiple of 256.
+Such a case names in need_at the kernel and the map extent it is there for, and fails where the planner routed the layer elsewhere.
 
 Reading a failure: "<layer> [<kernel label>] image i, y, x, channel c: |delta| / bound = r" names the layer, the kernel instantiation that ran it
 (SEMDEPTH_PROFILE_VERBOSE's label) and the worst element.  r <= 1 passes.  A ratio of a few units on many layers of one engine points at a format
@@ -25,11 +29,25 @@ KEEP, VERBOSE = "SEMDEPTH_KEEP_ACTIVATIONS", "SEMDEPTH_PROFILE_VERBOSE"
 FC_CHANNELS = np.r_[0:64, 2016:2080, 4032:4096]      # fc6 / fc7 at full size: the first 64, 64 across the tile boundary at 2048, the last 64
 
 
-def case(net, precision, H, W, frames, max_batch=None, small_batch=0, images="all", only=None, need=()):
+# predicates on the output extent (map height, map width) of a checked group, by name (need_at below)
+EXTENT = {
+    # full 16-row tiles and then a partial one (TH = 16 of conv_direct.hip, T3_TH of conv_direct3.hip)
+    "partial row tile after full ones": lambda h, w: h > 16 and h % 16 != 0,
+    # an upconv's output is twice its source
+    "source 3, 5 or 6 rows high": lambda h, w: h in (6, 10, 12),
+    "3 or 5 rows or columns": lambda h, w: h in (3, 5) or w in (3, 5),
+    "6 rows": lambda h, w: h == 6,
+}
+
+
+def case(net, precision, H, W, frames, max_batch=None, small_batch=0, images="all", only=None, need=(), need_at=()):
     """net: 'fcn8s' | 'resnet50' | 'vgg'.  images: 'all' or 'ends' (first and last frame's images).  only: check these layers alone (fc6 / fc7 at full
-    size).  need: kernel-label prefixes that must have run (a silently rerouted layer must not make the case pass)."""
+    size).  need: kernel-label prefixes that must have run (a silently rerouted layer must not make the case pass).  need_at: ((kernel-label
+    prefix, layer-name prefix, name of an EXTENT predicate), ...): a checked layer of that name, run by that kernel, must have an output map the
+    predicate holds for -- the proof that the case met the tile edge it is there for."""
+    assert all(e in EXTENT for _, _, e in need_at)
     return dict(net=net, precision=precision, H=H, W=W, frames=frames, max_batch=max_batch or frames, small_batch=small_batch, images=images,
-                only=only, need=tuple(need))
+                only=only, need=tuple(need), need_at=tuple(need_at))
 
 
 def case_id(c):
@@ -76,6 +94,79 @@ def _cases():
     # fc6 / fc7 alone at full size: the row-grouped, tap-skipping form of the phased GEMM block
     out.append(case("fcn8s", "bf16x3", 512, 1024, 8, images="ends", only=("fc6", "fc7"), need=("conv_dma3_kernel<2>", "conv_dma3_kernel<1>")))
     out.append(case("fcn8s", "f16x2", 512, 1024, 8, images="ends", only=("fc6", "fc7"), need=("conv_dma_hs_phased_kernel<2>", "conv_dma_hs_phased_kernel<1>")))
+    return out + _odd_cases()
+
+
+# Frame sizes that are no power of two (every case above has map heights 2^n: a 16-row tile covers a whole map or an exact number of tiles).
+#   192 x 256  maps 96x128, 48x64, 24x32, 12x16, 6x8, 3x4: the widths 128 / 64 / 32 keep the 3x3 layers on the direct kernels, the 24-row maps are one
+#              full row tile and a partial one (res3_x/conv2, iconv4, conv4_x and conv3_3 with its fused pool), the folded upconvs
+#              read 3- and 6-row sources (upconv6 / upconv5), fc6 runs on 6x8
+#   320 x 192  maps 160x96 .. 5x3: three tile columns at 96, the generic and GEMM routes below with M no multiple of 256, fc6 on 10x6, the
+#              deconv heads on one tile and a half
+#   384 x 128  vgg: the 3x1 deepest map and the folded upconv7 on it; the 24 / 12 / 6-row maps are 8 / 4 / 2 wide, so the GEMM routes run them (the
+#              direct kernel needs a width that is a multiple of 32 and stays on 192x64 and 96x32)
+_PART, _SRC = "partial row tile after full ones", "source 3, 5 or 6 rows high"
+# Per split engine, the kernel labels of the MI355X run behind profiles/layer_check_worst_ratios.txt:
+#   stem      the stem kernel
+#   direct    the direct 3x3 kernel that must have met a 24-row map
+#   upfold    monodepth: the kernel of the folded upconv6 / upconv5 (the GEMM-block form; the folded form of the DIRECT kernel starts at upconv4 on bf16x3)
+#   pool4     FCN-8s: the kernel of conv4_3 with its fused 2x2 pool, over the 24-row map
+_EDGE = {("resnet50", "bf16x3"): dict(stem="conv_stem_x3_kernel", direct="conv_direct_x3_kernel<2,2>", upfold="conv_dma3_kernel<2>"),
+         ("resnet50", "f16x2"): dict(stem="conv_stem_hs_kernel", direct="conv_direct_hs_kernel<2,2>", upfold="conv_dma_hs_kernel<2,4,2,2>"),
+         ("resnet50", "bf16x2"): dict(stem="conv_stem_kernel", direct="conv_direct_kernel<2,2>", upfold="conv_dma_kernel<2,4,2,2>"),
+         ("resnet50", "plan"): dict(stem="conv_stem_f16w_kernel", direct="conv_direct_f16x1_kernel<2,2>", upfold="conv_dma_f16x1_kernel<2,4,2,2>"),
+         ("resnet50", "mixed"): dict(stem="conv_stem_f16w_kernel", direct="conv_direct_f16w_kernel<2,2>", upfold="conv_dma_f16w_kernel<2,4,2,2>"),
+         ("fcn8s", "bf16x3"): dict(stem="conv_stem_x3_kernel", direct="conv_direct_x3_kernel<2,2>", pool4="conv_direct_x3_kernel<2,2>"),
+         ("fcn8s", "f16x2"): dict(stem="conv_stem_hs_kernel", direct="conv_direct_hs_kernel<2,2>", pool4="conv_direct_hs_kernel<2,2>"),
+         ("fcn8s", "bf16x2"): dict(stem="conv_stem_kernel", direct="conv_direct_kernel<2,2>", pool4="conv_direct_kernel<2,2>"),
+         ("fcn8s", "plan"): dict(stem="conv_stem_kernel", direct="conv_direct_f16w_x2_kernel<2,2>", pool4="conv_direct_f16x1_kernel<2,2>")}
+
+
+def _odd_cases():
+    out = []
+
+    def edge(n, p, splitc=None):
+        """need / need_at of a 192 x 256 case.  splitc: the label that runs the 24-row direct layers instead (small-batch level 2)"""
+        if p == "f32":          # (one kernel, conv_igemm, for every layer: nothing to be rerouted)
+            return dict(need=(), need_at=())
+        e = _EDGE[(n, p)]
+        direct = splitc or e["direct"]
+        at = [(direct, "", _PART)]
+        if n == "resnet50":     # res3_x/conv2 and iconv4 are the 24-row direct layers; upconv6 / upconv5 read the 3x4 and the 6x8 map
+            at += [(e["upfold"], "dec/upconv6", _SRC), (e["upfold"], "dec/upconv5", _SRC)]
+            if p == "bf16x3":   # (128 outputs: the folded form of the DIRECT kernel, on a 24-row output)
+                at += [("conv_direct_x3_fold_kernel", "dec/upconv4", _PART)]
+        else:
+            at += [(splitc or e["pool4"], "conv4_3+pool4", _PART)]
+        return dict(need=(e["stem"], direct), need_at=tuple(at))
+
+    for n in ("resnet50", "fcn8s"):
+        for p in ("f32", "bf16x3", "f16x2", "bf16x2", "plan") + (("mixed",) if n == "resnet50" else ()):
+            out.append(case(n, p, 192, 256, 1, **edge(n, p)))
+        for p in ("f32", "bf16x3", "f16x2", "plan"):      # (any kernel: the 96- and 24-wide maps leave the direct kernels; res5 is 5x3)
+            out.append(case(n, p, 320, 192, 1, need_at=(("", "enc/res5_3/conv3", "3 or 5 rows or columns"),) if n == "resnet50" else ()))
+    for p in ("f16x2", "bf16x3"):
+        out.append(case("vgg", p, 384, 128, 1, need_at=(("", "enc/conv7b", "3 or 5 rows or columns"),
+                                                        (_EDGE[("resnet50", p)]["upfold"], "dec/upconv7", _SRC))))
+    # a pass fed 3 frames on a handle of 4.  run_case first runs a full pass of 4 OTHER frames on the handle, so that the slots behind the fed
+    # images hold another image's activations and not the zeros of a fresh arena (zeros are what a padding row holds anyway: a kernel that counts
+    # the handle's images as real would pass on them); only the fed images are read back and compared
+    for n in ("resnet50", "fcn8s"):
+        for p in ("f16x2", "bf16x3"):
+            out.append(case(n, p, 192, 256, 3, max_batch=4, **edge(n, p)))
+    # the small-batch forms, whose partial last row tile had only run at 256 x 512 ("Rows of a partial last tile are not stored")
+    for n in ("fcn8s", "resnet50"):
+        e = edge(n, "f16x2")
+        out.append(case(n, "f16x2", 192, 256, 1, small_batch=1, need=e["need"] + ("conv_splitk_hs_kernel", "splitk_reduce_kernel"), need_at=e["need_at"]))
+        e = edge(n, "f16x2", splitc="conv_direct_splitc_hs_kernel")      # level 2 runs the 24-row direct layers split along their chunk axis
+        out.append(case(n, "f16x2", 192, 256, 1, small_batch=2, need=e["need"] + ("conv_splitk_hs_kernel", "splitc_reduce_kernel"), need_at=e["need_at"]))
+    # fc6 on a 6-row map in its row-grouped, tap-skipping form (at 192 x 256 and 320 x 192 fc6 / fc7 are too small for the phased GEMM block and run on
+    # conv_split_* / conv_splitk: the block wants 128 tiles of a full pass, a row group 256 / Wout images).  192 x 1024 with 16 frames: the 6 x 32 map,
+    # two groups of 8 images per output row, every output row within reach of a padding row of the 7 x 7 taps
+    out.append(case("fcn8s", "bf16x3", 192, 1024, 16, images="ends", only=("fc6", "fc7"), need=("conv_dma3_kernel<2>", "conv_dma3_kernel<1>"),
+                    need_at=(("conv_dma3_kernel<2>", "fc6", "6 rows"),)))
+    out.append(case("fcn8s", "f16x2", 192, 1024, 16, images="ends", only=("fc6", "fc7"), need=("conv_dma_hs_phased_kernel<2>", "conv_dma_hs_phased_kernel<1>"),
+                    need_at=(("conv_dma_hs_phased_kernel<2>", "fc6", "6 rows"),)))
     return out
 
 
@@ -108,8 +199,10 @@ def _frames(B, H, W, seed):
 
 
 def run_case(c, log=None):
-    """-> dict(rows=[(group name, kernel label, oracle.layers.Worst)], uncovered=[op names], labels={op: label}, missing=[needed families that did
-    not run], seconds).  Sets (and restores) the two environment switches an engine latches when it is created."""
+    """-> dict(rows=[(group name, kernel label, oracle.layers.Worst)], extents=[(group name, kernel label, (output map height, width))] (of a
+    conv with its fused 2x2 pool: the map the conv runs on, twice the stored one),
+    uncovered=[op names], labels={op: label}, missing=[needed families that did not run], unmet=[need_at requirements no checked layer met],
+    seconds).  Sets (and restores) the two environment switches an engine latches when it is created."""
     from oracle import layers as LY
     from semantic_depth_amd import _lib as L, weights as Wt
     from semantic_depth_amd.engine import Engine
@@ -132,8 +225,17 @@ def run_case(c, log=None):
     layers = LY.fcn8s_layers() if fcn else LY.monodepth_layers(enc)
     eng.load_weights(net_id, w)
     fr = _frames(B, H, W, seed=H + W + B)
-    assert B == 1 or not np.array_equal(fr[0], fr[-1])
+    assert all(not np.array_equal(fr[i], fr[j]) for i in range(B) for j in range(i))      # (a mixed-up image must show)
     dev = torch.from_numpy(fr).cuda()
+    if c["max_batch"] > B:
+        # a partial pass: an earlier FULL pass of other frames leaves its activations in every image slot of every tensor (each has memory of its
+        # own under KEEP), those behind the B fed images included
+        other = _frames(c["max_batch"], H, W, seed=H + W + B + 1)
+        assert all(not np.array_equal(o, f) for o in other for f in fr)
+        other = torch.from_numpy(other).cuda()
+        eng.fcn8s_forward(other) if fcn else eng.monodepth_forward(other)
+        stale = eng.net_tensor(net_id, "conv1_1" if fcn else "enc/conv1")      # (that pass's last image is there to be read behind the fed ones)
+        assert stale.shape[0] == (1 if fcn else 2) * c["max_batch"] and float(stale[-1].abs().max()) > 0
     eng.profile(True)
     logits = None
     if fcn:
@@ -173,6 +275,7 @@ def run_case(c, log=None):
                     raise
                 cache[name] = None
                 return None
+        assert t.shape[0] == nimg, (case_id(c), name, tuple(t.shape))      # the images of THIS pass, not those the handle has room for
         t = t[torch.as_tensor(sel, device=t.device)].cpu()
         if name == "input_pre":
             t = t[..., :3]                     # (the f32 engine stores the zero fourth channel of its float4 gathers)
@@ -181,7 +284,7 @@ def run_case(c, log=None):
 
     widths, h_, w_ = {"frames": W}, {}, {}
     numerics = None
-    rows, covered, pending = [], set(), []
+    rows, extents, covered, pending = [], [], set(), []
     scale = None if fcn else LY.mono_input_scale(plan)
     for i, Lr in enumerate(layers):
         if c["only"] and Lr.name not in c["only"]:
@@ -224,12 +327,16 @@ def run_case(c, log=None):
         label = " | ".join(labels[o] for o in ops) if ops else {"pool2": "maxpool2", "pool3z": "maxpool3z", "deconv": "deconv16s8_head",
                                                                "deconv_add": "deconv4s2_add", "conv": "conv_smalln"}.get(Lr.kind, Lr.kind)
         rows.append((wst.layer, label, wst))
+        hw = tuple(int(v) * (2 if len(group) == 2 and Lr.kind == "pool2" else 1) for v in got.shape[2:])      # (a fused pool: the conv's own map)
+        extents.append((wst.layer, label, hw))
         if log:
-            log(f"  {wst.layer:34s} {label:44s} {wst.ratio:9.4f}  at {wst.index}")
+            log(f"  {wst.layer:34s} {label:44s} {hw[0]:4d}x{hw[1]:<4d} {wst.ratio:9.4f}  at {wst.index}")
     assert not pending, [g.name for g in pending]
     all_labels = " ".join(labels.values())
-    res = dict(rows=rows, uncovered=sorted(set(labels) - covered), labels=labels, missing=[f for f in c["need"] if f not in all_labels],
-               seconds=time.time() - t0, plan=plan)
+    unmet = [f"{lab} on a layer '{pre}*' with an output map of: {e}" for lab, pre, e in c["need_at"]
+             if not any(lab in label and name.startswith(pre) and EXTENT[e](*hw) for name, label, hw in extents)]
+    res = dict(rows=rows, extents=extents, uncovered=sorted(set(labels) - covered), labels=labels, missing=[f for f in c["need"] if f not in all_labels],
+               unmet=unmet, seconds=time.time() - t0, plan=plan)
     eng.close()
     return res
 
@@ -240,31 +347,50 @@ def failure_lines(c, res):
 
 
 def table_lines(c, res):
-    """one line per kernel label of the case: the worst ratio and the layer it occurred in"""
-    worst = {}
+    """one line per kernel label of the case: the worst ratio, the layer it occurred in, and the output maps (height x width) the label ran on"""
+    worst, maps = {}, {}
     for name, label, w in res["rows"]:
         if label not in worst or w.ratio > worst[label][0]:
             worst[label] = (w.ratio, name)
+    for name, label, hw in res["extents"]:
+        maps.setdefault(label, set()).add(hw)
     return [f"{c['precision']:7s} {c['net']:9s} {c['H']}x{c['W']} B={c['frames']}/{c['max_batch']}" + (f" small_batch={c['small_batch']}" if c["small_batch"] else "") +
-            f"  {label:60s} {r:8.4f}  {name}" for label, (r, name) in sorted(worst.items())]
+            f"  {label:60s} {r:8.4f}  {name:34s} maps " + " ".join(f"{h}x{w}" for h, w in sorted(maps[label], reverse=True))
+            for label, (r, name) in sorted(worst.items())]
+
+
+def _is_256x512_of_8_frames(c):
+    """the cases whose slowest sets the time a case at a size that is no power of two may take (main)"""
+    return (c["H"], c["W"], c["frames"]) == (256, 512, 8)
 
 
 def main():
     torch.set_num_threads(min(os.cpu_count() or 1, 16))
     print("# worst |delta| / bound per (engine, geometry, kernel label) and the layer it occurred in; scripts/layer_check.py on the MI355X")
-    per_engine, bad = {}, []
+    per_engine, per_engine_odd, bad, secs = {}, {}, [], {}
     for c in CASES:
         res = run_case(c)
         for line in table_lines(c, res):
             print(line, flush=True)
         top = max(res["rows"], key=lambda r: r[2].ratio)
-        if top[2].ratio > per_engine.get(c["precision"], (0, "", ""))[0]:
-            per_engine[c["precision"]] = (top[2].ratio, case_id(c), top[0] + " [" + top[1] + "]")
+        odd = c["H"] & (c["H"] - 1) != 0      # a frame height that is no power of two
+        for table in (per_engine,) + ((per_engine_odd,) if odd else ()):
+            if top[2].ratio > table.get(c["precision"], (0, "", ""))[0]:
+                table[c["precision"]] = (top[2].ratio, case_id(c), top[0] + " [" + top[1] + "]")
         bad += failure_lines(c, res) + [f"{case_id(c)}: uncovered op {o}" for o in res["uncovered"]] + [f"{case_id(c)}: {f} did not run" for f in res["missing"]]
-        print(f"# {case_id(c)}: {len(res['rows'])} layers, {len(res['uncovered'])} uncovered ops, {res['seconds']:.1f} s", file=sys.stderr, flush=True)
+        bad += [f"{case_id(c)}: no {u}" for u in res["unmet"]]
+        secs[case_id(c)] = (res["seconds"], odd, _is_256x512_of_8_frames(c))
+        print(f"# {case_id(c)}: {len(res['rows'])} layers, {len(res['uncovered'])} uncovered ops, {res['seconds']:.1f} s", flush=True)
     print("# worst line per engine")
     for p, (r, cid, where) in per_engine.items():
         print(f"# {p:7s} {r:8.4f}  {cid}  {where}")
+    print("# worst line per engine at the frame sizes that are no power of two")
+    for p, (r, cid, where) in per_engine_odd.items():
+        print(f"# {p:7s} {r:8.4f}  {cid}  {where}")
+    limit = max(s for s, _, b8 in secs.values() if b8)
+    slowest = max((s, cid) for cid, (s, odd, _) in secs.items() if odd)
+    print(f"# slowest 256x512 B8 case {limit:.1f} s; slowest case at a size that is no power of two {slowest[0]:.1f} s ({slowest[1]})")
+    bad += [f"{cid}: {s:.1f} s, longer than the slowest 256x512 B8 case ({limit:.1f} s)" for cid, (s, odd, _) in secs.items() if odd and s > limit]
     print("# " + ("every layer inside its bound, no op uncovered" if not bad else "OUTSIDE:"))
     for b in bad:
         print("# " + b)

@@ -8,7 +8,10 @@ that were loaded, and compared element by element with the GPU's stored output. 
 of oracle/layers.py -- accumulation, weight planes, dropped products, output format, activation -- derived from csrc/split_fmt.hpp and not fitted.
 
 Every op of the plan is covered, alone or inside a named composite (a conv with its fused 2x2 pool; dec/tail1 = upconv1 -> iconv1 -> disp1): the count of
-uncovered ops is asserted to be zero, and the kernel families a case claims to cover are asserted from the profile labels."""
+uncovered ops is asserted to be zero, and the kernel families a case claims to cover are asserted from the profile labels.  The cases at frame sizes
+that are no power of two also assert WHERE a kernel ran (need_at: the direct kernel on a 24-row map, the folded upconv on a 3- and a 6-row source):
+the printed table carries the output maps of every kernel label.  (That no such case takes longer than the slowest 256x512 case of 8 frames is
+checked by scripts/layer_check.py over its own run: seconds compare within one run only, and pytest may run a single case.)"""
 import importlib.util
 import os
 
@@ -41,5 +44,7 @@ def test_every_layer_alone_is_within_its_derived_bound(case):
     assert res["rows"]
     assert len(res["uncovered"]) == 0, ("ops of the plan that no layer check covered", res["uncovered"])
     assert not res["missing"], ("kernel families the case claims to cover did not run", res["missing"], sorted(set(res["labels"].values())))
+    assert not res["unmet"], ("the case did not meet the tile edge it is there for: no", res["unmet"],
+                              sorted({(label, hw) for _, label, hw in res["extents"]}))
     bad = LC.failure_lines(case, res)
     assert not bad, "\n" + "\n".join(bad)
