@@ -771,6 +771,73 @@ sd_status sd_f2f_profile(sd_handle* h, const sd_rw_result* road_dev, const sd_f2
 sd_status sd_f2f_profile_host(const sd_rw_result* road, const sd_f2f_result* f2f, const double* depths, int D,
                               sd_f2f_depth_result* results_host /* [D] */);
 
+/* ---------------------------------------------------------------- measurement lines in the result images (opt-in)
+ * seq:330-333, step "8.A Project the 3D points that define the line to the image plane": two calls of print_line_on_image, commented out
+ * because the function was never written.  The project draws them -- the measured road-width line, the fence-to-fence line and, with a
+ * depth profile, the road's left and right edge along the profile and a rung per depth -- with a rule of its own, stated once, for host and
+ * device, in semantic_depth_amd/csrc/overlay_rule.hpp.  The reference gives only the two colours (0,0,255) and (0,255,0); the edge colour and
+ * the thicknesses are the project's choice.  No pixel identity with cv2.line is claimed; no anti-aliasing; a segment is not clipped at the
+ * near plane but skipped.
+ *   project   the inverse of make_Q / reprojectImageTo3D, in doubles, no contraction, in this order: cx, cy, f rounded to float32 (as the
+ *             Q matrix rounds them) and promoted; zn = -Z, the point is dropped unless zn > 0 (a NaN fails); s = f / zn; xn = cx + X s,
+ *             yn = cy - Y s (network pixels, centres at integers); xo = (xn + 0.5) ((double)dst_w / net_w) - 0.5 and yo likewise with the
+ *             heights (the pixel-centre alignment of cv2.resize); dropped unless |xo| <= SD_OVERLAY_MAX_COORD and |yo| <=
+ *             SD_OVERLAY_MAX_COORD (before any cast); q = (int32)floor(v * 256 + 0.5), in 1/256 pixel.
+ *   slots     a frame with D profile depths has 4 D + 2 slots (at most SD_OVERLAY_MAX_SEGS); slot order is paint order, the highest valid
+ *             slot that covers a pixel gives its colour.  Slot i (i < D - 1): the left edge, profile[i].left_pt -> profile[i + 1].left_pt in
+ *             the order the depths were given, when both entries are found (slot D - 1 is never valid).  Slot D + i: the same on right_pt.
+ *             Slot 2 D + i: the road rung of depth i, left_pt -> right_pt, when found.  Slot 3 D + i: the fence rung of depth i from the
+ *             sd_f2f_depth_result points, when ok (only with fence profile records).  Slot 4 D: the record's road-width line, when found.
+ *             Slot 4 D + 1: the fence record's line, when ok (only with fence records).  A slot whose segment exists but has a dropped end
+ *             point is not drawn and sets bit 0 of the frame's flag.
+ *   style     sd_overlay_style: rw_bgr colours the road rungs and the road-width line, f2f_bgr the fence rungs and the fence line, edge_bgr
+ *             the two edges (the image's channel order); thickness 1..SD_OVERLAY_MAX_THICKNESS for the two record lines,
+ *             profile_thickness likewise for everything from the profile; clip_top 0..dst_h: rows above it are never painted (the banner
+ *             stays clean); reserved = 0.
+ *   paint     sd_text_draw_host's rule on the segment: pixel (px, py), centre (256 px, 256 py), is painted iff its squared distance to the
+ *             segment is <= (128 thickness)^2, in exact integers; a zero-length segment is a disc.  A pixel no slot paints is never written.
+ * flags      bit 0: a segment of the frame was skipped for a dropped end point. */
+#define SD_OVERLAY_MAX_SEGS (4 * SD_PROFILE_MAX_DEPTHS + 2)
+#define SD_OVERLAY_MAX_COORD 32768
+#define SD_OVERLAY_MAX_THICKNESS 32
+typedef struct {
+    uint8_t rw_bgr[3], f2f_bgr[3], edge_bgr[3];
+    uint8_t reserved[3];               /* 0 */
+    int32_t thickness, profile_thickness, clip_top;
+} sd_overlay_style;                    /* 24 bytes */
+typedef struct {
+    int32_t ax, ay, bx, by;            /* the end points in 1/256 pixel */
+    uint8_t bgr[3];
+    uint8_t thickness;
+} sd_overlay_segment;                  /* 20 bytes */
+/* the device workspace sd_overlay_draw needs for B frames with D profile depths; 0 for B outside 1..65535 or D outside
+ * 0..SD_PROFILE_MAX_DEPTHS */
+size_t sd_overlay_workspace_bytes(int B, int D);
+/* DEVICE: draws the slots of frame b -- from records_dev[b], f2f_dev[b] (nullable: no slot 4 D + 1), rw_profile_dev[b][0 .. D) (needed when
+ * D > 0) and f2f_profile_dev[b][0 .. D) (nullable: no fence rungs), all read on the device -- into dst_dev u8 [B,dst_h,dst_w,3] IN PLACE; only
+ * painted pixels are written; flags_dev i32 [B] receives every frame's flag.  cams_host[b] (HOST pointer; cx, cy and f are used) is
+ * frame b's camera at the network size net_h x net_w; the cameras are staged through the workspace.  Two launches on `stream` (one
+ * workgroup per frame projects the end points and writes every slot, its clipped pixel box and the union of the boxes; 64 x 16 pixel
+ * tiles inside that union keep the slots whose box meets them and test their pixels from the last slot to the first), no atomics, no host
+ * synchronisation; every workspace byte that is read was written by the same call.  The handle need not be bound.  SD_ERR_INVALID, nothing
+ * launched: a null pointer (but the three nullable ones), B outside 1..65535, an extent outside 1..16384, D outside
+ * 0..SD_PROFILE_MAX_DEPTHS, D > 0 without rw_profile_dev, a style outside its caps, a camera whose cx, cy or f is not finite in float32,
+ * workspace_bytes below sd_overlay_workspace_bytes(B, D), a workspace that is not 16-byte aligned, records that are not 8-byte or flags
+ * that are not 4-byte aligned. */
+sd_status sd_overlay_draw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int dst_w, int net_h, int net_w, const sd_camera* cams_host,
+                          const sd_rw_result* records_dev, const sd_f2f_result* f2f_dev, const sd_rw_depth_result* rw_profile_dev,
+                          const sd_f2f_depth_result* f2f_profile_dev, int D, const sd_overlay_style* style_host, int32_t* flags_dev,
+                          void* workspace_dev, size_t workspace_bytes, void* stream);
+/* HOST: the valid segments of one frame in slot order, as data: segs_out[0 .. *n_out), *n_out <= 4 D + 2 (segs_out holds that many), and the
+ * frame's flag.  SD_ERR_INVALID, nothing written: as above. */
+sd_status sd_overlay_segments_host(const sd_rw_result* record, const sd_f2f_result* f2f, const sd_rw_depth_result* rw_profile,
+                                   const sd_f2f_depth_result* f2f_profile, int D, const sd_camera* cam, int net_h, int net_w, int dst_h, int dst_w,
+                                   const sd_overlay_style* style, sd_overlay_segment* segs_out, int* n_out, int32_t* flag_out);
+/* HOST: the paint rule for any n >= 0 segments on img_host u8 [h,w,3], in list order (a later segment paints over an earlier one), rows
+ * above clip_top untouched.  SD_ERR_INVALID, nothing drawn: a null pointer, an extent outside 1..16384, clip_top outside 0..h, a segment
+ * with a thickness outside 1..SD_OVERLAY_MAX_THICKNESS or a coordinate beyond 256 SD_OVERLAY_MAX_COORD in magnitude. */
+sd_status sd_overlay_draw_host(uint8_t* img_host, int h, int w, const sd_overlay_segment* segs, int n, int clip_top);
+
 /* ---------------------------------------------------------------- scoring the segmentation (fcn8s/fcn.py test mode, FCN.inference :384-492)
  * The test mode resizes the frame AND the label image with scipy.misc.imresize(img, image_shape) (:408, :412), which for uint8 input is
  * PIL.Image.resize((W, H), BILINEAR) -- not the cv2.resize cubic of sd_resize_cubic_u8 -- and scores argmax against

@@ -19,6 +19,7 @@ SD_PLY_ROW_CAP, SD_PLY_HEADER_CAP, SD_PLY_LINE_ROWS = 69, 209, 1001
 SD_TEXT_MAX_BYTES, SD_TEXT_MAX_SEGS, SD_TEXT_MAX_ITEMS, SD_TEXT_MAX_SCALE_Q8, SD_TEXT_MAX_THICKNESS, SD_TEXT_MAX_ORG = 64, 32, 4, 4096, 32, 32768
 SD_RENDER_MAX_EXTENT, SD_RENDER_MAX_POINT = 16384, 16
 SD_PROFILE_MAX_DEPTHS = 256
+SD_OVERLAY_MAX_SEGS, SD_OVERLAY_MAX_COORD, SD_OVERLAY_MAX_THICKNESS = 4 * 256 + 2, 32768, 32
 SD_SEG_CELLS = 10      # sd_seg_confusion: counters per frame, the 3 x 3 matrix and the predictions above 2
 SD_CMAP_GRAY, SD_CMAP_PLASMA = 0, 1      # sd_disp_image: the two colour maps
 SD_PREC_F32, SD_PREC_BF16X2, SD_PREC_MIXED, SD_PREC_PLAN, SD_PREC_BF16X3, SD_PREC_F16X2 = 0, 1, 2, 3, 4, 5
@@ -69,6 +70,15 @@ class sd_rw_depth_result(C.Structure):
 
 class sd_f2f_depth_result(C.Structure):
     _fields_ = [("dist", C.c_double), ("left_pt", C.c_double * 3), ("right_pt", C.c_double * 3), ("ok", C.c_int32), ("reserved", C.c_int32)]
+
+
+class sd_overlay_style(C.Structure):
+    _fields_ = [("rw_bgr", C.c_uint8 * 3), ("f2f_bgr", C.c_uint8 * 3), ("edge_bgr", C.c_uint8 * 3), ("reserved", C.c_uint8 * 3),
+                ("thickness", C.c_int32), ("profile_thickness", C.c_int32), ("clip_top", C.c_int32)]
+
+
+class sd_overlay_segment(C.Structure):
+    _fields_ = [("ax", C.c_int32), ("ay", C.c_int32), ("bx", C.c_int32), ("by", C.c_int32), ("bgr", C.c_uint8 * 3), ("thickness", C.c_uint8)]
 
 
 class sd_profile_bucket(C.Structure):
@@ -177,6 +187,12 @@ SIGNATURES = {
     "sd_text_items_rw_host": (C.c_int, [C.POINTER(sd_rw_result), C.c_char_p, C.c_int, C.c_int, C.POINTER(sd_text_item), C.POINTER(C.c_int)]),
     "sd_text_draw_host": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(sd_text_item), C.c_int]),
     "sd_text_glyph": (C.c_int, [C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "sd_overlay_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "sd_overlay_draw": (C.c_int, [_H, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(sd_camera), _P, _P, _P, _P, C.c_int,
+                                  C.POINTER(sd_overlay_style), _P, _P, C.c_size_t, _P]),
+    "sd_overlay_segments_host": (C.c_int, [C.POINTER(sd_rw_result), _P, _P, _P, C.c_int, C.POINTER(sd_camera), C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(sd_overlay_style), C.POINTER(sd_overlay_segment), C.POINTER(C.c_int), C.POINTER(C.c_int32)]),
+    "sd_overlay_draw_host": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(sd_overlay_segment), C.c_int, C.c_int]),
     "sd_render_workspace": (C.c_int, [C.c_int, C.c_int, C.POINTER(sd_render_camera), C.POINTER(C.c_size_t)]),
     "sd_render_rw": (C.c_int, [_H, _P, _P, _P, C.c_int, C.c_int, _P, C.POINTER(sd_render_camera), _P, _P, _P, C.c_size_t, _P]),
     "sd_render_rw_host": (C.c_int, [_P, _P, C.c_int, C.POINTER(sd_rw_result), C.POINTER(sd_render_camera), _P, C.POINTER(C.c_int32)]),

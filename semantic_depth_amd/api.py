@@ -310,6 +310,7 @@ class FrameProcessor:
             rows = Engine.profile_records(out["profile"])[0]
             f2p = Engine.f2f_profile_records(out["f2f_profile"])[0] if out.get("f2f_profile") is not None else None
             res["profile"] = []
+            res["profile_records"], res["f2f_profile_records"] = rows, f2p      # (the end points: save_frame_outputs(lines=) draws them)
             for i, dv in enumerate(self.depths):
                 r = rows[i]
                 row = dict(depth=dv, found=int(r["found"]), width=float(r["width"]), x_left=float(r["x_left"]), x_right=float(r["x_right"]),

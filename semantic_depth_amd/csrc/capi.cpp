@@ -19,6 +19,7 @@
 #include "png_in_gpu.hpp"
 #include "ply_gpu.hpp"
 #include "text_gpu.hpp"
+#include "overlay_gpu.hpp"
 #include "render_gpu.hpp"
 #include "rw_profile_gpu.hpp"
 #include "seg_eval_gpu.hpp"
@@ -54,6 +55,7 @@ struct sd_handle {
     size_t o_splitk = 0;            // workspace: the partial sums of the largest split layer (0 bytes without the switch)
     std::vector<CamDev> cams_stage;
     std::vector<CamDev> sweep_stage;     // sd_fuse_backproject_sweep: the [T][B] records of the last call (source of its upload)
+    std::vector<OverlayCamDev> overlay_stage;    // sd_overlay_draw: the cameras of the last call (source of its upload)
     std::vector<sdrwp::Window> rwp_stage;    // sd_road_width_profile: the sorted windows of the last call (source of its upload)
     sdpil::Windows pil_x, pil_y;             // sd_resize_pil_bilinear_u8: the windows of the last call (source of its uploads)
     sdpil::Windows disp_x, disp_y;           // sd_disp_image: the same for its resample
@@ -931,6 +933,46 @@ sd_status sd_text_draw_rw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int 
         return fail(h, SD_ERR_INVALID, "sd_text_draw_rw: workspace_dev must be 16-byte, records_dev 8-byte aligned");
     HIPCHK(h, launch_text_draw_rw(dst_dev, B, dst_h, dst_w, records_dev, reinterpret_cast<const uint8_t*>(depth_text), (int)dlen,
                                   static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
+    return SD_OK;
+}
+
+size_t sd_overlay_workspace_bytes(int B, int D) {
+    return B < 1 || B > 65535 || D < 0 || D > sdoverlay::kMaxDepths ? 0 : overlay_workspace_bytes(B, D);
+}
+
+sd_status sd_overlay_draw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int dst_w, int net_h, int net_w, const sd_camera* cams_host,
+                          const sd_rw_result* records_dev, const sd_f2f_result* f2f_dev, const sd_rw_depth_result* rw_profile_dev,
+                          const sd_f2f_depth_result* f2f_profile_dev, int D, const sd_overlay_style* style_host, int32_t* flags_dev,
+                          void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!h || !dst_dev || !cams_host || !records_dev || !style_host || !flags_dev || !workspace_dev)
+        return fail(h, SD_ERR_INVALID, "sd_overlay_draw: null pointer");
+    if (B < 1 || B > 65535) return fail(h, SD_ERR_INVALID, "sd_overlay_draw: B must be 1..65535");
+    if (!sdoverlay::sizes_ok(net_h, net_w, dst_h, dst_w)) return fail(h, SD_ERR_INVALID, "sd_overlay_draw: extents must be 1..16384");
+    if (D < 0 || D > sdoverlay::kMaxDepths || (D > 0 && !rw_profile_dev))
+        return fail(h, SD_ERR_INVALID, "sd_overlay_draw: D must be 0..256 and D > 0 needs rw_profile_dev");
+    const sd_overlay_style style = *style_host;       // read once, here: the kernels get this copy by value
+    if (!sdoverlay::style_ok(style, dst_h))
+        return fail(h, SD_ERR_INVALID, "sd_overlay_draw: style outside the caps (thicknesses 1..32, clip_top 0..dst_h)");
+    for (int b = 0; b < B; ++b)
+        if (!sdoverlay::camera_ok(cams_host[b])) return fail(h, SD_ERR_INVALID, "sd_overlay_draw: a camera's cx, cy or f is not finite in float32");
+    // every index the kernels form follows from B, D, the extents and this capacity: nothing is launched otherwise
+    if (workspace_bytes < overlay_workspace_bytes(B, D))
+        return fail(h, SD_ERR_INVALID, "sd_overlay_draw: workspace smaller than sd_overlay_workspace_bytes reports");
+    if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(records_dev) & 7) ||
+        (reinterpret_cast<uintptr_t>(f2f_dev) & 7) || (reinterpret_cast<uintptr_t>(rw_profile_dev) & 7) ||
+        (reinterpret_cast<uintptr_t>(f2f_profile_dev) & 7) || (reinterpret_cast<uintptr_t>(flags_dev) & 3))
+        return fail(h, SD_ERR_INVALID, "sd_overlay_draw: workspace_dev must be 16-byte, the records 8-byte, flags_dev 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    OverlayArgs a{};
+    a.dst = dst_dev; a.records = records_dev; a.f2f = f2f_dev; a.rw_profile = D > 0 ? rw_profile_dev : nullptr;
+    a.f2f_profile = D > 0 ? f2f_profile_dev : nullptr; a.flags = flags_dev; a.style = style;
+    a.B = B; a.D = D; a.h = dst_h; a.w = dst_w; a.net_h = net_h; a.net_w = net_w;
+    overlay_layout(a, static_cast<uint8_t*>(workspace_dev));
+    h->overlay_stage.resize((size_t)B);
+    for (int b = 0; b < B; ++b)
+        h->overlay_stage[(size_t)b] = OverlayCamDev{(double)(float)cams_host[b].cx, (double)(float)cams_host[b].cy, (double)(float)cams_host[b].f, 0.0};
+    HIPCHK(h, hipMemcpyAsync(a.cams, h->overlay_stage.data(), sizeof(OverlayCamDev) * (size_t)B, hipMemcpyHostToDevice, s));
+    HIPCHK(h, launch_overlay_draw(a, s));
     return SD_OK;
 }
 

@@ -96,7 +96,7 @@ def run_sequence(load_frames, n_frames: int, step, batch: int = 32, group=None, 
 
 def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", workers: int = 0, outputs=None, jpeg: str = "host",
                        engine=None, png: str | None = None, ply: str | None = None, text: str | None = None, render=None, video=None,
-                       png_in: str | None = None, disp: str | None = None) -> torch.Tensor:
+                       png_in: str | None = None, disp: str | None = None, lines=None) -> torch.Tensor:
     """run_sequence on FILES (semantic_depth_cityscapes_sequence.py:689-701 reads ``sorted(glob(input_folder))`` frame by frame): rank r
     decodes ONLY its shard of the sorted list -- frame_io.FrameFeeder: one native call per batch into pinned staging, upload one batch
     ahead, ``workers`` decode threads (default: this rank's share of the node's CPUs, frame_io.default_decode_workers) -- and hands every
@@ -111,7 +111,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     (FrameFeeder.entropy_fallback names them); the frames are the same bytes on all three.
     ``png_in`` (None = "host" | "device") is the feeder's ``png=`` (``png`` here already names the output writer): with "device" the PNG
     frames are only inflated on the host and their scanlines reconstructed on the GPU by ``engine``; the frames are the same bytes.
-    ``png``, ``ply``, ``text``, ``render``, ``video``, ``disp`` (None = what the SequenceOutputs was built with) go to SequenceOutputs.configure
+    ``png``, ``ply``, ``text``, ``render``, ``video``, ``disp``, ``lines`` (None = what the SequenceOutputs was built with) go to SequenceOutputs.configure
     before the first batch: the choices are described there, and what the step of make_engine_step does for each -- all but png="host",
     ply="host", text="json" and Video(route="host") need that step -- in its own docstring."""
     from .frame_io import FrameFeeder
@@ -125,7 +125,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     if outputs is not None:
         if len(outputs.names) != n_frames:
             raise ValueError(f"SequenceOutputs has {len(outputs.names)} names for {n_frames} frames")
-        outputs.configure(png, ply, text, render, video, disp)
+        outputs.configure(png, ply, text, render, video, disp, lines)
         outputs.begin(rank, world, lo, hi)
     try:
         parts = []
@@ -155,7 +155,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
 
 
 def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outputs=None, on_range: str | None = None, png: str | None = None,
-                     ply: str | None = None, text: str | None = None, render=None, video=None, depths=None, disp: str | None = None):
+                     ply: str | None = None, text: str | None = None, render=None, video=None, depths=None, disp: str | None = None, lines=None):
     """``step`` for run_sequence on a real Engine: host or device u8 frames of any size -> (cubic resize to the network shape on
     the GPU, semantic_depth_cityscapes_sequence.py:123-130) -> Engine.process_batch -> record buffer.
     ``camera_of(global_frame_index) -> engine.Camera`` (the sequence tool: cx = 1048.64/4·s, cy = 519.277/4·s, disp_mult = 3800).
@@ -187,7 +187,12 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     ``disp`` (None = what ``outputs`` was built with; "gray" or "plasma"): Engine.disparity_image turns process_batch's ``disp_pp`` into the
     disparity image of every frame at the original frame size, with the frames' Camera.disp_mult as multipliers -- five launches plus the
     resample's two, behind the networks -- and the ``<name>_disp.png`` files go through the PNG route chosen (png="device":
-    Engine.encode_png on the images).  With None nothing is launched."""
+    Engine.encode_png on the images).  With None nothing is launched.
+    ``lines`` (None = what ``outputs`` was built with; an outputs.OverlayLines): Engine.draw_result_lines draws the measured road-width line
+    -- with approach 'both' the fence-to-fence line, with a depth profile the road's edges and a rung per depth -- into the composed images,
+    two launches right behind the compose launch and before the text, the video frames and the PNG streams, below the banner rows
+    (clip_top = int(0.25 h)); the flags travel to ``outputs.submit`` with the batch's other small records, beside the cameras and the fence
+    records the writer restates the segments from.  With None nothing is launched and submit gets no new keyword."""
     from .engine import RoadWidthParams
     from .recompute import check_mode
 
@@ -195,7 +200,7 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
         raise ValueError(f"make_engine_step(on_range={on_range!r}) on an engine built with on_range={getattr(engine, 'on_range', 'raise')!r}")
     prm = params or RoadWidthParams()
     if outputs is not None:
-        outputs.configure(png, ply, text, render, video, disp)
+        outputs.configure(png, ply, text, render, video, disp, lines)
         if depths is not None:
             want = [float(d) for d in np.asarray(depths, dtype=np.float64).reshape(-1)]
             if outputs.profile is None:
@@ -248,12 +253,17 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
         if outputs.images or vid is not None:
             images = engine.compose_result_frames(fr, out["seg"]["road"], out["seg"]["fence"], rec, size[0], size[1], outputs.road_color,
                                                   outputs.fence_color, outputs.alpha)
+            if outputs.lines is not None:                          # the measurement lines, below the banner rows
+                more["lines_flags"] = engine.draw_result_lines(images, rec, cams, outputs.lines, f2f=out.get("f2f"), profile=more.get("profile"),
+                                                               f2f_profile=more.get("f2f_profile"), clip_top=int(0.25 * size[0]))[1]
             if outputs.text == "draw":                             # the banner text, before anything reads the images
                 engine.draw_result_text(images, rec, outputs.depth)
             if vid is not None and vid.route == "device":          # the frames of the video, behind the text
                 more["video_streams"] = engine.encode_jpeg(images, vid.quality, stream_stride=1024 + size[0] * size[1] * 3 // 2)
             if outputs.images and device_png:                      # the zlib streams, behind the compose launch
                 more["png_streams"] = engine.encode_png(images)
+        if outputs.lines is not None:
+            more.update(f2f=out.get("f2f"), cams=cams, net_size=(engine.H, engine.W))
         outputs.submit(lo, rec, size, images=images, final=out.get("road_final") if outputs.ply else None, **more)
         return rec
 

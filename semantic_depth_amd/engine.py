@@ -522,6 +522,43 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_text_draw_rw")
         return images
 
+    def draw_result_lines(self, images: torch.Tensor, records: torch.Tensor, cams, lines, f2f: torch.Tensor | None = None,
+                          profile: torch.Tensor | None = None, f2f_profile: torch.Tensor | None = None, clip_top: int = 0):
+        """the measurement lines of the result images (seq:330-333, the print_line_on_image calls the reference never wrote) drawn IN PLACE
+        into u8 [B,h,w,3] device ``images`` (compose_result_frames' output): the road-width line of ``records`` u8 [B,104], the fence line of
+        ``f2f`` u8 [B,152] (sd_f2f_result; None: none) and -- with ``profile`` u8 [B,D,48] (road_width_profile) -- the road's left and right
+        edge along the profile and a rung per depth, the fence rungs with ``f2f_profile`` u8 [B,D,64]; all read on the device.  ``cams``: the
+        frames' Camera at the network size (this engine's H x W); ``lines``: an outputs.OverlayLines; rows above ``clip_top`` are never
+        painted.  The rule is the project's own (include/semdepth.h; not cv2.line's pixels), the same pixels outputs.draw_lines paints for
+        outputs.overlay_segments' segments.  Two launches on the current stream, no synchronisation; the workspace is a torch allocation.
+        Returns (``images``, ``flags`` i32 [B]; bit 0: a segment of the frame was skipped because an end point does not project)."""
+        assert images.dtype == torch.uint8 and images.is_cuda and images.is_contiguous() and images.dim() == 4 and images.shape[3] == 3
+        B, h, w = (int(v) for v in images.shape[:3])
+        assert records.dtype == torch.uint8 and records.is_cuda and records.is_contiguous() and tuple(records.shape) == (B, RW_DTYPE.itemsize)
+        cams = list(cams)
+        if len(cams) != B:
+            raise ValueError(f"draw_result_lines: {len(cams)} cameras for {B} frames")
+        D = 0
+        if profile is not None:
+            D = int(profile.shape[1])
+            assert profile.dtype == torch.uint8 and profile.is_cuda and profile.is_contiguous() and tuple(profile.shape) == (B, D, RWP_DTYPE.itemsize)
+        if f2f is not None:
+            assert f2f.dtype == torch.uint8 and f2f.is_cuda and f2f.is_contiguous() and tuple(f2f.shape) == (B, F2F_DTYPE.itemsize)
+        if f2f_profile is not None:
+            if profile is None:
+                raise ValueError("draw_result_lines: f2f_profile needs profile")
+            assert f2f_profile.dtype == torch.uint8 and f2f_profile.is_cuda and f2f_profile.is_contiguous() and \
+                tuple(f2f_profile.shape) == (B, D, F2FP_DTYPE.itemsize)
+        carr = (L.sd_camera * B)(*[L.sd_camera(c.cx, c.cy, c.f, c.b, c.disp_mult) for c in cams])
+        style = lines.struct(clip_top)
+        flags = torch.empty((B,), dtype=torch.int32, device=self.device)
+        need = self.lib.sd_overlay_workspace_bytes(B, D)
+        ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_overlay_draw(self.h, _ptr(images), B, h, w, self.H, self.W, carr, _ptr(records), _ptr(f2f), _ptr(profile) if D else None,
+                                      _ptr(f2f_profile) if D else None, D, C.byref(style), _ptr(flags), _ptr(ws), need, self._stream())
+        L.check(self.lib, self.h, st, "sd_overlay_draw")
+        return images, flags
+
     def encode_png(self, images: torch.Tensor):
         """the device half of the result-image writer (sd_png_encode_bgr): u8 [B,h,w,3] BGR device ``images`` -> (``streams`` u8 [B,stride],
         ``sizes`` i64 [B]) device tensors: frame b's complete zlib stream (Paeth rows, run matches, one dynamic-Huffman block per 32 KiB chunk;

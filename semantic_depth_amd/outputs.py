@@ -5,6 +5,8 @@
     render_rw / RenderCamera        <- utils/render_ply.py (every _rw.ply behind a saved Open3D pinhole camera) as z-buffered square points
                                        with a rule of the project's own (opt-in, render=camera; not Open3D's OpenGL pixels)
     draw_text                       <- the cv2.putText calls of :352-401 / seq:313-327 on the project's own stroke font (opt-in, text="draw")
+    overlay_segments / draw_lines   <- the print_line_on_image calls the reference left commented out (seq:330-333): the measured lines, with a
+                                       rule of the project's own (opt-in, lines=OverlayLines(); not cv2.line's pixels)
     save_frame_outputs              <- semantic_depth.py:339-441  (``_only_segmentation.png``, the annotated ``.png``, ``_ROAD`` / ``_FENCE`` /
                                        combined / ``_ALL`` PLY files, incl. the three visualisation planes of the combined cloud)
     road_plane_grid / fence_plane_grids <- the ``plane3D`` arrays of :215-219, :294-309 rebuilt through the reference's own pcl call sequence
@@ -186,6 +188,115 @@ def draw_text(img: np.ndarray, items) -> np.ndarray:
     st = L.load().sd_text_draw_host(out.ctypes.data_as(C.c_void_p), out.shape[0], out.shape[1], text_items(items), len(items))
     if st != L.SD_OK:
         raise ValueError(f"draw_text: an item or the image is outside the caps of include/semdepth.h (status {st})")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ measurement lines
+SEG_DTYPE = np.dtype([("ax", "<i4"), ("ay", "<i4"), ("bx", "<i4"), ("by", "<i4"), ("bgr", "u1", 3), ("thickness", "u1")])      # sd_overlay_segment
+
+
+@dataclasses.dataclass(frozen=True)
+class OverlayLines:
+    """the style of the measurement lines drawn into the result images (sd_overlay_style, include/semdepth.h; opt-in, lines=): ``rw_bgr``
+    colours the road-width line and the road rungs of a depth profile, ``f2f_bgr`` the fence-to-fence line and the fence rungs, ``edge_bgr``
+    the road's left and right edge along the profile, in the image's channel order; ``thickness`` (1..32 pixels) is that of the two measured
+    lines, ``profile_thickness`` that of everything from the profile.  The two line colours are the reference's (seq:331-332); the edge
+    colour and the thicknesses are the project's choice."""
+    rw_bgr: tuple = (0, 0, 255)
+    f2f_bgr: tuple = (0, 255, 0)
+    edge_bgr: tuple = (0, 255, 255)
+    thickness: int = 3
+    profile_thickness: int = 1
+
+    def __post_init__(self):
+        for k in ("rw_bgr", "f2f_bgr", "edge_bgr"):
+            c = tuple(int(v) for v in getattr(self, k))
+            if len(c) != 3 or not all(0 <= v <= 255 for v in c):
+                raise ValueError(f"OverlayLines: {k} holds three values 0..255, got {getattr(self, k)!r}")
+            object.__setattr__(self, k, c)
+        for k in ("thickness", "profile_thickness"):
+            t = int(getattr(self, k))
+            if not 1 <= t <= 32:
+                raise ValueError(f"OverlayLines: {k} must be 1..32, got {getattr(self, k)!r}")
+            object.__setattr__(self, k, t)
+
+    def struct(self, clip_top: int = 0):
+        """the style as a _lib.sd_overlay_style; rows above ``clip_top`` are never painted"""
+        from . import _lib as L
+        s = L.sd_overlay_style()
+        s.rw_bgr[:], s.f2f_bgr[:], s.edge_bgr[:] = self.rw_bgr, self.f2f_bgr, self.edge_bgr
+        s.thickness, s.profile_thickness, s.clip_top = self.thickness, self.profile_thickness, int(clip_top)
+        return s
+
+    def as_dict(self) -> dict:
+        return {k: list(v) if isinstance(v, tuple) else v for k, v in dataclasses.asdict(self).items()}
+
+
+def _check_lines(lines):
+    if lines is not None and not isinstance(lines, OverlayLines):
+        raise ValueError(f"lines must be None or an outputs.OverlayLines, got {lines!r}")
+    return lines
+
+
+def overlay_segments(record, camera, net_size: tuple, size: tuple, lines: OverlayLines | None = None, f2f=None, profile=None, f2f_profile=None,
+                     clip_top: int = 0):
+    """the measurement lines of one frame as data (sd_overlay_segments_host: the rule of include/semdepth.h, the segments
+    Engine.draw_result_lines draws on the GPU): ``record`` a record of engine.RW_DTYPE, ``camera`` the frame's Camera (cx, cy, f) at the
+    network size ``net_size`` = (h, w), ``size`` = (h, w) of the image drawn into, ``f2f`` a record of engine.F2F_DTYPE or None,
+    ``profile`` / ``f2f_profile`` the D records of engine.RWP_DTYPE / F2FP_DTYPE of a depth profile or None.  Returns (``segs``, ``flag``):
+    the valid segments in paint order as an array of SEG_DTYPE, end points in 1/256 pixel, and the frame's flag (bit 0: a segment was
+    skipped because an end point does not project)."""
+    import ctypes as C
+
+    from . import _lib as L
+    from .engine import F2F_DTYPE, F2FP_DTYPE, RW_DTYPE, RWP_DTYPE
+    lines = _check_lines(lines) or OverlayLines()
+
+    def raw(a, dt, n):
+        if a is None:
+            return None
+        b = np.asarray(a)
+        b = np.ascontiguousarray(b.reshape(-1).view(np.uint8) if b.dtype == dt else b, dtype=np.uint8).reshape(-1)
+        if b.size != n * dt.itemsize:
+            raise ValueError(f"overlay_segments: expected {n} record(s) of {dt.itemsize} bytes, got {b.size} bytes")
+        return b
+
+    D = 0 if profile is None else int(np.asarray(profile).shape[0])
+    if f2f_profile is not None and profile is None:
+        raise ValueError("overlay_segments: f2f_profile needs profile")
+    rec, fr, pr, fpr = raw(record, RW_DTYPE, 1), raw(f2f, F2F_DTYPE, 1), raw(profile, RWP_DTYPE, D), raw(f2f_profile, F2FP_DTYPE, D)
+    ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data_as(C.c_void_p)      # noqa: E731
+    cam = L.sd_camera(float(camera.cx), float(camera.cy), float(camera.f), float(getattr(camera, "b", 0.0)), float(getattr(camera, "disp_mult", 0.0)))
+    segs = np.zeros((4 * D + 2,), SEG_DTYPE)
+    n, flag = C.c_int(), C.c_int32()
+    st = L.load().sd_overlay_segments_host(C.byref(L.sd_rw_result.from_buffer_copy(rec.tobytes())), ptr(fr), ptr(pr), ptr(fpr), D, C.byref(cam),
+                                           int(net_size[0]), int(net_size[1]), int(size[0]), int(size[1]), C.byref(lines.struct(clip_top)),
+                                           segs.ctypes.data_as(C.POINTER(L.sd_overlay_segment)), C.byref(n), C.byref(flag))
+    if st != L.SD_OK:
+        raise ValueError(f"overlay_segments: refused (status {st}): extents 1..16384, at most 256 depths, clip_top 0..h, a finite camera")
+    return segs[:n.value].copy(), int(flag.value)
+
+
+def segments_json(segs) -> list:
+    """overlay_segments' array as the list an ``_overlay.json`` carries under "lines": [ax, ay, bx, by] in 1/256 pixel, colour, thickness"""
+    return [dict(a=[int(s["ax"]), int(s["ay"])], b=[int(s["bx"]), int(s["by"])], color=[int(c) for c in s["bgr"]], thickness=int(s["thickness"]))
+            for s in segs]
+
+
+def draw_lines(img: np.ndarray, segs, clip_top: int = 0) -> np.ndarray:
+    """overlay_segments' segments rasterised into a copy of u8 [h,w,3] ``img`` in list order, rows above ``clip_top`` untouched
+    (sd_overlay_draw_host: the rule of include/semdepth.h, the pixels Engine.draw_result_lines paints on the GPU -- not cv2.line's)."""
+    import ctypes as C
+
+    from . import _lib as L
+    out = np.array(img, dtype=np.uint8, order="C", copy=True)
+    if out.ndim != 3 or out.shape[2] != 3:
+        raise ValueError(f"draw_lines: the image must be u8 [h,w,3], got {out.shape}")
+    s = np.ascontiguousarray(np.asarray(segs, dtype=SEG_DTYPE).reshape(-1))
+    st = L.load().sd_overlay_draw_host(out.ctypes.data_as(C.c_void_p), out.shape[0], out.shape[1],
+                                       s.ctypes.data_as(C.POINTER(L.sd_overlay_segment)) if len(s) else None, len(s), int(clip_top))
+    if st != L.SD_OK:
+        raise ValueError(f"draw_lines: a segment, the image or clip_top is outside the caps of include/semdepth.h (status {st})")
     return out
 
 
@@ -437,7 +548,7 @@ def resize_to_original(segmented_frame: np.ndarray, original_width: int, origina
 def save_frame_outputs(output_name: str, res: dict, depth: float, approach: str = "rw", segmented_frame: np.ndarray | None = None,
                        is_city: bool = False, times: dict | None = None, road_plane3D=None, road_colors_plane=None,
                        points3D_all=None, colors_all=None, original_size: tuple | None = None, params=None, fence_params=None,
-                       text: str = "json", render: RenderCamera | None = None, profile=None):
+                       text: str = "json", render: RenderCamera | None = None, profile=None, lines: OverlayLines | None = None, camera=None):
     """what FrameProcessor.process_frame writes when --save_data is set (semantic_depth.py:339-458), from the dict
     ``api.FrameProcessor.process_frame(..., want_clouds=True)`` returns.  Returns the list of files written.
     ``original_size`` = (original_height, original_width): the overlay is cubic-resized back to it before anything is drawn (:341);
@@ -447,9 +558,16 @@ def save_frame_outputs(output_name: str, res: dict, depth: float, approach: str 
     ``render``: None (default) or a RenderCamera: also ``<output_name>_render.png``, the final road cloud and the road-width line of the
     record behind that camera (render_rw, the host statement of the sequence tool's rendered clouds).
     ``profile``: None (default) or the depth profile of the frame (``res["profile"]`` of FrameProcessor(depths=); True takes it from
-    ``res``): also ``<output_name>_profile.txt`` (profile_text)."""
+    ``res``): also ``<output_name>_profile.txt`` (profile_text).
+    ``lines``: None (default) or an OverlayLines: the measured road-width line, with approach 'both' the fence-to-fence line and, when ``res``
+    carries a depth profile's records, the road's edges and the rungs along it are drawn into the annotated image on the host
+    (overlay_segments + draw_lines) behind the cubic resize and before the text, below the banner (clip_top = int(0.2 h)); the
+    ``_overlay.json`` gains "lines".  It needs ``camera`` (the frame's engine.Camera at the size of ``segmented_frame`` as given) and
+    ``segmented_frame``: ValueError otherwise, before anything is written."""
     _check_text(text)
     _check_render(render)
+    if _check_lines(lines) is not None and (camera is None or segmented_frame is None):
+        raise ValueError("save_frame_outputs: lines= needs camera= and segmented_frame=")
     files = []
     rec = res["record"]
     if not rec["found"]:
@@ -466,6 +584,7 @@ def save_frame_outputs(output_name: str, res: dict, depth: float, approach: str 
         left_f2f, right_f2f = f2["left_pt"][None, :].copy(), f2["right_pt"][None, :].copy()
         line_f2f, colors_line_f2f = pcl.create_3Dline_from_3Dpoints(left_f2f.copy(), right_f2f.copy(), [0, 255, 0])
     if segmented_frame is not None:
+        net_size = tuple(segmented_frame.shape[:2])
         if original_size is not None and tuple(segmented_frame.shape[:2]) != tuple(original_size):
             segmented_frame = resize_to_original(segmented_frame, int(original_size[1]), int(original_size[0]))     # :341-342
         files.append(write_png("{}_only_segmentation.png".format(output_name), segmented_frame))                  # :345
@@ -473,11 +592,19 @@ def save_frame_outputs(output_name: str, res: dict, depth: float, approach: str 
         banner, items = overlay_items(w, h, depth, is_city, left_rw, right_rw, dist_rw, "both" if both else "rw",
                                       left_f2f if both else None, right_f2f if both else None, res.get("dist_f2f"))
         img, items = draw_overlay(segmented_frame, banner, items)
+        doc = dict(banner=banner, items=items)
+        if lines is not None:
+            clip = int(0.2 * h)
+            segs, _ = overlay_segments(rec, camera, net_size, (h, w), lines, f2f=f2 if both else None, profile=res.get("profile_records"),
+                                       f2f_profile=res.get("f2f_profile_records") if both and res.get("profile_records") is not None else None,
+                                       clip_top=clip)
+            img = draw_lines(img, segs, clip)
+            doc["lines"] = segments_json(segs)
         if text == "draw":
             img = draw_text(img, items)
         files.append(write_png("{}.png".format(output_name), img))
         with open("{}_overlay.json".format(output_name), "w") as f:
-            json.dump(dict(banner=banner, items=items), f)
+            json.dump(doc, f)
         files.append("{}_overlay.json".format(output_name))
     if render is not None:
         files.append(write_png("{}_render.png".format(output_name), render_rw(res["road3D_final"], res["road_colors_final"], rec["left_pt"], rec["right_pt"], render)))
@@ -917,6 +1044,10 @@ class _Batch:
     disp_images: object = None
     disp_streams: object = None
     disp_flags: object = None
+    lines_flags: object = None
+    f2f: object = None
+    cams: object = None                     # the frames' cameras and the network size (host values): the writer restates the lines from them
+    net_size: object = None
 
 
 @dataclasses.dataclass
@@ -943,6 +1074,8 @@ class _HostBatch:
     disp_png: np.ndarray | None = None      # [n,stride] zlib streams of them, disp_png[i, :disp_sizes[i]] copied
     disp_sizes: np.ndarray | None = None
     disp_flags: np.ndarray | None = None    # [n] non-zero: the frame's map held a non-finite value
+    lines_flags: np.ndarray | None = None   # [n] bit 0: a measurement line of the frame was skipped
+    f2f: np.ndarray | None = None           # [n,152] fence records, for the lines of approach 'both'
 
 
 class _Stager:
@@ -1086,13 +1219,21 @@ class SequenceOutputs:
     (semantic_depth.py:681-683) at the original frame size on the GPU (Engine.disparity_image, submit(disp_images=, disp_flags=) or, with
     png="device", submit(disp_streams=)); the images or streams travel in the staged transfer as the renders do and the writer stores
     ``result_sequence_disp/<name>_disp.png`` through the PNG route chosen.  The manifest names those files under 'disp' and the frames
-    whose map held a non-finite value (it became byte 0) under 'disp_nonfinite'.  Works with images=False too."""
+    whose map held a non-finite value (it became byte 0) under 'disp_nonfinite'.  Works with images=False too.
+    ``lines``: None (default: no byte of any file changes, nothing more is copied or launched, the manifest is what it was and submit gets
+    no new keyword) or an OverlayLines: the step of make_engine_step also draws the measured road-width line -- with approach 'both' the
+    fence-to-fence line, with profile= the road's two edges and a rung per depth -- into the composed images on the GPU
+    (Engine.draw_result_lines, right behind the compose launch and before the text, below the banner rows: clip_top = int(0.25 h)), so the
+    PNGs of both routes and the video show them.  submit(lines_flags=, f2f=, cams=, net_size=) carries the per-frame flags and what the
+    writer needs to restate the segments (overlay_segments): each ``_overlay.json`` gains "lines", the manifest 'lines' (the style) and
+    'lines_flagged' (the frames of which a segment was skipped because an end point does not project)."""
 
-    png, ply_route, text, render, video, disp, _k = "host", "host", "json", None, None, None, 0    # (what configure() starts from)
+    png, ply_route, text, render, video, disp, lines, _k = "host", "host", "json", None, None, None, None, 0    # (what configure() starts from)
 
     def __init__(self, directory: str, names, depth: float = 10.0, images: bool = True, ply: bool | str = True, items: bool = True, level: int = 1,
                  threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, png: str = "host", text: str = "json",
-                 render: RenderCamera | None = None, video: Video | None = None, profile=None, disp: str | None = None):
+                 render: RenderCamera | None = None, video: Video | None = None, profile=None, disp: str | None = None,
+                 lines: OverlayLines | None = None):
         import threading
         from concurrent.futures import ThreadPoolExecutor
 
@@ -1101,7 +1242,7 @@ class SequenceOutputs:
             raise ValueError("PNG compression level must be 0..9")
         if png is None or ply is None or text is None:                # (None leaves a choice as it is only in configure)
             raise ValueError(f"png, ply and text must be given, got {png!r}, {ply!r}, {text!r}")
-        self.configure(png, "host" if isinstance(ply, bool) else ply, text, render, video, disp)
+        self.configure(png, "host" if isinstance(ply, bool) else ply, text, render, video, disp, lines)
         self.directory, self.names, self.depth = directory, list(names), float(depth)
         self.images, self.ply, self.items, self.level = bool(images), bool(ply), bool(items), int(level)
         self.road_color, self.fence_color, self.alpha = tuple(road_color), tuple(fence_color), int(alpha)
@@ -1125,13 +1266,16 @@ class SequenceOutputs:
         self.ply_fallback: list[int] = []                             # global indices of the frames ply="device" sent through rw_ply_bytes
         self.video_fallback: list[int] = []                           # global indices of the frames video route "device" encoded on the host
         self.disp_nonfinite: list[int] = []                           # global indices of the frames whose disparity map held a non-finite value
+        self.lines_flagged: list[int] = []                            # global indices of the frames of which lines= skipped a segment
         self._video_writer, self._video_next, self._video_turn = None, 0, threading.Condition()
 
     # ---------------------------------------------------------------- driver interface
-    def configure(self, png: str | None = None, ply: str | None = None, text: str | None = None, render=None, video=None, disp: str | None = None):
+    def configure(self, png: str | None = None, ply: str | None = None, text: str | None = None, render=None, video=None, disp: str | None = None,
+                  lines=None):
         """choose the routes described in the class docstring, before the first batch: ``png`` and ``ply`` "host" or "device", ``text`` "json"
-        or "draw", ``render`` a RenderCamera, ``video`` a Video, ``disp`` "gray" or "plasma"; None leaves a choice as it is.  Nothing changes
-        when the resulting combination is refused."""
+        or "draw", ``render`` a RenderCamera, ``video`` a Video, ``disp`` "gray" or "plasma", ``lines`` an OverlayLines; None leaves a choice
+        as it is.  Nothing changes when the resulting combination is refused."""
+        lines = self.lines if lines is None else lines
         png = self.png if png is None else png
         ply = self.ply_route if ply is None else ply
         text = self.text if text is None else text
@@ -1146,11 +1290,16 @@ class SequenceOutputs:
         _check_render(render)
         _check_video(video)
         _check_disp(disp)
+        _check_lines(lines)
         if self._k:
             raise RuntimeError("SequenceOutputs.configure after the first batch")
         if png == "device" and video is not None and video.route == "host":
             raise ValueError("Video(route='host') needs png='host': with png='device' no raw image reaches the host")
-        self.png, self.ply_route, self.text, self.render, self.video, self.disp = png, ply, text, render, video, disp
+        self.png, self.ply_route, self.text, self.render, self.video, self.disp, self.lines = png, ply, text, render, video, disp, lines
+
+    def set_lines(self, lines):
+        """the OverlayLines the measurement lines are drawn with (before the first batch)"""
+        self.configure(lines=lines)
 
     def set_png(self, png: str):
         """where the result images are compressed: "host" or "device" (before the first batch)"""
@@ -1196,7 +1345,8 @@ class SequenceOutputs:
         return self.png == "host" and (self.images or self.video is not None and self.video.route == "host")
 
     def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None, ply_text=None, renders=None, render_streams=None,
-               video_streams=None, profile=None, f2f_profile=None, disp_images=None, disp_streams=None, disp_flags=None):
+               video_streams=None, profile=None, f2f_profile=None, disp_images=None, disp_streams=None, disp_flags=None, lines_flags=None,
+               f2f=None, cams=None, net_size=None):
         """one batch: ``records`` u8 [n,104] (sd_rw_result), ``size`` = (h, w) of the original frames, ``images`` u8 [n,h,w,3] (the composed
         result images) or None, ``final`` = dict(xyz f32 [n,cap,3], rgb u8 [n,cap,3], n i32 [n]) (process_batch(want_final=True)'s
         road_final) or None, ``png_streams`` = (streams u8 [n,stride], sizes i64 [n]) of Engine.encode_png in place of ``images`` on the
@@ -1207,7 +1357,9 @@ class SequenceOutputs:
         route needs only ``images``), ``profile`` = u8 [n,D,48] of Engine.road_width_profile (process_batch(depths=)'s ``profile``) with
         profile=, ``f2f_profile`` = u8 [n,D,64] beside it (optional: the dist_f2f column), ``disp_images`` = u8 [n,h,w,3] of
         Engine.disparity_image with disp= (or ``disp_streams`` = Engine.encode_png of them on the png="device" route) and ``disp_flags`` =
-        its i32 [n] flags beside either (optional: the manifest's 'disp_nonfinite').  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
+        its i32 [n] flags beside either (optional: the manifest's 'disp_nonfinite'); with lines=: ``cams`` = the n frames' Camera and
+        ``net_size`` = (h, w) of the network they belong to (host values), ``f2f`` = u8 [n,152] fence records (optional: the fence lines) and
+        ``lines_flags`` = i32 [n] of Engine.draw_result_lines (optional: without them the writer's own restatement flags the frames).  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
         tensors of every step)."""
         if self.manifest is not None:
             raise RuntimeError("SequenceOutputs.submit after close")
@@ -1229,6 +1381,8 @@ class SequenceOutputs:
             raise ValueError("SequenceOutputs: profile= needs the [n, D, 48] records of Engine.road_width_profile (submit(profile=))")
         if _check_disp(self.disp) is not None and (disp_streams if device_png else disp_images) is None:
             raise ValueError("SequenceOutputs: disp= needs the images of Engine.disparity_image (submit(disp_images=); png='device': disp_streams=)")
+        if self.lines is not None and (cams is None or net_size is None or len(cams) != n):
+            raise ValueError("SequenceOutputs: lines= needs the frames' cameras and the network size (submit(cams=, net_size=))")
         while len(self._jobs) >= 2:                                    # at most two batches in flight
             self._files.extend(self._jobs.pop(0).result())
         slot = self._k & 1
@@ -1245,6 +1399,8 @@ class SequenceOutputs:
                        disp_images=disp_images if self.disp is not None and not device_png else None,
                        disp_streams=disp_streams if self.disp is not None and device_png else None,
                        disp_flags=disp_flags if self.disp is not None else None)
+        if self.lines is not None:
+            batch.lines_flags, batch.f2f, batch.cams, batch.net_size = lines_flags, f2f, list(cams), tuple(net_size)
         self._k += 1
         self._jobs.append(self._batches.submit(self._write_batch, batch))
 
@@ -1294,6 +1450,9 @@ class SequenceOutputs:
         if self.disp is not None:
             manifest["disp"] = [f for f in files if f.startswith(SEQ_DISP_DIR + os.sep)]
             manifest["disp_nonfinite"] = named(self.disp_nonfinite)
+        if self.lines is not None:
+            manifest["lines"] = self.lines.as_dict()
+            manifest["lines_flagged"] = named(self.lines_flagged)
         with open(self.manifest, "w") as f:
             json.dump(manifest, f, indent=1)
         if err is not None:
@@ -1311,7 +1470,8 @@ class SequenceOutputs:
             host = _HostBatch(st.fixed("rec", b.records), images=st.fixed("img", b.images if self._images_travel else None),
                               renders=st.fixed("render", b.renders), profile=st.fixed("profile", b.profile),
                               f2f_profile=st.fixed("f2f_profile", b.f2f_profile), disp_images=st.fixed("disp", b.disp_images),
-                              disp_flags=st.fixed("disp_flags", b.disp_flags))
+                              disp_flags=st.fixed("disp_flags", b.disp_flags), lines_flags=st.fixed("lines_flags", b.lines_flags),
+                              f2f=st.fixed("f2f", b.f2f))
             counts = None if b.final is None else st.fixed("n", b.final["n"])
             if b.png_streams is not None:
                 host.png_sizes = st.fixed("png_sizes", b.png_streams[1])
@@ -1389,8 +1549,16 @@ class SequenceOutputs:
                 left, right = ends(r)
                 banner, items = overlay_items_sequence(w, h, self.depth, bool(r["found"]), left, right, float(r["width"]) if r["found"] else None)
                 path = os.path.join(self.img_dir, "{}_overlay.json".format(names[i]))
+                doc = dict(banner=banner, items=items)
+                if self.lines is not None:                             # the segments the step drew, restated on the host
+                    segs, flag = overlay_segments(r, b.cams[i], b.net_size, (h, w), self.lines, f2f=None if host.f2f is None else host.f2f[i],
+                                                  profile=None if host.profile is None else host.profile[i],
+                                                  f2f_profile=None if host.f2f_profile is None else host.f2f_profile[i], clip_top=int(0.25 * h))
+                    doc["lines"] = segments_json(segs)
+                    if flag and host.lines_flags is None:
+                        self.lines_flagged.append(b.lo + i)
                 with open(path, "w") as f:
-                    json.dump(dict(banner=banner, items=items), f)
+                    json.dump(doc, f)
                 return path
 
             def write_profile_file(i):
@@ -1402,6 +1570,8 @@ class SequenceOutputs:
             if host.profile is not None:
                 os.makedirs(self.profile_dir, exist_ok=True)
                 futs.extend(self._writers.submit(write_profile_file, i) for i in range(n))
+            if host.lines_flags is not None:
+                self.lines_flagged.extend(b.lo + i for i in range(n) if host.lines_flags[i] != 0)
             if host.ply_flags is not None:
                 self.ply_fallback.extend(b.lo + i for i in range(n) if host.ply_flags[i] != 0)
             for i in range(n):
