@@ -111,9 +111,9 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     (FrameFeeder.entropy_fallback names them); the frames are the same bytes on all three.
     ``png_in`` (None = "host" | "device") is the feeder's ``png=`` (``png`` here already names the output writer): with "device" the PNG
     frames are only inflated on the host and their scanlines reconstructed on the GPU by ``engine``; the frames are the same bytes.
-    ``png``, ``ply``, ``text``, ``render``, ``video``, ``disp``, ``lines`` (None = what the SequenceOutputs was built with) go to SequenceOutputs.configure
-    before the first batch: the choices are described there, and what the step of make_engine_step does for each -- all but png="host",
-    ply="host", text="json" and Video(route="host") need that step -- in its own docstring."""
+    ``png``, ``ply``, ``text``, ``render``, ``video``, ``disp``, ``lines`` (None = what the SequenceOutputs was built with) go to
+    SequenceOutputs.configure before the first batch: its class docstring describes the choices, make_engine_step's what the step launches
+    for each."""
     from .frame_io import FrameFeeder
     engine = engine if engine is not None else getattr(step, "engine", None)
     paths = sorted(paths)
@@ -159,40 +159,28 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     """``step`` for run_sequence on a real Engine: host or device u8 frames of any size -> (cubic resize to the network shape on
     the GPU, semantic_depth_cityscapes_sequence.py:123-130) -> Engine.process_batch -> record buffer.
     ``camera_of(global_frame_index) -> engine.Camera`` (the sequence tool: cx = 1048.64/4·s, cy = 519.277/4·s, disp_mult = 3800).
-    ``outputs`` (outputs.SequenceOutputs, None = records only): also the sequence tool's files -- process_batch keeps the final road clouds
-    when PLYs are asked for, Engine.compose_result_frames makes the result images at the original frame size on the device, and the
-    batch goes to ``outputs.submit`` (copies on a side stream, written on host threads); the records are the same either way.
+    ``outputs`` (outputs.SequenceOutputs, None = records only): also the sequence tool's files -- the batch goes to ``outputs.submit``
+    (copies on a side stream, written on host threads); the records are the same either way.
     ``on_range`` (None = the engine's own mode; else it must match Engine(on_range=)): with 'recompute' the frames that left the fp16 range
     are recomputed on bf16x3 inside process_batch, so every batch's records, images and PLYs are final before gather_records and no rank
     raises from ``step.finish`` for them; ``step.recomputed`` (and the manifest's 'recomputed' names) lists those frames.
-    ``png``, ``ply``, ``text``, ``render``, ``video`` (None = what ``outputs`` was built with) go to SequenceOutputs.configure, which
-    describes the choices; what the step does for each, all on its own stream:
-    png="device": Engine.encode_png turns the composed images into zlib streams right behind the compose launch (behind the text and the
-    video frames when those are on), and only the streams' bytes travel to the host.
-    ply="device": Engine.format_rw_ply turns the final road clouds and the records into the text of the ``_rw.ply`` files, and only that
-    text travels to the host (the raw cloud of a frame the device did not format still does).
-    text="draw": Engine.draw_result_text rasterises the banner text into the composed images right behind the compose launch -- before
-    Engine.encode_png on the device PNG route, before the copy to the host on the other -- so both routes write it; the ``_overlay.json``
-    files are written as before.
-    render=camera: process_batch keeps the final road clouds even when no PLY is asked for, and Engine.render_rw draws them and the
-    road-width line behind that camera, behind the road chain; the ``<name>_render.png`` files go through the PNG route chosen
-    (png="device": Engine.encode_png on the renders).
-    video=Video: the composed images -- composed for this alone when ``outputs.images`` is off -- also become the frames of the result
-    video; on its "device" route Engine.encode_jpeg makes every frame's JPEG file behind Engine.draw_result_text, with a stream stride of
-    half the raw image (a frame that needs more is flagged and encoded on the host from its raw copy).
-    ``depths`` (None = what ``outputs`` was built with, SequenceOutputs(profile=); else it becomes the outputs' profile, and must agree with
-    one already chosen): process_batch(depths=) adds every frame's depth profile -- two launches behind the road chain, one more with
-    approach 'both' -- and the record tensors travel to ``outputs.submit`` with the batch's other small records.  Without ``outputs`` the
-    step returns the records only and ``depths`` asks for nothing.
-    ``disp`` (None = what ``outputs`` was built with; "gray" or "plasma"): Engine.disparity_image turns process_batch's ``disp_pp`` into the
-    disparity image of every frame at the original frame size, with the frames' Camera.disp_mult as multipliers -- five launches plus the
-    resample's two, behind the networks -- and the ``<name>_disp.png`` files go through the PNG route chosen (png="device":
-    Engine.encode_png on the images).  With None nothing is launched.
-    ``lines`` (None = what ``outputs`` was built with; an outputs.OverlayLines): Engine.draw_result_lines draws the measured road-width line
-    -- with approach 'both' the fence-to-fence line, with a depth profile the road's edges and a rung per depth -- into the composed images,
-    two launches right behind the compose launch and before the text, the video frames and the PNG streams, below the banner rows
-    (clip_top = int(0.25 h)); the flags travel to ``outputs.submit`` with the batch's other small records, beside the cameras and the fence
-    records the writer restates the segments from.  With None nothing is launched and submit gets no new keyword."""
+    ``png``, ``ply``, ``text``, ``render``, ``video``, ``disp``, ``lines`` (None = what ``outputs`` was built with) go to
+    SequenceOutputs.configure, whose class docstring describes the choices.  ``depths`` (None likewise) becomes the outputs' profile, and
+    must agree with one already chosen; without ``outputs`` it asks for nothing.
+    What the step launches for them, all on its own stream and in this order (a choice that is off launches nothing):
+      1. Engine.process_batch -- with want_final when PLYs or renders are on, so that it keeps the final road clouds, and with depths= for a
+         profile (two launches behind the road chain, one more with approach 'both').
+      2. ply="device": Engine.format_rw_ply, the text of the ``_rw.ply`` files from the final clouds and the records.
+      3. render=: Engine.render_rw behind that camera, then on the device PNG route Engine.encode_png of the renders.
+      4. disp=: Engine.disparity_image of ``disp_pp`` at the original frame size with the frames' Camera.disp_mult as multipliers (five
+         launches plus the resample's two), then on the device PNG route Engine.encode_png of the images.
+      5. ``outputs.images`` or video=: Engine.compose_result_frames, the result images at the original frame size; then, on those images:
+         a. lines=: Engine.draw_result_lines (two launches), right behind the compose launch;
+         b. text="draw": Engine.draw_result_text, before anything reads the images;
+         c. video route "device": Engine.encode_jpeg behind the text, with a stream stride of 1024 bytes plus half the raw image;
+         d. ``outputs.images`` on the device PNG route: Engine.encode_png, last.
+    The step hands ``outputs.submit`` exactly what those made, the flags of 4 and 5a among them, and with lines= the cameras, the network
+    size and the fence records (SequenceOutputs.submit lists the keywords)."""
     from .engine import RoadWidthParams
     from .recompute import check_mode
 
@@ -215,6 +203,11 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
         if outputs is not None and idx:
             outputs.mark_recomputed(idx)
 
+    def png_keyword(raw: str, streams: str, images):
+        """a batch of images of one PNG family as its keyword of outputs.submit: ``raw``, or ``streams`` = Engine.encode_png of them on the
+        device PNG route"""
+        return {streams: engine.encode_png(images)} if outputs.device_png else {raw: images}
+
     def step(frames, lo):
         fr = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames))
         fr = fr.to(engine.device, non_blocking=True)
@@ -226,45 +219,35 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
             rec = engine.process_batch(fr, cams, prm, approach=approach)["records"]
             note(lo)
             return rec
-        camera, vid, device_png = outputs.render, outputs.video, outputs.png == "device"
-        if outputs.profile is None:
-            out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.ply or camera is not None)
-        else:
-            out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.ply or camera is not None, depths=outputs.profile)
-            more_profile = dict(profile=out["profile"], f2f_profile=out.get("f2f_profile"))
+        # (depths=None is process_batch's default: no profile)
+        out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.wants_final, depths=outputs.profile)
         note(lo)
         rec = out["records"]
-        images = None
-        more = {} if outputs.profile is None else more_profile
-        if outputs.ply and outputs.ply_route == "device":           # the text of the PLY files
+        more = dict(images=None, final=out.get("road_final") if outputs.ply else None)
+        if outputs.profile is not None:
+            more.update(profile=out["profile"], f2f_profile=out.get("f2f_profile"))
+        if outputs.device_ply:                                     # the text of the PLY files
             more["ply_text"] = engine.format_rw_ply(out["road_final"], rec)
-        if camera is not None:                                     # the rendered clouds, behind the road chain
-            renders = engine.render_rw(out["road_final"], rec, camera)[0]
-            if device_png:
-                more["render_streams"] = engine.encode_png(renders)
-            else:
-                more["renders"] = renders
+        if outputs.render is not None:                             # the rendered clouds, behind the road chain
+            more.update(png_keyword("renders", "render_streams", engine.render_rw(out["road_final"], rec, outputs.render)[0]))
         if outputs.disp is not None:                               # the disparity images, behind the networks
             dimg, more["disp_flags"] = engine.disparity_image(out["disp_pp"], size[0], size[1], outputs.disp, mults=[c.disp_mult for c in cams])
-            if device_png:
-                more["disp_streams"] = engine.encode_png(dimg)
-            else:
-                more["disp_images"] = dimg
-        if outputs.images or vid is not None:
-            images = engine.compose_result_frames(fr, out["seg"]["road"], out["seg"]["fence"], rec, size[0], size[1], outputs.road_color,
-                                                  outputs.fence_color, outputs.alpha)
+            more.update(png_keyword("disp_images", "disp_streams", dimg))
+        if outputs.wants_composed:
+            images = more["images"] = engine.compose_result_frames(fr, out["seg"]["road"], out["seg"]["fence"], rec, size[0], size[1],
+                                                                   outputs.road_color, outputs.fence_color, outputs.alpha)
             if outputs.lines is not None:                          # the measurement lines, below the banner rows
                 more["lines_flags"] = engine.draw_result_lines(images, rec, cams, outputs.lines, f2f=out.get("f2f"), profile=more.get("profile"),
                                                                f2f_profile=more.get("f2f_profile"), clip_top=int(0.25 * size[0]))[1]
             if outputs.text == "draw":                             # the banner text, before anything reads the images
                 engine.draw_result_text(images, rec, outputs.depth)
-            if vid is not None and vid.route == "device":          # the frames of the video, behind the text
-                more["video_streams"] = engine.encode_jpeg(images, vid.quality, stream_stride=1024 + size[0] * size[1] * 3 // 2)
-            if outputs.images and device_png:                      # the zlib streams, behind the compose launch
-                more["png_streams"] = engine.encode_png(images)
+            if outputs.device_video:                               # the frames of the video, behind the text
+                more["video_streams"] = engine.encode_jpeg(images, outputs.video.quality, stream_stride=1024 + size[0] * size[1] * 3 // 2)
+            if outputs.images:                                     # (the zlib streams last)
+                more.update(png_keyword("images", "png_streams", images))
         if outputs.lines is not None:
             more.update(f2f=out.get("f2f"), cams=cams, net_size=(engine.H, engine.W))
-        outputs.submit(lo, rec, size, images=images, final=out.get("road_final") if outputs.ply else None, **more)
+        outputs.submit(lo, rec, size, **more)
         return rec
 
     # ('recompute': every clamp in a stored output is attributed to its frame and that frame recomputed, so the step has no verdict left

@@ -1023,6 +1023,22 @@ def rw_ply_bytes(road3D, road_colors, left_pt_rw=None, right_pt_rw=None) -> byte
     return PointCloud2Ply.ply_header.format(vertex_count=len(pts)).encode() + format_rows(pts, col, threads=1)
 
 
+@dataclasses.dataclass(frozen=True)
+class _PngFamily:
+    """one family of per-frame PNG files of SequenceOutputs; all of them go through the PNG route chosen (``png``, described there)"""
+    key: str                                # what a batch's payload of the family is filed under
+    subdir: str                             # the files are <directory>/<subdir>/<name><suffix>
+    suffix: str
+    size: str                               # (h, w) of the images: "frame" (the original frames') or "camera" (the RenderCamera's)
+    manifest_key: str | None                # the manifest lists the files under it (None: only under 'files')
+    early_dir: bool                         # the directory is made by the constructor (else by every batch that writes into it)
+
+
+_PNG_FAMILIES = (_PngFamily("images", SEQ_IMG_DIR, ".png", "frame", None, True),
+                 _PngFamily("render", SEQ_RENDER_DIR, "_render.png", "camera", "render", False),
+                 _PngFamily("disp", SEQ_DISP_DIR, "_disp.png", "frame", "disp", False))
+
+
 @dataclasses.dataclass
 class _Batch:
     """one batch as submit() accepted it: device or host tensors, the payloads of the routes that are off already None"""
@@ -1032,17 +1048,13 @@ class _Batch:
     size: tuple
     ev: object                              # an event of the producing stream, None for a host batch
     records: object
-    images: object = None
+    png: dict                               # family key -> the raw images u8 [n,h,w,3] or (streams, sizes), for the families that are on
+    images: object = None                   # the raw result images with video=: its frames (route "host") / the source of a flagged one
     final: object = None
-    png_streams: object = None
     ply_text: object = None
-    renders: object = None
-    render_streams: object = None
     video_streams: object = None
     profile: object = None
     f2f_profile: object = None
-    disp_images: object = None
-    disp_streams: object = None
     disp_flags: object = None
     lines_flags: object = None
     f2f: object = None
@@ -1054,25 +1066,18 @@ class _Batch:
 class _HostBatch:
     """numpy views of a _Batch on the host (pinned staging or the host tensors themselves), valid until its slot's next batch"""
     records: np.ndarray
-    images: np.ndarray | None = None        # the raw images, when they travel whole
+    png: dict = dataclasses.field(default_factory=dict)            # family key -> (raw images [n,h,w,3], None) or ([n,stride] zlib
+    #                                                                streams of which [i, :sizes[i]] was copied, sizes)
     clouds: list | None = None              # per frame (xyz, rgb), None for a frame whose text the device formatted
-    png: np.ndarray | None = None           # [n,stride] zlib streams, png[i, :png_sizes[i]] copied
-    png_sizes: np.ndarray | None = None
     ply_text: np.ndarray | None = None      # frame i's file is ply_text[ply_offsets[i]:ply_offsets[i + 1]] where ply_flags[i] == 0
     ply_offsets: np.ndarray | None = None
     ply_flags: np.ndarray | None = None
-    renders: np.ndarray | None = None
-    render_png: np.ndarray | None = None
-    render_sizes: np.ndarray | None = None
     video: np.ndarray | None = None         # [n,stride] JPEG files, video[i, :video_sizes[i]] copied where video_flags[i] == 0
     video_sizes: np.ndarray | None = None
     video_flags: np.ndarray | None = None
     video_raw: dict = dataclasses.field(default_factory=dict)      # frame -> raw image of a flagged video frame
     profile: np.ndarray | None = None       # [n,D,48] depth-profile records
     f2f_profile: np.ndarray | None = None   # [n,D,64]
-    disp_images: np.ndarray | None = None   # [n,h,w,3] disparity images, when they travel whole
-    disp_png: np.ndarray | None = None      # [n,stride] zlib streams of them, disp_png[i, :disp_sizes[i]] copied
-    disp_sizes: np.ndarray | None = None
     disp_flags: np.ndarray | None = None    # [n] non-zero: the frame's map held a non-finite value
     lines_flags: np.ndarray | None = None   # [n] bit 0: a measurement line of the frame was skipped
     f2f: np.ndarray | None = None           # [n,152] fence records, for the lines of approach 'both'
@@ -1169,10 +1174,8 @@ class SequenceOutputs:
     """what the sequence tool writes for every frame (seq:303-361), fed batch by batch by the step of ``make_engine_step(..., outputs=)``:
 
         <directory>/result_sequence_imgs/<name>.png           the overlay at the original frame size, 25 % banner when the line was found
-                                                              (``images``; Engine.compose_result_frames on the GPU, sd_png_encode_bgr_files
-                                                              or, with png="device", Engine.encode_png and sd_png_write_streams_files)
-        <directory>/result_sequence_imgs/<name>_overlay.json  the banner and the cv2.putText items of overlay_items_sequence (``items``;
-                                                              rasterised into the image only with text="draw", module docstring)
+                                                              (``images``; Engine.compose_result_frames on the GPU)
+        <directory>/result_sequence_imgs/<name>_overlay.json  the banner and the cv2.putText items of overlay_items_sequence (``items``)
         <directory>/result_sequence_ply/<name>_rw.ply         the denoised road cloud + the red road-width line (``ply``; rw_ply_bytes)
         <directory>/rendered_sequence/<name>_render.png       only with render=: the top view of the _rw.ply's rows (``render``)
         <directory>/result_imgs.avi                           only with video=: the result images as a Motion-JPEG AVI (``video``;
@@ -1183,49 +1186,47 @@ class SequenceOutputs:
 
     ``names``: output names of the WHOLE sorted frame list (sequence_names), indexed by global frame index.  submit() takes the device
     tensors of one batch, copies them into pinned staging on a side stream behind an event of the current stream, and writes them on
-    worker threads -- at most two batches in flight -- with the per-pixel and per-point work in native code (no interpreter lock).
+    worker threads -- at most two batches in flight -- with the per-pixel and per-point work in native code (no interpreter lock).  The
+    transfer has two phases (_fetch): first everything whose shape is known -- the records, whole images, and every count, size, offset
+    and flag -- then exactly the bytes those call for.
     ``threads``: native encoder threads per batch and PLY writer threads (0: frame_io.default_decode_workers()).
     The choices that follow can also be made after construction and before the first batch, by configure() (all at once; what
     make_engine_step and run_sequence_files do with their keywords of the same names) or by set_png / set_ply / set_text / set_render /
-    set_video / set_disp; the "device" routes, text="draw", render= and video= need the step of make_engine_step, which does the GPU half.
-    ``png``: "host" (default) copies the raw images to the host and deflates them there (sd_png_encode_bgr_files at ``level``); "device"
-    takes each frame's finished zlib stream from the GPU (Engine.encode_png, submit(png_streams=)): the sizes are copied first, then each
-    stream's exact byte count, and the host only writes the PNG chunks (sd_png_write_streams_files).  Same names, manifest and pixels.
+    set_video / set_disp / set_lines / set_profile.  All but png="host", ply="host", text="json" and Video(route="host") need the step of
+    make_engine_step, which does the GPU half (its docstring: what it launches for each, in which order); submit()'s docstring names the
+    keyword each payload arrives under.  Every choice that defaults to None then writes, copies and launches nothing more, changes no byte
+    of any file and leaves the manifest what it was.
+    ``png``: the route of every family of per-frame PNG files (_PNG_FAMILIES: the result images, the renders, the disparity images).
+    "host" (default): the raw images are copied to the host and deflated there (sd_png_encode_bgr_files at ``level``); "device": each
+    frame's finished zlib stream comes from the GPU (Engine.encode_png): the sizes are copied first, then each stream's exact byte
+    count, and the host only writes the PNG chunks (sd_png_write_streams_files).  Same names, manifest and pixels.
     ``ply``: False (no PLY files), True / "host" (default: the raw clouds are copied to the host and formatted there, rw_ply_bytes) or "device":
-    the step hands submit(ply_text=) the finished text of every file (Engine.format_rw_ply); the offsets and flags are copied first, then
+    the finished text of every file comes from the GPU (Engine.format_rw_ply); the offsets and flags are copied first, then
     text[:offsets[n]] in one copy, and the host only writes each slice.  A frame the device did not format (a non-zero flag: a non-finite
     coordinate or |v| >= 2^31) has its raw cloud copied and goes through rw_ply_bytes; the manifest names those frames under 'ply_fallback'.
     Same names and the same bytes.  (Whether PLYs are written at all stays what the constructor was given, ``self.ply``; the route is
     ``self.ply_route``.)
-    ``text``: "json" (default: the banner of the images stays empty, the text is in the ``_overlay.json`` files) or "draw": the step of
-    make_engine_step also rasterises it into the composed images on the GPU (Engine.draw_result_text) before they reach either PNG route.
-    ``render``: None (default: nothing more is written, the manifest is what it was) or a RenderCamera: the step of make_engine_step also
-    draws every frame's final road cloud and road-width line behind that camera on the GPU (Engine.render_rw, submit(renders=) or, with
-    png="device", submit(render_streams=)) and the writer stores ``<name>_render.png`` through the PNG route chosen; the manifest names
-    those files under 'render'.
-    ``video``: None (default: nothing more is written, the manifest is what it was) or a Video: the composed result images -- the very
-    images of the PNGs, banner text included with text="draw" -- also become the frames of ``result_imgs.avi``, in global frame order
-    although two batches are in flight (the appends are serialised by batch index).  route "device": the step of make_engine_step hands
-    submit(video_streams=) the finished JPEG files of Engine.encode_jpeg; sizes and flags are copied first, then each file's exact bytes; a
-    flagged frame (its file passed the stream stride) is encoded on the host from a raw copy of that frame and named under 'video_fallback'.
-    route "host": the raw images travel and sd_jpeg_encode_bgr_host makes the same bytes on the writer threads; it needs png="host".
-    Works with images=False too (submit still gets the images then).  The manifest names the files under 'video'.
-    ``profile``: None (default: nothing more is written, copied or launched, the manifest is what it was) or the list of depths of a depth
-    profile: the step of make_engine_step asks process_batch for it (``depths=``) and hands submit(profile=, f2f_profile=) the [n,D,48] /
-    [n,D,64] record tensors, which travel with the batch's other small records in the first phase of the staged transfer; the writer stores
-    ``result_sequence_profile/<name>.txt`` per frame.  The manifest names the depths under 'profile_depths' and the files under 'profile'.
-    ``disp``: None (default: nothing more is written, copied or launched, the manifest is what it was), "gray" or "plasma": the step of
-    make_engine_step also turns every frame's post-processed disparity map into the image of DepthFrame.disp_to_image
-    (semantic_depth.py:681-683) at the original frame size on the GPU (Engine.disparity_image, submit(disp_images=, disp_flags=) or, with
-    png="device", submit(disp_streams=)); the images or streams travel in the staged transfer as the renders do and the writer stores
-    ``result_sequence_disp/<name>_disp.png`` through the PNG route chosen.  The manifest names those files under 'disp' and the frames
-    whose map held a non-finite value (it became byte 0) under 'disp_nonfinite'.  Works with images=False too.
-    ``lines``: None (default: no byte of any file changes, nothing more is copied or launched, the manifest is what it was and submit gets
-    no new keyword) or an OverlayLines: the step of make_engine_step also draws the measured road-width line -- with approach 'both' the
-    fence-to-fence line, with profile= the road's two edges and a rung per depth -- into the composed images on the GPU
-    (Engine.draw_result_lines, right behind the compose launch and before the text, below the banner rows: clip_top = int(0.25 h)), so the
-    PNGs of both routes and the video show them.  submit(lines_flags=, f2f=, cams=, net_size=) carries the per-frame flags and what the
-    writer needs to restate the segments (overlay_segments): each ``_overlay.json`` gains "lines", the manifest 'lines' (the style) and
+    ``text``: "json" (default: the banner of the images stays empty, the text is in the ``_overlay.json`` files) or "draw": it is also
+    rasterised into the composed images on the GPU (Engine.draw_result_text) before they reach either PNG route or the video.
+    ``render``: None or a RenderCamera: every frame's final road cloud and road-width line are drawn behind that camera on the GPU
+    (Engine.render_rw); the manifest names the ``<name>_render.png`` files under 'render'.
+    ``video``: None or a Video: the composed result images -- the very images of the PNGs, lines and banner text included -- also become
+    the frames of ``result_imgs.avi``, in global frame order although two batches are in flight (the appends are serialised by batch
+    index); the manifest names the files under 'video'.  route "device": the finished JPEG files come from the GPU (Engine.encode_jpeg);
+    sizes and flags are copied first, then each file's exact bytes; a flagged frame (its file passed the stream stride) is encoded on the
+    host from a raw copy of that frame and named under 'video_fallback'.  route "host": the raw images travel whole and
+    sd_jpeg_encode_bgr_host makes the same bytes on the writer threads; it needs png="host".  Works with images=False too (submit still
+    gets the images then).
+    ``profile``: None or the list of depths of a depth profile (Engine.process_batch(depths=)): the [n,D,48] / [n,D,64] record tensors
+    travel with the batch's other small records in the first phase.  The manifest names the depths under 'profile_depths' and the files
+    under 'profile'.
+    ``disp``: None, "gray" or "plasma": every frame's post-processed disparity map becomes the image of DepthFrame.disp_to_image
+    (semantic_depth.py:681-683) at the original frame size on the GPU (Engine.disparity_image).  The manifest names the files under
+    'disp' and the frames whose map held a non-finite value (it became byte 0) under 'disp_nonfinite'.  Works with images=False too.
+    ``lines``: None or an OverlayLines: the measured road-width line -- with approach 'both' the fence-to-fence line, with profile= the
+    road's two edges and a rung per depth -- is drawn into the composed images on the GPU (Engine.draw_result_lines, below the banner
+    rows: clip_top = int(0.25 h)), so the PNGs of both routes and the video show them.  The writer restates the segments
+    (overlay_segments) from the frames' cameras and records: each ``_overlay.json`` gains "lines", the manifest 'lines' (the style) and
     'lines_flagged' (the frames of which a segment was skipped because an end point does not project)."""
 
     png, ply_route, text, render, video, disp, lines, _k = "host", "host", "json", None, None, None, None, 0    # (what configure() starts from)
@@ -1248,25 +1249,21 @@ class SequenceOutputs:
         self.road_color, self.fence_color, self.alpha = tuple(road_color), tuple(fence_color), int(alpha)
         self.threads = threads if threads > 0 else default_decode_workers()
         self.img_dir, self.ply_dir = os.path.join(directory, SEQ_IMG_DIR), os.path.join(directory, SEQ_PLY_DIR)
-        self.render_dir = os.path.join(directory, SEQ_RENDER_DIR)
         self.profile_dir = os.path.join(directory, SEQ_PROFILE_DIR)
-        self.disp_dir = os.path.join(directory, SEQ_DISP_DIR)
         self.profile = None
         self.set_profile(profile)
-        for d, on in ((self.img_dir, self.images or self.items), (self.ply_dir, self.ply)):
-            if on:
-                os.makedirs(d, exist_ok=True)
+        for d in [self._dir(f) for f in self._families if f.early_dir] + [self.img_dir] * self.items + [self.ply_dir] * self.ply:
+            os.makedirs(d, exist_ok=True)
         self.rank, self.world, self.shard = 0, 1, (0, len(self.names))
         self._batches = ThreadPoolExecutor(max_workers=2)           # one per batch in flight
         self._writers = ThreadPoolExecutor(max_workers=self.threads)  # PLY / JSON files of a batch
         self._jobs, self._files = [], []
         self._stagers = [_Stager(), _Stager()]                       # one per in-flight slot
         self.manifest = None
-        self.recomputed: list[int] = []                               # global indices of the frames recomputed on bf16x3 (on_range='recompute')
-        self.ply_fallback: list[int] = []                             # global indices of the frames ply="device" sent through rw_ply_bytes
-        self.video_fallback: list[int] = []                           # global indices of the frames video route "device" encoded on the host
-        self.disp_nonfinite: list[int] = []                           # global indices of the frames whose disparity map held a non-finite value
-        self.lines_flagged: list[int] = []                            # global indices of the frames of which lines= skipped a segment
+        # manifest key -> global indices of the frames that took the other path: recomputed on bf16x3 (on_range='recompute'), sent through
+        # rw_ply_bytes by ply="device", encoded on the host by video route "device", a non-finite value in the disparity map, a segment
+        # skipped by lines=
+        self._frames = {key: [] for key in ("recomputed", "ply_fallback", "video_fallback", "disp_nonfinite", "lines_flagged")}
         self._video_writer, self._video_next, self._video_turn = None, 0, threading.Condition()
 
     # ---------------------------------------------------------------- driver interface
@@ -1275,27 +1272,19 @@ class SequenceOutputs:
         """choose the routes described in the class docstring, before the first batch: ``png`` and ``ply`` "host" or "device", ``text`` "json"
         or "draw", ``render`` a RenderCamera, ``video`` a Video, ``disp`` "gray" or "plasma", ``lines`` an OverlayLines; None leaves a choice
         as it is.  Nothing changes when the resulting combination is refused."""
-        lines = self.lines if lines is None else lines
-        png = self.png if png is None else png
-        ply = self.ply_route if ply is None else ply
-        text = self.text if text is None else text
-        render = self.render if render is None else render
-        video = self.video if video is None else video
-        disp = self.disp if disp is None else disp
-        if png not in ("host", "device"):
-            raise ValueError(f"png must be 'host' or 'device', got {png!r}")
-        if ply not in ("host", "device") or isinstance(ply, bool):
-            raise ValueError(f"ply must be 'host' or 'device', got {ply!r}")
-        _check_text(text)
-        _check_render(render)
-        _check_video(video)
-        _check_disp(disp)
-        _check_lines(lines)
+        new = dict(png=png, ply_route=ply, text=text, render=render, video=video, disp=disp, lines=lines)
+        new = {name: getattr(self, name) if v is None else v for name, v in new.items()}
+        if new["png"] not in ("host", "device"):
+            raise ValueError(f"png must be 'host' or 'device', got {new['png']!r}")
+        if new["ply_route"] not in ("host", "device") or isinstance(new["ply_route"], bool):
+            raise ValueError(f"ply must be 'host' or 'device', got {new['ply_route']!r}")
+        for check, name in ((_check_text, "text"), (_check_render, "render"), (_check_video, "video"), (_check_disp, "disp"), (_check_lines, "lines")):
+            check(new[name])
         if self._k:
             raise RuntimeError("SequenceOutputs.configure after the first batch")
-        if png == "device" and video is not None and video.route == "host":
+        if new["png"] == "device" and new["video"] is not None and new["video"].route == "host":
             raise ValueError("Video(route='host') needs png='host': with png='device' no raw image reaches the host")
-        self.png, self.ply_route, self.text, self.render, self.video, self.disp, self.lines = png, ply, text, render, video, disp, lines
+        vars(self).update(new)
 
     def set_lines(self, lines):
         """the OverlayLines the measurement lines are drawn with (before the first batch)"""
@@ -1339,65 +1328,105 @@ class SequenceOutputs:
         """the shard [lo, hi) this rank writes (run_sequence_files calls it before the first batch)"""
         self.rank, self.world, self.shard = int(rank), int(world), (int(lo), int(hi))
 
+    # ---------------------------------------------------------------- the routes, each condition stated once
+    @property
+    def device_png(self) -> bool:
+        """the PNG families arrive as zlib streams (png="device")"""
+        return self.png == "device"
+
+    @property
+    def device_ply(self) -> bool:
+        """PLYs are written and arrive as text (ply="device")"""
+        return self.ply and self.ply_route == "device"
+
+    @property
+    def device_video(self) -> bool:
+        """a video is written and its frames arrive as JPEG files (route "device")"""
+        return self.video is not None and self.video.route == "device"
+
+    @property
+    def wants_final(self) -> bool:
+        """the step has to keep the final road clouds: for the PLYs or the renders"""
+        return self.ply or self.render is not None
+
+    @property
+    def wants_composed(self) -> bool:
+        """the step has to compose the result images: for their PNGs or the video"""
+        return self.images or self.video is not None
+
     @property
     def _images_travel(self) -> bool:
-        """whether the raw images cross to the host whole: for the host PNG route or the host video route"""
-        return self.png == "host" and (self.images or self.video is not None and self.video.route == "host")
+        """whether the raw result images cross to the host whole: for the host PNG route or the host video route"""
+        return not self.device_png and (self.images or self.video is not None and not self.device_video)
+
+    @property
+    def _families(self) -> tuple:
+        """the PNG families that are on"""
+        on = dict(images=self.images, render=self.render is not None, disp=self.disp is not None)
+        return tuple(f for f in _PNG_FAMILIES if on[f.key])
+
+    def _dir(self, family: _PngFamily) -> str:
+        return os.path.join(self.directory, family.subdir)
 
     def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None, ply_text=None, renders=None, render_streams=None,
                video_streams=None, profile=None, f2f_profile=None, disp_images=None, disp_streams=None, disp_flags=None, lines_flags=None,
                f2f=None, cams=None, net_size=None):
-        """one batch: ``records`` u8 [n,104] (sd_rw_result), ``size`` = (h, w) of the original frames, ``images`` u8 [n,h,w,3] (the composed
-        result images) or None, ``final`` = dict(xyz f32 [n,cap,3], rgb u8 [n,cap,3], n i32 [n]) (process_batch(want_final=True)'s
-        road_final) or None, ``png_streams`` = (streams u8 [n,stride], sizes i64 [n]) of Engine.encode_png in place of ``images`` on the
-        device route, ``ply_text`` = (text u8 [capacity], offsets i64 [n+1], flags i32 [n]) of Engine.format_rw_ply on the ply="device" route
-        (beside ``final``, which the flagged frames are written from), ``renders`` = u8 [n,height,width,3] of Engine.render_rw with render= (or
-        ``render_streams`` = Engine.encode_png of them on the png="device" route), ``video_streams`` = (streams u8 [n,stride], sizes i64 [n], flags
-        i32 [n]) of Engine.encode_jpeg with video= on its "device" route (beside ``images``, which a flagged frame is encoded from; its "host"
-        route needs only ``images``), ``profile`` = u8 [n,D,48] of Engine.road_width_profile (process_batch(depths=)'s ``profile``) with
-        profile=, ``f2f_profile`` = u8 [n,D,64] beside it (optional: the dist_f2f column), ``disp_images`` = u8 [n,h,w,3] of
-        Engine.disparity_image with disp= (or ``disp_streams`` = Engine.encode_png of them on the png="device" route) and ``disp_flags`` =
-        its i32 [n] flags beside either (optional: the manifest's 'disp_nonfinite'); with lines=: ``cams`` = the n frames' Camera and
-        ``net_size`` = (h, w) of the network they belong to (host values), ``f2f`` = u8 [n,152] fence records (optional: the fence lines) and
-        ``lines_flags`` = i32 [n] of Engine.draw_result_lines (optional: without them the writer's own restatement flags the frames).  Device or host tensors; the device ones must stay unmodified until the batch is written (they are new
-        tensors of every step)."""
+        """one batch: ``records`` u8 [n,104] (sd_rw_result) and ``size`` = (h, w) of the original frames, then what the choices of the class
+        docstring call for (anything else is ignored).  Device or host tensors; the device ones must stay unmodified until the batch is
+        written (they are new tensors of every step).
+        The PNG families, each as raw images u8 [n,h,w,3] with png="host" or as (streams u8 [n,stride], sizes i64 [n]) of Engine.encode_png
+        with png="device":
+            result images (``images``)      ``images`` (Engine.compose_result_frames)   | ``png_streams``
+            renders (render=)               ``renders`` (Engine.render_rw)              | ``render_streams``
+            disparity images (disp=)        ``disp_images`` (Engine.disparity_image)    | ``disp_streams``
+        ``images`` is also needed raw, on either PNG route and with images=False, by video=: as the frames on its "host" route, beside
+        ``video_streams`` = (streams u8 [n,stride], sizes i64 [n], flags i32 [n]) of Engine.encode_jpeg on its "device" route, where a flagged
+        frame is encoded from it.
+        ``final`` = dict(xyz f32 [n,cap,3], rgb u8 [n,cap,3], n i32 [n]) (process_batch(want_final=True)'s road_final) with ``ply``, and
+        beside it on the ply="device" route (the flagged frames are written from it) ``ply_text`` = (text u8 [capacity], offsets i64 [n+1],
+        flags i32 [n]) of Engine.format_rw_ply.
+        ``profile`` = u8 [n,D,48] of Engine.road_width_profile (process_batch(depths=)'s ``profile``) with profile=, ``f2f_profile`` = u8
+        [n,D,64] beside it (optional: the dist_f2f column).
+        ``disp_flags`` = the i32 [n] flags of Engine.disparity_image with disp= (optional: the manifest's 'disp_nonfinite').
+        With lines=: ``cams`` = the n frames' Camera and ``net_size`` = (h, w) of the network they belong to (host values), ``f2f`` = u8
+        [n,152] fence records (optional: the fence lines) and ``lines_flags`` = i32 [n] of Engine.draw_result_lines (optional: without them
+        the writer's own restatement flags the frames)."""
         if self.manifest is not None:
             raise RuntimeError("SequenceOutputs.submit after close")
         n = int(records.shape[0])
-        device_png, device_video = self.png == "device", self.video is not None and self.video.route == "device"
+        # family key -> its payload: of its two keywords (raw images, zlib streams) the one the PNG route calls for
+        payload = dict(images=(images, png_streams), render=(renders, render_streams), disp=(disp_images, disp_streams))
+        payload = {key: pair[self.device_png] for key, pair in payload.items()}
         if lo < 0 or lo + n > len(self.names):
             raise ValueError(f"frames {lo}..{lo + n - 1} are beyond the {len(self.names)} names")
-        if self.images and (png_streams if device_png else images) is None or self.ply and final is None:
-            raise ValueError("SequenceOutputs: this batch lacks the images (png='device': the streams) / final road clouds the outputs ask for")
-        if self.ply and self.ply_route == "device" and ply_text is None:
-            raise ValueError("SequenceOutputs: ply='device' needs the text of Engine.format_rw_ply (submit(ply_text=))")
-        if self.render is not None and (render_streams if device_png else renders) is None:
-            raise ValueError("SequenceOutputs: render= needs the images of Engine.render_rw (submit(renders=); png='device': render_streams=)")
-        if device_video and video_streams is None:
-            raise ValueError("SequenceOutputs: video route 'device' needs the files of Engine.encode_jpeg (submit(video_streams=))")
-        if self.video is not None and not device_video and images is None:
-            raise ValueError("SequenceOutputs: video route 'host' needs the raw images (submit(images=))")
-        if self.profile is not None and (profile is None or tuple(profile.shape[:2]) != (n, len(self.profile))):
-            raise ValueError("SequenceOutputs: profile= needs the [n, D, 48] records of Engine.road_width_profile (submit(profile=))")
-        if _check_disp(self.disp) is not None and (disp_streams if device_png else disp_images) is None:
-            raise ValueError("SequenceOutputs: disp= needs the images of Engine.disparity_image (submit(disp_images=); png='device': disp_streams=)")
-        if self.lines is not None and (cams is None or net_size is None or len(cams) != n):
-            raise ValueError("SequenceOutputs: lines= needs the frames' cameras and the network size (submit(cams=, net_size=))")
+        lacking = (
+            (self.images and payload["images"] is None or self.ply and final is None,
+             "this batch lacks the images (png='device': the streams) / final road clouds the outputs ask for"),
+            (self.device_ply and ply_text is None, "ply='device' needs the text of Engine.format_rw_ply (submit(ply_text=))"),
+            (self.render is not None and payload["render"] is None,
+             "render= needs the images of Engine.render_rw (submit(renders=); png='device': render_streams=)"),
+            (self.device_video and video_streams is None, "video route 'device' needs the files of Engine.encode_jpeg (submit(video_streams=))"),
+            (self.video is not None and not self.device_video and images is None, "video route 'host' needs the raw images (submit(images=))"),
+            (self.profile is not None and (profile is None or tuple(profile.shape[:2]) != (n, len(self.profile))),
+             "profile= needs the [n, D, 48] records of Engine.road_width_profile (submit(profile=))"),
+            (_check_disp(self.disp) is not None and payload["disp"] is None,
+             "disp= needs the images of Engine.disparity_image (submit(disp_images=); png='device': disp_streams=)"),
+            (self.lines is not None and (cams is None or net_size is None or len(cams) != n),
+             "lines= needs the frames' cameras and the network size (submit(cams=, net_size=))"))
+        for lacks, what in lacking:
+            if lacks:
+                raise ValueError("SequenceOutputs: " + what)
         while len(self._jobs) >= 2:                                    # at most two batches in flight
             self._files.extend(self._jobs.pop(0).result())
         slot = self._k & 1
         batch = _Batch(slot, self._k, lo, tuple(size), self._stagers[slot].event(records), records,
-                       images=images if self._images_travel or device_video else None,      # (device video: a flagged frame is encoded from its raw image)
+                       png={f.key: payload[f.key] for f in self._families},
+                       images=images if self.video is not None else None,
                        final=final,
-                       png_streams=png_streams if device_png else None,
-                       ply_text=ply_text if self.ply and self.ply_route == "device" else None,
-                       renders=renders if self.render is not None and not device_png else None,
-                       render_streams=render_streams if self.render is not None and device_png else None,
-                       video_streams=video_streams if device_video else None,
+                       ply_text=ply_text if self.device_ply else None,
+                       video_streams=video_streams if self.device_video else None,
                        profile=profile if self.profile is not None else None,
                        f2f_profile=f2f_profile if self.profile is not None else None,
-                       disp_images=disp_images if self.disp is not None and not device_png else None,
-                       disp_streams=disp_streams if self.disp is not None and device_png else None,
                        disp_flags=disp_flags if self.disp is not None else None)
         if self.lines is not None:
             batch.lines_flags, batch.f2f, batch.cams, batch.net_size = lines_flags, f2f, list(cams), tuple(net_size)
@@ -1407,7 +1436,12 @@ class SequenceOutputs:
     def mark_recomputed(self, frames):
         """global frame indices whose outputs came from the bf16x3 recompute (make_engine_step(on_range='recompute')): the manifest lists
         their names under 'recomputed'"""
-        self.recomputed.extend(int(i) for i in frames)
+        self._frames["recomputed"].extend(int(i) for i in frames)
+
+    def _flag(self, key: str, lo: int, flags):
+        """the frames lo + i whose flags[i] is non-zero join the manifest's list ``key`` (None: the batch carries no such flags)"""
+        if flags is not None:
+            self._frames[key].extend(lo + int(i) for i in np.flatnonzero(flags))
 
     def close(self, status: str = "ok") -> str:
         """wait for every batch, then write this rank's manifest LAST: the files written and ``status`` ('ok'; 'range_error' / 'error':
@@ -1432,27 +1466,21 @@ class SequenceOutputs:
         self.manifest = os.path.join(self.directory, "manifest_rank{}.json".format(self.rank))
         files = sorted(os.path.relpath(p, self.directory) for p in self._files)
 
-        def named(frames):
-            return [self.names[i] for i in sorted(set(frames))]
+        def below(subdir):
+            return [f for f in files if f.startswith(subdir + os.sep)]
 
+        value = {key: [self.names[i] for i in sorted(set(frames))] for key, frames in self._frames.items()}
+        value.update({f.manifest_key: below(f.subdir) for f in self._families if f.manifest_key})
+        value.update(video=[os.path.relpath(p, self.directory) for p in video_files], profile_depths=self.profile, profile=below(SEQ_PROFILE_DIR),
+                     lines=None if self.lines is None else self.lines.as_dict())
         manifest = dict(rank=self.rank, world=self.world, frames=list(self.shard), status=status, valid=status == "ok", files=files,
-                        recomputed=named(self.recomputed))
-        if self.ply and self.ply_route == "device":
-            manifest["ply_fallback"] = named(self.ply_fallback)
-        if self.render is not None:
-            manifest["render"] = [f for f in files if f.startswith(SEQ_RENDER_DIR + os.sep)]
-        if self.video is not None:
-            manifest["video"] = [os.path.relpath(p, self.directory) for p in video_files]
-            manifest["video_fallback"] = named(self.video_fallback)
-        if self.profile is not None:
-            manifest["profile_depths"] = list(self.profile)
-            manifest["profile"] = [f for f in files if f.startswith(SEQ_PROFILE_DIR + os.sep)]
-        if self.disp is not None:
-            manifest["disp"] = [f for f in files if f.startswith(SEQ_DISP_DIR + os.sep)]
-            manifest["disp_nonfinite"] = named(self.disp_nonfinite)
-        if self.lines is not None:
-            manifest["lines"] = self.lines.as_dict()
-            manifest["lines_flagged"] = named(self.lines_flagged)
+                        recomputed=value["recomputed"])
+        # (the choice, the keys it adds when it is on), in the manifest's order
+        for choice, keys in ((self.device_ply or None, ("ply_fallback",)), (self.render, ("render",)), (self.video, ("video", "video_fallback")),
+                             (self.profile, ("profile_depths", "profile")), (self.disp, ("disp", "disp_nonfinite")),
+                             (self.lines, ("lines", "lines_flagged"))):
+            if choice is not None:
+                manifest.update((key, value[key]) for key in keys)
         with open(self.manifest, "w") as f:
             json.dump(manifest, f, indent=1)
         if err is not None:
@@ -1461,35 +1489,27 @@ class SequenceOutputs:
 
     # ---------------------------------------------------------------- worker side
     def _fetch(self, b: _Batch) -> _HostBatch:
-        """the batch on the host, through its slot's stager, in two phases: first everything whose shape is known -- records, whole
-        images, renders, and the counts, sizes, offsets and flags -- then, once those are there, exactly what they call for: each stream's
-        bytes, the text in front of offsets[n], the clouds of the frames the device did not format (all of them without ``ply_text``) and
-        the raw image of a flagged video frame"""
+        """the batch on the host, through its slot's stager, in the two phases of the class docstring: two synchronisations per batch,
+        however many families are on"""
         st = self._stagers[b.slot]
         with st.behind(b.ev):
-            host = _HostBatch(st.fixed("rec", b.records), images=st.fixed("img", b.images if self._images_travel else None),
-                              renders=st.fixed("render", b.renders), profile=st.fixed("profile", b.profile),
-                              f2f_profile=st.fixed("f2f_profile", b.f2f_profile), disp_images=st.fixed("disp", b.disp_images),
+            host = _HostBatch(st.fixed("rec", b.records), profile=st.fixed("profile", b.profile), f2f_profile=st.fixed("f2f_profile", b.f2f_profile),
                               disp_flags=st.fixed("disp_flags", b.disp_flags), lines_flags=st.fixed("lines_flags", b.lines_flags),
                               f2f=st.fixed("f2f", b.f2f))
+            for key, p in b.png.items():
+                host.png[key] = (None, st.fixed(key + "_sizes", p[1])) if self.device_png else (st.fixed(key, p), None)
+            if self._images_travel and "images" not in b.png:         # images=False: the host video route still needs them whole
+                host.png["images"] = (st.fixed("images", b.images), None)
             counts = None if b.final is None else st.fixed("n", b.final["n"])
-            if b.png_streams is not None:
-                host.png_sizes = st.fixed("png_sizes", b.png_streams[1])
-            if b.render_streams is not None:
-                host.render_sizes = st.fixed("render_sizes", b.render_streams[1])
-            if b.disp_streams is not None:
-                host.disp_sizes = st.fixed("disp_sizes", b.disp_streams[1])
             if b.ply_text is not None:
                 host.ply_offsets, host.ply_flags = st.fixed("ply_offsets", b.ply_text[1]), st.fixed("ply_flags", b.ply_text[2])
             if b.video_streams is not None:
                 host.video_sizes, host.video_flags = st.fixed("video_sizes", b.video_streams[1]), st.fixed("video_flags", b.video_streams[2])
             st.sync()
-            if b.png_streams is not None:
-                host.png = st.rows("png", b.png_streams[0], host.png_sizes)
-            if b.render_streams is not None:
-                host.render_png = st.rows("render_png", b.render_streams[0], host.render_sizes)
-            if b.disp_streams is not None:
-                host.disp_png = st.rows("disp_png", b.disp_streams[0], host.disp_sizes)
+            if self.device_png:
+                for key, p in b.png.items():
+                    sizes = host.png[key][1]
+                    host.png[key] = (st.rows(key + "_png", p[0], sizes), sizes)
             if b.ply_text is not None:
                 host.ply_text = st.fixed("ply_text", b.ply_text[0][:int(host.ply_offsets[-1])])
             if b.final is not None:
@@ -1499,10 +1519,12 @@ class SequenceOutputs:
                 host.clouds = [(xyz[i], rgb[i]) if raw[i] else None for i in range(len(cn))]
             if b.video_streams is not None:
                 host.video = st.rows("video", b.video_streams[0], np.where(host.video_flags != 0, 0, host.video_sizes))
+                # a flagged frame is encoded from its raw image: a row of the whole images where they travel, else a copy of that frame alone
+                whole = host.png["images"][0] if self._images_travel else None
                 for i in np.flatnonzero(host.video_flags):
                     if b.images is None:
                         raise ValueError("SequenceOutputs: a flagged video frame needs the raw images (submit(images=))")
-                    host.video_raw[int(i)] = host.images[i] if host.images is not None else st.fixed(f"video_raw{i}", b.images[i])
+                    host.video_raw[int(i)] = whole[i] if whole is not None else st.fixed(f"video_raw{i}", b.images[i])
             st.sync()
         return host
 
@@ -1511,8 +1533,8 @@ class SequenceOutputs:
         threads; route "device": the files as they came, a flagged frame encoded here from its raw image"""
         q = self.video.quality
         if host.video is None:
-            return list(self._writers.map(lambda a: encode_jpeg_host(a, q), list(host.images)))
-        self.video_fallback.extend(b.lo + i for i in sorted(host.video_raw))
+            return list(self._writers.map(lambda a: encode_jpeg_host(a, q), list(host.png["images"][0])))
+        self._flag("video_fallback", b.lo, host.video_flags)
         return [encode_jpeg_host(host.video_raw[i], q) if i in host.video_raw else host.video[i, :int(size)].tobytes()
                 for i, size in enumerate(host.video_sizes)]
 
@@ -1556,7 +1578,7 @@ class SequenceOutputs:
                                                   f2f_profile=None if host.f2f_profile is None else host.f2f_profile[i], clip_top=int(0.25 * h))
                     doc["lines"] = segments_json(segs)
                     if flag and host.lines_flags is None:
-                        self.lines_flagged.append(b.lo + i)
+                        self._frames["lines_flagged"].append(b.lo + i)
                 with open(path, "w") as f:
                     json.dump(doc, f)
                 return path
@@ -1567,43 +1589,30 @@ class SequenceOutputs:
                 f2 = None if host.f2f_profile is None else np.ascontiguousarray(host.f2f_profile[i]).view(F2FP_DTYPE).reshape(-1)
                 return write_profile(os.path.join(self.profile_dir, "{}.txt".format(names[i])), self.profile, rows, f2)
 
+            def write_family(family):
+                """the batch's files of one PNG family, through whichever route its payload came by"""
+                data, sizes = host.png[family.key]
+                fh, fw = (self.render.height, self.render.width) if family.size == "camera" else (h, w)
+                if not family.early_dir:
+                    os.makedirs(self._dir(family), exist_ok=True)
+                paths = [os.path.join(self._dir(family), nm + family.suffix) for nm in names]
+                if sizes is not None:
+                    return write_png_streams(paths, data, sizes, fh, fw, self.threads)
+                assert data.shape == (n, fh, fw, 3), (data.shape, (n, fh, fw))
+                return write_png_batch(paths, data, self.level, self.threads)
+
             if host.profile is not None:
                 os.makedirs(self.profile_dir, exist_ok=True)
                 futs.extend(self._writers.submit(write_profile_file, i) for i in range(n))
-            if host.lines_flags is not None:
-                self.lines_flagged.extend(b.lo + i for i in range(n) if host.lines_flags[i] != 0)
-            if host.ply_flags is not None:
-                self.ply_fallback.extend(b.lo + i for i in range(n) if host.ply_flags[i] != 0)
+            for key, flags in (("lines_flagged", host.lines_flags), ("ply_fallback", host.ply_flags), ("disp_nonfinite", host.disp_flags)):
+                self._flag(key, b.lo, flags)
             for i in range(n):
                 if self.ply:
                     futs.append(self._writers.submit(write_ply, i))
                 if self.items:
                     futs.append(self._writers.submit(write_items, i))
-            if self.images and self.png == "device":
-                files.extend(write_png_streams([os.path.join(self.img_dir, "{}.png".format(nm)) for nm in names], host.png, host.png_sizes, h, w,
-                                               self.threads))
-            elif self.images:
-                assert host.images.shape == (n, h, w, 3), (host.images.shape, (n, h, w))
-                files.extend(write_png_batch([os.path.join(self.img_dir, "{}.png".format(nm)) for nm in names], host.images, self.level, self.threads))
-            if self.render is not None:
-                os.makedirs(self.render_dir, exist_ok=True)
-                paths = [os.path.join(self.render_dir, "{}_render.png".format(nm)) for nm in names]
-                rh, rw = self.render.height, self.render.width
-                if host.render_png is not None:
-                    files.extend(write_png_streams(paths, host.render_png, host.render_sizes, rh, rw, self.threads))
-                else:
-                    assert host.renders.shape == (n, rh, rw, 3), (host.renders.shape, (n, rh, rw))
-                    files.extend(write_png_batch(paths, host.renders, self.level, self.threads))
-            if self.disp is not None:
-                os.makedirs(self.disp_dir, exist_ok=True)
-                paths = [os.path.join(self.disp_dir, "{}_disp.png".format(nm)) for nm in names]
-                if host.disp_flags is not None:
-                    self.disp_nonfinite.extend(b.lo + i for i in range(n) if host.disp_flags[i] != 0)
-                if host.disp_png is not None:
-                    files.extend(write_png_streams(paths, host.disp_png, host.disp_sizes, h, w, self.threads))
-                else:
-                    assert host.disp_images.shape == (n, h, w, 3), (host.disp_images.shape, (n, h, w))
-                    files.extend(write_png_batch(paths, host.disp_images, self.level, self.threads))
+            for family in self._families:
+                files.extend(write_family(family))
             if self.video is not None:
                 frames = self._video_frames(b, host)
             files.extend(f.result() for f in futs)

@@ -1,9 +1,10 @@
 """Shared by tests/test_sequence_all_routes_cpu.py and tests/test_gpu_sequence_all_routes.py: three batches (3, 2 and 3 frames of
-24 x 32) for one SequenceOutputs with every route on -- png="device", ply="device", render=, video route "device", items -- built from the
-host statements of the device routes (sd_png_encode_zlib_host, sd_ply_format_rw_host, sd_jpeg_encode_bgr_host, outputs.render_rw), so that
-submit() gets what the step of make_engine_step would hand it.  Both staging slots are reused, once by a smaller and once by a larger
-batch.  Frame 1's cloud holds a NaN (PLY flag 1), frame 6 is noise whose video stream is withheld (size 0, flag 1), frame 3 has
-found = 0 and frame 5's cloud is empty."""
+24 x 32) for one SequenceOutputs with every route on -- png="device", ply="device", text="draw", render=, video route "device", disp=,
+profile=, lines=, items -- built from the host statements of the device routes (sd_png_encode_zlib_host, sd_ply_format_rw_host,
+sd_jpeg_encode_bgr_host, outputs.render_rw, outputs.disparity_image, outputs.overlay_segments), so that submit() gets what the step of
+make_engine_step would hand it.  Both staging slots are reused, once by a smaller and once by a larger batch.  Frame 1's cloud holds a
+NaN (PLY flag 1), frame 6 is noise whose video stream is withheld (size 0, flag 1), frame 3 has found = 0, frame 5's cloud is empty,
+frame 2's disparity map holds a NaN (disp flag 1) and frame 4 comes with a non-zero lines flag."""
 import functools
 import os
 
@@ -11,10 +12,11 @@ import numpy as np
 import torch
 
 import jpeg_enc_cases as JC
+import overlay_cases as O
 import ply_device_cases as PD
 import png_device_cases as PN
 from semantic_depth_amd import outputs
-from semantic_depth_amd.engine import RW_DTYPE
+from semantic_depth_amd.engine import RW_DTYPE, RWP_DTYPE, Camera
 
 H, W = 24, 32
 BATCHES = ((0, 3), (3, 2), (5, 3))                       # (first frame, frames)
@@ -25,6 +27,12 @@ CAP = 40
 QUALITY = 90
 VIDEO_STRIDE = 1024 + H * W * 3 // 2                     # the stride the step of make_engine_step gives Engine.encode_jpeg
 CAMERA = outputs.top_camera(48, 40)
+DISP_NAN_FRAME, LINES_FLAGGED_FRAME = 2, 4
+NET = (12, 16)                                           # the network size: of the disparity maps, and what the cameras belong to
+PROFILE = [8.0, 10.0]
+LINES = outputs.OverlayLines()
+# the keywords of the routes that came first; run(every=False) turns on only those
+BASE_KEYWORDS = ("records", "images", "final", "png_streams", "ply_text", "render_streams", "video_streams")
 
 
 def _rows(blobs, stride):
@@ -37,8 +45,14 @@ def _rows(blobs, stride):
 
 @functools.lru_cache(maxsize=None)
 def frames():
-    """per frame: dict(image, case (ply_device_cases: xyz, rgb, rec), render, jpeg)"""
+    """per frame: dict(image, case (ply_device_cases: xyz, rgb, rec), render, jpeg, disp (the disparity image), disp_flag, cam, profile
+    (RWP_DTYPE [2]: found at both depths, the end points in front of the camera), lines_flag)"""
     PD.lib()
+    rng = np.random.default_rng(5)
+    maps = (rng.random((len(NAMES), *NET), dtype=np.float32) * np.float32(0.08)).astype(np.float32)
+    maps[DISP_NAN_FRAME, 3, 4] = np.nan
+    disp, disp_flags = outputs.disparity_image(maps, H, W, "gray", np.full(len(NAMES), 3800.0, np.float32))
+    assert disp_flags.tolist() == [int(i == DISP_NAN_FRAME) for i in range(len(NAMES))]
     out = []
     for i in range(len(NAMES)):
         if i == NOISE_FRAME:
@@ -52,7 +66,15 @@ def frames():
         c = PD.case(NAMES[i], xyz, rec=rec, seed=i)
         found = bool(rec["found"])
         render = outputs.render_rw(c["xyz"], c["rgb"], rec["left_pt"] if found else None, rec["right_pt"] if found else None, CAMERA)
-        out.append(dict(image=image, case=c, render=render, jpeg=JC.encode_host(image, QUALITY)))
+        cam = Camera(cx=NET[1] / 2 + 0.01 * i, cy=NET[0] / 2 + 0.003, f=5.0001 + 0.1 * i, b=0.22, disp_mult=3800.0)
+        profile = np.zeros(len(PROFILE), RWP_DTYPE)
+        for k, d in enumerate(PROFILE):
+            profile[k]["found"], profile[k]["width"], profile[k]["n_window"] = 1, 6.0 - 0.25 * k + 0.01 * i, 5 + i
+            profile[k]["left_pt"] = O.point_at(cam, (H, W), 0.2 + 0.05 * k, 0.9 - 0.2 * k, d, net=NET).astype(np.float32)
+            profile[k]["right_pt"] = O.point_at(cam, (H, W), 0.8 - 0.05 * k, 0.9 - 0.2 * k, d, net=NET).astype(np.float32)
+            profile[k]["x_left"], profile[k]["x_right"] = profile[k]["left_pt"][0], profile[k]["right_pt"][0]
+        out.append(dict(image=image, case=c, render=render, jpeg=JC.encode_host(image, QUALITY), disp=disp[i], disp_flag=int(disp_flags[i]),
+                        cam=cam, profile=profile, lines_flag=int(i == LINES_FLAGGED_FRAME)))
     return out
 
 
@@ -84,26 +106,39 @@ def batches():
                              png_streams=_rows([PN.encode_host(f["image"]) for f in part], PN.bound(H, W)),
                              ply_text=(text, offsets, np.array(flags, np.int32)),
                              render_streams=_rows([PN.encode_host(f["render"]) for f in part], PN.bound(CAMERA.height, CAMERA.width)),
-                             video_streams=_rows(jpegs, VIDEO_STRIDE) + (vflags,))))
+                             video_streams=_rows(jpegs, VIDEO_STRIDE) + (vflags,),
+                             disp_streams=_rows([PN.encode_host(f["disp"]) for f in part], PN.bound(H, W)),
+                             disp_flags=np.array([f["disp_flag"] for f in part], np.int32),
+                             profile=np.stack([f["profile"] for f in part]).view(np.uint8).reshape(n, len(PROFILE), RWP_DTYPE.itemsize).copy(),
+                             lines_flags=np.array([f["lines_flag"] for f in part], np.int32), cams=[f["cam"] for f in part], net_size=NET)))
     return out
 
 
 def _tensors(v, to):
+    """the numpy arrays of ``v`` as tensors placed by ``to``; the host values (the cameras, the network size) as they are"""
     if isinstance(v, dict):
         return {k: _tensors(x, to) for k, x in v.items()}
     if isinstance(v, tuple):
         return tuple(_tensors(x, to) for x in v)
-    return to(torch.from_numpy(v))
+    return to(torch.from_numpy(v)) if isinstance(v, np.ndarray) else v
 
 
-def run(directory, to=lambda t: t, spoil=None):
-    """all batches through one SequenceOutputs with every route on; ``to`` places every tensor (``lambda t: t.cuda()``); ``spoil`` = the
-    index of a batch whose png_streams sizes get one entry too many.  Returns the SequenceOutputs, not closed."""
+def base(kw: dict) -> dict:
+    """the keywords of a batch that run(every=False) needs"""
+    return {k: kw[k] for k in BASE_KEYWORDS}
+
+
+def run(directory, to=lambda t: t, spoil=None, every=True):
+    """all batches through one SequenceOutputs with every route on (``every`` False: only png="device", ply="device", render= and the
+    video, the run this file made before text, disp, profile and lines were added to it); ``to`` places every tensor
+    (``lambda t: t.cuda()``); ``spoil`` = the index of a batch whose png_streams sizes get one entry too many.  Returns the
+    SequenceOutputs, not closed."""
+    more = dict(text="draw", disp="gray", profile=PROFILE, lines=LINES) if every else {}
     outs = outputs.SequenceOutputs(str(directory), NAMES, threads=2, png="device", ply="device", render=CAMERA,
-                                   video=outputs.Video(fps=25, quality=QUALITY, route="device"))
+                                   video=outputs.Video(fps=25, quality=QUALITY, route="device"), **more)
     outs.begin(0, 1, 0, len(NAMES))
     for k, (lo, kw) in enumerate(batches()):
-        kw = dict(kw)
+        kw = dict(kw) if every else base(kw)
         if k == spoil:
             kw["png_streams"] = (kw["png_streams"][0], np.append(kw["png_streams"][1], 0))
         kw = _tensors(kw, to)

@@ -164,14 +164,14 @@ def tree_digest(tree):
 
 
 def test_disp_none_leaves_files_and_manifest_as_they_were(tmp_path):
-    a = A.run(tmp_path / "a")
+    a = A.run(tmp_path / "a", every=False)                 # (the routes that were there before disp=)
     assert a.disp is None
     a.close()
     b = outputs.SequenceOutputs(str(tmp_path / "b"), A.NAMES, threads=2, png="device", ply="device", render=A.CAMERA,
                                 video=outputs.Video(fps=25, quality=A.QUALITY, route="device"), disp=None)
     b.begin(0, 1, 0, len(A.NAMES))
     for lo, kw in A.batches():
-        kw = A._tensors(dict(kw), lambda t: t)
+        kw = A._tensors(A.base(kw), lambda t: t)
         b.submit(lo, kw.pop("records"), (A.H, A.W), **kw, disp_images=None, disp_streams=None)
     b.close()
     ta, tb = A.tree(tmp_path / "a"), A.tree(tmp_path / "b")
@@ -202,7 +202,7 @@ def test_sequence_outputs_write_the_disparity_images(tmp_path, png, cmap):
     for lo, kw in A.batches():
         n = len(kw["records"])
         if png == "device":
-            kw = dict(kw, disp_streams=A._rows([PN.encode_host(im) for im in want[lo:lo + n]], PN.bound(A.H, A.W)), disp_flags=flags[lo:lo + n],
+            kw = dict(A.base(kw), disp_streams=A._rows([PN.encode_host(im) for im in want[lo:lo + n]], PN.bound(A.H, A.W)), disp_flags=flags[lo:lo + n],
                       profile=np.zeros((n, 2, 48), np.uint8))
         else:
             kw = dict(records=kw["records"], disp_images=want[lo:lo + n], disp_flags=flags[lo:lo + n])

@@ -12,5 +12,5 @@ def test_device_tensors_write_the_tree_of_the_host_arrays(tmp_path):
     A.run(tmp_path / "host").close()
     A.run(tmp_path / "device", to=lambda t: t.cuda()).close()
     host, device = A.tree(tmp_path / "host"), A.tree(tmp_path / "device")
-    assert sorted(device) == sorted(host) and len(host) == 4 * len(A.NAMES) + 2
+    assert sorted(device) == sorted(host) and len(host) == 6 * len(A.NAMES) + 2
     assert [k for k in host if device[k] != host[k]] == []

@@ -25,11 +25,25 @@ def test_every_route_in_one_run(tmp_path):
     assert list(frame_io.avi_frames(str(tmp_path / "result_imgs.avi"))) == want
     m = json.load(open(manifest))
     on_disk = sorted(set(A.tree(tmp_path)) - {"manifest_rank0.json"})
-    assert m["files"] == on_disk and len(on_disk) == 4 * len(A.NAMES) + 1
+    # per frame: the result image, its _overlay.json, the PLY, the render, the disparity image and the profile; and the video
+    assert m["files"] == on_disk and len(on_disk) == 6 * len(A.NAMES) + 1
     assert m["status"] == "ok" and m["valid"] is True and m["frames"] == [0, len(A.NAMES)]
     assert m["ply_fallback"] == [A.NAMES[A.NAN_FRAME]] and m["video_fallback"] == [A.NAMES[A.NOISE_FRAME]]
     assert m["video"] == ["result_imgs.avi"] and m["render"] == [f for f in on_disk if f.startswith(outputs.SEQ_RENDER_DIR + os.sep)]
     assert len(m["render"]) == len(A.NAMES)
+    for i, name in enumerate(A.NAMES):
+        assert np.array_equal(frame_io.imread(str(tmp_path / outputs.SEQ_DISP_DIR / f"{name}_disp.png")), fr[i]["disp"]), name
+        assert open(tmp_path / outputs.SEQ_PROFILE_DIR / f"{name}.txt").read() == outputs.profile_text(A.PROFILE, fr[i]["profile"]), name
+        doc = json.load(open(tmp_path / outputs.SEQ_IMG_DIR / f"{name}_overlay.json"))
+        segs, _ = outputs.overlay_segments(fr[i]["case"]["rec"], fr[i]["cam"], A.NET, (A.H, A.W), A.LINES, profile=fr[i]["profile"],
+                                           clip_top=int(0.25 * A.H))
+        assert doc["lines"] == outputs.segments_json(segs) and len(doc["lines"]) >= 2 * len(A.PROFILE), name
+    assert m["disp"] == [os.path.join(outputs.SEQ_DISP_DIR, f"{name}_disp.png") for name in A.NAMES]
+    assert m["profile"] == [os.path.join(outputs.SEQ_PROFILE_DIR, f"{name}.txt") for name in A.NAMES] and m["profile_depths"] == A.PROFILE
+    assert m["disp_nonfinite"] == [A.NAMES[A.DISP_NAN_FRAME]] and m["lines_flagged"] == [A.NAMES[A.LINES_FLAGGED_FRAME]]
+    assert m["lines"] == A.LINES.as_dict()
+    assert list(m) == ["rank", "world", "frames", "status", "valid", "files", "recomputed", "ply_fallback", "render", "video", "video_fallback",
+                       "profile_depths", "profile", "disp", "disp_nonfinite", "lines", "lines_flagged"]
 
 
 def test_a_failing_batch_passes_its_video_turn_on_once(tmp_path):
