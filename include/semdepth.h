@@ -727,6 +727,89 @@ sd_status sd_fence_to_fence(sd_handle* h, const float* fence_xyz, const uint8_t*
                             const sd_rw_result* road, const sd_f2f_params* params_host, sd_f2f_result* results,
                             float* left_xyz, uint8_t* left_rgb, float* right_xyz, uint8_t* right_rgb, void* stream);
 
+/* The bounding box of the cloud that ENTERS a plane fit -- what pcl.plane_grid lays its 5 cm lattice over (semantic_depth.py:215-219,
+ * :294-309): the road cloud after z-cut, MAD(y), MAD(x); each fence side after its MAD(x).  n = that cloud's point count; a, b = the two
+ * in-plane axes of pcl.plane_grid: road (x, z), fences (y, z); the bounds are the float32 np.amin / np.amax of those columns: a NaN in a
+ * column makes both of its bounds NaN, between -0.0 and +0.0 the minimum is -0.0 and the maximum +0.0.  n == 0: the four floats are 0. */
+typedef struct {
+    float lo_a, hi_a, lo_b, hi_b;
+    int32_t n;
+    int32_t pad;                       /* 0 */
+} sd_plane_box;                        /* 24 bytes */
+/* sd_road_width / sd_fence_to_fence with the boxes: boxes_dev (DEVICE, nullable) receives [B] (road) or [B][2] (fence: left, right).
+ * One more launch per plane fit (one workgroup per frame, wave shuffles, no floating-point atomics); every other output is bit-identical
+ * with and without it.  The calls above forward here with boxes_dev = NULL. */
+sd_status sd_road_width_boxes(sd_handle* h, const float* road_xyz, const uint8_t* road_rgb, const int32_t* n_road, int B, int cap,
+                              const sd_rw_params* params_host, sd_rw_result* results, float* final_xyz, uint8_t* final_rgb,
+                              int32_t* n_final, sd_plane_box* boxes_dev, void* stream);
+sd_status sd_fence_to_fence_boxes(sd_handle* h, const float* fence_xyz, const uint8_t* fence_rgb, const int32_t* n_fence, int B, int cap,
+                                  const sd_rw_result* road, const sd_f2f_params* params_host, sd_f2f_result* results,
+                                  float* left_xyz, uint8_t* left_rgb, float* right_xyz, uint8_t* right_rgb, sd_plane_box* boxes_dev,
+                                  void* stream);
+
+/* ---- scene PLYs: the 3D products of semantic_depth.py:404-431 for every frame of a batch, formatted on the GPU ----
+ * A file is the concatenation of the segments its mask selects, in the fixed order of semantic_depth.py:418-431:
+ *   ROAD        the final road cloud (sd_road_width's final_xyz / final_rgb / n_final)
+ *   ROAD_PLANE  the road plane lattice: pcl.plane_grid(axis 1) over the road box, lifted by record.plane, colour 200 200 200
+ *   RW_LINE     the 1001 rows of the road-width line exactly as sd_ply_format_rw writes them, when record.found (colour 250 0 0)
+ *   FENCE_L, FENCE_R   the denoised left / right fence clouds (sd_fence_to_fence's left_* / right_*; sizes f2f.counts[5], [6])
+ *   PLANE_L, PLANE_R   the fence plane lattices: pcl.plane_grid(axis 0) over the fence boxes, lifted by f2f.plane_left / plane_right,
+ *                      colour 40 70 40
+ *   F2F_LINE    the same line rule on f2f.left_pt / right_pt (float64 already), when f2f.ok (colour 0 255 0)
+ * The lattice (semantic_depth_amd/csrc/scene_format.hpp states it once for host and device) is np.arange's under numpy 2 for float32
+ * bounds: n_a = max(0, ceil(fl32(fl32(hi_a - lo_a) / fl32(0.05)))), a_0 = lo_a, a_1 = fl32(lo_a + fl32(0.05)), a_i = lo_a + i * (a_1 - a_0)
+ * in float64; row i is (a_{i mod n_a}, b_{i div n_a}); the lifted coordinate is (c_a * a + c_b * b) + C, without contraction.  A lattice is
+ * absent when its box has n == 0 or n_a * n_b == 0.  The fence inputs (clouds, f2f, fence boxes) are nullable: their segments are absent.
+ * Everything else is the contract of sd_ply_format_rw: zmin = the minimum z over ALL rows of the file, a row is kept iff z > zmin; rows
+ * and header as there; the files PACKED, offsets[B+1], flags[B]; no synchronisation; the result depends neither on the workspace's
+ * contents nor on the order of the workgroups.
+ * flags  0: produced.  1: a coordinate of a selected segment (a NaN box, a lifted coordinate and the line end points among them) is not
+ *        finite or has |v| >= 2^31, or a count is outside its capacity (n_road outside 0..cap_road, the two fence counts negative or
+ *        together above cap_fence, a lattice axis of 2^31 samples or more).  2: the text would pass text_capacity; the frames behind it
+ *        still pack.  3: a selected lattice has more than lattice_cap rows (0 on the host call: no cap).  A flagged frame has size 0. */
+#define SD_SCENE_ROAD 1u
+#define SD_SCENE_ROAD_PLANE 2u
+#define SD_SCENE_RW_LINE 4u
+#define SD_SCENE_FENCE_L 8u
+#define SD_SCENE_FENCE_R 16u
+#define SD_SCENE_PLANE_L 32u
+#define SD_SCENE_PLANE_R 64u
+#define SD_SCENE_F2F_LINE 128u
+#define SD_SCENE_ALL 255u
+/* the device workspace sd_scene_format needs for `mask`, and the text capacity that holds any content: B * (SD_PLY_HEADER_CAP + rows *
+ * SD_PLY_ROW_CAP) with rows = the bound the grid is sized from, the sum over the SELECTED segments only: cap_road (ROAD), cap_fence
+ * (FENCE_L and FENCE_R together), lattice_cap per lattice, SD_PLY_LINE_ROWS per line -- cap_road + cap_fence + 3 * lattice_cap + 2 *
+ * SD_PLY_LINE_ROWS for SD_SCENE_ALL.  SD_ERR_INVALID for B outside 1..65535, a negative cap, a mask beyond SD_SCENE_ALL or rows of
+ * 2^31 - 512 or more. */
+sd_status sd_scene_workspace(int B, int cap_road, int cap_fence, uint32_t lattice_cap, uint32_t mask, size_t* workspace_bytes,
+                             size_t* text_bound);
+/* DEVICE: the road group (xyz f32 [B,cap_road,3], rgb u8, n i32 [B]), the fence group (left / right xyz f32 [B,cap_fence,3], rgb u8; all
+ * four or none), records [B], f2f [B] (nullable; needed by the fence group), road_boxes [B] and fence_boxes [B][2] (nullable: no
+ * lattice) -> the files of `mask` packed into text_dev as sd_ply_format_rw packs its files.  Six launches on `stream` (one thread per
+ * frame makes the segment table: eight row counts, their prefix, n_a and the two steps per lattice, flag 3; then the five of
+ * sd_ply_format_rw over the scene's rows; a workgroup whose 256 rows lie behind the frame's last row exits at once).  SD_ERR_INVALID,
+ * nothing launched: as sd_ply_format_rw, and a fence group that is partly given or lacks f2f_dev, a mask beyond SD_SCENE_ALL. */
+sd_status sd_scene_format(sd_handle* h, const float* road_xyz_dev, const uint8_t* road_rgb_dev, const int32_t* n_road_dev, int cap_road,
+                          const float* left_xyz_dev, const uint8_t* left_rgb_dev, const float* right_xyz_dev, const uint8_t* right_rgb_dev,
+                          int cap_fence, int B, const sd_rw_result* records_dev, const sd_f2f_result* f2f_dev,
+                          const sd_plane_box* road_boxes_dev, const sd_plane_box* fence_boxes_dev, uint32_t mask, uint32_t lattice_cap,
+                          uint8_t* text_dev, size_t text_capacity, uint64_t* offsets_dev, int32_t* flags_dev, void* workspace_dev,
+                          size_t workspace_bytes, void* stream);
+/* HOST: the CPU statement of sd_scene_format for one frame (clouds as long as n_road and f2f->counts[5], [6] say): the same bytes into
+ * out_host[0 .. cap), *size_out = their count, *flag_out = 0; or *flag_out = 1 / 3 and *size_out = 0 under the rules above; or, when the
+ * text is longer than cap, *flag_out = 2, *size_out = the size it needs and nothing written.  SD_ERR_INVALID: a null record, a negative
+ * n_road, a fence cloud without its colours or without f2f, a mask beyond SD_SCENE_ALL. */
+sd_status sd_scene_format_host(const float* road_xyz_host, const uint8_t* road_rgb_host, int n_road, const float* left_xyz_host,
+                               const uint8_t* left_rgb_host, const float* right_xyz_host, const uint8_t* right_rgb_host,
+                               const sd_rw_result* record, const sd_f2f_result* f2f, const sd_plane_box* road_box,
+                               const sd_plane_box* fence_boxes, uint32_t mask, uint32_t lattice_cap, uint8_t* out_host, size_t cap,
+                               size_t* size_out, int32_t* flag_out);
+/* HOST: one lattice alone, by the same rule: box and plane (Cx, Cy, Cz, C) -> *n_a, *n_b and, when xyz_out is given, the n_a * n_b lattice
+ * points f64 [rows,3] in file order (axis 1: the road's (x, z) lattice lifted in y; axis 0: a fence's (y, z) lattice lifted in x).
+ * SD_ERR_INVALID: a null pointer, another axis, a box np.arange refuses, more rows than rows_cap. */
+sd_status sd_scene_lattice_host(const sd_plane_box* box, const double* plane, int axis, uint32_t* n_a, uint32_t* n_b, double* xyz_out,
+                                size_t rows_cap);
+
 /* ---------------------------------------------------------------- depth profile
  * The depth (sd_rw_params.depth, sd_f2f_params.depth) enters the road chain only in its last step and the fence chain only in the two
  * plane intersections.  These calls take the ONE denoised cloud (sd_road_width's final_xyz / n_final) and the ONE set of planes per

@@ -4,7 +4,7 @@ usage: python scripts/kernel_resources.py conv_dma.hip [--all]   (default: only 
 import os, re, subprocess, sys
 root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "semantic_depth_amd", "csrc")
 src = sys.argv[1]
-extra = ["-ffp-contract=off"] if src in ("fuse.hip", "pcl.hip", "ply_gpu.hip", "render_gpu.hip", "overlay_gpu.hip") else []
+extra = ["-ffp-contract=off"] if src in ("fuse.hip", "pcl.hip", "ply_gpu.hip", "scene_gpu.hip", "render_gpu.hip", "overlay_gpu.hip") else []
 r = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(root, src), "-o", "/dev/null",
                     "-Rpass-analysis=kernel-resource-usage"] + extra, capture_output=True, text=True)
 cur = None

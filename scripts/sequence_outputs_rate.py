@@ -2,7 +2,7 @@
 
     python scripts/sequence_outputs_rate.py [--frames 128] [--batch 32] [--precision f16x2] [--level 1] [--threads 0]
                                             [--png host|device|both] [--ply host|device|both] [--repeats 5] [--no-ply]
-                                            [--video off|device|host]
+                                            [--video off|device|host] [--scene host,device [--out profiles/scene_ply_rate.json]]
 
 Setup as bench.py --config 5 (smooth random frames, seeded weights, the monodepth bias calibrated so that the median depth is the
 measuring depth); the frames are written once, untimed.  Each run is timed from the first decode to the last file written
@@ -15,6 +15,12 @@ same way: with "both" (and one --png route) the two PLY routes are timed interle
 bytes per frame (on the device route: the text copied device-to-host) and the raw cloud bytes per frame (15 B per point, the host route's copy).
 --video device|host also writes the result video (SequenceOutputs(video=outputs.Video(route=...))) in every run with files on; the line then
 carries the route and the bytes of the AVI files per frame.  Compare against the same command without it.
+--scene host,device times the scene PLY files (SequenceOutputs(scene=outputs.Scene(route=...)), approach 'both') and nothing else: every
+other file of the tool is off, the listed routes are timed interleaved in one process, --repeats times each.  The line (also written to
+--out) carries each route's frames/s and time per batch (median, min, max), the bytes copied device-to-host per frame, the scene bytes
+written per frame, how many frames of the device route fell back to the host formatter, the time of the new kernels on one batch (device
+events around process_batch with and without want_boxes, and around Engine.format_scene_ply per file) and whether the device route is
+faster by the rule above, in time per batch: median(host) - median(device) > max(host) - min(host).
 """
 import argparse
 import json
@@ -42,6 +48,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5, help="timed runs per route with --png both / --ply both")
     ap.add_argument("--no-ply", dest="ply", action="store_false", help="no road PLYs (images and overlay items only)")
     ap.add_argument("--video", choices=("off", "device", "host"), default="off", help="also write the result video (Motion-JPEG AVI) on this route")
+    ap.add_argument("--scene", default="", help="comma-separated Scene routes to time (host,device): the scene PLY files alone, approach 'both'")
+    ap.add_argument("--out", default="", help="with --scene: also write the JSON line to this file")
     ap.add_argument("--keep", action="store_true", help="keep the written files (default: removed)")
     args = ap.parse_args()
     if args.png == "both" and args.ply_route == "both":
@@ -88,6 +96,16 @@ def main():
         eng.load_weights(L.SD_NET_MONODEPTH, {"dec/disp1/biases": (wm["dec/disp1/biases"] + np.float32(bias)).astype(np.float32)})
 
         threads = args.threads if args.threads > 0 else default_decode_workers()
+
+        if args.scene:
+            line = scene_rates(args, eng, cam, prm, paths, work, threads, B)
+            print(json.dumps(line))
+            if args.out:
+                with open(args.out, "w") as f:
+                    json.dump(line, f, indent=1)
+                    f.write("\n")
+            eng.close()
+            return
 
         def run(with_outputs, frame_paths, tag, route="host"):
             outs = None
@@ -178,6 +196,98 @@ def main():
             print("files kept in", work)
         else:
             shutil.rmtree(work, ignore_errors=True)
+
+
+def scene_rates(args, eng, cam, prm, paths, work, threads, B):
+    """the --scene mode: see the module docstring"""
+    import torch
+
+    from semantic_depth_amd import outputs
+    from semantic_depth_amd.distributed import make_engine_step, run_sequence_files
+    from semantic_depth_amd.engine import BOX_DTYPE, F2F_DTYPE, RW_DTYPE
+    from semantic_depth_amd.frame_io import FrameFeeder
+    routes = tuple(r for r in args.scene.split(",") if r)
+    assert routes and all(r in ("host", "device") for r in routes), routes
+    nb = -(-len(paths) // B)
+
+    def run(route, frame_paths, tag):
+        shutil.rmtree(os.path.join(work, tag), ignore_errors=True)
+        outs = outputs.SequenceOutputs(os.path.join(work, tag), outputs.sequence_names(frame_paths), depth=prm.depth, threads=threads,
+                                       images=False, items=False, ply=False, scene=outputs.Scene(route=route))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rec = run_sequence_files(frame_paths, make_engine_step(eng, lambda i: cam, prm, approach="both", outputs=outs), batch=B, device="cuda")
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, rec, json.load(open(outs.manifest))
+
+    for r in routes:
+        run(r, paths[:B], "warm_" + r)
+        shutil.rmtree(os.path.join(work, "warm_" + r), ignore_errors=True)
+    times, man, rec = {r: [] for r in routes}, {}, None
+    for _ in range(args.repeats):
+        for r in routes:
+            t, rec, man[r] = run(r, paths, "on_" + r)
+            times[r].append(t)
+
+    def size(tag, rel):
+        return os.path.getsize(os.path.join(work, tag, rel))
+
+    line = dict(frames=len(paths), batch=B, precision=args.precision, writer_threads=threads, host_cpus=len(os.sched_getaffinity(0)),
+                repeats=args.repeats, routes={})
+    recs = rec.cpu().numpy().view(RW_DTYPE).reshape(-1)
+    line["found"] = int(recs["found"].sum())
+    for r in routes:
+        per_batch = sorted(t / nb for t in times[r])
+        written = sum(size("on_" + r, f) for f in man[r]["scene"])
+        line["routes"][r] = dict(fps_median=round(len(paths) / float(np.median(times[r])), 1), s_per_batch=[round(v, 4) for v in per_batch],
+                                 s_per_batch_median=round(float(np.median(per_batch)), 4), s_per_batch_min=round(per_batch[0], 4),
+                                 s_per_batch_max=round(per_batch[-1], 4), scene_bytes_per_frame=written // len(paths),
+                                 fallback_frames=len(man[r]["scene_fallback"]))
+    # bytes copied device-to-host per frame, and the new kernels' time, from one batch processed here
+    feeder = FrameFeeder(paths[:B], B, device="cuda")
+    with feeder:
+        frames = next(iter(feeder))[0]
+    fr = eng.resize_cubic(frames)
+    cams = [cam] * B
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+
+    def timed(fn, n=3):
+        out, ms = None, []
+        for _ in range(n + 1):
+            a, b = ev(), ev()
+            a.record()
+            out = fn()
+            b.record()
+            torch.cuda.synchronize()
+            ms.append(a.elapsed_time(b))
+        return out, round(float(np.median(ms[1:])), 3)
+
+    _, ms_plain = timed(lambda: eng.process_batch(fr, cams, prm, approach="both", want_final=True))
+    out, ms_boxes = timed(lambda: eng.process_batch(fr, cams, prm, approach="both", want_final=True, want_boxes=True))
+    sc = outputs.Scene()
+    kernels = dict(process_batch_ms=ms_plain, process_batch_with_boxes_ms=ms_boxes)
+    d2h_device = 0
+    for key in sc.files:
+        (text, offsets, flags), ms = timed(lambda: eng.format_scene_ply(out["road_final"], out["fence_final"], out["records"], out["f2f"],
+                                                                          out["plane_boxes"], outputs.SCENE_FILES[key][1], sc.lattice_cap,
+                                                                          capacity=B * sc.capacity_per_frame))
+        kernels["format_" + key + "_ms"] = ms
+        kernels["format_" + key + "_flags"] = [int(v) for v in np.bincount(flags.cpu().numpy(), minlength=4)]
+        d2h_device += int(offsets[-1].item()) + 12 * B + 8
+    f2 = out["f2f"].cpu().numpy().view(F2F_DTYPE).reshape(-1)
+    points = int(out["road_final"]["n"].sum().item()) + int(f2["counts"][:, 5].sum()) + int(f2["counts"][:, 6].sum())
+    small = B * (RW_DTYPE.itemsize + F2F_DTYPE.itemsize + 3 * BOX_DTYPE.itemsize + 4)
+    if "host" in line["routes"]:
+        line["routes"]["host"]["d2h_bytes_per_frame"] = (points * 15 + small) // B
+    if "device" in line["routes"]:
+        line["routes"]["device"]["d2h_bytes_per_frame"] = (d2h_device + small) // B     # (a batch without fallback frames)
+    line["new_kernels_one_batch"] = kernels
+    if len(routes) == 2:
+        h_, d_ = line["routes"]["host"], line["routes"]["device"]
+        line["device_faster"] = bool(h_["s_per_batch_median"] - d_["s_per_batch_median"] > h_["s_per_batch_max"] - h_["s_per_batch_min"])
+        line["files_identical"] = all(open(os.path.join(work, "on_host", f), "rb").read() == open(os.path.join(work, "on_device", f), "rb").read()
+                                      for f in man["host"]["scene"])
+    return line
 
 
 if __name__ == "__main__":

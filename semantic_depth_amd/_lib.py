@@ -16,6 +16,10 @@ SD_ERR_INVALID, SD_ERR_HIP, SD_ERR_STATE, SD_ERR_NOTFOUND, SD_ERR_FORMAT = -1, -
 SD_ENC_VGG, SD_ENC_RESNET50 = 0, 1
 SD_NET_FCN8S, SD_NET_MONODEPTH = 0, 1
 SD_PLY_ROW_CAP, SD_PLY_HEADER_CAP, SD_PLY_LINE_ROWS = 69, 209, 1001
+# the segments of a scene file (sd_scene_format's mask), in file order
+(SD_SCENE_ROAD, SD_SCENE_ROAD_PLANE, SD_SCENE_RW_LINE, SD_SCENE_FENCE_L, SD_SCENE_FENCE_R, SD_SCENE_PLANE_L, SD_SCENE_PLANE_R,
+ SD_SCENE_F2F_LINE) = (1 << i for i in range(8))
+SD_SCENE_ALL = 255
 SD_TEXT_MAX_BYTES, SD_TEXT_MAX_SEGS, SD_TEXT_MAX_ITEMS, SD_TEXT_MAX_SCALE_Q8, SD_TEXT_MAX_THICKNESS, SD_TEXT_MAX_ORG = 64, 32, 4, 4096, 32, 32768
 SD_RENDER_MAX_EXTENT, SD_RENDER_MAX_POINT = 16384, 16
 SD_PROFILE_MAX_DEPTHS = 256
@@ -206,6 +210,14 @@ SIGNATURES = {
                                             C.c_size_t, _P]),
     "sd_road_width": (C.c_int, [_H, _P, _P, _P, C.c_int, C.c_int, C.POINTER(sd_rw_params), _P, _P, _P, _P, _P]),
     "sd_fence_to_fence": (C.c_int, [_H, _P, _P, _P, C.c_int, C.c_int, _P, C.POINTER(sd_f2f_params), _P, _P, _P, _P, _P, _P]),
+    "sd_road_width_boxes": (C.c_int, [_H, _P, _P, _P, C.c_int, C.c_int, C.POINTER(sd_rw_params), _P, _P, _P, _P, _P, _P]),
+    "sd_fence_to_fence_boxes": (C.c_int, [_H, _P, _P, _P, C.c_int, C.c_int, _P, C.POINTER(sd_f2f_params), _P, _P, _P, _P, _P, _P, _P]),
+    "sd_scene_workspace": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "sd_scene_format": (C.c_int, [_H, _P, _P, _P, C.c_int, _P, _P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_size_t,
+                                  _P, _P, _P, C.c_size_t, _P]),
+    "sd_scene_format_host": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.c_size_t,
+                                       C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    "sd_scene_lattice_host": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), _P, C.c_size_t]),
     "sd_rw_profile_workspace": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "sd_road_width_profile": (C.c_int, [_H, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_double, C.c_double, _P, _P, C.c_size_t, _P]),
     "sd_road_width_profile_host": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_double, C.c_double, _P]),

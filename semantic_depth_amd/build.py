@@ -1,6 +1,6 @@
 """Build libsemdepth.so (HIP, gfx950) in-tree.  `python -m semantic_depth_amd.build` or __graft_entry__.build().
 
-hipcc cross-compiles without a GPU.  fuse.hip / pcl.hip / rw_profile.hip / ply_gpu.hip / render_gpu.hip / disp_image_gpu.hip / overlay_gpu.hip are compiled with -ffp-contract=off because their
+hipcc cross-compiles without a GPU.  fuse.hip / pcl.hip / rw_profile.hip / ply_gpu.hip / scene_gpu.hip / render_gpu.hip / disp_image_gpu.hip / overlay_gpu.hip are compiled with -ffp-contract=off because their
 arithmetic must round exactly like numpy / OpenCV (no fused multiply-add); the conv engine uses the default.
 """
 from __future__ import annotations
@@ -40,6 +40,7 @@ SOURCES = [
     ("jpeg_entropy_gpu.hip", []),
     ("png_in_gpu.hip", []),
     ("ply_gpu.hip", ["-ffp-contract=off"]),
+    ("scene_gpu.hip", ["-ffp-contract=off"]),
     ("text_gpu.hip", []),
     ("overlay_gpu.hip", ["-ffp-contract=off"]),
     ("render_gpu.hip", ["-ffp-contract=off"]),
@@ -54,6 +55,7 @@ SOURCES = [
     ("host_jpeg.cpp", []),
     ("host_jpeg_entropy.cpp", []),
     ("host_ply.cpp", []),
+    ("host_scene.cpp", ["-ffp-contract=off"]),
     ("host_text.cpp", []),
     ("host_overlay.cpp", ["-ffp-contract=off"]),
     ("host_render.cpp", ["-ffp-contract=off"]),
@@ -62,7 +64,7 @@ SOURCES = [
     ("host_seg_eval.cpp", []),
     ("host_disp_image.cpp", ["-ffp-contract=off"]),
 ]
-HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", "jpeg_enc.hpp", "jpeg_enc_gpu.hpp", "jpeg_entropy.hpp", "jpeg_entropy_gpu.hpp", "png_unfilter.hpp", "png_in_gpu.hpp", "ply_format.hpp", "ply_gpu.hpp", "text_draw.hpp", "text_gpu.hpp", "overlay_rule.hpp", "overlay_gpu.hpp", "render_rule.hpp", "render_gpu.hpp", "rw_profile.hpp", "rw_profile_gpu.hpp", "pil_resample.hpp", "seg_eval_gpu.hpp", "disp_image_rule.hpp", "disp_image_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
+HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", "jpeg_enc.hpp", "jpeg_enc_gpu.hpp", "jpeg_entropy.hpp", "jpeg_entropy_gpu.hpp", "png_unfilter.hpp", "png_in_gpu.hpp", "ply_format.hpp", "ply_gpu.hpp", "scene_format.hpp", "scene_gpu.hpp", "text_draw.hpp", "text_gpu.hpp", "overlay_rule.hpp", "overlay_gpu.hpp", "render_rule.hpp", "render_gpu.hpp", "rw_profile.hpp", "rw_profile_gpu.hpp", "pil_resample.hpp", "seg_eval_gpu.hpp", "disp_image_rule.hpp", "disp_image_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
 
 
 def _hipcc() -> str:

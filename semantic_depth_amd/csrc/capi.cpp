@@ -18,6 +18,7 @@
 #include "jpeg_entropy_gpu.hpp"
 #include "png_in_gpu.hpp"
 #include "ply_gpu.hpp"
+#include "scene_gpu.hpp"
 #include "text_gpu.hpp"
 #include "overlay_gpu.hpp"
 #include "render_gpu.hpp"
@@ -917,6 +918,48 @@ sd_status sd_ply_format_rw(sd_handle* h, const float* xyz_dev, const uint8_t* rg
     return SD_OK;
 }
 
+static bool scene_dims_ok(int B, int cap_road, int cap_fence, uint32_t lattice_cap, uint32_t mask) {
+    return B >= 1 && B <= 65535 && cap_road >= 0 && cap_fence >= 0 && !(mask & ~(uint32_t)SD_SCENE_ALL) &&
+           sdscene::rows_bound(cap_road, cap_fence, lattice_cap, mask) <= (uint64_t)sdscene::kMaxRows - sdply::kBlockRows;
+}
+
+sd_status sd_scene_workspace(int B, int cap_road, int cap_fence, uint32_t lattice_cap, uint32_t mask, size_t* workspace_bytes, size_t* text_bound) {
+    if (!scene_dims_ok(B, cap_road, cap_fence, lattice_cap, mask)) return SD_ERR_INVALID;
+    if (workspace_bytes) *workspace_bytes = scene_workspace_bytes(B, cap_road, cap_fence, lattice_cap, mask);
+    if (text_bound) *text_bound = scene_text_bound(B, cap_road, cap_fence, lattice_cap, mask);
+    return SD_OK;
+}
+
+sd_status sd_scene_format(sd_handle* h, const float* road_xyz_dev, const uint8_t* road_rgb_dev, const int32_t* n_road_dev, int cap_road,
+                          const float* left_xyz_dev, const uint8_t* left_rgb_dev, const float* right_xyz_dev, const uint8_t* right_rgb_dev,
+                          int cap_fence, int B, const sd_rw_result* records_dev, const sd_f2f_result* f2f_dev,
+                          const sd_plane_box* road_boxes_dev, const sd_plane_box* fence_boxes_dev, uint32_t mask, uint32_t lattice_cap,
+                          uint8_t* text_dev, size_t text_capacity, uint64_t* offsets_dev, int32_t* flags_dev, void* workspace_dev,
+                          size_t workspace_bytes, void* stream) {
+    if (!h || !road_xyz_dev || !road_rgb_dev || !n_road_dev || !records_dev || !text_dev || !offsets_dev || !flags_dev || !workspace_dev)
+        return fail(h, SD_ERR_INVALID, "sd_scene_format: null pointer");
+    const int fence_ptrs = (left_xyz_dev != nullptr) + (left_rgb_dev != nullptr) + (right_xyz_dev != nullptr) + (right_rgb_dev != nullptr);
+    if ((fence_ptrs != 0 && fence_ptrs != 4) || (fence_ptrs && !f2f_dev))
+        return fail(h, SD_ERR_INVALID, "sd_scene_format: the fence group is all four arrays and f2f_dev, or none");
+    if (mask & ~(uint32_t)SD_SCENE_ALL) return fail(h, SD_ERR_INVALID, "sd_scene_format: mask beyond SD_SCENE_ALL");
+    if (!scene_dims_ok(B, cap_road, cap_fence, lattice_cap, mask))
+        return fail(h, SD_ERR_INVALID, "sd_scene_format: B must be 1..65535, the caps >= 0 and the row bound below 2^31 - 512");
+    // every index the kernels form follows from B, the caps, lattice_cap and these capacities: nothing is launched otherwise
+    if (workspace_bytes < scene_workspace_bytes(B, cap_road, cap_fence, lattice_cap, mask))
+        return fail(h, SD_ERR_INVALID, "sd_scene_format: workspace smaller than sd_scene_workspace reports");
+    auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+    if (mis(workspace_dev, 15) || mis(offsets_dev, 7) || mis(records_dev, 7) || mis(f2f_dev, 7) || mis(flags_dev, 3) || mis(road_xyz_dev, 3) ||
+        mis(n_road_dev, 3) || mis(left_xyz_dev, 3) || mis(right_xyz_dev, 3) || mis(road_boxes_dev, 3) || mis(fence_boxes_dev, 3))
+        return fail(h, SD_ERR_INVALID, "sd_scene_format: workspace_dev must be 16-byte, offsets_dev and the records 8-byte, the rest naturally aligned");
+    SceneBatch in{};
+    in.road_xyz = road_xyz_dev; in.road_rgb = road_rgb_dev; in.n_road = n_road_dev; in.cap_road = cap_road;
+    in.left_xyz = left_xyz_dev; in.left_rgb = left_rgb_dev; in.right_xyz = right_xyz_dev; in.right_rgb = right_rgb_dev; in.cap_fence = cap_fence;
+    in.B = B; in.records = records_dev; in.f2f = f2f_dev; in.road_boxes = road_boxes_dev; in.fence_boxes = fence_boxes_dev;
+    in.mask = mask; in.lattice_cap = lattice_cap;
+    HIPCHK(h, launch_scene_format(in, text_dev, text_capacity, offsets_dev, flags_dev, static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
+    return SD_OK;
+}
+
 size_t sd_text_workspace_bytes(int B) { return B < 1 || B > 65535 ? 0 : text_workspace_bytes(B); }
 
 sd_status sd_text_draw_rw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int dst_w, const sd_rw_result* records_dev, const char* depth_text,
@@ -1151,6 +1194,14 @@ sd_status sd_fuse_backproject_sweep(sd_handle* h, const float* disp_pp, const ui
 sd_status sd_road_width(sd_handle* h, const float* road_xyz, const uint8_t* road_rgb, const int32_t* n_road, int B, int cap,
                         const sd_rw_params* prm, sd_rw_result* results, float* final_xyz, uint8_t* final_rgb, int32_t* n_final,
                         void* stream) {
+    return sd_road_width_boxes(h, road_xyz, road_rgb, n_road, B, cap, prm, results, final_xyz, final_rgb, n_final, nullptr, stream);
+}
+
+static_assert(sizeof(PlaneBoxDev) == sizeof(sd_plane_box) && sizeof(sd_plane_box) == 24, "sd_plane_box is 24 bytes");
+
+sd_status sd_road_width_boxes(sd_handle* h, const float* road_xyz, const uint8_t* road_rgb, const int32_t* n_road, int B, int cap,
+                              const sd_rw_params* prm, sd_rw_result* results, float* final_xyz, uint8_t* final_rgb, int32_t* n_final,
+                              sd_plane_box* boxes_dev, void* stream) {
     if (!h || !road_xyz || !n_road || !prm || !results || B <= 0 || B > h->max_batch || cap <= 0 || cap > h->cap)
         return fail(h, SD_ERR_INVALID, "sd_road_width: bad arguments");
     if (!h->bound) return fail(h, SD_ERR_STATE, "sd_bind_memory first");
@@ -1171,6 +1222,8 @@ sd_status sd_road_width(sd_handle* h, const float* road_xyz, const uint8_t* road
     HIPCHK(h, launch_filter_coord({road_xyz, road_rgb, n_road}, {A, cA, n1}, B, cap, F_LT_NEG, 2, prm->z_cut, cmp, s));
     HIPCHK(h, launch_mad_filter({A, cA, n1}, {B2, cB, n2}, B, cap, 1, prm->mad_y, nullptr, cmp, s));
     HIPCHK(h, launch_mad_filter({B2, cB, n2}, {A, cA, n3}, B, cap, 0, prm->mad_x, nullptr, cmp, s));
+    // (the box of the cloud that enters the fit, for the plane lattice of the scene files)
+    if (boxes_dev) HIPCHK(h, launch_plane_box({A, cA, n3}, B, cap, 1, reinterpret_cast<PlaneBoxDev*>(boxes_dev), 1, 0, s));
     HIPCHK(h, launch_plane_filter({A, cA, n3}, {B2, cB, n4}, B, cap, 1, prm->plane_thr, plane, cmp, s));
     const int32_t* nlast = n4;
     const float* fin = B2;
@@ -1195,6 +1248,13 @@ sd_status sd_road_width(sd_handle* h, const float* road_xyz, const uint8_t* road
 sd_status sd_fence_to_fence(sd_handle* h, const float* fence_xyz, const uint8_t* fence_rgb, const int32_t* n_fence, int B, int cap,
                             const sd_rw_result* road, const sd_f2f_params* prm, sd_f2f_result* results, float* left_xyz,
                             uint8_t* left_rgb, float* right_xyz, uint8_t* right_rgb, void* stream) {
+    return sd_fence_to_fence_boxes(h, fence_xyz, fence_rgb, n_fence, B, cap, road, prm, results, left_xyz, left_rgb, right_xyz, right_rgb, nullptr,
+                                   stream);
+}
+
+sd_status sd_fence_to_fence_boxes(sd_handle* h, const float* fence_xyz, const uint8_t* fence_rgb, const int32_t* n_fence, int B, int cap,
+                                  const sd_rw_result* road, const sd_f2f_params* prm, sd_f2f_result* results, float* left_xyz,
+                                  uint8_t* left_rgb, float* right_xyz, uint8_t* right_rgb, sd_plane_box* boxes_dev, void* stream) {
     if (!h || !fence_xyz || !n_fence || !road || !prm || !results || B <= 0 || B > h->max_batch || cap <= 0 || cap > h->cap)
         return fail(h, SD_ERR_INVALID, "sd_fence_to_fence: bad arguments");
     if (!h->bound) return fail(h, SD_ERR_STATE, "sd_bind_memory first");
@@ -1218,8 +1278,11 @@ sd_status sd_fence_to_fence(sd_handle* h, const float* fence_xyz, const uint8_t*
     HIPCHK(h, launch_filter_coord({A, cA, C(1)}, {A, cA, C(2)}, B, cap, F_ABS_LT, 2, prm->z_max, nullptr, s));
     HIPCHK(h, launch_extract_pcls({A, cA, C(2)}, {Lb, cL, C(3)}, {Rb, cR, C(4)}, B, cap, 0, nullptr, s));
     HIPCHK(h, launch_mad_filter({Lb, cL, C(3)}, {Lb, cL, C(5)}, B, cap, 0, prm->mad_left, nullptr, nullptr, s));
+    // (the fits filter in place: each box is taken before its fit)
+    if (boxes_dev) HIPCHK(h, launch_plane_box({Lb, cL, C(5)}, B, cap, 0, reinterpret_cast<PlaneBoxDev*>(boxes_dev), 2, 0, s));
     HIPCHK(h, launch_plane_filter({Lb, cL, C(5)}, {Lb, cL, C(5)}, B, cap, 0, prm->plane_thr, p_left, nullptr, s));
     HIPCHK(h, launch_mad_filter({Rb, cR, C(4)}, {Rb, cR, C(6)}, B, cap, 0, prm->mad_right, nullptr, nullptr, s));
+    if (boxes_dev) HIPCHK(h, launch_plane_box({Rb, cR, C(6)}, B, cap, 0, reinterpret_cast<PlaneBoxDev*>(boxes_dev), 2, 1, s));
     HIPCHK(h, launch_plane_filter({Rb, cR, C(6)}, {Rb, cR, C(6)}, B, cap, 0, prm->plane_thr, p_right, nullptr, s));
     // denoised left / right fence clouds (the reference writes them to *_FENCE.ply, semantic_depth.py:412-415); sizes = counts[5], counts[6]
     if (left_xyz) HIPCHK(h, hipMemcpyAsync(left_xyz, Lb, (size_t)B * cap * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));

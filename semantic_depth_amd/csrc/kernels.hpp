@@ -394,6 +394,12 @@ size_t cmp_scratch_bytes(int B);
 hipError_t launch_filter_coord(CloudView in, CloudOut out, int B, int cap, int kind, int axis, double t, void* cscratch, hipStream_t s);
 hipError_t launch_mad_filter(CloudView in, CloudOut out, int B, int cap, int axis, double thr, float* stats, void* cscratch, hipStream_t s);
 hipError_t launch_plane_filter(CloudView in, CloudOut out, int B, int cap, int axis, double thr, double* coeff, void* cscratch, hipStream_t s);
+struct PlaneBoxDev {   // layout == sd_plane_box
+    float lo_a, hi_a, lo_b, hi_b; int32_t n, pad;
+};
+// the box of the cloud a plane fit of `axis` is about to read -> boxes[b * stride + slot]; launched BEFORE launch_plane_filter (which may
+// filter in place)
+hipError_t launch_plane_box(CloudView in, int B, int cap, int axis, PlaneBoxDev* boxes, int stride, int slot, hipStream_t s);
 // fence chain
 struct F2fResultDev {   // layout == sd_f2f_result
     double dist; double left_pt[3], right_pt[3]; double plane_left[4], plane_right[4];

@@ -637,6 +637,56 @@ hipError_t launch_plane_filter(CloudView in, CloudOut out, int B, int cap, int a
     return hipGetLastError();
 }
 
+// The bounding box of the cloud that enters a plane fit (sd_plane_box): np.amin / np.amax of the two in-plane columns, float32.  On the
+// monotone keys of f2key -0.0 sorts below +0.0; a NaN in a column makes both of its bounds NaN.  One workgroup per frame, wave shuffles.
+__global__ __launch_bounds__(TB) void plane_box_kernel(CloudView in, int cap, int axis, PlaneBoxDev* boxes, int stride, int slot) {
+    __shared__ unsigned s_key[4][NW];
+    __shared__ unsigned s_nan[NW];
+    const int b = blockIdx.x;
+    const float* xyz = in.xyz + (size_t)b * cap * 3;
+    const int n = min(in.n[b], cap);
+    const int ia = axis == 0 ? 1 : 0, ib = axis == 2 ? 1 : 2;
+    unsigned lo_a = 0xFFFFFFFFu, hi_a = 0u, lo_b = 0xFFFFFFFFu, hi_b = 0u, nan = 0u;      // nan: bit 0 column a, bit 1 column b
+#pragma unroll 4
+    for (int i = threadIdx.x; i < n; i += TB) {
+        const float va = xyz[(size_t)i * 3 + ia], vb = xyz[(size_t)i * 3 + ib];
+        const unsigned ka = f2key(va), kb = f2key(vb);
+        nan |= (va != va ? 1u : 0u) | (vb != vb ? 2u : 0u);
+        lo_a = ka < lo_a ? ka : lo_a; hi_a = ka > hi_a ? ka : hi_a;
+        lo_b = kb < lo_b ? kb : lo_b; hi_b = kb > hi_b ? kb : hi_b;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        unsigned t;
+        t = __shfl_xor(lo_a, o); lo_a = t < lo_a ? t : lo_a;
+        t = __shfl_xor(hi_a, o); hi_a = t > hi_a ? t : hi_a;
+        t = __shfl_xor(lo_b, o); lo_b = t < lo_b ? t : lo_b;
+        t = __shfl_xor(hi_b, o); hi_b = t > hi_b ? t : hi_b;
+        nan |= __shfl_xor(nan, o);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { s_key[0][w] = lo_a; s_key[1][w] = hi_a; s_key[2][w] = lo_b; s_key[3][w] = hi_b; s_nan[w] = nan; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int v = 1; v < NW; ++v) {
+            lo_a = s_key[0][v] < lo_a ? s_key[0][v] : lo_a; hi_a = s_key[1][v] > hi_a ? s_key[1][v] : hi_a;
+            lo_b = s_key[2][v] < lo_b ? s_key[2][v] : lo_b; hi_b = s_key[3][v] > hi_b ? s_key[3][v] : hi_b;
+            nan |= s_nan[v];
+        }
+        const float qnan = __uint_as_float(0x7fc00000u);
+        PlaneBoxDev r;
+        r.lo_a = n <= 0 ? 0.f : ((nan & 1u) ? qnan : key2f(lo_a)); r.hi_a = n <= 0 ? 0.f : ((nan & 1u) ? qnan : key2f(hi_a));
+        r.lo_b = n <= 0 ? 0.f : ((nan & 2u) ? qnan : key2f(lo_b)); r.hi_b = n <= 0 ? 0.f : ((nan & 2u) ? qnan : key2f(hi_b));
+        r.n = n < 0 ? 0 : n;
+        r.pad = 0;
+        boxes[(size_t)b * stride + slot] = r;
+    }
+}
+hipError_t launch_plane_box(CloudView in, int B, int cap, int axis, PlaneBoxDev* boxes, int stride, int slot, hipStream_t s) {
+    hipLaunchKernelGGL(plane_box_kernel, dim3(B), dim3(TB), 0, s, in, cap, axis, boxes, stride, slot);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------ K24 end points
 // pcl.get_end_points_of_road / get_end_points_of_segment (pcl.py:271-313) + width (semantic_depth.py:259):
 // window -(depth+w) < z < -(depth-w) in float64; first row with min x, first row with max x.

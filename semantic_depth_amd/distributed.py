@@ -96,7 +96,7 @@ def run_sequence(load_frames, n_frames: int, step, batch: int = 32, group=None, 
 
 def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", workers: int = 0, outputs=None, jpeg: str = "host",
                        engine=None, png: str | None = None, ply: str | None = None, text: str | None = None, render=None, video=None,
-                       png_in: str | None = None, disp: str | None = None, lines=None) -> torch.Tensor:
+                       png_in: str | None = None, disp: str | None = None, lines=None, scene=None) -> torch.Tensor:
     """run_sequence on FILES (semantic_depth_cityscapes_sequence.py:689-701 reads ``sorted(glob(input_folder))`` frame by frame): rank r
     decodes ONLY its shard of the sorted list -- frame_io.FrameFeeder: one native call per batch into pinned staging, upload one batch
     ahead, ``workers`` decode threads (default: this rank's share of the node's CPUs, frame_io.default_decode_workers) -- and hands every
@@ -111,7 +111,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     (FrameFeeder.entropy_fallback names them); the frames are the same bytes on all three.
     ``png_in`` (None = "host" | "device") is the feeder's ``png=`` (``png`` here already names the output writer): with "device" the PNG
     frames are only inflated on the host and their scanlines reconstructed on the GPU by ``engine``; the frames are the same bytes.
-    ``png``, ``ply``, ``text``, ``render``, ``video``, ``disp``, ``lines`` (None = what the SequenceOutputs was built with) go to
+    ``png``, ``ply``, ``text``, ``render``, ``video``, ``disp``, ``lines``, ``scene`` (None = what the SequenceOutputs was built with) go to
     SequenceOutputs.configure before the first batch: its class docstring describes the choices, make_engine_step's what the step launches
     for each."""
     from .frame_io import FrameFeeder
@@ -125,7 +125,7 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     if outputs is not None:
         if len(outputs.names) != n_frames:
             raise ValueError(f"SequenceOutputs has {len(outputs.names)} names for {n_frames} frames")
-        outputs.configure(png, ply, text, render, video, disp, lines)
+        outputs.configure(png, ply, text, render, video, disp, lines, scene)
         outputs.begin(rank, world, lo, hi)
     try:
         parts = []
@@ -155,7 +155,8 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
 
 
 def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outputs=None, on_range: str | None = None, png: str | None = None,
-                     ply: str | None = None, text: str | None = None, render=None, video=None, depths=None, disp: str | None = None, lines=None):
+                     ply: str | None = None, text: str | None = None, render=None, video=None, depths=None, disp: str | None = None, lines=None,
+                     scene=None):
     """``step`` for run_sequence on a real Engine: host or device u8 frames of any size -> (cubic resize to the network shape on
     the GPU, semantic_depth_cityscapes_sequence.py:123-130) -> Engine.process_batch -> record buffer.
     ``camera_of(global_frame_index) -> engine.Camera`` (the sequence tool: cx = 1048.64/4·s, cy = 519.277/4·s, disp_mult = 3800).
@@ -164,13 +165,16 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
     ``on_range`` (None = the engine's own mode; else it must match Engine(on_range=)): with 'recompute' the frames that left the fp16 range
     are recomputed on bf16x3 inside process_batch, so every batch's records, images and PLYs are final before gather_records and no rank
     raises from ``step.finish`` for them; ``step.recomputed`` (and the manifest's 'recomputed' names) lists those frames.
-    ``png``, ``ply``, ``text``, ``render``, ``video``, ``disp``, ``lines`` (None = what ``outputs`` was built with) go to
+    ``png``, ``ply``, ``text``, ``render``, ``video``, ``disp``, ``lines``, ``scene`` (None = what ``outputs`` was built with) go to
     SequenceOutputs.configure, whose class docstring describes the choices.  ``depths`` (None likewise) becomes the outputs' profile, and
     must agree with one already chosen; without ``outputs`` it asks for nothing.
     What the step launches for them, all on its own stream and in this order (a choice that is off launches nothing):
-      1. Engine.process_batch -- with want_final when PLYs or renders are on, so that it keeps the final road clouds, and with depths= for a
-         profile (two launches behind the road chain, one more with approach 'both').
+      1. Engine.process_batch -- with want_final when PLYs, renders or scene files are on, so that it keeps the final road (and fence)
+         clouds, with depths= for a profile (two launches behind the road chain, one more with approach 'both') and with want_boxes for
+         scene= (one launch beside each plane fit).
       2. ply="device": Engine.format_rw_ply, the text of the ``_rw.ply`` files from the final clouds and the records.
+         scene= on its "device" route: Engine.format_scene_ply once per file of Scene.files (six launches each; the ``_FENCE`` file only
+         with approach 'both'), with Scene.capacity_per_frame bytes per frame of the batch as the text capacity.
       3. render=: Engine.render_rw behind that camera, then on the device PNG route Engine.encode_png of the renders.
       4. disp=: Engine.disparity_image of ``disp_pp`` at the original frame size with the frames' Camera.disp_mult as multipliers (five
          launches plus the resample's two), then on the device PNG route Engine.encode_png of the images.
@@ -188,7 +192,7 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
         raise ValueError(f"make_engine_step(on_range={on_range!r}) on an engine built with on_range={getattr(engine, 'on_range', 'raise')!r}")
     prm = params or RoadWidthParams()
     if outputs is not None:
-        outputs.configure(png, ply, text, render, video, disp, lines)
+        outputs.configure(png, ply, text, render, video, disp, lines, scene)
         if depths is not None:
             want = [float(d) for d in np.asarray(depths, dtype=np.float64).reshape(-1)]
             if outputs.profile is None:
@@ -220,14 +224,23 @@ def make_engine_step(engine, camera_of, params=None, approach: str = "rw", outpu
             note(lo)
             return rec
         # (depths=None is process_batch's default: no profile)
-        out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.wants_final, depths=outputs.profile)
+        want_scene = outputs.scene is not None
+        out = engine.process_batch(fr, cams, prm, approach=approach, want_final=outputs.wants_final, depths=outputs.profile,
+                                   **(dict(want_boxes=True) if want_scene else {}))
         note(lo)
         rec = out["records"]
-        more = dict(images=None, final=out.get("road_final") if outputs.ply else None)
+        more = dict(images=None, final=out.get("road_final") if outputs.ply or want_scene else None)
         if outputs.profile is not None:
             more.update(profile=out["profile"], f2f_profile=out.get("f2f_profile"))
         if outputs.device_ply:                                     # the text of the PLY files
             more["ply_text"] = engine.format_rw_ply(out["road_final"], rec)
+        if want_scene:                                             # the scene files: their inputs and, on the device route, their text
+            from .outputs import SCENE_FILES
+            sc = more["scene"] = dict(fence_final=out.get("fence_final"), f2f=out.get("f2f"), boxes=out["plane_boxes"], text=None)
+            if outputs.device_scene:
+                sc["text"] = {key: engine.format_scene_ply(out["road_final"], sc["fence_final"], rec, sc["f2f"], sc["boxes"], SCENE_FILES[key][1],
+                                                           outputs.scene.lattice_cap, capacity=fr.shape[0] * outputs.scene.capacity_per_frame)
+                              for key in outputs.scene.files if key != "fence" or sc["fence_final"] is not None}
         if outputs.render is not None:                             # the rendered clouds, behind the road chain
             more.update(png_keyword("renders", "render_streams", engine.render_rw(out["road_final"], rec, outputs.render)[0]))
         if outputs.disp is not None:                               # the disparity images, behind the networks

@@ -29,6 +29,9 @@ RWP_DTYPE = np.dtype([("width", "<f8"), ("x_left", "<f4"), ("x_right", "<f4"), (
 assert RWP_DTYPE.itemsize == C.sizeof(L.sd_rw_depth_result) == 48
 F2FP_DTYPE = np.dtype([("dist", "<f8"), ("left_pt", "<f8", 3), ("right_pt", "<f8", 3), ("ok", "<i4"), ("reserved", "<i4")])
 assert F2FP_DTYPE.itemsize == C.sizeof(L.sd_f2f_depth_result) == 64
+# the box of the cloud that enters a plane fit (sd_plane_box): what the plane lattices of the scene files are laid over
+BOX_DTYPE = np.dtype([("lo_a", "<f4"), ("hi_a", "<f4"), ("lo_b", "<f4"), ("hi_b", "<f4"), ("n", "<i4"), ("pad", "<i4")])
+assert BOX_DTYPE.itemsize == 24
 
 
 @dataclass
@@ -634,6 +637,62 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_ply_format_rw")
         return out[:capacity], offsets, flags
 
+    def format_scene_ply(self, final: dict, fence_final: dict | None, records: torch.Tensor, f2f: torch.Tensor | None, boxes: dict | None,
+                         mask: int = L.SD_SCENE_ALL, lattice_cap: int = 1 << 18, capacity: int | None = None, out: torch.Tensor | None = None):
+        """the device half of the scene PLY writer (sd_scene_format): ``final`` / ``fence_final`` = process_batch(want_final=True)'s
+        road_final and fence_final (None with approach 'rw': the fence segments are absent), ``records`` u8 [B,104], ``f2f`` u8 [B,152] (None
+        likewise) and ``boxes`` = process_batch(want_boxes=True)'s plane_boxes (None: no lattice) -> (``text`` u8 [capacity], ``offsets`` i64
+        [B+1], ``flags`` i32 [B]) device tensors packed as format_rw_ply packs them; ``mask`` selects the segments (L.SD_SCENE_*): all eight
+        for the scene file, ROAD for ``_ROAD.ply``, FENCE_L | FENCE_R for ``_FENCE.ply``.  The bytes are outputs.scene_ply_bytes'.
+        flags[b] = 1: a non-finite or |v| >= 2^31 coordinate, a NaN box, a count outside its capacity (write the frame through
+        scene_ply_bytes); 2: its text would pass ``capacity``; 3: a lattice has more than ``lattice_cap`` rows (both: sd_scene_format_host);
+        all have size 0.  ``capacity`` None: the bound of the mask, B * (209 + rows * 69) with rows = cap + cap_fence + 3 lattice_cap + 2002 for all
+        eight segments and only the selected ones' share otherwise, unless ``out`` gives it; a larger ``capacity`` is cut to that bound.
+        Six launches on the current stream, no synchronisation; the workspace is a torch allocation."""
+        xyz, rgb, n = final["xyz"], final.get("rgb"), final["n"]
+        if rgb is None:
+            raise ValueError("format_scene_ply needs the colours of the road cloud (final['rgb'] is None)")
+        assert xyz.dtype == torch.float32 and xyz.is_cuda and xyz.is_contiguous() and xyz.dim() == 3 and xyz.shape[2] == 3
+        B, cap = int(xyz.shape[0]), int(xyz.shape[1])
+        assert rgb.dtype == torch.uint8 and rgb.is_cuda and rgb.is_contiguous() and tuple(rgb.shape) == (B, cap, 3)
+        assert n.dtype == torch.int32 and n.is_cuda and n.is_contiguous() and tuple(n.shape) == (B,)
+        assert records.dtype == torch.uint8 and records.is_cuda and records.is_contiguous() and tuple(records.shape) == (B, RW_DTYPE.itemsize)
+        fence = [None] * 4
+        cap_f = 0
+        if fence_final is not None:
+            if f2f is None or any(fence_final.get(k) is None for k in ("left_xyz", "left_rgb", "right_xyz", "right_rgb")):
+                raise ValueError("format_scene_ply: the fence clouds need their colours and the f2f records")
+            fence = [fence_final[k] for k in ("left_xyz", "left_rgb", "right_xyz", "right_rgb")]
+            cap_f = int(fence[0].shape[1])
+            for t, dt in zip(fence, (torch.float32, torch.uint8) * 2):
+                assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (B, cap_f, 3), t.shape
+        if f2f is not None:
+            assert f2f.dtype == torch.uint8 and f2f.is_cuda and f2f.is_contiguous() and tuple(f2f.shape) == (B, F2F_DTYPE.itemsize)
+        rbox = fbox = None
+        if boxes is not None:
+            rbox, fbox = boxes.get("road"), boxes.get("fence")
+            for t, shape in ((rbox, (B, BOX_DTYPE.itemsize)), (fbox, (B, 2, BOX_DTYPE.itemsize))):
+                assert t is None or (t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == shape), shape
+        need, bound = C.c_size_t(), C.c_size_t()
+        st = self.lib.sd_scene_workspace(B, cap, cap_f, int(lattice_cap), int(mask), C.byref(need), C.byref(bound))
+        L.check(self.lib, None, st, "sd_scene_workspace")
+        if out is not None:
+            assert out.dtype == torch.uint8 and out.is_cuda and out.is_contiguous() and out.dim() == 1
+            capacity = int(out.numel()) if capacity is None else int(capacity)
+            assert capacity <= out.numel()
+        else:
+            # (never more than the mask's own bound: the _ROAD and _FENCE files, without lattices and lines, need a fraction of the scene file's)
+            capacity = bound.value if capacity is None else min(int(capacity), bound.value)
+            out = torch.empty((max(capacity, 1),), dtype=torch.uint8, device=self.device)
+        offsets = torch.empty((B + 1,), dtype=torch.int64, device=self.device)
+        flags = torch.empty((B,), dtype=torch.int32, device=self.device)
+        ws = torch.empty((need.value,), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_scene_format(self.h, _ptr(xyz), _ptr(rgb), _ptr(n), cap, _ptr(fence[0]), _ptr(fence[1]), _ptr(fence[2]), _ptr(fence[3]), cap_f,
+                                      B, _ptr(records), _ptr(f2f), _ptr(rbox), _ptr(fbox), int(mask), int(lattice_cap), _ptr(out), capacity,
+                                      _ptr(offsets), _ptr(flags), _ptr(ws), need.value, self._stream())
+        L.check(self.lib, self.h, st, "sd_scene_format")
+        return out[:capacity], offsets, flags
+
     def render_rw(self, final: dict, records: torch.Tensor, camera, out: torch.Tensor | None = None):
         """the rendered view of every frame's ``_rw.ply`` (sd_render_rw): ``final`` = process_batch(want_final=True)'s road_final (xyz f32
         [B,cap,3], rgb u8 [B,cap,3], n i32 [B]), ``records`` u8 [B,104] (sd_rw_result) and ``camera`` (outputs.RenderCamera) -> (``images`` u8
@@ -792,28 +851,37 @@ class Engine:
         buf = self._sweep_buffers(T * B, B, T, cap or self.cap, want_rgb and frames is not None, want_fence and fence is not None)
         return self._fuse_sweep_into(buf, disp_pp, road, fence, frames, cams)
 
-    def road_width(self, road_xyz, n_road, params: RoadWidthParams = RoadWidthParams(), want_final: bool = False, road_rgb=None):
+    def road_width(self, road_xyz, n_road, params: RoadWidthParams = RoadWidthParams(), want_final: bool = False, road_rgb=None,
+                   boxes: torch.Tensor | None = None):
         """road chain (semantic_depth.py:203-259).  ``road_rgb`` (u8 [B,cap,3], optional): the colours the reference carries
         through every filter.  want_final: also return the denoised cloud -> (records, xyz, n) or, with colours,
-        (records, xyz, rgb, n)."""
+        (records, xyz, rgb, n).  ``boxes`` (a device u8 [B,24] tensor to fill, optional): the sd_plane_box of the cloud that enters the
+        plane fit (sd_road_width_boxes: one more launch, every other output bit-identical)."""
         B, cap = road_xyz.shape[0], road_xyz.shape[1]
         res = torch.empty((B, RW_DTYPE.itemsize), dtype=torch.uint8, device=self.device)    # (every byte of a record is written by the tail kernels)
         fin = torch.empty_like(road_xyz) if want_final else None
         frgb = torch.empty_like(road_rgb) if (want_final and road_rgb is not None) else None
         nfin = torch.empty((B,), dtype=torch.int32, device=self.device) if want_final else None
         prm = params.to_c()
-        st = self.lib.sd_road_width(self.h, _ptr(road_xyz), _ptr(road_rgb), _ptr(n_road), B, cap, C.byref(prm), _ptr(res), _ptr(fin),
-                                    _ptr(frgb), _ptr(nfin), self._stream())
+        if boxes is None:
+            st = self.lib.sd_road_width(self.h, _ptr(road_xyz), _ptr(road_rgb), _ptr(n_road), B, cap, C.byref(prm), _ptr(res), _ptr(fin),
+                                        _ptr(frgb), _ptr(nfin), self._stream())
+        else:
+            assert boxes.dtype == torch.uint8 and boxes.is_cuda and boxes.is_contiguous() and tuple(boxes.shape) == (B, BOX_DTYPE.itemsize), boxes.shape
+            st = self.lib.sd_road_width_boxes(self.h, _ptr(road_xyz), _ptr(road_rgb), _ptr(n_road), B, cap, C.byref(prm), _ptr(res), _ptr(fin),
+                                              _ptr(frgb), _ptr(nfin), _ptr(boxes), self._stream())
         L.check(self.lib, self.h, st, "sd_road_width")
         if not want_final:
             return res
         return (res, fin, nfin) if road_rgb is None else (res, fin, frgb, nfin)
 
     def fence_to_fence(self, fence_xyz, n_fence, road_records: torch.Tensor, params: FenceParams = FenceParams(), fence_rgb=None,
-                       want_clouds: bool = False):
+                       want_clouds: bool = False, boxes: torch.Tensor | None = None):
         """fence chain + fence-to-fence distance (semantic_depth.py:273-334) for B frames; ``road_records`` is the device
         buffer returned by road_width (its plane is the road plane).  Returns a device buffer of sd_f2f_result; with
-        want_clouds also the denoised left / right fence clouds (dict; sizes = counts[5], counts[6] of the records)."""
+        want_clouds also the denoised left / right fence clouds (dict; sizes = counts[5], counts[6] of the records).
+        ``boxes`` (a device u8 [B,2,24] tensor to fill, optional): the sd_plane_box of the left and the right cloud that enter their
+        plane fits (sd_fence_to_fence_boxes: two more launches, every other output bit-identical)."""
         B, cap = fence_xyz.shape[0], fence_xyz.shape[1]
         res = torch.zeros((B, F2F_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
         prm = params.to_c()
@@ -822,9 +890,15 @@ class Engine:
             cl["left_xyz"], cl["right_xyz"] = torch.empty_like(fence_xyz), torch.empty_like(fence_xyz)
             if fence_rgb is not None:
                 cl["left_rgb"], cl["right_rgb"] = torch.empty_like(fence_rgb), torch.empty_like(fence_rgb)
-        st = self.lib.sd_fence_to_fence(self.h, _ptr(fence_xyz), _ptr(fence_rgb), _ptr(n_fence), B, cap, _ptr(road_records), C.byref(prm),
-                                        _ptr(res), _ptr(cl["left_xyz"]), _ptr(cl["left_rgb"]), _ptr(cl["right_xyz"]), _ptr(cl["right_rgb"]),
-                                        self._stream())
+        if boxes is None:
+            st = self.lib.sd_fence_to_fence(self.h, _ptr(fence_xyz), _ptr(fence_rgb), _ptr(n_fence), B, cap, _ptr(road_records), C.byref(prm),
+                                            _ptr(res), _ptr(cl["left_xyz"]), _ptr(cl["left_rgb"]), _ptr(cl["right_xyz"]), _ptr(cl["right_rgb"]),
+                                            self._stream())
+        else:
+            assert boxes.dtype == torch.uint8 and boxes.is_cuda and boxes.is_contiguous() and tuple(boxes.shape) == (B, 2, BOX_DTYPE.itemsize), boxes.shape
+            st = self.lib.sd_fence_to_fence_boxes(self.h, _ptr(fence_xyz), _ptr(fence_rgb), _ptr(n_fence), B, cap, _ptr(road_records), C.byref(prm),
+                                                  _ptr(res), _ptr(cl["left_xyz"]), _ptr(cl["left_rgb"]), _ptr(cl["right_xyz"]),
+                                                  _ptr(cl["right_rgb"]), _ptr(boxes), self._stream())
         L.check(self.lib, self.h, st, "sd_fence_to_fence")
         return (res, cl) if want_clouds else res
 
@@ -898,24 +972,27 @@ class Engine:
 
     # ------------------------------------------------------------------ whole path
     def process_batch(self, frames: torch.Tensor, cams, params: RoadWidthParams = RoadWidthParams(), approach: str = "rw",
-                      fence_params: FenceParams | None = None, colours: bool = True, want_final: bool = False, depths=None):
+                      fence_params: FenceParams | None = None, colours: bool = True, want_final: bool = False, depths=None,
+                      want_boxes: bool = False):
         """FrameProcessor.process_frame for B frames at once (semantic_depth.py:98-334; seq:117-298): seg + depth + fusion +
         road chain (+ the fence chain and fence-to-fence distance when ``approach == 'both'``, :273-334).  ``colours``: carry
         the RGB of every point through the filters like the reference does (they feed only the PLY outputs).
         ``depths`` (None = off): also the depth profile of every frame, from the one denoised cloud and the one set of planes the chains
         leave: ``profile`` u8 [B, D, 48] (road_width_profile) and, with approach 'both', ``f2f_profile`` u8 [B, D, 64] (f2f_profile).
+        ``want_boxes``: also ``plane_boxes`` = dict(road u8 [B,24], fence u8 [B,2,24] or None without the fence chain): the sd_plane_box
+        (BOX_DTYPE) of the cloud that entered each plane fit, which the plane lattices of the scene files are laid over (format_scene_ply).
         Returns device tensors: seg, disp_pp, fuse, records (sd_rw_result), f2f (sd_f2f_result or None) [, final clouds]."""
         if approach not in ("rw", "both"):
             raise ValueError("approach must be 'rw' or 'both' (semantic_depth.py:743-745)")
         cams = list(cams)
         if depths is not None:
             depths = self._depth_array(depths)
-        out = self._process_batch(frames, cams, params, approach, fence_params, colours, want_final, depths)
+        out = self._process_batch(frames, cams, params, approach, fence_params, colours, want_final, depths, want_boxes)
         # ('recompute': ONE per-frame read behind both networks and the tail; the companion reruns the whole path on the flagged frames)
         return self._settle(frames, out, lambda e, f: e.process_batch(f, [cams[i] for i in self.last_recomputed], params, approach,
-                                                                      fence_params, colours, want_final, depths))
+                                                                      fence_params, colours, want_final, depths, want_boxes))
 
-    def _process_batch(self, frames, cams, params, approach, fence_params, colours, want_final, depths=None):
+    def _process_batch(self, frames, cams, params, approach, fence_params, colours, want_final, depths=None, want_boxes=False):
         seg = self._fcn8s(frames)
         if frames.shape[0] <= self.pass_frames:
             # the raw disparity pair stays in the activation arena: post-processing, back-projection and both gathers in ONE launch
@@ -928,7 +1005,11 @@ class Engine:
         out = dict(seg=seg, disp_pp=disp_pp, fuse=fz, f2f=None)
         # (a depth profile reads the denoised cloud: the chain runs once and keeps it, whether or not the caller asked for it)
         keep = want_final or depths is not None
-        rw = self.road_width(fz["road_xyz"], fz["n_road"], params, want_final=keep, road_rgb=fz["road_rgb"] if colours else None)
+        B = int(frames.shape[0])
+        if want_boxes:
+            out["plane_boxes"] = dict(road=torch.empty((B, BOX_DTYPE.itemsize), dtype=torch.uint8, device=self.device), fence=None)
+        rw = self.road_width(fz["road_xyz"], fz["n_road"], params, want_final=keep, road_rgb=fz["road_rgb"] if colours else None,
+                             boxes=out["plane_boxes"]["road"] if want_boxes else None)
         if keep:
             out["records"] = rw[0]
             if want_final:
@@ -939,8 +1020,10 @@ class Engine:
             out["records"] = rw
         if approach == "both":
             fp = fence_params or FenceParams(depth=params.depth)
+            if want_boxes:
+                out["plane_boxes"]["fence"] = torch.empty((B, 2, BOX_DTYPE.itemsize), dtype=torch.uint8, device=self.device)
             f2 = self.fence_to_fence(fz["fence_xyz"], fz["n_fence"], out["records"], fp, fence_rgb=fz["fence_rgb"] if colours else None,
-                                     want_clouds=want_final)
+                                     want_clouds=want_final, boxes=out["plane_boxes"]["fence"] if want_boxes else None)
             if want_final:
                 out["f2f"], out["fence_final"] = f2
             else:

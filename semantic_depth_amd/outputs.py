@@ -1023,6 +1023,145 @@ def rw_ply_bytes(road3D, road_colors, left_pt_rw=None, right_pt_rw=None) -> byte
     return PointCloud2Ply.ply_header.format(vertex_count=len(pts)).encode() + format_rows(pts, col, threads=1)
 
 
+# ------------------------------------------------------------------------------------------------ scene PLYs
+# the files of Scene(files=): key -> (suffix of <name> in result_sequence_ply, the segments of sd_scene_format's mask)
+SCENE_FILES = {"scene": ("_scene.ply", 255), "road": ("_ROAD.ply", 1), "fence": ("_FENCE.ply", 8 | 16)}
+
+
+@dataclasses.dataclass(frozen=True)
+class Scene:
+    """the 3D products of semantic_depth.py:404-431 for every frame of the sequence tool (opt-in, SequenceOutputs(scene=)), in
+    ``result_sequence_ply``: ``<name>_scene.ply`` (road cloud, road plane lattice, road-width line, both fence clouds, both fence plane
+    lattices, fence-to-fence line -- the fence part only with approach 'both'), ``<name>_ROAD.ply`` (the road cloud) and, with approach
+    'both', ``<name>_FENCE.ply`` (both fence clouds); ``files`` chooses among "scene", "road", "fence".  The format is
+    include/semdepth.h's (sd_scene_format): the road-width line is the sequence tool's, without the single-frame tool's z += 0.2.
+    ``route``: "device" (Engine.format_scene_ply makes the text on the GPU, only its bytes travel; a lattice of more than ``lattice_cap``
+    rows or a file beyond its share of ``capacity_per_frame`` bytes per frame of the batch sends that frame to the host formatter) or
+    "host" (the raw clouds, boxes and records travel and sd_scene_format_host makes the same bytes on the writer threads)."""
+    route: str = "device"
+    files: tuple = ("scene", "road", "fence")
+    lattice_cap: int = 1 << 18
+    capacity_per_frame: int = 24 << 20
+
+    def __post_init__(self):
+        object.__setattr__(self, "files", tuple(self.files))
+        object.__setattr__(self, "lattice_cap", int(self.lattice_cap))
+        object.__setattr__(self, "capacity_per_frame", int(self.capacity_per_frame))
+        if self.route not in ("device", "host"):
+            raise ValueError(f"Scene: route must be 'device' or 'host', got {self.route!r}")
+        if not self.files or len(set(self.files)) != len(self.files) or any(f not in SCENE_FILES for f in self.files):
+            raise ValueError(f"Scene: files must be distinct names among {tuple(SCENE_FILES)}, got {self.files!r}")
+        if not 0 <= self.lattice_cap < 1 << 29 or self.capacity_per_frame < 0:
+            raise ValueError("Scene: lattice_cap must be 0 .. 2^29 - 1 and capacity_per_frame >= 0")
+
+
+def _check_scene(scene):
+    if scene is not None and not isinstance(scene, Scene):
+        raise ValueError(f"scene must be None or an outputs.Scene, got {scene!r}")
+    return scene
+
+
+def _scene_lattice(box, plane, axis: int, color):
+    """pcl.plane_grid over a cloud that has the box's bounds; (None, None) when the box is empty (n == 0), the lattice has no point or
+    np.arange refuses the bounds (a NaN)"""
+    if box is None or int(box["n"]) == 0:
+        return None, None
+    ia, ib = [(1, 2), (0, 2), (0, 1)][axis]
+    corners = np.zeros((2, 3), np.float32)
+    corners[:, ia], corners[:, ib] = (box["lo_a"], box["hi_a"]), (box["lo_b"], box["hi_b"])
+    try:
+        pts, col = pcl.plane_grid(corners, dict(Cx=plane[0], Cy=plane[1], Cz=plane[2], C=plane[3]), axis, list(color))
+    except ValueError:
+        return None, None
+    return (pts, col) if len(pts) else (None, None)
+
+
+def scene_ply_bytes(road3D, road_colors, record, fence: dict | None = None, f2f=None, road_box=None, fence_boxes=None, mask: int = 255) -> bytes:
+    """the bytes of a scene file in plain numpy -- what sd_scene_format / sd_scene_format_host write, and what a frame they flag 1 is
+    written through: the segments ``mask`` selects (SCENE_FILES) in the order of semantic_depth.py:418-431, appended with np.append,
+    behind prepare_and_save_point_cloud's minimum-z filter, rows from sd_ply_format_rows.
+    ``road3D`` / ``road_colors``: the final road cloud; ``record``: its RW_DTYPE record; ``fence``: dict(left_xyz, left_rgb, right_xyz,
+    right_rgb) of the denoised fence clouds (already cut to their sizes) and ``f2f`` their F2F_DTYPE record, or None; ``road_box`` /
+    ``fence_boxes`` ([2]): the BOX_DTYPE boxes the lattices (pcl.plane_grid) are laid over, or None."""
+    from .point_cloud_2_ply import format_rows
+    parts = []
+    if mask & 1:
+        parts.append((np.asarray(road3D, np.float64).reshape(-1, 3), np.asarray(road_colors).reshape(-1, 3)))
+    if mask & 2:
+        parts.append(_scene_lattice(road_box, record["plane"], 1, (200, 200, 200)))
+    if mask & 4 and record["found"]:
+        parts.append(pcl.create_3Dline_from_3Dpoints(record["left_pt"].astype(np.float64)[None, :], record["right_pt"].astype(np.float64)[None, :],
+                                                     [250, 0, 0]))
+    if f2f is not None:
+        for bit, side in ((8, "left"), (16, "right")):
+            if mask & bit and fence is not None:
+                parts.append((np.asarray(fence[side + "_xyz"], np.float64).reshape(-1, 3), np.asarray(fence[side + "_rgb"]).reshape(-1, 3)))
+        for bit, k, side in ((32, 0, "plane_left"), (64, 1, "plane_right")):
+            if mask & bit and fence_boxes is not None:
+                parts.append(_scene_lattice(fence_boxes[k], f2f[side], 0, (40, 70, 40)))
+        if mask & 128 and f2f["ok"]:
+            parts.append(pcl.create_3Dline_from_3Dpoints(np.array(f2f["left_pt"], np.float64)[None, :], np.array(f2f["right_pt"], np.float64)[None, :],
+                                                         [0, 255, 0]))
+    pts, col = np.zeros((0, 3), np.float64), np.zeros((0, 3), np.float64)
+    for p, c in parts:
+        if p is not None:
+            pts, col = np.append(pts, p, axis=0), np.append(col, c, axis=0)
+    if len(pts):
+        keep = pts[:, 2] > pts[:, 2].min()
+        pts, col = pts[keep], col[keep]
+    return PointCloud2Ply.ply_header.format(vertex_count=len(pts)).encode() + format_rows(pts, col, threads=1)
+
+
+def scene_format_host(road3D, road_colors, record, fence: dict | None = None, f2f=None, road_box=None, fence_boxes=None, mask: int = 255,
+                      lattice_cap: int = 0):
+    """sd_scene_format_host on one frame (the arguments of scene_ply_bytes; float32 clouds, u8 colours) -> (bytes, flag): the file and 0,
+    or b"" and flag 1 (a coordinate the integer coder does not take: write the frame through scene_ply_bytes) or 3 (a lattice above
+    ``lattice_cap``; 0: no cap)."""
+    import ctypes as C
+
+    from . import _lib as L
+    from .engine import BOX_DTYPE, F2F_DTYPE, RW_DTYPE
+    lib = L.load()
+    keep = []                                               # (the arrays the pointers below point into)
+
+    def arr(a, dt, shape=None):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=dt)
+        keep.append(a if shape is None else a.reshape(shape))
+        return keep[-1].ctypes.data_as(C.c_void_p)
+
+    xyz = np.ascontiguousarray(road3D, np.float32).reshape(-1, 3)
+    n = len(xyz)
+    rec = np.ascontiguousarray(np.asarray(record, RW_DTYPE).reshape(1))
+    f2 = None if f2f is None else np.ascontiguousarray(np.asarray(f2f, F2F_DTYPE).reshape(1))
+    ptr = [arr(xyz, np.float32), arr(np.asarray(road_colors).reshape(-1, 3), np.uint8)]
+    rows = n + 2 * L.SD_PLY_LINE_ROWS
+    for side, j in (("left", 5), ("right", 6)):
+        given = fence is not None and f2 is not None
+        if given and len(np.asarray(fence[side + "_xyz"]).reshape(-1, 3)) < int(f2["counts"][0][j]):
+            raise ValueError(f"scene_format_host: the {side} fence cloud is shorter than its record says")
+        ptr += [arr(fence[side + "_xyz"], np.float32), arr(fence[side + "_rgb"], np.uint8)] if given else [None, None]
+        rows += int(f2["counts"][0][j]) if given else 0
+    rb = None if road_box is None else np.ascontiguousarray(np.asarray(road_box, BOX_DTYPE).reshape(1))
+    fb = None if fence_boxes is None else np.ascontiguousarray(np.asarray(fence_boxes, BOX_DTYPE).reshape(2))
+    na, nb = C.c_uint32(), C.c_uint32()
+    for box, plane, axis in ([(rb, rec["plane"][0], 1)] if rb is not None else []) + \
+                            ([(fb[k:k + 1], f2[side][0], 0) for k, side in enumerate(("plane_left", "plane_right"))] if fb is not None and f2 is not None else []):
+        if int(box["n"][0]) and lib.sd_scene_lattice_host(box.ctypes.data_as(C.c_void_p), np.ascontiguousarray(plane, np.float64).ctypes.data_as(C.c_void_p),
+                                                          axis, C.byref(na), C.byref(nb), None, 0) == L.SD_OK:
+            rows += na.value * nb.value                     # (a box the rule refuses: the call below flags the frame)
+    out = np.empty(L.SD_PLY_HEADER_CAP + max(rows, 0) * L.SD_PLY_ROW_CAP, np.uint8)
+    size, flag = C.c_size_t(), C.c_int32()
+    st = lib.sd_scene_format_host(ptr[0], ptr[1], n, ptr[2], ptr[3], ptr[4], ptr[5], rec.ctypes.data_as(C.c_void_p),
+                                  None if f2 is None else f2.ctypes.data_as(C.c_void_p), None if rb is None else rb.ctypes.data_as(C.c_void_p),
+                                  None if fb is None else fb.ctypes.data_as(C.c_void_p), int(mask), int(lattice_cap), out.ctypes.data_as(C.c_void_p),
+                                  out.size, C.byref(size), C.byref(flag))
+    if st != L.SD_OK or flag.value == 2:
+        raise RuntimeError(f"sd_scene_format_host failed (status {st}, flag {flag.value})")
+    return out[:size.value].tobytes(), int(flag.value)
+
+
 @dataclasses.dataclass(frozen=True)
 class _PngFamily:
     """one family of per-frame PNG files of SequenceOutputs; all of them go through the PNG route chosen (``png``, described there)"""
@@ -1060,6 +1199,7 @@ class _Batch:
     f2f: object = None
     cams: object = None                     # the frames' cameras and the network size (host values): the writer restates the lines from them
     net_size: object = None
+    scene: object = None                    # with scene=: dict(fence_final, f2f, boxes, text) as submit() describes it
 
 
 @dataclasses.dataclass
@@ -1081,6 +1221,8 @@ class _HostBatch:
     disp_flags: np.ndarray | None = None    # [n] non-zero: the frame's map held a non-finite value
     lines_flags: np.ndarray | None = None   # [n] bit 0: a measurement line of the frame was skipped
     f2f: np.ndarray | None = None           # [n,152] fence records, for the lines of approach 'both'
+    scene: dict | None = None               # with scene=: f2f [n,152] / None, road_box [n,24], fence_box [n,2,24] / None, fence: per frame the
+    #                                         four raw fence arrays or None, text: {file: (text, offsets, flags)} on the device route
 
 
 class _Stager:
@@ -1177,6 +1319,8 @@ class SequenceOutputs:
                                                               (``images``; Engine.compose_result_frames on the GPU)
         <directory>/result_sequence_imgs/<name>_overlay.json  the banner and the cv2.putText items of overlay_items_sequence (``items``)
         <directory>/result_sequence_ply/<name>_rw.ply         the denoised road cloud + the red road-width line (``ply``; rw_ply_bytes)
+        <directory>/result_sequence_ply/<name>_scene.ply      only with scene=: the frame's 3D scene; beside it <name>_ROAD.ply and, with approach
+                                                              'both', <name>_FENCE.ply (``scene``; scene_ply_bytes)
         <directory>/rendered_sequence/<name>_render.png       only with render=: the top view of the _rw.ply's rows (``render``)
         <directory>/result_imgs.avi                           only with video=: the result images as a Motion-JPEG AVI (``video``;
                                                               result_imgs_rank<r>.avi when world > 1, _part<k> when a file rolls over)
@@ -1227,14 +1371,22 @@ class SequenceOutputs:
     road's two edges and a rung per depth -- is drawn into the composed images on the GPU (Engine.draw_result_lines, below the banner
     rows: clip_top = int(0.25 h)), so the PNGs of both routes and the video show them.  The writer restates the segments
     (overlay_segments) from the frames' cameras and records: each ``_overlay.json`` gains "lines", the manifest 'lines' (the style) and
-    'lines_flagged' (the frames of which a segment was skipped because an end point does not project)."""
+    'lines_flagged' (the frames of which a segment was skipped because an end point does not project).
+    ``scene``: None or a Scene: every frame's 3D products (semantic_depth.py:404-431) as ``<name>_scene.ply``, ``<name>_ROAD.ply`` and, with
+    approach 'both', ``<name>_FENCE.ply`` in ``result_sequence_ply`` (Scene's docstring).  The step keeps the final road and fence clouds
+    and the boxes of the three plane fits (process_batch(want_final=True, want_boxes=True)).  route "device": the finished text of every
+    file comes from the GPU (Engine.format_scene_ply); offsets and flags are copied first, then each file's text[:offsets[n]] in one
+    copy; a flagged frame has its raw clouds copied and goes through sd_scene_format_host (flags 2 and 3: the capacity, a lattice above
+    lattice_cap) or scene_ply_bytes (flag 1: a coordinate the integer coder does not take).  route "host": the raw clouds, boxes and
+    records travel and sd_scene_format_host makes the same bytes on the writer threads.  The manifest names the files under 'scene' and
+    the frames of which the device left a file to the host under 'scene_fallback'."""
 
-    png, ply_route, text, render, video, disp, lines, _k = "host", "host", "json", None, None, None, None, 0    # (what configure() starts from)
+    png, ply_route, text, render, video, disp, lines, scene, _k = "host", "host", "json", None, None, None, None, None, 0    # (what configure() starts from)
 
     def __init__(self, directory: str, names, depth: float = 10.0, images: bool = True, ply: bool | str = True, items: bool = True, level: int = 1,
                  threads: int = 0, road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, png: str = "host", text: str = "json",
                  render: RenderCamera | None = None, video: Video | None = None, profile=None, disp: str | None = None,
-                 lines: OverlayLines | None = None):
+                 lines: OverlayLines | None = None, scene: Scene | None = None):
         import threading
         from concurrent.futures import ThreadPoolExecutor
 
@@ -1243,7 +1395,7 @@ class SequenceOutputs:
             raise ValueError("PNG compression level must be 0..9")
         if png is None or ply is None or text is None:                # (None leaves a choice as it is only in configure)
             raise ValueError(f"png, ply and text must be given, got {png!r}, {ply!r}, {text!r}")
-        self.configure(png, "host" if isinstance(ply, bool) else ply, text, render, video, disp, lines)
+        self.configure(png, "host" if isinstance(ply, bool) else ply, text, render, video, disp, lines, scene)
         self.directory, self.names, self.depth = directory, list(names), float(depth)
         self.images, self.ply, self.items, self.level = bool(images), bool(ply), bool(items), int(level)
         self.road_color, self.fence_color, self.alpha = tuple(road_color), tuple(fence_color), int(alpha)
@@ -1263,22 +1415,24 @@ class SequenceOutputs:
         # manifest key -> global indices of the frames that took the other path: recomputed on bf16x3 (on_range='recompute'), sent through
         # rw_ply_bytes by ply="device", encoded on the host by video route "device", a non-finite value in the disparity map, a segment
         # skipped by lines=
-        self._frames = {key: [] for key in ("recomputed", "ply_fallback", "video_fallback", "disp_nonfinite", "lines_flagged")}
+        self._frames = {key: [] for key in ("recomputed", "ply_fallback", "video_fallback", "disp_nonfinite", "lines_flagged", "scene_fallback")}
+        self._scene_files = []                                       # the scene=  files written (they share result_sequence_ply with the _rw.ply)
         self._video_writer, self._video_next, self._video_turn = None, 0, threading.Condition()
 
     # ---------------------------------------------------------------- driver interface
     def configure(self, png: str | None = None, ply: str | None = None, text: str | None = None, render=None, video=None, disp: str | None = None,
-                  lines=None):
+                  lines=None, scene=None):
         """choose the routes described in the class docstring, before the first batch: ``png`` and ``ply`` "host" or "device", ``text`` "json"
-        or "draw", ``render`` a RenderCamera, ``video`` a Video, ``disp`` "gray" or "plasma", ``lines`` an OverlayLines; None leaves a choice
-        as it is.  Nothing changes when the resulting combination is refused."""
-        new = dict(png=png, ply_route=ply, text=text, render=render, video=video, disp=disp, lines=lines)
+        or "draw", ``render`` a RenderCamera, ``video`` a Video, ``disp`` "gray" or "plasma", ``lines`` an OverlayLines, ``scene`` a Scene; None
+        leaves a choice as it is.  Nothing changes when the resulting combination is refused."""
+        new = dict(png=png, ply_route=ply, text=text, render=render, video=video, disp=disp, lines=lines, scene=scene)
         new = {name: getattr(self, name) if v is None else v for name, v in new.items()}
         if new["png"] not in ("host", "device"):
             raise ValueError(f"png must be 'host' or 'device', got {new['png']!r}")
         if new["ply_route"] not in ("host", "device") or isinstance(new["ply_route"], bool):
             raise ValueError(f"ply must be 'host' or 'device', got {new['ply_route']!r}")
-        for check, name in ((_check_text, "text"), (_check_render, "render"), (_check_video, "video"), (_check_disp, "disp"), (_check_lines, "lines")):
+        for check, name in ((_check_text, "text"), (_check_render, "render"), (_check_video, "video"), (_check_disp, "disp"), (_check_lines, "lines"),
+                            (_check_scene, "scene")):
             check(new[name])
         if self._k:
             raise RuntimeError("SequenceOutputs.configure after the first batch")
@@ -1309,6 +1463,10 @@ class SequenceOutputs:
     def set_video(self, video):
         """the Video the result images also become (before the first batch)"""
         self.configure(video=video)
+
+    def set_scene(self, scene):
+        """the Scene whose PLY files are written for every frame (before the first batch)"""
+        self.configure(scene=scene)
 
     def set_disp(self, disp: str):
         """the colour map of the per-frame disparity images: "gray" or "plasma" (before the first batch)"""
@@ -1346,8 +1504,13 @@ class SequenceOutputs:
 
     @property
     def wants_final(self) -> bool:
-        """the step has to keep the final road clouds: for the PLYs or the renders"""
-        return self.ply or self.render is not None
+        """the step has to keep the final road clouds: for the PLYs, the renders or the scene files"""
+        return self.ply or self.render is not None or self.scene is not None
+
+    @property
+    def device_scene(self) -> bool:
+        """scene files are written and arrive as text (route "device")"""
+        return self.scene is not None and self.scene.route == "device"
 
     @property
     def wants_composed(self) -> bool:
@@ -1370,7 +1533,7 @@ class SequenceOutputs:
 
     def submit(self, lo: int, records, size: tuple, images=None, final=None, png_streams=None, ply_text=None, renders=None, render_streams=None,
                video_streams=None, profile=None, f2f_profile=None, disp_images=None, disp_streams=None, disp_flags=None, lines_flags=None,
-               f2f=None, cams=None, net_size=None):
+               f2f=None, cams=None, net_size=None, scene=None):
         """one batch: ``records`` u8 [n,104] (sd_rw_result) and ``size`` = (h, w) of the original frames, then what the choices of the class
         docstring call for (anything else is ignored).  Device or host tensors; the device ones must stay unmodified until the batch is
         written (they are new tensors of every step).
@@ -1390,7 +1553,10 @@ class SequenceOutputs:
         ``disp_flags`` = the i32 [n] flags of Engine.disparity_image with disp= (optional: the manifest's 'disp_nonfinite').
         With lines=: ``cams`` = the n frames' Camera and ``net_size`` = (h, w) of the network they belong to (host values), ``f2f`` = u8
         [n,152] fence records (optional: the fence lines) and ``lines_flags`` = i32 [n] of Engine.draw_result_lines (optional: without them
-        the writer's own restatement flags the frames)."""
+        the writer's own restatement flags the frames).
+        With scene=: ``final`` as above and ``scene`` = dict(fence_final = process_batch(want_final=True)'s fence_final or None (approach
+        'rw'), f2f = u8 [n,152] or None, boxes = process_batch(want_boxes=True)'s plane_boxes, text = None on the "host" route, on the
+        "device" route {file: (text, offsets, flags) of Engine.format_scene_ply with that file's mask} for the files of Scene.files)."""
         if self.manifest is not None:
             raise RuntimeError("SequenceOutputs.submit after close")
         n = int(records.shape[0])
@@ -1400,7 +1566,7 @@ class SequenceOutputs:
         if lo < 0 or lo + n > len(self.names):
             raise ValueError(f"frames {lo}..{lo + n - 1} are beyond the {len(self.names)} names")
         lacking = (
-            (self.images and payload["images"] is None or self.ply and final is None,
+            (self.images and payload["images"] is None or (self.ply or self.scene is not None) and final is None,
              "this batch lacks the images (png='device': the streams) / final road clouds the outputs ask for"),
             (self.device_ply and ply_text is None, "ply='device' needs the text of Engine.format_rw_ply (submit(ply_text=))"),
             (self.render is not None and payload["render"] is None,
@@ -1412,7 +1578,10 @@ class SequenceOutputs:
             (_check_disp(self.disp) is not None and payload["disp"] is None,
              "disp= needs the images of Engine.disparity_image (submit(disp_images=); png='device': disp_streams=)"),
             (self.lines is not None and (cams is None or net_size is None or len(cams) != n),
-             "lines= needs the frames' cameras and the network size (submit(cams=, net_size=))"))
+             "lines= needs the frames' cameras and the network size (submit(cams=, net_size=))"),
+            (self.scene is not None and (scene is None or scene.get("boxes") is None or self.device_scene and not scene.get("text")),
+             "scene= needs the boxes of process_batch(want_boxes=True) and, on the device route, the text of Engine.format_scene_ply "
+             "(submit(scene=))"))
         for lacks, what in lacking:
             if lacks:
                 raise ValueError("SequenceOutputs: " + what)
@@ -1427,7 +1596,8 @@ class SequenceOutputs:
                        video_streams=video_streams if self.device_video else None,
                        profile=profile if self.profile is not None else None,
                        f2f_profile=f2f_profile if self.profile is not None else None,
-                       disp_flags=disp_flags if self.disp is not None else None)
+                       disp_flags=disp_flags if self.disp is not None else None,
+                       scene=scene if self.scene is not None else None)
         if self.lines is not None:
             batch.lines_flags, batch.f2f, batch.cams, batch.net_size = lines_flags, f2f, list(cams), tuple(net_size)
         self._k += 1
@@ -1472,13 +1642,14 @@ class SequenceOutputs:
         value = {key: [self.names[i] for i in sorted(set(frames))] for key, frames in self._frames.items()}
         value.update({f.manifest_key: below(f.subdir) for f in self._families if f.manifest_key})
         value.update(video=[os.path.relpath(p, self.directory) for p in video_files], profile_depths=self.profile, profile=below(SEQ_PROFILE_DIR),
-                     lines=None if self.lines is None else self.lines.as_dict())
+                     lines=None if self.lines is None else self.lines.as_dict(),
+                     scene=sorted(os.path.relpath(p, self.directory) for p in self._scene_files))
         manifest = dict(rank=self.rank, world=self.world, frames=list(self.shard), status=status, valid=status == "ok", files=files,
                         recomputed=value["recomputed"])
         # (the choice, the keys it adds when it is on), in the manifest's order
         for choice, keys in ((self.device_ply or None, ("ply_fallback",)), (self.render, ("render",)), (self.video, ("video", "video_fallback")),
                              (self.profile, ("profile_depths", "profile")), (self.disp, ("disp", "disp_nonfinite")),
-                             (self.lines, ("lines", "lines_flagged"))):
+                             (self.lines, ("lines", "lines_flagged")), (self.scene, ("scene", "scene_fallback"))):
             if choice is not None:
                 manifest.update((key, value[key]) for key in keys)
         with open(self.manifest, "w") as f:
@@ -1505,6 +1676,12 @@ class SequenceOutputs:
                 host.ply_offsets, host.ply_flags = st.fixed("ply_offsets", b.ply_text[1]), st.fixed("ply_flags", b.ply_text[2])
             if b.video_streams is not None:
                 host.video_sizes, host.video_flags = st.fixed("video_sizes", b.video_streams[1]), st.fixed("video_flags", b.video_streams[2])
+            if b.scene is not None:                                    # the fence records, the boxes and, on the device route, offsets and flags
+                boxes = b.scene["boxes"]
+                host.scene = dict(f2f=st.fixed("scene_f2f", b.scene.get("f2f")), road_box=st.fixed("scene_rbox", boxes["road"]),
+                                  fence_box=st.fixed("scene_fbox", boxes.get("fence")), fence=None,
+                                  text={key: (None, st.fixed("scene_off_" + key, t[1]), st.fixed("scene_flag_" + key, t[2]))
+                                        for key, t in (b.scene.get("text") or {}).items()})
             st.sync()
             if self.device_png:
                 for key, p in b.png.items():
@@ -1512,8 +1689,31 @@ class SequenceOutputs:
                     host.png[key] = (st.rows(key + "_png", p[0], sizes), sizes)
             if b.ply_text is not None:
                 host.ply_text = st.fixed("ply_text", b.ply_text[0][:int(host.ply_offsets[-1])])
+            scene_raw = None
+            if b.scene is not None:
+                # a frame's raw clouds travel on the host route, and on the device route when one of its files is flagged
+                scene_raw = np.ones(len(counts), bool)
+                if host.scene["text"]:
+                    scene_raw = np.zeros(len(counts), bool)
+                    for key, (_, offsets, flags) in host.scene["text"].items():
+                        host.scene["text"][key] = (st.fixed("scene_text_" + key, b.scene["text"][key][0][:int(offsets[-1])]), offsets, flags)
+                        scene_raw |= flags != 0
+                ff = b.scene.get("fence_final")
+                if ff is not None and host.scene["f2f"] is not None:
+                    from .engine import F2F_DTYPE
+                    fc = np.ascontiguousarray(host.scene["f2f"]).view(F2F_DTYPE).reshape(-1)["counts"]
+                    side = {k: st.ragged("scene_" + k, ff[k], np.where(scene_raw, np.clip(fc[:, j], 0, ff[k].shape[1]), 0).astype(np.int64))
+                            for k, j in (("left_xyz", 5), ("left_rgb", 5), ("right_xyz", 6), ("right_rgb", 6))}
+                    host.scene["fence"] = [{k: v[i] for k, v in side.items()} if scene_raw[i] else None for i in range(len(counts))]
             if b.final is not None:
-                raw = np.ones(len(counts), bool) if b.ply_text is None else host.ply_flags != 0
+                # which frames' raw road clouds travel: with PLYs on, all of them on the host route and the flagged ones on the device
+                # route (as before scene= existed); with PLYs off nothing read them, and now only scene= can ask for them (ply=False
+                # with final= given used to copy clouds that no writer looked at).  write_ply decides by the flags, not by this.
+                raw = np.zeros(len(counts), bool)
+                if self.ply:
+                    raw = np.ones(len(counts), bool) if b.ply_text is None else host.ply_flags != 0
+                if scene_raw is not None:
+                    raw = raw | scene_raw
                 cn = np.where(raw, counts, 0).astype(np.int64)
                 xyz, rgb = st.ragged("xyz", b.final["xyz"], cn), st.ragged("rgb", b.final["rgb"], cn)
                 host.clouds = [(xyz[i], rgb[i]) if raw[i] else None for i in range(len(cn))]
@@ -1556,7 +1756,7 @@ class SequenceOutputs:
 
             def write_ply(i):
                 path = os.path.join(self.ply_dir, "{}_rw.ply".format(names[i]))
-                if host.clouds[i] is None:                             # the device route: the slice is the file
+                if host.ply_text is not None and host.ply_flags[i] == 0:     # the device route: the slice is the file
                     with open(path, "wb") as f:
                         f.write(host.ply_text[int(host.ply_offsets[i]):int(host.ply_offsets[i + 1])].data)
                     return path
@@ -1564,6 +1764,33 @@ class SequenceOutputs:
                 xyz, rgb = host.clouds[i]
                 with open(path, "wb") as f:
                     f.write(rw_ply_bytes(xyz.astype(np.float64), rgb, left, right))
+                return path
+
+            def write_scene(i, key):
+                """one scene= file of frame i: the device's slice, or sd_scene_format_host from the raw copy (the host route, flags 2 and
+                3), or scene_ply_bytes (flag 1)"""
+                from .engine import BOX_DTYPE, F2F_DTYPE
+                sc = host.scene
+                suffix, mask = SCENE_FILES[key]
+                path = os.path.join(self.ply_dir, names[i] + suffix)
+                text = sc["text"].get(key)
+                if text is not None and text[2][i] == 0:
+                    data = text[0][int(text[1][i]):int(text[1][i + 1])].data
+                else:
+                    xyz, rgb = host.clouds[i]
+                    kw = dict(road3D=xyz, road_colors=rgb, record=recs[i], mask=mask,
+                              road_box=np.ascontiguousarray(sc["road_box"][i]).view(BOX_DTYPE).reshape(())
+                              )
+                    if sc["f2f"] is not None:
+                        kw["f2f"] = np.ascontiguousarray(sc["f2f"][i]).view(F2F_DTYPE).reshape(())
+                        kw["fence"] = None if sc["fence"] is None else sc["fence"][i]
+                        if sc["fence_box"] is not None:
+                            kw["fence_boxes"] = np.ascontiguousarray(sc["fence_box"][i]).view(BOX_DTYPE).reshape(2)
+                    data, flag = scene_format_host(**kw)
+                    if flag:
+                        data = scene_ply_bytes(**kw)
+                with open(path, "wb") as f:
+                    f.write(data)
                 return path
 
             def write_items(i):
@@ -1606,6 +1833,14 @@ class SequenceOutputs:
                 futs.extend(self._writers.submit(write_profile_file, i) for i in range(n))
             for key, flags in (("lines_flagged", host.lines_flags), ("ply_fallback", host.ply_flags), ("disp_nonfinite", host.disp_flags)):
                 self._flag(key, b.lo, flags)
+            scene_futs = []
+            if host.scene is not None:
+                os.makedirs(self.ply_dir, exist_ok=True)
+                # (the _FENCE file only with the fence chain: approach 'both')
+                keys = [k for k in self.scene.files if k != "fence" or host.scene["f2f"] is not None]
+                scene_futs = [self._writers.submit(write_scene, i, key) for i in range(n) for key in keys]
+                for key, (_, _, flags) in host.scene["text"].items():
+                    self._flag("scene_fallback", b.lo, flags)
             for i in range(n):
                 if self.ply:
                     futs.append(self._writers.submit(write_ply, i))
@@ -1616,6 +1851,9 @@ class SequenceOutputs:
             if self.video is not None:
                 frames = self._video_frames(b, host)
             files.extend(f.result() for f in futs)
+            scene_files = [f.result() for f in scene_futs]
+            self._scene_files.extend(scene_files)
+            files.extend(scene_files)
             return files
         finally:
             if self.video is not None:
