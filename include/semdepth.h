@@ -365,6 +365,80 @@ sd_status sd_jpeg_entropy_decode(sd_handle* h, const uint8_t* bytes_dev, size_t 
                                  const sd_jpeg_entropy_frame* frames_host, const sd_jpeg_interval* intervals_host, size_t interval_stride,
                                  const sd_jpeg_huff_table* tables_host, int B, int16_t* coef_dev, size_t coef_stride_bytes,
                                  int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* ---- JPEG frames, sync route: the GPU decodes the Huffman code in short pieces that find the decoder's state by themselves ----
+ * A sequential Huffman decoder at a bit position is in the state (p, u, k): bit position, data unit inside the MCU, zigzag index (k 0: a
+ * DC symbol comes next).  Two decoders that meet in one state agree from there on, and a decoder started at a byte boundary in the
+ * assumed state (u 0, k 0) nearly always falls into step with the true one within a few hundred bytes.  So an interval is cut into
+ * PIECES of subseq_bytes (a power of two, 32..1024): a speculative pass finds every piece's end state, a write pass decodes every piece
+ * from its predecessor's recorded end state and VERIFIES that it ends in its own; with the interval's true start that chain of
+ * equalities proves the sequential decode.  A file without DRI is one interval of all its MCUs, so this route reaches it.
+ * ELIGIBLE: the rule of sd_jpeg_entropy_plan with DRI = 0 admitted.
+ * The plan writes the CLEAN stream: the scan bytes with FF 00 resolved to FF and the RSTk markers dropped, the intervals one behind the
+ * other, so a bit position is a plain offset.
+ * sd_jpeg_sync_frame: as sd_jpeg_entropy_frame, with restart_interval the MCUs of one interval (DRI, or mcus_x * mcus_y without DRI: a
+ * field of 32 bits), clean_bytes the length of the clean stream, subseq_bytes the piece length the plan counted with and n_pieces the
+ * pieces of the frame.  sd_jpeg_sync_interval: the bytes [begin, end) of the interval in the clean stream and the index of its first
+ * piece; an interval of n bytes has max(1, ceil(n / subseq_bytes)) pieces, piece j covering [begin + j * subseq_bytes, ...) up to end. */
+typedef struct {
+    int32_t eligible;
+    int32_t ncomp;
+    int32_t mcus_x, mcus_y;
+    int32_t restart_interval;
+    int32_t n_intervals;
+    int32_t comp_h[3], comp_v[3], comp_dc[3], comp_ac[3];
+    uint32_t scan_begin, scan_end;
+    uint32_t clean_bytes, subseq_bytes, n_pieces;
+    uint32_t reserved;                /* 0 */
+} sd_jpeg_sync_frame;
+typedef struct {
+    uint32_t begin, end;
+    uint32_t first_piece;
+    uint32_t reserved;                /* 0 */
+} sd_jpeg_sync_interval;
+/* per-frame status words of the sync route beyond the four refusals of the entropy route (1..4) */
+#define SD_JPEG_SYNC_NOT_SYNCHRONISED 5   /* a piece did not end in its recorded state: the chain of equalities is broken */
+#define SD_JPEG_SYNC_BITS_RAN_OUT 6       /* the interval's pieces hold fewer data units than the interval has */
+#define SD_JPEG_SYNC_GROUP 256            /* pieces per workgroup of the speculative pass */
+/* HOST: the plan of one file for the sync route: sd_jpeg_entropy_plan's header parse and byte walk, with DRI = 0 admitted.  Writes
+ * *desc_out, *frame_out, tables_out[SD_JPEG_ENTROPY_TABLES], the first n_intervals entries of intervals_out and, when clean_out is not
+ * NULL, the clean stream (frame_out->clean_bytes bytes; never more than scan_end - scan_begin; the walk of a file that turns out not to be
+ * eligible may have written into clean_out as well, never beyond clean_capacity).  SD_OK with eligible 0 for a JPEG that is
+ * not eligible; SD_ERR_FORMAT for a file without SOI; SD_ERR_INVALID for NULL arguments, subseq_bytes that is no power of two in
+ * 32..1024, a file of 256 MiB or more, or an eligible file with more than interval_cap intervals or more than clean_capacity clean
+ * bytes (n_intervals / clean_bytes say what it needs; eligible stays 0). */
+sd_status sd_jpeg_sync_plan(const uint8_t* file_host, size_t len, int subseq_bytes, sd_jpeg_frame_desc* desc_out, sd_jpeg_sync_frame* frame_out,
+                            sd_jpeg_huff_table* tables_out, sd_jpeg_sync_interval* intervals_out, size_t interval_cap, uint8_t* clean_out,
+                            size_t clean_capacity);
+/* HOST: the batch form, as sd_plan_files_jpeg_entropy: file i's clean stream goes to bytes_out_host + i * byte_stride, zero-filled up
+ * to the next multiple of 16. */
+sd_status sd_plan_files_jpeg_sync(const char* const* paths, int n, int height, int width, int subseq_bytes, uint8_t* bytes_out_host,
+                                  size_t byte_stride, sd_jpeg_frame_desc* descs_out, sd_jpeg_sync_frame* frames_out, sd_jpeg_huff_table* tables_out,
+                                  sd_jpeg_sync_interval* intervals_out, size_t interval_stride, int threads, int* status_out);
+/* HOST: the CPU statement of sd_jpeg_sync_decode: the same checks, then the same passes (semantic_depth_amd/csrc/jpeg_sync.hpp) with the
+ * lanes of the kernels run in a loop, in the kernels' schedule, so it predicts which frames the device flags.  For every eligible frame
+ * it clears the frame's coefficients and writes what sd_jpeg_decode_coefficients writes; status_out[b] = 0, or the first code met (1..4
+ * as sd_jpeg_entropy_decode_host, 5, 6 above).  Status 0 implies the sequential decode; a flagged frame is to be decoded by
+ * sd_jpeg_decode_coefficients, which decides it.  Ineligible frames: status 0, coefficients untouched. */
+sd_status sd_jpeg_sync_decode_host(const uint8_t* bytes_host, size_t byte_stride, const sd_jpeg_frame_desc* descs, const sd_jpeg_sync_frame* frames,
+                                   const sd_jpeg_sync_interval* intervals, size_t interval_stride, const sd_jpeg_huff_table* tables, int B,
+                                   int subseq_bytes, int16_t* coef_out_host, size_t coef_stride_bytes, int32_t* status_out);
+/* bytes of device workspace sd_jpeg_sync_decode needs for B frames of at most max_pieces pieces each */
+sd_status sd_jpeg_sync_workspace(int B, size_t interval_stride, size_t max_pieces, size_t* bytes_out);
+/* DEVICE: B frames' clean streams (frame b at bytes_dev + b * byte_stride) -> coefficients and status words as
+ * sd_jpeg_sync_decode_host writes them: status_dev[b] is 0 exactly where that function writes 0, otherwise one of the frame's codes.
+ * The records, tables and ranges are HOST arrays: checked, then uploaded into workspace_dev by asynchronous copies on `stream`.  Six
+ * kernels: clear; the speculative pass (a lane per piece, 256 pieces per workgroup, bounded rounds); the pass across workgroups (a lane
+ * per workgroup, started from the previous workgroup's recorded end); the placement scan of the unit counts; the write pass with the
+ * verification; the segmented scan of the DC differences.  No kernel waits for another workgroup, none uses atomics.  Enqueued on
+ * `stream`, no synchronisation; the handle need not be bound.  SD_ERR_INVALID, and nothing is launched or copied: pointers or strides
+ * that are not multiples of 16; subseq_bytes that is no power of two in 32..1024 or not the plan's; a record that disagrees with its
+ * descriptor; coefficients beyond coef_stride_bytes; a range outside clean_bytes or byte_stride; piece indices that do not follow from
+ * the ranges; more intervals than interval_stride; a table not in decodable form; workspace_bytes below sd_jpeg_sync_workspace of the
+ * largest n_pieces. */
+sd_status sd_jpeg_sync_decode(sd_handle* h, const uint8_t* bytes_dev, size_t byte_stride, const sd_jpeg_frame_desc* descs_host,
+                              const sd_jpeg_sync_frame* frames_host, const sd_jpeg_sync_interval* intervals_host, size_t interval_stride,
+                              const sd_jpeg_huff_table* tables_host, int B, int subseq_bytes, int16_t* coef_dev, size_t coef_stride_bytes,
+                              int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
 /* ---- PNG frames, split route: the host only inflates, the GPU reconstructs the scanlines ----
  * What the reconstruction of one PNG frame needs besides its filtered scanlines.  channels is the bytes per pixel of the 8-bit colour type
  * (0 -> 1, 2 -> 3, 3 -> 1, 4 -> 2, 6 -> 4); palette holds the PLTE entries as the file has them (R, G, B), zero past palette_entries;

@@ -4,16 +4,18 @@ frames/s?  Measures, for frames of one size (default: generated Cityscapes-sized
   upload    pinned host -> HBM copy of decoded frames
   resize    Engine.resize_cubic to 512 x 1024 on the GPU
   feeder    frame_io.FrameFeeder end to end (decode + pinned upload + resize, one batch ahead), best and median of --repeats passes
-    python scripts/feed_rate.py [--frames 256] [--workers N] [--format png|jpeg] [--jpeg host|device|device_entropy] [--frames-dir DIR] [--out FILE]
+    python scripts/feed_rate.py [--frames 256] [--workers N] [--format png|jpeg] [--jpeg host|device|device_entropy|device_sync] [--frames-dir DIR] [--out FILE]
                                 [--size HxW] [--restart-rows N] [--encoder pillow|own] [--compare]
 --frames-dir times the *.png / *.jpg files of a directory instead of generating frames (JPEG frames cannot be written here without
 Pillow, which a GPU box may lack: write them elsewhere and ship them).  --jpeg device feeds through FrameFeeder(jpeg="device"): Huffman
 decoding on the host, reconstruction on the GPU; the script passes jpeg= only then, so --jpeg host also runs in a tree that lacks the
 split route (the parent commit's, for an A/B of the host route).  --jpeg device_entropy feeds through FrameFeeder(jpeg="device_entropy"):
 the host only finds the restart markers, the GPU decodes the Huffman code; it needs files with restart intervals: --restart-rows 1 makes
-Pillow write them, --encoder own writes the frames with the project's encoder (one interval per MCU row).  --compare runs the three JPEG
-routes on the same files in one process, interleaved pass by pass, and adds the plan's single-thread time and the HIP-event time of
-Engine.jpeg_entropy_decode.  Nothing is written unless --out is given.
+Pillow write them, --encoder own writes the frames with the project's encoder (one interval per MCU row).  --jpeg device_sync feeds
+through FrameFeeder(jpeg="device_sync"), which also takes files without restart intervals (--sync-piece: its piece length).  --compare
+runs the four JPEG routes on the same files in one process, interleaved pass by pass, and adds the plans' single-thread times and the
+HIP-event times of Engine.jpeg_entropy_decode (files with restart intervals only) and of Engine.jpeg_sync_decode at 64, 128 and 256 bytes
+per piece.  Nothing is written unless --out is given.
 """
 import argparse
 import ctypes as C
@@ -147,8 +149,58 @@ def _entropy_measurements(eng, paths, workers, res):
     feeder.close()
 
 
-def _feeder_pass(eng, paths, workers, route):
+def _sync_measurements(eng, paths, workers, res):
+    """the sync plan's host time per frame on one thread and the HIP-event time of Engine.jpeg_sync_decode on one resident batch (the
+    uploads of the records and the six kernels) at 64, 128 and 256 bytes per piece, with the frames each flags"""
+    lib = L.load()
+    bufs = [open(p, "rb").read() for p in paths[:8]]
+    cap = 1 << 16
+    d, fr = L.sd_jpeg_frame_desc(), L.sd_jpeg_sync_frame()
+    tables, iv = (L.sd_jpeg_huff_table * L.SD_JPEG_ENTROPY_TABLES)(), (L.sd_jpeg_sync_interval * cap)()
+    clean = np.empty(max(len(b) for b in bufs), np.uint8)
+    for rep in range(2):
+        t0 = time.perf_counter()
+        for b in bufs:
+            assert lib.sd_jpeg_sync_plan(b, len(b), 128, C.byref(d), C.byref(fr), tables, iv, cap, clean.ctypes.data_as(C.c_void_p), clean.nbytes) == L.SD_OK
+        res["sync_plan_ms_per_frame_1_thread"] = (time.perf_counter() - t0) / len(bufs) * 1e3
+    n = min(32, len(paths))
+    res["sync_decode_ms_per_batch"] = {}
+    for piece in (64, 128, 256):
+        feeder = frame_io.FrameFeeder(paths[:n], n, "cuda", workers, jpeg="device_sync", engine=eng, sync_piece=piece)
+        t0 = time.perf_counter()
+        host = feeder._plan_into(0, 0, n)
+        plan_ms = (time.perf_counter() - t0) * 1e3
+        if len(host["eligible"]) != n:
+            res["sync_decode_ms_per_batch"][str(piece)] = {"eligible": len(host["eligible"])}
+            feeder.close()
+            continue
+        used = -(-max(int(host["frames"][i].clean_bytes) for i in range(n)) // 16) * 16
+        sdev = host["pinned"]["bytes"][:n, :used].cuda()
+        h, w = host["size"]
+        out = torch.empty((n, frame_io.FrameFeeder.coef_stride_bytes(h, w) // 2), dtype=torch.int16, device="cuda")
+        args = (sdev, host["descs"], host["frames"], host["tables"], host["intervals"], host["ivs"], piece)
+        _, status = eng.jpeg_sync_decode(*args, out=out)
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(7):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            eng.jpeg_sync_decode(*args, out=out, status=status)
+            b.record()
+            b.synchronize()
+            times.append(a.elapsed_time(b))
+        res["sync_decode_ms_per_batch"][str(piece)] = {
+            "frames": n, "median": float(np.median(times)), "min": float(min(times)), "max": float(max(times)), "plan_ms_per_batch_native": plan_ms,
+            "clean_bytes_per_batch": int(sum(int(host["frames"][i].clean_bytes) for i in range(n))),
+            "pieces_per_frame_max": int(max(int(host["frames"][i].n_pieces) for i in range(n))),
+            "intervals_per_frame": int(host["frames"][0].n_intervals), "flagged_frames": int((status != 0).sum())}
+        feeder.close()
+
+
+def _feeder_pass(eng, paths, workers, route, sync_piece=None):
     kw = {"jpeg": route, "engine": eng} if route != "host" else {}
+    if route == "device_sync" and sync_piece:
+        kw["sync_piece"] = sync_piece
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     n = 0
@@ -156,7 +208,7 @@ def _feeder_pass(eng, paths, workers, route):
         for fr, lo in feeder:
             eng.resize_cubic(fr)
             n += fr.shape[0]
-        fallbacks = len(feeder.entropy_fallback)
+        fallbacks = len(feeder.sync_fallback if route == "device_sync" else feeder.entropy_fallback)
     torch.cuda.synchronize()
     return n / (time.perf_counter() - t0), fallbacks
 
@@ -166,11 +218,12 @@ def main():
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--workers", type=int, default=frame_io.default_decode_workers())
     ap.add_argument("--format", choices=("png", "jpeg"), default="png")
-    ap.add_argument("--jpeg", choices=("host", "device", "device_entropy"), default="host")
+    ap.add_argument("--jpeg", choices=("host", "device", "device_entropy", "device_sync"), default="host")
+    ap.add_argument("--sync-piece", type=int, default=frame_io.SYNC_PIECE_BYTES, help="--jpeg device_sync / --compare: bytes of the clean stream per lane")
     ap.add_argument("--size", default="1024x2048", help="HxW of the generated frames")
     ap.add_argument("--restart-rows", type=int, default=0, help="generated JPEG frames: Pillow's restart_marker_rows (0: no restart intervals)")
     ap.add_argument("--encoder", choices=("pillow", "own"), default="pillow", help="generated JPEG frames: Pillow, or the project's encoder")
-    ap.add_argument("--compare", action="store_true", help="JPEG frames: the three routes interleaved in this process, plan and kernel times")
+    ap.add_argument("--compare", action="store_true", help="JPEG frames: the four routes interleaved in this process, plan and kernel times")
     ap.add_argument("--frames-dir", default=None, help="time the *.png / *.jpg / *.jpeg files of this directory (one size) instead of generating frames")
     ap.add_argument("--repeats", type=int, default=3, help="timed passes of the feeder after one warm pass")
     ap.add_argument("--out", default=None, help="write the JSON record here (default: print only)")
@@ -233,20 +286,29 @@ def main():
             res["resize_fps"] = 32 * 5 / (time.perf_counter() - t0)
             del host, dev
             kw = {"jpeg": a.jpeg, "engine": eng} if a.jpeg != "host" else {}          # (nothing the parent commit's feeder lacks in host mode)
+            if a.jpeg == "device_sync":
+                kw["sync_piece"] = a.sync_piece
+            with open(paths[0], "rb") as f:
+                has_dri = b"\xff\xdd" in f.read(4096)                                 # (the DRI segment comes before the scan)
             if a.jpeg != "host" or a.compare:
                 _kernel_ms_per_batch(eng, paths, a.workers, res)
-            if a.jpeg == "device_entropy" or a.compare:
+            if a.jpeg == "device_entropy" or (a.compare and has_dri):
                 _entropy_measurements(eng, paths, a.workers, res)
-            if a.compare:                                                             # the three routes, pass by pass, in this process
-                routes = ("host", "device", "device_entropy")
+            if a.jpeg == "device_sync" or a.compare:
+                _sync_measurements(eng, paths, a.workers, res)
+            if a.compare:                                                             # the four routes, pass by pass, in this process
+                routes = ("host", "device", "device_entropy", "device_sync")
+                res["restart_intervals_in_files"], res["sync_piece"] = bool(has_dri), a.sync_piece
                 rates = {r: [] for r in routes}
                 for rep in range(a.repeats + 1):
                     for r in routes:
-                        fps, fb = _feeder_pass(eng, paths if rep else paths[:64], a.workers, r)
+                        fps, fb = _feeder_pass(eng, paths if rep else paths[:64], a.workers, r, a.sync_piece)
                         if rep:
                             rates[r].append(fps)
                         if r == "device_entropy":
                             res["entropy_fallback_frames"] = fb
+                        if r == "device_sync":
+                            res["sync_fallback_frames"] = fb
                 res["compare_feeder_fps"] = {r: {"median": float(np.median(v)), "passes": v} for r, v in rates.items()}
             rates = []
             for rep in range(a.repeats + 1):                                          # pass 0 warms (pinned staging allocation, page cache)

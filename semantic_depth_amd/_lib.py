@@ -130,6 +130,19 @@ class sd_jpeg_interval(C.Structure):
     _fields_ = [("begin", C.c_uint32), ("end", C.c_uint32)]
 
 
+class sd_jpeg_sync_frame(C.Structure):
+    _fields_ = [("eligible", C.c_int32), ("ncomp", C.c_int32), ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("restart_interval", C.c_int32),
+                ("n_intervals", C.c_int32), ("comp_h", C.c_int32 * 3), ("comp_v", C.c_int32 * 3), ("comp_dc", C.c_int32 * 3),
+                ("comp_ac", C.c_int32 * 3), ("scan_begin", C.c_uint32), ("scan_end", C.c_uint32), ("clean_bytes", C.c_uint32),
+                ("subseq_bytes", C.c_uint32), ("n_pieces", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class sd_jpeg_sync_interval(C.Structure):
+    _fields_ = [("begin", C.c_uint32), ("end", C.c_uint32), ("first_piece", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SD_JPEG_SYNC_NOT_SYNCHRONISED, SD_JPEG_SYNC_BITS_RAN_OUT, SD_JPEG_SYNC_GROUP = 5, 6, 256
+
 # every symbol include/semdepth.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 _H = C.c_void_p
@@ -166,6 +179,13 @@ SIGNATURES = {
     "sd_jpeg_entropy_decode_host": (C.c_int, [_P, C.c_size_t, _P, _P, _P, C.c_size_t, _P, C.c_int, _P, C.c_size_t, _P]),
     "sd_jpeg_entropy_workspace": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_size_t)]),
     "sd_jpeg_entropy_decode": (C.c_int, [_H, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _P, C.c_int, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
+    "sd_jpeg_sync_plan": (C.c_int, [_P, C.c_size_t, C.c_int, C.POINTER(sd_jpeg_frame_desc), C.POINTER(sd_jpeg_sync_frame), _P, _P, C.c_size_t, _P,
+                                    C.c_size_t]),
+    "sd_plan_files_jpeg_sync": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P, _P, C.c_size_t,
+                                          C.c_int, C.POINTER(C.c_int)]),
+    "sd_jpeg_sync_decode_host": (C.c_int, [_P, C.c_size_t, _P, _P, _P, C.c_size_t, _P, C.c_int, C.c_int, _P, C.c_size_t, _P]),
+    "sd_jpeg_sync_workspace": (C.c_int, [C.c_int, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "sd_jpeg_sync_decode": (C.c_int, [_H, _P, C.c_size_t, _P, _P, _P, C.c_size_t, _P, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, C.c_size_t, _P]),
     "sd_png_inflate_rows": (C.c_int, [_P, C.c_size_t, _P, C.c_size_t, C.POINTER(sd_png_frame_desc)]),
     "sd_inflate_files_png": (C.c_int, [C.POINTER(C.c_char_p), C.c_int, C.c_int, C.c_int, _P, C.c_size_t, C.POINTER(sd_png_frame_desc), C.c_int,
                                        C.POINTER(C.c_int)]),

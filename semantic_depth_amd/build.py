@@ -38,6 +38,7 @@ SOURCES = [
     ("png_gpu.hip", []),
     ("jpeg_enc_gpu.hip", []),
     ("jpeg_entropy_gpu.hip", []),
+    ("jpeg_sync_gpu.hip", []),
     ("png_in_gpu.hip", []),
     ("ply_gpu.hip", ["-ffp-contract=off"]),
     ("scene_gpu.hip", ["-ffp-contract=off"]),
@@ -54,6 +55,7 @@ SOURCES = [
     ("host_png.cpp", []),
     ("host_jpeg.cpp", []),
     ("host_jpeg_entropy.cpp", []),
+    ("host_jpeg_sync.cpp", []),
     ("host_ply.cpp", []),
     ("host_scene.cpp", ["-ffp-contract=off"]),
     ("host_text.cpp", []),
@@ -64,7 +66,7 @@ SOURCES = [
     ("host_seg_eval.cpp", []),
     ("host_disp_image.cpp", ["-ffp-contract=off"]),
 ]
-HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", "jpeg_enc.hpp", "jpeg_enc_gpu.hpp", "jpeg_entropy.hpp", "jpeg_entropy_gpu.hpp", "png_unfilter.hpp", "png_in_gpu.hpp", "ply_format.hpp", "ply_gpu.hpp", "scene_format.hpp", "scene_gpu.hpp", "text_draw.hpp", "text_gpu.hpp", "overlay_rule.hpp", "overlay_gpu.hpp", "render_rule.hpp", "render_gpu.hpp", "rw_profile.hpp", "rw_profile_gpu.hpp", "pil_resample.hpp", "seg_eval_gpu.hpp", "disp_image_rule.hpp", "disp_image_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
+HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", "jpeg_enc.hpp", "jpeg_enc_gpu.hpp", "jpeg_entropy.hpp", "jpeg_entropy_gpu.hpp", "jpeg_sync.hpp", "jpeg_sync_gpu.hpp", "png_unfilter.hpp", "png_in_gpu.hpp", "ply_format.hpp", "ply_gpu.hpp", "scene_format.hpp", "scene_gpu.hpp", "text_draw.hpp", "text_gpu.hpp", "overlay_rule.hpp", "overlay_gpu.hpp", "render_rule.hpp", "render_gpu.hpp", "rw_profile.hpp", "rw_profile_gpu.hpp", "pil_resample.hpp", "seg_eval_gpu.hpp", "disp_image_rule.hpp", "disp_image_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
 
 
 def _hipcc() -> str:

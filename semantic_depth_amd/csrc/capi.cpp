@@ -16,6 +16,7 @@
 #include "png_gpu.hpp"
 #include "jpeg_enc_gpu.hpp"
 #include "jpeg_entropy_gpu.hpp"
+#include "jpeg_sync_gpu.hpp"
 #include "png_in_gpu.hpp"
 #include "ply_gpu.hpp"
 #include "scene_gpu.hpp"
@@ -809,6 +810,37 @@ sd_status sd_jpeg_entropy_decode(sd_handle* h, const uint8_t* bytes_dev, size_t 
         return fail(h, SD_ERR_INVALID, "sd_jpeg_entropy_decode: workspace smaller than sd_jpeg_entropy_workspace reports");
     HIPCHK(h, launch_jpeg_entropy_decode(bytes_dev, byte_stride, descs_host, frames_host, intervals_host, interval_stride, tables_host, B, coef_dev,
                                          coef_stride_bytes / sizeof(int16_t), status_dev, static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
+    return SD_OK;
+}
+
+sd_status sd_jpeg_sync_workspace(int B, size_t interval_stride, size_t max_pieces, size_t* bytes_out) {
+    if (B < 1 || B > 65535 || interval_stride < 1 || interval_stride > ((size_t)1 << 24) || max_pieces > ((size_t)1 << 24) || !bytes_out) return SD_ERR_INVALID;
+    *bytes_out = jpeg_sync_workspace_bytes(B, interval_stride, max_pieces);
+    return SD_OK;
+}
+
+sd_status sd_jpeg_sync_decode(sd_handle* h, const uint8_t* bytes_dev, size_t byte_stride, const sd_jpeg_frame_desc* descs_host,
+                              const sd_jpeg_sync_frame* frames_host, const sd_jpeg_sync_interval* intervals_host, size_t interval_stride,
+                              const sd_jpeg_huff_table* tables_host, int B, int subseq_bytes, int16_t* coef_dev, size_t coef_stride_bytes,
+                              int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream) {
+    if (!h || !bytes_dev || !descs_host || !frames_host || !intervals_host || !tables_host || B < 1 || B > 65535 || !coef_dev || !status_dev ||
+        !workspace_dev || interval_stride < 1 || interval_stride > ((size_t)1 << 24))
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_sync_decode: bad arguments");
+    // the lanes fetch aligned 8-byte words of the clean stream and the clearing kernel stores 16-byte pieces
+    if ((reinterpret_cast<uintptr_t>(bytes_dev) & 15) || (byte_stride & 15) || (reinterpret_cast<uintptr_t>(coef_dev) & 15) || (coef_stride_bytes & 15) ||
+        (reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(status_dev) & 3))
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_sync_decode: bytes_dev, byte_stride, coef_dev, coef_stride_bytes and workspace_dev must be multiples of 16");
+    // every index the kernels form follows from records that agree with their descriptors and these capacities: nothing is launched otherwise
+    const char* why = "";
+    if (!sdjsync::args_ok(byte_stride, descs_host, frames_host, intervals_host, interval_stride, tables_host, B, subseq_bytes, coef_stride_bytes, &why))
+        return fail(h, SD_ERR_INVALID, std::string("sd_jpeg_sync_decode: ") + why);
+    size_t most = 0;
+    for (int b = 0; b < B; ++b)
+        if (frames_host[b].eligible && frames_host[b].n_pieces > most) most = frames_host[b].n_pieces;
+    if (most > ((size_t)1 << 24) || workspace_bytes < jpeg_sync_workspace_bytes(B, interval_stride, most))
+        return fail(h, SD_ERR_INVALID, "sd_jpeg_sync_decode: workspace smaller than sd_jpeg_sync_workspace reports for the largest frame");
+    HIPCHK(h, launch_jpeg_sync_decode(bytes_dev, byte_stride, frames_host, intervals_host, interval_stride, tables_host, B, subseq_bytes, most, coef_dev,
+                                      coef_stride_bytes / sizeof(int16_t), status_dev, static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
     return SD_OK;
 }
 

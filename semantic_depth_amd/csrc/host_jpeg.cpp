@@ -652,6 +652,87 @@ struct Decoder {
         return SD_OK;
     }
 
+    // The plan of the sync route (sd_jpeg_sync_plan): plan()'s rule with DRI = 0 admitted -- such a scan is one interval of all its
+    // MCUs -- and the same byte walk, which here also writes the CLEAN stream: the data between the FFs copied, FF 00 as FF, the RSTk
+    // dropped.  S is the piece length the piece indices are counted with.
+    sd_status plan_sync(int S, sd_jpeg_frame_desc* desc, sd_jpeg_sync_frame* fr, sd_jpeg_huff_table* tables, sd_jpeg_sync_interval* iv, size_t iv_cap,
+                        uint8_t* clean, size_t clean_cap) {
+        std::memset(desc, 0, sizeof(*desc));
+        std::memset(fr, 0, sizeof(*fr));
+        std::memset(tables, 0, sizeof(*tables) * SD_JPEG_ENTROPY_TABLES);
+        if (parse(false) != SD_OK || !sos || progressive || restart < 0) return SD_OK;
+        if (sos_len < 1) return SD_OK;
+        const int ns = sos[0];
+        if (ns != ncomp || sos_len < 1 + 2 * (size_t)ns + 3) return SD_OK;
+        for (int i = 0; i < ncomp; ++i) {
+            if (sos[1 + 2 * i] != comp[i].id) return SD_OK;
+            for (int j = 0; j < i; ++j) if (comp[j].id == comp[i].id) return SD_OK;
+            comp[i].td = sos[2 + 2 * i] >> 4; comp[i].ta = sos[2 + 2 * i] & 15;
+            if (comp[i].td > 3 || comp[i].ta > 3) return SD_OK;
+            if (!dc[comp[i].td].present || !ac[comp[i].ta].present || !qt_ok[comp[i].tq]) return SD_OK;
+        }
+        const int mcus_x = (W + 8 * hmax - 1) / (8 * hmax), mcus_y = (H + 8 * vmax - 1) / (8 * vmax);
+        const int64_t total = (int64_t)mcus_x * mcus_y;
+        if (total < 1 || total > 0x7fffffff) return SD_OK;
+        const int64_t per = restart ? restart : total, n_iv = (total + per - 1) / per;
+        size_t pos = sos_data, from = sos_data;      // from: the first byte not yet copied
+        size_t out = 0, begin_out = 0;               // clean bytes so far; where the open interval began
+        uint64_t piece = 0;
+        int64_t count = 0;
+        bool closed = false;
+        auto copy = [&](size_t upto) {               // the data bytes [from, upto)
+            if (clean && out + (upto - from) <= clean_cap) std::memcpy(clean + out, f + from, upto - from);
+            out += upto - from;
+        };
+        auto close = [&]() {
+            if ((size_t)count < iv_cap) { iv[count].begin = (uint32_t)begin_out; iv[count].end = (uint32_t)out; iv[count].first_piece = (uint32_t)piece; iv[count].reserved = 0; }
+            piece += out > begin_out ? (out - begin_out + (size_t)S - 1) / (size_t)S : 1;
+            ++count;
+            begin_out = out;
+        };
+        while (pos < len) {
+            const uint8_t* q = static_cast<const uint8_t*>(std::memchr(f + pos, 0xFF, len - pos));
+            if (!q) break;
+            const size_t at = (size_t)(q - f);
+            if (at + 1 >= len) break;
+            const int m = f[at + 1];
+            if (m == 0x00) { copy(at + 1); from = pos = at + 2; continue; }      // the FF is data, its 00 is not
+            const bool last = count + 1 == n_iv;
+            if (!last && m == 0xD0 + (int)(count & 7)) {
+                copy(at);
+                close();
+                from = pos = at + 2;
+                continue;
+            }
+            if (last && m == 0xD9 && at + 2 == len) {
+                copy(at);
+                close();
+                fr->scan_begin = (uint32_t)sos_data; fr->scan_end = (uint32_t)at;
+                closed = true;
+            }
+            break;
+        }
+        if (!closed) return SD_OK;
+        for (int i = 0; i < ncomp; ++i) std::memcpy(qt_used[i], qt[comp[i].tq], sizeof(qt_used[i]));
+        fill_desc(desc);
+        fr->ncomp = ncomp; fr->mcus_x = mcus_x; fr->mcus_y = mcus_y; fr->restart_interval = (int32_t)per; fr->n_intervals = (int32_t)n_iv;
+        fr->clean_bytes = (uint32_t)out; fr->subseq_bytes = (uint32_t)S; fr->n_pieces = (uint32_t)piece;
+        for (int i = 0; i < ncomp; ++i) {
+            fr->comp_h[i] = comp[i].h; fr->comp_v[i] = comp[i].v; fr->comp_dc[i] = comp[i].td; fr->comp_ac[i] = comp[i].ta;
+            for (int k = 0; k < 2; ++k) {
+                const Huff& h = k ? ac[comp[i].ta] : dc[comp[i].td];
+                sd_jpeg_huff_table& t = tables[k ? 4 + comp[i].ta : comp[i].td];
+                std::memcpy(t.look, h.look, sizeof(t.look));
+                std::memcpy(t.vals, h.vals, sizeof(t.vals));
+                for (int l = 1; l <= 16; ++l) { t.mincode[l] = h.mincode[l]; t.maxcode[l] = h.maxcode[l]; t.valptr[l] = h.valptr[l]; }
+                t.maxcode[17] = h.maxcode[17];
+            }
+        }
+        if ((size_t)n_iv > iv_cap || (clean && out > clean_cap)) return SD_ERR_INVALID;       // (eligible stays 0; the record says what the file needs)
+        fr->eligible = 1;
+        return SD_OK;
+    }
+
     // the back half from a coefficient buffer: the planes of a descriptor's geometry, every block transformed, then emit_bgr
     sd_status reconstruct(const int16_t* coef, const sd_jpeg_frame_desc& d, uint8_t* out, size_t cap) {
         if (!sdjpeg::desc_ok(d) || cap < (size_t)d.height * d.width * 3) return SD_ERR_INVALID;
@@ -775,6 +856,22 @@ extern "C" sd_status sd_jpeg_entropy_plan(const uint8_t* file_host, size_t len, 
         Decoder d;
         d.f = file_host; d.len = len;
         return d.plan(desc_out, frame_out, tables_out, intervals_out, interval_cap);
+    } catch (...) {
+        return SD_ERR_INVALID;
+    }
+}
+
+extern "C" sd_status sd_jpeg_sync_plan(const uint8_t* file_host, size_t len, int subseq_bytes, sd_jpeg_frame_desc* desc_out, sd_jpeg_sync_frame* frame_out,
+                                       sd_jpeg_huff_table* tables_out, sd_jpeg_sync_interval* intervals_out, size_t interval_cap, uint8_t* clean_out,
+                                       size_t clean_capacity) {
+    if (frame_out) std::memset(frame_out, 0, sizeof(*frame_out));       // eligible is 0 on every return but the eligible one
+    if (!file_host || !desc_out || !frame_out || !tables_out || (!intervals_out && interval_cap) || len >= ((size_t)1 << 28)) return SD_ERR_INVALID;
+    if (subseq_bytes < 32 || subseq_bytes > 1024 || (subseq_bytes & (subseq_bytes - 1))) return SD_ERR_INVALID;
+    if (len < 2 || file_host[0] != 0xFF || file_host[1] != 0xD8) return SD_ERR_FORMAT;
+    try {
+        Decoder d;
+        d.f = file_host; d.len = len;
+        return d.plan_sync(subseq_bytes, desc_out, frame_out, tables_out, intervals_out, interval_cap, clean_out, clean_capacity);
     } catch (...) {
         return SD_ERR_INVALID;
     }

@@ -104,11 +104,13 @@ def run_sequence_files(paths, step, batch: int = 32, group=None, device="cuda", 
     ``outputs`` (default: ``step.outputs``, set by ``make_engine_step(..., outputs=)``): an outputs.SequenceOutputs the step feeds; this
     rank writes the files of its shard only, and the manifest last -- 'ok', or 'range_error' / 'error' when the run raised (the files
     written before are then not valid outputs; the exception still propagates).
-    ``jpeg`` ("host" | "device" | "device_entropy") and ``engine`` go to the feeder: with "device" the JPEG frames are only entropy-decoded on
+    ``jpeg`` ("host" | "device" | "device_entropy" | "device_sync") and ``engine`` go to the feeder: with "device" the JPEG frames are only entropy-decoded on
     the host and reconstructed on the GPU by ``engine`` (default: ``step.engine``, set by make_engine_step); with "device_entropy" the files
     that have restart intervals (one interleaved sequential scan, DRI > 0, nothing but stuffed bytes and the expected RSTk markers in it) are
     entropy-decoded on the GPU as well, the host only finds their markers, and every other JPEG falls back to the host decoder
-    (FrameFeeder.entropy_fallback names them); the frames are the same bytes on all three.
+    (FrameFeeder.entropy_fallback names them); with "device_sync" the files without restart intervals are entropy-decoded on the GPU too,
+    in short pieces that find the decoder's state by themselves (FrameFeeder.sync_fallback names the frames that took the host decoder);
+    the frames are the same bytes on all four.
     ``png_in`` (None = "host" | "device") is the feeder's ``png=`` (``png`` here already names the output writer): with "device" the PNG
     frames are only inflated on the host and their scanlines reconstructed on the GPU by ``engine``; the frames are the same bytes.
     ``png``, ``ply``, ``text``, ``render``, ``video``, ``disp``, ``lines``, ``scene`` (None = what the SequenceOutputs was built with) go to

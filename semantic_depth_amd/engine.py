@@ -489,6 +489,39 @@ class Engine:
         L.check(self.lib, self.h, st, "sd_jpeg_entropy_decode")
         return out, status
 
+    def jpeg_sync_decode(self, clean: torch.Tensor, descs, frames, tables, intervals, interval_stride: int, subseq_bytes: int,
+                         coef_stride: int | None = None, out: torch.Tensor | None = None, status: torch.Tensor | None = None):
+        """the device half of the sync JPEG route (sd_jpeg_sync_decode): ``clean`` u8 [B, byte_stride] device tensor of the frames' clean
+        streams (byte_stride a multiple of 16) plus the plan records of sd_jpeg_sync_plan / sd_plan_files_jpeg_sync at ``subseq_bytes``
+        -- ``descs`` B _lib.sd_jpeg_frame_desc, ``frames`` B _lib.sd_jpeg_sync_frame, ``tables`` B * 8 _lib.sd_jpeg_huff_table,
+        ``intervals`` B * interval_stride _lib.sd_jpeg_sync_interval, all HOST ctypes arrays -> (coef int16 [B, coef_stride], status
+        int32 [B]) device tensors: the coefficients sd_jpeg_decode_coefficients writes for every eligible frame whose status word is 0
+        (1..4: the stream was refused; 5: the pieces did not synchronise; 6: the bits ran out -- the host decoder decides those
+        frames); ineligible frames keep what ``out`` held.  A lane per piece of subseq_bytes, files without DRI included, on the current
+        stream, no synchronisation: the host arrays must stay unchanged until the stream has passed the call when they are pinned."""
+        assert clean.dtype == torch.uint8 and clean.is_cuda and clean.is_contiguous() and clean.dim() == 2
+        B = clean.shape[0]
+        if B < 1 or len(descs) < B or len(frames) < B:
+            raise ValueError("jpeg_sync_decode: one descriptor and one record per frame")
+        if coef_stride is None:
+            coef_stride = out.shape[1] if out is not None else max(-(-descs[i].coef_elems() // 8) * 8 for i in range(B))
+        if out is None:
+            out = torch.empty((B, coef_stride), dtype=torch.int16, device=self.device)
+        if status is None:
+            status = torch.empty((B,), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int16 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (B, coef_stride)
+        assert status.dtype == torch.int32 and status.is_cuda and status.is_contiguous() and status.numel() >= B
+        most = max([1] + [frames[i].n_pieces for i in range(B) if frames[i].eligible])
+        need = C.c_size_t()
+        st = self.lib.sd_jpeg_sync_workspace(B, interval_stride, most, C.byref(need))
+        L.check(self.lib, None, st, "sd_jpeg_sync_workspace")
+        ws = torch.empty((need.value,), dtype=torch.uint8, device=self.device)
+        st = self.lib.sd_jpeg_sync_decode(self.h, _ptr(clean), clean.shape[1], _raw(descs), _raw(frames), _raw(intervals), interval_stride,
+                                          _raw(tables), B, subseq_bytes, _ptr(out), coef_stride * 2, _ptr(status), _ptr(ws), need.value,
+                                          self._stream())
+        L.check(self.lib, self.h, st, "sd_jpeg_sync_decode")
+        return out, status
+
     def compose_result_frames(self, frames: torch.Tensor, road: torch.Tensor, fence: torch.Tensor, records: torch.Tensor, out_h: int, out_w: int,
                               road_color=(128, 64, 128), fence_color=(190, 153, 153), alpha: int = 64, out: torch.Tensor | None = None) -> torch.Tensor:
         """the sequence tool's result image (semantic_depth_cityscapes_sequence.py:303-336) for B device frames in one launch

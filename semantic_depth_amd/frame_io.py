@@ -19,6 +19,8 @@ conversion and the EXIF orientation on the GPU (Engine.jpeg_reconstruct), byte f
 ``jpeg="device_entropy"`` moves the Huffman decoder to the GPU as well for files with restart intervals (the project's own encoder,
 MJPEG cameras, Pillow's restart_marker_rows / restart_marker_blocks): the host only finds the markers (sd_plan_files_jpeg_entropy, a
 byte scan), Engine.jpeg_entropy_decode decodes one restart interval per lane, and every other file falls back to the host decoder.
+``jpeg="device_sync"`` reaches the files without restart intervals too: the host writes the scan without stuffing and markers
+(sd_plan_files_jpeg_sync) and Engine.jpeg_sync_decode decodes it in short pieces that find the decoder's state by themselves.
 """
 from __future__ import annotations
 
@@ -30,6 +32,8 @@ from concurrent.futures import ThreadPoolExecutor
 import numpy as np
 
 from . import _lib as L
+
+SYNC_PIECE_BYTES = 64       # jpeg="device_sync": bytes of the clean stream one lane decodes ("JPEG entropy decoding in pieces")
 
 _SIG = b"\x89PNG\r\n\x1a\n"
 _CHANNELS = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
@@ -236,6 +240,13 @@ class FrameFeeder:
     the feeder's own: the feeder waits on that stream, never on the compute stream.  Frames, indices, batch boundaries and the PNG
     handling are those of the other routes.  It takes the Huffman decoder off the host threads; it is not the faster feeder yet: with one
     interval per MCU row it measured slower than ``jpeg="device"`` at 512x1024, 1024x2048 and 3024x4032.
+    ``jpeg="device_sync"`` (same needs): the entropy route for files WITHOUT restart intervals as well -- what Pillow's default save,
+    cv2.imwrite and most cameras write.  The worker thread plans the files (sd_plan_files_jpeg_sync) and writes their CLEAN streams
+    (stuffing resolved, RST markers dropped) into pinned staging; Engine.jpeg_sync_decode cuts every interval -- a scan without DRI is
+    one -- into pieces of ``sync_piece`` bytes that find the decoder's state by themselves, decodes a piece per lane and verifies the
+    chain of states, so a status word of 0 means the sequential decode.  Ineligible files (progressive, multi-scan, stray markers) and
+    frames the kernels flag (refused streams, pieces that did not synchronise, bits that ran out) go through the host decoder;
+    ``sync_fallback`` lists them as ``entropy_fallback`` does.  Frames, indices and batch boundaries are those of the other routes.
     ``png="device"`` (same needs; combines with every ``jpeg=`` choice): the worker thread only walks the chunks of the batch's PNG
     files and inflates their IDAT streams into pinned staging (sd_inflate_files_png), one batch ahead as well.  The filtered scanlines
     go up as they are -- about the byte count of the BGR frame -- and Engine.png_reconstruct runs the filter recurrence, the channel
@@ -245,7 +256,8 @@ class FrameFeeder:
     are read back only for a batch that holds a palette frame, on the same copy stream ("PNG reconstruction on the
     device")."""
 
-    def __init__(self, paths, batch: int, device="cuda", workers: int = 0, jpeg: str = "host", engine=None, png: str = "host"):
+    def __init__(self, paths, batch: int, device="cuda", workers: int = 0, jpeg: str = "host", engine=None, png: str = "host",
+                 sync_piece: int = SYNC_PIECE_BYTES):
         import os
         import torch
         self.paths, self.batch, self.device = list(paths), batch, torch.device(device)
@@ -258,8 +270,12 @@ class FrameFeeder:
         self.png = png
         self._pinned_rows = [None, None]
         self._others = [None, None]           # png="device": per staging slot, the feeder that takes the batch's files that are not PNGs
-        if jpeg not in ("host", "device", "device_entropy"):
-            raise ValueError(f"FrameFeeder: jpeg must be 'host', 'device' or 'device_entropy', not {jpeg!r}")
+        if jpeg not in ("host", "device", "device_entropy", "device_sync"):
+            raise ValueError(f"FrameFeeder: jpeg must be 'host', 'device', 'device_entropy' or 'device_sync', not {jpeg!r}")
+        if sync_piece not in (32, 64, 128, 256, 512, 1024):
+            raise ValueError(f"FrameFeeder: sync_piece must be a power of two from 32 to 1024, not {sync_piece!r}")
+        self.sync_piece = sync_piece
+        self.sync_fallback = []
         if jpeg != "host" and self.device.type != "cuda":
             raise ValueError(f"FrameFeeder: jpeg={jpeg!r} reconstructs the frames on the GPU; device='cpu' has none")
         if jpeg != "host" and engine is None:
@@ -409,8 +425,10 @@ class FrameFeeder:
         return buf, descs
 
     def _plan_into(self, slot: int, lo: int, hi: int):
-        """entropy route, host part of one batch: the plan call into pinned staging, the host coefficient decoder for the JPEGs that are
-        not eligible, the BGR route for the files that are not JPEGs"""
+        """entropy and sync routes, host part of one batch: the plan call into pinned staging (the sync route's writes the clean
+        stream there), the host coefficient decoder for the JPEGs that are not eligible, the BGR route for the files that are not JPEGs"""
+        sync = self.jpeg == "device_sync"
+        frame_t, interval_t = (L.sd_jpeg_sync_frame, L.sd_jpeg_sync_interval) if sync else (L.sd_jpeg_entropy_frame, L.sd_jpeg_interval)
         import os
         torch = self._torch
         h, w = self._header_size(self.paths[lo])
@@ -430,20 +448,24 @@ class FrameFeeder:
                 return torch.empty((nbytes,), dtype=torch.uint8, pin_memory=True)
             st_ = self._pinned_ent[slot] = dict(
                 bytes=torch.empty((self.batch, byte_stride), dtype=torch.uint8, pin_memory=True), ivs=ivs,
-                descs=pin(self.batch * C.sizeof(L.sd_jpeg_frame_desc)), frames=pin(self.batch * C.sizeof(L.sd_jpeg_entropy_frame)),
-                tables=pin(self.batch * T * C.sizeof(L.sd_jpeg_huff_table)), intervals=pin(self.batch * ivs * C.sizeof(L.sd_jpeg_interval)),
+                descs=pin(self.batch * C.sizeof(L.sd_jpeg_frame_desc)), frames=pin(self.batch * C.sizeof(frame_t)),
+                tables=pin(self.batch * T * C.sizeof(L.sd_jpeg_huff_table)), intervals=pin(self.batch * ivs * C.sizeof(interval_t)),
                 status=torch.empty((self.batch,), dtype=torch.int32, pin_memory=True))
         byte_stride = st_["bytes"].shape[1]
         # the records live in the pinned buffers: the C call uploads them with asynchronous copies, and a slot is not planned into again
         # before the event of its last batch has passed
         descs = (L.sd_jpeg_frame_desc * n).from_address(st_["descs"].data_ptr())
-        frames = (L.sd_jpeg_entropy_frame * n).from_address(st_["frames"].data_ptr())
+        frames = (frame_t * n).from_address(st_["frames"].data_ptr())
         tables = (L.sd_jpeg_huff_table * (n * T)).from_address(st_["tables"].data_ptr())
-        intervals = (L.sd_jpeg_interval * (n * ivs)).from_address(st_["intervals"].data_ptr())
+        intervals = (interval_t * (n * ivs)).from_address(st_["intervals"].data_ptr())
         arr = (C.c_char_p * n)(*[os_fsencode(p) for p in self.paths[lo:hi]])
         status = (C.c_int * n)()
-        self._lib.sd_plan_files_jpeg_entropy(arr, n, h, w, C.c_void_p(st_["bytes"].data_ptr()), byte_stride, descs, frames, tables, intervals,
-                                             ivs, self.workers, status)
+        if sync:
+            self._lib.sd_plan_files_jpeg_sync(arr, n, h, w, self.sync_piece, C.c_void_p(st_["bytes"].data_ptr()), byte_stride, descs, frames, tables,
+                                              intervals, ivs, self.workers, status)
+        else:
+            self._lib.sd_plan_files_jpeg_entropy(arr, n, h, w, C.c_void_p(st_["bytes"].data_ptr()), byte_stride, descs, frames, tables, intervals,
+                                                 ivs, self.workers, status)
         others = [i for i in range(n) if status[i] == L.SD_ERR_FORMAT]
         eligible = [i for i in range(n) if status[i] == L.SD_OK and frames[i].eligible]
         # every other file -- not eligible, unreadable, too large for the staging -- is the host decoder's: it decodes it or raises what
@@ -467,8 +489,12 @@ class FrameFeeder:
 
     def _entropy_reconstruct(self, host):
         """entropy route, GPU part of one batch on the current stream: the scan bytes' upload, the entropy kernels, the uploads of the
-        host-decoded frames, the status words' way back on the feeder's copy stream, then the reconstruction of the "device" route"""
+        host-decoded frames, the status words' way back on the feeder's copy stream, then the reconstruction of the "device" route.
+        The sync route is the same walk with Engine.jpeg_sync_decode on the clean streams; its flagged frames are real (a stream the
+        pieces did not synchronise on, or whose bits ran out, is the host decoder's to decide) and are listed in ``sync_fallback``."""
         torch = self._torch
+        sync = self.jpeg == "device_sync"
+        fell = self.sync_fallback if sync else self.entropy_fallback
         n, lo, (h, w), pin = host["n"], host["lo"], host["size"], host["pinned"]
         dev = torch.empty((n, h, w, 3), dtype=torch.uint8, device=self.device)
         cstride = self.coef_stride_bytes(h, w) // 2
@@ -480,8 +506,12 @@ class FrameFeeder:
             sdev = torch.empty((n, pin["bytes"].shape[1]), dtype=torch.uint8, device=self.device)
             sdev.copy_(pin["bytes"][:n], non_blocking=True)
             status = torch.empty((n,), dtype=torch.int32, device=self.device)
-            self.engine.jpeg_entropy_decode(sdev, host["descs"], host["frames"], host["tables"], host["intervals"], host["ivs"], out=cdev,
-                                            status=status)
+            if sync:
+                self.engine.jpeg_sync_decode(sdev, host["descs"], host["frames"], host["tables"], host["intervals"], host["ivs"], self.sync_piece,
+                                             out=cdev, status=status)
+            else:
+                self.engine.jpeg_entropy_decode(sdev, host["descs"], host["frames"], host["tables"], host["intervals"], host["ivs"], out=cdev,
+                                                status=status)
             for i in host["eligible"]:
                 descs[i] = host["descs"][i]
             if self._copy_stream is None:
@@ -498,7 +528,7 @@ class FrameFeeder:
                 k = fdescs[j].coef_elems()
                 cdev[i, :k].copy_(buf[j, :k], non_blocking=True)
                 descs[i] = fdescs[j]
-                self.entropy_fallback.append((lo + i, "ineligible"))
+                fell.append((lo + i, "ineligible"))
         if host["eligible"]:
             self._copy_stream.synchronize()                 # the feeder's own stream: the status words are in pinned memory now
             flagged = [i for i in host["eligible"] if int(pin["status"][i]) != 0]
@@ -511,8 +541,8 @@ class FrameFeeder:
                     k = fdescs[j].coef_elems()
                     cdev[i, :k].copy_(buf[j, :k], non_blocking=True)
                     descs[i] = fdescs[j]
-                    self.entropy_fallback.append((lo + i, "flagged"))
-                self.entropy_fallback.sort()
+                    fell.append((lo + i, "flagged"))
+                fell.sort()
         j0 = 0
         while j0 < len(jp):                                 # runs of consecutive JPEG frames, as on the "device" route
             j1 = j0 + 1
@@ -559,9 +589,9 @@ class FrameFeeder:
             sub = self._others[slot]
             if sub is None:
                 sub = self._others[slot] = FrameFeeder([], self.batch, device=self.device, workers=self.workers, jpeg=self.jpeg,
-                                                       engine=self.engine if self.jpeg != "host" else None)
+                                                       engine=self.engine if self.jpeg != "host" else None, sync_piece=self.sync_piece)
             sub.paths = [self.paths[lo + i] for i in others]
-            stage = {"host": sub._decode_into, "device": sub._decode_coef_into, "device_entropy": sub._plan_into}[self.jpeg]
+            stage = {"host": sub._decode_into, "device": sub._decode_coef_into, "device_entropy": sub._plan_into, "device_sync": sub._plan_into}[self.jpeg]
             rest = stage(slot, 0, len(others))
             rh, rw = tuple(rest.shape[1:3]) if self.jpeg == "host" else (rest[3] if self.jpeg == "device" else rest["size"])
             if (rh, rw) != (h, w):
@@ -614,7 +644,8 @@ class FrameFeeder:
             else:
                 rdev2 = (sub._reconstruct if self.jpeg == "device" else sub._entropy_reconstruct)(rest)
                 self.entropy_fallback += [(lo + host["others"][j], why) for j, why in sub.entropy_fallback]
-                sub.entropy_fallback = []
+                self.sync_fallback += [(lo + host["others"][j], why) for j, why in sub.sync_fallback]
+                del sub.entropy_fallback[:], sub.sync_fallback[:]
             for j, i in enumerate(host["others"]):
                 dev[i].copy_(rdev2[j], non_blocking=True)
         if palette:
@@ -631,11 +662,12 @@ class FrameFeeder:
         if not ranges:
             return
         with ThreadPoolExecutor(max_workers=1) as ahead:
-            decode = {"host": self._decode_into, "device": self._decode_coef_into, "device_entropy": self._plan_into}[self.jpeg]
-            rebuild = {"device": self._reconstruct, "device_entropy": self._entropy_reconstruct}.get(self.jpeg)
+            decode = {"host": self._decode_into, "device": self._decode_coef_into, "device_entropy": self._plan_into, "device_sync": self._plan_into}[self.jpeg]
+            rebuild = {"device": self._reconstruct, "device_entropy": self._entropy_reconstruct, "device_sync": self._entropy_reconstruct}.get(self.jpeg)
             if self.png == "device":
                 decode, rebuild = self._inflate_into, self._png_reconstruct
             self.entropy_fallback = []
+            self.sync_fallback = []
             fut = ahead.submit(decode, 0, *ranges[0])
             events = [None, None]
             for k, (lo, hi) in enumerate(ranges):
