@@ -107,6 +107,12 @@ def _kernel_ms_per_batch(eng, paths, workers, res):
     res["reconstruct_kernels_ms_per_batch"] = {"frames": n, "median": float(np.median(times)), "min": float(min(times)), "max": float(max(times))}
 
 
+def _staged_plan(feeder, n):
+    """the host half of the feeder's plan stage on its first n files -> (the plan, the stage's pinned staging, (h, w))"""
+    stage, batch = feeder.stages[0], feeder._decode_into(0, 0, n)
+    return batch.payload[stage.name], batch.pinned[stage.name], batch.size
+
+
 def _entropy_measurements(eng, paths, workers, res):
     """the plan's host time per frame on one thread (against coefficients_ms_per_frame_1_thread on the same files) and the HIP-event
     time of Engine.jpeg_entropy_decode on one resident batch: the uploads of the records, the clearing kernel and the decoding kernel"""
@@ -124,16 +130,15 @@ def _entropy_measurements(eng, paths, workers, res):
     n = min(32, len(paths))
     feeder = frame_io.FrameFeeder(paths[:n], n, "cuda", workers, jpeg="device_entropy", engine=eng)
     t0 = time.perf_counter()
-    host = feeder._plan_into(0, 0, n)
+    plan, staged, (h, w) = _staged_plan(feeder, n)
     res["plan_ms_per_batch_native"] = (time.perf_counter() - t0) * 1e3
-    assert len(host["eligible"]) == n
-    used = max(int(host["frames"][i].scan_end - host["frames"][i].scan_begin) for i in range(n))
+    assert len(plan.eligible) == n
+    used = max(int(plan.frames[i].scan_end - plan.frames[i].scan_begin) for i in range(n))
     used = -(-used // 16) * 16
     res["scan_bytes_per_frame_max"] = used
-    sdev = host["pinned"]["bytes"][:n, :used].cuda()
-    h, w = host["size"]
+    sdev = staged.bytes[:n, :used].cuda()
     out = torch.empty((n, frame_io.FrameFeeder.coef_stride_bytes(h, w) // 2), dtype=torch.int16, device="cuda")
-    args = (sdev, host["descs"], host["frames"], host["tables"], host["intervals"], host["ivs"])
+    args = (sdev, plan.descs, plan.frames, plan.tables, plan.intervals, plan.ivs)
     _, status = eng.jpeg_entropy_decode(*args, out=out)
     torch.cuda.synchronize()
     assert int(status.abs().sum()) == 0
@@ -168,17 +173,16 @@ def _sync_measurements(eng, paths, workers, res):
     for piece in (64, 128, 256):
         feeder = frame_io.FrameFeeder(paths[:n], n, "cuda", workers, jpeg="device_sync", engine=eng, sync_piece=piece)
         t0 = time.perf_counter()
-        host = feeder._plan_into(0, 0, n)
+        plan, staged, (h, w) = _staged_plan(feeder, n)
         plan_ms = (time.perf_counter() - t0) * 1e3
-        if len(host["eligible"]) != n:
-            res["sync_decode_ms_per_batch"][str(piece)] = {"eligible": len(host["eligible"])}
+        if len(plan.eligible) != n:
+            res["sync_decode_ms_per_batch"][str(piece)] = {"eligible": len(plan.eligible)}
             feeder.close()
             continue
-        used = -(-max(int(host["frames"][i].clean_bytes) for i in range(n)) // 16) * 16
-        sdev = host["pinned"]["bytes"][:n, :used].cuda()
-        h, w = host["size"]
+        used = -(-max(int(plan.frames[i].clean_bytes) for i in range(n)) // 16) * 16
+        sdev = staged.bytes[:n, :used].cuda()
         out = torch.empty((n, frame_io.FrameFeeder.coef_stride_bytes(h, w) // 2), dtype=torch.int16, device="cuda")
-        args = (sdev, host["descs"], host["frames"], host["tables"], host["intervals"], host["ivs"], piece)
+        args = (sdev, plan.descs, plan.frames, plan.tables, plan.intervals, plan.ivs, piece)
         _, status = eng.jpeg_sync_decode(*args, out=out)
         torch.cuda.synchronize()
         times = []
@@ -191,9 +195,9 @@ def _sync_measurements(eng, paths, workers, res):
             times.append(a.elapsed_time(b))
         res["sync_decode_ms_per_batch"][str(piece)] = {
             "frames": n, "median": float(np.median(times)), "min": float(min(times)), "max": float(max(times)), "plan_ms_per_batch_native": plan_ms,
-            "clean_bytes_per_batch": int(sum(int(host["frames"][i].clean_bytes) for i in range(n))),
-            "pieces_per_frame_max": int(max(int(host["frames"][i].n_pieces) for i in range(n))),
-            "intervals_per_frame": int(host["frames"][0].n_intervals), "flagged_frames": int((status != 0).sum())}
+            "clean_bytes_per_batch": int(sum(int(plan.frames[i].clean_bytes) for i in range(n))),
+            "pieces_per_frame_max": int(max(int(plan.frames[i].n_pieces) for i in range(n))),
+            "intervals_per_frame": int(plan.frames[0].n_intervals), "flagged_frames": int((status != 0).sum())}
         feeder.close()
 
 

@@ -5,26 +5,12 @@
 #include "../../include/semdepth.h"
 #include "jpeg_sync.hpp"
 
-#include <atomic>
-#include <cstdio>
+#include "file_pool.hpp"
+
 #include <cstring>
-#include <thread>
 #include <vector>
 
 namespace {
-
-bool read_whole_file(const char* path, std::vector<uint8_t>& buf) {
-    FILE* fp = std::fopen(path, "rb");
-    if (!fp) return false;
-    std::fseek(fp, 0, SEEK_END);
-    const long n = std::ftell(fp);
-    std::fseek(fp, 0, SEEK_SET);
-    if (n <= 0) { std::fclose(fp); return false; }
-    buf.resize((size_t)n);
-    const size_t got = std::fread(buf.data(), 1, (size_t)n, fp);
-    std::fclose(fp);
-    return got == (size_t)n;
-}
 
 using namespace sdjsync;
 
@@ -111,49 +97,22 @@ extern "C" sd_status sd_plan_files_jpeg_sync(const char* const* paths, int n, in
     if (!paths || n < 0 || height <= 0 || width <= 0 || !bytes_out_host || !descs_out || !frames_out || !tables_out || !intervals_out ||
         !sdjsync::subseq_ok(subseq_bytes))
         return SD_ERR_INVALID;
-    if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : (threads > n ? (n > 0 ? n : 1) : threads);
-    std::atomic<int> next(0), failed(0);
-    auto work = [&]() {
-        std::vector<uint8_t> file;
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= n) break;
-            sd_status st = SD_ERR_NOTFOUND;
-            sd_jpeg_sync_frame& fr = frames_out[i];
-            std::memset(&fr, 0, sizeof(fr));
-            try {
-                if (paths[i] && read_whole_file(paths[i], file)) {
-                    uint8_t* clean = bytes_out_host + (size_t)i * byte_stride;
-                    st = sd_jpeg_sync_plan(file.data(), file.size(), subseq_bytes, &descs_out[i], &fr, tables_out + (size_t)i * SD_JPEG_ENTROPY_TABLES,
-                                           intervals_out + (size_t)i * interval_stride, interval_stride, clean, byte_stride);
-                    if (st == SD_OK && fr.eligible) {
-                        const sd_jpeg_frame_desc& d = descs_out[i];
-                        const bool swap = d.orientation >= 5;
-                        if ((swap ? d.width : d.height) != height || (swap ? d.height : d.width) != width) st = SD_ERR_INVALID;
-                        else {                                     // the kernels fetch whole aligned words: zeros behind the stream
-                            const size_t upto = ((size_t)fr.clean_bytes + 15) & ~(size_t)15;
-                            std::memset(clean + fr.clean_bytes, 0, (upto < byte_stride ? upto : byte_stride) - fr.clean_bytes);
-                        }
-                    }
-                    if (st != SD_OK) fr.eligible = 0;
-                }
-            } catch (...) {
-                st = SD_ERR_INVALID;
-                fr.eligible = 0;
+    if (n > 0) std::memset(frames_out, 0, (size_t)n * sizeof(*frames_out));      // a file that is not planned is not eligible
+    return sdfiles::for_each_file(paths, n, threads, status_out, false, [&](int i, const std::vector<uint8_t>& file) -> sd_status {
+        sd_jpeg_sync_frame& fr = frames_out[i];
+        uint8_t* clean = bytes_out_host + (size_t)i * byte_stride;
+        sd_status st = sd_jpeg_sync_plan(file.data(), file.size(), subseq_bytes, &descs_out[i], &fr, tables_out + (size_t)i * SD_JPEG_ENTROPY_TABLES,
+                                         intervals_out + (size_t)i * interval_stride, interval_stride, clean, byte_stride);
+        if (st == SD_OK && fr.eligible) {
+            if (!sdfiles::oriented_size_is(descs_out[i], height, width)) st = SD_ERR_INVALID;
+            else {                                             // the kernels fetch whole aligned words: zeros behind the stream
+                const size_t upto = ((size_t)fr.clean_bytes + 15) & ~(size_t)15;
+                std::memset(clean + fr.clean_bytes, 0, (upto < byte_stride ? upto : byte_stride) - fr.clean_bytes);
             }
-            if (status_out) status_out[i] = st;
-            if (st != SD_OK && st != SD_ERR_FORMAT) failed.fetch_add(1);
         }
-    };
-    std::vector<std::thread> pool;
-    try {
-        for (int t = 1; t < threads; ++t) pool.emplace_back(work);
-    } catch (...) {
-    }
-    work();
-    for (auto& th : pool) th.join();
-    return failed.load() ? SD_ERR_INVALID : SD_OK;
+        if (st != SD_OK) fr.eligible = 0;
+        return st;
+    });
 }
 
 extern "C" sd_status sd_jpeg_sync_decode_host(const uint8_t* bytes_host, size_t byte_stride, const sd_jpeg_frame_desc* descs, const sd_jpeg_sync_frame* frames,

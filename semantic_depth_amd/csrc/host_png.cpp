@@ -71,6 +71,8 @@ extern "C" sd_status sd_png_unfilter_bgr(const uint8_t* filtered, int height, in
 #include <thread>
 #include <vector>
 
+#include "file_pool.hpp"
+
 namespace {
 
 inline uint32_t be32(const uint8_t* p) { return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3]; }
@@ -150,19 +152,6 @@ sd_status image_decode(const uint8_t* f, size_t len, uint8_t* out, size_t out_ca
     }
 }
 
-bool read_file(const char* path, std::vector<uint8_t>& buf) {
-    FILE* fp = std::fopen(path, "rb");
-    if (!fp) return false;
-    std::fseek(fp, 0, SEEK_END);
-    const long n = std::ftell(fp);
-    std::fseek(fp, 0, SEEK_SET);
-    if (n <= 0) { std::fclose(fp); return false; }
-    buf.resize((size_t)n);
-    const size_t got = std::fread(buf.data(), 1, (size_t)n, fp);
-    std::fclose(fp);
-    return got == (size_t)n;
-}
-
 }  // namespace
 
 extern "C" sd_status sd_png_decode_bgr(const uint8_t* file_host, size_t len, uint8_t* bgr_out_host, size_t out_capacity, int* height_out,
@@ -182,37 +171,13 @@ extern "C" sd_status sd_image_decode_bgr(const uint8_t* file_host, size_t len, u
 extern "C" sd_status sd_decode_files_bgr(const char* const* paths, int n, int height, int width, uint8_t* out_host, size_t frame_stride,
                                          int threads, int* status_out) {
     if (!paths || n < 0 || height <= 0 || width <= 0 || !out_host || frame_stride < (size_t)height * width * 3) return SD_ERR_INVALID;
-    if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : (threads > n ? (n > 0 ? n : 1) : threads);
-    std::atomic<int> next(0), failed(0);
-    auto work = [&]() {
-        std::vector<uint8_t> file;
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= n) break;
-            sd_status st = SD_ERR_NOTFOUND;
-            try {
-                if (paths[i] && read_file(paths[i], file)) {
-                    int h = 0, w = 0;
-                    st = image_decode(file.data(), file.size(), nullptr, 0, &h, &w);
-                    if (st == SD_OK && (h != height || w != width)) st = SD_ERR_INVALID;     // every frame of a batch has the batch's shape
-                    if (st == SD_OK) st = image_decode(file.data(), file.size(), out_host + (size_t)i * frame_stride, frame_stride, nullptr, nullptr);
-                }
-            } catch (...) {
-                st = SD_ERR_INVALID;
-            }
-            if (status_out) status_out[i] = st;
-            if (st != SD_OK) failed.fetch_add(1);
-        }
-    };
-    std::vector<std::thread> pool;
-    try {
-        for (int t = 1; t < threads; ++t) pool.emplace_back(work);
-    } catch (...) {                                             // (thread creation refused: the calling thread and the workers that exist do the batch)
-    }
-    work();
-    for (auto& th : pool) th.join();
-    return failed.load() ? SD_ERR_INVALID : SD_OK;
+    return sdfiles::for_each_file(paths, n, threads, status_out, true, [&](int i, const std::vector<uint8_t>& file) -> sd_status {
+        int h = 0, w = 0;
+        sd_status st = image_decode(file.data(), file.size(), nullptr, 0, &h, &w);
+        if (st == SD_OK && (h != height || w != width)) st = SD_ERR_INVALID;     // every frame of a batch has the batch's shape
+        if (st == SD_OK) st = image_decode(file.data(), file.size(), out_host + (size_t)i * frame_stride, frame_stride, nullptr, nullptr);
+        return st;
+    });
 }
 
 // the same pool for the split JPEG route: file i -> quantised coefficients + descriptor (sd_jpeg_decode_coefficients); a file that is
@@ -220,45 +185,16 @@ extern "C" sd_status sd_decode_files_bgr(const char* const* paths, int n, int he
 extern "C" sd_status sd_decode_files_jpeg_coef(const char* const* paths, int n, int height, int width, int16_t* coef_out_host,
                                                size_t frame_stride_bytes, sd_jpeg_frame_desc* descs_out, int threads, int* status_out) {
     if (!paths || n < 0 || height <= 0 || width <= 0 || !coef_out_host || !descs_out || (frame_stride_bytes & 1)) return SD_ERR_INVALID;
-    if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : (threads > n ? (n > 0 ? n : 1) : threads);
-    std::atomic<int> next(0), failed(0);
-    auto work = [&]() {
-        std::vector<uint8_t> file;
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= n) break;
-            sd_status st = SD_ERR_NOTFOUND;
-            try {
-                if (paths[i] && read_file(paths[i], file)) {
-                    if (file.size() < 2 || file[0] != 0xFF || file[1] != 0xD8) st = SD_ERR_FORMAT;
-                    else {
-                        sd_jpeg_frame_desc d;
-                        st = sd_jpeg_decode_coefficients(file.data(), file.size(), nullptr, 0, &d);
-                        if (st == SD_OK) {
-                            const bool swap = d.orientation >= 5;
-                            if ((swap ? d.width : d.height) != height || (swap ? d.height : d.width) != width) st = SD_ERR_INVALID;
-                        }
-                        if (st == SD_OK)
-                            st = sd_jpeg_decode_coefficients(file.data(), file.size(), coef_out_host + (size_t)i * (frame_stride_bytes / 2),
-                                                             frame_stride_bytes, &descs_out[i]);
-                    }
-                }
-            } catch (...) {
-                st = SD_ERR_INVALID;
-            }
-            if (status_out) status_out[i] = st;
-            if (st != SD_OK && st != SD_ERR_FORMAT) failed.fetch_add(1);
-        }
-    };
-    std::vector<std::thread> pool;
-    try {
-        for (int t = 1; t < threads; ++t) pool.emplace_back(work);
-    } catch (...) {
-    }
-    work();
-    for (auto& th : pool) th.join();
-    return failed.load() ? SD_ERR_INVALID : SD_OK;
+    return sdfiles::for_each_file(paths, n, threads, status_out, false, [&](int i, const std::vector<uint8_t>& file) -> sd_status {
+        if (file.size() < 2 || file[0] != 0xFF || file[1] != 0xD8) return SD_ERR_FORMAT;
+        sd_jpeg_frame_desc d;
+        sd_status st = sd_jpeg_decode_coefficients(file.data(), file.size(), nullptr, 0, &d);
+        if (st == SD_OK && !sdfiles::oriented_size_is(d, height, width)) st = SD_ERR_INVALID;
+        if (st == SD_OK)
+            st = sd_jpeg_decode_coefficients(file.data(), file.size(), coef_out_host + (size_t)i * (frame_stride_bytes / 2), frame_stride_bytes,
+                                             &descs_out[i]);
+        return st;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -333,40 +269,14 @@ extern "C" sd_status sd_png_inflate_rows(const uint8_t* file_host, size_t len, u
 extern "C" sd_status sd_inflate_files_png(const char* const* paths, int n, int height, int width, uint8_t* rows_out_host, size_t frame_stride,
                                           sd_png_frame_desc* descs_out, int threads, int* status_out) {
     if (!paths || n < 0 || height <= 0 || width <= 0 || !rows_out_host || !descs_out) return SD_ERR_INVALID;
-    if (threads <= 0) threads = (int)std::thread::hardware_concurrency();
-    threads = threads < 1 ? 1 : (threads > n ? (n > 0 ? n : 1) : threads);
-    std::atomic<int> next(0), failed(0);
-    auto work = [&]() {
-        std::vector<uint8_t> file;
-        for (;;) {
-            const int i = next.fetch_add(1);
-            if (i >= n) break;
-            sd_status st = SD_ERR_NOTFOUND;
-            try {
-                if (paths[i] && read_file(paths[i], file)) {
-                    if (file.size() < 8 || std::memcmp(file.data(), kPngSig, 8) != 0) st = SD_ERR_FORMAT;
-                    else {
-                        sd_png_frame_desc d;
-                        st = png_inflate(file.data(), file.size(), nullptr, 0, &d);
-                        if (st == SD_OK && (d.height != height || d.width != width)) st = SD_ERR_INVALID;
-                        if (st == SD_OK) st = png_inflate(file.data(), file.size(), rows_out_host + (size_t)i * frame_stride, frame_stride, &descs_out[i]);
-                    }
-                }
-            } catch (...) {
-                st = SD_ERR_INVALID;
-            }
-            if (status_out) status_out[i] = st;
-            if (st != SD_OK && st != SD_ERR_FORMAT) failed.fetch_add(1);
-        }
-    };
-    std::vector<std::thread> pool;
-    try {
-        for (int t = 1; t < threads; ++t) pool.emplace_back(work);
-    } catch (...) {
-    }
-    work();
-    for (auto& th : pool) th.join();
-    return failed.load() ? SD_ERR_INVALID : SD_OK;
+    return sdfiles::for_each_file(paths, n, threads, status_out, false, [&](int i, const std::vector<uint8_t>& file) -> sd_status {
+        if (file.size() < 8 || std::memcmp(file.data(), kPngSig, 8) != 0) return SD_ERR_FORMAT;
+        sd_png_frame_desc d;
+        sd_status st = png_inflate(file.data(), file.size(), nullptr, 0, &d);
+        if (st == SD_OK && (d.height != height || d.width != width)) st = SD_ERR_INVALID;
+        if (st == SD_OK) st = png_inflate(file.data(), file.size(), rows_out_host + (size_t)i * frame_stride, frame_stride, &descs_out[i]);
+        return st;
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -10,24 +10,21 @@ feeder that keeps the GPU supplied.
 
 PNG decode stays on the host by default: DEFLATE and the PNG predictors are serial byte recurrences; a frame costs a few
 milliseconds of one core (scripts/feed_rate.py measures decode, pinned H2D and resize rates against the benchmarked
-frames/s; DESIGN.md quotes them).  ``png="device"`` keeps only the chunk walk and the inflate there (sd_inflate_files_png) and runs
-the predictors -- a row per lane, the rows of a frame one pixel behind each other --, the channel shuffle and the palette lookup on
-the GPU (Engine.png_reconstruct), byte for byte the host route's frames.  JPEG frames (the reference's own example frame is one) have two routes: ``jpeg="host"``, the
-default, decodes them completely on the host threads as well; ``jpeg="device"`` keeps only the serial part there -- the Huffman
-decoder, to quantised coefficients (sd_decode_files_jpeg_coef) -- and runs the inverse DCT, the chroma upsampling, the colour
-conversion and the EXIF orientation on the GPU (Engine.jpeg_reconstruct), byte for byte the host route's frames;
-``jpeg="device_entropy"`` moves the Huffman decoder to the GPU as well for files with restart intervals (the project's own encoder,
-MJPEG cameras, Pillow's restart_marker_rows / restart_marker_blocks): the host only finds the markers (sd_plan_files_jpeg_entropy, a
-byte scan), Engine.jpeg_entropy_decode decodes one restart interval per lane, and every other file falls back to the host decoder.
-``jpeg="device_sync"`` reaches the files without restart intervals too: the host writes the scan without stuffing and markers
-(sd_plan_files_jpeg_sync) and Engine.jpeg_sync_decode decodes it in short pieces that find the decoder's state by themselves.
+frames/s; DESIGN.md quotes them), and JPEG frames (the reference's own example frame is one) are decoded completely on the host
+threads as well.  The opt-in routes keep only the serial part of a decode on the host and finish the frames on the GPU, byte for byte
+the host route's: ``png="device"`` (the PNG predictors), ``jpeg="device"`` (everything behind the Huffman decoder),
+``jpeg="device_entropy"`` (the Huffman decoder too, for files with restart intervals) and ``jpeg="device_sync"`` (for files without
+them as well).  Each is a stage of the feeder below, described there.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 import struct
 import zlib
 from concurrent.futures import ThreadPoolExecutor
+from dataclasses import dataclass, field
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -96,7 +93,6 @@ def imread(path: str) -> np.ndarray:
 
 def _avi_chunks(f, start: int, end: int):
     """(fourcc, payload offset, payload size) of the chunks in [start, end) of an open RIFF file"""
-    import struct
     pos = start
     while pos + 8 <= end:
         f.seek(pos)
@@ -110,7 +106,6 @@ def _avi_chunks(f, start: int, end: int):
 
 def _avi_layout(f):
     """(avih fields, strh fields, offset of the 'movi' fourcc, (offset, size) of the idx1 payload or None) of an open AVI file"""
-    import struct
     f.seek(0)
     head = f.read(12)
     if len(head) < 12 or head[:4] != b"RIFF" or head[8:] != b"AVI ":
@@ -150,7 +145,6 @@ def avi_info(path: str) -> dict:
 def avi_frames(path: str):
     """the frames of a Motion-JPEG AVI (outputs.MjpegAviWriter's files) as byte strings -- each a complete JPEG file, decode_jpeg reads it --
     in index order, read through idx1 (offsets relative to the 'movi' fourcc)"""
-    import struct
     with open(path, "rb") as f:
         _, _, movi, idx1 = _avi_layout(f)
         if idx1 is None:
@@ -191,7 +185,6 @@ def _local_ranks() -> int:
     (SLURM_TASKS_PER_NODE is always set by srun, SLURM_NTASKS_PER_NODE only with --ntasks-per-node), else WORLD_SIZE -- the conservative single-node
     assumption for a job started by hand with RANK / WORLD_SIZE: on several nodes it UNDER-subscribes the decode threads (affinity / WORLD_SIZE each),
     never over-subscribes them --, else 1"""
-    import os
     for k in ("LOCAL_WORLD_SIZE", "OMPI_COMM_WORLD_LOCAL_SIZE", "MPI_LOCALNRANKS", "SLURM_NTASKS_PER_NODE", "SLURM_TASKS_PER_NODE", "WORLD_SIZE"):
         v = os.environ.get(k, "")
         try:
@@ -207,7 +200,6 @@ def default_decode_workers() -> int:
     """decode threads of ONE rank: the CPUs this process may run on (its affinity mask, capped by the cgroup CPU quota -- os.cpu_count()
     reports the host's 256 whatever the container may use) divided by the ranks of the node (_local_ranks), at least 1, at most 128.
     Eight ranks on a 256-CPU node get 32 threads each instead of 8 x 128."""
-    import os
     try:
         n = len(os.sched_getaffinity(0))
     except (AttributeError, OSError):
@@ -218,47 +210,356 @@ def default_decode_workers() -> int:
     return max(1, min(n // _local_ranks(), 128))
 
 
+def _runs(values):
+    """(position of the first, length) of every run of consecutive integers in the ascending list ``values``: a run of consecutive
+    frames is a contiguous slice of the batch tensor, so a kernel writes straight into it"""
+    p0 = 0
+    while p0 < len(values):
+        p1 = p0 + 1
+        while p1 < len(values) and values[p1] == values[p1 - 1] + 1:
+            p1 += 1
+        yield p0, p1 - p0
+        p0 = p1
+
+
+def _unreadable(bad, size) -> ValueError:
+    """what every route raises for the (path, status) pairs ``bad`` of a batch"""
+    h, w = size
+    return ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
+
+
+@dataclass
+class StagedBatch:
+    """what the host halves of a batch hand to the device halves: ``n`` frames from global index ``lo`` of ``size`` (h, w) after the
+    orientation; ``kind[i]`` names the stage that took frame i; ``pinned[name]`` is that stage's pinned staging in use (the asynchronous
+    uploads read it, so it is not written again before the event of this batch has passed) and ``payload[name]`` what its host half made
+    for its device half"""
+    n: int
+    lo: int
+    size: tuple
+    kind: list
+    pinned: dict = field(default_factory=dict)
+    payload: dict = field(default_factory=dict)
+
+
+class _Stage:
+    """one way from files to frames.  ``host(slot, batch, idx)`` runs on the worker thread: it reads the files ``idx`` (ascending batch
+    indices) into the pinned staging of ``slot``, marks the frames it takes in ``batch.kind``, raises for a file nobody can read and
+    returns the indices that are the next stage's.  ``device(batch, dev)`` runs on the consumer's thread: the uploads and launches of
+    its frames on the current stream into the u8 [n,h,w,3] tensor ``dev`` (it makes the tensor when it is the first stage) -> dev.
+    ``settle(batch)`` runs after every device half of the batch: the place for a read-back that need not hold up the other stages.
+    Row j of a stage's staging and device tensors belongs to the file idx[j]."""
+    name = None
+
+    def __init__(self, feeder):
+        self.f = feeder
+        self.staging = [None, None]           # pinned, per slot: this stage's own, released by its close()
+
+    def close(self):
+        self.staging = [None, None]
+
+    def settle(self, batch):
+        pass
+
+    def take(self, batch, idx):
+        for i in idx:
+            batch.kind[i] = self.name
+
+    def rows(self, batch):
+        """the rows j of this stage's frames"""
+        return [j for j, i in enumerate(batch.payload[self.name].idx) if batch.kind[i] == self.name]
+
+    def tensor(self, batch, dev):
+        h, w = batch.size
+        return dev if dev is not None else self.f._torch.empty((batch.n, h, w, 3), dtype=self.f._torch.uint8, device=self.f.device)
+
+    def files(self, batch, idx, call, refuse=True):
+        """one native batch call ``call(paths, k, status)`` on the files idx -> the per-file statuses; a file that is not the call's
+        format (SD_ERR_FORMAT) is left to the next stage, any other failure raises unless ``refuse`` is off"""
+        paths = [self.f.paths[batch.lo + i] for i in idx]
+        arr = (C.c_char_p * len(idx))(*[os.fsencode(p) for p in paths])
+        status = (C.c_int * len(idx))()
+        if call(arr, len(idx), status) != L.SD_OK and refuse:
+            raise _unreadable([(p, s) for p, s in zip(paths, status) if s not in (L.SD_OK, L.SD_ERR_FORMAT)], batch.size)
+        return status
+
+
+class _BgrStage(_Stage):
+    """the last stage of every route and the only one of the default route: sd_decode_files_bgr (C++ threads, no interpreter lock)
+    reads and decodes PNG and JPEG files completely, straight into pinned u8 frames; the device half is their asynchronous upload"""
+    name = "bgr"
+
+    def host(self, slot, batch, idx):
+        f, torch = self.f, self.f._torch
+        h, w = batch.size
+        buf = self.staging[slot]
+        if buf is None or tuple(buf.shape[1:3]) != (h, w):
+            buf = self.staging[slot] = torch.empty((f.batch, h, w, 3), dtype=torch.uint8, pin_memory=f.device.type == "cuda")
+        self.files(batch, idx, lambda arr, k, status: f._lib.sd_decode_files_bgr(arr, k, h, w, C.c_void_p(buf.data_ptr()), h * w * 3, f.workers, status))
+        self.take(batch, idx)
+        batch.pinned[self.name], batch.payload[self.name] = buf, SimpleNamespace(idx=idx)
+        return []
+
+    def device(self, batch, dev):
+        buf, idx = batch.pinned[self.name], batch.payload[self.name].idx
+        if dev is None:                                   # the whole batch is this stage's: one copy
+            return buf[:batch.n].to(self.f.device, non_blocking=True)
+        for j, i in enumerate(idx):
+            dev[i].copy_(buf[j], non_blocking=True)
+        return dev
+
+
+class _JpegDeviceStage(_Stage):
+    """what the stages that reconstruct JPEG frames on the GPU share: the host coefficient decoder and Engine.jpeg_reconstruct (inverse
+    DCT, chroma upsampling, colour conversion, EXIF orientation), byte for byte the host decoder's frames"""
+
+    def host_coef(self, batch, idx, buf=None):
+        """the host Huffman decoder (sd_decode_files_jpeg_coef) on the files idx -> (pinned int16 rows -- ``buf`` where it fits --,
+        descriptors, statuses)"""
+        f, torch = self.f, self.f._torch
+        h, w = batch.size
+        stride = f.coef_stride_bytes(h, w)                # the batch's frame size fixes the staging stride
+        if buf is None or buf.shape[1] != stride // 2 or buf.shape[0] < len(idx):
+            buf = torch.empty((max(f.batch, len(idx)), stride // 2), dtype=torch.int16, pin_memory=True)
+        descs = (L.sd_jpeg_frame_desc * len(idx))()
+        status = self.files(batch, idx, lambda arr, k, status: f._lib.sd_decode_files_jpeg_coef(arr, k, h, w, C.c_void_p(buf.data_ptr()), stride, descs,
+                                                                                                   f.workers, status))
+        return buf, descs, status
+
+    @staticmethod
+    def replace_coef(cdev, descs, rows, buf, src):
+        """a host decode of the frames ``rows`` takes their place: row p of the pinned ``buf`` with descriptor src[p] -> row rows[p] of
+        ``cdev`` and of ``descs``, asynchronously"""
+        for p, j in enumerate(rows):
+            used = src[p].coef_elems()
+            cdev[j, :used].copy_(buf[p, :used], non_blocking=True)
+            descs[j] = src[p]
+
+    def reconstruct(self, batch, dev, cdev, descs):
+        idx, rows = batch.payload[self.name].idx, self.rows(batch)
+        for p0, m in _runs([idx[j] for j in rows]):
+            j0, i0 = rows[p0], idx[rows[p0]]
+            run = (L.sd_jpeg_frame_desc * m)(*[descs[j] for j in range(j0, j0 + m)])
+            self.f.engine.jpeg_reconstruct(cdev[j0:j0 + m], run, out=dev[i0:i0 + m])
+
+
+class _CoefStage(_JpegDeviceStage):
+    """``jpeg="device"``: the JPEG files are only entropy-decoded on the host, into a pinned int16 staging buffer; each frame's
+    coefficients are uploaded asynchronously and Engine.jpeg_reconstruct writes the frames into the batch tensor behind the upload"""
+    name = "coef"
+
+    def host(self, slot, batch, idx):
+        buf, descs, status = self.host_coef(batch, idx, self.staging[slot])
+        self.staging[slot] = buf
+        self.take(batch, [i for i, s in zip(idx, status) if s == L.SD_OK])
+        batch.pinned[self.name], batch.payload[self.name] = buf, SimpleNamespace(idx=idx, descs=descs)
+        return [i for i, s in zip(idx, status) if s == L.SD_ERR_FORMAT]
+
+    def device(self, batch, dev):
+        torch = self.f._torch
+        buf, p, rows = batch.pinned[self.name], batch.payload[self.name], self.rows(batch)
+        dev = self.tensor(batch, dev)
+        if rows:
+            cdev = torch.empty((len(p.idx), buf.shape[1]), dtype=torch.int16, device=self.f.device)
+            for j in rows:                                # what each frame really has (a 4:2:0 frame has half of a 4:4:4 frame's)
+                used = p.descs[j].coef_elems()
+                cdev[j, :used].copy_(buf[j, :used], non_blocking=True)
+            self.reconstruct(batch, dev, cdev, p.descs)
+        return dev
+
+
+class _EntropyStage(_JpegDeviceStage):
+    """``jpeg="device_entropy"``: the worker thread only PLANS the JPEG files (sd_plan_files_jpeg_entropy: header parse and a byte scan
+    for the restart markers) and copies their scan bytes into pinned staging.  The scan bytes go up instead of the coefficients -- at
+    most a few bits per coefficient instead of 16 -- and Engine.jpeg_entropy_decode fills the coefficient tensor on the GPU, one restart
+    interval per lane; Engine.jpeg_reconstruct then runs as on the "device" route.  A file is eligible when it is a sequential 8-bit
+    file with ONE interleaved scan, DRI > 0, and nothing in its scan data but stuffed bytes, the expected RSTk markers and the closing
+    EOI (include/semdepth.h states the rule).  Every other JPEG (progressive, multi-scan, no restart intervals, truncated, stray markers,
+    too large for the staging) and every frame whose stream the kernel flags is decoded by the host decoder and uploaded into its slot;
+    a frame that decoder refuses as well raises what the "device" route raises.  ``FrameFeeder.entropy_fallback`` lists those frames.
+    It takes the Huffman decoder off the host threads; it is not the faster feeder yet: with one interval per MCU row it measured
+    slower than ``jpeg="device"`` at 512x1024, 1024x2048 and 3024x4032."""
+    name, fell = "entropy", "entropy_fallback"
+    frame_t, interval_t = L.sd_jpeg_entropy_frame, L.sd_jpeg_interval
+
+    def plan(self, arr, k, size, pin, plan, status):
+        return self.f._lib.sd_plan_files_jpeg_entropy(arr, k, *size, C.c_void_p(pin.bytes.data_ptr()), pin.bytes.shape[1], plan.descs, plan.frames,
+                                                      plan.tables, plan.intervals, plan.ivs, self.f.workers, status)
+
+    def decode(self, sdev, plan, cdev, status):
+        self.f.engine.jpeg_entropy_decode(sdev, plan.descs, plan.frames, plan.tables, plan.intervals, plan.ivs, out=cdev, status=status)
+
+    def host(self, slot, batch, idx):
+        f, torch = self.f, self.f._torch
+        h, w = batch.size
+        k = len(idx)
+        sizes = []
+        for i in idx:
+            try:
+                sizes.append(os.path.getsize(f.paths[batch.lo + i]))
+            except OSError:
+                sizes.append(0)
+        byte_stride = max(16, -(-max(sizes) // 16) * 16)            # the scan bytes are fewer than the file's
+        ivs = max(64, min(-(-h // 8) * -(-w // 8), 16384))          # ranges per frame: a file with more falls back to the host decoder
+        T = L.SD_JPEG_ENTROPY_TABLES
+        pin = self.staging[slot]
+        if pin is None or pin.bytes.shape[1] < byte_stride or pin.ivs != ivs:
+            def pinned(nbytes):
+                return torch.empty((nbytes,), dtype=torch.uint8, pin_memory=True)
+            pin = self.staging[slot] = SimpleNamespace(
+                bytes=torch.empty((f.batch, byte_stride), dtype=torch.uint8, pin_memory=True), ivs=ivs, coef=None, flagged_coef=None,
+                descs=pinned(f.batch * C.sizeof(L.sd_jpeg_frame_desc)), frames=pinned(f.batch * C.sizeof(self.frame_t)),
+                tables=pinned(f.batch * T * C.sizeof(L.sd_jpeg_huff_table)), intervals=pinned(f.batch * ivs * C.sizeof(self.interval_t)),
+                status=torch.empty((f.batch,), dtype=torch.int32, pin_memory=True))
+        # the records live in the pinned buffers: the C call uploads them with asynchronous copies, and a slot is not planned into again
+        # before the event of its last batch has passed
+        plan = SimpleNamespace(idx=idx, ivs=ivs, descs=(L.sd_jpeg_frame_desc * k).from_address(pin.descs.data_ptr()),
+                               frames=(self.frame_t * k).from_address(pin.frames.data_ptr()),
+                               tables=(L.sd_jpeg_huff_table * (k * T)).from_address(pin.tables.data_ptr()),
+                               intervals=(self.interval_t * (k * ivs)).from_address(pin.intervals.data_ptr()))
+        status = self.files(batch, idx, lambda arr, k, status: self.plan(arr, k, batch.size, pin, plan, status), refuse=False)
+        plan.eligible = [j for j in range(k) if status[j] == L.SD_OK and plan.frames[j].eligible]
+        # every other JPEG -- not eligible, unreadable, too large for the staging -- is the host decoder's: it decodes it or raises what
+        # the "device" route raises for the batch
+        plan.fallback = [j for j in range(k) if status[j] != L.SD_ERR_FORMAT and j not in plan.eligible]
+        if plan.fallback:
+            pin.coef, plan.fdescs, _ = self.host_coef(batch, [idx[j] for j in plan.fallback], pin.coef)
+        self.take(batch, [idx[j] for j in range(k) if status[j] != L.SD_ERR_FORMAT])
+        batch.pinned[self.name], batch.payload[self.name] = pin, plan
+        return [idx[j] for j in range(k) if status[j] == L.SD_ERR_FORMAT]
+
+    def device(self, batch, dev):
+        """the scan bytes' upload, the entropy kernels, the uploads of the host-decoded frames, the status words' way back on the
+        feeder's copy stream, then the reconstruction of the "device" route"""
+        f, torch = self.f, self.f._torch
+        pin, plan = batch.pinned[self.name], batch.payload[self.name]
+        dev = self.tensor(batch, dev)
+        k = len(plan.idx)
+        if not self.rows(batch):
+            return dev
+        fell = []
+        descs = (L.sd_jpeg_frame_desc * k)()
+        cdev = torch.empty((k, f.coef_stride_bytes(*batch.size) // 2), dtype=torch.int16, device=f.device)
+        if plan.eligible:
+            # whole rows of the staging buffer (its stride is the largest file of the batches so far): one contiguous pinned copy
+            sdev = torch.empty((k, pin.bytes.shape[1]), dtype=torch.uint8, device=f.device)
+            sdev.copy_(pin.bytes[:k], non_blocking=True)
+            status = torch.empty((k,), dtype=torch.int32, device=f.device)
+            self.decode(sdev, plan, cdev, status)
+            for j in plan.eligible:
+                descs[j] = plan.descs[j]
+            arrived = f._read_back(status, pin.status[:k])
+        if plan.fallback:
+            self.replace_coef(cdev, descs, plan.fallback, pin.coef, plan.fdescs)
+            fell += [(j, "ineligible") for j in plan.fallback]
+        if plan.eligible:
+            arrived()
+            flagged = [j for j in plan.eligible if int(pin.status[j]) != 0]
+            # On the entropy route this is defensive only: the tests know no stream the host decoder accepts and the kernel flags, so in
+            # practice the host decoder raises here what the "device" route raises.  Should it accept, its coefficients replace the slot's
+            # (from a pinned buffer that asynchronous copies read: kept until this staging slot is planned into again).
+            if flagged:
+                pin.flagged_coef, fdescs, _ = self.host_coef(batch, [plan.idx[j] for j in flagged])
+                self.replace_coef(cdev, descs, flagged, pin.flagged_coef, fdescs)
+                fell += [(j, "flagged") for j in flagged]
+        f._fell_back(self.fell, [(batch.lo + plan.idx[j], why) for j, why in fell])
+        self.reconstruct(batch, dev, cdev, descs)
+        return dev
+
+
+class _SyncStage(_EntropyStage):
+    """``jpeg="device_sync"``: the entropy route for files WITHOUT restart intervals as well -- what Pillow's default save, cv2.imwrite
+    and most cameras write.  The worker thread plans the files (sd_plan_files_jpeg_sync) and writes their CLEAN streams (stuffing
+    resolved, RST markers dropped) into pinned staging; Engine.jpeg_sync_decode cuts every interval -- a scan without DRI is one -- into
+    pieces of ``sync_piece`` bytes that find the decoder's state by themselves, decodes a piece per lane and verifies the chain of
+    states, so a status word of 0 means the sequential decode.  Ineligible files (progressive, multi-scan, stray markers) and frames the
+    kernels flag (refused streams, pieces that did not synchronise, bits that ran out: real cases, the host decoder's to decide) go
+    through the host decoder; ``FrameFeeder.sync_fallback`` lists them."""
+    name, fell = "sync", "sync_fallback"
+    frame_t, interval_t = L.sd_jpeg_sync_frame, L.sd_jpeg_sync_interval
+
+    def plan(self, arr, k, size, pin, plan, status):
+        return self.f._lib.sd_plan_files_jpeg_sync(arr, k, *size, self.f.sync_piece, C.c_void_p(pin.bytes.data_ptr()), pin.bytes.shape[1], plan.descs,
+                                                   plan.frames, plan.tables, plan.intervals, plan.ivs, self.f.workers, status)
+
+    def decode(self, sdev, plan, cdev, status):
+        self.f.engine.jpeg_sync_decode(sdev, plan.descs, plan.frames, plan.tables, plan.intervals, plan.ivs, self.f.sync_piece, out=cdev, status=status)
+
+
+class _PngRowsStage(_Stage):
+    """``png="device"``: the worker thread only walks the chunks of the PNG files and inflates their IDAT streams into pinned staging
+    (sd_inflate_files_png).  The filtered scanlines go up as they are -- about the byte count of the BGR frame -- and
+    Engine.png_reconstruct runs the filter recurrence, the channel map and the palette lookup on the GPU, a run of consecutive PNG
+    frames per launch, straight into the batch tensor.  A file the inflate refuses, and a palette frame the kernel flags for an index
+    beyond its palette, raise what the host route raises.  The status words are read back only for a batch that holds a palette frame,
+    on the feeder's copy stream, after the other stages' launches ("PNG reconstruction on the device")."""
+    name = "png_rows"
+
+    def host(self, slot, batch, idx):
+        f, torch = self.f, self.f._torch
+        h, w = batch.size
+        stride = f.png_rows_stride(h, w)
+        pin = self.staging[slot]
+        if pin is None or pin.rows.shape[1] != stride:
+            pin = self.staging[slot] = SimpleNamespace(
+                rows=torch.empty((f.batch, stride), dtype=torch.uint8, pin_memory=True),
+                descs=torch.empty((f.batch * C.sizeof(L.sd_png_frame_desc),), dtype=torch.uint8, pin_memory=True),
+                status=torch.empty((f.batch,), dtype=torch.int32, pin_memory=True))
+        # the descriptors live in the pinned buffer: the C call uploads them with an asynchronous copy, and a slot is not inflated into
+        # again before the event of its last batch has passed
+        descs = (L.sd_png_frame_desc * len(idx)).from_address(pin.descs.data_ptr())
+        status = self.files(batch, idx, lambda arr, k, status: f._lib.sd_inflate_files_png(arr, k, h, w, C.c_void_p(pin.rows.data_ptr()), stride, descs,
+                                                                                             f.workers, status))
+        self.take(batch, [i for i, s in zip(idx, status) if s == L.SD_OK])
+        batch.pinned[self.name], batch.payload[self.name] = pin, SimpleNamespace(idx=idx, descs=descs, arrived=None, palette=[])
+        return [i for i, s in zip(idx, status) if s == L.SD_ERR_FORMAT]
+
+    def device(self, batch, dev):
+        f, torch = self.f, self.f._torch
+        pin, p, rows = batch.pinned[self.name], batch.payload[self.name], self.rows(batch)
+        dev = self.tensor(batch, dev)
+        if not rows:
+            return dev
+        k = len(p.idx)
+        rdev = torch.empty((k, pin.rows.shape[1]), dtype=torch.uint8, device=f.device)
+        status = torch.zeros((k,), dtype=torch.int32, device=f.device)
+        for j in rows:                                              # the rows each frame really has
+            used = -(-p.descs[j].rows_bytes() // 16) * 16
+            rdev[j, :used].copy_(pin.rows[j, :used], non_blocking=True)
+        for p0, m in _runs([p.idx[j] for j in rows]):
+            j0, i0 = rows[p0], p.idx[rows[p0]]
+            run = (L.sd_png_frame_desc * m).from_address(pin.descs.data_ptr() + j0 * C.sizeof(L.sd_png_frame_desc))
+            f.engine.png_reconstruct(rdev[j0:j0 + m], run, out=dev[i0:i0 + m], status=status[j0:j0 + m])
+        p.palette = [j for j in rows if p.descs[j].color_type == 3]
+        if p.palette:                                               # only an index beyond the palette can be flagged
+            p.arrived = f._read_back(status, pin.status[:k])
+        return dev
+
+    def settle(self, batch):
+        pin, p = batch.pinned[self.name], batch.payload[self.name]
+        if p.arrived:
+            p.arrived()
+            bad = [(self.f.paths[batch.lo + p.idx[j]], L.SD_ERR_INVALID) for j in p.palette if int(pin.status[j]) != 0]
+            if bad:                                                 # what the host route raises for a file with an index beyond its palette
+                raise _unreadable(bad, batch.size)
+
+
 class FrameFeeder:
-    """iterate over (frames u8 [n,h,w,3] on ``device``, first global index) for the sorted ``paths``: every batch is read and decoded
-    by ONE native call (sd_decode_files_bgr: ``workers`` C++ threads, no interpreter lock) straight into a pinned staging buffer,
-    uploaded asynchronously, one batch ahead of the consumer (two staging buffers).
-    ``jpeg="device"`` (needs ``engine``, an engine.Engine whose handle launches the kernels, and a GPU ``device``): the JPEG files of a
-    batch are only entropy-decoded on the host (sd_decode_files_jpeg_coef into a pinned int16 staging buffer, one batch ahead as well);
-    each frame's coefficients are uploaded asynchronously and Engine.jpeg_reconstruct writes the frames into the same u8 [n,h,w,3]
-    device tensor behind the upload, on the current stream.  PNG files of such a batch go the BGR way into that tensor.  The frames,
-    indices and batch boundaries are those of ``jpeg="host"``.
-    ``jpeg="device_entropy"`` (same needs): the worker thread only PLANS the JPEG files of a batch (sd_plan_files_jpeg_entropy: header
-    parse and a byte scan for the restart markers) and copies their scan bytes into pinned staging, one batch ahead as well.  The scan
-    bytes go up instead of the coefficients -- also a much smaller upload, at most a few bits per coefficient instead of 16 -- and
-    Engine.jpeg_entropy_decode fills the coefficient tensor on the GPU, one restart interval per lane; Engine.jpeg_reconstruct then runs
-    as on the "device" route.  A file is eligible when it is a sequential 8-bit file with ONE interleaved scan, DRI > 0, and nothing in
-    its scan data but stuffed bytes, the expected RSTk markers and the closing EOI (include/semdepth.h states the rule).  Every other
-    JPEG (progressive, multi-scan, no restart intervals, truncated, stray markers) and every frame whose stream the kernel flags is
-    decoded by the host decoder (sd_decode_files_jpeg_coef) and uploaded into its slot; a frame that decoder refuses as well raises what
-    the "device" route raises.  ``entropy_fallback`` lists (global frame index, "ineligible" | "flagged") of the frames that took the
-    host decoder during the last iteration.  The kernel's per-frame status words come back through pinned memory on a copy stream of
-    the feeder's own: the feeder waits on that stream, never on the compute stream.  Frames, indices, batch boundaries and the PNG
-    handling are those of the other routes.  It takes the Huffman decoder off the host threads; it is not the faster feeder yet: with one
-    interval per MCU row it measured slower than ``jpeg="device"`` at 512x1024, 1024x2048 and 3024x4032.
-    ``jpeg="device_sync"`` (same needs): the entropy route for files WITHOUT restart intervals as well -- what Pillow's default save,
-    cv2.imwrite and most cameras write.  The worker thread plans the files (sd_plan_files_jpeg_sync) and writes their CLEAN streams
-    (stuffing resolved, RST markers dropped) into pinned staging; Engine.jpeg_sync_decode cuts every interval -- a scan without DRI is
-    one -- into pieces of ``sync_piece`` bytes that find the decoder's state by themselves, decodes a piece per lane and verifies the
-    chain of states, so a status word of 0 means the sequential decode.  Ineligible files (progressive, multi-scan, stray markers) and
-    frames the kernels flag (refused streams, pieces that did not synchronise, bits that ran out) go through the host decoder;
-    ``sync_fallback`` lists them as ``entropy_fallback`` does.  Frames, indices and batch boundaries are those of the other routes.
-    ``png="device"`` (same needs; combines with every ``jpeg=`` choice): the worker thread only walks the chunks of the batch's PNG
-    files and inflates their IDAT streams into pinned staging (sd_inflate_files_png), one batch ahead as well.  The filtered scanlines
-    go up as they are -- about the byte count of the BGR frame -- and Engine.png_reconstruct runs the filter recurrence, the channel
-    map and the palette lookup on the GPU, a run of consecutive PNG frames per launch, straight into the batch tensor.  The files that
-    are not PNGs go down the ``jpeg=`` route.  Frames, indices and batch boundaries are those of ``png="host"``; a file the inflate
-    refuses, and a palette frame the kernel flags for an index beyond its palette, raise what the host route raises.  The status words
-    are read back only for a batch that holds a palette frame, on the same copy stream ("PNG reconstruction on the
-    device")."""
+    """iterate over (frames u8 [n,h,w,3] on ``device``, first global index) for the sorted ``paths``, ``batch`` files at a time, one
+    batch ahead of the consumer (two staging slots).  Every route yields the frames of ``frame_io.imread``, with the same indices and
+    batch boundaries, and raises the same ValueError for a batch with a file that cannot be read at the batch's size (that of its first
+    file).  ``png="device"`` and ``jpeg="device" | "device_entropy" | "device_sync"`` move work from the ``workers`` host threads to the
+    GPU; they need ``engine`` (an engine.Engine whose handle launches the kernels) and a GPU ``device``.
+
+    A route is a chain of stages (``stages``): the PNG-rows stage when ``png="device"``, the chosen JPEG stage, the host BGR stage.
+    Each has a host half (worker thread: files -> pinned staging) and a device half (the consumer's thread: uploads and launches on
+    the current stream); a stage handles the files it is given and names the rest, which go to the next stage.  The stages' docstrings
+    describe the routes.  ``entropy_fallback`` / ``sync_fallback`` list (global frame index, "ineligible" | "flagged") of the frames that
+    took the host decoder on those routes during the last iteration.  Status words come back through pinned memory on a copy stream of
+    the feeder's own: the feeder waits on that stream, never on the compute stream."""
 
     def __init__(self, paths, batch: int, device="cuda", workers: int = 0, jpeg: str = "host", engine=None, png: str = "host",
                  sync_piece: int = SYNC_PIECE_BYTES):
-        import os
         import torch
         self.paths, self.batch, self.device = list(paths), batch, torch.device(device)
         if png not in ("host", "device"):
@@ -267,62 +568,32 @@ class FrameFeeder:
             raise ValueError(f"FrameFeeder: png={png!r} reconstructs the frames on the GPU; device='cpu' has none")
         if png != "host" and engine is None:
             raise ValueError(f"FrameFeeder: png={png!r} needs engine= (the handle that launches the reconstruction kernels)")
-        self.png = png
-        self._pinned_rows = [None, None]
-        self._others = [None, None]           # png="device": per staging slot, the feeder that takes the batch's files that are not PNGs
-        if jpeg not in ("host", "device", "device_entropy", "device_sync"):
+        jpeg_stages = {"host": (), "device": (_CoefStage,), "device_entropy": (_EntropyStage,), "device_sync": (_SyncStage,)}
+        if jpeg not in jpeg_stages:
             raise ValueError(f"FrameFeeder: jpeg must be 'host', 'device', 'device_entropy' or 'device_sync', not {jpeg!r}")
         if sync_piece not in (32, 64, 128, 256, 512, 1024):
             raise ValueError(f"FrameFeeder: sync_piece must be a power of two from 32 to 1024, not {sync_piece!r}")
-        self.sync_piece = sync_piece
-        self.sync_fallback = []
         if jpeg != "host" and self.device.type != "cuda":
             raise ValueError(f"FrameFeeder: jpeg={jpeg!r} reconstructs the frames on the GPU; device='cpu' has none")
         if jpeg != "host" and engine is None:
             raise ValueError(f"FrameFeeder: jpeg={jpeg!r} needs engine= (the handle that launches the reconstruction kernels)")
-        self.jpeg, self.engine = jpeg, engine
-        self.entropy_fallback = []
-        self._pinned_ent = [None, None]
-        self._copy_stream = None
-        self._pinned_coef = [None, None]
-        self._pinned_png = [None, None]
+        self.png, self.jpeg, self.engine, self.sync_piece = png, jpeg, engine, sync_piece
+        self.entropy_fallback, self.sync_fallback = [], []
         self.workers = workers if workers > 0 else default_decode_workers()
         self._torch = torch
-        self._pinned = [None, None]
         self._lib = L.load()
+        self._copy_stream = None
+        self.stages = [stage(self) for stage in ((_PngRowsStage,) if png == "device" else ()) + jpeg_stages[jpeg] + (_BgrStage,)]
 
     def close(self):
-        self._pinned = [None, None]
-        self._pinned_coef = [None, None]
-        self._pinned_png = [None, None]
-        self._pinned_ent = [None, None]
-        self._pinned_rows = [None, None]
-        for f in self._others:
-            if f is not None:
-                f.close()
-        self._others = [None, None]
+        for stage in self.stages:
+            stage.close()
 
     def __enter__(self):
         return self
 
     def __exit__(self, *exc):
         self.close()
-
-    def _decode_into(self, slot: int, lo: int, hi: int):
-        torch = self._torch
-        with open(self.paths[lo], "rb") as f:
-            h, w = image_size(f.read())
-        buf = self._pinned[slot]
-        if buf is None or tuple(buf.shape[1:3]) != (h, w) or buf.shape[0] < hi - lo:
-            buf = self._pinned[slot] = torch.empty((self.batch, h, w, 3), dtype=torch.uint8, pin_memory=self.device.type == "cuda")
-        n = hi - lo
-        arr = (C.c_char_p * n)(*[os_fsencode(p) for p in self.paths[lo:hi]])
-        status = (C.c_int * n)()
-        st = self._lib.sd_decode_files_bgr(arr, n, h, w, C.c_void_p(buf.data_ptr()), h * w * 3, self.workers, status)
-        if st != L.SD_OK:
-            bad = [(self.paths[lo + i], status[i]) for i in range(n) if status[i] != L.SD_OK]
-            raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
-        return buf[:n]
 
     @staticmethod
     def _header_size(path) -> tuple:
@@ -342,318 +613,51 @@ class FrameFeeder:
         size; the bound is symmetric in h and w, so it covers the transposing orientations), rounded up to the 16 bytes the kernels load"""
         return 3 * (-(-h // 16) * 16) * (-(-w // 16) * 16) * 2
 
-    def _decode_coef_into(self, slot: int, lo: int, hi: int):
-        """device route, host part of one batch: -> (pinned int16 [n, stride / 2] coefficients, descriptors, [(i, pinned BGR frame)]
-        of the files that are not JPEGs, (h, w))"""
-        torch = self._torch
-        h, w = self._header_size(self.paths[lo])          # the header pass: the batch's frame size fixes the staging stride
-        stride = self.coef_stride_bytes(h, w)
-        n = hi - lo
-        buf = self._pinned_coef[slot]
-        if buf is None or buf.shape[1] != stride // 2 or buf.shape[0] < n:
-            buf = self._pinned_coef[slot] = torch.empty((self.batch, stride // 2), dtype=torch.int16, pin_memory=True)
-        arr = (C.c_char_p * n)(*[os_fsencode(p) for p in self.paths[lo:hi]])
-        status = (C.c_int * n)()
-        descs = (L.sd_jpeg_frame_desc * n)()
-        st = self._lib.sd_decode_files_jpeg_coef(arr, n, h, w, C.c_void_p(buf.data_ptr()), stride, descs, self.workers, status)
-        if st != L.SD_OK:
-            bad = [(self.paths[lo + i], status[i]) for i in range(n) if status[i] not in (L.SD_OK, L.SD_ERR_FORMAT)]
-            raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
-        others = [i for i in range(n) if status[i] == L.SD_ERR_FORMAT]
-        png = []
-        if others:                                        # not JPEGs: the BGR route, into a pinned buffer of their own
-            pb = self._pinned_png[slot]
-            if pb is None or tuple(pb.shape[1:3]) != (h, w):
-                pb = self._pinned_png[slot] = torch.empty((self.batch, h, w, 3), dtype=torch.uint8, pin_memory=True)
-            k = len(others)
-            arr2 = (C.c_char_p * k)(*[os_fsencode(self.paths[lo + i]) for i in others])
-            status2 = (C.c_int * k)()
-            if self._lib.sd_decode_files_bgr(arr2, k, h, w, C.c_void_p(pb.data_ptr()), h * w * 3, self.workers, status2) != L.SD_OK:
-                bad = [(self.paths[lo + i], status2[j]) for j, i in enumerate(others) if status2[j] != L.SD_OK]
-                raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
-            png = [(i, pb[j]) for j, i in enumerate(others)]
-        return buf[:n], descs, png, (h, w)
-
-    def _reconstruct(self, host):
-        """device route, GPU part of one batch, all on the current stream: per-frame asynchronous uploads of the coefficients each
-        frame really has (a 4:2:0 frame has half of a 4:4:4 frame's), the two kernels, the PNG frames' uploads"""
-        torch = self._torch
-        coef, descs, png, (h, w) = host
-        n = coef.shape[0]
-        dev = torch.empty((n, h, w, 3), dtype=torch.uint8, device=self.device)
-        is_png = {i for i, _ in png}
-        jp = [i for i in range(n) if i not in is_png]
-        if jp:
-            cdev = torch.empty((len(jp), coef.shape[1]), dtype=torch.int16, device=self.device)
-            sub = (L.sd_jpeg_frame_desc * len(jp))()
-            for j, i in enumerate(jp):
-                used = descs[i].coef_elems()
-                cdev[j, :used].copy_(coef[i, :used], non_blocking=True)
-                sub[j] = descs[i]
-            # a run of consecutive JPEG frames is a contiguous slice of the batch tensor: the kernels write straight into it (a batch
-            # without PNG files is one run), and nothing but the coefficient copies crosses the bus
-            j0 = 0
-            while j0 < len(jp):
-                j1 = j0 + 1
-                while j1 < len(jp) and jp[j1] == jp[j1 - 1] + 1:
-                    j1 += 1
-                run = (L.sd_jpeg_frame_desc * (j1 - j0))(*[sub[j] for j in range(j0, j1)])
-                self.engine.jpeg_reconstruct(cdev[j0:j1], run, out=dev[jp[j0]:jp[j0] + (j1 - j0)])
-                j0 = j1
-        for i, frame in png:
-            dev[i].copy_(frame, non_blocking=True)
-        return dev
-
-    def _host_coef(self, slot, idx, lo, h, w):
-        """the host coefficient decoder on the files lo + i, i in idx -> (pinned int16 rows, descriptors), or the ValueError of the
-        "device" route"""
-        torch = self._torch
-        stride = self.coef_stride_bytes(h, w)
-        buf = self._pinned_coef[slot] if slot is not None else None
-        if buf is None or buf.shape[1] != stride // 2 or buf.shape[0] < len(idx):
-            buf = torch.empty((max(self.batch, len(idx)), stride // 2), dtype=torch.int16, pin_memory=True)
-            if slot is not None:
-                self._pinned_coef[slot] = buf
-        k = len(idx)
-        arr = (C.c_char_p * k)(*[os_fsencode(self.paths[lo + i]) for i in idx])
-        status = (C.c_int * k)()
-        descs = (L.sd_jpeg_frame_desc * k)()
-        st = self._lib.sd_decode_files_jpeg_coef(arr, k, h, w, C.c_void_p(buf.data_ptr()), stride, descs, self.workers, status)
-        if st != L.SD_OK:
-            bad = [(self.paths[lo + i], status[j]) for j, i in enumerate(idx) if status[j] not in (L.SD_OK, L.SD_ERR_FORMAT)]
-            raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
-        return buf, descs
-
-    def _plan_into(self, slot: int, lo: int, hi: int):
-        """entropy and sync routes, host part of one batch: the plan call into pinned staging (the sync route's writes the clean
-        stream there), the host coefficient decoder for the JPEGs that are not eligible, the BGR route for the files that are not JPEGs"""
-        sync = self.jpeg == "device_sync"
-        frame_t, interval_t = (L.sd_jpeg_sync_frame, L.sd_jpeg_sync_interval) if sync else (L.sd_jpeg_entropy_frame, L.sd_jpeg_interval)
-        import os
-        torch = self._torch
-        h, w = self._header_size(self.paths[lo])
-        n = hi - lo
-        sizes = []
-        for p in self.paths[lo:hi]:
-            try:
-                sizes.append(os.path.getsize(p))
-            except OSError:
-                sizes.append(0)
-        byte_stride = max(16, -(-max(sizes) // 16) * 16)            # the scan bytes are fewer than the file's
-        ivs = max(64, min(-(-h // 8) * -(-w // 8), 16384))          # ranges per frame: a file with more falls back to the host decoder
-        T = L.SD_JPEG_ENTROPY_TABLES
-        st_ = self._pinned_ent[slot]
-        if st_ is None or st_["bytes"].shape[1] < byte_stride or st_["ivs"] != ivs:
-            def pin(nbytes):
-                return torch.empty((nbytes,), dtype=torch.uint8, pin_memory=True)
-            st_ = self._pinned_ent[slot] = dict(
-                bytes=torch.empty((self.batch, byte_stride), dtype=torch.uint8, pin_memory=True), ivs=ivs,
-                descs=pin(self.batch * C.sizeof(L.sd_jpeg_frame_desc)), frames=pin(self.batch * C.sizeof(frame_t)),
-                tables=pin(self.batch * T * C.sizeof(L.sd_jpeg_huff_table)), intervals=pin(self.batch * ivs * C.sizeof(interval_t)),
-                status=torch.empty((self.batch,), dtype=torch.int32, pin_memory=True))
-        byte_stride = st_["bytes"].shape[1]
-        # the records live in the pinned buffers: the C call uploads them with asynchronous copies, and a slot is not planned into again
-        # before the event of its last batch has passed
-        descs = (L.sd_jpeg_frame_desc * n).from_address(st_["descs"].data_ptr())
-        frames = (frame_t * n).from_address(st_["frames"].data_ptr())
-        tables = (L.sd_jpeg_huff_table * (n * T)).from_address(st_["tables"].data_ptr())
-        intervals = (interval_t * (n * ivs)).from_address(st_["intervals"].data_ptr())
-        arr = (C.c_char_p * n)(*[os_fsencode(p) for p in self.paths[lo:hi]])
-        status = (C.c_int * n)()
-        if sync:
-            self._lib.sd_plan_files_jpeg_sync(arr, n, h, w, self.sync_piece, C.c_void_p(st_["bytes"].data_ptr()), byte_stride, descs, frames, tables,
-                                              intervals, ivs, self.workers, status)
-        else:
-            self._lib.sd_plan_files_jpeg_entropy(arr, n, h, w, C.c_void_p(st_["bytes"].data_ptr()), byte_stride, descs, frames, tables, intervals,
-                                                 ivs, self.workers, status)
-        others = [i for i in range(n) if status[i] == L.SD_ERR_FORMAT]
-        eligible = [i for i in range(n) if status[i] == L.SD_OK and frames[i].eligible]
-        # every other file -- not eligible, unreadable, too large for the staging -- is the host decoder's: it decodes it or raises what
-        # the "device" route raises for the batch
-        fallback = [i for i in range(n) if i not in others and i not in eligible]
-        fb = self._host_coef(slot, fallback, lo, h, w) if fallback else None
-        png = []
-        if others:
-            pb = self._pinned_png[slot]
-            if pb is None or tuple(pb.shape[1:3]) != (h, w):
-                pb = self._pinned_png[slot] = torch.empty((self.batch, h, w, 3), dtype=torch.uint8, pin_memory=True)
-            k = len(others)
-            arr2 = (C.c_char_p * k)(*[os_fsencode(self.paths[lo + i]) for i in others])
-            status2 = (C.c_int * k)()
-            if self._lib.sd_decode_files_bgr(arr2, k, h, w, C.c_void_p(pb.data_ptr()), h * w * 3, self.workers, status2) != L.SD_OK:
-                bad = [(self.paths[lo + i], status2[j]) for j, i in enumerate(others) if status2[j] != L.SD_OK]
-                raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
-            png = [(i, pb[j]) for j, i in enumerate(others)]
-        return dict(n=n, lo=lo, size=(h, w), pinned=st_, descs=descs, frames=frames, tables=tables, intervals=intervals, ivs=ivs,
-                    eligible=eligible, fallback=fallback, fb=fb, png=png)
-
-    def _entropy_reconstruct(self, host):
-        """entropy route, GPU part of one batch on the current stream: the scan bytes' upload, the entropy kernels, the uploads of the
-        host-decoded frames, the status words' way back on the feeder's copy stream, then the reconstruction of the "device" route.
-        The sync route is the same walk with Engine.jpeg_sync_decode on the clean streams; its flagged frames are real (a stream the
-        pieces did not synchronise on, or whose bits ran out, is the host decoder's to decide) and are listed in ``sync_fallback``."""
-        torch = self._torch
-        sync = self.jpeg == "device_sync"
-        fell = self.sync_fallback if sync else self.entropy_fallback
-        n, lo, (h, w), pin = host["n"], host["lo"], host["size"], host["pinned"]
-        dev = torch.empty((n, h, w, 3), dtype=torch.uint8, device=self.device)
-        cstride = self.coef_stride_bytes(h, w) // 2
-        descs = (L.sd_jpeg_frame_desc * n)()
-        jp = sorted(host["eligible"] + host["fallback"])
-        cdev = torch.empty((n, cstride), dtype=torch.int16, device=self.device) if jp else None
-        if host["eligible"]:
-            # whole rows of the staging buffer (its stride is the largest file of the batches so far): one contiguous pinned copy
-            sdev = torch.empty((n, pin["bytes"].shape[1]), dtype=torch.uint8, device=self.device)
-            sdev.copy_(pin["bytes"][:n], non_blocking=True)
-            status = torch.empty((n,), dtype=torch.int32, device=self.device)
-            if sync:
-                self.engine.jpeg_sync_decode(sdev, host["descs"], host["frames"], host["tables"], host["intervals"], host["ivs"], self.sync_piece,
-                                             out=cdev, status=status)
-            else:
-                self.engine.jpeg_entropy_decode(sdev, host["descs"], host["frames"], host["tables"], host["intervals"], host["ivs"], out=cdev,
-                                                status=status)
-            for i in host["eligible"]:
-                descs[i] = host["descs"][i]
-            if self._copy_stream is None:
-                self._copy_stream = torch.cuda.Stream(self.device)
-            done = torch.cuda.Event()
-            done.record()
-            with torch.cuda.stream(self._copy_stream):
-                self._copy_stream.wait_event(done)
-                pin["status"][:n].copy_(status, non_blocking=True)
-            status.record_stream(self._copy_stream)
-        if host["fallback"]:
-            buf, fdescs = host["fb"]
-            for j, i in enumerate(host["fallback"]):
-                k = fdescs[j].coef_elems()
-                cdev[i, :k].copy_(buf[j, :k], non_blocking=True)
-                descs[i] = fdescs[j]
-                fell.append((lo + i, "ineligible"))
-        if host["eligible"]:
-            self._copy_stream.synchronize()                 # the feeder's own stream: the status words are in pinned memory now
-            flagged = [i for i in host["eligible"] if int(pin["status"][i]) != 0]
-            # Defensive only: the tests know no stream the host decoder accepts and the kernel flags, so in practice the host decoder
-            # raises here what the "device" route raises.  Should it accept, its coefficients replace the slot's.
-            if flagged:
-                buf, fdescs = self._host_coef(None, flagged, lo, h, w)
-                pin["flagged_coef"] = buf                   # (pinned, read by asynchronous copies: kept until this staging slot is planned into again)
-                for j, i in enumerate(flagged):
-                    k = fdescs[j].coef_elems()
-                    cdev[i, :k].copy_(buf[j, :k], non_blocking=True)
-                    descs[i] = fdescs[j]
-                    fell.append((lo + i, "flagged"))
-                fell.sort()
-        j0 = 0
-        while j0 < len(jp):                                 # runs of consecutive JPEG frames, as on the "device" route
-            j1 = j0 + 1
-            while j1 < len(jp) and jp[j1] == jp[j1 - 1] + 1:
-                j1 += 1
-            run = (L.sd_jpeg_frame_desc * (j1 - j0))(*[descs[jp[j]] for j in range(j0, j1)])
-            self.engine.jpeg_reconstruct(cdev[jp[j0]:jp[j0] + (j1 - j0)], run, out=dev[jp[j0]:jp[j0] + (j1 - j0)])
-            j0 = j1
-        for i, frame in host["png"]:
-            dev[i].copy_(frame, non_blocking=True)
-        return dev
-
     @staticmethod
     def png_rows_stride(h: int, w: int) -> int:
         """bytes that hold the filtered rows of any 8-bit PNG frame of h x w: a filter byte plus four channels per row, rounded up to the
         16 bytes the kernel loads"""
         return -(-(h * (1 + 4 * w)) // 16) * 16
 
-    def _inflate_into(self, slot: int, lo: int, hi: int):
-        """PNG device route, host part of one batch: the chunk walk and the inflate of every PNG file into pinned staging
-        (sd_inflate_files_png); the files that are not PNGs go down the ``jpeg=`` route of a feeder of their own"""
-        torch = self._torch
-        h, w = self._header_size(self.paths[lo])
-        stride = self.png_rows_stride(h, w)
-        n = hi - lo
-        st_ = self._pinned_rows[slot]
-        if st_ is None or st_["rows"].shape[1] != stride:
-            st_ = self._pinned_rows[slot] = dict(
-                rows=torch.empty((self.batch, stride), dtype=torch.uint8, pin_memory=True),
-                descs=torch.empty((self.batch * C.sizeof(L.sd_png_frame_desc),), dtype=torch.uint8, pin_memory=True),
-                status=torch.empty((self.batch,), dtype=torch.int32, pin_memory=True))
-        # the descriptors live in the pinned buffer: the C call uploads them with an asynchronous copy, and a slot is not inflated into
-        # again before the event of its last batch has passed
-        descs = (L.sd_png_frame_desc * n).from_address(st_["descs"].data_ptr())
-        arr = (C.c_char_p * n)(*[os_fsencode(p) for p in self.paths[lo:hi]])
-        status = (C.c_int * n)()
-        st = self._lib.sd_inflate_files_png(arr, n, h, w, C.c_void_p(st_["rows"].data_ptr()), stride, descs, self.workers, status)
-        if st != L.SD_OK:
-            bad = [(self.paths[lo + i], status[i]) for i in range(n) if status[i] not in (L.SD_OK, L.SD_ERR_FORMAT)]
-            raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
-        others = [i for i in range(n) if status[i] == L.SD_ERR_FORMAT]
-        rest = None
-        if others:
-            sub = self._others[slot]
-            if sub is None:
-                sub = self._others[slot] = FrameFeeder([], self.batch, device=self.device, workers=self.workers, jpeg=self.jpeg,
-                                                       engine=self.engine if self.jpeg != "host" else None, sync_piece=self.sync_piece)
-            sub.paths = [self.paths[lo + i] for i in others]
-            stage = {"host": sub._decode_into, "device": sub._decode_coef_into, "device_entropy": sub._plan_into, "device_sync": sub._plan_into}[self.jpeg]
-            rest = stage(slot, 0, len(others))
-            rh, rw = tuple(rest.shape[1:3]) if self.jpeg == "host" else (rest[3] if self.jpeg == "device" else rest["size"])
-            if (rh, rw) != (h, w):
-                bad = [(p, L.SD_ERR_INVALID) for p in sub.paths]
-                raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
-        return dict(n=n, lo=lo, size=(h, w), pinned=st_, descs=descs, others=others, rest=rest, slot=slot)
+    def _decode_into(self, slot: int, lo: int, hi: int) -> StagedBatch:
+        """the host half of one batch, on the worker thread: the size of the first file is the batch's, every stage takes its files of
+        those it is given and the rest goes to the next stage"""
+        batch = StagedBatch(hi - lo, lo, self._header_size(self.paths[lo]), [None] * (hi - lo))
+        rest = list(range(hi - lo))
+        for stage in self.stages:
+            if rest:
+                rest = stage.host(slot, batch, rest)
+        return batch
 
-    def _png_reconstruct(self, host):
-        """PNG device route, GPU part of one batch on the current stream: the uploads of the rows each frame really has, one kernel per
-        run of consecutive PNG frames writing straight into the batch tensor, the status words' way back on the feeder's copy stream when
-        the batch holds a palette frame, then the frames of the other files"""
-        torch = self._torch
-        n, lo, (h, w), pin, descs = host["n"], host["lo"], host["size"], host["pinned"], host["descs"]
-        dev = torch.empty((n, h, w, 3), dtype=torch.uint8, device=self.device)
-        others = set(host["others"])
-        pg = [i for i in range(n) if i not in others]
-        status = None
-        if pg:
-            stride = pin["rows"].shape[1]
-            rdev = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
-            status = torch.zeros((n,), dtype=torch.int32, device=self.device)
-            for i in pg:
-                used = -(-descs[i].rows_bytes() // 16) * 16
-                rdev[i, :used].copy_(pin["rows"][i, :used], non_blocking=True)
-            size = C.sizeof(L.sd_png_frame_desc)
-            j0 = 0
-            while j0 < len(pg):                                 # a run of consecutive PNG frames is a contiguous slice of the batch tensor
-                j1 = j0 + 1
-                while j1 < len(pg) and pg[j1] == pg[j1 - 1] + 1:
-                    j1 += 1
-                i0, m = pg[j0], j1 - j0
-                run = (L.sd_png_frame_desc * m).from_address(pin["descs"].data_ptr() + i0 * size)
-                self.engine.png_reconstruct(rdev[i0:i0 + m], run, out=dev[i0:i0 + m], status=status[i0:i0 + m])
-                j0 = j1
-        palette = [i for i in pg if descs[i].color_type == 3]
-        if palette:                                             # only an index beyond the palette can be flagged
-            if self._copy_stream is None:
-                self._copy_stream = torch.cuda.Stream(self.device)
-            done = torch.cuda.Event()
-            done.record()
-            with torch.cuda.stream(self._copy_stream):
-                self._copy_stream.wait_event(done)
-                pin["status"][:n].copy_(status, non_blocking=True)
-            status.record_stream(self._copy_stream)
-        if host["others"]:
-            sub = self._others[host["slot"]]
-            rest = host["rest"]
-            if self.jpeg == "host":
-                rdev2 = rest.to(self.device, non_blocking=True)
-            else:
-                rdev2 = (sub._reconstruct if self.jpeg == "device" else sub._entropy_reconstruct)(rest)
-                self.entropy_fallback += [(lo + host["others"][j], why) for j, why in sub.entropy_fallback]
-                self.sync_fallback += [(lo + host["others"][j], why) for j, why in sub.sync_fallback]
-                del sub.entropy_fallback[:], sub.sync_fallback[:]
-            for j, i in enumerate(host["others"]):
-                dev[i].copy_(rdev2[j], non_blocking=True)
-        if palette:
-            self._copy_stream.synchronize()                     # the feeder's own stream: the status words are in pinned memory now
-            bad = [(self.paths[lo + i], L.SD_ERR_INVALID) for i in palette if int(pin["status"][i]) != 0]
-            if bad:                                             # what the host route raises for a file with an index beyond its palette
-                raise ValueError(f"FrameFeeder: {len(bad)} frame(s) of the batch could not be read as {h}x{w} PNG / JPEG frames: {bad[:3]}")
+    def _upload(self, batch: StagedBatch):
+        """the device half of one batch, all on the current stream, stage by stage -> the u8 [n,h,w,3] device tensor"""
+        mine = [stage for stage in self.stages if stage.name in batch.payload]
+        dev = None
+        for stage in mine:
+            dev = stage.device(batch, dev)
+        for stage in mine:
+            stage.settle(batch)
         return dev
+
+    def _read_back(self, status, pinned):
+        """start the copy of the device tensor ``status`` into ``pinned`` on the feeder's own stream, behind the work queued on the current
+        stream so far -> a function that returns once the words are in pinned memory"""
+        torch = self._torch
+        if self._copy_stream is None:
+            self._copy_stream = torch.cuda.Stream(self.device)
+        done = torch.cuda.Event()
+        done.record()
+        with torch.cuda.stream(self._copy_stream):
+            self._copy_stream.wait_event(done)
+            pinned.copy_(status, non_blocking=True)
+        status.record_stream(self._copy_stream)
+        return self._copy_stream.synchronize
+
+    def _fell_back(self, which: str, frames):
+        """note (global index, why) of frames that took the host decoder in ``entropy_fallback`` or ``sync_fallback``"""
+        fell = getattr(self, which)
+        fell += frames
+        fell.sort()
 
     def __iter__(self):
         torch = self._torch
@@ -662,13 +666,8 @@ class FrameFeeder:
         if not ranges:
             return
         with ThreadPoolExecutor(max_workers=1) as ahead:
-            decode = {"host": self._decode_into, "device": self._decode_coef_into, "device_entropy": self._plan_into, "device_sync": self._plan_into}[self.jpeg]
-            rebuild = {"device": self._reconstruct, "device_entropy": self._entropy_reconstruct, "device_sync": self._entropy_reconstruct}.get(self.jpeg)
-            if self.png == "device":
-                decode, rebuild = self._inflate_into, self._png_reconstruct
-            self.entropy_fallback = []
-            self.sync_fallback = []
-            fut = ahead.submit(decode, 0, *ranges[0])
+            self.entropy_fallback, self.sync_fallback = [], []
+            fut = ahead.submit(self._decode_into, 0, *ranges[0])
             events = [None, None]
             for k, (lo, hi) in enumerate(ranges):
                 host = fut.result()
@@ -676,14 +675,9 @@ class FrameFeeder:
                     slot = (k + 1) & 1
                     if events[slot] is not None:
                         events[slot].synchronize()          # the upload out of that staging buffer (two batches ago) has finished
-                    fut = ahead.submit(decode, slot, *ranges[k + 1])
-                dev = rebuild(host) if rebuild else host.to(self.device, non_blocking=True)
+                    fut = ahead.submit(self._decode_into, slot, *ranges[k + 1])
+                dev = self._upload(host)
                 if self.device.type == "cuda":
                     events[k & 1] = torch.cuda.Event()
                     events[k & 1].record()
                 yield dev, lo
-
-
-def os_fsencode(p) -> bytes:
-    import os
-    return os.fsencode(p)

@@ -401,3 +401,71 @@ def test_default_decode_workers_divides_by_the_ranks_of_the_node(monkeypatch):
     monkeypatch.setenv("LOCAL_WORLD_SIZE", "1")
     monkeypatch.setattr(frame_io, "_cgroup_cpu_quota", lambda: 16)
     assert frame_io.default_decode_workers() == 16
+
+
+# ------------------------------------------------------------------------------------------------ the five native batch readers, one file list
+BATCH_FILES = ("good.jpg", "good.png", "missing.jpg", None, "truncated.jpg", "truncated.png", "other_size.jpg", "other_size.png")
+# (return value, status per file of BATCH_FILES) as the readers answered before they shared one file pool: SD_OK 0, SD_ERR_INVALID -1,
+# SD_ERR_NOTFOUND -4 (missing and NULL paths), SD_ERR_FORMAT -5 (a readable file of the other format: no failure).  A truncated JPEG is
+# planned as "not eligible" (status 0), which leaves it to the host decoder; a JPEG of another size is refused only where it is eligible.
+BATCH_STATUS = {
+    "sd_decode_files_bgr": (-1, [0, 0, -4, -4, -1, -1, -1, -1]),
+    "sd_decode_files_jpeg_coef": (-1, [0, -5, -4, -4, -1, -5, -1, -5]),
+    "sd_inflate_files_png": (-1, [-5, 0, -4, -4, -5, -1, -5, -1]),
+    "sd_plan_files_jpeg_entropy": (-1, [0, -5, -4, -4, 0, -5, -1, -5]),
+    "sd_plan_files_jpeg_sync": (-1, [0, -5, -4, -4, 0, -5, -1, -5]),
+}
+
+
+def batch_reader_statuses(lib, L, paths, h, w, threads):
+    """every native batch reader once on ``paths`` (bytes or None) at h x w -> {name: (return value, [status per file])}"""
+    import ctypes as C
+    n = len(paths)
+    arr = (C.c_char_p * max(n, 1))(*paths)
+    stride, ivs, T = 1 << 14, 64, L.SD_JPEG_ENTROPY_TABLES
+    out = np.zeros((max(n, 1), stride), np.uint8)
+    ptr = out.ctypes.data_as(C.c_void_p)
+    descs, pdescs = (L.sd_jpeg_frame_desc * max(n, 1))(), (L.sd_png_frame_desc * max(n, 1))()
+    tables = (L.sd_jpeg_huff_table * (max(n, 1) * T))()
+    eframes, eivs = (L.sd_jpeg_entropy_frame * max(n, 1))(), (L.sd_jpeg_interval * (max(n, 1) * ivs))()
+    sframes, sivs = (L.sd_jpeg_sync_frame * max(n, 1))(), (L.sd_jpeg_sync_interval * (max(n, 1) * ivs))()
+    calls = {
+        "sd_decode_files_bgr": lambda st: lib.sd_decode_files_bgr(arr, n, h, w, ptr, stride, threads, st),
+        "sd_decode_files_jpeg_coef": lambda st: lib.sd_decode_files_jpeg_coef(arr, n, h, w, ptr, stride, descs, threads, st),
+        "sd_inflate_files_png": lambda st: lib.sd_inflate_files_png(arr, n, h, w, ptr, stride, pdescs, threads, st),
+        "sd_plan_files_jpeg_entropy": lambda st: lib.sd_plan_files_jpeg_entropy(arr, n, h, w, ptr, stride, descs, eframes, tables, eivs, ivs, threads, st),
+        "sd_plan_files_jpeg_sync": lambda st: lib.sd_plan_files_jpeg_sync(arr, n, h, w, 64, ptr, stride, descs, sframes, tables, sivs, ivs, threads, st),
+    }
+    got = {}
+    for name, call in calls.items():
+        status = (C.c_int * max(n, 1))(*([77] * max(n, 1)))
+        got[name] = (call(status), list(status)[:n])
+    return got
+
+
+def write_batch_files(folder, h=16, w=24):
+    """BATCH_FILES in ``folder`` -> their paths as bytes (None stays None): the JPEGs from the project's encoder (restart intervals: eligible
+    on both plan routes), the "other size" files two rows taller"""
+    rng = np.random.default_rng(12)
+    files = {}
+    for name, rows in (("good", h), ("other_size", h + 2)):
+        img = rng.integers(0, 256, (rows, w, 3), dtype=np.uint8)
+        files[name + ".jpg"] = outputs.encode_jpeg_host(img, 90)
+        files[name + ".png"] = open(outputs.write_png(os.path.join(folder, name + ".png"), img), "rb").read()
+    for ext in (".jpg", ".png"):
+        files["truncated" + ext] = files["good" + ext][:len(files["good" + ext]) // 2]
+    for name, data in files.items():
+        open(os.path.join(folder, name), "wb").write(data)
+    return [None if name is None else os.fsencode(os.path.join(folder, name)) for name in BATCH_FILES]
+
+
+def test_the_batch_readers_report_the_same_statuses_at_every_thread_count(tmp_path):
+    """sd_decode_files_bgr, sd_decode_files_jpeg_coef, sd_inflate_files_png, sd_plan_files_jpeg_entropy and sd_plan_files_jpeg_sync on a
+    good file, a missing path, a NULL path, a truncated file, a file of the other format and a file of another size, with 1, 3 and more
+    threads than files: per-file statuses and return values are those of BATCH_STATUS; no files is SD_OK"""
+    from semantic_depth_amd import _lib as L
+    lib = L.load()
+    paths = write_batch_files(str(tmp_path))
+    for threads in (1, 3, len(paths) + 5):
+        assert batch_reader_statuses(lib, L, paths, 16, 24, threads) == BATCH_STATUS, threads
+        assert batch_reader_statuses(lib, L, [], 16, 24, threads) == {name: (L.SD_OK, []) for name in BATCH_STATUS}, threads
