@@ -1174,6 +1174,11 @@ int sd_small_batch_split(long rows, int cout, int kpad, int cus, int* k_tiles_pe
 int sd_small_batch_split_direct(long items, int nchunks, int cus, int* chunks_per_slice_out);
 /* the layers of `net` this handle runs split, as "layer:S,layer:S" (empty: none); SD_ERR_INVALID when cap is too small */
 sd_status sd_small_batch_plan(const sd_handle* h, sd_net net, char* layers_out, size_t cap);
+/* which kernel runs every conv layer of `net` in a call of `frames` frames (0 = a full pass): one line "layer label slices\n" per layer, in launch order.
+ * `label` is the per-layer profile label (the one SEMDEPTH_PROFILE_VERBOSE prints), `slices` the small-batch split (1 = one launch; above it the layer's reduce
+ * launch follows).  A layer nothing can run is listed with the text of the error its call fails with in place of the label.  Needs no bound memory and no
+ * device.  SD_ERR_INVALID when cap is too small (the text is cut at cap - 1) */
+sd_status sd_conv_forms(const sd_handle* h, sd_net net, int frames, char* out, size_t cap);
 
 /* the same count without a device synchronisation: an 8-byte device-to-host copy enqueued on `stream` behind the work already on it
  * (host_dst = pinned host memory of the caller).  The host-side classes use it to turn a range violation into an ERROR of the call that

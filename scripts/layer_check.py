@@ -12,20 +12,19 @@ seconds compare within one run only, main() here checks that over its own run an
 small-batch forms at 192 x 256, and fc6 / fc7 alone at 192 x 1024 with 16 frames (_odd_cases): partial row tiles behind full ones, maps 3 and 5 pixels high or wide, GEMMs whose M is no multiple of 256.
 Such a case names in need_at the kernel and the map extent it is there for, and fails where the planner routed the layer elsewhere.
 
-Reading a failure: "<layer> [<kernel label>] image i, y, x, channel c: |delta| / bound = r" names the layer, the kernel instantiation that ran it
-(SEMDEPTH_PROFILE_VERBOSE's label) and the worst element.  r <= 1 passes.  A ratio of a few units on many layers of one engine points at a format
+Reading a failure: "<layer> [<kernel label>] image i, y, x, channel c: |delta| / bound = r" names the layer, the kernel the handle records for it
+(the label of Engine.conv_forms / SEMDEPTH_PROFILE_VERBOSE) and the worst element.  r <= 1 passes.  A ratio of a few units on many layers of one engine points at a format
 term of the bound (oracle/layers.py SCHEMES / OUT_FORMATS); hundreds and more on one layer, at an edge pixel, the last image or one channel group, is a
 kernel, a weight relayout or a planner bug -- see tests/test_layer_check_cpu.py for what each kind of mistake looks like."""
 import os
 import sys
-import tempfile
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-KEEP, VERBOSE = "SEMDEPTH_KEEP_ACTIVATIONS", "SEMDEPTH_PROFILE_VERBOSE"
+KEEP = "SEMDEPTH_KEEP_ACTIVATIONS"
 FC_CHANNELS = np.r_[0:64, 2016:2080, 4032:4096]      # fc6 / fc7 at full size: the first 64, 64 across the tile boundary at 2048, the last 64
 
 
@@ -173,24 +172,6 @@ def _odd_cases():
 CASES = _cases()
 
 
-class _Stderr:
-    """the bytes the library writes to file descriptor 2 inside the block (the per-layer lines of sd_profile_read)"""
-
-    def __enter__(self):
-        sys.stderr.flush()
-        self.tmp = tempfile.TemporaryFile()
-        self.saved = os.dup(2)
-        os.dup2(self.tmp.fileno(), 2)
-        return self
-
-    def __exit__(self, *exc):
-        os.dup2(self.saved, 2)
-        os.close(self.saved)
-        self.tmp.seek(0)
-        self.text = self.tmp.read().decode(errors="replace")
-        self.tmp.close()
-
-
 _weights = {}
 
 
@@ -202,7 +183,7 @@ def run_case(c, log=None):
     """-> dict(rows=[(group name, kernel label, oracle.layers.Worst)], extents=[(group name, kernel label, (output map height, width))] (of a
     conv with its fused 2x2 pool: the map the conv runs on, twice the stored one),
     uncovered=[op names], labels={op: label}, missing=[needed families that did not run], unmet=[need_at requirements no checked layer met],
-    seconds).  Sets (and restores) the two environment switches an engine latches when it is created."""
+    seconds).  Sets (and restores) the environment switch an engine latches when it is created."""
     from oracle import layers as LY
     from semantic_depth_amd import _lib as L, weights as Wt
     from semantic_depth_amd.engine import Engine
@@ -211,8 +192,8 @@ def run_case(c, log=None):
     net_id = L.SD_NET_FCN8S if fcn else L.SD_NET_MONODEPTH
     enc = "resnet50" if fcn else c["net"]
     H, W, B = c["H"], c["W"], c["frames"]
-    saved = {k: os.environ.get(k) for k in (KEEP, VERBOSE)}
-    os.environ[KEEP] = os.environ[VERBOSE] = "1"
+    saved = {k: os.environ.get(k) for k in (KEEP,)}
+    os.environ[KEEP] = "1"
     try:
         eng = Engine(H, W, c["max_batch"], enc, precision=c["precision"], small_batch=c["small_batch"])
     finally:
@@ -236,20 +217,13 @@ def run_case(c, log=None):
         eng.fcn8s_forward(other) if fcn else eng.monodepth_forward(other)
         stale = eng.net_tensor(net_id, "conv1_1" if fcn else "enc/conv1")      # (that pass's last image is there to be read behind the fed ones)
         assert stale.shape[0] == (1 if fcn else 2) * c["max_batch"] and float(stale[-1].abs().max()) > 0
-    eng.profile(True)
     logits = None
     if fcn:
         logits = eng.fcn8s_forward(dev, want_logits=True)["logits"]
     else:
         eng.monodepth_forward(dev, want_raw=True)
-    with _Stderr() as cap:
-        eng.profile_read()
-    eng.profile(False)
-    labels = {}
-    for line in cap.text.splitlines():
-        if line.startswith("[sd_profile]"):
-            op, lab = line.split()[1], line.split("TF/s", 1)[1].strip()
-            labels[op] = labels[op] + " + " + lab if op in labels else lab
+    # the kernel of each conv layer of this call: the handle's own record (Engine.conv_forms), which run_plan launches from
+    labels = {op: " + ".join(L.conv_launches(*form)) for op, form in eng.conv_forms(net_id, B).items()}
     # the images the float64 side looks at
     nimg = B if fcn else 2 * B
     per = 1 if fcn else 2

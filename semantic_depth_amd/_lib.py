@@ -274,6 +274,7 @@ SIGNATURES = {
     "sd_small_batch_split": (C.c_int, [C.c_long, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "sd_small_batch_split_direct": (C.c_int, [C.c_long, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "sd_small_batch_plan": (C.c_int, [_H, C.c_int, C.c_char_p, C.c_size_t]),
+    "sd_conv_forms": (C.c_int, [_H, C.c_int, C.c_int, C.c_char_p, C.c_size_t]),
 }
 
 _lib = None
@@ -312,3 +313,20 @@ def check(lib, handle, status, what=""):
     if status != SD_OK:
         msg = lib.sd_last_error(handle).decode() if handle else ""
         raise SdError(f"{what}: {lib.sd_status_string(status).decode()} ({status}) {msg}")
+
+
+def conv_launches(label, slices) -> list:
+    """the kernel labels of a listed layer's launches: the reduce launch of a split layer follows its GEMM / direct launch"""
+    return [label] if slices == 1 else [label, "splitk_reduce_kernel" if label.startswith("conv_splitk") else "splitc_reduce_kernel"]
+
+
+def conv_forms(lib, handle, net, frames=0) -> dict:
+    """{conv layer: (label, slices)} from sd_conv_forms (frames = 0: a full pass); a layer nothing can run carries its error text as the label"""
+    buf = C.create_string_buffer(1 << 16)
+    check(lib, handle, lib.sd_conv_forms(handle, net, frames, buf, len(buf)), "sd_conv_forms")
+    out = {}
+    for line in buf.value.decode().splitlines():
+        name, rest = line.split(" ", 1)
+        label, slices = rest.rsplit(" ", 1)
+        out[name] = (label, int(slices))
+    return out

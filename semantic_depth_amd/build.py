@@ -51,6 +51,7 @@ SOURCES = [
     ("seg_eval_gpu.hip", []),
     ("disp_image_gpu.hip", ["-ffp-contract=off"]),
     ("plan.cpp", []),
+    ("conv_form.cpp", []),
     ("capi.cpp", []),
     ("host_png.cpp", []),
     ("host_jpeg.cpp", []),
@@ -66,7 +67,7 @@ SOURCES = [
     ("host_seg_eval.cpp", []),
     ("host_disp_image.cpp", ["-ffp-contract=off"]),
 ]
-HEADERS = ["kernels.hpp", "plan.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", "jpeg_enc.hpp", "jpeg_enc_gpu.hpp", "jpeg_entropy.hpp", "jpeg_entropy_gpu.hpp", "jpeg_sync.hpp", "jpeg_sync_gpu.hpp", "png_unfilter.hpp", "png_in_gpu.hpp", "ply_format.hpp", "ply_gpu.hpp", "scene_format.hpp", "scene_gpu.hpp", "text_draw.hpp", "text_gpu.hpp", "overlay_rule.hpp", "overlay_gpu.hpp", "render_rule.hpp", "render_gpu.hpp", "rw_profile.hpp", "rw_profile_gpu.hpp", "pil_resample.hpp", "seg_eval_gpu.hpp", "disp_image_rule.hpp", "disp_image_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
+HEADERS = ["kernels.hpp", "plan.hpp", "conv_form.hpp", "split_fmt.hpp", "jpeg_common.hpp", "jpeg_gpu.hpp", "png_deflate.hpp", "png_gpu.hpp", "jpeg_enc.hpp", "jpeg_enc_gpu.hpp", "jpeg_entropy.hpp", "jpeg_entropy_gpu.hpp", "jpeg_sync.hpp", "jpeg_sync_gpu.hpp", "png_unfilter.hpp", "png_in_gpu.hpp", "ply_format.hpp", "ply_gpu.hpp", "scene_format.hpp", "scene_gpu.hpp", "text_draw.hpp", "text_gpu.hpp", "overlay_rule.hpp", "overlay_gpu.hpp", "render_rule.hpp", "render_gpu.hpp", "rw_profile.hpp", "rw_profile_gpu.hpp", "pil_resample.hpp", "seg_eval_gpu.hpp", "disp_image_rule.hpp", "disp_image_gpu.hpp", os.path.join("..", "..", "include", "semdepth.h")]
 
 
 def _hipcc() -> str:

@@ -28,6 +28,7 @@
 #include "disp_image_gpu.hpp"
 #include "kernels.hpp"
 #include "plan.hpp"
+#include "conv_form.hpp"
 
 using namespace sd;
 
@@ -54,6 +55,7 @@ struct sd_handle {
     int last_fcn_images = 0, last_mono_images = 0;
     int reserve_cus = 0;            // sd_set_reserved_cus: CUs the persistent conv launches leave free
     int small_batch = 0, cus = 0;   // sd_set_small_batch: the split-K forms of the under-filled GEMM layers; the CU count its rule reads (latched with it)
+    std::vector<ConvForm> forms[2];   // [sd_net], per op of the plan: the kernel form of a full pass (resolve_forms; default records for the other ops)
     size_t o_splitk = 0;            // workspace: the partial sums of the largest split layer (0 bytes without the switch)
     std::vector<CamDev> cams_stage;
     std::vector<CamDev> sweep_stage;     // sd_fuse_backproject_sweep: the [T][B] records of the last call (source of its upload)
@@ -67,7 +69,7 @@ struct sd_handle {
     std::string err;
     // profiling (sd_profile): event pairs around conv launches
     bool prof = false;
-    struct ProfRec { const char* kernel; double flops; hipEvent_t a, b; const char* op; int M, N, K; double bytes; };
+    struct ProfRec { std::string kernel; double flops; hipEvent_t a, b; const char* op; int M, N, K; double bytes; };
     std::vector<ProfRec> prof_recs;
     // one event per conv launch: the end event of a conv is the start event of the conv launched right behind it (two events per
     // launch cost 1.8 % of a step: every record is a barrier packet on the stream)
@@ -96,57 +98,32 @@ NetPlan& plan_of(sd_handle* h, sd_net net) { return net == SD_NET_FCN8S ? h->fcn
 const NetPlan& plan_of(const sd_handle* h, sd_net net) { return net == SD_NET_FCN8S ? h->fcn : h->mono; }
 char* warena(sd_handle* h, sd_net net) { return net == SD_NET_FCN8S ? h->wf : h->wm; }
 
-// conv_dma3.hip's precomputed gathers of an OP_CONV (ConvParams::flat / noup): a property of the plan and the handle's switches
-void dma3_gather(const sd_handle* h, const NetPlan& p, const OpDesc& op, int& flat, int& noup) {
-    const bool ph3 = op.scheme == SC_BF16X3 || op.scheme == SC_HS;     // the phased 256 x 256 GEMM block of conv_dma3.hip exists for these two
-    flat = (ph3 && op.k == 1 && !op.fold && !op.up[0] && !(op.nsrc > 1 && op.up[1]) && op.nsrc <= 2 && !(h->sw & SW_NO_FLAT)) ? 1 : 0;
-    noup = (ph3 && op.nsrc == 1 && !(h->sw & SW_NO_FLAT)) ? 1 : 0;       // (conv_dma3's precomputed gather: ONE source geometry)
-    for (int j = 0; j < op.nsrc; ++j) {      // (32-bit byte offsets inside a plane of every source; strides 1 or 2)
-        const TensorDesc& t = p.tensors[op.src[j]];
-        if ((size_t)p.images * t.H * t.W * t.C * 2 >= ((size_t)1 << 32)) flat = noup = 0;
-        // (a folded op keeps up[0] = 1 from the plan, but its table reads the source at its own resolution: tap layers without upsample)
-        if ((op.up[j] && !op.fold) || op.sstride[j] < 1 || op.sstride[j] > 2) noup = 0;
+// the per-op form tables of a full pass; built where the facts they read become final (sd_create, sd_set_small_batch)
+void resolve_forms(sd_handle* h) {
+    for (sd_net net : {SD_NET_FCN8S, SD_NET_MONODEPTH}) {
+        const NetPlan& p = plan_of(h, net);
+        h->forms[net].clear();
+        for (const OpDesc& op : p.ops) h->forms[net].push_back(resolve_conv_form({h->sw, h->small_batch, h->cus}, p, op, p.images));
     }
 }
 
-// sd_set_small_batch: slices of the K axis this op runs in on this handle (1 = not split).  Reads what the handle fixes -- the images of a full
-// pass, the layer, the CU count -- never a call.  Candidates: OP_CONV GEMMs of the three-product engine with an all-vec K axis, no fused pool, no
-// fold, no sub-planar output, Cout % 256 == 0, that conv_dma3's ring can carry with a precomputed gather (1x1 layers, single-source tap layers)
-int op_ksplit(const sd_handle* h, const NetPlan& p, const OpDesc& op) {
-    if (!h->small_batch || op.kind != OP_CONV || op.scheme != SC_HS || (h->sw & SW_NO_DMA)) return 1;
-    const TensorDesc& d = p.tensors[op.dst];
-    if (!op.vec || op.Kvec != op.Kpad || op.fuse_pool || op.fold || d.planar16 || op.residual >= 0 || d.C % 256 || p.weights[op.w].CoutPad != d.C) return 1;
-    int flat, noup;
-    dma3_gather(h, p, op, flat, noup);
-    if (!flat && !noup) return 1;
-    if (!flat && !(op.k >= 3 && op.sstride[0] == 1)) return 1;       // (the tap layers the HS ring takes: k x k, stride 1 -- conv_dma3_eligible)
-    return conv_splitk_slices((long)p.images * d.H * d.W, d.C, op.Kpad, h->cus);
+// the form of op i in a call of `images` images: the table's, except for the ops whose form reads the call (ConvForm::reads_images), which a partial pass
+// resolves again into `called`
+const ConvForm& form_of(const sd_handle* h, sd_net net, size_t i, int images, ConvForm& called) {
+    const NetPlan& p = plan_of(h, net);
+    const ConvForm& f = h->forms[net][i];
+    return images == p.images || !f.reads_images ? f : called = resolve_conv_form({h->sw, h->small_batch, h->cus}, p, p.ops[i], images);
 }
 
-// sd_set_small_batch level 2: slices of the chunk axis this op runs in on this handle (1 = not split).  Like op_ksplit it reads what the handle fixes.  Candidates:
-// OP_CONV_DIRECT layers of the three-product engine in the 64-channel-pass form (fused 2x2 pool and concatenated sources included), not folded, not the
-// all-upsampled (source-resolution tile) instantiation, no padded channels.  The output may be sub-planar (the hand-off between two direct layers: conv4_1 ->
-// conv4_2 -> conv4_3): the reduce launch writes either layout.  (SEMDEPTH_DISABLE=direct: the planner makes no such op)
-int op_dsplit(const sd_handle* h, const NetPlan& p, const OpDesc& op) {
-    if (h->small_batch < 2 || op.kind != OP_CONV_DIRECT || op.scheme != SC_HS) return 1;
-    const TensorDesc& d = p.tensors[op.dst];
-    if (d.fmt != PL_HS || op.nsplit < 1 || d.C != 64 * op.nsplit || op.fold || (d.Ctf > 0 && d.Ctf < d.C)) return 1;
-    const int H = d.H << op.fuse_pool, W = d.W << op.fuse_pool;        // conv resolution
-    bool all_up = true;
-    for (int i = 0; i < op.nsrc; ++i) all_up = all_up && op.up[i] == 1;
-    if (all_up && !(H & 1) && !(W & 1)) return 1;
-    return conv_splitc_slices(conv_direct_items(W, H, p.images, op.nsplit), op.nchunks, h->cus);
-}
-
+// sd_set_small_batch: the partial sums of the largest split layer (a chunk-split direct layer keeps them at conv resolution: before a fused pool)
 size_t splitk_scratch_bytes(const sd_handle* h) {
     size_t mx = 0;
-    for (const NetPlan* p : {&h->fcn, &h->mono})
-        for (const OpDesc& op : p->ops) {
-            const TensorDesc& d = p->tensors[op.dst];
-            const int S = op_ksplit(h, *p, op);
-            if (S > 1) mx = std::max(mx, (size_t)S * p->images * d.H * d.W * d.C * sizeof(float));
-            const int Sd = op_dsplit(h, *p, op);        // (partials at conv resolution: before a fused pool)
-            if (Sd > 1) mx = std::max(mx, (size_t)Sd * p->images * (d.H << op.fuse_pool) * (d.W << op.fuse_pool) * d.C * sizeof(float));
+    for (sd_net net : {SD_NET_FCN8S, SD_NET_MONODEPTH})
+        for (size_t i = 0; i < h->forms[net].size(); ++i) {
+            const NetPlan& p = plan_of(h, net);
+            const OpDesc& op = p.ops[i];
+            if (const int S = h->forms[net][i].slices; S > 1)
+                mx = std::max(mx, (size_t)S * p.images * (p.tensors[op.dst].H << op.fuse_pool) * (p.tensors[op.dst].W << op.fuse_pool) * p.tensors[op.dst].C * sizeof(float));
         }
     return mx;
 }
@@ -238,7 +215,7 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, 
     };
     // a conv launch in a profiling bracket: its start event is the end event of the conv launched right before it when nothing else came between
     // (sd_handle::prof_pool).  M x Nc: the record's GEMM extent; `kernel` names the launch for the record
-    auto bracketed = [&](const OpDesc& op, hipError_t& e, int M, int Nc, auto&& launch, auto&& kernel, double extra_bytes = -1.0) -> sd_status {
+    auto bracketed = [&](const OpDesc& op, hipError_t& e, int M, int Nc, auto&& launch, const char* kernel, double extra_bytes = -1.0) -> sd_status {
         // (extra_bytes >= 0: a launch that carries none of the op's algorithmic work -- the reduce half of a split-K layer: its record holds these bytes)
         if (!h->prof) { e = launch(); return SD_OK; }
         hipEvent_t ea = h->prof_last, eb = nullptr;
@@ -247,15 +224,21 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, 
         e = launch();
         hipEventRecord(eb, s);
         h->prof_last = eb;
-        h->prof_recs.push_back({kernel(), extra_bytes >= 0 ? 0.0 : op.flops * N / p.images, ea, eb, op.name.c_str(), M, Nc, op.K, extra_bytes >= 0 ? extra_bytes : op_bytes(op)});
+        h->prof_recs.push_back({kernel, extra_bytes >= 0 ? 0.0 : op.flops * N / p.images, ea, eb, op.name.c_str(), M, Nc, op.K, extra_bytes >= 0 ? extra_bytes : op_bytes(op)});
         return SD_OK;
     };
     for (const WeightSlot& wsl : p.weights)
         if (!wsl.loaded) return fail(h, SD_ERR_STATE, "weight not loaded: " + wsl.name);
     h->prof_last = nullptr;                 // (other work may have been put on the stream since the previous call)
-    for (const OpDesc& op : p.ops) {
+    const bool verbose = (h->sw & SW_PROFILE_VERBOSE) != 0;
+    ConvForm called;        // (a partial pass: the record of an op whose form reads the call)
+    for (size_t i = 0; i < p.ops.size(); ++i) {
+        const OpDesc& op = p.ops[i];
         hipError_t e = hipSuccess;
         sd_status st = SD_OK;
+        // conv ops: the handle's form names the launcher and its variant (DESIGN.md "which kernel runs a layer"); here only pointers and the call's size are filled in
+        const ConvForm& f = form_of(h, net, i, N, called);
+        const char* const label = (verbose ? f.verbose : f.label).c_str();
         switch (op.kind) {
             case OP_PRE_VGG:
                 e = launch_pre_vgg(frames, T(op.dst), (long)nframes * h->H * h->W, p.tensors[op.dst].fmt, PL(op.dst), s);
@@ -264,96 +247,57 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, 
                 e = launch_pre_mono(frames, T(op.dst), nframes, h->H, h->W, p.tensors[op.dst].fmt, PL(op.dst), p.input_scale == 1.f ? 1 : 0, s);
                 break;
             case OP_CONV: {
+                if (f.error) return fail(h, SD_ERR_STATE, f.error);
                 const TensorDesc& d = p.tensors[op.dst];
-                const TensorDesc& s0 = p.tensors[op.src[0]];
-                ConvParams c{};
-                c.nsrc = op.nsrc; c.Ctot = op.Ctot;
-                c.N = N; c.Hin = s0.H * (op.up[0] ? 2 : 1); c.Win = s0.W * (op.up[0] ? 2 : 1);
-                c.pool = op.fuse_pool;
-                c.Hout = d.H << c.pool; c.Wout = d.W << c.pool; c.Cout = d.C; c.CoutPad = p.weights[op.w].CoutPad;
-                c.kh = c.kw = op.k; c.stride = op.sstride[0]; c.pad = op.pad;
-                c.K = op.K; c.Kpad = op.Kpad;
-                c.wt = Wp(op.w); c.bias = Wp(op.b);
-                c.ktab = reinterpret_cast<const KEntry*>(wbase + op.tab_offset);
-                c.vec = op.vec; c.vtiles = op.Kvec / 32;
-                c.simple = op.nsrc == 1 && op.vec && op.Kvec == op.Kpad && op.sstride[0] == 1 && !op.up[0] && op.k * op.k <= 64 &&
-                           op.Kpad == op.k * op.k * s0.C;
-                if (!c.simple && op.nsrc == 2 && op.k == 1 && op.vec && op.Kvec == op.Kpad && !op.up[0] && !op.up[1] && op.pad == 0 &&
-                    s0.C % 32 == 0 && p.tensors[op.src[1]].C % 32 == 0 && op.Kpad == s0.C + p.tensors[op.src[1]].C)
-                    c.simple = 2;
+                ConvParams c = f.conv;
+                c.N = N; c.wt = Wp(op.w); c.bias = Wp(op.b); c.ktab = reinterpret_cast<const KEntry*>(wbase + op.tab_offset);
                 c.residual = op.residual >= 0 ? T(op.residual) : nullptr;
-                c.out = T(op.dst);
-                c.act = op.act; c.m_fastest = op.m_fastest;
-                c.out_plane = PL(op.dst); c.Nmax = p.images;
+                c.out = T(op.dst); c.out_plane = PL(op.dst); c.src0 = T(op.src[0]); c.src0_plane = PL(op.src[0]);
                 c.zero16 = h->ws + h->o_misc + 256;        // the arena is zero-filled and nothing writes here
-                const bool split = p.engine != ENG_F32;
-                c.scheme = op.scheme; c.out_fmt = d.fmt; c.alpha = op.scheme == SC_HS ? 1.f / p.weights[op.w].wscale : 1.f;
-                c.src0 = T(op.src[0]); c.src0_plane = PL(op.src[0]);
-                c.out_planar16 = d.planar16;
-                c.sw = h->sw; c.reserve_cus = h->reserve_cus;
-                c.sat = sat_counter(h);
-                // conv_dma3.hip, k x k stride-1 layers on one source (fc6): one output row of 256 / Wout images per tile, taps on padding rows skipped
-                const bool ph3 = op.scheme == SC_BF16X3 || op.scheme == SC_HS;     // the phased 256 x 256 GEMM block of conv_dma3.hip exists for these two
-                if (ph3 && !op.fold && op.nsrc == 1 && op.vec && op.Kvec == op.Kpad && op.k >= 3 && op.sstride[0] == 1 && !op.up[0] && !c.pool &&
-                    op.Kpad == op.k * op.k * s0.C && c.Wout > 0 && 256 % c.Wout == 0 && N % (256 / c.Wout) == 0 && !(h->sw & SW_NO_ROWSKIP))
-                    c.rowgrp = 256 / c.Wout;
-                dma3_gather(h, p, op, c.flat, c.noup);
-                if (op.fold) {          // (conv_dma3.hip: the GEMM's pixel space is the source itself)
-                    c.fold = 1; c.simple = 0; c.Hin = s0.H; c.Win = s0.W; c.Hout = s0.H; c.Wout = s0.W; c.kh = c.kw = 2;
-                }
-                if (const int S = op_ksplit(h, p, op); S > 1) {
+                c.alpha = op.scheme == SC_HS ? 1.f / p.weights[op.w].wscale : 1.f;
+                c.reserve_cus = h->reserve_cus; c.sat = sat_counter(h);
+                c.rowgrp = f.rowgrp && N % f.rowgrp == 0 ? f.rowgrp : 0;      // CALL-DEPENDENT (conv_form.cpp): row groups only when the call's images fill them
+                const int M = N * c.Hout * c.Wout * (c.fold ? 4 : 1);
+                if (f.family == CF_SPLITK) {
                     // sd_set_small_batch: the k-range form of the HS ring into the partial-sum scratch, then the reduce launch with the layer's epilogue
-                    // (no row groups: a slice is a contiguous range of the whole K axis)
-                    c.rowgrp = 0; c.ksplit = S; c.partial = reinterpret_cast<float*>(h->ws + h->o_splitk);
-                    const int M = N * c.Hout * c.Wout;
-                    st = bracketed(op, e, M, d.C, [&] { return launch_conv_splitk(c, s); }, [&] { return conv_splitk_kernel_name(c); });
+                    c.partial = reinterpret_cast<float*>(h->ws + h->o_splitk);
+                    st = bracketed(op, e, M, d.C, [&] { return launch_conv_dma3(c, f.variant, f.s16, s); }, label);
                     if (st != SD_OK || e != hipSuccess) break;
-                    st = bracketed(op, e, M, d.C, [&] { return launch_splitk_reduce(c, s); }, [&] { return "splitk_reduce_kernel"; },
-                                   (double)M * d.C * (S * sizeof(float) + elem_bytes(d.fmt)));
+                    st = bracketed(op, e, M, d.C, [&] { return launch_splitk_reduce(c, s); }, "splitk_reduce_kernel",
+                                   (double)M * d.C * (f.slices * sizeof(float) + elem_bytes(d.fmt)));
                     break;
                 }
-                const bool dma3 = split && conv_dma3_eligible(c) && !(h->sw & SW_NO_DMA);
-                const bool dma = !dma3 && split && conv_dma_variant(c) != 0 && !(h->sw & SW_NO_DMA);
-                const bool stem = split && !dma && !dma3 && conv_stem_eligible(c);
-                if (c.out_planar16 && !stem && !dma) return fail(h, SD_ERR_STATE, "sub-planar output needs the LDS-DMA or the stem conv kernel");
-                if (c.pool && !dma) return fail(h, SD_ERR_STATE, "fused pool needs the LDS-DMA conv kernel");
-                if (c.fold && !dma3 && !(dma && c.scheme != SC_BF16X3)) return fail(h, SD_ERR_STATE, "an upsample-folded conv needs the conv_dma3 kernel (bf16 x 3) or a two-plane form of conv_dma");
-                st = bracketed(op, e, N * c.Hout * c.Wout * (c.fold ? 4 : 1), d.C,
-                               [&] { return dma3 ? launch_conv_dma3(c, s) : dma ? launch_conv_dma(c, s) : stem ? launch_conv_stem(c, s) : split ? launch_conv_split(c, s) : launch_conv_igemm(c, s); },
-                               [&] { return dma3 ? conv_dma3_kernel_name(c) : dma ? conv_dma_kernel_name(c) : stem ? conv_stem_kernel_name(c) : split ? conv_split_kernel_name(c) : conv_igemm_kernel_name(c); });
+                st = bracketed(op, e, M, d.C, [&] {
+                    switch (f.family) {
+                        case CF_DMA3: return launch_conv_dma3(c, f.variant, f.s16, s);
+                        case CF_DMA: return launch_conv_dma(c, f.variant, s);
+                        case CF_STEM: return launch_conv_stem(c, s);
+                        case CF_SPLIT: return launch_conv_split(c, f.variant, s);
+                        case CF_IGEMM: return launch_conv_igemm(c, s);
+                        default: return hipErrorInvalidValue;
+                    }
+                }, label);
                 break;
             }
             case OP_CONV_DIRECT: {
                 const TensorDesc& d = p.tensors[op.dst];
-                ConvDirectParams c{};
-                c.chunks = reinterpret_cast<const DirectChunk*>(wbase + op.tab_offset);
-                c.nchunks = op.nchunks;
-                c.pool = op.fuse_pool;
-                c.N = N; c.H = d.H << c.pool; c.W = d.W << c.pool;
-                c.nsplit = op.nsplit; c.Cout = d.C / op.nsplit; c.Cstride = d.C; c.out_planar16 = d.planar16;
-                c.nreal = (d.Ctf > 0 && d.Ctf < d.C) ? d.Ctf : 0;
-                c.all_up = 1;
-                for (int i = 0; i < op.nsrc; ++i) c.all_up = c.all_up && op.up[i] == 1;
-                c.fold = op.fold;
-                c.wt = reinterpret_cast<const u32x4_t*>(Wp(op.w)); c.bias = Wp(op.b);
-                c.out = T(op.dst); c.out_plane = PL(op.dst); c.act = op.act; c.Nmax = p.images;
+                ConvDirectParams c = f.dir;
+                c.N = N; c.chunks = reinterpret_cast<const DirectChunk*>(wbase + op.tab_offset);
+                c.wt = reinterpret_cast<const u32x4_t*>(Wp(op.w)); c.bias = Wp(op.b); c.out = T(op.dst); c.out_plane = PL(op.dst);
                 c.zero16 = h->ws + h->o_misc + 256;
-                c.rows_per_wave = 2;
-                c.scheme = op.scheme; c.out_fmt = d.fmt; c.alpha = op.scheme == SC_HS ? 1.f / p.weights[op.w].wscale : 1.f;
-                c.sw = h->sw; c.reserve_cus = h->reserve_cus;
-                c.sat = sat_counter(h);
-                const bool x3 = op.scheme == SC_BF16X3;
-                if (const int S = op_dsplit(h, p, op); S > 1) {
+                c.alpha = op.scheme == SC_HS ? 1.f / p.weights[op.w].wscale : 1.f;
+                c.reserve_cus = h->reserve_cus; c.sat = sat_counter(h);
+                if (f.family == CF_DIRECT_SPLITC) {
                     // sd_set_small_batch level 2: the chunk-range form into the partial-sum scratch, then the reduce launch with the layer's epilogue
-                    c.csplit = S; c.partial = reinterpret_cast<float*>(h->ws + h->o_splitk);
-                    st = bracketed(op, e, N * c.H * c.W, d.C, [&] { return launch_conv_direct_splitc(c, s); }, [&] { return "conv_direct_splitc_hs_kernel"; });
+                    c.partial = reinterpret_cast<float*>(h->ws + h->o_splitk);
+                    st = bracketed(op, e, N * c.H * c.W, d.C, [&] { return launch_conv_direct_splitc(c, s); }, label);
                     if (st != SD_OK || e != hipSuccess) break;
-                    st = bracketed(op, e, N * c.H * c.W, d.C, [&] { return launch_splitc_reduce(c, s); }, [&] { return "splitc_reduce_kernel"; },
-                                   (double)N * d.C * ((double)c.H * c.W * S * sizeof(float) + (double)d.H * d.W * elem_bytes(d.fmt)));
+                    st = bracketed(op, e, N * c.H * c.W, d.C, [&] { return launch_splitc_reduce(c, s); }, "splitc_reduce_kernel",
+                                   (double)N * d.C * ((double)c.H * c.W * f.slices * sizeof(float) + (double)d.H * d.W * elem_bytes(d.fmt)));
                     break;
                 }
-                st = bracketed(op, e, N * c.H * c.W, d.C, [&] { return x3 ? launch_conv_direct3(c, s) : launch_conv_direct(c, s); },
-                               [&] { return x3 ? conv_direct3_kernel_name(c) : conv_direct_kernel_name(c); });
+                st = bracketed(op, e, N * c.H * c.W, d.C,
+                               [&] { return f.family == CF_DIRECT3 ? launch_conv_direct3(c, f.direct, s) : launch_conv_direct(c, f.direct, s); }, label);
                 break;
             }
             case OP_DEC_TAIL1: {
@@ -368,7 +312,7 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, 
                 c.scheme = engine_forms(p.engine).conv;
                 const bool hs = c.scheme == SC_HS;
                 c.alpha = hs ? 1.f / p.weights[op.w].wscale : 1.f; c.alpha2 = hs ? 1.f / p.weights[op.w2].wscale : 1.f;
-                st = bracketed(op, e, N * d.H * d.W, 16, [&] { return launch_dec_tail1(c, s); }, [&] { return hs ? "dec_tail1_hs_kernel" : "dec_tail1_x3_kernel"; });
+                st = bracketed(op, e, N * d.H * d.W, 16, [&] { return launch_dec_tail1(c, s); }, label);
                 break;
             }
             case OP_SMALLN: {
@@ -531,6 +475,7 @@ static sd_status create_impl(sd_handle** out, int device, int H, int W, int max_
         delete h;
         return SD_ERR_INVALID;
     }
+    resolve_forms(h);
     carve_workspace(h);
     *out = h;
     return SD_OK;
@@ -1562,13 +1507,13 @@ sd_status sd_profile_read(sd_handle* h, sd_profile_bucket* out, int cap_buckets,
         HIPCHK(h, hipEventElapsedTime(&ms, r.a, r.b));
         if (verbose)
             std::fprintf(stderr, "[sd_profile] %-28s M=%-8d N=%-5d K=%-6d %8.3f ms %7.2f TF/s  %s\n", r.op, r.M, r.N, r.K, ms,
-                         r.flops / (ms * 1e-3) / 1e12, r.kernel);
+                         r.flops / (ms * 1e-3) / 1e12, r.kernel.c_str());
         int b = 0;
-        while (b < n && std::strcmp(out[b].kernel, r.kernel) != 0) ++b;
+        while (b < n && r.kernel != out[b].kernel) ++b;
         if (b == n) {
             if (n == cap_buckets) continue;
             std::memset(&out[n], 0, sizeof(out[n]));
-            std::strncpy(out[n].kernel, r.kernel, 63);
+            std::strncpy(out[n].kernel, r.kernel.c_str(), 63);
             ++n;
         }
         out[b].launches += 1;
@@ -1615,6 +1560,7 @@ sd_status sd_set_small_batch(sd_handle* h, int on) {
         h->cus = n;
     }
     h->small_batch = on < 0 ? 1 : on;       // (any other non-zero value has always meant "on")
+    resolve_forms(h);
     carve_workspace(h);
     return SD_OK;
 }
@@ -1645,13 +1591,25 @@ sd_status sd_small_batch_plan(const sd_handle* h, sd_net net, char* layers_out, 
     if (!h || !layers_out || !cap) return SD_ERR_INVALID;
     const NetPlan& p = plan_of(h, net);
     std::string out;
-    for (const OpDesc& op : p.ops) {
-        const int Sk = op_ksplit(h, p, op), S = Sk > 1 ? Sk : op_dsplit(h, p, op);
-        if (S > 1) out += (out.empty() ? "" : ",") + op.name + ":" + std::to_string(S);
-    }
+    for (size_t i = 0; i < p.ops.size(); ++i)
+        if (const int S = h->forms[net][i].slices; S > 1) out += (out.empty() ? "" : ",") + p.ops[i].name + ":" + std::to_string(S);
     std::strncpy(layers_out, out.c_str(), cap - 1);
     layers_out[cap - 1] = 0;
     return out.size() + 1 > cap ? SD_ERR_INVALID : SD_OK;
+}
+
+sd_status sd_conv_forms(const sd_handle* h, sd_net net, int frames, char* out, size_t cap) {
+    if (!h || !out || !cap || frames < 0 || frames > h->chunk) return SD_ERR_INVALID;
+    const NetPlan& p = plan_of(h, net);
+    std::string text;
+    for (size_t i = 0; i < p.ops.size(); ++i) {
+        ConvForm called;
+        const ConvForm& f = form_of(h, net, i, frames ? frames * (p.images / p.frames) : p.images, called);
+        if (f.family != CF_NONE || f.error) text += p.ops[i].name + " " + (f.error ? std::string(f.error) : f.verbose) + " " + std::to_string(f.slices) + "\n";
+    }
+    std::strncpy(out, text.c_str(), cap - 1);
+    out[cap - 1] = 0;
+    return text.size() + 1 > cap ? SD_ERR_INVALID : SD_OK;
 }
 
 sd_status sd_set_reserved_cus(sd_handle* h, int n) {

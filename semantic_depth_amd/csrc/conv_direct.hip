@@ -623,8 +623,9 @@ __global__ __launch_bounds__(512, (N16 && MT == 1) ? 2 : 1) void conv_direct_ker
     }
 }
 
-hipError_t launch_conv_direct(const ConvDirectParams& p, hipStream_t s) {
-    if ((p.act == ACT_SIGMOID03 || p.nreal) && (p.Cout > 16 || p.nsplit != 1 || p.pool || (p.sw & SW_NO_N16))) return hipErrorInvalidValue;
+// v: the tile shape the form resolved (conv_form.cpp) -- 64-channel passes, <= 32 channels, or the 16-wide MFMA form; up: source-resolution halo tiles
+hipError_t launch_conv_direct(const ConvDirectParams& p, DirectVariant v, hipStream_t s) {
+    if ((p.act == ACT_SIGMOID03 || p.nreal) && !v.n16) return hipErrorInvalidValue;
     if (p.out_fmt == PL_F16X2 && p.Cout <= 16 && p.nsplit == 1 && !p.pool) return hipErrorInvalidValue;      // (the 16-wide form writes PL_BF16X2 and PL_F16)
     if (p.W % D_TW || p.Cout > 64 || p.Cout % 8 || p.nsplit < 1 || p.nsplit > 8 || (p.nsplit > 1 && p.Cout != 64)) return hipErrorInvalidValue;
     static int cus = 0;
@@ -637,13 +638,10 @@ hipError_t launch_conv_direct(const ConvDirectParams& p, hipStream_t s) {
     ConvDirectParams q = p;
     if (p.pool && (p.rows_per_wave != 2 || (p.H & 1) || (p.W & 1))) return hipErrorInvalidValue;
     if (p.rows_per_wave != 2) return hipErrorInvalidValue;       // (8-row tiles of the 32/64-channel kernels were measured no better and are not built)
-    const int nb = p.Cout <= 32 ? 1 : 2;
-    const bool n16 = p.Cout <= 16 && p.nsplit == 1 && !p.pool && !(p.sw & SW_NO_N16);
     // N16 layers (full-resolution decoder tail: two chunks of little arithmetic per tile) are bound by the DMA latency of
     // a two-stage ring: 8-row tiles, 64 KiB of LDS, TWO workgroups per CU cover each other's waits
     // every source behind a x2 upsample: source-resolution halo tiles (48 KiB of LDS for N16 with 16-row tiles: they stay)
-    const bool up = p.all_up && !(p.H & 1) && !(p.W & 1);
-    const int th = n16 && !up ? 8 : 16;
+    const auto [nb, n16, up, th] = v;
     const int tiles = (int)conv_direct_items(p.W, p.H, p.N, p.nsplit, th);
     // persistent grid: as many workgroups as the instantiation keeps resident (1-3 per CU, by LDS and registers)
 #define SD_DIRECT_(NB_, MT_, F16_, N16_, UP_, W1_, X2_, ...) \
@@ -714,25 +712,6 @@ hipError_t launch_conv_direct_splitc(const ConvDirectParams& p, hipStream_t s) {
     const long slots = (long)(cus - p.reserve_cus > 0 ? cus - p.reserve_cus : 1) * per_cu;
     hipLaunchKernelGGL(kern, dim3((unsigned)(items < slots ? items : slots)), dim3(512), 0, s, p);
     return hipGetLastError();
-}
-
-// label of the instantiation family launch_conv_direct picks (profiling buckets): 64-channel passes, <= 32 channels, or the
-// 16-wide MFMA form
-const char* conv_direct_kernel_name(const ConvDirectParams& p) {
-    const bool n16 = p.Cout <= 16 && p.nsplit == 1 && !p.pool && !(p.sw & SW_NO_N16);
-    static const char* const names[4][3] = {
-        {"conv_direct_kernel<1,n16>", "conv_direct_kernel<1,2>", "conv_direct_kernel<2,2>"},
-        {"conv_direct_f16w_kernel<1,n16>", "conv_direct_f16w_kernel<1,2>", "conv_direct_f16w_kernel<2,2>"},
-        {"conv_direct_f16x1_kernel<1,n16>", "conv_direct_f16x1_kernel<1,2>", "conv_direct_f16x1_kernel<2,2>"},
-        {"conv_direct_hs_kernel<1,n16>", "conv_direct_hs_kernel<1,2>", "conv_direct_hs_kernel<2,2>"}};
-    const int shape = n16 ? 0 : p.Cout <= 32 ? 1 : 2;
-    switch (p.scheme) {
-        case SC_HS: return p.fold ? (p.Cout <= 32 ? "conv_direct_hs_fold_kernel<1>" : "conv_direct_hs_fold_kernel<2>") : names[3][shape];
-        case SC_F16XW: return "conv_direct_f16w_x2_kernel<2,2>";
-        case SC_F16X1: return names[2][shape];
-        case SC_F16W: return names[1][shape];
-        default: return names[0][shape];
-    }
 }
 
 }  // namespace sd

@@ -531,7 +531,7 @@ __global__ __launch_bounds__(512, 1) void conv_direct3_kernel(const ConvDirectPa
 #undef SD_PHASE
 }
 
-hipError_t launch_conv_direct3(const ConvDirectParams& p, hipStream_t s) {
+hipError_t launch_conv_direct3(const ConvDirectParams& p, DirectVariant v, hipStream_t s) {
     if (p.act == ACT_SIGMOID03 || p.nreal || p.out_planar16 || p.scheme != SC_BF16X3 || p.out_fmt != PL_BF16X3) return hipErrorInvalidValue;   // (heads run as small-N kernels)
     if (p.W % T3_TW || p.Cout > 64 || p.Cout % 8 || p.nsplit < 1 || p.nsplit > 8 || (p.nsplit > 1 && p.Cout != 64)) return hipErrorInvalidValue;
     if (p.pool && ((p.H & 1) || (p.W & 1))) return hipErrorInvalidValue;
@@ -542,13 +542,13 @@ hipError_t launch_conv_direct3(const ConvDirectParams& p, hipStream_t s) {
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidDevice;
         cus = prop.multiProcessorCount;
     }
-    const bool up = p.all_up && !(p.H & 1) && !(p.W & 1);
+    const bool up = v.up;
     const int tiles = (p.W / T3_TW) * ((p.H + T3_TH - 1) / T3_TH) * p.N * p.nsplit;
     const int wgs = cus - p.reserve_cus > 0 ? cus - p.reserve_cus : 1;
     const dim3 grid((unsigned)(tiles < wgs ? tiles : wgs));        // persistent: one workgroup per CU (158 KB of LDS)
     if (p.fold) {             // upsample-folded upconv layers: source-resolution tiles, two-slot ring, kept fragments
         if (!up || p.pool) return hipErrorInvalidValue;
-        if (p.Cout <= 32) hipLaunchKernelGGL((conv_direct3_kernel<1, true, 2, 2, true>), grid, dim3(512), 0, s, p);
+        if (v.nb == 1) hipLaunchKernelGGL((conv_direct3_kernel<1, true, 2, 2, true>), grid, dim3(512), 0, s, p);
         else hipLaunchKernelGGL((conv_direct3_kernel<2, true, 2, 2, true>), grid, dim3(512), 0, s, p);
         return hipGetLastError();
     }
@@ -556,15 +556,10 @@ hipError_t launch_conv_direct3(const ConvDirectParams& p, hipStream_t s) {
     // fragments: -1 %, profiles/r03d_conv_direct3_keep_ab.txt) and the three-slot ring of the NB = 1 layers (equal or 3-6 % slower,
     // profiles/r03g_conv_direct3_ring3_ab.txt); the kernel template keeps both forms, nothing launches them.
 #define SD_D3(NB_, UP_) hipLaunchKernelGGL((conv_direct3_kernel<NB_, UP_, 2, 2>), grid, dim3(512), 0, s, p)
-    if (p.Cout <= 32) { if (up) SD_D3(1, true); else SD_D3(1, false); }
+    if (v.nb == 1) { if (up) SD_D3(1, true); else SD_D3(1, false); }
     else { if (up) SD_D3(2, true); else SD_D3(2, false); }
 #undef SD_D3
     return hipGetLastError();
-}
-
-const char* conv_direct3_kernel_name(const ConvDirectParams& p) {
-    if (p.fold) return p.Cout <= 32 ? "conv_direct_x3_fold_kernel<1>" : "conv_direct_x3_fold_kernel<2>";
-    return p.Cout <= 32 ? "conv_direct_x3_kernel<1,2>" : "conv_direct_x3_kernel<2,2>";
 }
 
 }  // namespace sd

@@ -11,8 +11,9 @@ void launch_dma_v3(const ConvParams& p, long M, hipStream_t s);      // 256 x 64
 void launch_dma_v4(const ConvParams& p, long M, hipStream_t s);      // 256 x 32
 void launch_dma_v5(const ConvParams& p, long M, hipStream_t s);      // 256 x 256
 
+// the block shape 1..5 of a layer (0: not applicable).  Called by resolve_conv_form only; reads no pointer and nothing of the call
 int conv_dma_variant(const ConvParams& p) {
-    if (!p.vec || !p.zero16 || p.Cout % 32 || p.Kpad < 64) return 0;
+    if (!p.vec || p.Cout % 32 || p.Kpad < 64) return 0;
     // the block shape is chosen on a FULL pass of the engine (ConvParams::Nmax), not on the frames of this call: a call with fewer frames runs the same
     // kernels on fewer tiles, so a frame's result cannot depend on the call it is computed in even where two block shapes round differently (ADVICE r5 #3;
     // conv_dma3_eligible has counted this way since round 5)
@@ -34,37 +35,11 @@ int conv_dma_variant(const ConvParams& p) {
     return 0;
 }
 
-hipError_t launch_conv_dma(const ConvParams& p, hipStream_t s) {
-    const long M = (long)p.N * p.Hout * p.Wout;
-    const int v = conv_dma_variant(p);
-    if (v == 1) launch_dma_v1(p, M, s);
-    else if (v == 2) launch_dma_v2(p, M, s);
-    else if (v == 3) launch_dma_v3(p, M, s);
-    else if (v == 4) launch_dma_v4(p, M, s);
-    else if (v == 5 && p.scheme != SC_BF16X3) launch_dma_v5(p, M, s);
-    else return hipErrorInvalidValue;
+hipError_t launch_conv_dma(const ConvParams& p, int block, hipStream_t s) {
+    static void (*const launch[5])(const ConvParams&, long, hipStream_t) = {launch_dma_v1, launch_dma_v2, launch_dma_v3, launch_dma_v4, launch_dma_v5};
+    if (!p.zero16 || block < 1 || block > 5 || (block == 5 && p.scheme == SC_BF16X3)) return hipErrorInvalidValue;
+    launch[block - 1](p, (long)p.N * p.Hout * p.Wout, s);
     return hipGetLastError();
-}
-
-const char* conv_dma_kernel_name(const ConvParams& p) {
-    static const char* const names3[5] = {"conv_dma_x3_kernel<2,4,2,2>", "conv_dma_x3_kernel<4,2,2,2>", "conv_dma_x3_kernel<4,2,2,1>", "conv_dma_x3_kernel<8,1,1,1>",
-                                          "conv_dma_x3_kernel<2,4,2,2>"};
-    static const char* const names[3][5] = {
-        {"conv_dma_kernel<2,4,2,2>", "conv_dma_kernel<4,2,2,2>", "conv_dma_kernel<4,2,2,1>", "conv_dma_kernel<8,1,1,1>", "conv_dma_kernel<2,4,4,2>"},
-        {"conv_dma_f16w_kernel<2,4,2,2>", "conv_dma_f16w_kernel<4,2,2,2>", "conv_dma_f16w_kernel<4,2,2,1>", "conv_dma_f16w_kernel<8,1,1,1>",
-         "conv_dma_f16w_kernel<2,4,4,2>"},
-        {"conv_dma_f16x1_kernel<2,4,2,2>", "conv_dma_f16x1_kernel<4,2,2,2>", "conv_dma_f16x1_kernel<4,2,2,1>", "conv_dma_f16x1_kernel<8,1,1,1>",
-         "conv_dma_f16x1_kernel<2,4,4,2>"}};
-    static const char* const namesh[5] = {"conv_dma_hs_kernel<2,4,2,2>", "conv_dma_hs_kernel<4,2,2,2>", "conv_dma_hs_kernel<4,2,2,1>", "conv_dma_hs_kernel<8,1,1,1>",
-                                          "conv_dma_hs_kernel<2,4,4,2>"};
-    const int v = conv_dma_variant(p), i = v >= 1 && v <= 5 ? v - 1 : 2;
-    switch (p.scheme) {
-        case SC_BF16X3: return names3[i];
-        case SC_HS: return namesh[i];
-        case SC_F16X1: return names[2][i];
-        case SC_F16W: return names[1][i];
-        default: return names[0][i];
-    }
 }
 
 }  // namespace sd

@@ -641,15 +641,23 @@ __global__ __launch_bounds__(512, 1) void conv_splitk_hs_kernel(const ConvParams
     conv_dma3_body<MODE, true, S16, true>(p, M, tilesM, tilesN);
 }
 
-int conv_dma3_mode(const ConvParams& p);
-// layers the 256 x 256 phased block takes: bf16 x 3, all-vec K axis, Cout a multiple of 256 and enough blocks to occupy the chip
-bool conv_dma3_eligible(const ConvParams& p) {
-    if ((p.scheme != SC_BF16X3 && p.scheme != SC_HS) || !p.vec || !p.zero16 || p.pool || p.out_planar16 || p.residual || p.Cout % G3_BN || p.Kpad < 64 || p.CoutPad != p.Cout) return false;
+// what the 256 x 256 phased block can run: bf16 x 3 or HS, all-vec K axis, plain unpadded outputs with Cout a multiple of 256
+static bool dma3_valid(const ConvParams& p) {
+    return (p.scheme == SC_BF16X3 || p.scheme == SC_HS) && p.vec && !p.pool && !p.out_planar16 && p.Cout % G3_BN == 0 && p.Kpad >= 64 && p.CoutPad == p.Cout;
+}
+
+// gather variant a layer runs: 1 = 1x1 layers (one offset per source geometry), 2 = tap layers without upsample (fc6, the folded upconvs, strided
+// 3x3: precomputed pixel offset + scalar tap offset), 0 = the general gather.  Called by resolve_conv_form only
+int conv_dma3_mode(const ConvParams& p) { return (p.flat && !p.fold && !p.rowgrp) ? 1 : p.noup ? 2 : 0; }
+
+// layers the phased block takes (resolve_conv_form only): what it can run, without a residual, and enough blocks to occupy the chip
+bool conv_dma3_eligible(const ConvParams& p, int mode, bool residual) {
+    if (!dma3_valid(p) || residual) return false;
     // SD_PREC_F16X2: measured against the two-stage block of conv_dma.hip (profiles/r05_hs_phased_gemm_ab.txt), the two-phase ring wins on the 1x1 layers (fc7
     // 1.50 -> 1.29 ms, the res2 / res5 block tails 3-12 %) and -- since a piece's address arithmetic is formed once per k-tile -- on the row-grouped fc6
     // (6.93 -> 6.50 ms: it also skips the taps on padding rows), and loses on the small strided 3x3 of res4_6 (0.135 -> 0.178): the 1x1 layers and fc6 only
     // (the rule must not look at the call: the k x k stride-1 single-source layers -- fc6 --, row-grouped or not)
-    if (p.scheme == SC_HS && conv_dma3_mode(p) != 1 && !(p.kh >= 3 && p.stride == 1 && !p.fold && p.noup)) return false;
+    if (p.scheme == SC_HS && mode != 1 && !(p.kh >= 3 && p.stride == 1 && !p.fold && p.noup)) return false;
     if (p.fold) return true;                                   // (a folded layer always runs here when it can: its results must not depend on the batch)
     if (p.sw & SW_NO_DMA3) return false;                       // (A/B switch of the handle)
     // enough tiles to occupy the chip -- counted on a FULL pass of the engine (ConvParams::Nmax), not on the frames of this call: this block and conv_dma.hip's
@@ -658,18 +666,6 @@ bool conv_dma3_eligible(const ConvParams& p) {
     // scripts/batch_independence_full_size.py)
     const long M = (long)(p.Nmax > 0 ? p.Nmax : p.N) * p.Hout * p.Wout;
     return ((M + G3_BM - 1) / G3_BM) * (p.Cout / G3_BN) >= 128;
-}
-
-// gather variant a layer runs: 1 = 1x1 layers (one offset per source geometry), 2 = tap layers without upsample (fc6, the folded upconvs, strided
-// 3x3: precomputed pixel offset + scalar tap offset), 0 = the general gather
-int conv_dma3_mode(const ConvParams& p) { return (p.flat && !p.fold && !p.rowgrp) ? 1 : p.noup ? 2 : 0; }
-
-// one bucket per form for the bench line; the per-layer listing of SEMDEPTH_PROFILE_VERBOSE names the gather variant
-const char* conv_dma3_kernel_name(const ConvParams& p) {
-    static const char* const x3[3] = {"conv_dma3_kernel<0>", "conv_dma3_kernel<1>", "conv_dma3_kernel<2>"};
-    static const char* const hs[3] = {"conv_dma_hs_phased_kernel<0>", "conv_dma_hs_phased_kernel<1>", "conv_dma_hs_phased_kernel<2>"};
-    if (p.sw & SW_PROFILE_VERBOSE) return (p.scheme == SC_HS ? hs : x3)[conv_dma3_mode(p)];
-    return p.scheme == SC_HS ? "conv_dma_hs_phased_kernel" : "conv_dma3_kernel";
 }
 
 // Split-K (sd_set_small_batch).  The rule reads what a handle fixes and nothing of a call: the rows of a FULL pass, the layer's shape, the CU count.
@@ -688,40 +684,21 @@ int conv_splitk_slices(long rows, int cout, int kpad, int cus) {
     return S < 4 ? 1 : (int)S;         // (measured: the layers the caps left at S = 2 or 3 lost to their unsplit launch)
 }
 
-const char* conv_splitk_kernel_name(const ConvParams& p) {
-    if (p.sw & SW_PROFILE_VERBOSE) return conv_dma3_mode(p) == 1 ? "conv_splitk_hs_kernel<1>" : "conv_splitk_hs_kernel<2>";
-    return "conv_splitk_hs_kernel";
-}
-
-// the GEMM half of a split layer: partial[s] = the accumulators of slice s (splitk_reduce.hip adds them up and applies the epilogue)
-hipError_t launch_conv_splitk(const ConvParams& p, hipStream_t s) {
-    const int mode = conv_dma3_mode(p);
-    if (p.scheme != SC_HS || !p.vec || !p.zero16 || p.pool || p.out_planar16 || p.residual || p.fold || p.rowgrp || p.Cout % G3_BN || p.CoutPad != p.Cout ||
-        (mode != 1 && mode != 2) || !p.partial || p.ksplit < 2 || p.ksplit > 16 || (p.Kpad / 32) / p.ksplit < 8)
-        return hipErrorInvalidValue;
+// mode, s16: the gather and the MFMA shape the form resolved -- 16x16x32 for every bf16 x 3 layer and the three-product engine's 1x1 layers (-1.9 % on them; its
+// fc6 is 2 % faster on 32x32x16: r05_mfma16_ab.txt); SEMDEPTH_MFMA32: the 32x32x16 form everywhere (same-box A/B)
+hipError_t launch_conv_dma3(const ConvParams& p, int mode, bool s16, hipStream_t s) {
+    if (!dma3_valid(p) || !p.zero16 || p.residual || mode < 0 || mode > 2 || (s16 && p.scheme == SC_HS && mode != 1)) return hipErrorInvalidValue;
     const long M = (long)p.N * p.Hout * p.Wout;
     const int tilesM = (int)((M + G3_BM - 1) / G3_BM), tilesN = p.Cout / G3_BN;
-    const dim3 grid((unsigned)(tilesM * tilesN), (unsigned)p.ksplit);
-    // (the forms of the unsplit HS layers: 16x16x32 MFMAs for the 1x1 layers, 32x32x16 for the tap layers)
-    const bool s16 = !(p.sw & SW_MFMA32);
-    if (mode == 1) {
-        if (s16) hipLaunchKernelGGL((conv_splitk_hs_kernel<1, true>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN);
-        else hipLaunchKernelGGL((conv_splitk_hs_kernel<1, false>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN);
-    } else {
-        hipLaunchKernelGGL((conv_splitk_hs_kernel<2, false>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN);
+    if (p.ksplit) {     // the GEMM half of a split layer: partial[s] = the accumulators of slice s (splitk_reduce.hip adds them up and applies the epilogue)
+        if (p.scheme != SC_HS || p.fold || p.rowgrp || mode == 0 || !p.partial || p.ksplit < 2 || p.ksplit > 16 || (p.Kpad / 32) / p.ksplit < 8) return hipErrorInvalidValue;
+        const dim3 grid((unsigned)(tilesM * tilesN), (unsigned)p.ksplit);
+        if (mode == 1 && s16) hipLaunchKernelGGL((conv_splitk_hs_kernel<1, true>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN);
+        else if (mode == 1) hipLaunchKernelGGL((conv_splitk_hs_kernel<1, false>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN);
+        else hipLaunchKernelGGL((conv_splitk_hs_kernel<2, false>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN);
+        return hipGetLastError();
     }
-    return hipGetLastError();
-}
-
-hipError_t launch_conv_dma3(const ConvParams& p, hipStream_t s) {
-    if (!conv_dma3_eligible(p)) return hipErrorInvalidValue;
-    const long M = (long)p.N * p.Hout * p.Wout;
-    const int tilesM = (int)((M + G3_BM - 1) / G3_BM), tilesN = p.Cout / G3_BN;
     const dim3 grid((unsigned)(tilesM * tilesN * (p.fold ? 4 : 1)));
-    const int mode = conv_dma3_mode(p);
-    // the 16x16x32 form: every bf16 x 3 layer and the three-product engine's 1x1 layers (-1.9 % on them; its fc6 is 2 % faster on 32x32x16: r05_mfma16_ab.txt).
-    // SEMDEPTH_MFMA32: the 32x32x16 form everywhere (same-box A/B)
-    const bool s16 = !(p.sw & SW_MFMA32);
 #define SD_G3(MODE_, HS_) do { if (s16) hipLaunchKernelGGL((conv_dma3_kernel<MODE_, HS_, !(HS_) || (MODE_) == 1>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN); \
                                 else hipLaunchKernelGGL((conv_dma3_kernel<MODE_, HS_, false>), grid, dim3(512), 0, s, p, (int)M, tilesM, tilesN); } while (0)
 #define SD_G3_MODE(HS_) do { if (mode == 1) SD_G3(1, HS_); else if (mode == 2) SD_G3(2, HS_); else SD_G3(0, HS_); } while (0)

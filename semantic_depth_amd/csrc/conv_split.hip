@@ -383,9 +383,10 @@ int conv_split_tile_n(int Cout) {
 }
 
 // big tiles (8 waves) when there are enough of them to fill the chip: a 128x256 / 256x128 tile moves 25 % fewer bytes
-// from L2 per flop than 128x128 and halves the per-thread staging work on the wider side
-static int split_variant(const ConvParams& p) {
-    const long M = (long)p.N * p.Hout * p.Wout;
+// from L2 per flop than 128x128 and halves the per-thread staging work on the wider side.  Called by resolve_conv_form only.
+// CALL-DEPENDENT: the 512-tile threshold counts the pixels of the call (`images`), not of a full pass
+int conv_split_variant(const ConvParams& p, int images) {
+    const long M = (long)images * p.Hout * p.Wout;
     const int tn = conv_split_tile_n(p.Cout);
     if (tn == 128) {
         if (p.Cout % 256 == 0 && ((M + 127) / 128) * (p.Cout / 256) >= 512) return 0;    // 128 x 256
@@ -394,32 +395,13 @@ static int split_variant(const ConvParams& p) {
     return tn == 64 ? 3 : 4;
 }
 
-hipError_t launch_conv_split(const ConvParams& p, hipStream_t s) {
-    switch (split_variant(p)) {
+hipError_t launch_conv_split(const ConvParams& p, int tile, hipStream_t s) {
+    switch (tile) {
         case 0:  return launch_scfg<2, 4, 2, 2>(p, s);   // 128 x 256, 8 waves
         case 1:  return launch_scfg<4, 2, 2, 2>(p, s);   // 256 x 128, 8 waves
         case 2:  return launch_scfg<2, 2, 2, 2>(p, s);   // 128 x 128
         case 3:  return launch_scfg<4, 1, 2, 2>(p, s);   // 256 x 64
         default: return launch_scfg<4, 1, 2, 1>(p, s);   // 256 x 32 (Cout = 16 is padded to 32)
-    }
-}
-
-const char* conv_split_kernel_name(const ConvParams& p) {
-    static const char* const x3[5] = {"conv_split_x3_kernel<2,4,2,2>", "conv_split_x3_kernel<4,2,2,2>", "conv_split_x3_kernel<2,2,2,2>",
-                                      "conv_split_x3_kernel<4,1,2,2>", "conv_split_x3_kernel<4,1,2,1>"};
-    static const char* const f16w[5] = {"conv_split_f16w_kernel<2,4,2,2>", "conv_split_f16w_kernel<4,2,2,2>", "conv_split_f16w_kernel<2,2,2,2>",
-                                        "conv_split_f16w_kernel<4,1,2,2>", "conv_split_f16w_kernel<4,1,2,1>"};
-    static const char* const bf16[2][5] = {
-        {"conv_split_kernel<2,4,2,2,false>", "conv_split_kernel<4,2,2,2,false>", "conv_split_kernel<2,2,2,2,false>", "conv_split_kernel<4,1,2,2,false>",
-         "conv_split_kernel<4,1,2,1,false>"},
-        {"conv_split_kernel<2,4,2,2,true>", "conv_split_kernel<4,2,2,2,true>", "conv_split_kernel<2,2,2,2,true>", "conv_split_kernel<4,1,2,2,true>",
-         "conv_split_kernel<4,1,2,1,true>"}};
-    const int v = split_variant(p);
-    switch (p.scheme) {
-        case SC_BF16X3: return x3[v];
-        case SC_HS: return "conv_split_hs_kernel";
-        case SC_F16W: case SC_F16X1: return f16w[v];
-        default: return bf16[p.vec ? 1 : 0][v];
     }
 }
 

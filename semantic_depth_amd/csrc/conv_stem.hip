@@ -233,29 +233,23 @@ __global__ __launch_bounds__(512, 1) void conv_stem_kernel(const ConvParams p) {
     }
 }
 
-// eligible: split engine, one 4-channel source without upsample, odd k <= 7, stride 1 or 2, Cout 32 or 64 unpadded
-bool conv_stem_eligible(const ConvParams& p) {
-    if (!p.src0 || p.nsrc != 1 || p.Ctot != 4 || p.kh != p.kw || !(p.kh & 1) || p.kh > 7 || (p.stride != 1 && p.stride != 2)) return false;
-    if ((p.Cout != 32 && p.Cout != 64) || p.CoutPad != p.Cout || p.Wout % ST_TW || p.residual || p.pool) return false;
+// what the kernel can run: one 4-channel source without upsample, odd k <= 7, stride 1 or 2, Cout 32 or 64 unpadded, no fused pool, tiles within the LDS budget
+static bool stem_valid(const ConvParams& p) {
+    if (p.nsrc != 1 || p.Ctot != 4 || p.kh != p.kw || !(p.kh & 1) || p.kh > 7 || (p.stride != 1 && p.stride != 2)) return false;
+    if ((p.Cout != 32 && p.Cout != 64) || p.CoutPad != p.Cout || p.Wout % ST_TW || p.pool) return false;
     if (p.out_planar16 && p.Cout % 16) return false;
     const int rw = p.stride == 1 ? 2 : 1, th = 8 * rw;
     const int ih = (th - 1) * p.stride + p.kh, iw = (ST_TW - 1) * p.stride + p.kh;
     const int npl = p.scheme == SC_BF16X3 ? 3 : 2, nb = p.Cout / 32;
     const size_t lds = (size_t)npl * ST_MAXPIX * 8 + (size_t)(p.Kpad / 8) * p.Cout * 16 * npl + (size_t)8 * 32 * (64 * nb + 16);
-    return ih * iw <= ST_MAXPIX && lds + 512 <= 160 * 1024 && (p.kh * p.kw * 4 + 15) / 16 <= 32 && !(p.sw & SW_NO_STEM);      // (+ the tap table)
+    return ih * iw <= ST_MAXPIX && lds + 512 <= 160 * 1024 && (p.kh * p.kw * 4 + 15) / 16 <= 32;      // (+ the tap table)
 }
 
-const char* conv_stem_kernel_name(const ConvParams& p) {
-    switch (p.scheme) {
-        case SC_BF16X3: return "conv_stem_x3_kernel";
-        case SC_HS: return "conv_stem_hs_kernel";
-        case SC_F16W: case SC_F16X1: return "conv_stem_f16w_kernel";
-        default: return "conv_stem_kernel";
-    }
-}
+// eligible (resolve_conv_form only): what the kernel can run, without a residual, unless SEMDEPTH_DISABLE=stem
+bool conv_stem_eligible(const ConvParams& p, bool residual) { return stem_valid(p) && !residual && !(p.sw & SW_NO_STEM); }
 
 hipError_t launch_conv_stem(const ConvParams& p, hipStream_t s) {
-    if (!conv_stem_eligible(p)) return hipErrorInvalidValue;
+    if (!stem_valid(p) || !p.src0 || p.residual) return hipErrorInvalidValue;
     static int cus = 0;
     if (!cus) {
         int dev = 0;
@@ -267,8 +261,7 @@ hipError_t launch_conv_stem(const ConvParams& p, hipStream_t s) {
     const int tiles = (p.Wout / ST_TW) * ((p.Hout + 8 * rw - 1) / (8 * rw)) * p.N;
     const int npl = p.scheme == SC_BF16X3 ? 3 : 2;
     const size_t wbytes = (size_t)(p.Kpad / 8) * p.Cout * 16 * npl;
-    const size_t lds = (size_t)npl * ST_MAXPIX * 8 + wbytes + (size_t)8 * 32 * (64 * nb + 16);
-    if (lds + 512 > 160 * 1024) return hipErrorInvalidValue;
+    const size_t lds = (size_t)npl * ST_MAXPIX * 8 + wbytes + (size_t)8 * 32 * (64 * nb + 16);       // (stem_valid: within the budget)
     const int wgs = cus - p.reserve_cus > 0 ? cus - p.reserve_cus : 1;
     const dim3 grid((unsigned)(tiles < wgs ? tiles : wgs));
 #define SD_STEM(NB_, RW_, F_, ...)                                                                                     \

@@ -118,27 +118,22 @@ __host__ __device__ inline void conv_splitk_range(int kt, int S, int s, int& fir
     first = s * base + (s < rem ? s : rem);
     count = base + (s < rem ? 1 : 0);
 }
+// Which of these a layer takes is resolved once per handle (conv_form.hpp): the rules are called by resolve_conv_form only, a launcher is handed its variant.
 int conv_splitk_slices(long rows, int cout, int kpad, int cus);      // conv_dma3.hip: the rule (1 = not split)
-hipError_t launch_conv_splitk(const ConvParams& p, hipStream_t s);   // conv_dma3.hip: the k-range form of the HS ring -> ConvParams::partial
-const char* conv_splitk_kernel_name(const ConvParams& p);
 hipError_t launch_splitk_reduce(const ConvParams& p, hipStream_t s); // splitk_reduce.hip: sum of the slices + the HS epilogue
 hipError_t launch_conv_igemm(const ConvParams& p, hipStream_t s);
-const char* conv_igemm_kernel_name(const ConvParams& p);
 // split-bf16 engine (conv_split.hip): wt = two bf16 planes [Kpad/8][CoutPad][8] (hi, then lo)
-hipError_t launch_conv_split(const ConvParams& p, hipStream_t s);
-const char* conv_split_kernel_name(const ConvParams& p);
 int conv_split_tile_n(int Cout);
-// LDS-DMA pipeline for the wide vec layers of the split engine (conv_dma.hip); variant 0 = not applicable
+int conv_split_variant(const ConvParams& p, int images);             // tile 0..4 for the pixel count of a CALL of `images` images
+hipError_t launch_conv_split(const ConvParams& p, int tile, hipStream_t s);
+// LDS-DMA pipeline for the wide vec layers of the split engine (conv_dma.hip); block 0 = not applicable
 int conv_dma_variant(const ConvParams& p);
-hipError_t launch_conv_dma(const ConvParams& p, hipStream_t s);
-bool conv_stem_eligible(const ConvParams& p);                        // conv_stem.hip: layers on the 4-channel network input
+hipError_t launch_conv_dma(const ConvParams& p, int block, hipStream_t s);
+bool conv_stem_eligible(const ConvParams& p, bool residual);         // conv_stem.hip: layers on the 4-channel network input
 hipError_t launch_conv_stem(const ConvParams& p, hipStream_t s);
-const char* conv_stem_kernel_name(const ConvParams& p);
-const char* conv_dma_kernel_name(const ConvParams& p);
-bool conv_dma3_eligible(const ConvParams& p);                        // conv_dma3.hip: bf16 x 3, 256 x 256 block with phased weight planes
-hipError_t launch_conv_dma3(const ConvParams& p, hipStream_t s);
-int conv_dma3_mode(const ConvParams& p);                             // gather variant (conv_dma3_kernel<MODE>) the layer runs
-const char* conv_dma3_kernel_name(const ConvParams& p);
+int conv_dma3_mode(const ConvParams& p);                             // conv_dma3.hip (bf16 x 3 / HS, 256 x 256 block, phased weight planes): the gather variant
+bool conv_dma3_eligible(const ConvParams& p, int mode, bool residual);
+hipError_t launch_conv_dma3(const ConvParams& p, int mode, bool s16, hipStream_t s);     // s16: 16x16x32 MFMAs; ConvParams::ksplit: the k-range form of the HS ring -> partial
 
 #ifdef __HIPCC__
 // ELU for the conv epilogues.  expm1f() is a ~60-instruction library routine and the monodepth layers apply it to every
@@ -241,15 +236,15 @@ struct ConvDirectParams {
     int csplit;                  // > 1 (sd_set_small_batch level 2; conv_direct_splitc_hs_kernel + splitc_reduce_kernel): slices of the chunk axis (conv_splitk_range over nchunks)
     float* partial;              // chunk split: f32 partial sums [csplit][N * H * W][Cstride] at conv (pre-pool) resolution in the workspace
 };
+// tile shape of a direct launch (conv_form.cpp): passes of <= 32 (nb 1) or 64 (nb 2) channels, the 16-wide MFMA form, source-resolution halo tiles, tile rows
+struct DirectVariant { int nb; bool n16, up; int th; };
 // work items of a direct launch: (32-pixel-wide tile of th rows) x (pass of <= 64 output channels).  The launcher's grid and the chunk-split rule both count with it
 inline long conv_direct_items(int W, int H, int images, int nsplit, int th = 16) { return (long)(W / 32) * ((H + th - 1) / th) * images * nsplit; }
 int conv_splitc_slices(long items, int nchunks, int cus);               // conv_direct.hip: the rule of the chunk split (1 = not split)
 hipError_t launch_conv_direct_splitc(const ConvDirectParams& p, hipStream_t s);   // conv_direct.hip: the chunk-range form of the 64-channel-pass HS kernel -> ConvDirectParams::partial
 hipError_t launch_splitc_reduce(const ConvDirectParams& p, hipStream_t s);        // splitk_reduce.hip: sum of the slices + the direct kernel's HS epilogue (incl. the fused pool)
-hipError_t launch_conv_direct3(const ConvDirectParams& p, hipStream_t s);       // conv_direct3.hip: the bf16 x 3 form (SD_PREC_BF16X3)
-const char* conv_direct3_kernel_name(const ConvDirectParams& p);
-hipError_t launch_conv_direct(const ConvDirectParams& p, hipStream_t s);
-const char* conv_direct_kernel_name(const ConvDirectParams& p);
+hipError_t launch_conv_direct3(const ConvDirectParams& p, DirectVariant v, hipStream_t s);       // conv_direct3.hip: the bf16 x 3 form (SD_PREC_BF16X3)
+hipError_t launch_conv_direct(const ConvDirectParams& p, DirectVariant v, hipStream_t s);
 
 // the full-resolution decoder tail of the bf16 x 3 monodepth in one launch (dec_tail.hip): upconv1 -> iconv1 -> disp1[..., 0]
 struct DecTailParams {

@@ -1142,6 +1142,11 @@ class Engine:
             out[name] = {k: int(v) for k, v in (s.rsplit(":", 1) for s in buf.value.decode().split(",") if s)}
         return out
 
+    def conv_forms(self, net, frames=None) -> dict:
+        """{conv layer: (kernel label, slices)} of ``net`` (L.SD_NET_*) in a call of ``frames`` frames (None: a full pass), in launch order: what the
+        handle resolved, read without a device.  The label is the per-layer profile label; slices > 1 means the layer's reduce launch follows."""
+        return L.conv_forms(self.lib, self.h, net, frames or 0)
+
     def saturation_count(self, reset: bool = False) -> int:
         """values the fp16 output formats of the reduced-precision plans had to clamp at +-65504 (or that were NaN) since the arenas were
         bound / the last reset (synchronises).  Non-zero = the plan does not fit these weights: use more products or precision='f32'."""
