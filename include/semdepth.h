@@ -26,7 +26,8 @@
  *   sd_monodepth_forward that wrote the pair and BEFORE the next sd_monodepth_forward (an event each way).  Tensors the caller owns
  *   (masks, frames, clouds, records) are the caller's to order.  Every other call (sd_resize_cubic_u8 aside, which touches only
  *   o_rsz) belongs on the stream of its family, or behind a synchronisation.
- *   The workspace regions (carve_workspace in capi.cpp) and the call families that touch them -- net = network calls, tail = tail calls:
+ *   The workspace regions (struct Arena in csrc/handle_arena.hpp: o_x is its field x, o_misc its fields scalar, zero, f2f_counts, f2f_planes and
+ *   sat) and the call families that touch them -- net = network calls, tail = tail calls:
  *     o_fcn       FCN-8s activations                          net (sd_fcn8s_forward) reads + writes; sd_net_tensor reads
  *     o_mono      monodepth activations                       net (sd_monodepth_forward) reads + writes; sd_net_tensor reads
  *       raw pair  the plan's output tensor inside o_mono      net (sd_monodepth_forward) writes; tail (fusion from the arena) reads

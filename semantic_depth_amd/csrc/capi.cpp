@@ -29,6 +29,7 @@
 #include "kernels.hpp"
 #include "plan.hpp"
 #include "conv_form.hpp"
+#include "handle_arena.hpp"
 
 using namespace sd;
 
@@ -45,18 +46,15 @@ struct sd_handle {
     char* wf = nullptr;   // FCN weight arena
     char* wm = nullptr;   // monodepth weight arena
     char* ws = nullptr;   // workspace arena
-    // workspace carve (byte offsets)
-    size_t o_fcn = 0, o_mono = 0, o_fuse = 0, o_fuse1 = 0, o_cams = 0, o_bufA = 0, o_bufB = 0, o_rgbA = 0, o_rgbB = 0, o_cnt = 0, o_plane = 0, o_o3d = 0, o_misc = 0, o_rsz = 0, o_cmp = 0, o_rsz_cmp = 0;
+    Arena a{};            // where everything lives in it (handle_arena.hpp)
     std::vector<int> rsz_host;      // tap tables of the last sd_resize_cubic_u8 geometry (kept alive for the async upload)
     int rsz_key[4] = {0, 0, 0, 0};
     std::vector<int> cmp_rsz_host;  // the same for sd_compose_result_frames (own slot: the input resize and the output compose alternate
     int cmp_rsz_key[4] = {0, 0, 0, 0};   //  every batch with different geometries, and a shared slot would re-upload and synchronise each time)
-    size_t ws_bytes = 0;
     int last_fcn_images = 0, last_mono_images = 0;
     int reserve_cus = 0;            // sd_set_reserved_cus: CUs the persistent conv launches leave free
     int small_batch = 0, cus = 0;   // sd_set_small_batch: the split-K forms of the under-filled GEMM layers; the CU count its rule reads (latched with it)
     std::vector<ConvForm> forms[2];   // [sd_net], per op of the plan: the kernel form of a full pass (resolve_forms; default records for the other ops)
-    size_t o_splitk = 0;            // workspace: the partial sums of the largest split layer (0 bytes without the switch)
     std::vector<CamDev> cams_stage;
     std::vector<CamDev> sweep_stage;     // sd_fuse_backproject_sweep: the [T][B] records of the last call (source of its upload)
     std::vector<OverlayCamDev> overlay_stage;    // sd_overlay_draw: the cameras of the last call (source of its upload)
@@ -79,10 +77,6 @@ struct sd_handle {
 };
 
 namespace {
-
-size_t al(size_t v) { return (v + 255) / 256 * 256; }
-size_t sat_bytes(int max_batch) { return al(sizeof(uint64_t) + (size_t)(3 * max_batch + SAT_IMG_PAD + 1) * sizeof(uint32_t)); }
-constexpr int RSZ_MAX = 16384;     // largest destination extent of sd_resize_cubic_u8
 
 sd_status fail(sd_handle* h, sd_status code, const std::string& msg) {
     if (h) h->err = msg;
@@ -129,33 +123,17 @@ size_t splitk_scratch_bytes(const sd_handle* h) {
 }
 
 void carve_workspace(sd_handle* h) {
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t r = off; off += al(bytes); return r; };
-    const size_t B = (size_t)h->max_batch, cap = (size_t)h->cap;
-    h->o_fcn = take(h->fcn.act_bytes);
-    h->o_mono = take(h->mono.act_bytes);
-    h->o_fuse = take(fuse_scratch_bytes(h->max_batch, h->H, h->W));
-    h->o_fuse1 = take(fuse_onepass_scratch_bytes(h->max_batch, h->H, h->W));
-    h->o_cams = take(sizeof(CamDev) * B);
-    h->o_bufA = take(B * cap * 3 * sizeof(float));
-    h->o_bufB = take(B * cap * 3 * sizeof(float));
-    h->o_rgbA = take(B * cap * 3);            // colours travel with the points through every filter (semantic_depth.py:206-245)
-    h->o_rgbB = take(B * cap * 3);
-    h->o_cnt = take(B * sizeof(int32_t) * 24);
-    h->o_plane = take(B * sizeof(double) * 4);
-    h->o_o3d = take(o3d_scratch_bytes(h->max_batch, h->cap));
-    h->o_misc = take(4096 + al(B * 7 * sizeof(int32_t)) + al(B * 12 * sizeof(double)) + sat_bytes(h->max_batch));   // scalars | f2f counts | f2f planes | clamp counters
-    h->o_cmp = take(cmp_scratch_bytes(h->max_batch));
-    h->o_rsz = take((size_t)RSZ_MAX * 16 * sizeof(int));          // resize tap tables: [RSZ_MAX][4] x idx | x weight | y idx | y weight
-    h->o_rsz_cmp = take((size_t)RSZ_MAX * 16 * sizeof(int));      // the same layout for sd_compose_result_frames
-    h->o_splitk = take(splitk_scratch_bytes(h));                  // (last: the other offsets do not depend on the switch)
-    h->ws_bytes = off;
+    h->a = Arena({h->max_batch, h->H, h->W, h->cap, h->fcn.act_bytes, h->mono.act_bytes, splitk_scratch_bytes(h)});
 }
+// the arena's regions as pointers: the only places that add to h->ws
+template <class T = char> T* at(sd_handle* h, size_t off) { return reinterpret_cast<T*>(h->ws + off); }
+char* act_base(sd_handle* h, sd_net net) { return at(h, net == SD_NET_FCN8S ? h->a.fcn : h->a.mono); }
+void* zero_page(sd_handle* h) { return at(h, h->a.zero); }      // the arena is zero-filled there and nothing writes it
 
 sd_status upload_tables(sd_handle* h, sd_net net) {
     NetPlan& p = plan_of(h, net);
     char* wbase = warena(h, net);
-    const char* abase = h->ws + (net == SD_NET_FCN8S ? h->o_fcn : h->o_mono);
+    const char* abase = act_base(h, net);
     for (const OpDesc& op : p.ops) {
         if (op.kind == OP_CONV_DIRECT) {
             std::vector<DirectChunk> chunks;
@@ -183,23 +161,19 @@ static hipEvent_t prof_event(sd_handle* h) {
     return h->prof_pool[h->prof_used++];
 }
 
-// one chunk through a plan.  frames: u8 [nframes,H,W,3] (device)
-// the fp16 clamp counters at the end of the o_misc scratch: the 64-bit global count (sd_saturation_count), then its per-image uint32
-// slots for one pass (split_fmt.hpp sat_check: 2 images per frame at most + SAT_IMG_PAD), then the per-frame counts (sd_saturation_frames),
-// then the count of the clamps no frame owns (rows of a partial last GEMM tile: zero-padded rows that write nothing; sd_saturation_settle)
-unsigned long long* sat_counter(sd_handle* h) {
-    const size_t B = (size_t)h->max_batch;
-    return reinterpret_cast<unsigned long long*>(h->ws + h->o_misc + 4096 + al(B * 7 * sizeof(int32_t)) + al(B * 12 * sizeof(double)));
-}
-int sat_img_slots(sd_handle* h) { return 2 * h->max_batch + SAT_IMG_PAD; }
-unsigned* sat_frames(sd_handle* h) { return reinterpret_cast<unsigned*>(sat_counter(h) + 1) + sat_img_slots(h); }
-unsigned* sat_orphans(sd_handle* h) { return sat_frames(h) + h->max_batch; }
+// the fp16 clamp counters (SatLayout, handle_arena.hpp)
+size_t sat_bytes(int max_batch) { return SatLayout(max_batch).total; }
+unsigned long long* sat_counter(sd_handle* h) { return at<unsigned long long>(h, h->a.sat + SatLayout(h->max_batch).count); }
+unsigned* sat_img(sd_handle* h) { return at<unsigned>(h, h->a.sat + SatLayout(h->max_batch).img); }
+int sat_img_slots(sd_handle* h) { return (int)SatLayout(h->max_batch).img_slots; }
+unsigned* sat_frames(sd_handle* h) { return at<unsigned>(h, h->a.sat + SatLayout(h->max_batch).frames); }
+unsigned* sat_orphans(sd_handle* h) { return at<unsigned>(h, h->a.sat + SatLayout(h->max_batch).orphans); }
 
 // one chunk through a plan.  frames: u8 [nframes,H,W,3] (device), frames frame0.. of the caller's batch
 sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, int nframes, const HeadOut* head, hipStream_t s) {
     NetPlan& p = plan_of(h, net);
     char* wbase = warena(h, net);
-    char* abase = h->ws + (net == SD_NET_FCN8S ? h->o_fcn : h->o_mono);
+    char* abase = act_base(h, net);
     const int N = nframes * (p.images / p.frames);
     auto T = [&](int t) -> float* { return reinterpret_cast<float*>(abase + p.tensors[t].offset); };
     auto Wp = [&](int w) -> const float* { return reinterpret_cast<const float*>(wbase + p.weights[w].offset); };
@@ -253,14 +227,14 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, 
                 c.N = N; c.wt = Wp(op.w); c.bias = Wp(op.b); c.ktab = reinterpret_cast<const KEntry*>(wbase + op.tab_offset);
                 c.residual = op.residual >= 0 ? T(op.residual) : nullptr;
                 c.out = T(op.dst); c.out_plane = PL(op.dst); c.src0 = T(op.src[0]); c.src0_plane = PL(op.src[0]);
-                c.zero16 = h->ws + h->o_misc + 256;        // the arena is zero-filled and nothing writes here
+                c.zero16 = zero_page(h);
                 c.alpha = op.scheme == SC_HS ? 1.f / p.weights[op.w].wscale : 1.f;
                 c.reserve_cus = h->reserve_cus; c.sat = sat_counter(h);
                 c.rowgrp = f.rowgrp && N % f.rowgrp == 0 ? f.rowgrp : 0;      // CALL-DEPENDENT (conv_form.cpp): row groups only when the call's images fill them
                 const int M = N * c.Hout * c.Wout * (c.fold ? 4 : 1);
                 if (f.family == CF_SPLITK) {
                     // sd_set_small_batch: the k-range form of the HS ring into the partial-sum scratch, then the reduce launch with the layer's epilogue
-                    c.partial = reinterpret_cast<float*>(h->ws + h->o_splitk);
+                    c.partial = at<float>(h, h->a.splitk);
                     st = bracketed(op, e, M, d.C, [&] { return launch_conv_dma3(c, f.variant, f.s16, s); }, label);
                     if (st != SD_OK || e != hipSuccess) break;
                     st = bracketed(op, e, M, d.C, [&] { return launch_splitk_reduce(c, s); }, "splitk_reduce_kernel",
@@ -284,12 +258,12 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, 
                 ConvDirectParams c = f.dir;
                 c.N = N; c.chunks = reinterpret_cast<const DirectChunk*>(wbase + op.tab_offset);
                 c.wt = reinterpret_cast<const u32x4_t*>(Wp(op.w)); c.bias = Wp(op.b); c.out = T(op.dst); c.out_plane = PL(op.dst);
-                c.zero16 = h->ws + h->o_misc + 256;
+                c.zero16 = zero_page(h);
                 c.alpha = op.scheme == SC_HS ? 1.f / p.weights[op.w].wscale : 1.f;
                 c.reserve_cus = h->reserve_cus; c.sat = sat_counter(h);
                 if (f.family == CF_DIRECT_SPLITC) {
                     // sd_set_small_batch level 2: the chunk-range form into the partial-sum scratch, then the reduce launch with the layer's epilogue
-                    c.partial = reinterpret_cast<float*>(h->ws + h->o_splitk);
+                    c.partial = at<float>(h, h->a.splitk);
                     st = bracketed(op, e, N * c.H * c.W, d.C, [&] { return launch_conv_direct_splitc(c, s); }, label);
                     if (st != SD_OK || e != hipSuccess) break;
                     st = bracketed(op, e, N * c.H * c.W, d.C, [&] { return launch_splitc_reduce(c, s); }, "splitc_reduce_kernel",
@@ -323,7 +297,7 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, 
                 c.in_fmt = s0.fmt; c.out_fmt = p.tensors[op.dst].fmt; c.in_plane = PL(op.src[0]); c.out_plane = PL(op.dst);
                 c.in_sub = s0.planar16 ? (size_t)p.images * s0.H * s0.W * 16 : 0;
                 c.out_c = p.tensors[op.dst].C;
-                c.zero16 = h->ws + h->o_misc + 256;
+                c.zero16 = zero_page(h);
                 c.sw = h->sw;
                 e = launch_conv_smalln(c, s);
                 break;
@@ -357,7 +331,7 @@ sd_status run_plan(sd_handle* h, sd_net net, const uint8_t* frames, int frame0, 
     }
     (net == SD_NET_FCN8S ? h->last_fcn_images : h->last_mono_images) = N;
     // the pass's per-image clamp counts -> the counts of frames frame0.. (a monodepth frame's fliplr copy is its own frame's)
-    HIPCHK(h, launch_sat_fold(reinterpret_cast<unsigned*>(sat_counter(h) + 1), sat_frames(h) + frame0, sat_orphans(h), N,
+    HIPCHK(h, launch_sat_fold(sat_img(h), sat_frames(h) + frame0, sat_orphans(h), N,
                               p.images / p.frames == 2 ? 1 : 0, sat_img_slots(h), s));
     return SD_OK;
 }
@@ -371,7 +345,7 @@ CamDev make_cam(const sd_camera& c) {
     return d;
 }
 
-int32_t* cnt_slot(sd_handle* h, int i) { return reinterpret_cast<int32_t*>(h->ws + h->o_cnt) + (size_t)i * h->max_batch; }
+int32_t* cnt_slot(sd_handle* h, CntSlot i) { return at<int32_t>(h, h->a.cnt) + (size_t)i * h->max_batch; }
 
 }  // namespace
 
@@ -477,6 +451,11 @@ static sd_status create_impl(sd_handle** out, int device, int H, int W, int max_
     }
     resolve_forms(h);
     carve_workspace(h);
+    if (!h->a.fence_views_fit) {      // (cannot happen at any size in use: 15 bytes per point against the 161 of the Open3D region)
+        std::fprintf(stderr, "sd_create: the fence chain's views do not fit the Open3D scratch\n");
+        delete h;
+        return SD_ERR_STATE;
+    }
     *out = h;
     return SD_OK;
 }
@@ -494,7 +473,7 @@ sd_status sd_query_memory(const sd_handle* h, size_t* fcn_w, size_t* mono_w, siz
     if (!h) return SD_ERR_INVALID;
     if (fcn_w) *fcn_w = h->fcn.weight_bytes;
     if (mono_w) *mono_w = h->mono.weight_bytes;
-    if (ws) *ws = h->ws_bytes;
+    if (ws) *ws = h->a.total;
     return SD_OK;
 }
 
@@ -503,7 +482,7 @@ sd_status sd_bind_memory(sd_handle* h, void* wf, void* wm, void* ws) {
     HIPCHK(h, hipSetDevice(h->device));
     h->wf = (char*)wf; h->wm = (char*)wm; h->ws = (char*)ws;
     h->bound = true;
-    HIPCHK(h, hipMemset(h->ws + h->o_misc, 0, 4096));      // zero page (+256), the scalar slot (+0)
+    HIPCHK(h, hipMemset(at(h, h->a.scalar), 0, kScalarSlotBytes + kZeroPageBytes));      // the scalar slot and the zero page behind it
     HIPCHK(h, hipMemset(sat_counter(h), 0, sat_bytes(h->max_batch)));      // the clamp counters
     sd_status st = upload_tables(h, SD_NET_FCN8S);
     if (st != SD_OK) return st;
@@ -666,15 +645,16 @@ static void resize_tables(int dst, int src, int* idx, int* wgt) {
 // stream first, because the previous tables may still be in use)
 static sd_status upload_resize_tables(sd_handle* h, size_t off, int* key_store, std::vector<int>& host, int src_h, int src_w, int dst_h,
                                       int dst_w, hipStream_t s, int** xi, int** xa, int** yi, int** ya) {
-    int* dev = reinterpret_cast<int*>(h->ws + off);
-    *xi = dev; *xa = dev + 4 * (size_t)RSZ_MAX; *yi = dev + 8 * (size_t)RSZ_MAX; *ya = dev + 12 * (size_t)RSZ_MAX;
+    const RszLayout l;
+    int* dev = at<int>(h, off);
+    *xi = at<int>(h, off + l.xi); *xa = at<int>(h, off + l.xa); *yi = at<int>(h, off + l.yi); *ya = at<int>(h, off + l.ya);
     const int key[4] = {src_h, src_w, dst_h, dst_w};
     if (std::memcmp(key, key_store, sizeof(key)) != 0) {
         HIPCHK(h, hipStreamSynchronize(s));
-        host.assign((size_t)RSZ_MAX * 16, 0);
+        host.assign(l.total / sizeof(int), 0);        // (the host copy has the same layout)
         int* hx = host.data();
-        resize_tables(dst_w, src_w, hx, hx + 4 * (size_t)RSZ_MAX);
-        resize_tables(dst_h, src_h, hx + 8 * (size_t)RSZ_MAX, hx + 12 * (size_t)RSZ_MAX);
+        resize_tables(dst_w, src_w, hx + l.xi / sizeof(int), hx + l.xa / sizeof(int));
+        resize_tables(dst_h, src_h, hx + l.yi / sizeof(int), hx + l.ya / sizeof(int));
         HIPCHK(h, hipMemcpy(dev, hx, host.size() * sizeof(int), hipMemcpyHostToDevice));
         std::memcpy(key_store, key, sizeof(key));
     }
@@ -693,7 +673,7 @@ sd_status sd_resize_cubic_u8(sd_handle* h, const uint8_t* src, int B, int src_h,
         return SD_OK;
     }
     int *xi, *xa, *yi, *ya;
-    const sd_status st = upload_resize_tables(h, h->o_rsz, h->rsz_key, h->rsz_host, src_h, src_w, dst_h, dst_w, s, &xi, &xa, &yi, &ya);
+    const sd_status st = upload_resize_tables(h, h->a.rsz, h->rsz_key, h->rsz_host, src_h, src_w, dst_h, dst_w, s, &xi, &xa, &yi, &ya);
     if (st != SD_OK) return st;
     HIPCHK(h, launch_resize_cubic_u8(src, dst, B, src_h, src_w, dst_h, dst_w, channels, xi, xa, yi, ya, s));
     return SD_OK;
@@ -703,7 +683,7 @@ sd_status sd_jpeg_reconstruct_workspace(const sd_jpeg_frame_desc* descs_host, in
     if (!descs_host || B <= 0 || !bytes_out) return SD_ERR_INVALID;
     for (int b = 0; b < B; ++b)
         if (!sdjpeg::desc_ok(descs_host[b])) return SD_ERR_INVALID;
-    *bytes_out = jpeg_workspace_bytes(descs_host, B);
+    *bytes_out = sdjpeg::workspace_bytes(descs_host, B);
     return SD_OK;
 }
 
@@ -723,7 +703,7 @@ sd_status sd_jpeg_reconstruct_bgr(sd_handle* h, const int16_t* coef_dev, size_t 
         if ((size_t)d.height * d.width * 3 > bgr_frame_stride)
             return fail(h, SD_ERR_INVALID, "sd_jpeg_reconstruct_bgr: frame " + std::to_string(b) + " is larger than bgr_frame_stride");
     }
-    if (workspace_bytes < jpeg_workspace_bytes(descs_host, B))
+    if (workspace_bytes < sdjpeg::workspace_bytes(descs_host, B))
         return fail(h, SD_ERR_INVALID, "sd_jpeg_reconstruct_bgr: workspace smaller than sd_jpeg_reconstruct_workspace reports");
     HIPCHK(h, launch_jpeg_reconstruct(coef_dev, frame_stride_bytes / sizeof(int16_t), descs_host, B, bgr_dev, bgr_frame_stride,
                                       static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
@@ -732,7 +712,7 @@ sd_status sd_jpeg_reconstruct_bgr(sd_handle* h, const int16_t* coef_dev, size_t 
 
 sd_status sd_jpeg_entropy_workspace(int B, size_t interval_stride, size_t* bytes_out) {
     if (B < 1 || B > 65535 || interval_stride < 1 || interval_stride > ((size_t)1 << 24) || !bytes_out) return SD_ERR_INVALID;
-    *bytes_out = jpeg_entropy_workspace_bytes(B, interval_stride);
+    *bytes_out = sdjent::Layout(B, interval_stride).total;
     return SD_OK;
 }
 
@@ -751,7 +731,7 @@ sd_status sd_jpeg_entropy_decode(sd_handle* h, const uint8_t* bytes_dev, size_t 
     const char* why = "";
     if (!sdjent::args_ok(byte_stride, descs_host, frames_host, intervals_host, interval_stride, tables_host, B, coef_stride_bytes, &why))
         return fail(h, SD_ERR_INVALID, std::string("sd_jpeg_entropy_decode: ") + why);
-    if (workspace_bytes < jpeg_entropy_workspace_bytes(B, interval_stride))
+    if (workspace_bytes < sdjent::Layout(B, interval_stride).total)
         return fail(h, SD_ERR_INVALID, "sd_jpeg_entropy_decode: workspace smaller than sd_jpeg_entropy_workspace reports");
     HIPCHK(h, launch_jpeg_entropy_decode(bytes_dev, byte_stride, descs_host, frames_host, intervals_host, interval_stride, tables_host, B, coef_dev,
                                          coef_stride_bytes / sizeof(int16_t), status_dev, static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
@@ -760,7 +740,7 @@ sd_status sd_jpeg_entropy_decode(sd_handle* h, const uint8_t* bytes_dev, size_t 
 
 sd_status sd_jpeg_sync_workspace(int B, size_t interval_stride, size_t max_pieces, size_t* bytes_out) {
     if (B < 1 || B > 65535 || interval_stride < 1 || interval_stride > ((size_t)1 << 24) || max_pieces > ((size_t)1 << 24) || !bytes_out) return SD_ERR_INVALID;
-    *bytes_out = jpeg_sync_workspace_bytes(B, interval_stride, max_pieces);
+    *bytes_out = sdjsync::Layout(B, interval_stride, max_pieces).total;
     return SD_OK;
 }
 
@@ -782,7 +762,7 @@ sd_status sd_jpeg_sync_decode(sd_handle* h, const uint8_t* bytes_dev, size_t byt
     size_t most = 0;
     for (int b = 0; b < B; ++b)
         if (frames_host[b].eligible && frames_host[b].n_pieces > most) most = frames_host[b].n_pieces;
-    if (most > ((size_t)1 << 24) || workspace_bytes < jpeg_sync_workspace_bytes(B, interval_stride, most))
+    if (most > ((size_t)1 << 24) || workspace_bytes < sdjsync::Layout(B, interval_stride, most).total)
         return fail(h, SD_ERR_INVALID, "sd_jpeg_sync_decode: workspace smaller than sd_jpeg_sync_workspace reports for the largest frame");
     HIPCHK(h, launch_jpeg_sync_decode(bytes_dev, byte_stride, frames_host, intervals_host, interval_stride, tables_host, B, subseq_bytes, most, coef_dev,
                                       coef_stride_bytes / sizeof(int16_t), status_dev, static_cast<uint8_t*>(workspace_dev), (hipStream_t)stream));
@@ -791,7 +771,7 @@ sd_status sd_jpeg_sync_decode(sd_handle* h, const uint8_t* bytes_dev, size_t byt
 
 sd_status sd_png_reconstruct_workspace(int B, size_t* bytes_out) {
     if (B < 1 || B > 65535 || !bytes_out) return SD_ERR_INVALID;
-    *bytes_out = png_in_workspace_bytes(B);
+    *bytes_out = sdpngin::Layout(B).total;
     return SD_OK;
 }
 
@@ -806,7 +786,7 @@ sd_status sd_png_reconstruct_bgr(sd_handle* h, const uint8_t* rows_dev, size_t f
     // every index the kernel forms follows from descriptors of the call's size and these capacities: nothing is launched otherwise
     const char* why = "";
     if (!png_in_args_ok(frame_stride, descs_host, B, height, width, out_stride, &why)) return fail(h, SD_ERR_INVALID, std::string("sd_png_reconstruct_bgr: ") + why);
-    if (workspace_bytes < png_in_workspace_bytes(B))
+    if (workspace_bytes < sdpngin::Layout(B).total)
         return fail(h, SD_ERR_INVALID, "sd_png_reconstruct_bgr: workspace smaller than sd_png_reconstruct_workspace reports");
     HIPCHK(h, launch_png_reconstruct(rows_dev, frame_stride, descs_host, B, height, width, bgr_out_dev, out_stride, status_dev,
                                      static_cast<uint8_t*>(workspace_dev), (h->sw & SW_PNG_ONE_WAVE) ? 1 : sdpngin::kWaves, (hipStream_t)stream));
@@ -815,7 +795,7 @@ sd_status sd_png_reconstruct_bgr(sd_handle* h, const uint8_t* rows_dev, size_t f
 
 sd_status sd_png_encode_workspace(int B, int height, int width, size_t* workspace_bytes, size_t* stream_stride) {
     if (B < 1 || B > 65535 || height < 1 || width < 1 || height > sdpng::kMaxExtent || width > sdpng::kMaxExtent) return SD_ERR_INVALID;
-    if (workspace_bytes) *workspace_bytes = png_workspace_bytes(B, height, width);
+    if (workspace_bytes) *workspace_bytes = sdpng::Layout(B, height, width).total;
     if (stream_stride) *stream_stride = sdpng::stream_bound(height, width);
     return SD_OK;
 }
@@ -830,7 +810,7 @@ sd_status sd_png_encode_bgr(sd_handle* h, const uint8_t* frames_dev, size_t fram
     if (frame_stride < (size_t)height * width * 3) return fail(h, SD_ERR_INVALID, "sd_png_encode_bgr: frame_stride below height * width * 3");
     if (stream_stride < sdpng::stream_bound(height, width))
         return fail(h, SD_ERR_INVALID, "sd_png_encode_bgr: stream_stride below the bound sd_png_encode_workspace reports");
-    if (workspace_bytes < png_workspace_bytes(B, height, width))
+    if (workspace_bytes < sdpng::Layout(B, height, width).total)
         return fail(h, SD_ERR_INVALID, "sd_png_encode_bgr: workspace smaller than sd_png_encode_workspace reports");
     if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(sizes_dev) & 7))
         return fail(h, SD_ERR_INVALID, "sd_png_encode_bgr: workspace_dev must be 16-byte, sizes_dev 8-byte aligned");
@@ -841,7 +821,7 @@ sd_status sd_png_encode_bgr(sd_handle* h, const uint8_t* frames_dev, size_t fram
 
 sd_status sd_jpeg_encode_workspace(int B, int height, int width, size_t* workspace_bytes, size_t* stream_bound) {
     if (B < 1 || B > 65535 || height < 1 || width < 1 || height > sdjenc::kMaxExtent || width > sdjenc::kMaxExtent) return SD_ERR_INVALID;
-    if (workspace_bytes) *workspace_bytes = jpeg_enc_workspace_bytes(B, height);
+    if (workspace_bytes) *workspace_bytes = sdjenc::Layout(B, height).total;
     if (stream_bound) *stream_bound = sdjenc::stream_bound(height, width);
     return SD_OK;
 }
@@ -857,7 +837,7 @@ sd_status sd_jpeg_encode_bgr(sd_handle* h, const uint8_t* frames_dev, size_t fra
     // every index the kernels form follows from the extents and these capacities: nothing is launched otherwise
     if (frame_stride < (size_t)height * width * 3) return fail(h, SD_ERR_INVALID, "sd_jpeg_encode_bgr: frame_stride below height * width * 3");
     if (stream_stride < (size_t)sdjenc::kHeaderLen) return fail(h, SD_ERR_INVALID, "sd_jpeg_encode_bgr: stream_stride below the header's 613 bytes");
-    if (workspace_bytes < jpeg_enc_workspace_bytes(B, height))
+    if (workspace_bytes < sdjenc::Layout(B, height).total)
         return fail(h, SD_ERR_INVALID, "sd_jpeg_encode_bgr: workspace smaller than sd_jpeg_encode_workspace reports");
     if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(sizes_dev) & 7) || (reinterpret_cast<uintptr_t>(flags_dev) & 3))
         return fail(h, SD_ERR_INVALID, "sd_jpeg_encode_bgr: workspace_dev must be 16-byte, sizes_dev 8-byte, flags_dev 4-byte aligned");
@@ -872,7 +852,7 @@ constexpr int kPlyMaxCap = 0x7fffffff - sdply::kLineRows - sdply::kBlockRows;   
 
 sd_status sd_ply_format_workspace(int B, int cap, size_t* workspace_bytes, size_t* text_bound) {
     if (B < 1 || B > 65535 || cap < 0 || cap > kPlyMaxCap) return SD_ERR_INVALID;
-    if (workspace_bytes) *workspace_bytes = ply_workspace_bytes(B, cap);
+    if (workspace_bytes) *workspace_bytes = sdply::Layout(B, cap).total;
     if (text_bound) *text_bound = ply_text_bound(B, cap);
     return SD_OK;
 }
@@ -884,7 +864,7 @@ sd_status sd_ply_format_rw(sd_handle* h, const float* xyz_dev, const uint8_t* rg
         return fail(h, SD_ERR_INVALID, "sd_ply_format_rw: null pointer");
     if (B < 1 || B > 65535 || cap < 0 || cap > kPlyMaxCap) return fail(h, SD_ERR_INVALID, "sd_ply_format_rw: B must be 1..65535, cap >= 0");
     // every index the kernels form follows from B, cap and these capacities: nothing is launched otherwise
-    if (workspace_bytes < ply_workspace_bytes(B, cap))
+    if (workspace_bytes < sdply::Layout(B, cap).total)
         return fail(h, SD_ERR_INVALID, "sd_ply_format_rw: workspace smaller than sd_ply_format_workspace reports");
     if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(offsets_dev) & 7) ||
         (reinterpret_cast<uintptr_t>(flags_dev) & 3) || (reinterpret_cast<uintptr_t>(xyz_dev) & 3) || (reinterpret_cast<uintptr_t>(n_dev) & 3) ||
@@ -902,7 +882,7 @@ static bool scene_dims_ok(int B, int cap_road, int cap_fence, uint32_t lattice_c
 
 sd_status sd_scene_workspace(int B, int cap_road, int cap_fence, uint32_t lattice_cap, uint32_t mask, size_t* workspace_bytes, size_t* text_bound) {
     if (!scene_dims_ok(B, cap_road, cap_fence, lattice_cap, mask)) return SD_ERR_INVALID;
-    if (workspace_bytes) *workspace_bytes = scene_workspace_bytes(B, cap_road, cap_fence, lattice_cap, mask);
+    if (workspace_bytes) *workspace_bytes = sdscene::Layout(B, cap_road, cap_fence, lattice_cap, mask).total;
     if (text_bound) *text_bound = scene_text_bound(B, cap_road, cap_fence, lattice_cap, mask);
     return SD_OK;
 }
@@ -922,7 +902,7 @@ sd_status sd_scene_format(sd_handle* h, const float* road_xyz_dev, const uint8_t
     if (!scene_dims_ok(B, cap_road, cap_fence, lattice_cap, mask))
         return fail(h, SD_ERR_INVALID, "sd_scene_format: B must be 1..65535, the caps >= 0 and the row bound below 2^31 - 512");
     // every index the kernels form follows from B, the caps, lattice_cap and these capacities: nothing is launched otherwise
-    if (workspace_bytes < scene_workspace_bytes(B, cap_road, cap_fence, lattice_cap, mask))
+    if (workspace_bytes < sdscene::Layout(B, cap_road, cap_fence, lattice_cap, mask).total)
         return fail(h, SD_ERR_INVALID, "sd_scene_format: workspace smaller than sd_scene_workspace reports");
     auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
     if (mis(workspace_dev, 15) || mis(offsets_dev, 7) || mis(records_dev, 7) || mis(f2f_dev, 7) || mis(flags_dev, 3) || mis(road_xyz_dev, 3) ||
@@ -937,7 +917,7 @@ sd_status sd_scene_format(sd_handle* h, const float* road_xyz_dev, const uint8_t
     return SD_OK;
 }
 
-size_t sd_text_workspace_bytes(int B) { return B < 1 || B > 65535 ? 0 : text_workspace_bytes(B); }
+size_t sd_text_workspace_bytes(int B) { return B < 1 || B > 65535 ? 0 : sdtext::Layout(B).total; }
 
 sd_status sd_text_draw_rw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int dst_w, const sd_rw_result* records_dev, const char* depth_text,
                           void* workspace_dev, size_t workspace_bytes, void* stream) {
@@ -948,7 +928,7 @@ sd_status sd_text_draw_rw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int 
     const size_t dlen = strnlen(depth_text, sdtext::kMaxDepthBytes + 1);
     if (dlen > (size_t)sdtext::kMaxDepthBytes) return fail(h, SD_ERR_INVALID, "sd_text_draw_rw: depth_text longer than 23 bytes");
     // every index the kernels form follows from B, the extents and this capacity: nothing is launched otherwise
-    if (workspace_bytes < text_workspace_bytes(B)) return fail(h, SD_ERR_INVALID, "sd_text_draw_rw: workspace smaller than sd_text_workspace_bytes reports");
+    if (workspace_bytes < sdtext::Layout(B).total) return fail(h, SD_ERR_INVALID, "sd_text_draw_rw: workspace smaller than sd_text_workspace_bytes reports");
     if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(records_dev) & 7))
         return fail(h, SD_ERR_INVALID, "sd_text_draw_rw: workspace_dev must be 16-byte, records_dev 8-byte aligned");
     HIPCHK(h, launch_text_draw_rw(dst_dev, B, dst_h, dst_w, records_dev, reinterpret_cast<const uint8_t*>(depth_text), (int)dlen,
@@ -957,7 +937,7 @@ sd_status sd_text_draw_rw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int 
 }
 
 size_t sd_overlay_workspace_bytes(int B, int D) {
-    return B < 1 || B > 65535 || D < 0 || D > sdoverlay::kMaxDepths ? 0 : overlay_workspace_bytes(B, D);
+    return B < 1 || B > 65535 || D < 0 || D > sdoverlay::kMaxDepths ? 0 : sdoverlay::Layout(B, D).total;
 }
 
 sd_status sd_overlay_draw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int dst_w, int net_h, int net_w, const sd_camera* cams_host,
@@ -976,7 +956,7 @@ sd_status sd_overlay_draw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int 
     for (int b = 0; b < B; ++b)
         if (!sdoverlay::camera_ok(cams_host[b])) return fail(h, SD_ERR_INVALID, "sd_overlay_draw: a camera's cx, cy or f is not finite in float32");
     // every index the kernels form follows from B, D, the extents and this capacity: nothing is launched otherwise
-    if (workspace_bytes < overlay_workspace_bytes(B, D))
+    if (workspace_bytes < sdoverlay::Layout(B, D).total)
         return fail(h, SD_ERR_INVALID, "sd_overlay_draw: workspace smaller than sd_overlay_workspace_bytes reports");
     if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(records_dev) & 7) ||
         (reinterpret_cast<uintptr_t>(f2f_dev) & 7) || (reinterpret_cast<uintptr_t>(rw_profile_dev) & 7) ||
@@ -998,7 +978,7 @@ sd_status sd_overlay_draw(sd_handle* h, uint8_t* dst_dev, int B, int dst_h, int 
 
 sd_status sd_render_workspace(int B, int cap, const sd_render_camera* cam_host, size_t* workspace_bytes) {
     if (B < 1 || B > 65535 || cap < 0 || cap > kPlyMaxCap || !cam_host || !workspace_bytes || !sdrender::valid_camera(*cam_host)) return SD_ERR_INVALID;
-    *workspace_bytes = render_workspace_bytes(B, cap, *cam_host);
+    *workspace_bytes = sdrender::Layout(B, cap, *cam_host).total;
     return SD_OK;
 }
 
@@ -1012,7 +992,7 @@ sd_status sd_render_rw(sd_handle* h, const float* xyz_dev, const uint8_t* rgb_de
     if (!sdrender::valid_camera(cam))
         return fail(h, SD_ERR_INVALID, "sd_render_rw: camera outside the caps (finite fields, z_near > 0, extents 1..16384, point_size 1..16)");
     // every index the kernels form follows from B, cap, the camera's extents and this capacity: nothing is launched otherwise
-    if (workspace_bytes < render_workspace_bytes(B, cap, cam))
+    if (workspace_bytes < sdrender::Layout(B, cap, cam).total)
         return fail(h, SD_ERR_INVALID, "sd_render_rw: workspace smaller than sd_render_workspace reports");
     if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(records_dev) & 7) ||
         (reinterpret_cast<uintptr_t>(flags_dev) & 3) || (reinterpret_cast<uintptr_t>(xyz_dev) & 3) || (reinterpret_cast<uintptr_t>(n_dev) & 3) ||
@@ -1032,7 +1012,7 @@ sd_status sd_compose_result_frames(sd_handle* h, const uint8_t* frames, const ui
     if (!h->bound) return fail(h, SD_ERR_STATE, "sd_bind_memory first");
     hipStream_t s = (hipStream_t)stream;
     int *xi, *xa, *yi, *ya;
-    const sd_status st = upload_resize_tables(h, h->o_rsz_cmp, h->cmp_rsz_key, h->cmp_rsz_host, src_h, src_w, dst_h, dst_w, s, &xi, &xa, &yi, &ya);
+    const sd_status st = upload_resize_tables(h, h->a.rsz_cmp, h->cmp_rsz_key, h->cmp_rsz_host, src_h, src_w, dst_h, dst_w, s, &xi, &xa, &yi, &ya);
     if (st != SD_OK) return st;
     ComposeArgs a{};
     a.xi = xi; a.xa = xa; a.yi = yi; a.ya = ya;
@@ -1060,7 +1040,7 @@ sd_status sd_monodepth_forward(sd_handle* h, const uint8_t* frames, int B, float
     const size_t npix = (size_t)h->H * h->W;
     hipStream_t s = (hipStream_t)stream;
     const NetPlan& p = h->mono;
-    const float* raw = reinterpret_cast<const float*>(h->ws + h->o_mono + p.tensors[p.t_output].offset);
+    const float* raw = reinterpret_cast<const float*>(act_base(h, SD_NET_MONODEPTH) + p.tensors[p.t_output].offset);
     for (int b0 = 0; b0 < B; b0 += h->chunk) {
         const int nb = std::min(h->chunk, B - b0);
         sd_status st = run_plan(h, SD_NET_MONODEPTH, frames + (size_t)b0 * npix * 3, b0, nb, nullptr, s);
@@ -1083,7 +1063,7 @@ static sd_status fuse_impl(sd_handle* h, const float* disp_pp, const float* disp
     hipStream_t s = (hipStream_t)stream;
     std::vector<CamDev> cd(B);
     for (int b = 0; b < B; ++b) cd[b] = make_cam(cams[b]);
-    CamDev* dcams = reinterpret_cast<CamDev*>(h->ws + h->o_cams);
+    CamDev* dcams = at<CamDev>(h, h->a.cams);
     if (h->cams_stage.size() != (size_t)B || std::memcmp(h->cams_stage.data(), cd.data(), sizeof(CamDev) * B) != 0) {
         h->cams_stage = cd;
         HIPCHK(h, hipMemcpyAsync(dcams, h->cams_stage.data(), sizeof(CamDev) * B, hipMemcpyHostToDevice, s));
@@ -1093,16 +1073,16 @@ static sd_status fuse_impl(sd_handle* h, const float* disp_pp, const float* disp
     p.B = B; p.H = h->H; p.W = h->W; p.cap = cap; p.sw = h->sw;
     p.dense = dense; p.road_xyz = road_xyz; p.road_rgb = frames ? road_rgb : nullptr; p.n_road = n_road;
     p.fence_xyz = fence_xyz; p.fence_rgb = frames ? fence_rgb : nullptr; p.n_fence = n_fence;
-    const size_t nblk = ((size_t)h->H * h->W + 255) / 256;
-    p.blk_counts = reinterpret_cast<int32_t*>(h->ws + h->o_fuse);
-    p.blk_offsets = p.blk_counts + (size_t)h->max_batch * nblk * 2;
+    const FuseLayout fl(h->max_batch, h->H, h->W);
+    p.blk_counts = at<int32_t>(h, h->a.fuse + fl.blk_counts);
+    p.blk_offsets = at<int32_t>(h, h->a.fuse + fl.blk_offsets);
     // one-pass form: look-back words + tickets; the words carry an epoch, so the scratch is zeroed only every 1023 launches
     p.disp_raw = disp_raw; p.pp_out = pp_out;
-    // (layout of fuse_onepass_scratch_bytes: the look-back words of max_batch frames, then the tickets)
-    p.lb_state = reinterpret_cast<unsigned long long*>(h->ws + h->o_fuse1);
-    p.lb_ticket = reinterpret_cast<int32_t*>(h->ws + h->o_fuse1 + (fuse_onepass_scratch_bytes(h->max_batch, h->H, h->W) - 256 - (size_t)h->max_batch * 4));
+    const Fuse1Layout f1(h->max_batch, h->H, h->W);
+    p.lb_state = at<unsigned long long>(h, h->a.fuse1 + f1.state);
+    p.lb_ticket = at<int32_t>(h, h->a.fuse1 + f1.ticket);
     if (h->fuse_epoch == 0 || h->fuse_epoch >= 1023) {
-        HIPCHK(h, hipMemsetAsync(h->ws + h->o_fuse1, 0, fuse_onepass_scratch_bytes(h->max_batch, h->H, h->W), s));
+        HIPCHK(h, hipMemsetAsync(at(h, h->a.fuse1), 0, f1.total, s));
         h->fuse_epoch = 0;
     }
     p.epoch = ++h->fuse_epoch;
@@ -1126,7 +1106,7 @@ sd_status sd_postprocess_fuse_backproject(sd_handle* h, const float* disp_raw, f
         if (h->last_mono_frames < B || B > h->chunk)
             return fail(h, SD_ERR_STATE, "sd_postprocess_fuse_backproject: no raw disparities of a monodepth pass of >= B frames in the arena");
         const NetPlan& p = h->mono;
-        disp_raw = reinterpret_cast<const float*>(h->ws + h->o_mono + p.tensors[p.t_output].offset);
+        disp_raw = reinterpret_cast<const float*>(act_base(h, SD_NET_MONODEPTH) + p.tensors[p.t_output].offset);
     }
     return fuse_impl(h, nullptr, disp_raw, disp_pp_out, road, fence, frames, cams, B, cap, nullptr, road_xyz, road_rgb, n_road, fence_xyz,
                      fence_rgb, n_fence, stream);
@@ -1134,7 +1114,7 @@ sd_status sd_postprocess_fuse_backproject(sd_handle* h, const float* disp_raw, f
 
 size_t sd_fuse_sweep_workspace(int B, int T, int H, int W) {
     if (B < 1 || T < 1 || H < 1 || W < 1 || (long long)T * B > 65535) return 0;
-    return fuse_sweep_workspace_bytes(B, T, H, W);
+    return SweepLayout(B, T, H, W).total;
 }
 
 sd_status sd_fuse_backproject_sweep(sd_handle* h, const float* disp_pp, const uint8_t* road, const uint8_t* fence, const uint8_t* frames,
@@ -1149,7 +1129,7 @@ sd_status sd_fuse_backproject_sweep(sd_handle* h, const float* disp_pp, const ui
         return fail(h, SD_ERR_INVALID, "sd_fuse_backproject_sweep: the fence cloud needs its mask and its counter, its colours need the cloud");
     if ((road_rgb || fence_rgb) && !frames) return fail(h, SD_ERR_INVALID, "sd_fuse_backproject_sweep: a colour output needs frames");
     // every index the kernels form follows from B, T, cap, the handle's H x W and this capacity: nothing is launched otherwise
-    if (workspace_bytes < fuse_sweep_workspace_bytes(B, T, h->H, h->W))
+    if (workspace_bytes < SweepLayout(B, T, h->H, h->W).total)
         return fail(h, SD_ERR_INVALID, "sd_fuse_backproject_sweep: workspace smaller than sd_fuse_sweep_workspace reports");
     if ((reinterpret_cast<uintptr_t>(workspace_dev) & 15) || (reinterpret_cast<uintptr_t>(disp_pp) & 3) || (reinterpret_cast<uintptr_t>(road_xyz) & 3) ||
         (reinterpret_cast<uintptr_t>(fence_xyz) & 3) || (reinterpret_cast<uintptr_t>(n_road) & 3) || (reinterpret_cast<uintptr_t>(n_fence) & 3))
@@ -1160,7 +1140,7 @@ sd_status sd_fuse_backproject_sweep(sd_handle* h, const float* disp_pp, const ui
     p.B = B; p.T = T; p.H = h->H; p.W = h->W; p.cap = cap; p.sw = h->sw;
     p.road_xyz = road_xyz; p.road_rgb = road_rgb; p.n_road = n_road;
     p.fence_xyz = fence_xyz; p.fence_rgb = fence_rgb; p.n_fence = fence_xyz ? n_fence : nullptr;
-    fuse_sweep_layout(p, static_cast<uint8_t*>(workspace_dev));
+    fuse_sweep_carve(p, static_cast<uint8_t*>(workspace_dev));
     h->sweep_stage.resize((size_t)T * B);
     for (size_t i = 0; i < (size_t)T * B; ++i) h->sweep_stage[i] = make_cam(cams[i]);
     HIPCHK(h, hipMemcpyAsync(const_cast<CamDev*>(p.cams), h->sweep_stage.data(), sizeof(CamDev) * (size_t)T * B, hipMemcpyHostToDevice, s));
@@ -1183,19 +1163,19 @@ sd_status sd_road_width_boxes(sd_handle* h, const float* road_xyz, const uint8_t
         return fail(h, SD_ERR_INVALID, "sd_road_width: bad arguments");
     if (!h->bound) return fail(h, SD_ERR_STATE, "sd_bind_memory first");
     hipStream_t s = (hipStream_t)stream;
-    float* A = reinterpret_cast<float*>(h->ws + h->o_bufA);
-    int32_t *n1 = cnt_slot(h, 1), *n2 = cnt_slot(h, 2), *n3 = cnt_slot(h, 3), *n4 = cnt_slot(h, 4), *n5 = cnt_slot(h, 5),
-            *n6 = cnt_slot(h, 6);
-    double* plane = reinterpret_cast<double*>(h->ws + h->o_plane);
-    void* o3d = h->ws + h->o_o3d;
+    float* A = at<float>(h, h->a.bufA);
+    int32_t *n1 = cnt_slot(h, CNT_RW_ZCUT), *n2 = cnt_slot(h, CNT_RW_MAD_Y), *n3 = cnt_slot(h, CNT_RW_MAD_X), *n4 = cnt_slot(h, CNT_RW_PLANE),
+            *n5 = cnt_slot(h, CNT_RW_SOR), *n6 = cnt_slot(h, CNT_RW_ROR);
+    double* plane = at<double>(h, h->a.plane);
+    void* o3d = at(h, h->a.o3d);
     RwResultDev* res = reinterpret_cast<RwResultDev*>(results);
     // the stages ping-pong between arenas A and B2: with distinct input and output the ordered compaction of a frame runs on
     // 64 workgroups instead of one (pcl.hip: multi-block compaction)
-    float* B2 = reinterpret_cast<float*>(h->ws + h->o_bufB);
+    float* B2 = at<float>(h, h->a.bufB);
     // colours (nullable): the reference carries road_colors through every filter (semantic_depth.py:206-245)
-    uint8_t* cA = road_rgb ? reinterpret_cast<uint8_t*>(h->ws + h->o_rgbA) : nullptr;
-    uint8_t* cB = road_rgb ? reinterpret_cast<uint8_t*>(h->ws + h->o_rgbB) : nullptr;
-    void* cmp = h->ws + h->o_cmp;
+    uint8_t* cA = road_rgb ? at<uint8_t>(h, h->a.rgbA) : nullptr;
+    uint8_t* cB = road_rgb ? at<uint8_t>(h, h->a.rgbB) : nullptr;
+    void* cmp = at(h, h->a.cmp);
     HIPCHK(h, launch_filter_coord({road_xyz, road_rgb, n_road}, {A, cA, n1}, B, cap, F_LT_NEG, 2, prm->z_cut, cmp, s));
     HIPCHK(h, launch_mad_filter({A, cA, n1}, {B2, cB, n2}, B, cap, 1, prm->mad_y, nullptr, cmp, s));
     HIPCHK(h, launch_mad_filter({B2, cB, n2}, {A, cA, n3}, B, cap, 0, prm->mad_x, nullptr, cmp, s));
@@ -1236,18 +1216,17 @@ sd_status sd_fence_to_fence_boxes(sd_handle* h, const float* fence_xyz, const ui
         return fail(h, SD_ERR_INVALID, "sd_fence_to_fence: bad arguments");
     if (!h->bound) return fail(h, SD_ERR_STATE, "sd_bind_memory first");
     hipStream_t s = (hipStream_t)stream;
-    float* A = reinterpret_cast<float*>(h->ws + h->o_bufA);     // fence, then left fence
-    float* Rb = reinterpret_cast<float*>(h->ws + h->o_bufB);    // right fence
-    float* Lb = reinterpret_cast<float*>(h->ws + h->o_o3d);     // left fence (the Open3D scratch is idle here)
-    const size_t pts = (size_t)h->max_batch * h->cap;
-    uint8_t* cA = fence_rgb ? reinterpret_cast<uint8_t*>(h->ws + h->o_rgbA) : nullptr;
-    uint8_t* cR = fence_rgb ? reinterpret_cast<uint8_t*>(h->ws + h->o_rgbB) : nullptr;
-    uint8_t* cL = fence_rgb ? reinterpret_cast<uint8_t*>(h->ws + h->o_o3d) + al(pts * 3 * sizeof(float)) : nullptr;
+    const O3dLayout views(h->max_batch, h->cap);       // (the fence chain's views over the idle Open3D region)
+    float* A = at<float>(h, h->a.bufA);     // fence, then left fence
+    float* Rb = at<float>(h, h->a.bufB);    // right fence
+    float* Lb = at<float>(h, h->a.o3d + views.fence_left_xyz);
+    uint8_t* cA = fence_rgb ? at<uint8_t>(h, h->a.rgbA) : nullptr;
+    uint8_t* cR = fence_rgb ? at<uint8_t>(h, h->a.rgbB) : nullptr;
+    uint8_t* cL = fence_rgb ? at<uint8_t>(h, h->a.o3d + views.fence_left_rgb) : nullptr;
     if ((left_rgb || right_rgb) && !fence_rgb) return fail(h, SD_ERR_INVALID, "sd_fence_to_fence: colour outputs need fence_rgb");
-    int32_t* cnt = cnt_slot(h, 8);                              // [7][max_batch]: slots 8..14
-    auto C = [&](int j) { return cnt + (size_t)j * h->max_batch; };
-    int32_t* packed = reinterpret_cast<int32_t*>(h->ws + h->o_misc + 4096);
-    double* planes = reinterpret_cast<double*>(h->ws + h->o_misc + 4096 + al((size_t)h->max_batch * 7 * sizeof(int32_t)));   // road | left | right, [B][4] each
+    auto C = [&](int j) { return cnt_slot(h, (CntSlot)(CNT_F2F_FENCE + j)); };      // row j of sd_f2f_result::counts
+    int32_t* packed = at<int32_t>(h, h->a.f2f_counts);
+    double* planes = at<double>(h, h->a.f2f_planes);   // road | left | right, [B][4] each
     double *p_road = planes, *p_left = planes + (size_t)B * 4, *p_right = planes + (size_t)B * 8;
     HIPCHK(h, hipMemcpyAsync(C(0), n_fence, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, launch_gather_planes(reinterpret_cast<const RwResultDev*>(road), B, p_road, s));
@@ -1267,7 +1246,7 @@ sd_status sd_fence_to_fence_boxes(sd_handle* h, const float* fence_xyz, const ui
     if (left_rgb) HIPCHK(h, hipMemcpyAsync(left_rgb, cL, (size_t)B * cap * 3, hipMemcpyDeviceToDevice, s));
     if (right_rgb) HIPCHK(h, hipMemcpyAsync(right_rgb, cR, (size_t)B * cap * 3, hipMemcpyDeviceToDevice, s));
     // counts array for the kernel is [7][B] contiguous: compact the strided slots
-    for (int j = 0; j < 7; ++j)
+    for (int j = 0; j < CNT_F2F_ROWS; ++j)
         HIPCHK(h, hipMemcpyAsync(packed + (size_t)j * B, C(j), (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
     HIPCHK(h, launch_f2f(p_road, p_left, p_right, B, prm->depth, packed, reinterpret_cast<F2fResultDev*>(results), s));
     return SD_OK;
@@ -1293,7 +1272,7 @@ sd_status sd_road_width_profile(sd_handle* h, const float* xyz_dev, const int32_
     hipStream_t s = (hipStream_t)stream;
     h->rwp_stage.resize((size_t)D);
     sdrwp::sorted_windows(depths_host, D, window, depth_offset, h->rwp_stage.data());
-    HIPCHK(h, hipMemcpyAsync(workspace_dev, h->rwp_stage.data(), sizeof(sdrwp::Window) * (size_t)D, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(static_cast<uint8_t*>(workspace_dev) + sdrwp::Layout(B, cap, D).windows, h->rwp_stage.data(), sizeof(sdrwp::Window) * (size_t)D, hipMemcpyHostToDevice, s));
     HIPCHK(h, launch_rw_profile(xyz_dev, n_dev, B, cap, D, workspace_dev, results_dev, s));
     return SD_OK;
 }
@@ -1314,6 +1293,15 @@ sd_status sd_f2f_profile(sd_handle* h, const sd_rw_result* road_dev, const sd_f2
     return SD_OK;
 }
 
+// the four window tables of a PIL resample into their places in its workspace `ws` (the windows stay alive in the handle for the copies)
+static sd_status upload_pil_tables(sd_handle* h, uint8_t* ws, const sdpil::Layout& l, const sdpil::Windows& x, const sdpil::Windows& y, hipStream_t s) {
+    HIPCHK(h, hipMemcpyAsync(ws + l.x_bounds, x.bounds.data(), x.bounds.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(ws + l.x_k, x.k.data(), x.k.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(ws + l.y_bounds, y.bounds.data(), y.bounds.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(ws + l.y_k, y.k.data(), y.k.size() * 4, hipMemcpyHostToDevice, s));
+    return SD_OK;
+}
+
 sd_status sd_resize_pil_bilinear_u8(sd_handle* h, const uint8_t* src_dev, int B, int src_h, int src_w, int pixel_stride, int channels, int reverse,
                                     uint8_t* dst_dev, int dst_h, int dst_w, void* workspace_dev, size_t workspace_bytes, void* stream) {
     if (!h || !src_dev || !dst_dev || !workspace_dev) return fail(h, SD_ERR_INVALID, "sd_resize_pil_bilinear_u8: null pointer");
@@ -1331,11 +1319,7 @@ sd_status sd_resize_pil_bilinear_u8(sd_handle* h, const uint8_t* src_dev, int B,
     if (h->pil_x.taps > sdpil::taps_bound(src_w, dst_w) || h->pil_y.taps > sdpil::taps_bound(src_h, dst_h))
         return fail(h, SD_ERR_STATE, "sd_resize_pil_bilinear_u8: a window is longer than its bound");
     uint8_t* ws = static_cast<uint8_t*>(workspace_dev);
-    const size_t tx = sdpil::tables_bytes(src_w, dst_w);
-    HIPCHK(h, hipMemcpyAsync(ws, h->pil_x.bounds.data(), h->pil_x.bounds.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(ws + sdpil::al16((size_t)dst_w * 8), h->pil_x.k.data(), h->pil_x.k.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(ws + tx, h->pil_y.bounds.data(), h->pil_y.bounds.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(ws + tx + sdpil::al16((size_t)dst_h * 8), h->pil_y.k.data(), h->pil_y.k.size() * 4, hipMemcpyHostToDevice, s));
+    if (const sd_status st = upload_pil_tables(h, ws, sdpil::Layout(B, src_h, src_w, dst_h, dst_w, channels), h->pil_x, h->pil_y, s); st != SD_OK) return st;
     HIPCHK(h, launch_pil_resample_u8(src_dev, B, src_h, src_w, pixel_stride, channels, reverse ? 1 : 0, dst_dev, dst_h, dst_w, h->pil_x, ws, s));
     return SD_OK;
 }
@@ -1348,7 +1332,7 @@ sd_status sd_disp_image(sd_handle* h, const float* disp_dev, const float* mult_h
     if (height < 1 || width < 1 || out_h < 1 || out_w < 1 || !sddisp::valid_sizes(height, width, out_h, out_w))
         return fail(h, SD_ERR_INVALID, "sd_disp_image: extents in 1..16384 and a downscale factor of at most 32 per axis");
     // every index the kernels form follows from these sizes, the windows made below and this capacity: nothing is launched otherwise
-    const sddisp::Layout l = sddisp::layout(B, height, width, out_h, out_w);
+    const sddisp::Layout l(B, height, width, out_h, out_w);
     if (workspace_bytes < l.total || (reinterpret_cast<uintptr_t>(workspace_dev) & 15))
         return fail(h, SD_ERR_INVALID, "sd_disp_image: workspace smaller than sd_disp_image_workspace reports, or not 16-byte aligned");
     if ((reinterpret_cast<uintptr_t>(disp_dev) & 3) || (reinterpret_cast<uintptr_t>(flags_dev) & 3))
@@ -1361,12 +1345,7 @@ sd_status sd_disp_image(sd_handle* h, const float* disp_dev, const float* mult_h
         sdpil::pil_windows(height, out_h, h->disp_y);
         if (h->disp_x.taps > sdpil::taps_bound(width, out_w) || h->disp_y.taps > sdpil::taps_bound(height, out_h))
             return fail(h, SD_ERR_STATE, "sd_disp_image: a window is longer than its bound");
-        uint8_t* pw = ws + l.pil;
-        const size_t tx = sdpil::tables_bytes(width, out_w);
-        HIPCHK(h, hipMemcpyAsync(pw, h->disp_x.bounds.data(), h->disp_x.bounds.size() * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(pw + sdpil::al16((size_t)out_w * 8), h->disp_x.k.data(), h->disp_x.k.size() * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(pw + tx, h->disp_y.bounds.data(), h->disp_y.bounds.size() * 4, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(pw + tx + sdpil::al16((size_t)out_h * 8), h->disp_y.k.data(), h->disp_y.k.size() * 4, hipMemcpyHostToDevice, s));
+        if (const sd_status st = upload_pil_tables(h, ws + l.pil, sdpil::Layout(B, height, width, out_h, out_w, 1), h->disp_x, h->disp_y, s); st != SD_OK) return st;
     }
     if (mult_host) {
         h->disp_mult.assign(mult_host, mult_host + B);
@@ -1393,7 +1372,7 @@ sd_status sd_seg_confusion(sd_handle* h, const uint8_t* pred_dev, const uint8_t*
 
 // ---------------------------------------------------------------- pcl.py function by function (single cloud)
 static sd_status set_n(sd_handle* h, int n, int32_t** dn, hipStream_t s) {
-    *dn = reinterpret_cast<int32_t*>(h->ws + h->o_misc);
+    *dn = at<int32_t>(h, h->a.scalar);
     HIPCHK(h, hipMemsetD32Async((hipDeviceptr_t)*dn, n, 1, s));
     return SD_OK;
 }
@@ -1409,26 +1388,26 @@ static sd_status set_n(sd_handle* h, int n, int32_t** dn, hipStream_t s) {
 sd_status sd_pcl_remove_from_to(sd_handle* h, const float* xyz, const uint8_t* rgb, int n, int axis, double to_meter,
                                 float* xyz_out, uint8_t* rgb_out, int32_t* n_out, void* stream) {
     PCL_PROLOGUE();
-    HIPCHK(h, launch_filter_coord({xyz, rgb, dn}, {xyz_out, rgb_out, n_out}, 1, cap1, F_LT_NEG, axis, to_meter, h->ws + h->o_cmp, s));
+    HIPCHK(h, launch_filter_coord({xyz, rgb, dn}, {xyz_out, rgb_out, n_out}, 1, cap1, F_LT_NEG, axis, to_meter, at(h, h->a.cmp), s));
     return SD_OK;
 }
 sd_status sd_pcl_threshold_complete(sd_handle* h, const float* xyz, const uint8_t* rgb, int n, int axis, double threshold,
                                     float* xyz_out, uint8_t* rgb_out, int32_t* n_out, void* stream) {
     PCL_PROLOGUE();
-    HIPCHK(h, launch_filter_coord({xyz, rgb, dn}, {xyz_out, rgb_out, n_out}, 1, cap1, F_ABS_LT, axis, threshold, h->ws + h->o_cmp, s));
+    HIPCHK(h, launch_filter_coord({xyz, rgb, dn}, {xyz_out, rgb_out, n_out}, 1, cap1, F_ABS_LT, axis, threshold, at(h, h->a.cmp), s));
     return SD_OK;
 }
 sd_status sd_pcl_remove_noise_by_mad(sd_handle* h, const float* xyz, const uint8_t* rgb, int n, int axis, double threshold,
                                      float* xyz_out, uint8_t* rgb_out, int32_t* n_out, float* stats_out, void* stream) {
     PCL_PROLOGUE();
-    HIPCHK(h, launch_mad_filter({xyz, rgb, dn}, {xyz_out, rgb_out, n_out}, 1, cap1, axis, threshold, stats_out, h->ws + h->o_cmp, s));
+    HIPCHK(h, launch_mad_filter({xyz, rgb, dn}, {xyz_out, rgb_out, n_out}, 1, cap1, axis, threshold, stats_out, at(h, h->a.cmp), s));
     return SD_OK;
 }
 sd_status sd_pcl_remove_noise_by_fitting_plane(sd_handle* h, const float* xyz, const uint8_t* rgb, int n, int axis, double threshold,
                                                float* xyz_out, uint8_t* rgb_out, int32_t* n_out, double* coeff_out, void* stream) {
     PCL_PROLOGUE();
     if (axis < 0 || axis > 2) return fail(h, SD_ERR_INVALID, "axis");
-    HIPCHK(h, launch_plane_filter({xyz, rgb, dn}, {xyz_out, rgb_out, n_out}, 1, cap1, axis, threshold, coeff_out, h->ws + h->o_cmp, s));
+    HIPCHK(h, launch_plane_filter({xyz, rgb, dn}, {xyz_out, rgb_out, n_out}, 1, cap1, axis, threshold, coeff_out, at(h, h->a.cmp), s));
     return SD_OK;
 }
 sd_status sd_pcl_extract_pcls(sd_handle* h, const float* xyz, const uint8_t* rgb, int n, int axis, float* left_xyz, uint8_t* left_rgb,
@@ -1456,15 +1435,15 @@ sd_status sd_o3d_statistical_outlier_removal(sd_handle* h, const float* xyz, con
                                              double* mean_dist_out, void* stream) {
     PCL_PROLOGUE();
     if (nb_neighbors < 1 || nb_neighbors > 16) return fail(h, SD_ERR_INVALID, "nb_neighbors must be in 1..16");
-    if (o3d_scratch_bytes(1, cap1) > o3d_scratch_bytes(h->max_batch, h->cap)) return fail(h, SD_ERR_INVALID, "cloud too large");
-    HIPCHK(h, launch_sor({xyz, rgb, dn}, {xyz_out, rgb_out, n_out}, 1, cap1, nb_neighbors, std_ratio, h->ws + h->o_o3d, mean_dist_out, h->ws + h->o_cmp, s));
+    if (O3dLayout(1, cap1).total > O3dLayout(h->max_batch, h->cap).total) return fail(h, SD_ERR_INVALID, "cloud too large");
+    HIPCHK(h, launch_sor({xyz, rgb, dn}, {xyz_out, rgb_out, n_out}, 1, cap1, nb_neighbors, std_ratio, at(h, h->a.o3d), mean_dist_out, at(h, h->a.cmp), s));
     return SD_OK;
 }
 sd_status sd_o3d_radius_outlier_removal(sd_handle* h, const float* xyz, const uint8_t* rgb, int n, int nb_points, double radius,
                                         float* xyz_out, uint8_t* rgb_out, int32_t* n_out, void* stream) {
     PCL_PROLOGUE();
-    if (o3d_scratch_bytes(1, cap1) > o3d_scratch_bytes(h->max_batch, h->cap)) return fail(h, SD_ERR_INVALID, "cloud too large");
-    HIPCHK(h, launch_ror({xyz, rgb, dn}, {xyz_out, rgb_out, n_out}, 1, cap1, nb_points, radius, h->ws + h->o_o3d, h->ws + h->o_cmp, s));
+    if (O3dLayout(1, cap1).total > O3dLayout(h->max_batch, h->cap).total) return fail(h, SD_ERR_INVALID, "cloud too large");
+    HIPCHK(h, launch_ror({xyz, rgb, dn}, {xyz_out, rgb_out, n_out}, 1, cap1, nb_points, radius, at(h, h->a.o3d), at(h, h->a.cmp), s));
     return SD_OK;
 }
 
@@ -1481,7 +1460,7 @@ sd_status sd_net_tensor(sd_handle* h, sd_net net, const char* name, float* out, 
     if (!h->bound) return fail(h, SD_ERR_STATE, "sd_bind_memory first");
     const size_t numel = (size_t)N * t.H * t.W * (t.fmt != PL_F32 ? t.Ctf : t.C);
     if (numel > cap_floats) return fail(h, SD_ERR_INVALID, "output buffer too small");
-    const char* abase = h->ws + (net == SD_NET_FCN8S ? h->o_fcn : h->o_mono);
+    const char* abase = act_base(h, net);
     if (t.fmt != PL_F32)      // split planes -> f32
         HIPCHK(h, launch_unsplit(reinterpret_cast<const float*>(abase + t.offset), out, (long)N * t.H * t.W, t.C, t.Ctf, (size_t)p.images * t.H * t.W * t.C,
                                  t.planar16 ? (size_t)p.images * t.H * t.W * 16 : 0, t.fmt, (hipStream_t)stream));

@@ -203,7 +203,7 @@ unsigned frame_blocks(size_t units, int B) {
 
 hipError_t launch_disp_image(const float* disp, int B, int h, int w, int out_h, int out_w, int cmap, int has_mult, uint8_t* dst, int32_t* flags,
                              const sdpil::Windows& wx, uint8_t* workspace, hipStream_t s) {
-    const Layout l = layout(B, h, w, out_h, out_w);
+    const Layout l(B, h, w, out_h, out_w);
     Cells* cells = reinterpret_cast<Cells*>(workspace + l.cells);
     float* mult = reinterpret_cast<float*>(workspace + l.mult);
     uint8_t* bytes = workspace + l.bytes;

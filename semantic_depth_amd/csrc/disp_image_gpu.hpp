@@ -6,7 +6,7 @@
 
 namespace sd {
 
-// disp f32 [B,h,w] -> dst u8 [B,out_h,out_w,3] BGR, flags i32 [B].  workspace: sddisp::layout(...).total bytes, 16-byte aligned; the caller
+// disp f32 [B,h,w] -> dst u8 [B,out_h,out_w,3] BGR, flags i32 [B].  workspace: sddisp::Layout(...).total bytes, 16-byte aligned; the caller
 // has copied the frames' multipliers to its `mult` part (has_mult) and, when the sizes differ, the four window tables of the resample to
 // their places in its `pil` part (`wx`: the host copy of the x windows), in stream order before this.  Five launches, seven when the sizes
 // differ (six when only the widths do); no synchronisation, no allocation.

@@ -122,26 +122,18 @@ inline bool valid_map(int cmap) { return cmap >= 0 && cmap < kMaps; }
 inline bool valid_sizes(int h, int w, int out_h, int out_w) { return sdpil::axis_ok(h, out_h) && sdpil::axis_ok(w, out_w); }
 inline bool resized(int h, int w, int out_h, int out_w) { return h != out_h || w != out_w; }
 
-// ---- workspace of the device route (disp_image_gpu.hip), every part 16-byte aligned:
-// [cells u32 [B][4]: key min, key max, lo8, hi8][mult f32 [B]][bytes u8 [B][h][w]] and, when the sizes differ, [resized u8 [B][out_h][out_w]]
-// [the resample's own workspace, sdpil::workspace_bytes(..., channels = 1)]
-struct Layout {
-    size_t cells, mult, bytes, resized, pil, total;
+// ---- workspace of the device route (disp_image_gpu.hip); every part 16-byte aligned
+struct Layout : sdarena::Walker {
+    size_t B, px, out_px, pil_bytes;      // (out_px, pil_bytes: 0 when the sizes do not differ; the two parts are then empty, at `total`)
+    Layout(int B_, int h, int w, int out_h, int out_w)
+        : B((size_t)B_), px((size_t)h * w), out_px(sddisp::resized(h, w, out_h, out_w) ? (size_t)out_h * out_w : 0),
+          pil_bytes(out_px ? sdpil::workspace_bytes(B_, h, w, out_h, out_w, 1) : 0) {}
+    size_t cells = take(B * 4 * sizeof(uint32_t), 16);      // u32 [B][4]: key min, key max, lo8, hi8
+    size_t mult = take(B * sizeof(float), 16);              // f32 [B]
+    size_t bytes = take(B * px, 16);                        // u8 [B][h][w]
+    size_t resized = take(B * out_px, 16);                  // u8 [B][out_h][out_w]
+    size_t pil = take(pil_bytes, 16);                       // the resample's own workspace, sdpil::Layout(..., channels = 1)
+    size_t total = end(16);
 };
-inline Layout layout(int B, int h, int w, int out_h, int out_w) {
-    using sdpil::al16;
-    Layout l{};
-    l.cells = 0;
-    l.mult = l.cells + al16((size_t)B * 4 * sizeof(uint32_t));
-    l.bytes = l.mult + al16((size_t)B * sizeof(float));
-    l.resized = l.bytes + al16((size_t)B * h * w);
-    l.pil = l.resized;
-    l.total = l.resized;
-    if (resized(h, w, out_h, out_w)) {
-        l.pil = l.resized + al16((size_t)B * out_h * out_w);
-        l.total = l.pil + al16(sdpil::workspace_bytes(B, h, w, out_h, out_w, 1));
-    }
-    return l;
-}
 
 }  // namespace sddisp

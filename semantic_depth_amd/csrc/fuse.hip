@@ -47,11 +47,6 @@ hipError_t launch_post_process(const float* disp_raw, float* disp_pp, int B, int
 }
 
 // ---------------------------------------------------------------------------------------------
-size_t fuse_scratch_bytes(int B, int H, int W) {
-    size_t nblk = ((size_t)H * W + 255) / 256;
-    return (size_t)B * nblk * 2 * sizeof(int32_t) * 2;
-}
-
 __global__ __launch_bounds__(256) void fuse_count_kernel(const uint8_t* __restrict__ road, const uint8_t* __restrict__ fence,
                                                          int npix, int nblk, int32_t* __restrict__ blk_counts) {
     const int b = blockIdx.y, blk = blockIdx.x;
@@ -293,20 +288,12 @@ __global__ __launch_bounds__(256) void fuse_write4_kernel(const FuseParams p, in
 //     sub-tile's points in LDS and writing them as coalesced dword runs (165 us), 1024- / 4096-pixel blocks (252 / 170 us: the
 //     ticket + look-back cost per block shows below 4096 pixels), closed forms for the interior columns / the sparse Q (kept:
 //     they are exact, but the f64 arithmetic was not the limiter).
-#ifndef SD_F1_SUB
-#define SD_F1_SUB 8
-#endif
 #ifndef SD_F1_WAVES
 #define SD_F1_WAVES 4
 #endif
-constexpr int F1_SUB = SD_F1_SUB;                       // sub-tiles of 1024 pixels (256 threads x 4 pixels) per block
-constexpr int F1_PIX = 1024 * F1_SUB;           // pixels per block: one ticket, one look-back, one published word
+// (F1_SUB sub-tiles of 1024 pixels per block, F1_PIX pixels per block and the scratch, Fuse1Layout: tail_layout.hpp)
 __device__ __forceinline__ unsigned long long f1_pack(unsigned epoch, unsigned flag, unsigned r, unsigned f) {
     return ((unsigned long long)epoch << 54) | ((unsigned long long)flag << 52) | ((unsigned long long)r << 26) | (unsigned long long)f;
-}
-size_t fuse_onepass_scratch_bytes(int B, int H, int W) {
-    const size_t nblk = ((size_t)H * W + F1_PIX - 1) / F1_PIX;
-    return (size_t)B * nblk * 8 + (size_t)B * 4 + 256;
 }
 bool fuse_onepass_eligible(const FuseParams& p) {
     return p.W % 4 == 0 && (p.H * p.W) % 4 == 0 && !p.dense && (p.road_xyz || p.fence_xyz) && p.lb_state && p.lb_ticket && p.epoch &&
@@ -577,19 +564,14 @@ hipError_t launch_fuse(const FuseParams& p, hipStream_t s) {
 //   * positions come from the wave prefix as in fuse_write4_kernel: consecutive kept pixels write consecutive rows of a slot, a point
 //     is one 12-byte store
 //   * the last block of a frame knows the frame's totals (its offset + its own count) and writes them to the T slots' counters
-// Workspace (the caller's; every byte read is written by the same call): [T][B] CamDev | blk_counts [B][nblk][2] | blk_offsets [B][nblk][2].
+// Workspace: SweepLayout (tail_layout.hpp).
 constexpr int SWEEP_TC = 32;
 struct SweepCam { double q[16]; float mult; int sparse; };      // CamDev + "Q has make_cam's zero pattern"
-static size_t sweep_align16(size_t v) { return (v + 15) & ~(size_t)15; }
-static size_t sweep_blk_bytes(int B, int H, int W) { return sweep_align16((size_t)B * (((size_t)H * W + 255) / 256) * 2 * sizeof(int32_t)); }
-size_t fuse_sweep_workspace_bytes(int B, int T, int H, int W) {
-    return sweep_align16((size_t)T * B * sizeof(CamDev)) + 2 * sweep_blk_bytes(B, H, W);
-}
-void fuse_sweep_layout(SweepParams& p, uint8_t* ws) {
-    p.cams = reinterpret_cast<CamDev*>(ws);
-    ws += sweep_align16((size_t)p.T * p.B * sizeof(CamDev));
-    p.blk_counts = reinterpret_cast<int32_t*>(ws);
-    p.blk_offsets = reinterpret_cast<int32_t*>(ws + sweep_blk_bytes(p.B, p.H, p.W));
+void fuse_sweep_carve(SweepParams& p, uint8_t* ws) {
+    const SweepLayout l(p.B, p.T, p.H, p.W);
+    p.cams = reinterpret_cast<CamDev*>(ws + l.cams);
+    p.blk_counts = reinterpret_cast<int32_t*>(ws + l.blk_counts);
+    p.blk_offsets = reinterpret_cast<int32_t*>(ws + l.blk_offsets);
 }
 
 // PPT pixels per thread: 4 (W % 4 == 0, aligned inputs: the loads of fuse_write4_kernel) or 1 (any geometry)

@@ -12,7 +12,7 @@ static_assert(SD_CMAP_GRAY == 0 && SD_CMAP_PLASMA == 1 && sddisp::kMaps == 2, "t
 
 extern "C" sd_status sd_disp_image_workspace(int B, int h, int w, int out_h, int out_w, size_t* bytes_out) {
     if (!bytes_out || B < 1 || B > 65535 || !sddisp::valid_sizes(h, w, out_h, out_w)) return SD_ERR_INVALID;
-    *bytes_out = sddisp::layout(B, h, w, out_h, out_w).total;
+    *bytes_out = sddisp::Layout(B, h, w, out_h, out_w).total;
     return SD_OK;
 }
 

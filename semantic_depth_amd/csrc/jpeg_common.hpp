@@ -7,6 +7,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "arena.hpp"
+
 #if defined(__HIPCC__)
 #define SD_JPEG_HD __host__ __device__
 #else
@@ -123,6 +125,18 @@ inline bool desc_ok(const sd_jpeg_frame_desc& d) {
         off += (int64_t)d.blocks_w[i] * d.blocks_h[i] * 64;
     }
     return true;
+}
+
+// ---- workspace of the device half (jpeg_gpu.hip): frame after frame, component after component, each padded u8 plane
+// [blocks_h * 8][blocks_w * 8] at a 256-byte boundary.  One walk serves the size query and the launcher: plane[c] of the next frame
+inline void take_planes(sdarena::Walker& w, const sd_jpeg_frame_desc& d, size_t plane[3]) {
+    for (int c = 0; c < d.ncomp; ++c) plane[c] = w.take((size_t)d.blocks_w[c] * d.blocks_h[c] * 64, 256);
+}
+inline size_t workspace_bytes(const sd_jpeg_frame_desc* descs, int B) {
+    sdarena::Walker w;
+    size_t plane[3];
+    for (int b = 0; b < B; ++b) take_planes(w, descs[b], plane);
+    return w.end(256);
 }
 
 }  // namespace sdjpeg

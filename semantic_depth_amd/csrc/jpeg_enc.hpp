@@ -4,11 +4,19 @@
 // functions and all of it is integer arithmetic, so they agree on every bit; what differs is only who walks the blocks (one loop on the host,
 // one workgroup per MCU row on the device).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
 #include <stddef.h>
 #include <stdint.h>
 
+#include "arena.hpp"
+
+#if defined(__HIPCC__)
 #define SDJENC_HD __host__ __device__ inline
+#else
+#define SDJENC_HD inline
+#endif
 
 namespace sdjenc {
 
@@ -292,5 +300,15 @@ SDJENC_HD void make_header(uint8_t* p, uint16_t (*div)[64], int h, int w, int qu
     u16(0xFFDD); u16(4); u16(mcus_w(w));
     u16(0xFFDA); u16(12); u8(3); u8(1); u8(0x00); u8(2); u8(0x11); u8(3); u8(0x11); u8(0); u8(63); u8(0);
 }
+
+// ---- workspace of the device route (jpeg_enc_gpu.hip).  No coded byte passes through it: the rows are coded twice, once for their sizes
+// and once into place.
+struct Layout : sdarena::Walker {
+    size_t n;                        // MCU rows of all frames
+    Layout(int B, int h) : n((size_t)B * (size_t)mcu_rows(h)) {}
+    size_t offsets = take(n * 8, 16);      // u64 [n], 16-byte aligned (with the workspace): a row's offset inside its frame's file
+    size_t rowsize = take(n * 4, 4);       // u32 [n], 4: its bytes
+    size_t total = end(16);
+};
 
 }  // namespace sdjenc

@@ -247,9 +247,9 @@ hipError_t launch_jpeg_encode(const uint8_t* frames, size_t frame_stride, int B,
     EncArgs a{};
     a.frames = frames; a.frame_stride = frame_stride; a.h = h; a.w = w; a.mw = mcus_w(w); a.mh = mcu_rows(h);
     a.streams = streams; a.stream_stride = stream_stride; a.sizes = sizes; a.flags = flags;
-    const size_t n = (size_t)B * a.mh;
-    a.offsets = reinterpret_cast<uint64_t*>(workspace);
-    a.rowsize = reinterpret_cast<uint32_t*>(a.offsets + n);
+    const Layout l(B, h);
+    a.offsets = reinterpret_cast<uint64_t*>(workspace + l.offsets);
+    a.rowsize = reinterpret_cast<uint32_t*>(workspace + l.rowsize);
     make_header(a.header, a.div, h, w, quality);
     const dim3 grid((unsigned)a.mh, (unsigned)B);
     hipLaunchKernelGGL(jpeg_row_kernel<false>, grid, dim3(kThreads), 0, s, a);

@@ -6,12 +6,7 @@
 
 namespace sd {
 
-// workspace of B frames of r MCU rows each: [B * r] u64 offsets of the rows inside their frame's file, then [B * r] u32 row sizes.  No
-// coded byte passes through it: the rows are coded twice, once for their sizes and once into place.
-inline size_t jpeg_enc_workspace_bytes(int B, int h) {
-    const size_t n = (size_t)B * (size_t)sdjenc::mcu_rows(h);
-    return (n * (sizeof(uint64_t) + sizeof(uint32_t)) + 15) & ~(size_t)15;
-}
+// workspace: sdjenc::Layout (jpeg_enc.hpp)
 
 // frames u8 [B,h,w,3] BGR at frame_stride -> one JFIF file per frame at streams + b * stream_stride, sizes[b] = its bytes, flags[b] = 1
 // (and size 0) when it would pass stream_stride.  The caller has checked the extents (1..16384), the quality (1..100), stream_stride >=

@@ -181,4 +181,14 @@ inline bool args_ok(size_t byte_stride, const sd_jpeg_frame_desc* descs, const s
     return true;
 }
 
+// ---- workspace of the device route (jpeg_entropy_gpu.hip): the launcher's three uploads, every part 16-byte aligned
+struct Layout : sdarena::Walker {
+    size_t B, stride;
+    Layout(int B_, size_t interval_stride) : B((size_t)B_), stride(interval_stride) {}
+    size_t frames = take(B * sizeof(sd_jpeg_entropy_frame), 16);
+    size_t tables = take(B * kTables * sizeof(sd_jpeg_huff_table), 16);       // [B][kTables]
+    size_t intervals = take(B * stride * sizeof(sd_jpeg_interval), 16);       // [B][interval_stride]
+    size_t total = end(16);
+};
+
 }  // namespace sdjent

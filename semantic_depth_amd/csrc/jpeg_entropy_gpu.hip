@@ -79,12 +79,10 @@ hipError_t launch_jpeg_entropy_decode(const uint8_t* bytes, size_t byte_stride, 
                                       int16_t* coef, size_t coef_stride_elems, int32_t* status, uint8_t* workspace, hipStream_t s) {
     EntArgs a{};
     a.bytes = bytes; a.byte_stride = byte_stride; a.interval_stride = interval_stride; a.coef = coef; a.coef_stride = coef_stride_elems; a.status = status;
-    uint8_t* w = workspace;
-    sd_jpeg_entropy_frame* frames = reinterpret_cast<sd_jpeg_entropy_frame*>(w);
-    w += jpeg_entropy_part((size_t)B * sizeof(sd_jpeg_entropy_frame));
-    sd_jpeg_huff_table* tables = reinterpret_cast<sd_jpeg_huff_table*>(w);
-    w += jpeg_entropy_part((size_t)B * sdjent::kTables * sizeof(sd_jpeg_huff_table));
-    sd_jpeg_interval* intervals = reinterpret_cast<sd_jpeg_interval*>(w);
+    const sdjent::Layout l(B, interval_stride);
+    sd_jpeg_entropy_frame* frames = reinterpret_cast<sd_jpeg_entropy_frame*>(workspace + l.frames);
+    sd_jpeg_huff_table* tables = reinterpret_cast<sd_jpeg_huff_table*>(workspace + l.tables);
+    sd_jpeg_interval* intervals = reinterpret_cast<sd_jpeg_interval*>(workspace + l.intervals);
     a.frames = frames; a.tables = tables; a.intervals = intervals;
     hipError_t e = hipMemcpyAsync(frames, frames_host, (size_t)B * sizeof(sd_jpeg_entropy_frame), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return e;

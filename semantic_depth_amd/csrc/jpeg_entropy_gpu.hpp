@@ -6,13 +6,7 @@
 
 namespace sd {
 
-// workspace of B frames: [B] sd_jpeg_entropy_frame, [B * 8] sd_jpeg_huff_table, [B * interval_stride] sd_jpeg_interval, each part
-// rounded up to 16 bytes
-inline size_t jpeg_entropy_part(size_t bytes) { return (bytes + 15) & ~(size_t)15; }
-inline size_t jpeg_entropy_workspace_bytes(int B, size_t interval_stride) {
-    return jpeg_entropy_part((size_t)B * sizeof(sd_jpeg_entropy_frame)) + jpeg_entropy_part((size_t)B * sdjent::kTables * sizeof(sd_jpeg_huff_table)) +
-           jpeg_entropy_part((size_t)B * interval_stride * sizeof(sd_jpeg_interval));
-}
+// workspace: sdjent::Layout (jpeg_entropy.hpp)
 
 // The caller has run sdjent::args_ok() and checked the alignments and the workspace size.  Uploads the records, the tables and the
 // frames' ranges from the host arrays into the workspace (three asynchronous copies on s), clears the eligible frames' coefficients

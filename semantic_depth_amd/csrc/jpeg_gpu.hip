@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void jpeg_colour_kernel(const JpegGroupArgs g,
 
 hipError_t launch_jpeg_reconstruct(const int16_t* coef, size_t frame_stride_elems, const sd_jpeg_frame_desc* descs, int B, uint8_t* bgr,
                                    size_t bgr_frame_stride, uint8_t* workspace, hipStream_t s) {
-    size_t ws_off = 0;
+    sdarena::Walker ws_walk;
     for (int b0 = 0; b0 < B; b0 += JPEG_GROUP) {
         const int nb = B - b0 < JPEG_GROUP ? B - b0 : JPEG_GROUP;
         JpegGroupArgs g{};
@@ -153,11 +153,12 @@ hipError_t launch_jpeg_reconstruct(const int16_t* coef, size_t frame_stride_elem
             JpegFrameDev& f = g.f[k];
             f.H = d.height; f.W = d.width; f.ncomp = d.ncomp; f.hmax = d.hmax; f.vmax = d.vmax;
             f.orientation = d.orientation; f.transform = d.adobe_transform;
+            size_t plane[3];
+            sdjpeg::take_planes(ws_walk, d, plane);
             for (int c = 0; c < d.ncomp; ++c) {
                 f.bw[c] = d.blocks_w[c]; f.bh[c] = d.blocks_h[c];
                 f.coef_off[c] = (unsigned long long)d.coef_offset[c];
-                f.plane_off[c] = ws_off;
-                ws_off += jpeg_plane_slot(d, c);
+                f.plane_off[c] = plane[c];
                 for (int q = 0; q < 64; ++q) f.qt[c][q] = d.qt[c][q];
                 const size_t blocks = (size_t)d.blocks_w[c] * d.blocks_h[c];
                 max_blocks = blocks > max_blocks ? blocks : max_blocks;

@@ -6,14 +6,7 @@
 
 namespace sd {
 
-// the workspace holds frame after frame, component after component, each padded u8 plane at a 256-byte boundary
-inline size_t jpeg_plane_slot(const sd_jpeg_frame_desc& d, int c) { return ((size_t)d.blocks_w[c] * d.blocks_h[c] * 64 + 255) / 256 * 256; }
-inline size_t jpeg_workspace_bytes(const sd_jpeg_frame_desc* descs, int B) {
-    size_t n = 0;
-    for (int b = 0; b < B; ++b)
-        for (int c = 0; c < descs[b].ncomp; ++c) n += jpeg_plane_slot(descs[b], c);
-    return n;
-}
+// workspace: sdjpeg::take_planes / sdjpeg::workspace_bytes (jpeg_common.hpp)
 
 // every descriptor must have passed sdjpeg::desc_ok and the buffers must hold what the descriptors imply (capi.cpp checks both)
 hipError_t launch_jpeg_reconstruct(const int16_t* coef, size_t frame_stride_elems, const sd_jpeg_frame_desc* descs, int B, uint8_t* bgr,

@@ -329,4 +329,22 @@ inline bool args_ok(size_t byte_stride, const sd_jpeg_frame_desc* descs, const s
     return true;
 }
 
+// ---- workspace of the device route (jpeg_sync_gpu.hip) for frames of at most P pieces, P = max_pieces rounded up to whole workgroups of
+// kGroup (at least one); every part 16-byte aligned
+inline size_t piece_stride(size_t max_pieces) {
+    const size_t g = kGroup;
+    return (max_pieces < 1 ? 1 : (max_pieces + g - 1) / g) * g;
+}
+struct Layout : sdarena::Walker {
+    size_t B, stride, P;
+    Layout(int B_, size_t interval_stride, size_t max_pieces) : B((size_t)B_), stride(interval_stride), P(piece_stride(max_pieces)) {}
+    size_t frames = take(B * sizeof(sd_jpeg_sync_frame), 16);                     // the launcher's three uploads
+    size_t tables = take(B * kTables * sizeof(sd_jpeg_huff_table), 16);           // [B][kTables]
+    size_t intervals = take(B * stride * sizeof(sd_jpeg_sync_interval), 16);      // [B][interval_stride]
+    size_t rec = take(B * P * sizeof(Rec), 16);                                   // Rec [B][P]: the pieces' records
+    size_t group_end = take(B * (P / kGroup) * sizeof(Rec), 16);                  // Rec [B][P / kGroup]: the workgroups' end records
+    size_t before = take(B * P * sizeof(uint32_t), 16);                           // u32 [B][P]: the unit ordinals
+    size_t total = end(16);
+};
+
 }  // namespace sdjsync

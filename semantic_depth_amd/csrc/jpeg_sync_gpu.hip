@@ -250,21 +250,16 @@ hipError_t launch_jpeg_sync_decode(const uint8_t* bytes, size_t byte_stride, con
                                    size_t interval_stride, const sd_jpeg_huff_table* tables_host, int B, int subseq_bytes, size_t max_pieces, int16_t* coef,
                                    size_t coef_stride_elems, int32_t* status, uint8_t* workspace, hipStream_t s) {
     SyncArgs a{};
-    const size_t P = jpeg_sync_piece_stride(max_pieces);
+    const size_t P = sdjsync::piece_stride(max_pieces);
     a.bytes = bytes; a.byte_stride = byte_stride; a.interval_stride = interval_stride; a.coef = coef; a.coef_stride = coef_stride_elems; a.status = status;
     a.piece_stride = P; a.S = (uint32_t)subseq_bytes;
-    uint8_t* w = workspace;
-    sd_jpeg_sync_frame* frames = reinterpret_cast<sd_jpeg_sync_frame*>(w);
-    w += jpeg_sync_part((size_t)B * sizeof(sd_jpeg_sync_frame));
-    sd_jpeg_huff_table* tables = reinterpret_cast<sd_jpeg_huff_table*>(w);
-    w += jpeg_sync_part((size_t)B * kTables * sizeof(sd_jpeg_huff_table));
-    sd_jpeg_sync_interval* intervals = reinterpret_cast<sd_jpeg_sync_interval*>(w);
-    w += jpeg_sync_part((size_t)B * interval_stride * sizeof(sd_jpeg_sync_interval));
-    a.rec = reinterpret_cast<Rec*>(w);
-    w += jpeg_sync_part((size_t)B * P * sizeof(Rec));
-    a.group_end = reinterpret_cast<Rec*>(w);
-    w += jpeg_sync_part((size_t)B * (P / kGroup) * sizeof(Rec));
-    a.before = reinterpret_cast<uint32_t*>(w);
+    const sdjsync::Layout l(B, interval_stride, max_pieces);
+    sd_jpeg_sync_frame* frames = reinterpret_cast<sd_jpeg_sync_frame*>(workspace + l.frames);
+    sd_jpeg_huff_table* tables = reinterpret_cast<sd_jpeg_huff_table*>(workspace + l.tables);
+    sd_jpeg_sync_interval* intervals = reinterpret_cast<sd_jpeg_sync_interval*>(workspace + l.intervals);
+    a.rec = reinterpret_cast<Rec*>(workspace + l.rec);
+    a.group_end = reinterpret_cast<Rec*>(workspace + l.group_end);
+    a.before = reinterpret_cast<uint32_t*>(workspace + l.before);
     a.frames = frames; a.tables = tables; a.intervals = intervals;
     hipError_t e = hipMemcpyAsync(frames, frames_host, (size_t)B * sizeof(sd_jpeg_sync_frame), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return e;

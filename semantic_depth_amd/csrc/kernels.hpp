@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tail_layout.hpp"
+
 namespace sd {
 
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
@@ -296,7 +298,7 @@ bool conv_smalln_tiled(Planes in_fmt, int k, int W, int C, int nout);   // the L
 hipError_t launch_pre_vgg(const uint8_t* frames, float* out, long npix, Planes fmt, size_t plane, hipStream_t s);                 // K1
 hipError_t launch_pre_mono(const uint8_t* frames, float* out, int B, int H, int W, Planes fmt, size_t plane, int raw, hipStream_t s);      // /255 (raw: not) + fliplr pair
 hipError_t launch_maxpool2(const float* x, float* y, int N, int H, int W, int C, Planes fmt, size_t plane_in, size_t plane_out, hipStream_t s);
-constexpr int SAT_IMG_PAD = 512;       // per-image clamp slots past a pass's images: the rows of a partial last GEMM tile (< 512) past the last image
+// (SAT_IMG_PAD, the per-image clamp slots past a pass's images: handle_arena.hpp)
 // behind a pass: add the per-image fp16 clamp counts img[0..nimg) into frames[i >> shift], those of the slots past nimg into *orphans,
 // and zero all nslots of them (ops_misc.hip)
 hipError_t launch_sat_fold(unsigned* img, unsigned* frames, unsigned* orphans, int nimg, int shift, int nslots, hipStream_t s);
@@ -314,7 +316,7 @@ hipError_t launch_deconv16s8_head(const float* x, const float* w, const float* b
 // ---------------------------------------------------------------------------------------------
 // fusion (fuse.hip; compiled with -ffp-contract=off: bit-exact vs numpy / OpenCV arithmetic)
 // ---------------------------------------------------------------------------------------------
-struct CamDev { double q[16]; float mult; };   // Q rounded to f32 then widened; multiplier as f32
+// (CamDev and the scratch layouts of fuse.hip and pcl.hip: tail_layout.hpp)
 hipError_t launch_post_process(const float* disp_raw, float* disp_pp, int B, int H, int W, hipStream_t s);
 // resize.hip: cv2.INTER_CUBIC for u8 frames; xi/xa (yi/ya): [dw][4] ([dh][4]) tap indices and fixed-point weights (device)
 hipError_t launch_resize_cubic_u8(const uint8_t* src, uint8_t* dst, int B, int sh, int sw, int dh, int dw, int C, const int* xi, const int* xa,
@@ -349,9 +351,7 @@ struct FuseParams {
     int32_t* lb_ticket;        // scratch [B]: arrival tickets (zero between launches)
     unsigned epoch;            // 1..1023, different from the previous launch on this scratch (0 = freshly zeroed scratch)
 };
-size_t fuse_onepass_scratch_bytes(int B, int H, int W);
 bool fuse_onepass_eligible(const FuseParams& p);
-size_t fuse_scratch_bytes(int B, int H, int W);
 hipError_t launch_fuse(const FuseParams& p, hipStream_t s);
 // camera sweep (fuse.hip fuse_sweep_write_kernel): T trial cameras per frame behind one count + scan; slot t * B + b of the outputs
 struct SweepParams {
@@ -365,8 +365,7 @@ struct SweepParams {
     int32_t* blk_offsets;      // workspace [B][nblk][2]
     unsigned sw;               // Switch bits of the handle (SW_NO_FUSE4: one pixel per thread)
 };
-size_t fuse_sweep_workspace_bytes(int B, int T, int H, int W);
-void fuse_sweep_layout(SweepParams& p, uint8_t* workspace);             // sets cams, blk_counts, blk_offsets from B, T, H, W
+void fuse_sweep_carve(SweepParams& p, uint8_t* workspace);             // sets cams, blk_counts, blk_offsets from SweepLayout(B, T, H, W)
 hipError_t launch_fuse_sweep(const SweepParams& p, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
@@ -384,8 +383,7 @@ struct CloudView { const float* xyz; const uint8_t* rgb; const int32_t* n; };   
 struct CloudOut { float* xyz; uint8_t* rgb; int32_t* n; };
 
 enum FilterKind { F_LT_NEG = 0 /* coord < -t */, F_ABS_LT = 1 /* |coord| < t */ };
-// cscratch (nullable, cmp_scratch_bytes(B)): with it and in != out the ordered compaction runs on 64 workgroups per frame
-size_t cmp_scratch_bytes(int B);
+// cscratch (nullable, CmpLayout(B).total bytes): with it and in != out the ordered compaction runs on 64 workgroups per frame
 hipError_t launch_filter_coord(CloudView in, CloudOut out, int B, int cap, int kind, int axis, double t, void* cscratch, hipStream_t s);
 hipError_t launch_mad_filter(CloudView in, CloudOut out, int B, int cap, int axis, double thr, float* stats, void* cscratch, hipStream_t s);
 hipError_t launch_plane_filter(CloudView in, CloudOut out, int B, int cap, int axis, double thr, double* coeff, void* cscratch, hipStream_t s);
@@ -406,7 +404,7 @@ hipError_t launch_f2f(const double* road_plane, const double* left_plane, const 
                       const int32_t* cnt /* [7][B] */, F2fResultDev* out, hipStream_t s);
 hipError_t launch_gather_planes(const RwResultDev* res, int B, double* planes, hipStream_t s);
 hipError_t launch_end_points(CloudView in, int B, int cap, double depth, double window, RwResultDev* res, hipStream_t s);
-size_t o3d_scratch_bytes(int B, int cap);
+// scratch: O3dLayout(B, cap).total bytes
 hipError_t launch_sor(CloudView in, CloudOut out, int B, int cap, int k, double ratio, void* scratch, double* mean_out, void* cscratch,
                       hipStream_t s);
 hipError_t launch_ror(CloudView in, CloudOut out, int B, int cap, int nb, double radius, void* scratch, void* cscratch, hipStream_t s);

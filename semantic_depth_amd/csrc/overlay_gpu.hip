@@ -176,9 +176,10 @@ __global__ __launch_bounds__(kThreads) void overlay_raster_kernel(OverlayArgs a)
 }  // namespace
 
 void overlay_layout(OverlayArgs& a, uint8_t* workspace) {
-    a.cams = reinterpret_cast<OverlayCamDev*>(workspace);
-    a.heads = reinterpret_cast<OverlayFrameHead*>(workspace + (size_t)a.B * sizeof(OverlayCamDev));
-    a.slots = reinterpret_cast<OverlaySlot*>(workspace + (size_t)a.B * (sizeof(OverlayCamDev) + sizeof(OverlayFrameHead)));
+    const sdoverlay::Layout l(a.B, a.D);
+    a.cams = reinterpret_cast<OverlayCamDev*>(workspace + l.cams);
+    a.heads = reinterpret_cast<OverlayFrameHead*>(workspace + l.heads);
+    a.slots = reinterpret_cast<OverlaySlot*>(workspace + l.slots);
 }
 
 hipError_t launch_overlay_draw(OverlayArgs a, hipStream_t s) {

@@ -9,7 +9,9 @@
 // of two products below 2^48: below 2^49 < 2^50.  |w|^2, |P - B|^2 and |d|^2 are below 2^49 as well, r^2 = (128 * 32)^2 = 2^24; all of these
 // fit an int64.  r^2 |d|^2 < 2^73 and (w x d)^2 < 2^98 do not: hit() forms both as 128-bit products.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -17,7 +19,11 @@
 #include "../../include/semdepth.h"
 #include "text_draw.hpp"
 
+#if defined(__HIPCC__)
 #define SDOVL_HD __host__ __device__ inline
+#else
+#define SDOVL_HD inline
+#endif
 
 namespace sdoverlay {
 
@@ -144,5 +150,30 @@ SDOVL_HD bool seg_box(const sd_overlay_segment& s, int h, int w, int clip_top, i
     box[3] = y1 > h - 1 ? h - 1 : y1;
     return box[0] <= box[2] && box[1] <= box[3];
 }
+
+// ---- workspace of the device route (overlay_gpu.hip)
+// a frame's camera as the host stages it: cx, cy, f rounded to float32 and promoted
+struct CamDev {
+    double cx, cy, f, pad;
+};
+// what overlay_setup_kernel leaves per frame for overlay_raster_kernel: the union of the boxes of the frame's valid slots (empty: x0 > x1)
+struct FrameHead {
+    int32_t box[4];
+};
+// ... and per slot: the segment, whether it paints at all (a valid segment with a non-empty box) and that box
+struct Slot {
+    sd_overlay_segment seg;
+    int32_t valid;
+    int32_t box[4];      // x0, y0, x1, y1, clipped to rows clip_top .. h - 1 of the frame
+};
+static_assert(sizeof(CamDev) == 32 && sizeof(FrameHead) == 16 && sizeof(Slot) == 40, "overlay workspace layout");
+struct Layout : sdarena::Walker {
+    size_t B, nslots;
+    Layout(int B_, int D) : B((size_t)B_), nslots((size_t)B_ * slots_of(D)) {}
+    size_t cams = take(B * sizeof(CamDev), 16);           // CamDev [B], 16-byte aligned: the caller's upload
+    size_t heads = take(B * sizeof(FrameHead), 16);       // FrameHead [B], 16
+    size_t slots = take(nslots * sizeof(Slot), 16);       // Slot [B][slots_of(D)], 16
+    size_t total = end();
+};
 
 }  // namespace sdoverlay

@@ -300,22 +300,14 @@ __device__ void block_compact(const float* __restrict__ xyz, const uint8_t* __re
 // below compute their per-frame statistics with one workgroup as before (COMPACT = false: statistics only, written to the
 // frame's parameter record) and leave the data movement to these two kernels.
 constexpr int CMP_G = 64;            // slices (workgroups) per frame
-constexpr int CMP_PARAMS = 8;        // doubles per frame: MAD {median, mad}; plane {C0, C1, C2}; statistical filter {threshold}
-struct MedG { unsigned klo, khi, cnt, below, nan, done; float med, madv; };      // per-frame state of a multi-block median
+static_assert(CMP_G == CMP_SLICES && MED_CAP == CMP_MED_KEYS, "CmpLayout (tail_layout.hpp) sizes the scratch from these two");
+// (CMP_PARAMS doubles per frame and the scratch itself: CmpLayout, tail_layout.hpp)
 struct CmpScratch { int* blk_cnt; double* params; MedG* med; unsigned* medbuf; };
-size_t cmp_scratch_bytes(int B) {
-    return (size_t)B * (CMP_G * sizeof(int) + CMP_PARAMS * sizeof(double) + sizeof(MedG) + (size_t)MED_CAP * sizeof(unsigned)) + 1024;
-}
 static CmpScratch cmp_carve(void* base, int B) {
-    CmpScratch c;
-    c.params = reinterpret_cast<double*>(base);
-    char* q = reinterpret_cast<char*>(base) + ((size_t)B * CMP_PARAMS * sizeof(double) + 255) / 256 * 256;
-    c.blk_cnt = reinterpret_cast<int*>(q);
-    q += ((size_t)B * CMP_G * sizeof(int) + 255) / 256 * 256;
-    c.med = reinterpret_cast<MedG*>(q);
-    q += ((size_t)B * sizeof(MedG) + 255) / 256 * 256;
-    c.medbuf = reinterpret_cast<unsigned*>(q);
-    return c;
+    char* q = reinterpret_cast<char*>(base);
+    const CmpLayout l(B);
+    return {reinterpret_cast<int*>(q + l.blk_cnt), reinterpret_cast<double*>(q + l.params), reinterpret_cast<MedG*>(q + l.med),
+            reinterpret_cast<unsigned*>(q + l.medbuf)};
 }
 __device__ __forceinline__ void cmp_slice(int n, int g, int& lo, int& hi) {
     const int S = ((n + CMP_G - 1) / CMP_G + 255) / 256 * 256;
@@ -880,16 +872,12 @@ hipError_t launch_gather_planes(const RwResultDev* res, int B, double* planes, h
 //   statistical filter: cell size adapts to the cloud (~6 points per cell), shells until kth d2 <= (shell*cell)^2
 //   radius filter     : cell = radius/4; cells entirely inside the ball are counted without touching their points,
 //                       cells entirely outside are skipped, the search stops as soon as the count exceeds nb_points
-constexpr int GRID_CELLS = 1 << 19;
-constexpr int KMAX = 16;
+// (GRID_CELLS, KMAX, the scan segments, GridMeta and the scratch itself: O3dLayout, tail_layout.hpp)
 constexpr int SOR_RMAX = 16;       // shells searched before the brute-force fallback
 constexpr int SOR_RSOFT = 2;       // shells searched one-thread-per-query (99 % of a dense cloud end here); a query that needs more
                                    // hands its k best so far to the wave-cooperative kernel, which continues at the next shell
                                    // (RSOFT = 1 measured: per-thread kernel 2.95 -> 2.64 ms, cooperative kernel 0.55 -> 1.37 ms)
-constexpr int SCAN_SEG = 2048;     // cells per scan segment
-constexpr int SCAN_NSEG = GRID_CELLS / SCAN_SEG;
 
-struct GridMeta { double ox, oy, oz, inv; double cell; int gx, gy, gz, occupied; double ext[3], mn[3], mxz; int nonfinite, pad_; };
 // does the grid hold every finite point inside its NOMINAL cells along each axis (no clamping into the face layers)?  Then, with
 // no non-finite point in the cloud either, a face layer is an ordinary bounded cell.
 __device__ __forceinline__ bool grid_covers(const GridMeta& g) {
@@ -898,40 +886,20 @@ __device__ __forceinline__ bool grid_covers(const GridMeta& g) {
            g.mxz < g.oz + (double)g.gz * g.cell * m && g.ox <= g.mn[0] && g.oy <= g.mn[1];
 }
 
-struct O3dScratch {       // carved from one arena, per-frame strides
-    GridMeta* meta;       // [B]
-    int* cell_cnt;        // [B][GRID_CELLS]      counts, then scatter cursors; behind them [B][8] bounding-box accumulators
-    int* cell_start;      // [B][GRID_CELLS + 1]
-    int* seg_sum;         // [B][SCAN_NSEG]
-    int* cell_of;         // [B][cap]
-    int* sidx;            // [B][cap]  original index of the j-th sorted point
-    float* sxyz;          // [B][cap][4]: the cell-sorted copy, one 16-byte load per candidate (w unused)
-    double* mean_d;       // [B][cap]  (by original index)
-    uint8_t* keep;        // [B][cap]
-    int* hard_n;          // [B]  statistical filter: queries deferred to the wave-cooperative search (list in cell_of)
-    double* hard_best;    // [B][cap][KMAX]  their k best distances after the per-thread shells (ascending, inf padded)
+struct O3dScratch {       // the regions of O3dLayout as pointers
+    GridMeta* meta;
+    int *cell_cnt, *cell_start, *seg_sum, *cell_of, *sidx;
+    float* sxyz;
+    double* mean_d;
+    uint8_t* keep;
+    int* hard_n;
+    double* hard_best;
 };
-size_t o3d_scratch_bytes(int B, int cap) {
-    size_t per = sizeof(GridMeta) + (size_t)GRID_CELLS * 4 + (size_t)(GRID_CELLS + 1) * 4 + SCAN_NSEG * 4 + (size_t)cap * (4 + 4 + 16 + 8 + 1) +
-                 (size_t)cap * KMAX * 8;
-    return (size_t)B * (per + 4 + 32) + 8192 + 256;
-}
 static O3dScratch carve(void* base, int B, int cap) {
-    O3dScratch s;
     char* p = (char*)base;
-    auto take = [&](size_t bytes) { char* r = p; p += (bytes + 255) / 256 * 256; return r; };
-    s.meta = (GridMeta*)take(sizeof(GridMeta) * B);
-    s.mean_d = (double*)take((size_t)B * cap * 8);
-    s.cell_cnt = (int*)take((size_t)B * GRID_CELLS * 4 + (size_t)B * 32);
-    s.cell_start = (int*)take((size_t)B * (GRID_CELLS + 1) * 4);
-    s.seg_sum = (int*)take((size_t)B * SCAN_NSEG * 4);
-    s.cell_of = (int*)take((size_t)B * cap * 4);
-    s.sidx = (int*)take((size_t)B * cap * 4);
-    s.sxyz = (float*)take((size_t)B * cap * 16);
-    s.keep = (uint8_t*)take((size_t)B * cap);
-    s.hard_n = (int*)take((size_t)B * 4);
-    s.hard_best = (double*)take((size_t)B * cap * KMAX * 8);
-    return s;
+    const O3dLayout l(B, cap);
+    return {(GridMeta*)(p + l.meta), (int*)(p + l.cell_cnt), (int*)(p + l.cell_start), (int*)(p + l.seg_sum), (int*)(p + l.cell_of), (int*)(p + l.sidx),
+            (float*)(p + l.sxyz), (double*)(p + l.mean_d), (uint8_t*)(p + l.keep), (int*)(p + l.hard_n), (double*)(p + l.hard_best)};
 }
 
 __device__ __forceinline__ int cell_coord(double p, double o, double inv, int g) {

@@ -20,6 +20,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "arena.hpp"
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define SDPIL_HD __host__ __device__
 #else
@@ -96,17 +98,25 @@ constexpr int32_t kHalf = 1 << (kPrecisionBits - 1);
 // the counter a pixel adds to: cell 3 * class(label) + prediction, or cell 9 for a prediction that names no class
 SDPIL_HD inline int seg_cell(int table_class, int pred) { return pred > 2 ? 9 : table_class * 3 + pred; }
 
-// ---- workspace of the device route (seg_eval_gpu.hip): [x bounds][x k][y bounds][y k][intermediate], every part 16-byte aligned
-inline size_t al16(size_t v) { return (v + 15) / 16 * 16; }
 // the longest window an axis can have, without making the windows: 2 * support + 1 rounded up
 inline int taps_bound(int in, int out) {
     const long long f = in > out ? ((long long)in + out - 1) / out : 1;
     return (int)(2 * f + 1);
 }
-inline size_t tables_bytes(int in, int out) { return al16((size_t)out * 2 * 4) + al16((size_t)taps_bound(in, out) * out * 4); }
 inline size_t mid_pitch(int dst_w, int channels) { return ((size_t)dst_w * channels + 3) / 4 * 4; }     // dword rows for the vertical pass
-inline size_t workspace_bytes(int B, int src_h, int src_w, int dst_h, int dst_w, int channels) {
-    return tables_bytes(src_w, dst_w) + tables_bytes(src_h, dst_h) + al16((size_t)B * src_h * mid_pitch(dst_w, channels));
-}
+
+// ---- workspace of the device route (seg_eval_gpu.hip); every part 16-byte aligned
+struct Layout : sdarena::Walker {
+    size_t B, sh, sw, dh, dw, pitch;
+    Layout(int B_, int src_h, int src_w, int dst_h, int dst_w, int channels)
+        : B((size_t)B_), sh((size_t)src_h), sw((size_t)src_w), dh((size_t)dst_h), dw((size_t)dst_w), pitch(mid_pitch(dst_w, channels)) {}
+    size_t x_bounds = take(dw * 2 * 4, 16);                               // i32 [dst_w][2]: first source sample and length of every x window
+    size_t x_k = take(taps_bound((int)sw, (int)dw) * dw * 4, 16);         // i32 [dst_w][taps_bound(src_w, dst_w)]: their weights
+    size_t y_bounds = take(dh * 2 * 4, 16);                               // i32 [dst_h][2]
+    size_t y_k = take(taps_bound((int)sh, (int)dh) * dh * 4, 16);         // i32 [dst_h][taps_bound(src_h, dst_h)]
+    size_t mid = take(B * sh * pitch, 16);                                // u8 [B][src_h][mid_pitch]: the horizontal pass's rows, read by the vertical pass
+    size_t total = end(16);
+};
+inline size_t workspace_bytes(int B, int src_h, int src_w, int dst_h, int dst_w, int channels) { return Layout(B, src_h, src_w, dst_h, dst_w, channels).total; }
 
 }  // namespace sdpil

@@ -4,11 +4,19 @@
 // on every digit; what differs is only who walks the rows (one loop on the host, one lane per row on the device).  The text is that of
 // outputs.rw_ply_bytes (point_cloud_2_ply.py's header and "%f %f %f %d %d %d" rows behind its minimum-z filter).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
 #include <stddef.h>
 #include <stdint.h>
 
+#include "arena.hpp"
+
+#if defined(__HIPCC__)
 #define SDPLY_HD __host__ __device__ inline
+#else
+#define SDPLY_HD inline
+#endif
 
 namespace sdply {
 
@@ -205,5 +213,20 @@ SDPLY_HD void row_point(const Frame& f, int r, double* p, uint8_t* c) {
     c[1] = 0;
     c[2] = 0;
 }
+
+// ---- workspace of the device route (ply_gpu.hip): the declarations are the walk; packed, every region ends on a multiple of the next one's alignment
+struct Layout : sdarena::Walker {
+    size_t nb, B;       // row blocks of all frames (nblk = blocks_per_frame(cap) each), frames
+    Layout(int B_, int cap) : nb((size_t)B_ * blocks_per_frame(cap)), B((size_t)B_) {}
+    size_t bmin = take(nb * 8, 8);       // f64 [B][nblk], 8-byte aligned: per row block the minimum z of its rows
+    size_t boff = take(nb * 8, 8);       // u64 [B][nblk], 8: the block's offset inside the frame's rows
+    size_t zmin = take(B * 8, 8);        // f64 [B], 8: the frame's minimum z
+    size_t fbase = take(B * 8, 8);       // u64 [B], 8: where the frame's rows begin in the text
+    size_t blen = take(nb * 4, 4);       // u32 [B][nblk], 4: the block's bytes
+    size_t bcnt = take(nb * 4, 4);       // u32 [B][nblk], 4: its kept rows
+    size_t bbad = take(nb * 4, 4);       // u32 [B][nblk], 4: its range verdict
+    size_t slack = end();                // 64 bytes of historical slack: nothing reads or writes them
+    size_t total = end_with_slack(64);
+};
 
 }  // namespace sdply

@@ -252,17 +252,18 @@ __global__ __launch_bounds__(kThreads) void ply_rows_kernel(PlyArgs a) {
 
 hipError_t launch_ply_format(const float* xyz, const uint8_t* rgb, const int32_t* n, int B, int cap, const sd_rw_result* records, uint8_t* text,
                              size_t capacity, uint64_t* offsets, int32_t* flags, uint8_t* workspace, hipStream_t s) {
-    const size_t nblk = blocks_per_frame(cap), nb = (size_t)B * nblk;
+    const size_t nblk = blocks_per_frame(cap);
     PlyArgs a{};
     a.xyz = xyz; a.rgb = rgb; a.n = n; a.records = records; a.B = B; a.cap = cap; a.nblk = (uint32_t)nblk;
     a.text = text; a.capacity = capacity; a.offsets = offsets; a.flags = flags;
-    a.bmin = reinterpret_cast<double*>(workspace);
-    a.boff = reinterpret_cast<uint64_t*>(a.bmin + nb);
-    a.zmin = reinterpret_cast<double*>(a.boff + nb);
-    a.fbase = reinterpret_cast<uint64_t*>(a.zmin + B);
-    a.blen = reinterpret_cast<uint32_t*>(a.fbase + B);
-    a.bcnt = a.blen + nb;
-    a.bbad = a.bcnt + nb;
+    const Layout l(B, cap);
+    a.bmin = reinterpret_cast<double*>(workspace + l.bmin);
+    a.boff = reinterpret_cast<uint64_t*>(workspace + l.boff);
+    a.zmin = reinterpret_cast<double*>(workspace + l.zmin);
+    a.fbase = reinterpret_cast<uint64_t*>(workspace + l.fbase);
+    a.blen = reinterpret_cast<uint32_t*>(workspace + l.blen);
+    a.bcnt = reinterpret_cast<uint32_t*>(workspace + l.bcnt);
+    a.bbad = reinterpret_cast<uint32_t*>(workspace + l.bbad);
     const dim3 grid((unsigned)nblk, (unsigned)B);
     hipLaunchKernelGGL(ply_scan_kernel, grid, dim3(kThreads), 0, s, a);
     hipLaunchKernelGGL(ply_min_kernel, dim3((unsigned)B), dim3(kThreads), 0, s, a);

@@ -4,11 +4,19 @@
 // call these functions, so they agree on every tie and every bit; what differs is only who walks the bytes (one loop on the host, one
 // workgroup per chunk on the device).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
 #include <stddef.h>
 #include <stdint.h>
 
+#include "arena.hpp"
+
+#if defined(__HIPCC__)
 #define SDPNG_HD __host__ __device__ inline
+#else
+#define SDPNG_HD inline
+#endif
 
 namespace sdpng {
 
@@ -225,5 +233,19 @@ SDPNG_HD void adler_append(uint32_t& a, uint32_t& b, uint32_t len, uint32_t A, u
     b = (uint32_t)((b + (uint64_t)(len % kAdlerMod) * a + Bsum) % kAdlerMod);
     a = (a + A) % kAdlerMod;
 }
+
+// ---- workspace of the device route (png_gpu.hip)
+constexpr size_t kSlot = kChunk + kChunkSlack;
+struct Layout : sdarena::Walker {
+    size_t n;                        // chunks of all frames
+    Layout(int B, int h, int w) : n((size_t)B * num_chunks(h, w)) {}
+    size_t slots = take(n * kSlot, 16);    // u8 [n][kSlot], 16-byte aligned: the coded chunks
+    size_t offsets = take(n * 8, 8);       // u64 [n], 8: a chunk's offset inside its frame's stream
+    size_t csize = take(n * 4, 4);         // u32 [n], 4: its coded size
+    size_t adler_a = take(n * 4, 4);       // u32 [n], 4: its two Adler partials
+    size_t adler_b = take(n * 4, 4);       // u32 [n], 4
+    size_t slack = end();                  // 64 bytes of historical slack: nothing reads or writes them
+    size_t total = end_with_slack(64);
+};
 
 }  // namespace sdpng

@@ -296,15 +296,15 @@ __global__ __launch_bounds__(kThreads) void png_gather_kernel(PngArgs a) {
 hipError_t launch_png_encode(const uint8_t* frames, size_t frame_stride, int B, int h, int w, uint8_t* streams, size_t stream_stride,
                              uint64_t* sizes, uint8_t* workspace, hipStream_t s) {
     const size_t nch = sdpng::num_chunks(h, w);
-    const size_t n = (size_t)B * nch;
     PngArgs a{};
     a.frames = frames; a.frame_stride = frame_stride; a.h = h; a.w = w; a.nchunks = (uint32_t)nch;
     a.streams = streams; a.stream_stride = stream_stride; a.sizes = sizes;
-    a.slots = workspace;
-    a.offsets = reinterpret_cast<uint64_t*>(workspace + n * kPngSlot);
-    a.csize = reinterpret_cast<uint32_t*>(a.offsets + n);
-    a.adler_a = a.csize + n;
-    a.adler_b = a.adler_a + n;
+    const sdpng::Layout l(B, h, w);
+    a.slots = workspace + l.slots;
+    a.offsets = reinterpret_cast<uint64_t*>(workspace + l.offsets);
+    a.csize = reinterpret_cast<uint32_t*>(workspace + l.csize);
+    a.adler_a = reinterpret_cast<uint32_t*>(workspace + l.adler_a);
+    a.adler_b = reinterpret_cast<uint32_t*>(workspace + l.adler_b);
     hipLaunchKernelGGL(png_chunk_kernel, dim3((unsigned)nch, (unsigned)B), dim3(kThreads), 0, s, a);
     hipLaunchKernelGGL(png_layout_kernel, dim3((unsigned)B), dim3(kThreads), 0, s, a);
     hipLaunchKernelGGL(png_gather_kernel, dim3((unsigned)nch, (unsigned)B), dim3(kThreads), 0, s, a);

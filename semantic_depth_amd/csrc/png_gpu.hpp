@@ -6,13 +6,8 @@
 
 namespace sd {
 
-// workspace of B frames of n chunks each: [B * n] chunk slots of kChunk + kChunkSlack bytes, then per chunk its coded size, the two
-// Adler partials (u32 each) and its offset inside the frame's stream (u64)
-constexpr size_t kPngSlot = sdpng::kChunk + sdpng::kChunkSlack;
-inline size_t png_workspace_bytes(int B, int h, int w) {
-    const size_t n = (size_t)B * sdpng::num_chunks(h, w);
-    return n * kPngSlot + n * (3 * sizeof(uint32_t) + sizeof(uint64_t)) + 64;
-}
+// workspace: sdpng::Layout (png_deflate.hpp)
+constexpr size_t kPngSlot = sdpng::kSlot;
 
 // frames u8 [B,h,w,3] BGR at frame_stride -> one zlib stream per frame at streams + b * stream_stride, sizes[b] = its bytes.  The caller
 // has checked the extents (1..16384), stream_stride >= sdpng::stream_bound and the workspace size.  Three launches on s, no synchronisation.

@@ -216,7 +216,7 @@ hipError_t launch(const uint8_t* rows, size_t frame_stride, const sd_png_frame_d
 
 hipError_t launch_png_reconstruct(const uint8_t* rows, size_t frame_stride, const sd_png_frame_desc* descs_host, int B, int height, int width,
                                   uint8_t* out, size_t out_stride, int32_t* status, uint8_t* workspace, int waves, hipStream_t s) {
-    sd_png_frame_desc* descs = reinterpret_cast<sd_png_frame_desc*>(workspace);
+    sd_png_frame_desc* descs = reinterpret_cast<sd_png_frame_desc*>(workspace + sdpngin::Layout(B).descs);
     hipError_t e = hipMemcpyAsync(descs, descs_host, (size_t)B * sizeof(sd_png_frame_desc), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return e;
     return waves == 1 ? launch<1>(rows, frame_stride, descs, B, height, width, out, out_stride, status, s)

@@ -7,8 +7,7 @@
 
 namespace sd {
 
-// workspace of B frames: [B] sd_png_frame_desc, rounded up to 16 bytes
-inline size_t png_in_workspace_bytes(int B) { return ((size_t)B * sizeof(sd_png_frame_desc) + 15) & ~(size_t)15; }
+// workspace: sdpngin::Layout (png_unfilter.hpp)
 
 // bytes of frame_stride a frame of `channels` needs: its rows, rounded up to the 16-byte pieces the lanes load
 inline size_t png_in_rows_bytes(int height, int width, int channels) {

@@ -4,6 +4,9 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/semdepth.h"
+#include "arena.hpp"
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define SDPNGIN_HD __host__ __device__ inline
 #else
@@ -57,5 +60,12 @@ SDPNGIN_HD uint32_t to_bgr(int ctype, uint32_t px) {
     if (ctype == 2 || ctype == 6) return ((px >> 16) & 255) | (px & 0xFF00) | ((px & 255) << 16);
     return (px & 255) * 0x010101u;
 }
+
+// ---- workspace of the device route (png_in_gpu.hip)
+struct Layout : sdarena::Walker {
+    explicit Layout(int B) : descs(take((size_t)B * sizeof(sd_png_frame_desc), 16)) {}
+    size_t descs;                // sd_png_frame_desc [B], 16-byte aligned: the launcher's upload
+    size_t total = end(16);
+};
 
 }  // namespace sdpngin

@@ -165,10 +165,11 @@ hipError_t launch_render_rw(const float* xyz, const uint8_t* rgb, const int32_t*
     RenderArgs a{};
     a.xyz = xyz; a.rgb = rgb; a.n = n; a.records = records; a.B = B; a.cap = cap; a.nblk = (uint32_t)nblk;
     a.cam = cam; a.dst = dst; a.flags = flags;
-    a.pixels = render_key_count(B, cam);
-    a.keys = reinterpret_cast<unsigned long long*>(workspace);
-    a.bmin = reinterpret_cast<double*>(a.keys + a.pixels);
-    a.zmin = a.bmin + (size_t)B * nblk;
+    a.pixels = sdrender::key_count(B, cam);
+    const sdrender::Layout l(B, cap, cam);
+    a.keys = reinterpret_cast<unsigned long long*>(workspace + l.keys);
+    a.bmin = reinterpret_cast<double*>(workspace + l.bmin);
+    a.zmin = reinterpret_cast<double*>(workspace + l.zmin);
     const dim3 grid((unsigned)nblk, (unsigned)B);
     hipLaunchKernelGGL(render_scan_kernel, grid, dim3(kThreads), 0, s, a);
     hipLaunchKernelGGL(render_min_kernel, dim3((unsigned)B), dim3(kThreads), 0, s, a);

@@ -7,12 +7,7 @@
 
 namespace sd {
 
-// workspace of B frames: the depth keys u64 [B,height,width] first (16-byte aligned with the workspace), then per 256-row block its minimum
-// z (f64) and per frame the minimum z (f64)
-inline size_t render_key_count(int B, const sd_render_camera& cam) { return (size_t)B * (size_t)cam.height * (size_t)cam.width; }
-inline size_t render_workspace_bytes(int B, int cap, const sd_render_camera& cam) {
-    return (render_key_count(B, cam) + (size_t)B * sdply::blocks_per_frame(cap) + (size_t)B) * sizeof(uint64_t) + 64;
-}
+// workspace: sdrender::Layout (render_rule.hpp)
 
 // xyz f32 [B,cap,3], rgb u8 [B,cap,3], n i32 [B], records [B] -> dst u8 [B,height,width,3] BGR, flags i32 [B].  The caller has checked B, cap,
 // the camera, the pointers and the workspace.  Five launches on s, no synchronisation.

@@ -93,4 +93,16 @@ SDPLY_HD void resolve(const sd_render_camera& c, uint64_t key, const uint8_t* rg
     out[2] = 250;
 }
 
+// ---- workspace of the device route (render_gpu.hip)
+inline size_t key_count(int B, const sd_render_camera& cam) { return (size_t)B * (size_t)cam.height * (size_t)cam.width; }
+struct Layout : sdarena::Walker {
+    size_t px, nb, B;
+    Layout(int B_, int cap, const sd_render_camera& cam) : px(key_count(B_, cam)), nb((size_t)B_ * sdply::blocks_per_frame(cap)), B((size_t)B_) {}
+    size_t keys = take(px * 8, 16);      // u64 [B][height][width], 16-byte aligned (with the workspace): the depth keys, cleared two at a time
+    size_t bmin = take(nb * 8, 8);       // f64 [B][blocks_per_frame(cap)], 8: per 256-row block its minimum z
+    size_t zmin = take(B * 8, 8);        // f64 [B], 8: the frame's minimum z
+    size_t slack = end();                // 64 bytes of historical slack: nothing reads or writes them
+    size_t total = end_with_slack(64);
+};
+
 }  // namespace sdrender

@@ -78,8 +78,9 @@ __global__ __launch_bounds__(RWP_THREADS) void rw_profile_merge_kernel(const flo
 
 hipError_t launch_rw_profile(const float* xyz, const int32_t* n, int B, int cap, int D, void* workspace, sd_rw_depth_result* results, hipStream_t s) {
     const int G = slices_of(cap);
-    const Window* windows = static_cast<const Window*>(workspace);
-    Partial* partial = reinterpret_cast<Partial*>(static_cast<uint8_t*>(workspace) + windows_bytes(D));
+    const Layout l(B, cap, D);
+    const Window* windows = reinterpret_cast<const Window*>(static_cast<uint8_t*>(workspace) + l.windows);
+    Partial* partial = reinterpret_cast<Partial*>(static_cast<uint8_t*>(workspace) + l.partial);
     hipLaunchKernelGGL(rw_profile_partial_kernel, dim3(G, B), dim3(RWP_THREADS), 0, s, xyz, n, cap, windows, D, partial);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;

@@ -12,6 +12,8 @@
 #include <cstdint>
 #include <cstring>
 
+#include "arena.hpp"
+
 #if defined(__HIPCC__)
 #define SD_RWP_HD __host__ __device__
 #else
@@ -149,10 +151,15 @@ inline int slices_of(int cap) {
     const long long g = ((long long)cap + RWP_SLICE - 1) / RWP_SLICE;
     return (int)std::min<long long>(std::max<long long>(g, 1), RWP_MAX_SLICES);
 }
-inline size_t windows_bytes(int D) { return ((size_t)D * sizeof(Window) + 15) / 16 * 16; }
-inline size_t workspace_bytes(int B, int cap, int D) {
-    return windows_bytes(D) + (size_t)B * slices_of(cap) * D * sizeof(Partial);
-}
+// ---- workspace of the device route (rw_profile.hip), 16-byte aligned
+struct Layout : sdarena::Walker {
+    size_t D, parts;
+    Layout(int B, int cap, int D_) : D((size_t)D_), parts((size_t)B * slices_of(cap) * D_) {}
+    size_t windows = take(D * sizeof(Window), 16);           // Window [D], sorted: the caller copies them here in stream order before the launches
+    size_t partial = take(parts * sizeof(Partial), 16);      // Partial [B][slices_of(cap)][D]: written by the first launch, read by the second
+    size_t total = end();
+};
+inline size_t workspace_bytes(int B, int cap, int D) { return Layout(B, cap, D).total; }
 
 // The D windows in ascending depth, each with the caller's index of its depth (a stable sort: equal depths keep the caller's order,
 // and each of them is a window of its own).  out has room for D records.

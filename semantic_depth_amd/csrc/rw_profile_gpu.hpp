@@ -6,8 +6,7 @@
 
 namespace sd {
 
-// workspace: sdrwp::workspace_bytes(B, cap, D) bytes, 16-byte aligned; its first sdrwp::windows_bytes(D) bytes hold the D sorted
-// sdrwp::Window records (the caller copies them there in stream order before this), the rest is written and read by the two launches.
+// workspace: sdrwp::Layout (rw_profile.hpp), 16-byte aligned; the caller copies the D sorted windows to its `windows` part in stream order before this.
 hipError_t launch_rw_profile(const float* xyz, const int32_t* n, int B, int cap, int D, void* workspace, sd_rw_depth_result* results, hipStream_t s);
 
 struct F2fDepths {

@@ -242,4 +242,17 @@ SDSCENE_HD void row_point(const SceneIn& in, const SegTable& t, uint32_t r, doub
     }
 }
 
+// ---- workspace of the device route (scene_gpu.hip): sdply::Layout's regions over nblk = blocks_bound(..., mask) row blocks, and a segment table per frame
+struct Layout : sdarena::Walker {
+    size_t nb, B;
+    Layout(int B_, int cap_road, int cap_fence, uint32_t lattice_cap, uint32_t mask)
+        : nb((size_t)B_ * (size_t)blocks_bound(cap_road, cap_fence, lattice_cap, mask)), B((size_t)B_) {}
+    size_t bmin = take(nb * 8, 8), boff = take(nb * 8, 8);                            // f64, u64 [B][nblk], 8-byte aligned
+    size_t zmin = take(B * 8, 8), fbase = take(B * 8, 8);                             // f64, u64 [B], 8
+    size_t tab = take(B * sizeof(SegTable), 8);                                       // SegTable [B], 8
+    size_t blen = take(nb * 4, 4), bcnt = take(nb * 4, 4), bbad = take(nb * 4, 4);    // u32 [B][nblk], 4
+    size_t slack = end();                                                             // 64 bytes of historical slack: nothing reads or writes them
+    size_t total = end_with_slack(64);
+};
+
 }  // namespace sdscene

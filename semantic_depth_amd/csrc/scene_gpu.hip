@@ -289,18 +289,19 @@ __global__ __launch_bounds__(kThreads) void scene_rows_kernel(SceneArgs a) {
 hipError_t launch_scene_format(const SceneBatch& in, uint8_t* text, size_t capacity, uint64_t* offsets, int32_t* flags, uint8_t* workspace,
                                hipStream_t s) {
     const int B = in.B;
-    const size_t nblk = (size_t)sdscene::blocks_bound(in.cap_road, in.cap_fence, in.lattice_cap, in.mask), nb = (size_t)B * nblk;
+    const size_t nblk = (size_t)sdscene::blocks_bound(in.cap_road, in.cap_fence, in.lattice_cap, in.mask);
     SceneArgs a{};
     a.in = in; a.nblk = (uint32_t)nblk;
     a.text = text; a.capacity = capacity; a.offsets = offsets; a.flags = flags;
-    a.bmin = reinterpret_cast<double*>(workspace);
-    a.boff = reinterpret_cast<uint64_t*>(a.bmin + nb);
-    a.zmin = reinterpret_cast<double*>(a.boff + nb);
-    a.fbase = reinterpret_cast<uint64_t*>(a.zmin + B);
-    a.tab = reinterpret_cast<SegTable*>(a.fbase + B);
-    a.blen = reinterpret_cast<uint32_t*>(a.tab + B);
-    a.bcnt = a.blen + nb;
-    a.bbad = a.bcnt + nb;
+    const sdscene::Layout l(B, in.cap_road, in.cap_fence, in.lattice_cap, in.mask);
+    a.bmin = reinterpret_cast<double*>(workspace + l.bmin);
+    a.boff = reinterpret_cast<uint64_t*>(workspace + l.boff);
+    a.zmin = reinterpret_cast<double*>(workspace + l.zmin);
+    a.fbase = reinterpret_cast<uint64_t*>(workspace + l.fbase);
+    a.tab = reinterpret_cast<SegTable*>(workspace + l.tab);
+    a.blen = reinterpret_cast<uint32_t*>(workspace + l.blen);
+    a.bcnt = reinterpret_cast<uint32_t*>(workspace + l.bcnt);
+    a.bbad = reinterpret_cast<uint32_t*>(workspace + l.bbad);
     const dim3 grid((unsigned)nblk, (unsigned)B);
     hipLaunchKernelGGL(scene_table_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, s, a);
     hipLaunchKernelGGL(scene_scan_kernel, grid, dim3(kThreads), 0, s, a);

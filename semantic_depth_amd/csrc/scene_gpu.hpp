@@ -19,11 +19,7 @@ struct SceneBatch {
     uint32_t mask, lattice_cap;
 };
 
-// workspace of B frames of nb = blocks_bound(..., mask) row blocks each: ply_gpu.hpp's slots per block and per frame, and a segment table per frame
-inline size_t scene_workspace_bytes(int B, int cap_road, int cap_fence, uint32_t lattice_cap, uint32_t mask) {
-    const size_t nb = (size_t)B * (size_t)sdscene::blocks_bound(cap_road, cap_fence, lattice_cap, mask);
-    return nb * (2 * sizeof(uint64_t) + 3 * sizeof(uint32_t)) + (size_t)B * (2 * sizeof(uint64_t) + sizeof(sdscene::SegTable)) + 64;
-}
+// workspace: sdscene::Layout (scene_format.hpp)
 inline size_t scene_text_bound(int B, int cap_road, int cap_fence, uint32_t lattice_cap, uint32_t mask) {
     return (size_t)B * ((size_t)sdply::kHeaderCap + (size_t)sdscene::rows_bound(cap_road, cap_fence, lattice_cap, mask) * sdply::kRowCap);
 }

@@ -111,12 +111,12 @@ __global__ __launch_bounds__(kThreads) void pil_v_kernel(const uint8_t* __restri
 
 hipError_t launch_pil_resample_u8(const uint8_t* src, int B, int src_h, int src_w, int pixel_stride, int channels, int reverse, uint8_t* dst,
                                   int dst_h, int dst_w, const Windows& wx, uint8_t* workspace, hipStream_t s) {
-    const size_t tx = tables_bytes(src_w, dst_w), ty = tables_bytes(src_h, dst_h);
-    const int32_t* xb = reinterpret_cast<const int32_t*>(workspace);
-    const int32_t* xk = reinterpret_cast<const int32_t*>(workspace + al16((size_t)dst_w * 2 * 4));
-    const int32_t* yb = reinterpret_cast<const int32_t*>(workspace + tx);
-    const int32_t* yk = reinterpret_cast<const int32_t*>(workspace + tx + al16((size_t)dst_h * 2 * 4));
-    uint8_t* mid = workspace + tx + ty;
+    const Layout l(B, src_h, src_w, dst_h, dst_w, channels);
+    const int32_t* xb = reinterpret_cast<const int32_t*>(workspace + l.x_bounds);
+    const int32_t* xk = reinterpret_cast<const int32_t*>(workspace + l.x_k);
+    const int32_t* yb = reinterpret_cast<const int32_t*>(workspace + l.y_bounds);
+    const int32_t* yk = reinterpret_cast<const int32_t*>(workspace + l.y_k);
+    uint8_t* mid = workspace + l.mid;
     const bool vertical = dst_h != src_h;
     const int tiles = (dst_w + kTileX - 1) / kTileX;
     int span_bytes = 0;       // the widest tile's span

@@ -7,7 +7,7 @@
 
 namespace sd {
 
-// workspace: sdpil::workspace_bytes(...) bytes, 16-byte aligned, laid out [x bounds][x k][y bounds][y k][intermediate]; the caller has
+// workspace: sdpil::Layout (pil_resample.hpp), 16-byte aligned; the caller has
 // copied the four tables to their places (`wx`: the host copy of the x windows, which sizes the tiles) in stream order before this.  Two launches (one when dst_h == src_h).
 hipError_t launch_pil_resample_u8(const uint8_t* src, int B, int src_h, int src_w, int pixel_stride, int channels, int reverse, uint8_t* dst,
                                   int dst_h, int dst_w, const sdpil::Windows& wx, uint8_t* workspace, hipStream_t s);

@@ -17,14 +17,20 @@
 // |vertex| <= 2^23 + 64 * 24 * 4096 < 2^24, pixel centre < 2^22, so |w| < 2^25 per axis; |d| <= 28 * 4096 < 2^17 per axis; hence
 // |w.d| and |w x d| < 2^43 and |w|^2 < 2^51 fit an int64, r^2 |d|^2 < 2^24 * 2^35 = 2^59, and (w x d)^2 < 2^86 takes the 128-bit product.
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#endif
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/semdepth.h"
 #include "ply_format.hpp"
 
+#if defined(__HIPCC__)
 #define SDTEXT_HD __host__ __device__ inline
+#else
+#define SDTEXT_HD inline
+#endif
 
 namespace sdtext {
 
@@ -391,5 +397,22 @@ SDTEXT_HD int sequence_items(const sd_rw_result& rec, const uint8_t* depth, int 
     seq_tail(out[3], n);
     return 4;
 }
+
+// ---- workspace of the device route (text_gpu.hip)
+// what text_layout_kernel leaves per frame for text_raster_kernel: the items, and per item its pixel box and the pen position of every character
+struct Extra {
+    int32_t box[4];                      // x0, y0, x1, y1, clipped to the frame; empty when x0 > x1 or y0 > y1
+    uint16_t pen[kMaxBytes + 2];         // pen[c] = the advances of the characters before c, pen[len] = the item's
+};
+struct FrameWs {
+    int32_t n, pad[3];
+    sd_text_item it[kMaxItems];
+    Extra ex[kMaxItems];
+};
+struct Layout : sdarena::Walker {
+    explicit Layout(int B) : frames(take((size_t)B * sizeof(FrameWs), 4)) {}
+    size_t frames;              // FrameWs [B], 4-byte aligned
+    size_t total = end();
+};
 
 }  // namespace sdtext

@@ -140,7 +140,7 @@ hipError_t launch_text_draw_rw(uint8_t* dst, int B, int h, int w, const sd_rw_re
     TextArgs a{};
     a.dst = dst;
     a.records = records;
-    a.ws = reinterpret_cast<TextFrameWs*>(workspace);
+    a.ws = reinterpret_cast<TextFrameWs*>(workspace + sdtext::Layout(B).frames);
     a.B = B;
     a.h = h;
     a.w = w;

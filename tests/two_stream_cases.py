@@ -14,6 +14,7 @@ import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CAPI = os.path.join(ROOT, "semantic_depth_amd", "csrc", "capi.cpp")
+ARENA = os.path.join(ROOT, "semantic_depth_amd", "csrc", "handle_arena.hpp")
 BENCH = os.path.join(ROOT, "bench.py")
 HEADER = os.path.join(ROOT, "include", "semdepth.h")
 
@@ -60,7 +61,7 @@ def pipelined_steps(eng, batches, cams, prm, approach, colours, side_priority):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the access table
-# Every region carve_workspace (capi.cpp) takes, at its granularity; o_misc by its parts (its carve line names them), the raw disparity pair as
+# Every region struct Arena (csrc/handle_arena.hpp) takes, at its granularity; o_misc by its parts (regions of their own there), the raw disparity pair as
 # a region of its own inside o_mono.  "who": the call families of semdepth.h's Streams paragraph.
 REGIONS = {
     "o_fcn": "FCN-8s activations",
@@ -114,9 +115,14 @@ ACCESS = {
 }
 
 
-def carved_regions(path=CAPI):
-    """the names of every `h->o_* = take(` line of carve_workspace"""
-    return re.findall(r"h->(o_\w+)\s*=\s*take\(", open(path).read())
+def carved_regions(path=ARENA):
+    """every region struct Arena takes (its `<field> = take(` declarations), under the name semdepth.h documents it by: o_<field>, and o_misc for
+    the five fields the header lists as its parts"""
+    src = open(path).read()
+    arena = src[src.index("struct Arena :"):]
+    misc = {"scalar", "zero", "f2f_counts", "f2f_planes", "sat"}
+    names = ["o_misc" if f in misc else "o_" + f for f in re.findall(r"\b(\w+) = take\(", arena[:arena.index("};")])]
+    return list(dict.fromkeys(names))
 
 
 # ------------------------------------------------------------------------------------------------------------------ choreography from source
